@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """bench.py — gang-fit decisions/sec + FIFO Filter latency on MI355X (BASELINE.json's metric, both halves).
 
-Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.
+Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line on rank 0.  Such a plain run measures the
+headline alone: a warm-up (W tickets + three short worker windows), then ONE window of exactly K steps in the
+`streamed_tickets` regime below (the faster regime in every run on record); no roofline, no CPU baseline, no extras.  `value`,
+`ms_per_step` and the other fields of the line mean what they mean in a --full run.  `--full` runs everything described here and writes it to bench_full.json.  `--dump-outputs DIR`
+writes what the timed path returned for its last step (result records and placements) as DIR/*.npy.
   * step      = one pass of the hot path over one batch: the independent gang-fit decision (SparkBinPack + tightlyPackExecutors
                 + driver-fit check) of every application of the headline workload's pending table (10 000 nodes x 1 000 pending
                 apps, SURVEY.md 8d distributions), inputs already resident in HBM.  The K steps of a window are served in TWO
@@ -19,7 +23,8 @@ Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line o
   * timing    = W warm-up steps, then windows of EXACTLY K steps, each bracketed by barrier + synchronize on both sides,
                 wall time = max over ranks of (rank's clock from the opening barrier to its own synchronize after step K).  A
                 K-step window is 0.1-0.2 ms at the driver's K = 20, where one scheduler hiccup moves the figure by tens of
-                percent, so `--windows` (default 9) such windows are timed and the MEDIAN is reported; every window is listed.
+                percent, so a --full run times `--windows` (default 9) such windows and reports the MEDIAN; every window is
+                listed.  A plain run times one window: choose K so that it lasts long enough.
   * N > 1     = the pending-app table shards across ranks (independent decisions: no data-path collective);
                 every rank holds the full node table; per-GPU work is fixed -> "weak" scaling.
   * roofline  = ONE definition of `frac` everywhere (headline, config 3, FIFO chain): three measured fractions —
@@ -301,6 +306,52 @@ def run_config3(ctx, torch, dev, stream, timed_graph, steps=100):
 # bench_full.json next to this file (GANGFIT_BENCH_FULL names another path).
 
 LINE_LIMIT = 4096
+DUMP_LIMIT_BYTES = 60_000_000  # --dump-outputs: all files together stay below 64 MB
+
+
+def headline_fields(args, world, n_apps, wall, batches_in_flight, used_worker, backend, dist):
+    """The headline's fields of the result dict, from the median (--full) or only (plain run) K-step window of wall seconds."""
+    return {
+        "metric": "gang-fit decisions/sec at 10k nodes x 1k pending apps (+ p99 Filter latency: fifo_filter)",
+        "value": world * n_apps * args.steps / wall,
+        "unit": "decisions/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": wall / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int64",
+        "data": "synthetic",
+        "config": {"workload": f"independent batch, tightly-pack, {args.nodes} nodes x {args.apps} pending apps per GPU, "
+                               "3-D (cpu milli, mem bytes, gpu) int64, SURVEY.md 8d/C2 distributions, seed 0x5EED0010",
+                   "nodes": args.nodes, "apps_per_gpu": args.apps, "algo": "tightly-pack", "mode": "independent",
+                   "batches_in_flight": batches_in_flight,
+                   "regime": "streamed_tickets (resident worker)" if used_worker else "launch_per_batch (one graph of K launches)",
+                   "sharding": "pending apps across ranks, node table replicated, no collective",
+                   # what the process group was: "nccl" = RCCL over xGMI with one rank per GPU (rccl_ranks = its world size);
+                   # "gloo" only in the one-GPU smoke run of the N > 1 control flow; "none" for N = 1
+                   "backend": backend, "rccl_ranks": (dist.get_world_size() if (dist is not None and backend == "nccl") else 0)},
+    }
+
+
+def dump_outputs(path, results, exec_nodes):
+    """--dump-outputs: what the timed path returned for its last step, as float64 .npy files under `path` — the four fields of
+    every application's result record (results_<field>.npy) and the placements (exec_nodes.npy: application a's executor
+    nodes are exec_nodes[o : o + exec_len[a]], o = the sum of k over the applications before a).  The inputs are seeded, so
+    two runs with the same arguments compare file for file.  Above DUMP_LIMIT_BYTES in all, every array keeps the same share
+    of its elements, drawn with a fixed seed."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {f"results_{f}": results[f] for f in results.dtype.names}
+    arrays["exec_nodes"] = exec_nodes
+    keep = min(1.0, DUMP_LIMIT_BYTES / (8 * sum(a.size for a in arrays.values())))
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).astype(np.float64)
+        if keep < 1.0:
+            a = a[np.sort(rng.choice(a.size, int(a.size * keep), replace=False))]
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def _r(x, digits=6):
@@ -331,7 +382,8 @@ def _trim_roofline(rf):
 
 def compact_line(full):
     """The ONE line of the contract from the full result dict: metric, value, unit, n_gpus, steps, warmup, ms_per_step, dtype,
-    config, a trimmed roofline (+ the FIFO chain's) and cpu_baseline.  Never longer than LINE_LIMIT characters."""
+    config and, from a --full run, a trimmed roofline (+ the FIFO chain's) and cpu_baseline.  Never longer than LINE_LIMIT
+    characters."""
     line = {k: _r(full.get(k)) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                                         "scaling", "vs_baseline", "dtype", "data")}
     cfg = dict(full.get("config") or {})
@@ -358,7 +410,8 @@ def compact_line(full):
         for k in ("filter_p50_ms", "filter_p99_ms", "filter_warm_p50_ms", "lone_wavefront_issue_frac", "kernel_ms_le_filter_p50"):
             c[k] = _r(fc.get(k))
         t["fifo_chain"] = c
-    line["roofline"] = t
+    if rf:  # (a plain run measures no roofline)
+        line["roofline"] = t
     cb = full.get("cpu_baseline")
     if cb:
         c = {k: _r(cb.get(k)) for k in ("value", "unit", "cores", "kind")}
@@ -371,9 +424,10 @@ def compact_line(full):
         if ac.get("value"):
             c["all_cores"] = {"value": _r(ac.get("value")), "cores": ac.get("cores")}
         line["cpu_baseline"] = c
-    line["full"] = full.get("full_results_file")
+    if "full_results_file" in full:
+        line["full"] = full["full_results_file"]
     text = json.dumps(line, separators=(",", ":"))
-    if len(text) > LINE_LIMIT and "fifo_chain" in line["roofline"]:
+    if len(text) > LINE_LIMIT and "fifo_chain" in line.get("roofline", {}):
         line["roofline"]["fifo_chain"].pop("fractions", None)
         text = json.dumps(line, separators=(",", ":"))
     if len(text) > LINE_LIMIT:  # cannot happen with the fields above; a guard, so that the driver always gets a line it can parse
@@ -442,7 +496,20 @@ def main():
     ap.add_argument("--headline-only", action="store_true",
                     help="nothing but the headline batch and its roofline (the profiling passes use it: every launch of "
                          "fit_independent_kernel in the trace is then a headline launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything this benchmark measures: both regimes of the headline over --windows windows, its roofline, "
+                         "the FIFO Filter, the CPU baselines and the extras (written to bench_full.json).  Without it the run "
+                         "times the headline alone and the options above except --gpus / --steps / --warmup / --worker-sets / "
+                         "--nodes / --apps have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned for its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and (args.headline_only or args.config3_only):
+        ap.error("--headline-only and --config3-only select parts of a --full run")
+    if not args.full and args.worker_sets == 0:
+        ap.error("--worker-sets 0 (launch path only) needs --full: a plain run times the resident worker")
     if args.headline_only:
         args.no_extras = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -561,6 +628,67 @@ def main():
         ctx.graph_destroy(g)
         return _median(walls_), _median(kerns_), walls_, "graph"
 
+    # The RESIDENT WORKER (gf_worker_*, gangfit_worker.inc) serves a window's K batches as K tickets (one doorbell): ONE launch,
+    # `worker_sets` groups of wavefronts taking the tickets in turn with several in flight, gone when the last one is done
+    # (gf_worker_stop), so the closing synchronize finds an idle device.  Every ticket writes its own result / placement arrays
+    # (eight sets in rotation).
+    NOUT = 8
+    w_res = [torch.zeros_like(d_res) for _ in range(NOUT)]
+    w_exec = [torch.zeros_like(d_exec) for _ in range(NOUT)]
+
+    def worker_tickets(n):
+        """n prepared tickets of the headline batch, a bounded stream: the worker leaves after the last one."""
+        return ctx.worker_batches([(len(apps), d_apps.data_ptr(), w_res[i % NOUT].data_ptr(), w_exec[i % NOUT].data_ptr(), total_k)
+                                   for i in range(n)], leave_after=True)
+
+    def worker_window(arr, on_idle=None):
+        """The tickets of arr between barrier + synchronize on both sides, the worker's launch and departure inside the window;
+        max-over-ranks wall s.  on_idle runs once the device is idle, before the closing barrier."""
+        barrier()
+        t0 = time.perf_counter()
+        ctx.worker_submit_prepared(TIGHT, arr)
+        ctx.worker_stop()
+        torch.cuda.synchronize()
+        wall_ = time.perf_counter() - t0
+        if on_idle is not None:
+            on_idle()
+        barrier()
+        if dist is not None:
+            t = torch.tensor([wall_], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            wall_ = float(t.item())
+        return wall_
+
+    def last_step_outputs(res, exec_nodes):
+        """Host copies of what a caller of the timed path receives for one step: its result records and placements."""
+        return (res.cpu().numpy().view(gangfit._native.RESULT_DTYPE),
+                exec_nodes.cpu().numpy().view(np.uint32)[:total_k])
+
+    if not args.full:
+        # ---- a plain run: the headline alone, ONE window of exactly K tickets through the resident worker: the regime behind
+        #      `value` in every --full run on record (README.md), 2.5x the launch path at K = 20.  Warm-up: W tickets, then the
+        #      three worker windows a --full run serves before it times the worker (of at most 2 000 tickets each, so that a
+        #      large K does not triple the run)
+        ctx.set_option("worker_sets", max(0, args.worker_sets))  # 0 = the library chooses at every launch
+        arr = worker_tickets(args.steps)
+        if args.warmup > 0:
+            worker_window(worker_tickets(args.warmup))
+        warm = worker_tickets(min(args.steps, 2000))
+        for _ in range(3):
+            worker_window(warm)
+        wall = worker_window(arr)
+        sets_used, _ = ctx.worker_geometry()
+        out = headline_fields(args, world, len(apps), wall, sets_used, True, backend, dist)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, *last_step_outputs(w_res[(args.steps - 1) % NOUT], w_exec[(args.steps - 1) % NOUT]))
+        ctx.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            print(compact_line(out), flush=True)
+        return
+
     if args.config3_only:
         c3 = run_config3(ctx, torch, dev, stream, timed_graph)
         ctx.close()
@@ -610,45 +738,28 @@ def main():
         wall, kern_ms = _median(walls), _median([b for _, b in ws])
     else:
         wall, kern_ms, walls = eager_wall, eager_kern_ms, eager_walls
-    # ---- the same K steps through the RESIDENT WORKER (gf_worker_*, gangfit_worker.inc): the batches of an independent-mode
-    #      window do not depend on each other, so nothing but the launch model makes them wait for each other.  A window posts
-    #      its K batches as K tickets (one doorbell), the worker — ONE launch, `worker_sets` groups of wavefronts taking the
-    #      tickets in turn — serves them with several in flight and leaves when the last one is done (gf_worker_stop), so the
-    #      closing synchronize finds an idle device.  The worker's launch and its departure are inside the window.  Every ticket
-    #      writes its own result / placement arrays (eight sets in rotation); they are compared with the launch path's.
+    # ---- the same K steps through the RESIDENT WORKER: the batches of an independent-mode window do not depend on each other,
+    #      so nothing but the launch model makes them wait for each other.  Its answers are compared with the launch path's.
     seq_wall, seq_walls = wall, walls
     worker_info = None
     used_worker = False
     wkern = []
     worker_sets_used = None
     if args.worker_sets != 0:
-        NOUT = 8
-        w_res = [torch.zeros_like(d_res) for _ in range(NOUT)]
-        w_exec = [torch.zeros_like(d_exec) for _ in range(NOUT)]
         try:
             ctx.set_option("worker_sets", max(0, args.worker_sets))  # 0 = the library chooses at every launch
-            arr = ctx.worker_batches([(len(apps), d_apps.data_ptr(), w_res[i % NOUT].data_ptr(), w_exec[i % NOUT].data_ptr(), total_k)
-                                      for i in range(args.steps)], leave_after=True)  # a window is a bounded stream: K tickets, then the worker leaves
+            arr = worker_tickets(args.steps)
 
-            def window_worker():
-                barrier()
-                t0 = time.perf_counter()
-                ctx.worker_submit_prepared(TIGHT, arr)  # exactly K tickets
-                ctx.worker_stop()                       # served, then the worker leaves the device
-                torch.cuda.synchronize()
-                wall_ = time.perf_counter() - t0
-                try:  # HIP events on the worker's own stream around its launch: device time of this window's K tickets
+            def kernel_time():  # HIP events on the worker's own stream around its launch: device time of this window's K tickets
+                try:
                     kms, ktk = ctx.worker_kernel_time()
                     if ktk == args.steps:
                         wkern.append(kms / ktk)
                 except Exception:
                     pass
-                barrier()
-                if dist is not None:
-                    t = torch.tensor([wall_], dtype=torch.float64, device=dev)
-                    dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                    wall_ = float(t.item())
-                return wall_
+
+            def window_worker():
+                return worker_window(arr, on_idle=kernel_time)
 
             wkern = []
             for _ in range(3):
@@ -673,7 +784,9 @@ def main():
                 wall, walls, used_worker = _median(wwalls), wwalls, True
         except Exception as e:
             worker_info = {"error": f"{type(e).__name__}: {e}"}
-    decisions_per_s = world * len(apps) * args.steps / wall
+    if args.dump_outputs and rank == 0:  # the last step of the regime behind `value`, before the legs below reuse d_res / d_exec
+        dump_outputs(args.dump_outputs, *(last_step_outputs(w_res[(args.steps - 1) % NOUT], w_exec[(args.steps - 1) % NOUT])
+                                          if used_worker else last_step_outputs(d_res, d_exec)))
 
     # ---- roofline of the kernel behind `value` (and, beside it, of the other regime's kernel)
     alg_bytes = wl.algorithmic_bytes(len(s.exec_order), w.k)  # full scan of the executor order per decision
@@ -690,8 +803,7 @@ def main():
             # application, a ticket then takes twenty times as long, and a long stream of such tickets lets the leader idle out
             # between two postings (round 6's K = 2 000 profile held 31 relaunches of 64 tickets each from this one window)
             n_cnt = min(args.steps, 20)
-            arr_cnt = ctx.worker_batches([(len(apps), d_apps.data_ptr(), w_res[i % NOUT].data_ptr(), w_exec[i % NOUT].data_ptr(), total_k)
-                                          for i in range(n_cnt)], leave_after=True)
+            arr_cnt = worker_tickets(n_cnt)
             ctx.scan_stats(enable=True, reset=True)
             ctx.worker_submit_prepared(TIGHT, arr_cnt)
             ctx.worker_stop()
@@ -799,28 +911,8 @@ def main():
                         "bandwidth roof; a batch is ~1 000 wavefronts on 1 024 SIMDs, each a short chain of dependent L2 / HBM round "
                         "trips (DESIGN.md 4.1).  frac_of_launch_floor = empty-kernel launch / the launch path's kernel.")
 
-    out = {
-        "metric": "gang-fit decisions/sec at 10k nodes x 1k pending apps (+ p99 Filter latency: fifo_filter)",
-        "value": decisions_per_s,
-        "unit": "decisions/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": wall / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "int64",
-        "data": "synthetic",
-        "config": {"workload": f"independent batch, tightly-pack, {args.nodes} nodes x {args.apps} pending apps per GPU, "
-                               "3-D (cpu milli, mem bytes, gpu) int64, SURVEY.md 8d/C2 distributions, seed 0x5EED0010",
-                   "nodes": args.nodes, "apps_per_gpu": args.apps, "algo": "tightly-pack", "mode": "independent",
-                   "batches_in_flight": worker_sets_used if used_worker else 1,
-                   "regime": "streamed_tickets (resident worker)" if used_worker else "launch_per_batch (one graph of K launches)",
-                   "sharding": "pending apps across ranks, node table replicated, no collective",
-                   # what the process group was: "nccl" = RCCL over xGMI with one rank per GPU (rccl_ranks = its world size);
-                   # "gloo" only in the one-GPU smoke run of the N > 1 control flow; "none" for N = 1
-                   "backend": backend, "rccl_ranks": (dist.get_world_size() if (dist is not None and backend == "nccl") else 0)},
+    out = headline_fields(args, world, len(apps), wall, worker_sets_used if used_worker else 1, used_worker, backend, dist)
+    out.update({
         "timing": {"windows": len(walls), "steps_per_window": args.steps, "statistic": "median of the windows (max over ranks each)",
                    "submission": ("resident worker: K tickets per window, one doorbell; the worker's launch and its departure are "
                                   "inside the window (gf_worker_submit_dev + gf_worker_stop)" if used_worker else
@@ -836,7 +928,7 @@ def main():
                    "eager_ms_per_step": eager_wall / args.steps * 1e3, "eager_kernel_ms": eager_kern_ms,
                    "eager_note": "the same K steps submitted by K gf_fit_batch_dev calls from Python (host-bound)"},
         "roofline": roofline,
-    }
+    })
 
     def fifo_latency(c, algo, queue, calls, warm=5):
         """One blocking gf_fit_batch(FIFO_CHAIN) per call, a different head each time.  The interpreter's cyclic garbage

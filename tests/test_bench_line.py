@@ -4,6 +4,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,3 +85,44 @@ def test_self_launch_command(monkeypatch):
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1"
     assert cmd[-4:] == ["--gpus", "4", "--steps", "20"] and cmd[-5].endswith("bench.py")
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
+
+
+def test_plain_run_line_has_no_measured_legs():
+    """A plain run's dict (the headline fields only) makes a complete line without roofline, cpu_baseline or full file."""
+    full = _canned()
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                                  "vs_baseline", "dtype", "data", "config")}
+    line = json.loads(bench.compact_line(plain))
+    assert line["value"] == pytest.approx(full["value"], rel=1e-5)
+    assert line["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)
+    assert not {"roofline", "cpu_baseline", "full"} & set(line)
+
+
+def test_dump_outputs_files_and_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 file per result field + the placements, exact for node ids; above the size limit a fixed
+    sample of every array, the same from run to run."""
+    from gangfit import _native as N
+
+    rng = np.random.default_rng(3)
+    res = np.zeros(50, dtype=N.RESULT_DTYPE)
+    for f in res.dtype.names:
+        res[f] = rng.integers(0, 2**32 - 1, size=50, dtype=np.uint32).astype(res.dtype[f])
+    nodes = rng.integers(0, 2**32 - 1, size=400, dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path / "all"), res, nodes)
+    names = sorted(p.name for p in (tmp_path / "all").iterdir())
+    assert names == sorted([f"results_{f}.npy" for f in res.dtype.names] + ["exec_nodes.npy"])
+    for f in res.dtype.names:
+        a = np.load(tmp_path / "all" / f"results_{f}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, res[f].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "all" / "exec_nodes.npy"), nodes.astype(np.float64))
+
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8 * 120)  # 600 elements in all -> a fifth of each array
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), res, nodes)
+    total = 0
+    for p in (tmp_path / "s1").iterdir():
+        a, b = np.load(p), np.load(tmp_path / "s2" / p.name)
+        assert np.array_equal(a, b)
+        total += a.size
+    assert total <= 120
+    assert set(np.load(tmp_path / "s1" / "exec_nodes.npy")) <= set(nodes.astype(np.float64))

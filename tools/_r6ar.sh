@@ -6,7 +6,7 @@ timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_worker.py 
 for lib in "" noahead "" noahead; do
   if [ -n "$lib" ]; then export GANGFIT_LIB=$PWD/k8s-spark-scheduler_amd/variants/libgangfit_$lib.so; else unset GANGFIT_LIB; fi
   timeout 300 python tools/probe_variants.py ind 2>&1 | grep -v amdgpu.ids >> $OUT/variants.txt
-  timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']['regimes']

@@ -29,9 +29,9 @@ for w in $WHAT; do
       ;;
     bench)
       t0=$(date +%s.%N)
-      GANGFIT_BENCH_FULL="$OUT/bench_full_steps20.json" timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"; echo "bench20 rc=$? wall=$(python -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s"
+      GANGFIT_BENCH_FULL="$OUT/bench_full_steps20.json" timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_steps20.json" 2> "$OUT/bench_steps20.err"; echo "bench20 rc=$? wall=$(python -c "import time,sys; print(round(time.time()-float(sys.argv[1]),1))" $t0) s"
       tail -1 "$OUT/bench_steps20.json" | wc -c; tail -1 "$OUT/bench_steps20.json"
-      GANGFIT_BENCH_FULL="$OUT/bench_full_default_headline.json" timeout 900 python bench.py --no-extras --no-cpu-baseline > "$OUT/bench_default_headline.json" 2> "$OUT/bench_default.err"; echo "bench rc=$?"
+      GANGFIT_BENCH_FULL="$OUT/bench_full_default_headline.json" timeout 900 python bench.py --full --no-extras --no-cpu-baseline > "$OUT/bench_default_headline.json" 2> "$OUT/bench_default.err"; echo "bench rc=$?"
       tail -1 "$OUT/bench_default_headline.json" | cut -c1-600
       ;;
     two)

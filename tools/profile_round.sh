@@ -46,16 +46,16 @@ for g in $GROUPS_; do
   case $g in
     headline)
       BUSY_PASS=1
-      run_group hl20 300 python $ROOT/bench.py --headline-only --steps 20 --warmup 5 ${BENCH_ARGS:-}
-      run_group hl 300 python $ROOT/bench.py --headline-only ${BENCH_ARGS:-}
+      run_group hl20 300 python $ROOT/bench.py --full --headline-only --steps 20 --warmup 5 ${BENCH_ARGS:-}
+      run_group hl 300 python $ROOT/bench.py --full --headline-only ${BENCH_ARGS:-}
       BUSY_PASS=
       ;;
     chain)
-      run_group chain 300 python $ROOT/bench.py --steps 20 --warmup 5 --windows 3 --filter-calls 30 --no-cpu-baseline --no-extras --fifo-protocols cold --worker-sets 0
+      run_group chain 300 python $ROOT/bench.py --full --steps 20 --warmup 5 --windows 3 --filter-calls 30 --no-cpu-baseline --no-extras --fifo-protocols cold --worker-sets 0
       ;;
     config3)
       BUSY_PASS=1
-      run_group c3 300 python $ROOT/bench.py --config3-only
+      run_group c3 300 python $ROOT/bench.py --full --config3-only
       BUSY_PASS=
       ;;
     zoned)
@@ -71,7 +71,7 @@ for g in $GROUPS_; do
       done
       ;;
     full)
-      FULL="python $ROOT/bench.py --steps 50 --warmup 5 --windows 3 --filter-calls 30 --no-cpu-baseline --worker-sets 0 ${BENCH_ARGS:-}"
+      FULL="python $ROOT/bench.py --full --steps 50 --warmup 5 --windows 3 --filter-calls 30 --no-cpu-baseline --worker-sets 0 ${BENCH_ARGS:-}"
       timeout 500 rocprofv3 --kernel-trace --stats -T -f csv -d "$OUT/stats" -o stats -- $FULL > "$OUT/stats.log" 2>&1
       timeout 500 rocprofv3 --kernel-trace --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_IDX_ACTIVE SQ_WAVES SQ_WAVE_CYCLES -T -f csv -d "$OUT/pmc_lds" -o pmc -- $FULL > "$OUT/pmc_lds.log" 2>&1
       ;;

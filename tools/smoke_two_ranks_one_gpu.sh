@@ -6,7 +6,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT"
 GANGFIT_BENCH_FULL=${GANGFIT_BENCH_FULL:-/tmp/bench_full_two_ranks.json} \
-  timeout 500 python bench.py --gpus 2 --steps 20 --warmup 3 --windows 3 --filter-calls 5 --no-cpu-baseline > /tmp/two_ranks.out 2> /tmp/two_ranks.err
+  timeout 500 python bench.py --full --gpus 2 --steps 20 --warmup 3 --windows 3 --filter-calls 5 --no-cpu-baseline > /tmp/two_ranks.out 2> /tmp/two_ranks.err
 rc=$?
 echo "rc=$rc"
 tail -1 /tmp/two_ranks.out | python -c "import sys, json; l = json.loads(sys.stdin.read()); print('parsed: n_gpus', l['n_gpus'], 'backend', l['config']['backend'], 'rccl_ranks', l['config']['rccl_ranks'], 'value', l['value'])" || tail -5 /tmp/two_ranks.err

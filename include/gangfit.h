@@ -523,6 +523,9 @@ int gf_launch_floor(gf_ctx *ctx, void *stream, uint32_t iters, float *us_per_lau
  * L1 but through its L2: an array whose CONTENT is replaced while the worker is resident must be replaced by a stream
  * operation that completed before the submit (a finished copy or kernel), as for any kernel launch.  GF_WORKER_HOST_OUTPUTS:
  * d_results / d_exec_nodes are device addresses of PINNED HOST memory (no cache write-back before the completion word).
+ * Without it (device-resident outputs), d_exec_nodes[exec_off .. exec_off + k) of a record whose result has has_capacity == 0
+ * is UNSPECIFIED: tightly-pack writes its placements straight into the caller's array while it searches, and a gang that does
+ * not fit may leave some of them there.
  * GF_WORKER_LEAVE_AFTER on the LAST batch of a submit: the caller has nothing more to post — a worker that this submit launches
  * (none was resident) serves what is posted and leaves the device by itself, without waiting to be told (gf_worker_stop /
  * gf_worker_wait behind it return as soon as the last answer is out; a bounded stream — K batches, then something else — saves the

@@ -1,6 +1,5 @@
 // gangfit_api_worker.cpp — the resident worker of the independent batch (gf_worker_*; device side: gangfit_worker.inc).
 #include "gangfit_ctx.h"
-#include <cstdio>
 
 using namespace gfapi;
 
@@ -316,22 +315,7 @@ int gf_worker_submit_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_batches, const gf
                 need_launch = false;
                 if (const int rc = worker_launch(ctx, algo, first); rc != GF_OK) return rc;
             }
-#ifdef GF_WORKER_HOST_DEBUG  // where the posting loop's time goes, and how many of the tickets in flight are done when the oldest is
-            const auto td0 = std::chrono::steady_clock::now();
-#endif
             if (const int rc = worker_wait_ticket(ctx, w.posted - kRing); rc != GF_OK) return rc;
-#ifdef GF_WORKER_HOST_DEBUG
-            {
-                static double wait_ns = 0;
-                static uint64_t n_wait = 0, done_behind = 0;
-                wait_ns += std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - td0).count();
-                for (uint64_t q = w.posted - kRing + 1; q < w.posted; ++q) done_behind += host_load(&w.h->done[q % kRing]) == q + 1 ? 1 : 0;
-                if ((++n_wait % 1900) == 0)
-                    std::fprintf(stderr, "[worker host] %llu waits: %.0f ns each, %.1f of the %u younger tickets already complete, relayed %llu of %llu posted\n",
-                                 (unsigned long long)n_wait, wait_ns / n_wait, (double)done_behind / n_wait, kRing - 1,
-                                 (unsigned long long)host_load(&w.h->consumed), (unsigned long long)w.posted);
-            }
-#endif
             worker_advance(w);
         }
         const gf_worker_batch& b = batches[i];

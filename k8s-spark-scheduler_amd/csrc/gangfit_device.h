@@ -137,13 +137,10 @@ hipError_t launch_fit_independent(gf_algo algo, const NodeTable& table, const Sp
                                   uint32_t* d_feasible_sync = nullptr);
 
 // ---- the resident worker of the independent batch (gangfit_worker.inc; host side: gangfit_api_worker.cpp)
-#ifndef GF_WORKER_RING
-#define GF_WORKER_RING 64  // (a power of two; every translation unit must see the same value)
-#endif
-constexpr uint32_t kWorkerRing = GF_WORKER_RING;
+constexpr uint32_t kWorkerRing = 64;  // tickets in flight at most (a power of two: the host waits for ticket t - 64 before it posts t)
 constexpr uint32_t kWorkerInline = 16;  // tickets a launch of the worker carries in its arguments (at most one per set)
 constexpr int kWorkerWaves = 16;             // wavefronts per workgroup of the worker kernel (one workgroup fills a CU)
-constexpr uint32_t kWorkerCountStride = 64;  // words between two tickets' counters: one 256-byte line (one memory channel) each  // tickets in flight at most (host side waits for ticket t - kWorkerRing before it posts t)
+constexpr uint32_t kWorkerCountStride = 64;  // words between two tickets' counters: one 256-byte line (one memory channel) each
 
 // A ticket: six self-validating 8-byte words.  word[0] = ticket number + 1; words 1..5 carry worker_tag(ticket) in their
 // top sixteen bits (device and pinned-host addresses, the placement count and n_apps | flags << 32 all stay below 2^48): a

@@ -52,27 +52,15 @@
 //   * shape ids (rows of the matrix, 64 per role) no longer need chunk-index rows in LDS: a 100 000-node table with three
 //     zones, whose masks alone fill LDS, runs this path for every shape.
 
-#ifndef GF_MINFRAG_DECIDE_PROFILE
-#define GF_MINFRAG_DECIDE_PROFILE 0  // 1: a profiled run (gf_scan_stats) reports the decide phase of wavefront 0 split four ways —
-#endif                               //    driver search | tables + value domain | level plan | position walks — in place of phases 2..5
-// Experiment switch: the block-cooperative fallback (shapes with a capacity of kMfBins or more somewhere) as a real call
-// (-DGF_MF_BLOCK_DECIDE_INLINE='__attribute__((noinline))') instead of inlined into the chain loop.
-#ifndef GF_MF_BLOCK_DECIDE_INLINE
-#define GF_MF_BLOCK_DECIDE_INLINE __forceinline__
-#endif
-#ifndef GF_MF_HELPERS
-#define GF_MF_HELPERS 4  // wavefronts that share the matrix / histogram patch of a commit (touched slot i to helper i mod n);
-                         // round 4 measured 8 and 12: 6.03 / 5.99 ms against 6.05 (single-AZ 7.92 / 7.86 against 7.95) — inside the noise
-#endif
-#ifndef GF_MINFRAG_WAVES
-#define GF_MINFRAG_WAVES 16
-#endif
+// Wavefronts that share the matrix / histogram patch of a commit (touched slot i to helper i mod n); round 4 measured 8 and 12:
+// 6.03 / 5.99 ms against 6.05 (single-AZ 7.92 / 7.86 against 7.95) — inside the noise.
+constexpr uint32_t kMfHelpers = 4;
 // Wavefronts of the workgroup (template parameter NWV of the kernel and of the block-cooperative passes): every wavefront repeats
 // the uniform parts of the decision, and with w wavefronts per SIMD each of those instructions costs 4w cycles.  The launch
 // bound is also the register budget: sixteen wavefronts = 128 VGPRs per lane (this kernel then spills 22-27 of them to scratch),
 // eight = 256 (no spill).  Eight are enough for up to three candidate views + four patch helpers + the emitter
 // (fifo_minfrag_waves); more views take sixteen.
-constexpr uint32_t kMfNWmax = GF_MINFRAG_WAVES;
+constexpr uint32_t kMfNWmax = 16;
 static_assert(kMfNWmax == 8 || kMfNWmax == 16, "minimal-fragmentation chain: 8 or 16 wavefronts");
 template <int NWV>
 __device__ __forceinline__ constexpr uint64_t mf_own_pattern() {
@@ -289,7 +277,7 @@ __device__ __forceinline__ MfStats mf_pass(const ZView& Z, uint32_t n_x, const N
 // on success R holds the run list (ds_out, nruns_out).
 typedef __attribute__((address_space(3))) uint32_t lds_u32w;
 template <int NWV>
-__device__ GF_MF_BLOCK_DECIDE_INLINE bool mf_block_decide(const ZView& Z, uint32_t n_d, uint32_t n_x, uint32_t n_chunks, const NAppR& p,
+__device__ __forceinline__ bool mf_block_decide(const ZView& Z, uint32_t n_d, uint32_t n_x, uint32_t n_chunks, const NAppR& p,
                                                 const RunList& R, lds_u32w* chunk_cnt, lds_u32w* chunk_pre, lds_u64* chunk_msk,
                                                 lds_mfshared* sh, uint32_t cand,
                                                 uint32_t wave, int lane, uint32_t tid, uint32_t& xpar, uint32_t& ds_out,
@@ -670,15 +658,7 @@ __device__ __forceinline__ uint32_t mf_first_from(const ZView& Z, uint32_t n_x, 
 __device__ __forceinline__ bool mf_hist_decide(const ZView& Z, const int32_t* hrow, int32_t* frow, uint32_t n_d, uint32_t n_x,
                                                const NAppR& p, const RunList& R, lds_mfshared* sh, uint32_t cand, int lane,
                                                uint32_t& ds_out, uint32_t& nruns_out, unsigned long long& visited,
-                                               unsigned long long* prof /* 4 phase counters of a profiled run, else nullptr */,
                                                bool wait_patch) {
-    unsigned long long tq = prof ? __builtin_readcyclecounter() : 0ull;
-#define GF_DPHASE(i)                                                 \
-    if (prof) {                                                      \
-        const unsigned long long now = __builtin_readcyclecounter(); \
-        prof[i] += now - tq;                                         \
-        tq = now;                                                    \
-    }
     const int32_t K = p.k;
     nruns_out = 0;
     ds_out = 0;
@@ -688,7 +668,6 @@ __device__ __forceinline__ bool mf_hist_decide(const ZView& Z, const int32_t* hr
     uint32_t ds = (uint32_t)p0;
     ds_out = ds;
     if (K == 0) return true;
-    GF_DPHASE(0)
     // the previous application committed into this view and the helper wavefront is still patching its tables: the driver
     // search above needed none of them, everything below does
     if (wait_patch) {
@@ -722,7 +701,6 @@ __device__ __forceinline__ bool mf_hist_decide(const ZView& Z, const int32_t* hr
             if (maxcap < K && mfb_sum_below(b, lane, kMfBins) < K) return false;  // cannot happen
         }
     }
-    GF_DPHASE(1)
     // ---- minimalFragmentation (:59-91), in the value domain first: which levels, how many nodes of each, which last node
     bool single;
     int32_t cmin = K;
@@ -740,9 +718,7 @@ __device__ __forceinline__ bool mf_hist_decide(const ZView& Z, const int32_t* hr
         uint32_t from = (uint32_t)mfb_at(fp, cmin);
         if (cap1 == cmin && ds < from) from = ds;
         if (from >= n_x) from = 0;  // a table entry that was never set: cannot happen for a counted capacity
-        GF_DPHASE(2)
         const uint32_t pos = mf_first_from(Z, n_x, ds, cap1, lane, cmin, from, visited);
-        GF_DPHASE(3)
         if (pos == GF_NO_NODE) return false;  // cannot happen; a logic error would show up as a parity failure
         if (lane == 0) {
             if (pos != ds && !(cap0 == cmin && ds < pos)) frow[cmin] = (int32_t)pos;  // see the tightening below
@@ -772,7 +748,6 @@ __device__ __forceinline__ bool mf_hist_decide(const ZView& Z, const int32_t* hr
     int32_t Rem = K;
     int32_t m = mfb_max_below(b, lane, K);
     uint32_t base_run = 0;
-    GF_DPHASE(2)
     for (;;) {
         if (m <= 0) return false;  // unreachable when the capacity sum sufficed
         const uint32_t count = (uint32_t)mfb_at(b, m);
@@ -813,9 +788,7 @@ __device__ __forceinline__ bool mf_hist_decide(const ZView& Z, const int32_t* hr
         }
         m = m2;
     }
-    GF_DPHASE(3)
     return true;
-#undef GF_DPHASE
 }
 
 // RES: the whole table is in LDS (lds_slots >= n_slots, decided by the launcher): the global-tail branch of every slot access
@@ -911,7 +884,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
     __syncthreads();
     // the helper wavefronts of the histogram path: up to four that evaluate no candidate view (none with 16 candidates)
     const uint32_t hw = (hist != nullptr && capmat != nullptr && n_cand < NW) ? n_cand : NW;
-    const uint32_t n_help = hw < NW ? ((NW - hw) < (uint32_t)GF_MF_HELPERS ? (NW - hw) : (uint32_t)GF_MF_HELPERS) : 0u;
+    const uint32_t n_help = hw < NW ? ((NW - hw) < kMfHelpers ? (NW - hw) : kMfHelpers) : 0u;
     // ... and one more that writes the winner's result and expands its runs to ExecutorNodes behind the end-of-application
     // barrier: global stores are acknowledged ~2 us after they are issued and memory operations of a wavefront return in
     // order, so a winner that stored its own placement would find its next loads (histograms, matrix rows) queued behind
@@ -991,7 +964,6 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
     uint32_t a = 0;
     unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};
     unsigned long long xvis = 0;  // slots the histogram path's walks looked at (this wavefront)
-    unsigned long long dph[4] = {0, 0, 0, 0};  // -DGF_MINFRAG_DECIDE_PROFILE=1: driver search | tables + value domain | plan | walk
     unsigned long long tph = stats != nullptr ? __builtin_readcyclecounter() : 0ull;
     const unsigned long long t0_cycles = tph;
     const unsigned long long t0_real = wall_clock64();
@@ -1147,7 +1119,6 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
                 uint32_t ds = 0, nruns = 0;
                 int32_t* hrow = hist + ((size_t)c * n_shapes + app.shape_x) * kMfBins;
                 const bool feasible = mf_hist_decide(ZV, hrow, hrow + hist_words, T.n_d, T.n_x, app, R, sh, c, lane, ds, nruns, xvis,
-                                                     (stats != nullptr && wave == 0 && GF_MINFRAG_DECIDE_PROFILE) ? dph : nullptr,
                                                      sh->pl_seq == a && sh->pl_view == c);
                 GF_MPHASE(1)
                 if (feasible && nruns > kZRunMax && ewv < NW)  // spilled runs (global stores): the emitting helper reads them
@@ -1351,8 +1322,6 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
         stats->fifo_shader_cycles = __builtin_readcyclecounter() - t0_cycles;
         stats->fifo_realtime_ticks = wall_clock64() - t0_real;
         for (int i = 0; i < 6; ++i) stats->fifo_phase_cycles[i] = ph[i];
-        if (GF_MINFRAG_DECIDE_PROFILE)  // the decide phase split four ways, in place of the last four phases
-            for (int i = 0; i < 4; ++i) stats->fifo_phase_cycles[2 + i] = dph[i];
     }
     if (lane == 0 && stats != nullptr && xvis != 0) atomicAdd(&stats->exec_slots_visited, xvis);
     for (uint32_t r = a + tid; r < n_apps; r += BLOCK) {

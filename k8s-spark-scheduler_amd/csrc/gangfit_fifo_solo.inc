@@ -121,17 +121,7 @@ struct NarrowBlockView {
     }
 };
 
-#ifndef GF_SOLO_WAVES
-#define GF_SOLO_WAVES 16  // wavefronts of the workgroup (launch bound = VGPR budget: 16 -> 128 per lane, 8 -> 256)
-#endif
-#ifndef GF_SOLO_EAGER_TAIL
-#define GF_SOLO_EAGER_TAIL 2  // tables beyond the LDS front re-test the application's two shapes behind a commit: 2 (default) behind commits
-                              // to chunks of the global tail only — the LDS front is lazy like a resident table —, 1 behind every commit
-                              // (rounds 4-5a: 2.33 against 2.08 ms per config-5 chain, profiles/r5ac_c5_eager_tail.txt), 0 never
-#endif
-#ifndef GF_SOLO_EXP
-#define GF_SOLO_EXP 0  // timing experiments only (tools/micro/solo_experiments.sh): 1 no result store, 2 no run-head store, 4 no commit
-#endif
+constexpr int kSoloWaves = 16;  // wavefronts of the workgroup (launch bound = VGPR budget: 16 -> 128 per lane, 8 -> 256)
 
 // "This value is needed HERE": keeps the compiler from sinking an LDS load below a branch that does not always use it (it
 // would then pay one LDS round trip per use instead of one for the whole group of loads issued together).
@@ -414,12 +404,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
     const int wave = (int)__builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned long long t0_cycles = __builtin_readcyclecounter();
     const unsigned long long t0_real = wall_clock64();
-#ifdef GF_SOLO_PROLOGUE_MARKS  // experiment build: where the prologue's cycles go (thread 0; reported in place of the rare endings' cycles)
-    unsigned long long pmark[4] = {0, 0, 0, 0};
-#define GF_PMARK(i) pmark[i] = __builtin_readcyclecounter() - t0_cycles;
-#else
-#define GF_PMARK(i)
-#endif
     const uint32_t nc = T.n_chunks;
     const uint32_t nw = (nc + 63u) / 64u;  // 64-bit words per shape in the shape index = groups of 64 chunks
     const uint32_t nwp = nw < 4u ? 4u : nw;  // row stride of the index: the chain reads the first four words as two b128
@@ -532,7 +516,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
         sh->ckpt_cmd = kCkptDone;
     }
     __syncthreads();
-    GF_PMARK(0)  // records prepared (fused), table front / maxima / masks in LDS
     for (uint32_t v = tid; v < 2 * n_apps; v += BLOCK) {
         const uint32_t role = v & 1u;  // 0 = executor request, 1 = driver request
         const NApp* rec = napps + (v >> 1);
@@ -611,12 +594,10 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
         reinterpret_cast<uint32_t*>(&rec->pad)[role] = id;  // pad = {shape_x, shape_d}
     }
     const uint32_t n_shapes = (uint32_t)scount[0];
-    GF_PMARK(1)  // shape ids assigned
     // dominators: when a chunk holds no slot for shape s any more it holds none for a shape of the same role that asks for at
     // least as much in every dimension — their index bits are cleared (and, on a rollback, set) together with s's own, so a
     // filled chunk is discovered once per family of shapes instead of once per shape (a stale visit costs ~600 cycles).  The
     // masks are built below, lane = shape, next to the index (`up`); wavefront 0 leaves them in sdom for the chain.
-    GF_PMARK(2)  // dominator masks
     {
         // bit c of shape s <=> some candidate slot of chunk c fits s.  Lane = shape id for the shape table (read from LDS once,
         // handed out with v_readlane: a shape per LDS round trip made this loop 4 k cycles per chunk, and a 100 000-node table has
@@ -722,7 +703,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
     }
     __threadfence_block();
     __syncthreads();
-    GF_PMARK(3)  // shape index built (all wavefronts)
     {
         const uint32_t n0 = n_apps < (uint32_t)kFusedStage ? n_apps : (uint32_t)kFusedStage;
         const u32x4* src = reinterpret_cast<const u32x4*>(napps);
@@ -951,10 +931,12 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                     } else if (lane_bit(sm)) {
                         GF_SOLO_STORE(c, a0, a1, a2)
                     }
-                    if (GF_SOLO_EAGER_TAIL && !RESIDENT && (GF_SOLO_EAGER_TAIL == 1 || c >= lds_chunks)) {
+                    if (!RESIDENT && c >= lds_chunks) {
                         // Tables with a global tail keep the EAGER index: a stale visit out there is a real call and two dependent
                         // memory round trips (cold after a snapshot rebuild), not one LDS read — the first chain on a just-installed
-                        // 100 000-node snapshot was 0.23 ms slower with the lazy index although the warm one was faster.
+                        // 100 000-node snapshot was 0.23 ms slower with the lazy index although the warm one was faster.  The LDS
+                        // front stays lazy like a resident table (re-testing behind every commit, rounds 4-5a: 2.33 against 2.08 ms
+                        // per config-5 chain, profiles/r5ac_c5_eager_tail.txt).
                         const uint64_t cxm = uniform64(lxm[c]), cdm = uniform64(ldm[c]);
                         const uint64_t bx = fit_mask(a0, a1, a2, app.exe0, app.exe1, app.exe2, cxm);
                         const uint64_t bd = fit_mask(a0, a1, a2, app.drv0, app.drv1, app.drv2, cdm);
@@ -1020,7 +1002,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                             const int32_t t = room <= 0 ? 0 : (room < c0 ? room : c0);
                             // one run head per node (expand_translate_kernel fills the run); lanes without one store to a spare word
                             // instead of being masked out
-                            if (!(GF_SOLO_EXP & 2)) *(t > 0 ? heads + start : dummy_word) = j;
+                            *(t > 0 ? heads + start : dummy_word) = j;
                             hm = __builtin_amdgcn_sicmp(t, 0, 38);  // lanes with t > 0
                             taken += tot;
                         } else {
@@ -1036,7 +1018,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                         // from the list after the scan cost two dependent LDS round trips and a scalar hand-over per chunk.
                         const bool fin = taken >= K;
                         if (GF_OFTEN(hm != 0)) {
-                            if (!(GF_SOLO_EXP & 4) && !last) commit_chunk(c, a0, a1, a2, hm);
+                            if (!last) commit_chunk(c, a0, a1, a2, hm);
                             if (!fin) {  // (every lane writes the same two words)
                                 hchunk[nhit] = (int32_t)c;
                                 hmask[nhit] = hm;
@@ -1050,18 +1032,16 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                 // ---- K == 0 or every executor placed by the lazy scan
                 // (every lane stores the same sixteen bytes to the same address: one write, and no execution-mask save / restore
                 //  around it — with `lane == 0` the store and its mask hand-overs cost the chain 5 %)
-                if (!(GF_SOLO_EXP & 1)) {
-                    gf_result r;
-                    r.has_capacity = 1;
-                    r.driver_node = p0;  // SLOT id; expand_translate_kernel maps it to the node index
-                    r.exec_len = (uint32_t)K;
-                    r.evaluated = (ALGO == GF_ALGO_TIGHTLY_PACK && K > 0) ? kEvalHeads : kEvalDone;
-                    results[a] = r;
-                }
+                gf_result r;
+                r.has_capacity = 1;
+                r.driver_node = p0;  // SLOT id; expand_translate_kernel maps it to the node index
+                r.exec_len = (uint32_t)K;
+                r.evaluated = (ALGO == GF_ALGO_TIGHTLY_PACK && K > 0) ? kEvalHeads : kEvalDone;
+                results[a] = r;
                 // ---- the driver sits in a chunk without executors (sparkpods.go:139-146: the driver request only if no executor
                 //      landed on the driver's node); nothing is subtracted behind the driver being filtered (resource.go:321-328)
-                if (!(GF_SOLO_EXP & 4) && !last && !pc_done) {
-                    if (RESIDENT || (GF_SOLO_EAGER_TAIL != 1 && pc < lds_chunks)) {
+                if (!last && !pc_done) {
+                    if (RESIDENT || pc < lds_chunks) {
                         // one LDS atomic per dimension, every lane on its own slot (all but the driver's add zero): nothing of the
                         // driver's chunk has to stay in registers across the executor scan, nothing is masked out
                         lds_i32* p_ = lblk + (size_t)pc * kBlkDwords + lane;
@@ -1124,9 +1104,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                 //  and to the chain's end — what follows until fifo_shader_cycles is the epilogue)
                 rare_cyc[0] = t_chain_begin - t0_cycles;
                 rare_n[0] = __builtin_readcyclecounter() - t0_cycles;
-#ifdef GF_SOLO_PROLOGUE_MARKS
-                for (int i = 0; i < 4; ++i) rare_cyc[1 + i] = pmark[i];
-#endif
                 for (int i = 0; i < 5; ++i) {
                     stats->fifo_rare_count[i] = rare_n[i];
                     stats->fifo_rare_cycles[i] = rare_cyc[i];

@@ -486,6 +486,9 @@ __device__ __forceinline__ double wave_serial_sum_runs(double carry, double v, u
 // roundings of the chooser's own interval arithmetic.  A negative term (an available quantity above the schedulable one)
 // makes *err infinite.  chooseBestResult only COMPARES the averages: zoned_choose_bounded decides from (value, bound) when
 // the intervals separate and asks for the slice-order sums (SERIAL = true, one more barrier) when they do not.
+// prof (loads | arithmetic | sum, in cycles): no caller passes it any more.  Taking it out changes the code generated for the zone
+// kernels — the function is optimised on its own, loop and tests of prof included, before it is inlined — and wants a measurement
+// of its own.
 template <bool RESERVE_EXECS, bool SERIAL = true, class View>
 __device__ __forceinline__ double wave_runs_avg_max(const View& V, const int64_t unit[3], const int64_t* __restrict__ sched,
                                                     uint32_t n_slots, const gf_app& w, uint32_t ds, const RunList& R,
@@ -706,19 +709,11 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
     // the winner's does (commit_done); a second barrier for everybody only publishes the commit where there is no helper
     // (sixteen views) or the table has a global tail.
     const bool kCommitBarrier = AZ_AWARE && (tail_in_global || ew >= (uint32_t)NW);
-#ifdef GF_ZONED_SERIAL_AVG  // experiment / self-check build: every average is the slice-order sum (the round-3 kernel)
-    constexpr bool kSerialAvg = true;
-#else
-    constexpr bool kSerialAvg = false;
-#endif
 
     int32_t failed_at = -1;
     uint32_t a = 0;
     bool wait_commit = false;  // this wavefront won the previous application and the helper is subtracting its usage
     unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};
-#if defined(GF_EXP_AVG_PROFILE) || defined(GF_EXP_DECIDE_PROFILE)
-    unsigned long long aph[3] = {0, 0, 0};
-#endif
     unsigned long long tph = stats != nullptr ? __builtin_readcyclecounter() : 0ull;
     const unsigned long long t0_cycles = tph;
     const unsigned long long t0_real = wall_clock64();
@@ -814,27 +809,13 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             bool feasible = false;
             const bool indexed = app.shape_x != kZNoShape;
             const bool hopeless = indexed && K > 0 && (int64_t)sh->total_cap[wave][app.shape_x] < K;
-#if defined(GF_EXP_DECIDE_PROFILE)  // experiment build: view setup + bound | driver search | executor scan (wave 0)
-            unsigned long long td0 = __builtin_readcyclecounter();
-            if (stats != nullptr && wave == 0) aph[0] += td0 - tph;
-#endif
             const int64_t p0 = hopeless ? -1 : nwave_first_driver(ZV, T.n_d, app, lane);
-#if defined(GF_EXP_DECIDE_PROFILE)
-            if (stats != nullptr && wave == 0) {
-                const unsigned long long now = __builtin_readcyclecounter();
-                aph[1] += now - td0;
-                td0 = now;
-            }
-#endif
             if (p0 >= 0) {
                 my_ds = (uint32_t)p0;
                 if (K == 0) {
                     feasible = true;
                 } else {
                     const int64_t S_d = nwave_tight_runs(ZV, T.n_x, app, my_ds, R, my_nruns, my_on_ds, lane);
-#if defined(GF_EXP_DECIDE_PROFILE)
-                    if (stats != nullptr && wave == 0) aph[2] += __builtin_readcyclecounter() - td0;
-#endif
                     if (S_d >= K) {
                         feasible = true;
                     } else {  // the first fitting candidate's node is where the executors were needed (wave_fallback)
@@ -863,19 +844,14 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 }
-#if defined(GF_EXP_AVG_PROFILE)  // experiment build: the averages split three ways (loads | arithmetic | sum)
-                mx = wave_runs_avg_max<true, kSerialAvg>(V, unit, sched, T.n_slots, w, my_ds, R, my_nruns, my_on_ds, lane,
-                                                         (stats != nullptr && wave == 0) ? aph : nullptr, &me);
-#else
-                mx = wave_runs_avg_max<true, kSerialAvg>(V, unit, sched, T.n_slots, w, my_ds, R, my_nruns, my_on_ds, lane, nullptr, &me);
-#endif
+                mx = wave_runs_avg_max<true, false>(V, unit, sched, T.n_slots, w, my_ds, R, my_nruns, my_on_ds, lane, nullptr, &me);
             }
             if (lane == 0) {
                 sh->feas[par][wave] = feasible ? 1 : 0;
                 sh->ds[par][wave] = my_ds;
                 sh->nruns[par][wave] = my_nruns;
                 sh->mx[par][wave] = mx;
-                if (!kSerialAvg) sh->me[par][wave] = me;
+                sh->me[par][wave] = me;
             }
             if (feasible && my_nruns > kZRunMax && ew < (uint32_t)NW)  // spilled runs (global): the helper reads them
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -891,10 +867,10 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             if (lane < 16) {
                 f = sh->feas[par][lane];
                 m = sh->mx[par][lane];
-                if (!kSerialAvg) e = sh->me[par][lane];
+                e = sh->me[par][lane];
             }
-            best = kSerialAvg ? zoned_choose_best(f, m, n_zone_cand, lane) : zoned_choose_bounded(f, m, e, n_zone_cand, lane);
-            if (!kSerialAvg && GF_RARE(best == kChooseUndecided)) {
+            best = zoned_choose_bounded(f, m, e, n_zone_cand, lane);
+            if (GF_RARE(best == kChooseUndecided)) {
                 // the bounds do not separate the candidates (ties between zones with equal nodes, an unbounded candidate): the
                 // reference's own sums, one more barrier — every wavefront reaches the same verdict from the same published values
                 if (wave < n_zone_cand && my_feasible) {
@@ -1071,9 +1047,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
         stats->fifo_shader_cycles = __builtin_readcyclecounter() - t0_cycles;
         stats->fifo_realtime_ticks = wall_clock64() - t0_real;
         for (int i = 0; i < 6; ++i) stats->fifo_phase_cycles[i] = ph[i];
-#if defined(GF_EXP_AVG_PROFILE) || defined(GF_EXP_DECIDE_PROFILE)
-        for (int i = 0; i < 3; ++i) stats->fifo_phase_cycles[3 + i] = aph[i];
-#endif
     }
 }
 

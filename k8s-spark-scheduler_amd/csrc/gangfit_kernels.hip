@@ -31,14 +31,8 @@ namespace gangfit {
 namespace {
 
 constexpr int kWave = 64;
-#ifndef GF_MF_TEAM
-#define GF_MF_TEAM 1  // minimal-fragmentation, independent batch: the wavefronts of a workgroup share ONE application's passes (team_minfrag_hist); 0 = one application per wavefront
-#endif
 constexpr int kMfHistBins = 256;  // minimal-fragmentation: capacities below this are counted in a histogram (Orders::mf_hist)
-#ifndef GF_WAVES_PER_BLOCK
-#define GF_WAVES_PER_BLOCK 4
-#endif
-constexpr int kWavesPerBlock = GF_WAVES_PER_BLOCK;  // independent-batch kernel: apps (= waves) per workgroup
+constexpr int kWavesPerBlock = 4;  // independent-batch kernel: apps (= waves) per workgroup
 constexpr int kMfTeamMax = kWavesPerBlock;          // ... and the wavefronts of a minimal-fragmentation team
 
 // ------------------------------------------------------------------------------------------------ wave primitives
@@ -52,16 +46,6 @@ __device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
 
 // Inclusive prefix sum over the 64 lanes of a wave, 7 DPP adds, no LDS traffic.
 __device__ __forceinline__ int32_t wave_inclusive_scan(int32_t v) {
-#ifdef GF_SCAN_SHFL
-    int32_t x = v;
-    const int lane = lane_id();
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        int32_t y = __shfl_up(x, d, kWave);
-        if (lane >= d) x += y;
-    }
-    return x;
-#else
     int32_t x = v;
     x += __builtin_amdgcn_update_dpp(0, v, GF_DPP_ROW_SHR(1), 0xf, 0xf, false);
     x += __builtin_amdgcn_update_dpp(0, v, GF_DPP_ROW_SHR(2), 0xf, 0xf, false);
@@ -71,7 +55,6 @@ __device__ __forceinline__ int32_t wave_inclusive_scan(int32_t v) {
     x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_BCAST15, 0xa, 0xf, false);
     x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_BCAST31, 0xc, 0xf, false);
     return x;
-#endif
 }
 
 __device__ __forceinline__ int32_t read_lane(int32_t v, int src) { return __builtin_amdgcn_readlane(v, src); }
@@ -173,26 +156,10 @@ __device__ __forceinline__ int32_t cap_dim(int64_t a, int64_t e, double rcp, int
     return q < k ? q : k;
 }
 
-#ifdef GF_PLAIN_DIVIDE
-// Reference implementation used by the self-test and by -DGF_PLAIN_DIVIDE builds: compiler-emulated 64-bit divide.
-__device__ __forceinline__ int32_t cap_dim_ref(int64_t a, int64_t e, int32_t k) {
-    if (a < 0) return 0;
-    if (e == 0) return k;
-    const int64_t q = a / e;
-    return q < (int64_t)k ? (int32_t)q : k;
-}
-#endif
-
 __device__ __forceinline__ int32_t cap3(int64_t a0, int64_t a1, int64_t a2, const App& app) {
-#ifdef GF_PLAIN_DIVIDE
-    int32_t c = cap_dim_ref(a0, app.exe0, app.k);
-    int32_t m = cap_dim_ref(a1, app.exe1, app.k);
-    int32_t g = cap_dim_ref(a2, app.exe2, app.k);
-#else
     int32_t c = cap_dim(a0, app.exe0, app.rcp0, app.k);
     int32_t m = cap_dim(a1, app.exe1, app.rcp1, app.k);
     int32_t g = cap_dim(a2, app.exe2, app.rcp2, app.k);
-#endif
     c = c < m ? c : m;
     return c < g ? c : g;
 }
@@ -374,9 +341,6 @@ struct Orders {
     const int32_t* nmem = nullptr;
     const int32_t* ngpu = nullptr;
     int64_t nunit0 = 1, nunit1 = 1, nunit2 = 1;
-#ifdef GF_MF_PROBE  // experiment build: where a minimal-fragmentation decision's cycles go (summed over the launch's applications)
-    unsigned long long* mf_probe = nullptr;
-#endif
     __device__ __forceinline__ void lend_minfrag(lds_u32h* lds, const NodeTable& T) {
         mf_hist = lds;
         mf_lent = true;
@@ -397,9 +361,6 @@ struct Orders {
 // wt (wave-uniform; constant false everywhere but in the resident worker): the placements leave as write-through
 // (system-scope) stores — the destination is read by someone else while this kernel is still running.
 __device__ __forceinline__ void put_out(uint32_t* __restrict__ p, uint32_t v, bool wt) {
-#if defined(GF_WK_NOSTORE) && GF_WK_NOSTORE
-    if (wt) return;  // (measurement build of the worker: see gangfit_worker.inc)
-#endif
     if (wt)
         __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     else
@@ -1111,16 +1072,6 @@ __device__ __forceinline__ void wave_commit_from_list(const View& V, const App& 
 // ------------------------------------------------------------------------------------------------ independent batch
 
 // One wave per app, 4 apps per workgroup.  Grid = ceil(n_apps / 4) >> 256 CUs at the target sizes.
-#ifndef GF_IND_WAVES_PER_EU
-#define GF_IND_WAVES_PER_EU 0  // experiment switch: > 0 asks the compiler for that many wavefronts per SIMD (VGPR and SGPR budget)
-#endif
-#if GF_IND_WAVES_PER_EU == 96
-#define GF_IND_OCC __attribute__((amdgpu_num_sgpr(96), amdgpu_num_vgpr(64)))
-#elif GF_IND_WAVES_PER_EU > 0
-#define GF_IND_OCC __attribute__((amdgpu_waves_per_eu(GF_IND_WAVES_PER_EU, GF_IND_WAVES_PER_EU)))
-#else
-#define GF_IND_OCC
-#endif
 // One wavefront per application, four wavefronts per workgroup.  (Round 4 measured two applications per wavefront for batches
 // that need more than one round of wavefronts — both records requested together, the second parked in two VGPR lanes while the
 // first is decided, 5 000 wavefronts for config 3 instead of 10 000: 13.0-13.2 us against 11.5 us, profiles/r4a_variants.txt.
@@ -1168,13 +1119,13 @@ __device__ __forceinline__ void feasible_collect(uint32_t* words, uint32_t* dst,
 // operations return in order, a store is acknowledged after ~2 us): 37 us per call.  The placements are still made — same
 // decision code — and stay in device memory.  A separate instantiation: the batch kernel proper carries none of this.
 template <int ALGO, bool FEAS>
-__global__ __launch_bounds__(kWave* kWavesPerBlock) GF_IND_OCC void fit_independent_kernel(
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void fit_independent_kernel(
     NodeTable T, SparseTable G, uint32_t n_apps, const gf_app* __restrict__ apps, gf_result* __restrict__ results,
     uint32_t* __restrict__ exec_nodes, uint32_t* __restrict__ scratch, uint64_t scratch_half,
     ScanStats* __restrict__ stats) {
     const int lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr bool kMfTeam = ALGO == GF_ALGO_MINIMAL_FRAGMENTATION && GF_MF_TEAM != 0;
+    constexpr bool kMfTeam = ALGO == GF_ALGO_MINIMAL_FRAGMENTATION;
     const uint32_t a = kMfTeam ? blockIdx.x : blockIdx.x * kWavesPerBlock + wave;
     const bool reports = !kMfTeam || wave == 0u;  // (a team's wavefronts reach the same decision: one of them reports it)
     const uint32_t n_waves = n_apps;
@@ -1196,13 +1147,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) GF_IND_OCC void fit_independ
             O.mf_team_base = (lds_u32h*)mf_hist;
             O.mf_words = (lds_u32h*)mf_words;
         }
-#ifdef GF_MF_PROBE
-        if (stats != nullptr) O.mf_probe = &stats->fifo_phase_cycles[0];
-#endif
     }
-#ifdef GF_MF_PROBE
-    const unsigned long long t_kernel0 = __builtin_readcyclecounter();
-#endif
     // every launch starts with cold L2s: the chunk index of group 0 and the app record are requested together
     //      (unconditionally — a branch here would make the compiler wait for the loads at the join; the general layout
     //      ignores the values, the buffers exist in both layouts)
@@ -1226,10 +1171,6 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) GF_IND_OCC void fit_independ
         }
     };
     decide(load_app(apps, a), a);
-#ifdef GF_MF_PROBE
-    if constexpr (ALGO == GF_ALGO_MINIMAL_FRAGMENTATION)
-        if (!FEAS && stats != nullptr && lane == 0 && reports) atomicAdd(&stats->fifo_phase_cycles[0], __builtin_readcyclecounter() - t_kernel0);
-#endif
     if (!FEAS && stats != nullptr && lane == 0 && reports) {
         atomicAdd(&stats->exec_slots_visited, xvis);
         atomicAdd(&stats->driver_slots_visited, dvis);
@@ -1872,7 +1813,7 @@ hipError_t launch_fit_independent(gf_algo algo, const NodeTable& table, const Sp
     if (d_feasible != nullptr && d_feasible_sync == nullptr) return hipErrorInvalidValue;
     const dim3 block(kWave * kWavesPerBlock);
     // (minimal-fragmentation: a workgroup per application — its wavefronts share the passes over the executor order)
-    const bool team = algo == GF_ALGO_MINIMAL_FRAGMENTATION && GF_MF_TEAM != 0;
+    const bool team = algo == GF_ALGO_MINIMAL_FRAGMENTATION;
     const dim3 grid(team ? n_apps : (n_apps + kWavesPerBlock - 1) / kWavesPerBlock);
     const dim3 grid_feas(grid.x + 1);  // + the collecting workgroup
 #define GF_IND(ALGO)                                                                                                               \
@@ -1973,7 +1914,7 @@ hipError_t launch_solo(const FifoPlan& P, const NodeTable& T, const NarrowTable&
                        uint64_t half, int32_t* d_failed, const ChainCkpt& ck, const SoloFused& F, ScanStats* d_stats,
                        hipStream_t stream) {
     const size_t lds = fifo_solo_lds_bytes(P.lds_slots_solo, T.n_chunks);
-    constexpr int NW = GF_SOLO_WAVES;  // wavefront 0 walks the chain; all of them share the prologue, the checkpoints and the epilogue
+    constexpr int NW = kSoloWaves;  // wavefront 0 walks the chain; all of them share the prologue, the checkpoints and the epilogue
     const bool resident = P.lds_slots_solo >= T.n_slots;
 #define GF_SOLO(PR, RE)                                                                                                     \
     return launch_one_workgroup(fit_fifo_solo_kernel<ALGO, NW, PR, RE>, NW, lds, stream, T, NT, P.lds_slots_solo, n_apps,    \

@@ -39,9 +39,6 @@ constexpr int64_t kCapInf = INT64_MAX;  // math.MaxInt on a 64-bit Go build (cap
 __device__ __forceinline__ int64_t cap_dim_full(int64_t a, int64_t e, double rcp) {
     if (a < 0) return 0;         // reserved > available
     if (e == 0) return kCapInf;  // wave-uniform
-#ifdef GF_PLAIN_DIVIDE
-    return a / e;
-#else
     const double qf = (double)a * rcp;
     if (qf < 1099511627776.0) {  // 2^40
         int64_t q = (int64_t)qf;  // qf >= 0: truncation == floor
@@ -53,7 +50,6 @@ __device__ __forceinline__ int64_t cap_dim_full(int64_t a, int64_t e, double rcp
         return q;
     }
     return a / e;  // a >= 0, e > 0: truncation == floor
-#endif
 }
 
 __device__ __forceinline__ int64_t wave_min_i64(int64_t v) { return -wave_max_i64(-v); }  // callers keep v > INT64_MIN
@@ -90,10 +86,7 @@ __device__ __forceinline__ int64_t mf_cap(const View& V, const Orders& O, const 
 // of the one-launch batch spent 19 cycles per instruction waiting for them (profiles/r5c_summary.md: 322 us for 122 M
 // instructions).  The walk therefore requests up to kMfAhead candidate chunks at once and hands them to f in order; a walk that
 // f stops early has requested at most kMfAhead - 1 chunks it did not need.
-#ifndef GF_MF_AHEAD
-#define GF_MF_AHEAD 4  // (8 measured: profiles/r5ar_minfrag_ahead8.txt)
-#endif
-constexpr int kMfAhead = GF_MF_AHEAD;
+constexpr int kMfAhead = 4;  // (8 measured: profiles/r5ar_minfrag_ahead8.txt)
 template <class View, class F>
 __device__ __forceinline__ void mf_for_each_chunk(const View& V, const Orders& O, const App& app, uint32_t ds, int lane,
                                                   F f) {
@@ -239,10 +232,7 @@ __device__ __forceinline__ int32_t mf_ncap_of(bool cand, int32_t a0, int32_t a1,
     return cand ? (cm < g ? cm : g) : 0;
 }
 
-#ifndef GF_MF_AHEAD_NARROW
-#define GF_MF_AHEAD_NARROW 4
-#endif
-constexpr int kMfAheadNarrow = GF_MF_AHEAD_NARROW;  // chunks of the scaled columns requested together
+constexpr int kMfAheadNarrow = 4;  // chunks of the scaled columns requested together
 // mf_for_each_chunk on the scaled columns: f(j, capacity) for every slot of the chunks the maxima index cannot rule out.
 // [c_lo, c_hi): the chunks of the order this wavefront walks (a TEAM of wavefronts shares one application: team_minfrag_hist).
 template <class View, class F>
@@ -308,27 +298,21 @@ __device__ __forceinline__ uint64_t mf_peers8(uint32_t v, bool valid) {
     return peers;
 }
 
-#ifndef GF_MF_RUN_HEADS
-#define GF_MF_RUN_HEADS 64  // pass 1: chunks with at most this many runs of equal capacities count them by run (0 = always by value;
-                            // 64 = always by run, and the by-value code is not even compiled: 6 / 12 / 24 / 64 gave 61.0 / 59.5 / 55.8 /
-                            // 44.8 us per 1 000 applications, profiles/r6bf_minfrag_run_heads.txt)
-#endif
 // Pass 1's "who speaks for whom" by RUNS: a lane whose capacity differs from its predecessor's speaks for the lanes behind it that
 // hold the same one (neighbours in the priority order mostly do) — a shift, a compare, a ballot and the distance to the next head
 // instead of mf_peers8's eight ballots with their sixteen selects.  Equal capacities that are not neighbours speak separately (to the
-// same bin: served one after the other), so a chunk of many short runs takes the ballot form instead: `by_run` is wave-uniform.
-// n: the lanes this one speaks for (0: it does not speak).
-__device__ __forceinline__ bool mf_run_heads(uint32_t v, bool valid, int lane, uint32_t& n) {
+// same bin: served one after the other).  Returns the lanes this one speaks for (0: it does not speak).
+// (Counting by value with mf_peers8 for chunks of many short runs measured slower at every threshold: 6 / 12 / 24 runs gave
+// 61.0 / 59.5 / 55.8 us per 1 000 applications, always by run 44.8 us — profiles/r6bf_minfrag_run_heads.txt.)
+__device__ __forceinline__ uint32_t mf_run_heads(uint32_t v, bool valid, int lane) {
     const uint32_t key = valid ? v : 0x80000000u;
     uint32_t prev = (uint32_t)__shfl_up((int)key, 1, kWave);
     if (lane == 0) prev = ~key;
     const uint64_t heads = __ballot(key != prev);
     const uint64_t speakers = heads & __ballot(valid);
-    if ((uint32_t)__popcll((unsigned long long)speakers) > (uint32_t)GF_MF_RUN_HEADS) return false;
     const uint64_t rest = lane == kWave - 1 ? 0ull : heads >> (lane + 1);
     const uint32_t len = rest ? (uint32_t)__ffsll((unsigned long long)rest) : (uint32_t)(kWave - lane);
-    n = ((speakers >> lane) & 1ull) ? len : 0u;
-    return true;
+    return ((speakers >> lane) & 1ull) ? len : 0u;
 }
 
 // Value of bin c (wave-uniform) from the per-lane registers (lane l holds bins 4l .. 4l+3).
@@ -355,9 +339,6 @@ __device__ __forceinline__ bool wave_minfrag_hist(const View& V, const Orders& O
     lds_mf4* const C4 = (lds_mf4*)C;
     A4[lane] = mf_u32x4{0u, 0u, 0u, 0u};
     B4[lane] = mf_u32x4{GF_NO_NODE, GF_NO_NODE, GF_NO_NODE, GF_NO_NODE};
-#ifdef GF_MF_PROBE
-    const unsigned long long tq0 = __builtin_readcyclecounter();
-#endif
     // The scaled requests and their multipliers as LANE values for the passes: they are wave-uniform, the compiler keeps them in
     // scalar registers, has none left and reloads every one of them from its spill lane at every use (nineteen v_readlane per
     // chunk of the pass); as vector operands they cost twelve registers and no instruction.
@@ -385,27 +366,15 @@ __device__ __forceinline__ bool wave_minfrag_hist(const View& V, const Orders& O
         // two of them per chunk kept the CU's LDS busy for ~120 cycles per chunk of ANY of its wavefronts (5.2 conflicts per active
         // LDS cycle in profiles/pmc_zoned.json): what the pass was bound by once four wavefronts per SIMD hid its latency
         const bool binned = c > 0 && c < kMfHistBins;
-        uint32_t n_run = 0;
-        if (GF_MF_RUN_HEADS > 0 && mf_run_heads((uint32_t)c, binned, lane, n_run)) {
-            if (n_run != 0u) {  // (a run's first lane holds its smallest slot)
-                __hip_atomic_fetch_add(A + (uint32_t)c, n_run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_min(B + (uint32_t)c, j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            return true;
-        }
-        const uint64_t peers = mf_peers8((uint32_t)c, binned);
-        if (binned && (peers & lt_mask) == 0ull) {
-            __hip_atomic_fetch_add(A + (uint32_t)c, (uint32_t)__popcll((unsigned long long)peers), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t n_run = mf_run_heads((uint32_t)c, binned, lane);
+        if (n_run != 0u) {  // (a run's first lane holds its smallest slot)
+            __hip_atomic_fetch_add(A + (uint32_t)c, n_run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_min(B + (uint32_t)c, j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         return true;
     });
     const bool big = cmax >= kMfHistBins;
     visited += O.n_x;
-#ifdef GF_MF_PROBE
-    const unsigned long long tq1 = __builtin_readcyclecounter();
-    if (O.mf_probe != nullptr && lane == 0) atomicAdd(O.mf_probe + 2, tq1 - tq0);
-#endif
     if (__ballot(big) != 0ull) return false;
     const mf_u32x4 cnt4 = A4[lane], pos4 = B4[lane];  // (LDS operations of a wavefront execute in order)
     const uint32_t cn[4] = {cnt4.x, cnt4.y, cnt4.z, cnt4.w};
@@ -500,10 +469,6 @@ __device__ __forceinline__ bool wave_minfrag_hist(const View& V, const Orders& O
             break;
         }
     }
-#ifdef GF_MF_PROBE
-    const unsigned long long tq2 = __builtin_readcyclecounter();
-    if (O.mf_probe != nullptr && lane == 0) atomicAdd(O.mf_probe + 3, tq2 - tq1);
-#endif
     // ---- pass 2: the runs of the drained levels, every node by its rank among its level's nodes in priority order
     uint32_t left = n_runs + (next_level >= 0 ? 1u : 0u);
     if (left != 0u) {
@@ -531,9 +496,6 @@ __device__ __forceinline__ bool wave_minfrag_hist(const View& V, const Orders& O
         visited += O.n_x;
     }
     if (R > 0 && last_pos != GF_NO_NODE) mf_emit_one<SLOTS>(O, out, K - R, R, last_pos, lane);  // (always found when S >= K)
-#ifdef GF_MF_PROBE
-    if (O.mf_probe != nullptr && lane == 0) atomicAdd(O.mf_probe + 4, __builtin_readcyclecounter() - tq2);
-#endif
     return true;
 }
 
@@ -584,9 +546,6 @@ __device__ __forceinline__ bool team_minfrag_hist(const View& V, const Orders& O
     GF_KEEP(nv.un0);
     GF_KEEP(nv.un1);
     GF_KEEP(nv.un2);
-#ifdef GF_MF_PROBE  // wavefront 0 of the team: own quarter of pass 1 | barriers + rows + plan | pass 2
-    const unsigned long long tq0 = __builtin_readcyclecounter();
-#endif
     const uint32_t xc = (O.n_x + kWave - 1) / kWave;
     const uint32_t per = (xc + team - 1u) / team;
     const uint32_t c_lo = rank * per < xc ? rank * per : xc, c_hi = c_lo + per < xc ? c_lo + per : xc;
@@ -598,17 +557,9 @@ __device__ __forceinline__ bool team_minfrag_hist(const View& V, const Orders& O
         // two of them per chunk kept the CU's LDS busy for ~120 cycles per chunk of ANY of its wavefronts (5.2 conflicts per active
         // LDS cycle in profiles/pmc_zoned.json): what the pass was bound by once four wavefronts per SIMD hid its latency
         const bool binned = c > 0 && c < kMfHistBins;
-        uint32_t n_run = 0;
-        if (GF_MF_RUN_HEADS > 0 && mf_run_heads((uint32_t)c, binned, lane, n_run)) {
-            if (n_run != 0u) {  // (a run's first lane holds its smallest slot)
-                __hip_atomic_fetch_add(A + (uint32_t)c, n_run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_min(B + (uint32_t)c, j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            return true;
-        }
-        const uint64_t peers = mf_peers8((uint32_t)c, binned);
-        if (binned && (peers & lt_mask) == 0ull) {
-            __hip_atomic_fetch_add(A + (uint32_t)c, (uint32_t)__popcll((unsigned long long)peers), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const uint32_t n_run = mf_run_heads((uint32_t)c, binned, lane);
+        if (n_run != 0u) {  // (a run's first lane holds its smallest slot)
+            __hip_atomic_fetch_add(A + (uint32_t)c, n_run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_min(B + (uint32_t)c, j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         return true;
@@ -618,10 +569,6 @@ __device__ __forceinline__ bool team_minfrag_hist(const View& V, const Orders& O
         if (lane == 0) O.mf_words[rank] = (uint32_t)wmax;
     }
     visited += O.n_x;  // (wavefront 0 reports for the team: a pass of the team = one pass over the order)
-#ifdef GF_MF_PROBE
-    const unsigned long long tq1 = __builtin_readcyclecounter();
-    if (O.mf_probe != nullptr && lane == 0 && rank == 0u) atomicAdd(O.mf_probe + 2, tq1 - tq0);
-#endif
     lds_barrier();  // every quarter's rows are complete
     uint32_t cn[4] = {0u, 0u, 0u, 0u}, fp[4] = {GF_NO_NODE, GF_NO_NODE, GF_NO_NODE, GF_NO_NODE}, pre[4] = {0u, 0u, 0u, 0u}, own[4] = {0u, 0u, 0u, 0u};
     uint32_t tmax = 0;
@@ -729,10 +676,6 @@ __device__ __forceinline__ bool team_minfrag_hist(const View& V, const Orders& O
         }
     }
     const bool last_from_plan = last_pos != GF_NO_NODE;
-#ifdef GF_MF_PROBE
-    const unsigned long long tq2 = __builtin_readcyclecounter();
-    if (O.mf_probe != nullptr && lane == 0 && rank == 0u) atomicAdd(O.mf_probe + 3, tq2 - tq1);
-#endif
     // what the plan wants from THIS quarter: of every drained level the nodes with ranks [pre, pre + own) below `taken`, and the
     // next level's node of rank next_rank when it lies in here
     uint32_t left;
@@ -770,9 +713,6 @@ __device__ __forceinline__ bool team_minfrag_hist(const View& V, const Orders& O
         }, c_lo, c_hi);
         visited += O.n_x;
     }
-#ifdef GF_MF_PROBE
-    if (O.mf_probe != nullptr && lane == 0 && rank == 0u) atomicAdd(O.mf_probe + 4, __builtin_readcyclecounter() - tq2);
-#endif
     // what is left goes to the node the plan named (wavefront 0 emits) or to the one this quarter found
     if (R > 0 && last_pos != GF_NO_NODE && (last_from_plan ? rank == 0u : true)) mf_emit_one<SLOTS>(O, out, K - R, R, last_pos, lane);
     return true;
@@ -788,23 +728,11 @@ __device__ __forceinline__ int64_t wave_minfrag(const View& V, const Orders& O, 
     if (O.mf_lent && O.ncpu != nullptr && K > 0) {  // the histogram form, where it applies (wave-uniform)
         MfNarrow na;
         int64_t S_h = 0;
-#ifdef GF_MF_PROBE
-        const unsigned long long tp0 = __builtin_readcyclecounter();
-        const bool nok = mf_narrow_app(app, O, na);
-        const unsigned long long tp1 = __builtin_readcyclecounter();
-        if (O.mf_probe != nullptr && lane == 0 && O.mf_rank == 0u) atomicAdd(O.mf_probe + 1, tp1 - tp0);
-        if (nok && (O.mf_team > 1u ? team_minfrag_hist<View, SLOTS>(V, O, app, na, ds, out, lane, visited, S_h)
-                                   : wave_minfrag_hist<View, SLOTS>(V, O, app, na, ds, out, lane, visited, S_h))) {
-            if (O.mf_probe != nullptr && lane == 0) atomicAdd(O.mf_probe + 5, 1ull << (16 * (threadIdx.x >> 6)));
-            return S_h;
-        }
-#else
         if (O.mf_team > 1u) {  // (wave-uniform, and the same in every wavefront of the team: both barriers are met by all)
             if (mf_narrow_app(app, O, na) && team_minfrag_hist<View, SLOTS>(V, O, app, na, ds, out, lane, visited, S_h)) return S_h;
         } else if (mf_narrow_app(app, O, na) && wave_minfrag_hist<View, SLOTS>(V, O, app, na, ds, out, lane, visited, S_h)) {
             return S_h;
         }
-#endif
     }
     // capacities, their clamped sum and maximum (capacity.go:78-113, minimal_fragmentation.go:64-67)
     int64_t lsum = 0, lmax = 0;

@@ -27,42 +27,22 @@
 // groups.  And plain stores to pinned host memory stay in the L2 until a write-back: a ticket completed with all-zero
 // answers on the host.)
 
-// The per-application pipeline of a wavefront (round 6; each a build switch, all on: profiles/r6b_worker_variants.txt — a ticket
+// The per-application pipeline of a wavefront (round 6, each step measured on its own: profiles/r6b_worker_variants.txt — a ticket
 // 1.37 -> 1.22 us in a long stream, a window of twenty 54.9 -> 51.2 us):
-//   GF_WK_DIRECT   tightly-pack placements leave as write-through stores straight from the run emission (device-resident
-//                  destinations: no private slice, no read-back of the wavefront's own stores)
-//   GF_WK_RECORDS  the records of all applications a wavefront serves in a ticket (up to eight) in ONE load instruction
-//   GF_WK_G0LDS    group 0 of the chunk index (the same for every application while the worker lives) read once into LDS
-//   GF_WK_NOSTORE  measurement only, WRONG ANSWERS: 1 = no placement stores, 2 = no result stores either (-8 %: the stores are
-//                  not what a ticket waits for)
+//   direct     tightly-pack placements leave as write-through stores straight from the run emission (device-resident
+//              destinations: no private slice, no read-back of the wavefront's own stores)
+//   kRecords   the records of all applications a wavefront serves in a ticket (up to eight) in ONE load instruction
+//   s_g0       group 0 of the chunk index (the same for every application while the worker lives) read once into LDS
+//   kDynamic   the applications of a ticket that a workgroup serves are HANDED OUT (an LDS counter per round) instead of
+//              belonging to fixed wavefronts: sixteen wavefronts finish a ticket within one application of each other.
+// Leaving out the placement and result stores altogether (a measurement build with wrong answers, since retired) was 8 % faster:
+// the stores are not what a ticket waits for.
 // Measured and removed in the same round (profiles/r6c_worker_lds_table_not_kept.txt): the scaled int32 table resident in LDS
 // (145 KB per workgroup, a chunk visit three ds_read_b32) — same answers, 1.64 us per ticket: with sixteen wavefronts per CU the
 // bound is the SIMDs' issue slots, not the table's read latency, and the resident table adds instructions.
-#ifndef GF_WK_DIRECT
-#define GF_WK_DIRECT 1
-#endif
-#ifndef GF_WK_RECORDS
-#define GF_WK_RECORDS 1
-#endif
-#ifndef GF_WK_G0LDS
-#define GF_WK_G0LDS 1
-#endif
-#ifndef GF_WK_NOSTORE
-#define GF_WK_NOSTORE 0
-#endif
-//   GF_WK_DYNAMIC  the applications of a ticket that a workgroup serves are HANDED OUT (an LDS counter per round) instead of
-//                  belonging to fixed wavefronts: sixteen wavefronts finish a ticket within one application of each other.
-#ifndef GF_WK_DYNAMIC
-#define GF_WK_DYNAMIC 1
-#endif
 // Measured and removed (profiles/r6u_worker_record_cache_not_kept.txt): an LDS record cache per workgroup (the records of a round's
 // applications 16 .. 47 requested a round ahead) — no difference: the wavefronts of a CU are in different phases and hide each
 // other's record latency.
-#ifndef GF_WK_RING_SCOPE  // scope of the leader's relay stores and of the ticket probes: experiment switch
-#define GF_WK_RING_SCOPE __HIP_MEMORY_SCOPE_AGENT
-#endif
-
-
 
 __device__ __forceinline__ unsigned long long sys_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -93,7 +73,7 @@ __device__ __forceinline__ App load_app_uncached(const gf_app* apps, uint32_t a,
     return r;
 }
 
-// The same fields from a register that holds eight records (lane 8 i + f = word f of record i): GF_WK_RECORDS.
+// The same fields from a register that holds eight records (lane 8 i + f = word f of record i): kRecords.
 __device__ __forceinline__ App app_from_lanes(unsigned long long w, uint32_t i) {
     const int b = (int)(8u * i);
     App r;
@@ -127,11 +107,9 @@ template <int ALGO>
 __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(NodeTable T, SparseTable G, WorkerArgs W) {
     __shared__ uint32_t s_cnt[8];               // applications the workgroup has finished, per round (recycled every eight rounds)
     __shared__ uint32_t s_round[kWorkerWaves];  // rounds each wavefront has finished
-    __shared__ unsigned long long s_next[8];    // (round << 32) | applications of that round handed out so far (GF_WK_DYNAMIC)
-#if GF_WK_G0LDS
+    __shared__ unsigned long long s_next[8];    // (round << 32) | applications of that round handed out so far (kDynamic)
     // group 0 of the chunk index: lane l = chunk l (maxima x 3, dcand, xcand)
     __shared__ unsigned long long s_g0[5][kWave];
-#endif
     const int lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (blockIdx.x == 0) {
@@ -140,13 +118,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         unsigned long long consumed = W.first_ticket;
         unsigned long long last = wall_clock64();
         if (lane == 0) sys_store(&W.host->state, 1ull);
-#ifdef GF_WK_PROF  // the relay: looks that found tickets, 100 MHz ticks between a look and the end of its relay, tickets per look
-        unsigned long long lp_looks = 0, lp_ticks = 0, lp_tickets = 0, lp_max = 0, lp_idle_looks = 0;
-#endif
         for (;;) {
-#ifdef GF_WK_PROF
-            const unsigned long long lp_t0 = wall_clock64();
-#endif
             // the doorbell and the stop word travel together: one round trip over the host link per look, not two
             const unsigned long long posted = sys_load(&W.host->posted);
             const unsigned long long stop = sys_load(&W.host->stop);
@@ -167,21 +139,11 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                         const unsigned long long t = consumed + (unsigned long long)(lane >> 3) + 8ull * (unsigned long long)q;
                         if (t < posted)
                             __hip_atomic_store(reinterpret_cast<unsigned long long*>(&W.dev->ring[(uint32_t)(t % kWorkerRing)]) + (lane & 7), w4[q],
-                                               __ATOMIC_RELAXED, GF_WK_RING_SCOPE);
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
                     const unsigned long long step = posted - consumed < 32ull ? posted - consumed : 32ull;
                     consumed += step;
-#ifdef GF_WK_PROF
-                    lp_tickets += step;
-                    lp_max = step > lp_max ? step : lp_max;
-#endif
                 }
-#ifdef GF_WK_PROF
-                if (lane == 0) __hip_atomic_store(&W.dev->count[1], (uint32_t)consumed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (a spare word: the relayed frontier)
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                ++lp_looks;
-                lp_ticks += wall_clock64() - lp_t0;
-#endif
                 last = wall_clock64();
                 continue;
             }
@@ -189,13 +151,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             // stop word), or for lack of work
             if (stop == 1ull || (stop >= 2ull && consumed >= stop - 2ull) || (W.leave_after != 0ull && consumed >= W.leave_after) ||
                 wall_clock64() - last > W.idle_ticks) {
-#ifdef GF_WK_PROF
-                if (W.stats != nullptr && lane == 0) {
-                    atomicAdd(&W.stats->exec_slots_visited, lp_looks);
-                    atomicAdd(&W.stats->driver_slots_visited, lp_ticks);
-                    atomicAdd(&W.stats->fifo_realtime_ticks, lp_tickets | (lp_max << 32));
-                }
-#endif
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every ticket word is out before the quit word
                 if (lane == 0) {
                     __hip_atomic_store(&W.dev->quit, W.generation, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -233,7 +188,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     if (threadIdx.x < kCountSlots) s_cnt[threadIdx.x] = 0;
     if (threadIdx.x < 8) s_next[threadIdx.x] = 0ull;
     if (threadIdx.x < (uint32_t)kWorkerWaves) s_round[threadIdx.x] = 0;
-#if GF_WK_G0LDS
     if (wave == 0) {  // the tables do not change while the worker lives
         const Group0 g = load_group0(V, O, lane);
         s_g0[0][lane] = (unsigned long long)g.m0;
@@ -242,18 +196,17 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         s_g0[3][lane] = g.dcand;
         s_g0[4][lane] = g.xcand;
     }
-#endif
     __syncthreads();  // the only barrier of the kernel: the LDS words above
     typedef __attribute__((address_space(1))) const gf_app glb_app;
     typedef __attribute__((address_space(1))) gf_result glb_result;
     typedef __attribute__((address_space(1))) uint32_t glb_u32w;
     constexpr unsigned long long kPtrMask = 0x0000FFFFFFFFFFFFull;
-    constexpr bool kRecords = GF_WK_RECORDS != 0 && ALGO != GF_ALGO_MINIMAL_FRAGMENTATION;  // (that instance is at its register budget)
+    constexpr bool kRecords = ALGO != GF_ALGO_MINIMAL_FRAGMENTATION;  // (that instance is at its register budget)
     // the six words of ticket tt as they are now (lane l < 6: word l), and whether they are that ticket's
     auto load_words = [&](unsigned long long tt) {
         const unsigned long long* line = reinterpret_cast<const unsigned long long*>(&W.dev->ring[(uint32_t)(tt % kWorkerRing)]);
         unsigned long long w = 0;
-        if (lane < 6) w = __hip_atomic_load(line + lane, __ATOMIC_RELAXED, GF_WK_RING_SCOPE);
+        if (lane < 6) w = __hip_atomic_load(line + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return w;
     };
     auto words_valid = [&](unsigned long long w, unsigned long long tt) {
@@ -267,7 +220,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         if (ai < n_apps_) r = sys_load(reinterpret_cast<const unsigned long long*>(apps_ + ai) + (lane & 7));
         return r;
     };
-    // GF_WK_DYNAMIC: the next application of round r of this workgroup (its i-th: wave-uniform).  The counter word carries the round
+    // kDynamic: the next application of round r of this workgroup (its i-th: wave-uniform).  The counter word carries the round
     // it counts for: the first wavefront to arrive in a round turns the word over (compare-and-swap), nobody ever resets it.
     auto grab = [&](uint32_t r) {
         uint32_t got = 0;
@@ -303,7 +256,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             __builtin_amdgcn_s_sleep(4);
         }
     };
-    constexpr bool kDynamic = GF_WK_DYNAMIC != 0 && kRecords;
+    constexpr bool kDynamic = kRecords;
     uint32_t i_cur = 0;  // kDynamic: the application grabbed for the start of this round (with its record in wrec), if grabbed_cur
     bool grabbed_cur = false;
     unsigned long long w_cur = 0;
@@ -318,24 +271,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     unsigned long long wrec = 0;  // the records of this round (kRecords)
     bool recs_loaded = false;
     uint32_t round = 0;
-#ifdef GF_WK_PROF
-    // Instrumented build (tools/build_variants_fast.sh prof:"-DGF_WK_PROF"; gf_scan_stats on): where the rounds of two wavefronts of
-    // ONE workgroup (set 0's first) go, shader cycles summed over their rounds — wavefront 0 into fifo_phase_cycles, wavefront 5
-    // into fifo_rare_cycles: [0] the ticket, [1] the round guard, [2] until the first record is in registers, [3] the decisions,
-    // [4] the answers' stores issued, [5] next records requested + drain + completion; rounds in fifo_shader_cycles.
-    unsigned long long wp[6] = {0, 0, 0, 0, 0, 0}, wp_rounds = 0, wp_hits = 0, wp_probes = 0;  // look-ahead hits, probes of the probe loop
-    unsigned long long wp_depth[5] = {0, 0, 0, 0, 0}, wp_lead = 0, wp_lead_n = 0;
-    const bool wp_on = W.stats != nullptr && (wave == 0 || (wave == 5 && blockIdx.x == 1u));  // (wavefront 0 of EVERY workgroup: min / max below)
-    unsigned long long wp_t = __builtin_readcyclecounter();
-#define GF_WKP(i)                                                   \
-    if (wp_on) {                                                    \
-        const unsigned long long n_ = __builtin_readcyclecounter(); \
-        wp[i] += n_ - wp_t;                                         \
-        wp_t = n_;                                                  \
-    }
-#else
-#define GF_WKP(i)
-#endif
     for (;;) {
         // ---- the ticket: brought along by the launch, requested a round ago, or probed for now
         if (W.leave_after != 0ull && t >= W.leave_after) break;  // a bounded stream: nothing behind its last ticket will come
@@ -343,9 +278,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             bool quit_seen = false, gone = false;
             for (;;) {
                 w_cur = load_words(t);
-#ifdef GF_WK_PROF
-                ++wp_probes;
-#endif
                 if (words_valid(w_cur, t)) break;
                 if (quit_seen) {  // (one more probe after the quit word was seen: the leader left before ticket t)
                     gone = true;
@@ -357,7 +289,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             if (gone) break;  // every round this wavefront finished has been counted when it finished
             recs_loaded = false;
         }
-        GF_WKP(0)
         // (a ticket's pointers name global memory — device or mapped pinned host memory —: said so, or every access through
         //  them is a flat instruction that counts against both wait counters)
         const gf_app* apps = (const gf_app*)reinterpret_cast<glb_app*>((uint64_t)read_lane((int64_t)w_cur, 1) & kPtrMask);
@@ -378,7 +309,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         // the count words are recycled every kCountSlots rounds: not before every wavefront of the workgroup has left the round
         // that used this one (it practically never waits: the wavefronts serve the same tickets at the same pace)
         round_guard(round);
-        GF_WKP(1)
         // kDynamic: the workgroup's applications of this ticket are i = 0 .. total - 1, application (i mod 16) of row (i div 16)
         const uint32_t f0 = bsr * kWorkerWaves;
         const uint32_t total = f0 < n_apps ? ((n_apps - 1u - f0) / app_stride + 1u) * kWorkerWaves : 0u;
@@ -396,33 +326,15 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         //  leaving the words in an LDS mailbox for the other fifteen — no faster: sixteen times the probes of rounds 3-5 on the
         //  same lines are not what a stream of tickets waits for.)
         const unsigned long long w_next = load_words(t + W.sets);
-#ifdef GF_WK_PROF  // how far ahead of the set is the device ring?  tickets t + k sets, k = 1 .. 5, there when the round begins
-        if (wp_on && wave == 0) {
-            const uint32_t frontier = __hip_atomic_load(&W.dev->count[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (frontier >= (uint32_t)t) {
-                wp_lead += (unsigned long long)(frontier - (uint32_t)t);
-                ++wp_lead_n;
-            }
-            for (unsigned k = 1; k <= 5; ++k) {
-                const unsigned long long wk = load_words(t + (unsigned long long)k * W.sets);
-                wp_depth[k - 1] += words_valid(wk, t + (unsigned long long)k * W.sets) ? 1 : 0;
-            }
-        }
-#endif
         // per slot: the placements as the wave-level code writes (and, distribute-evenly, re-reads) them, then its two
         // survivor lists — all private to this launch; the caller's arrays only see write-through stores
         uint32_t* priv = W.scratch + (size_t)slot * 3 * W.scratch_stride;
         uint32_t* scratch = priv + W.scratch_stride;
-#if GF_WK_DIRECT
         // device-resident destination (gf_worker_submit_dev without GF_WORKER_HOST_OUTPUTS): the run emission itself writes
         // through; a destination in pinned host memory keeps the private slice and the coalesced copy-out (lone dwords over
         // the host link cost more than the read-back)
         const bool direct = ALGO == GF_ALGO_TIGHTLY_PACK && ((w5 >> 32) & 1ull) == 0;
-#else
-        constexpr bool direct = false;
-#endif
         uint32_t mine = 0, it = 0;
-        bool first = true;
         for (uint32_t a = kDynamic ? app_index(i_cur) : first_app; kDynamic ? i_cur < total : a < n_apps;
              a = kDynamic ? a : a + app_stride) {
             if constexpr (kDynamic) {
@@ -435,15 +347,11 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             }
             App app{};
             Group0 g0{};
-#if GF_WK_G0LDS
             g0.m0 = (int64_t)s_g0[0][lane];
             g0.m1 = (int64_t)s_g0[1][lane];
             g0.m2 = (int64_t)s_g0[2][lane];
             g0.dcand = s_g0[3][lane];
             g0.xcand = s_g0[4][lane];
-#else
-            g0 = load_group0(V, O, lane);
-#endif
             if constexpr (kDynamic) {
                 app = app_from_lanes(wrec, 0);
             } else if constexpr (kRecords) {
@@ -456,31 +364,21 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             } else {
                 app = load_app_uncached(apps, a, lane);  // (waits for its load: everything issued before it has returned)
             }
-#ifdef GF_WK_PROF
-            if (first) {
-                asm volatile("" ::"v"(app.drv0), "v"(app.k));
-                GF_WKP(2)
-            }
-#endif
-            first = false;
             unsigned long long xvis = 0, dvis = 0;
             Decision dec = wave_decide<ALGO, GlobalView, false>(V, O, app, (direct ? exec_nodes : priv) + app.exec_off,
                                                                 scratch + app.exec_off, scratch + half + app.exec_off, lane, xvis,
                                                                 dvis, merged ? &g0 : nullptr, &G, direct);
-            GF_WKP(3)
-#ifndef GF_WK_PROF  // (the instrumented build keeps the counters' atomics — one line, the whole device — out of its rounds)
             if (W.stats != nullptr && lane == 0) {
                 atomicAdd(&W.stats->exec_slots_visited, xvis);
                 atomicAdd(&W.stats->driver_slots_visited, dvis);
             }
-#endif
-            if (dec.feasible && !direct && GF_WK_NOSTORE == 0) {
+            if (dec.feasible && !direct) {
                 // this wavefront's own stores, read back through its CU's L1 / L2 and sent out write-through
                 for (int32_t i = lane; i < app.k; i += kWave)
                     __hip_atomic_store(exec_nodes + app.exec_off + i, priv[app.exec_off + i], __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_SYSTEM);
             }
-            if (lane < 2 && GF_WK_NOSTORE < 2) {  // the 16-byte result as two write-through words
+            if (lane < 2) {  // the 16-byte result as two write-through words
                 if (dec.feasible && dec.ds_node == GF_NO_NODE) dec.ds_node = T.slot_node[dec.ds];
                 const unsigned long long lo = (unsigned long long)(uint32_t)(dec.feasible ? 1 : 0) |
                                               ((unsigned long long)(dec.feasible ? dec.ds_node : GF_NO_NODE) << 32);
@@ -489,7 +387,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                                    __HIP_MEMORY_SCOPE_SYSTEM);
             }
             ++mine;
-            GF_WKP(4)
             if constexpr (kDynamic) {  // the next application of this round, whoever's it would have been
                 i_cur = grab(round);
                 a = app_index(i_cur);
@@ -500,9 +397,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         //      records are requested now, so that ONE wait covers them and this round's stores.
         const unsigned long long t_next = t + W.sets;
         const bool have_next = words_valid(w_next, t_next);
-#ifdef GF_WK_PROF
-        wp_hits += have_next ? 1 : 0;
-#endif
         unsigned long long wrec_next = 0;
         uint32_t i_next = 0;
         if (kDynamic && have_next) {  // the first application of the next round and its record, before this round's stores are drained
@@ -541,22 +435,11 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                     uint32_t before = 0;
                     if (lane == 0) {
                         __hip_atomic_store(&s_cnt[rs], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef GF_WK_PROF  // when did the FIRST workgroup finish its share of this ticket?  (spare word 2 of the slot's line, kept inverted)
-                        const uint32_t tm_ = (uint32_t)wall_clock64();
-                        if (W.stats != nullptr) atomicMax(&W.dev->count[slot * kWorkerCountStride + 2], 0xFFFFFFFFu - tm_);
-#endif
                         before = __hip_atomic_fetch_add(&W.dev->count[slot * kWorkerCountStride], share, __ATOMIC_RELAXED,
                                                         __HIP_MEMORY_SCOPE_AGENT);
                         if (before + share == n_apps) {  // ... and the workgroup's complete the ticket: the host is told
                             __hip_atomic_store(&W.dev->count[slot * kWorkerCountStride], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             sys_store(&W.host->done[slot], t + 1ull);
-#ifdef GF_WK_PROF
-                            if (W.stats != nullptr) {  // ticks (100 MHz) from the first workgroup's share to the ticket's completion
-                                const uint32_t inv = atomicExch(&W.dev->count[slot * kWorkerCountStride + 2], 0u);
-                                atomicAdd(&W.stats->fifo_rare_cycles[0], (unsigned long long)(tm_ - (0xFFFFFFFFu - inv)));
-                                atomicAdd(&W.stats->fifo_rare_count[0], 1ull);
-                            }
-#endif
                         }
                     }
                 }
@@ -564,10 +447,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         }
         ++round;
         if (lane == 0) s_round[wave] = round;  // (rounds this wavefront has left behind: the guard above)
-        GF_WKP(5)
-#ifdef GF_WK_PROF
-        ++wp_rounds;
-#endif
         t = t_next;
         w_cur = w_next;
         have_cur = have_next;
@@ -577,27 +456,4 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         grabbed_cur = kDynamic && have_next;
     }
     if (lane == 0) s_round[wave] = kRoundGone;  // never in anybody's way
-#ifdef GF_WK_PROF
-    if (wp_on && lane == 0) {
-        if (wave == 0 && blockIdx.x != 1u) {
-            // over all workgroups: the smallest / largest share of a wavefront 0's rounds spent waiting for a ticket (per mille),
-            // and the slowest workgroup's decisions per round
-            const unsigned long long tot = wp[0] + wp[1] + wp[2] + wp[3] + wp[4] + wp[5];
-            const unsigned long long idle = tot ? wp[0] * 1000ull / tot : 0ull;
-            atomicMax(&W.stats->fifo_rare_count[1], idle);
-            atomicMax(&W.stats->fifo_rare_count[2], 1000ull - idle);  // (the counters start at zero: the minimum as a maximum)
-            atomicMax(&W.stats->fifo_rare_count[3], wp_rounds ? wp[3] / wp_rounds : 0ull);
-            atomicMax(&W.stats->fifo_rare_count[4], (1ull << 30) - (wp_rounds ? wp[3] / wp_rounds : 0ull));
-        } else if (wave == 0) {
-            for (int i = 0; i < 6; ++i) atomicAdd(&W.stats->fifo_phase_cycles[i], wp[i]);
-            atomicAdd(&W.stats->fifo_shader_cycles, wp_rounds);
-            atomicAdd(&W.stats->fifo_hw_id, wp_hits | (wp_probes << 32));
-            if (blockIdx.x == 1u) printf("[worker prof] tickets t + k sets in the device ring when a round begins, k = 1..5: %llu %llu %llu %llu %llu of %llu rounds\n",
-                                         wp_depth[0], wp_depth[1], wp_depth[2], wp_depth[3], wp_depth[4], wp_rounds);
-            if (blockIdx.x == 1u) printf("[worker prof] the relayed frontier is %llu tickets ahead of the round's ticket on average (first ticket %llu, last %llu)\n",
-                                         wp_lead_n ? wp_lead / wp_lead_n : 0ull, W.first_ticket, t);
-        }  // (wavefront 5's phases gave way to the completion spread: fifo_rare_cycles[0] / fifo_rare_count[0])
-    }
-#endif
-#undef GF_WKP
 }

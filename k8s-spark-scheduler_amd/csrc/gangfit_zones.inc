@@ -340,12 +340,6 @@ __device__ __forceinline__ void wave_avg_efficiency_runs(const EffView& E, const
     avg[3] = max_sum / len;
 }
 
-#ifndef GF_ZONED_SPARSE
-#define GF_ZONED_SPARSE 1  // experiment switch: 0 = gangs of gpu executors on the full table
-#endif
-#ifndef GF_ZONED_RUN_AVG
-#define GF_ZONED_RUN_AVG 1  // experiment switch: 0 = the entry-wise averages for every gang
-#endif
 constexpr int kFusedWaves = 4;  // wavefronts (= candidate views decided at the same time) per application
 constexpr int kRunBlocks = 8;   // wave_avg_max_tight_runs: placements of up to kRunBlocks * 64 executors ...
 constexpr uint32_t kRunMax = 63;  // ... on up to kRunMax nodes (one lane stays free for a driver that hosts no executor)
@@ -479,7 +473,7 @@ __global__ __launch_bounds__(kWave* kFusedWaves, ALGO == GF_ALGO_MINIMAL_FRAGMEN
         // such a gang walks 7-20 chunks of the zone's range for a few slots each, and the launch waits for it: 22.3 us against
         // 19.0 without gpu requests, tools/probe_zoned_parts.py): the view's candidate words are the zone's, and its placements
         // name slots of the full table — what the averages below and the copy-out index.
-        constexpr bool kSparse = ALGO == GF_ALGO_TIGHTLY_PACK && GF_ZONED_SPARSE != 0;
+        constexpr bool kSparse = ALGO == GF_ALGO_TIGHTLY_PACK;
         const SparseTable GV{G.cpu, G.mem, G.gpu, G.slot_of_sub, G.cmax, zone_view ? G.zmask + (size_t)c * G.n_chunks : G.xmask,
                              G.sub_of_slot, kSparse ? G.n_x : 0u, G.n_chunks, G.zmask, G.slot_of_sub};
         const Decision dec = wave_decide<ALGO, GlobalView, true>(V, O, app, out, scratch + app.exec_off,
@@ -500,7 +494,7 @@ __global__ __launch_bounds__(kWave* kFusedWaves, ALGO == GF_ALGO_MINIMAL_FRAGMEN
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             bool done = false;
-            if (ALGO == GF_ALGO_TIGHTLY_PACK && GF_ZONED_RUN_AVG && K >= 1 && K <= (int64_t)kRunBlocks * kWave)
+            if (ALGO == GF_ALGO_TIGHTLY_PACK && K >= 1 && K <= (int64_t)kRunBlocks * kWave)
                 done = wave_avg_max_tight_runs(EV, app, dec.ds, out, lane, (lds_u32r*)&sh.runs[wave][0], avg[3]);
             if (!done) wave_avg_efficiency_runs<ALGO>(EV, app, dec.ds, out, lane, avg);
         }

@@ -34,16 +34,16 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build_native(force: bool = False, extra_flags=()) -> str:
+def build_native(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 ... -> k8s-spark-scheduler_amd/libgangfit.so.  The translation units are compiled side by side
     (one hipcc process each: the two kernel files take most of a minute, the five host files a few seconds), then linked."""
     srcs = [os.path.join(CSRC, s) for s in _SOURCES]
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + _HEADERS  # .inc files are #included by the .hip
-    if force or extra_flags or _stale(LIB_PATH, deps):
+    if force or _stale(LIB_PATH, deps):
         import tempfile
         from concurrent.futures import ThreadPoolExecutor
 
-        common = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC, *extra_flags]
+        common = [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", INCLUDE, "-I", CSRC]
         with tempfile.TemporaryDirectory(prefix="gangfit_build_") as tmp:
             objs = [os.path.join(tmp, os.path.basename(s) + ".o") for s in srcs]
 

@@ -22,5 +22,5 @@ for i in range(12):
     q = np.roll(apps, -i)
     t0 = time.perf_counter(); ctx.fit_batch(1, 0, q); first.append((time.perf_counter() - t0) * 1e3)
 again = ctx.fit_batch(1, 0, apps)
-print(f"lib {os.environ.get('GANGFIT_LIB', 'default')}: cold chain p50 {np.median(cold):.3f} p99 {np.percentile(cold, 99):.3f} ms; first chain on a fresh snapshot p50 {np.median(first):.3f} ms; "
+print(f"cold chain p50 {np.median(cold):.3f} p99 {np.percentile(cold, 99):.3f} ms; first chain on a fresh snapshot p50 {np.median(first):.3f} ms; "
       f"answers stable {bool(np.array_equal(again.results, ref.results) and np.array_equal(again.exec_nodes, ref.exec_nodes))} crc {int(np.bitwise_xor.reduce(ref.exec_nodes.astype(np.uint64) * np.arange(1, len(ref.exec_nodes) + 1, dtype=np.uint64))) & 0xFFFFFFFF:08x}")

@@ -110,13 +110,14 @@ int gf_version(void);
  *   n_dev == 1 (or device_ids NULL, n_dev 0 = device 0): everything runs on that device.
  *   n_dev  > 1 (<= 16): ONE context over several devices of the box — the node table shards by range of the priority order
  *     (SURVEY.md section 8e).  gf_snapshot_set / gf_zones_set / gf_orders_set / gf_snapshot_build install the snapshot on
- *     every device; gf_fit_batch(GF_MODE_INDEPENDENT) with tightly-pack or distribute-evenly then evaluates every
- *     application on every device's range (four device steps per device) and stitches the result with three exchanges
- *     done by peer access over xGMI inside the call: two all-gathers of 16 B per application (written straight into the
- *     peers' tables) and one reduction of the placement buffer onto the first device.  Same gf_result / ExecutorNodes as on
- *     one device, bit for bit.  Everything else (FIFO chains — each commit must be visible to the next scan —, zone-aware
- *     and minimal-fragmentation packers, orders that do not merge into one, single executors, findNodes, efficiencies, the
- *     *_dev entry points) runs on the first device.  One submitting thread per device issues that device's launches
+ *     every device; gf_fit_batch(GF_MODE_INDEPENDENT) with tightly-pack, distribute-evenly, single-az-tightly-pack or
+ *     az-aware-tightly-pack then evaluates every application on every device's range (four device steps per device; the
+ *     zone-aware packers once per candidate view: every zone, plus the plain order for az-aware — they need the schedulable
+ *     columns and at most 64 views) and stitches the result with three exchanges done by peer access over xGMI inside the
+ *     call: two all-gathers of 16 B per application and view (written straight into the peers' tables) and one reduction of
+ *     the placement buffer onto the first device.  Same gf_result / ExecutorNodes as on one device, bit for bit.  Everything
+ *     else (FIFO chains — each commit must be visible to the next scan —, the minimal-fragmentation packers, orders that do
+ *     not merge into one, single executors, findNodes, efficiencies, the *_dev entry points) runs on the first device.  One submitting thread per device issues that device's launches
  *     (the calling thread is the first device's; the others park between batches), so a batch costs the host about what
  *     one device's half a dozen runtime calls cost.  A device id may repeat (several shards on one GPU): that is how the
  *     path is tested on a one-GPU box — the shards of one device then share a sub-context (one launch per step with a grid
@@ -422,10 +423,22 @@ int gf_find_nodes(gf_ctx *ctx, int chained, uint32_t n_req, const int64_t *exe, 
  * exchange over RCCL/xGMI between consecutive steps (the caller owns the communicator; k8s-spark-scheduler_amd/gangfit/
  * sharded.py drives it with torch.distributed):
  *     gf_shard_partials_dev -> all-gather -> gf_shard_drivers_dev -> all-gather -> gf_shard_emit_dev
- *     -> all-reduce(SUM, uint32) of d_exec2 -> gf_shard_finish_dev
+ *     -> all-reduce(SUM, uint32) of the leading reduce_words of d_exec2 -> gf_shard_finish_dev
  * after which EVERY rank holds the complete results: the same gf_result / ExecutorNodes as gf_fit_batch_dev on one GPU.
- * Tightly-pack and distribute-evenly only; the FIFO chain does not shard (each commit must be visible to the next
- * scan): it runs as replicas.  All pointers are device pointers; calls are asynchronous on `stream`. */
+ * Tightly-pack, distribute-evenly, single-az-tightly-pack and az-aware-tightly-pack (the zone-aware two need the schedulable
+ * columns of gf_snapshot_set and at most 64 candidate views); the minimal-fragmentation packers return GF_ERR_UNSUPPORTED.
+ * The FIFO chain does not shard (each commit must be visible to the next scan): it runs as replicas.  All pointers are
+ * device pointers; calls are asynchronous on `stream`.
+ * Layout (gf_shard_layout gives the numbers for a context, packer and batch):
+ *   records = records per application: 1 for the plain packers; for the zone-aware ones the candidate views, n_cand = the
+ *             zones of the evaluation list (+ 1 for az-aware: the plain order).  d_out of partials / drivers holds
+ *             records * n_apps records ([view][app]); the gathered tables are [n_shards][records][n_apps].
+ *   d_exec2 = exec2_words uint32: 2 * half for the plain packers ([0, half) the placements as node index + 1, [half, 2 half)
+ *             the capacities distribute-evenly needs for passes >= 2); n_cand * half for the zone-aware ones (region c = view
+ *             c's placement as slot + 1: the finish step computes every zone's average efficiency from them, chooses, writes
+ *             the results and leaves the winner's node ids in [0, half)).
+ *   reduce_words = the leading words of d_exec2 the all-reduce must sum: half (tightly-pack), 2 * half (distribute-evenly),
+ *             n_cand * half (zone-aware). */
 typedef struct gf_shard_partial {
     int64_t cap_sum;   /* sum over the range of min(capacity, K) with nothing reserved; may stop early once >= 2K */
     int64_t fit_count; /* nodes of the range with capacity >= 1 (distribute-evenly pass 1); same early stop */
@@ -444,15 +457,21 @@ int gf_shard_partials_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_a
 int gf_shard_drivers_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app *d_apps,
                          const gf_shard_partial *d_all_partials /* [n_shards][n_apps] */, gf_shard_driver *d_out,
                          void *stream);
-/* d_exec2: 2 * half uint32 (half >= sum of k); zeroed here; [0, half) receives this shard's slice of the placements as
- * node index + 1, [half, 2 * half) the capacities distribute-evenly needs for passes >= 2. */
+/* d_exec2: exec2_words uint32 (gf_shard_layout; half >= sum of k); zeroed here; receives this shard's slice of the
+ * placements (see the layout above).  d_results: written here for the plain packers, by gf_shard_finish_dev for the zone-aware ones. */
 int gf_shard_emit_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app *d_apps,
                       const gf_shard_partial *d_all_partials, const gf_shard_driver *d_all_drivers /* [n_shards][n_apps] */,
                       gf_result *d_results, uint32_t *d_exec2, uint64_t half, void *stream);
-/* after the all-reduce: d_exec2[0, half) becomes the concatenated ExecutorNodes of gf_fit_batch_dev */
+/* after the all-reduce: d_exec2[0, half) becomes the concatenated ExecutorNodes of gf_fit_batch_dev (zone-aware packers: and
+ * d_results the results) */
 int gf_shard_finish_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app *d_apps,
                         const gf_shard_partial *d_all_partials, const gf_shard_driver *d_all_drivers,
-                        const gf_result *d_results, uint32_t *d_exec2, uint64_t half, void *stream);
+                        gf_result *d_results, uint32_t *d_exec2, uint64_t half, void *stream);
+/* The layout above for one batch (half = sum of k + 1) of `algo` on this context's installed snapshot, zones and orders: so
+ * that a caller sizes its buffers without knowing how a packer works inside.  Any out pointer may be NULL.  Returns what the
+ * shard steps would: GF_ERR_UNSUPPORTED for a packer or layout they do not serve. */
+int gf_shard_layout(gf_ctx *ctx, gf_algo algo, uint64_t half, uint32_t *records_per_app, uint64_t *exec2_words,
+                    uint64_t *reduce_words);
 
 /* Working copy of the available table after the last GF_MODE_FIFO_CHAIN call (n_nodes x 3, row-major) — lets tests
  * compare the replayed residuals with availableNodesSchedulingMetadata after fitEarlierDrivers. */

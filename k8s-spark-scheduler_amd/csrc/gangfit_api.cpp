@@ -63,6 +63,8 @@ int view_refresh(gf_ctx* v) {
     v->d_sched.alias(p->d_sched);
     v->d_node_tab.alias(p->d_node_tab);
     v->d_zmasks.alias(p->d_zmasks);
+    v->zspan_ok = p->zspan_ok;
+    if (p->zspan_ok) v->d_zspan.alias(p->d_zspan);
     // the working copies are the view's own
     if (v->have_orders) {
         GF_HIP(v, v->d_work.reserve(3 * (size_t)v->n_slots));
@@ -291,6 +293,7 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->d_sched.release();
     ctx->d_node_tab.release();
     ctx->d_zmasks.release();
+    ctx->d_zspan.release();
     ctx->h_zmasks.release();
     ctx->d_zres.release();
     ctx->d_zexec.release();
@@ -388,19 +391,19 @@ int gf_set_option(gf_ctx* ctx, const char* key, int64_t value) {
         }
         if (gk == "group_fault") {
             ctx->g_fault = (int)value;
-            ctx->g_verified_epoch = 0;
+            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = 0;
             return GF_OK;
         }
         if (gk == "group_shard_off") {  // read-back for tests: 1 sets, 0 clears (and re-arms the self-check)
             ctx->g_shard_off = value != 0;
-            ctx->g_verified_epoch = 0;
+            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = 0;
             return GF_OK;
         }
         if (gk == "group_exchange") {
             for (void* c : ctx->g_comms)
                 if (c) (void)rccl().CommDestroy(c);
             ctx->g_comms.clear();
-            ctx->g_verified_epoch = 0;  // the other exchange proves itself on its first batch
+            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = 0;  // the other exchange proves itself on its first batch
             if (value == 0) return GF_OK;
             if (ctx->g_total_shards != ctx->group.size())
                 return fail(ctx, GF_ERR_UNSUPPORTED, "a device hosts several shards: the RCCL exchange wants one rank per physical device");

@@ -6,13 +6,30 @@ using namespace gfapi;
 
 namespace gfapi {
 
+bool is_shard_zone_algo(gf_algo algo) { return algo == GF_ALGO_SINGLE_AZ_TIGHTLY_PACK || algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK; }
+
+// candidate views of a zone-aware batch: the zones of the evaluation list, plus the plain order for az-aware
+static uint32_t shard_views(const gf_ctx* ctx, gf_algo algo) {
+    return is_shard_zone_algo(algo) ? ctx->n_zones + (algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u) : 1u;
+}
+
 int shard_ready(gf_ctx* ctx, gf_algo algo, gangfit::ShardRange* r) {
     if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a sharded fit");
     if (!ctx->merged)
         return fail(ctx, GF_ERR_UNSUPPORTED, "node-range sharding needs the merged slot layout (driver and executor "
                                              "orders must be subsequences of one priority order)");
-    if (algo != GF_ALGO_TIGHTLY_PACK && algo != GF_ALGO_DISTRIBUTE_EVENLY)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "node-range sharding serves tightly-pack and distribute-evenly only");
+    if (algo != GF_ALGO_TIGHTLY_PACK && algo != GF_ALGO_DISTRIBUTE_EVENLY && !is_shard_zone_algo(algo))
+        return fail(ctx, GF_ERR_UNSUPPORTED, "node-range sharding serves tightly-pack, distribute-evenly, single-az-tightly-pack "
+                                             "and az-aware-tightly-pack only");
+    if (is_shard_zone_algo(algo)) {
+        if (!ctx->have_sched)
+            return fail(ctx, GF_ERR_UNSUPPORTED, "zone-aware packers compare packing efficiencies: node-range sharding needs the "
+                                                 "schedulable columns of gf_snapshot_set");
+        const uint32_t n_cand = shard_views(ctx, algo);
+        if (n_cand == 0 || n_cand > 64)
+            return fail(ctx, GF_ERR_UNSUPPORTED, "node-range sharding of a zone-aware packer needs 1 to 64 candidate views (zones of "
+                                                 "the evaluation list, plus one for az-aware), not %u", n_cand);
+    }
     const uint64_t xc = ((uint64_t)ctx->n_x + 63) / 64;  // chunks of the merged order (the sentinel slot hosts nothing)
     r->c_lo = (uint32_t)(xc * ctx->shard / ctx->n_shards);
     r->c_hi = (uint32_t)(xc * (ctx->shard + 1) / ctx->n_shards);
@@ -30,6 +47,32 @@ int shard_ready(gf_ctx* ctx, gf_algo algo, gangfit::ShardRange* r) {
 // (a context without the prefix table — a view — takes the full order)
 static gangfit::SparseTable shard_sparse(gf_ctx* ctx) {
     return (ctx->n_g != 0 && !ctx->g_prefix.empty()) ? make_sparse(ctx) : gangfit::SparseTable{};
+}
+// the candidate views of a zone-aware packer (after shard_ready); nullptr for the plain packers
+static const gangfit::ShardZones* shard_zones(gf_ctx* ctx, gf_algo algo, gangfit::ShardZones* z) {
+    if (!is_shard_zone_algo(algo)) return nullptr;
+    z->xmask = ctx->d_zmasks.ptr;
+    z->dmask = ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride;
+    z->span = ctx->zspan_ok ? ctx->d_zspan.ptr : nullptr;
+    z->sched = ctx->d_sched.ptr;
+    z->n_zones = ctx->n_zones;
+    z->stride = ctx->zstride;
+    z->n_cand = shard_views(ctx, algo);
+    z->az_aware = algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u;
+    return z;
+}
+// What a batch's buffers hold (gf_shard_layout): records per application and view, placement buffer words, words to reduce
+struct ShardLayout {
+    uint32_t records;
+    uint64_t exec2_words, reduce_words;
+};
+static ShardLayout shard_layout_of(const gf_ctx* ctx, gf_algo algo, uint64_t half) {
+    if (is_shard_zone_algo(algo)) {
+        const uint32_t v = shard_views(ctx, algo);
+        return ShardLayout{v, (uint64_t)v * half, (uint64_t)v * half};  // region c: view c's placement (slot + 1)
+    }
+    // [0, half) the placements, [half, 2 half) the capacities of distribute-evenly's pass 1
+    return ShardLayout{1u, 2 * half, algo == GF_ALGO_DISTRIBUTE_EVENLY ? 2 * half : half};
 }
 
 // ---- the submitting threads (GroupPool, gangfit_ctx.h)
@@ -86,11 +129,12 @@ void GroupPool::barrier() {
     }
 }
 
-// gf_fit_batch on a multi-device context.  Independent batches of the two plain packers are node-range sharded across the
-// sub-contexts (the four steps of gangfit_shard.inc with the three exchanges done by peer access — the
-// producing kernels write straight into every device's gathered table, shard_reduce_pull_kernel collects the placements — or
-// by RCCL); everything else — FIFO chains (each commit must be visible to the next scan), the zone-aware and
-// minimal-fragmentation packers, orders that do not merge — runs on the first device.
+// gf_fit_batch on a multi-device context.  Independent batches of the two plain packers and of the zone-aware tightly-pack
+// packers are node-range sharded across the sub-contexts (the four steps of gangfit_shard.inc with the
+// three exchanges done by peer access — the producing kernels write straight into every device's gathered table,
+// shard_reduce_pull_kernel collects the placements — or by RCCL); everything else — FIFO chains (each commit must be visible to
+// the next scan), the minimal-fragmentation packers, orders that do not merge, zone-aware batches without the schedulable
+// columns or with more than 64 candidate views — runs on the first device.
 //
 // One sub-context = one DEVICE and the shards it hosts: per step ONE launch per device (a grid row per hosted shard), one
 // upload of the records, one gathered table and one placement buffer per device.  With several devices device d's calls are
@@ -100,9 +144,13 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
                     uint32_t* exec_nodes, uint64_t exec_nodes_cap, int32_t* chain_failed_at) {
     std::lock_guard<std::recursive_mutex> glock(g->mu);
     gf_ctx* const first = g->group[0];
-    bool sharded = mode == GF_MODE_INDEPENDENT && (algo == GF_ALGO_TIGHTLY_PACK || algo == GF_ALGO_DISTRIBUTE_EVENLY) && n_apps > 0 &&
-                   !g->g_shard_off;
-    for (gf_ctx* s : g->group) sharded = sharded && s->have_orders && s->merged;
+    const bool zoned = is_shard_zone_algo(algo);
+    bool sharded = mode == GF_MODE_INDEPENDENT && (algo == GF_ALGO_TIGHTLY_PACK || algo == GF_ALGO_DISTRIBUTE_EVENLY || zoned) &&
+                   n_apps > 0 && !g->g_shard_off;
+    for (gf_ctx* s : g->group) {
+        sharded = sharded && s->have_orders && s->merged;
+        if (zoned) sharded = sharded && s->have_sched && shard_views(s, algo) >= 1 && shard_views(s, algo) <= 64;
+    }
     if (!sharded) {
         const int rc = gf_fit_batch(first, mode, algo, n_apps, apps, results, exec_nodes, exec_nodes_cap, chain_failed_at);
         if (rc != GF_OK) g->err = first->err;
@@ -130,13 +178,17 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         return fail(g, GF_ERR_CAPACITY, "exec_nodes holds %llu entries, %llu needed", (unsigned long long)exec_nodes_cap,
                     (unsigned long long)total_k);
     const uint64_t half = total_k + 1;
-    // what the reduce of the placement buffers carries: its second half (the capacities of pass 1's nodes) is distribute-evenly's
-    const size_t reduce_words = (size_t)(algo == GF_ALGO_DISTRIBUTE_EVENLY ? 2 * half : half);
+    // records per application and view, the placement buffer and what the reduce of it carries (shard_layout_of)
+    const ShardLayout lay = shard_layout_of(first, algo, half);
+    const uint32_t rec = lay.records;
+    const size_t reduce_words = (size_t)lay.reduce_words;
     GF_HIP(g, g->h_results.reserve(n_apps));
     GF_HIP(g, g->h_exec.reserve(total_k + 1));
     // ---- buffers on every device (growth only: no-ops from the second batch of a size on) and what each device's kernels
     //      must know about the others: every gathered table, every placement buffer
     gangfit::ShardSet set[gangfit::kMaxGroupDevices];
+    gangfit::ShardZones zones[gangfit::kMaxGroupDevices];
+    const gangfit::ShardZones* zv[gangfit::kMaxGroupDevices] = {};
     gangfit::PeerPtrs part_all{}, drv_all{}, exec_others{};
     for (uint32_t d = 0; d < D; ++d) {
         gf_ctx* c = g->group[d];
@@ -158,13 +210,14 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
             set[d].g_lo[q] = r.g_lo;
             set[d].g_hi[q] = r.g_hi;
         }
+        zv[d] = shard_zones(c, algo, &zones[d]);
         GF_HIP(g, c->d_apps.reserve(n_apps));
         GF_HIP(g, c->d_results.reserve(n_apps));
-        GF_HIP(g, c->g_part_loc.reserve((size_t)c->my_shards.size() * n_apps));
-        GF_HIP(g, c->g_drv_loc.reserve((size_t)c->my_shards.size() * n_apps));
-        GF_HIP(g, c->g_part_all.reserve((size_t)S * n_apps));
-        GF_HIP(g, c->g_drv_all.reserve((size_t)S * n_apps));
-        GF_HIP(g, c->g_exec2.reserve(2 * half));
+        GF_HIP(g, c->g_part_loc.reserve((size_t)c->my_shards.size() * rec * n_apps));
+        GF_HIP(g, c->g_drv_loc.reserve((size_t)c->my_shards.size() * rec * n_apps));
+        GF_HIP(g, c->g_part_all.reserve((size_t)S * rec * n_apps));
+        GF_HIP(g, c->g_drv_all.reserve((size_t)S * rec * n_apps));
+        GF_HIP(g, c->g_exec2.reserve(lay.exec2_words));
         part_all.p[d] = c->g_part_all.ptr;
         drv_all.p[d] = c->g_drv_all.ptr;
         if (d > 0) exec_others.p[exec_others.n++] = c->g_exec2.ptr;
@@ -185,15 +238,15 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         if (!GF_STEP(d, hipSetDevice(c->device))) return;
         if (!GF_STEP(d, hipMemcpyAsync(c->d_apps.ptr, g->h_apps.ptr, (size_t)n_apps * sizeof(gf_app), hipMemcpyHostToDevice, c->stream))) return;
         if (!GF_STEP(d, gangfit::launch_shard_partials(algo, make_table(c, c->d_snap.ptr), shard_sparse(c), set[d], n_apps, c->d_apps.ptr, c->g_part_loc.ptr,
-                                                       use_rccl ? no_peers : part_all, c->stream)))
+                                                       use_rccl ? no_peers : part_all, c->stream, zv[d])))
             return;
         if (g->g_fault == 2 && d > 0 && !use_rccl) {  // fault injection: this device's capacity sums arrive as zeros everywhere
             for (uint32_t t = 0; t < D; ++t)
                 for (uint32_t sh : c->my_shards)
-                    (void)GF_STEP(d, hipMemsetAsync(static_cast<gf_shard_partial*>(part_all.p[t]) + (size_t)sh * n_apps, 0,
-                                                   (size_t)n_apps * sizeof(gf_shard_partial), c->stream));
+                    (void)GF_STEP(d, hipMemsetAsync(static_cast<gf_shard_partial*>(part_all.p[t]) + (size_t)sh * rec * n_apps, 0,
+                                                   (size_t)rec * n_apps * sizeof(gf_shard_partial), c->stream));
         } else if (g->g_fault == 2 && d > 0) {
-            (void)GF_STEP(d, hipMemsetAsync(c->g_part_loc.ptr, 0, (size_t)n_apps * sizeof(gf_shard_partial), c->stream));
+            (void)GF_STEP(d, hipMemsetAsync(c->g_part_loc.ptr, 0, (size_t)rec * n_apps * sizeof(gf_shard_partial), c->stream));
         }
         if (D > 1 && !use_rccl) (void)GF_STEP(d, hipEventRecord(c->g_ev[0], c->stream));
     };
@@ -207,7 +260,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         if (rc_of[d] != GF_OK || !GF_STEP(d, hipSetDevice(c->device))) return;
         if (D > 1 && !use_rccl) wait_others(d, 0);
         if (!GF_STEP(d, gangfit::launch_shard_drivers(make_table(c, c->d_snap.ptr), set[d], n_apps, c->d_apps.ptr, c->g_part_all.ptr,
-                                                      c->g_drv_loc.ptr, use_rccl ? no_peers : drv_all, c->stream)))
+                                                      c->g_drv_loc.ptr, use_rccl ? no_peers : drv_all, c->stream, zv[d])))
             return;
         if (D > 1 && !use_rccl) (void)GF_STEP(d, hipEventRecord(c->g_ev[1], c->stream));
     };
@@ -216,7 +269,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         if (rc_of[d] != GF_OK || !GF_STEP(d, hipSetDevice(c->device))) return;
         if (D > 1 && !use_rccl) wait_others(d, 1);
         if (!GF_STEP(d, gangfit::launch_shard_emit(algo, make_table(c, c->d_snap.ptr), shard_sparse(c), set[d], n_apps, c->d_apps.ptr, c->g_part_all.ptr,
-                                                   c->g_drv_all.ptr, c->d_results.ptr, c->g_exec2.ptr, half, c->stream)))
+                                                   c->g_drv_all.ptr, c->d_results.ptr, c->g_exec2.ptr, half, c->stream, zv[d])))
             return;
         if (D > 1) (void)GF_STEP(d, hipEventRecord(c->g_ev[2], c->stream));
     };
@@ -228,8 +281,9 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
             if (g->g_fault != 1 && D > 1)  // fault injection: the other devices' placement slices never arrive
                 if (!GF_STEP(0, gangfit::launch_shard_reduce_pull(exec_others, first->g_exec2.ptr, reduce_words, first->stream))) return;
         }
+        const gangfit::NodeTable ft = make_table(first, first->d_snap.ptr);
         if (!GF_STEP(0, gangfit::launch_shard_finish(algo, S, n_apps, first->d_apps.ptr, first->g_part_all.ptr, first->g_drv_all.ptr,
-                                                     first->d_results.ptr, first->g_exec2.ptr, half, first->stream)))
+                                                     first->d_results.ptr, first->g_exec2.ptr, half, first->stream, &ft, zv[0])))
             return;
         if (!GF_STEP(0, hipMemcpyAsync(g->h_results.ptr, first->d_results.ptr, (size_t)n_apps * sizeof(gf_result), hipMemcpyDeviceToHost, first->stream))) return;
         if (total_k && !GF_STEP(0, hipMemcpyAsync(g->h_exec.ptr, first->g_exec2.ptr, (size_t)total_k * sizeof(uint32_t), hipMemcpyDeviceToHost, first->stream))) return;
@@ -267,11 +321,11 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         };
         for (uint32_t d = 0; d < D; ++d) step_partials(d);
         if (rccl_all_gather([](gf_ctx* c) { return (const void*)c->g_part_loc.ptr; }, [](gf_ctx* c) { return (void*)c->g_part_all.ptr; },
-                            (size_t)n_apps * sizeof(gf_shard_partial)) != 0)
+                            (size_t)rec * n_apps * sizeof(gf_shard_partial)) != 0)
             return fail_drained("ncclAllGather of the capacity sums failed");
         for (uint32_t d = 0; d < D; ++d) step_drivers(d);
         if (rccl_all_gather([](gf_ctx* c) { return (const void*)c->g_drv_loc.ptr; }, [](gf_ctx* c) { return (void*)c->g_drv_all.ptr; },
-                            (size_t)n_apps * sizeof(gf_shard_driver)) != 0)
+                            (size_t)rec * n_apps * sizeof(gf_shard_driver)) != 0)
             return fail_drained("ncclAllGather of the driver records failed");
         for (uint32_t d = 0; d < D; ++d) step_emit(d);
         // the reduction north_star names: sum of the placement slices onto the first device, over xGMI
@@ -312,10 +366,12 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         }
     std::memcpy(results, g->h_results.ptr, (size_t)n_apps * sizeof(gf_result));
     if (total_k) std::memcpy(exec_nodes, g->h_exec.ptr, (size_t)total_k * sizeof(uint32_t));
-    // ---- self-check: the first sharded batch on every newly installed snapshot is also answered by the first device alone.
-    //      A wrong exchange (peer stores that did not land, a collective that reduced something else) must not decide a
-    //      Filter: on a mismatch the context stops sharding, says why, and serves the first device's answer.
-    if (g->g_verify && first->snap_epoch != g->g_verified_epoch) {
+    // ---- self-check: the first sharded batch of each packer family (plain, zone-aware) on every newly installed snapshot is
+    //      also answered by the first device alone.  A wrong exchange (peer stores that did not land, a collective that reduced
+    //      something else) must not decide a Filter: on a mismatch the context stops sharding, says why, and serves the first
+    //      device's answer.
+    uint64_t& verified = g->g_verified_epoch[zoned ? 1 : 0];
+    if (g->g_verify && first->snap_epoch != verified) {
         std::vector<gf_result> ref_res(n_apps);
         std::vector<uint32_t> ref_exec((size_t)total_k + 1);
         const int rc = gf_fit_batch(first, mode, algo, n_apps, apps, ref_res.data(), ref_exec.data(), total_k, nullptr);
@@ -329,7 +385,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
                 same = std::memcmp(ref_exec.data() + g->h_apps.ptr[a].exec_off, exec_nodes + g->h_apps.ptr[a].exec_off,
                                    (size_t)ref_res[a].exec_len * sizeof(uint32_t)) == 0;
         if (same) {
-            g->g_verified_epoch = first->snap_epoch;
+            verified = first->snap_epoch;
         } else {
             g->g_shard_off = true;
             g->err = "the node-range sharded batch disagreed with the first device's own answer: sharding is off for this context";
@@ -367,8 +423,9 @@ int gf_shard_partials_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_a
     const int rc = shard_ready(ctx, algo, &r);
     if (rc != GF_OK) return rc;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    gangfit::ShardZones z{};
     GF_HIP(ctx, gangfit::launch_shard_partials(algo, make_table(ctx, ctx->d_snap.ptr), shard_sparse(ctx), gangfit::shard_set_of(r), n_apps, d_apps, d_out,
-                                               gangfit::PeerPtrs{}, st));
+                                               gangfit::PeerPtrs{}, st, shard_zones(ctx, algo, &z)));
     return GF_OK;
 }
 
@@ -383,8 +440,9 @@ int gf_shard_drivers_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_ap
     const int rc = shard_ready(ctx, algo, &r);
     if (rc != GF_OK) return rc;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    gangfit::ShardZones z{};
     GF_HIP(ctx, gangfit::launch_shard_drivers(make_table(ctx, ctx->d_snap.ptr), gangfit::shard_set_of(r), n_apps, d_apps, d_all_partials,
-                                              d_out, gangfit::PeerPtrs{}, st));
+                                              d_out, gangfit::PeerPtrs{}, st, shard_zones(ctx, algo, &z)));
     return GF_OK;
 }
 
@@ -400,14 +458,15 @@ int gf_shard_emit_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* 
     const int rc = shard_ready(ctx, algo, &r);
     if (rc != GF_OK) return rc;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    gangfit::ShardZones z{};
     GF_HIP(ctx, gangfit::launch_shard_emit(algo, make_table(ctx, ctx->d_snap.ptr), shard_sparse(ctx), gangfit::shard_set_of(r), n_apps, d_apps, d_all_partials,
-                                           d_all_drivers, d_results, d_exec2, half, st));
+                                           d_all_drivers, d_results, d_exec2, half, st, shard_zones(ctx, algo, &z)));
     return GF_OK;
 }
 
 int gf_shard_finish_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps,
                         const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
-                        const gf_result* d_results, uint32_t* d_exec2, uint64_t half, void* stream) {
+                        gf_result* d_results, uint32_t* d_exec2, uint64_t half, void* stream) {
     if (ctx != nullptr && !ctx->group.empty())
         return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
     if (!ctx) return GF_ERR_INVALID;
@@ -417,8 +476,27 @@ int gf_shard_finish_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app
     const int rc = shard_ready(ctx, algo, &r);
     if (rc != GF_OK) return rc;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    gangfit::ShardZones z{};
+    const gangfit::NodeTable t = make_table(ctx, ctx->d_snap.ptr);
     GF_HIP(ctx, gangfit::launch_shard_finish(algo, ctx->n_shards, n_apps, d_apps, d_all_partials, d_all_drivers,
-                                             d_results, d_exec2, half, st));
+                                             d_results, d_exec2, half, st, &t, shard_zones(ctx, algo, &z)));
+    return GF_OK;
+}
+
+int gf_shard_layout(gf_ctx* ctx, gf_algo algo, uint64_t half, uint32_t* records_per_app, uint64_t* exec2_words,
+                    uint64_t* reduce_words) {
+    if (ctx != nullptr && !ctx->group.empty())
+        return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
+    if (!ctx) return GF_ERR_INVALID;
+    if (half == 0) return fail(ctx, GF_ERR_INVALID, "half must be at least 1 (sum of k + 1)");
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    gangfit::ShardRange r{};
+    const int rc = shard_ready(ctx, algo, &r);
+    if (rc != GF_OK) return rc;
+    const ShardLayout lay = shard_layout_of(ctx, algo, half);
+    if (records_per_app) *records_per_app = lay.records;
+    if (exec2_words) *exec2_words = lay.exec2_words;
+    if (reduce_words) *reduce_words = lay.reduce_words;
     return GF_OK;
 }
 

@@ -441,6 +441,18 @@ int gf_orders_set(gf_ctx* ctx, const uint32_t* driver_order, uint32_t n_d, const
         ctx->n_zones = nz;
         ctx->zstride = zstride;
         ctx->zd_row0 = nz;
+        // each zone's chunk span on the merged order (node-range shards skip the zones outside their range: gangfit_shard.inc)
+        std::vector<uint32_t> span(4 * (size_t)nz + 4, 0);
+        for (uint32_t zi = 0; zi < nz && mergeable; ++zi) {
+            uint32_t lo = n_chunks, hi = 0;
+            for (uint32_t c = 0; c < n_chunks; ++c)
+                if (zx[(size_t)zi * zstride + c] | zd[(size_t)zi * zstride + c]) {
+                    lo = c < lo ? c : lo;
+                    hi = c + 1;
+                }
+            span[4 * (size_t)zi] = lo < hi ? lo : 0;
+            span[4 * (size_t)zi + 1] = hi;
+        }
         if (ctx->n_g != 0) {  // SparseTable::xmask (row 0: every sub-slot) and ::zmask (row 1 + zi: the sub-slots of zone eval[zi])
             const uint32_t gch = ctx->n_gpad / 64u;
             const uint32_t* gnode = ctx->h_gidx.ptr;
@@ -451,9 +463,26 @@ int gf_orders_set(gf_ctx* ctx, const uint32_t* driver_order, uint32_t n_d, const
                 for (uint32_t zi = 0; zi < nz; ++zi)
                     if (eval[zi] == z) gm[(size_t)gch * (1u + zi) + (i >> 6)] |= 1ull << (i & 63);
             }
+            for (uint32_t zi = 0; zi < nz; ++zi) {  // ... and its span on the compact gpu table
+                uint32_t lo = gch, hi = 0;
+                for (uint32_t c = 0; c < gch; ++c)
+                    if (gm[(size_t)gch * (1u + zi) + c]) {
+                        lo = c < lo ? c : lo;
+                        hi = c + 1;
+                    }
+                span[4 * (size_t)zi + 2] = lo < hi ? lo : 0;
+                span[4 * (size_t)zi + 3] = hi;
+            }
             GF_HIP(ctx, ctx->d_gmask.reserve(gm.size()));
             GF_HIP(ctx, hipMemcpyAsync(ctx->d_gmask.ptr, gm.data(), gm.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
             GF_HIP(ctx, gf_wait_stream(ctx->stream));  // gm is a local
+        }
+        ctx->zspan_ok = false;
+        if (mergeable && nz) {
+            GF_HIP(ctx, ctx->d_zspan.reserve(span.size()));
+            GF_HIP(ctx, hipMemcpyAsync(ctx->d_zspan.ptr, span.data(), span.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+            GF_HIP(ctx, gf_wait_stream(ctx->stream));  // span is a local
+            ctx->zspan_ok = true;
         }
     }
     GF_HIP(ctx, gf_wait_stream(ctx->stream));
@@ -874,6 +903,7 @@ int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_
         ctx->n_zones = nz;
         ctx->zstride = n_chunks;
         ctx->zd_row0 = n_zones;
+        ctx->zspan_ok = false;  // (the zone masks were built on the device: the shards scan every zone over their whole range)
         ctx->have_orders = true;
         ctx->work_valid = false;
         ++ctx->snap_epoch;

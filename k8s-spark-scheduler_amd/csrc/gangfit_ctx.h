@@ -330,6 +330,11 @@ struct gf_ctx {
     PinnedBuf<uint64_t> h_zmasks;
     uint32_t n_zones = 0, zstride = 0;
     uint32_t zd_row0 = 0;              // row of d_zmasks where the driver masks start (n_zones, or the zone count of a device build)
+    // [n_zones][4] the chunks [lo, hi) of the merged order holding each zone's candidates, then the chunks [lo, hi) of the compact gpu
+    // table holding its sub-slots: where a node-range shard may skip a zone (gangfit_shard.inc).  Built by gf_orders_set on the merged
+    // layout; zspan_ok = false (a snapshot built on the device): every zone spans the whole order
+    DeviceBuf<uint32_t> d_zspan;
+    bool zspan_ok = false;
     bool host_stale = false;           // the host mirrors (avail / sched / h_node_slot) still sit on the device (gf_snapshot_build)
     // every node's available quantities lie at or below its schedulable ones in the snapshot on the device (gf_snapshot_set checked the
     // host arrays; a snapshot built on the device leaves it false): then every term of an average packing efficiency is >= 0
@@ -384,7 +389,9 @@ struct gf_ctx {
     DeviceBuf<uint32_t> g_exec2;                         // 2 * half: placements (node + 1) | capacities
     hipEvent_t g_ev[3] = {nullptr, nullptr, nullptr};    // behind partials+push | drivers+push | emit
     // ... and these in the routing object
-    uint64_t g_verified_epoch = 0;  // snapshot epoch whose first sharded batch agreed with the first device's own answer
+    // snapshot epoch whose first sharded batch agreed with the first device's own answer, per packer family: [0] the plain packers,
+    // [1] the zone-aware ones (their steps differ, so each family proves itself on its first batch of a snapshot)
+    uint64_t g_verified_epoch[2] = {0, 0};
     bool g_verify = true;           // option "group_verify"
     bool g_shard_off = false;       // a sharded batch disagreed: every batch is served by the first device from then on
     int g_fault = 0;                // option "group_fault" (tests): 1 = the placement reduction is skipped, 2 = zeroed capacity sums
@@ -541,6 +548,7 @@ int view_refresh(gf_ctx* v);
 
 // ---- what the translation units offer each other
 // gangfit_api_group.cpp
+bool is_shard_zone_algo(gf_algo algo);  // single-az-tightly-pack, az-aware-tightly-pack: node-range sharded by candidate views
 int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, const gf_app* apps, gf_result* results,
                     uint32_t* exec_nodes, uint64_t exec_nodes_cap, int32_t* chain_failed_at);
 // gangfit_api_fit.cpp

@@ -382,21 +382,39 @@ struct PeerPtrs {
     void* p[kMaxGroupDevices];
     uint32_t n;
 };
-// gpu_view (n_x == 0: none): gangs whose executors need a gpu are summed / emitted from the range's part of the compact table
+// The candidate views of the zone-aware tightly-pack packers on the shard steps (single-az-tightly-pack, az-aware-tightly-pack):
+// views [0, n_zones) are the zones of the evaluation list (ZoneTable's masks, the compact gpu table's SparseTable::zmask rows),
+// view n_zones — az-aware only — the plain order.  A step runs per (application, view); records are laid out
+// [n_shards][n_cand][n_apps], and view c's placement is region c of the placement buffer (c * half words in).
+struct ShardZones {
+    const uint64_t* xmask;  // [n_zones][stride] executor-candidate bits by slot
+    const uint64_t* dmask;  // [n_zones][stride] driver-candidate bits by slot (merged layout)
+    const uint32_t* span;   // [n_zones][4]: the 64-slot chunks [lo, hi) of the order that hold the zone's candidates, then the
+                            // chunks [lo, hi) of the compact gpu table that hold its sub-slots; nullptr: every zone spans everything
+    const int64_t* sched;   // [3][n_slots] SchedulableResources in slot order (the averages chooseBestResult compares)
+    uint32_t n_zones, stride;
+    uint32_t n_cand;        // n_zones (+ 1 for az-aware); 1 <= n_cand <= 64
+    uint32_t az_aware;
+};
+// gpu_view (n_x == 0: none): gangs whose executors need a gpu are summed / emitted from the range's part of the compact table.
+// zones == nullptr: the plain packers (one record per application); otherwise the zone-aware ones (algo is then ignored).
 hipError_t launch_shard_partials(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
                                  uint32_t n_apps, const gf_app* d_apps, gf_shard_partial* d_out, const PeerPtrs& dsts,
-                                 hipStream_t stream);
+                                 hipStream_t stream, const ShardZones* zones = nullptr);
 hipError_t launch_shard_drivers(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
                                 const gf_shard_partial* d_all_partials, gf_shard_driver* d_out, const PeerPtrs& dsts,
-                                hipStream_t stream);
-// (zeroes d_exec2 first; every hosted shard writes its slice of the ONE buffer, row 0 also the results)
+                                hipStream_t stream, const ShardZones* zones = nullptr);
+// (zeroes d_exec2 first — 2 * half words, n_cand * half for the zone-aware packers; every hosted shard writes its slice of the ONE
+// buffer, row 0 also the results of the plain packers: the zone-aware ones leave every choice to the finish step)
 hipError_t launch_shard_emit(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
                              uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
                              const gf_shard_driver* d_all_drivers, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
-                             hipStream_t stream);
+                             hipStream_t stream, const ShardZones* zones = nullptr);
+// (zone-aware packers: d_results is written here, from the table's slot_node / columns and zones->sched)
 hipError_t launch_shard_finish(gf_algo algo, uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps,
                                const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
-                               const gf_result* d_results, uint32_t* d_exec2, uint64_t half, hipStream_t stream);
+                               gf_result* d_results, uint32_t* d_exec2, uint64_t half, hipStream_t stream,
+                               const NodeTable* table = nullptr, const ShardZones* zones = nullptr);
 // d_dst[i] += sum over srcs of src[i], n uint32 entries (only the first device finishes a batch: the all-reduce is a reduce)
 hipError_t launch_shard_reduce_pull(const PeerPtrs& srcs, uint32_t* d_dst, size_t n, hipStream_t stream);
 

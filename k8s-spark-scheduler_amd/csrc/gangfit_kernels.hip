@@ -2277,12 +2277,22 @@ inline dim3 app_grid(uint32_t n_apps) { return dim3((n_apps + kWavesPerBlock - 1
 
 inline dim3 shard_grid(uint32_t n_apps, const ShardSet& set) { return dim3((n_apps + kWavesPerBlock - 1) / kWavesPerBlock, set.n); }
 
+// (zone-aware views: grid z = candidate view)
+inline dim3 shard_grid(uint32_t n_apps, const ShardSet& set, const ShardZones& z) {
+    return dim3((n_apps + kWavesPerBlock - 1) / kWavesPerBlock, set.n, z.n_cand);
+}
+inline bool shard_zones_ok(const ShardZones* z) { return z->n_cand >= 1 && z->n_cand <= 64 && z->n_zones + (z->az_aware ? 1u : 0u) == z->n_cand; }
+
 hipError_t launch_shard_partials(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
                                  uint32_t n_apps, const gf_app* d_apps, gf_shard_partial* d_out, const PeerPtrs& dsts,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, const ShardZones* zones) {
     if (n_apps == 0 || set.n == 0) return hipSuccess;
     const dim3 block(kWave * kWavesPerBlock);
-    if (algo == GF_ALGO_TIGHTLY_PACK)
+    if (zones != nullptr) {
+        if (!shard_zones_ok(zones)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(shard_partials_zoned_kernel, shard_grid(n_apps, set, *zones), block, 0, stream, table, gpu_view, set, *zones,
+                           n_apps, d_apps, d_out, dsts);
+    } else if (algo == GF_ALGO_TIGHTLY_PACK)
         hipLaunchKernelGGL(shard_partials_kernel<GF_ALGO_TIGHTLY_PACK>, shard_grid(n_apps, set), block, 0, stream, table, gpu_view,
                            set, n_apps, d_apps, d_out, dsts);
     else
@@ -2293,22 +2303,32 @@ hipError_t launch_shard_partials(gf_algo algo, const NodeTable& table, const Spa
 
 hipError_t launch_shard_drivers(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
                                 const gf_shard_partial* d_all_partials, gf_shard_driver* d_out, const PeerPtrs& dsts,
-                                hipStream_t stream) {
+                                hipStream_t stream, const ShardZones* zones) {
     if (n_apps == 0 || set.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(shard_drivers_kernel, shard_grid(n_apps, set), dim3(kWave * kWavesPerBlock), 0, stream, table, set,
-                       n_apps, d_apps, d_all_partials, d_out, dsts);
+    if (zones != nullptr) {
+        if (!shard_zones_ok(zones)) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(shard_drivers_zoned_kernel, shard_grid(n_apps, set, *zones), dim3(kWave * kWavesPerBlock), 0, stream, table,
+                           set, *zones, n_apps, d_apps, d_all_partials, d_out, dsts);
+    } else {
+        hipLaunchKernelGGL(shard_drivers_kernel, shard_grid(n_apps, set), dim3(kWave * kWavesPerBlock), 0, stream, table, set,
+                           n_apps, d_apps, d_all_partials, d_out, dsts);
+    }
     return hipGetLastError();
 }
 
 hipError_t launch_shard_emit(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
                              uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
                              const gf_shard_driver* d_all_drivers, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
-                             hipStream_t stream) {
+                             hipStream_t stream, const ShardZones* zones) {
     if (n_apps == 0 || set.n == 0) return hipSuccess;
-    hipError_t e = hipMemsetAsync(d_exec2, 0, 2 * half * sizeof(uint32_t), stream);
+    if (zones != nullptr && !shard_zones_ok(zones)) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_exec2, 0, (zones != nullptr ? zones->n_cand : 2u) * half * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     const dim3 block(kWave * kWavesPerBlock);
-    if (algo == GF_ALGO_TIGHTLY_PACK)
+    if (zones != nullptr)
+        hipLaunchKernelGGL(shard_emit_zoned_kernel, shard_grid(n_apps, set, *zones), block, 0, stream, table, gpu_view, set, *zones,
+                           n_apps, d_apps, d_all_partials, d_all_drivers, d_exec2, half);
+    else if (algo == GF_ALGO_TIGHTLY_PACK)
         hipLaunchKernelGGL(shard_emit_kernel<GF_ALGO_TIGHTLY_PACK>, shard_grid(n_apps, set), block, 0, stream, table, gpu_view,
                            set, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
     else
@@ -2319,8 +2339,19 @@ hipError_t launch_shard_emit(gf_algo algo, const NodeTable& table, const SparseT
 
 hipError_t launch_shard_finish(gf_algo algo, uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps,
                                const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
-                               const gf_result* d_results, uint32_t* d_exec2, uint64_t half, hipStream_t stream) {
+                               gf_result* d_results, uint32_t* d_exec2, uint64_t half, hipStream_t stream,
+                               const NodeTable* table, const ShardZones* zones) {
     if (n_apps == 0) return hipSuccess;
+    if (zones != nullptr) {
+        if (table == nullptr || !shard_zones_ok(zones)) return hipErrorInvalidValue;
+        if (zones->az_aware)
+            hipLaunchKernelGGL(shard_finish_zoned_kernel<true>, dim3(n_apps), dim3(kWave * kFusedWaves), 0, stream, *table, *zones,
+                               n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
+        else
+            hipLaunchKernelGGL(shard_finish_zoned_kernel<false>, dim3(n_apps), dim3(kWave * kFusedWaves), 0, stream, *table, *zones,
+                               n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
+        return hipGetLastError();
+    }
     const dim3 block(kWave * kWavesPerBlock);
     if (algo == GF_ALGO_TIGHTLY_PACK)
         hipLaunchKernelGGL(shard_finish_kernel<GF_ALGO_TIGHTLY_PACK>, app_grid(n_apps), block, 0, stream, n_shards, n_apps,

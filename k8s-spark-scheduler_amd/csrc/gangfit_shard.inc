@@ -26,6 +26,16 @@
 //
 // Sums are allowed to stop early once they reach 2K: every later use only needs them exactly below K, and
 // 2K - c0 + c1 >= K keeps the driver test right.  Merged slot layout only (driver position == slot).
+//
+// The zone-aware tightly-pack packers (the *_zoned kernels; single_az.go:23-97, az_aware_pack_tightly.go:27-38): per zone, single-AZ
+// tightly-pack is plain tightly-pack on the zone's candidates, so the same steps run once per (application, candidate view)
+// — grid z = view c of ShardZones: the zones of the evaluation list, plus the plain order for az-aware — with the view's
+// masks and its records at [shard][c][app].  A zone is usually one stretch of the priority order (the reference sorts it
+// AZ-major), so a shard intersects its range with the zone's chunk span first and skips the zone when that is empty.  Emit
+// writes view c's slice of its placement (slot + 1) into region c of the buffer; the choice between the zones needs every
+// zone's average Max packing efficiency, a float64 sum in slice order that shards cannot split, so the finish step
+// (shard_finish_zoned_kernel) computes the averages from the reduced placements — every rank holds the replicated snapshot and
+// schedulable columns — with the device functions of fit_zoned_fused_kernel, chooses and writes the result.
 
 template <bool DRV, class View>
 __device__ __forceinline__ uint64_t range_group_mask(const View& V, uint32_t g, uint32_t c_lo, uint32_t c_hi, int64_t r0,
@@ -67,8 +77,11 @@ struct ShardSums {
 };
 
 // Every rank derives the same global picture from the two gathered tables (wave-uniform scalar loops over shards).
+// (Row: uint32_t n_apps for the plain packers; the zone-aware views pass size_t n_cand * n_apps — records between two shards' rows —
+// with pointers that start at their view's row)
+template <class Row>
 __device__ __forceinline__ ShardSums shard_sums(const gf_shard_partial* __restrict__ all_part,
-                                                const gf_shard_driver* __restrict__ all_drv, uint32_t n_apps, uint32_t a,
+                                                const gf_shard_driver* __restrict__ all_drv, Row n_apps, uint32_t a,
                                                 uint32_t shard, uint32_t n_shards) {
     ShardSums r;
     r.before_cap = r.before_fit = r.total_fit = 0;
@@ -330,6 +343,274 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void shard_finish_kernel(
             any = any || m != 0;
         }
         if (!any) break;  // cannot happen for a feasible app; guards against a non-terminating loop
+    }
+}
+
+// ---- the zone-aware tightly-pack packers (the views of ShardZones; see the top of this file)
+// Candidate view c of a zone-aware batch on grid row q: its masks, and the shard's ranges intersected with the zone's span
+// (chunks of the order in [c_lo, c_hi), sub-slots of the compact gpu table in [g_lo, g_hi)).  The plain view keeps all of them.
+struct ShardView {
+    const uint64_t* xm;
+    const uint64_t* dm;
+    const uint64_t* gxm;
+    uint32_t c_lo, c_hi, g_lo, g_hi;
+};
+__device__ __forceinline__ ShardView shard_view(const NodeTable& T, const SparseTable& G, const ShardSet& SS, const ShardZones& SZ,
+                                                uint32_t q, uint32_t c) {
+    ShardView v{T.xmask, T.dmask, G.xmask, SS.c_lo[q], SS.c_hi[q], SS.g_lo[q], SS.g_hi[q]};
+    if (c < SZ.n_zones) {
+        v.xm = SZ.xmask + (size_t)c * SZ.stride;
+        v.dm = SZ.dmask + (size_t)c * SZ.stride;
+        v.gxm = G.zmask + (size_t)c * G.n_chunks;
+        if (SZ.span != nullptr) {
+            const uint32_t* sp = SZ.span + 4 * (size_t)c;  // (wave-uniform: scalar loads)
+            v.c_lo = v.c_lo > sp[0] ? v.c_lo : sp[0];
+            v.c_hi = v.c_hi < sp[1] ? v.c_hi : sp[1];
+            v.g_lo = v.g_lo > sp[2] * kWave ? v.g_lo : sp[2] * kWave;
+            v.g_hi = v.g_hi < sp[3] * kWave ? v.g_hi : sp[3] * kWave;
+        }
+        if (v.c_hi < v.c_lo) v.c_hi = v.c_lo;  // (an empty range: the scans visit no chunk)
+        if (v.g_hi < v.g_lo) v.g_hi = v.g_lo;
+    }
+    return v;
+}
+
+
+// Partials of view c = blockIdx.z: tightly-pack's capacity sum over the shard's part of the zone (or of the plain order).
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void shard_partials_zoned_kernel(NodeTable T, SparseTable G, ShardSet SS, ShardZones SZ,
+                                                                                    uint32_t n_apps, const gf_app* __restrict__ apps,
+                                                                                    gf_shard_partial* __restrict__ part, PeerPtrs dsts) {
+    const int lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t a = blockIdx.x * kWavesPerBlock + wave;
+    if (a >= n_apps) return;
+    const uint32_t q = blockIdx.y, c = blockIdx.z;
+    const ShardView zv = shard_view(T, G, SS, SZ, q, c);
+    const App app = load_app(apps, a);
+    const int64_t K = app.k;
+    int64_t S = 0;
+    auto visit = [&](const GlobalView& V, uint32_t n_x, uint32_t j, bool in) {
+        int32_t cp = 0;
+        int64_t a0, a1, a2;
+        if (load_with_cand<false>(V, j, n_x, a0, a1, a2) && in) {
+            if (cap_ge1(a0, a1, a2, app)) cp = cap3(a0, a1, a2, app);
+        }
+        S += read_lane(wave_inclusive_scan(cp), kWave - 1);
+        return S < 2 * K;
+    };
+    if (K != 0) {
+        if (G.n_x != 0 && app.exe2 > 0) {  // wave-uniform: the range's part of the view's sub-slots of the compact gpu table
+            GlobalView VS = shard_sparse_view(G);
+            VS.xm = VS.dm = zv.gxm;
+            if (zv.g_lo < zv.g_hi)
+                shard_scan_range(VS, zv.g_lo, zv.g_hi, app.exe0, app.exe1, app.exe2, lane,
+                                 [&](uint32_t j, bool in) { return visit(VS, G.n_x, j, in); });
+        } else if (zv.c_lo < zv.c_hi) {
+            const GlobalView V{T.cpu, T.mem, T.gpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, zv.xm, zv.dm,
+                               T.n_chunks};
+            shard_scan_range(V, zv.c_lo * kWave, zv.c_hi * kWave, app.exe0, app.exe1, app.exe2, lane,
+                             [&](uint32_t j, bool in) { return visit(V, T.n_x, j, in); });
+        }
+    }
+    if (lane == 0) {
+        gf_shard_partial p;
+        p.cap_sum = S;
+        p.fit_count = 0;  // (distribute-evenly's count: not used by tightly-pack)
+        shard_publish(p, dsts, part, q * SZ.n_cand + c, SS.shard[q] * SZ.n_cand + c, n_apps, a);
+    }
+}
+
+// Drivers of view c: the first driver candidate of the shard's part of the zone with fit && S - c0 + c1 >= K.
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void shard_drivers_zoned_kernel(NodeTable T, ShardSet SS, ShardZones SZ,
+                                                                                   uint32_t n_apps, const gf_app* __restrict__ apps,
+                                                                                   const gf_shard_partial* __restrict__ all_part,
+                                                                                   gf_shard_driver* __restrict__ drv_out, PeerPtrs dsts) {
+    const int lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t a = blockIdx.x * kWavesPerBlock + wave;
+    if (a >= n_apps) return;
+    const uint32_t q = blockIdx.y, c = blockIdx.z, n_shards = SS.n_shards;
+    const ShardView zv = shard_view(T, SparseTable{}, SS, SZ, q, c);
+    const App app = load_app(apps, a);
+    const GlobalView V{T.cpu, T.mem, T.gpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, zv.xm, zv.dm, T.n_chunks};
+    const int64_t K = app.k;
+    const size_t row = (size_t)SZ.n_cand * n_apps;
+    int64_t S = 0;
+    for (uint32_t t = 0; t < n_shards; ++t) S += all_part[(size_t)t * row + (size_t)c * n_apps + a].cap_sum;
+    gf_shard_driver out;
+    out.pos = GF_NO_NODE;
+    out.d_cap = 0;
+    out.d_fit = 0;
+    out.reserved = 0;
+    bool found = S < K;  // (as in shard_drivers_kernel: no candidate can pass total >= K)
+    for (uint32_t g = zv.c_lo / kWave; !found && zv.c_lo < zv.c_hi && g * kWave < zv.c_hi; ++g) {
+        uint64_t m = range_group_mask<true>(V, g, zv.c_lo, zv.c_hi, app.drv0, app.drv1, app.drv2, lane);
+        while (m) {
+            const uint32_t ch = g * kWave + (uint32_t)(__ffsll((unsigned long long)m) - 1);
+            m &= m - 1;
+            const uint32_t i = ch * kWave + lane;
+            bool ok = false;
+            int32_t dc = 0;
+            int64_t a0, a1, a2;
+            if (load_with_cand<true>(V, i, T.n_d, a0, a1, a2)) {
+                if (driver_fits(a0, a1, a2, app)) {  // binpack.go:69
+                    int64_t total = S;
+                    if (i < T.n_x && V.xcand(i)) {  // the driver's node is an executor candidate of the view
+                        dc = cap3(a0 - app.drv0, a1 - app.drv1, a2 - app.drv2, app) - cap3(a0, a1, a2, app);
+                        total = S + dc;
+                    }
+                    ok = total >= K;
+                }
+            }
+            const uint64_t fm = __ballot(ok);
+            if (fm) {
+                const int src = __ffsll((unsigned long long)fm) - 1;
+                out.pos = ch * kWave + (uint32_t)src;
+                out.d_cap = read_lane(dc, src);
+                found = true;
+                break;
+            }
+        }
+    }
+    if (lane == 0) shard_publish(out, dsts, drv_out, q * SZ.n_cand + c, SS.shard[q] * SZ.n_cand + c, n_apps, a);
+}
+
+// Emit of view c: the shard's slice of the view's tightly-pack placement, as slot + 1, into region c of the buffer (c * half words
+// in).  No result record: the finish step chooses.
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void shard_emit_zoned_kernel(
+    NodeTable T, SparseTable G, ShardSet SS, ShardZones SZ, uint32_t n_apps, const gf_app* __restrict__ apps,
+    const gf_shard_partial* __restrict__ all_part, const gf_shard_driver* __restrict__ all_drv, uint32_t* __restrict__ exec2,
+    uint64_t half) {
+    const int lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t a = blockIdx.x * kWavesPerBlock + wave;
+    if (a >= n_apps) return;
+    const uint32_t q = blockIdx.y, c = blockIdx.z;
+    const ShardView zv = shard_view(T, G, SS, SZ, q, c);
+    const App app = load_app(apps, a);
+    const int64_t K = app.k;
+    const ShardSums GS = shard_sums(all_part + (size_t)c * n_apps, all_drv + (size_t)c * n_apps, (size_t)SZ.n_cand * n_apps, a,
+                                    SS.shard[q], SS.n_shards);
+    if (GS.pos == GF_NO_NODE || K == 0) return;
+    uint32_t* out = exec2 + (size_t)c * half + app.exec_off;
+    int64_t taken = GS.before_cap;
+    if (taken >= K) return;
+    // slot_of: sub-slot -> slot (the compact gpu table), nullptr when j is a slot of the full table already
+    auto visit = [&](const GlobalView& V, uint32_t n_x, const uint32_t* __restrict__ slot_of, uint32_t ds, uint32_t j, bool in) {
+        int32_t cp = 0;
+        int64_t a0, a1, a2;
+        if (load_with_cand<false>(V, j, n_x, a0, a1, a2) && in) {
+            if (j == ds) {
+                a0 -= app.drv0;
+                a1 -= app.drv1;
+                a2 -= app.drv2;
+            }
+            if (cap_ge1(a0, a1, a2, app)) cp = cap3(a0, a1, a2, app);
+        }
+        const int32_t incl = wave_inclusive_scan(cp);  // pack_tightly.go:45-61, continued from the ranges before this one
+        const int32_t tot = read_lane(incl, kWave - 1);
+        if (tot > 0) {
+            const int64_t start = taken + (int64_t)(incl - cp);
+            const int64_t room = K - start;
+            const int32_t t = room <= 0 ? 0 : (room < (int64_t)cp ? (int32_t)room : cp);
+            uint32_t id = 0;
+            if (t > 0) id = (slot_of != nullptr ? slot_of[j] : j) + 1u;
+            emit_runs(out, start, t, id, lane);
+        }
+        taken += tot;
+        return taken < K;
+    };
+    if (G.n_x != 0 && app.exe2 > 0) {  // wave-uniform: the range's part of the view's sub-slots of the compact gpu table
+        GlobalView VS = shard_sparse_view(G);
+        VS.xm = VS.dm = zv.gxm;
+        const uint32_t ds_sub = G.sub_of_slot[GS.pos];
+        if (zv.g_lo < zv.g_hi)
+            shard_scan_range(VS, zv.g_lo, zv.g_hi, app.exe0, app.exe1, app.exe2, lane,
+                             [&](uint32_t j, bool in) { return visit(VS, G.n_x, G.slot_of_sub, ds_sub, j, in); });
+    } else if (zv.c_lo < zv.c_hi) {
+        const GlobalView V{T.cpu, T.mem, T.gpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, zv.xm, zv.dm,
+                           T.n_chunks};
+        shard_scan_range(V, zv.c_lo * kWave, zv.c_hi * kWave, app.exe0, app.exe1, app.exe2, lane,
+                         [&](uint32_t j, bool in) { return visit(V, T.n_x, nullptr, GS.pos, j, in); });
+    }
+}
+
+// The zone-aware packers' finish, after the all-reduce: a workgroup per application, a wavefront per candidate view (as in
+// fit_zoned_fused_kernel).  Each wavefront turns its view's placement back into slots, computes the zone's average Max from
+// them with the one-launch kernel's device functions — the same additions in the same order — and leaves its verdict in LDS;
+// then chooseBestResult (single_az.go:75-97: strict < from 0.0, the first zone of the evaluation list on a tie), the az-aware
+// fallback to the plain view (az_aware_pack_tightly.go:33-37), the result record, and the winner's slots translated to node
+// ids into region 0 = [exec_off, exec_off + K) of the buffer (zeros when nothing won).
+template <bool AZ_AWARE>
+__global__ __launch_bounds__(kWave* kFusedWaves) void shard_finish_zoned_kernel(
+    NodeTable T, ShardZones SZ, uint32_t n_shards, uint32_t n_apps, const gf_app* __restrict__ apps,
+    const gf_shard_partial* __restrict__ all_part, const gf_shard_driver* __restrict__ all_drv, gf_result* __restrict__ results,
+    uint32_t* __restrict__ exec2, uint64_t half) {
+    __shared__ FusedShared sh;
+    const uint32_t tid = threadIdx.x;
+    const int lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t a = blockIdx.x;
+    if (a >= n_apps) return;
+    const uint32_t n_zone_cand = SZ.n_zones, n_cand = SZ.n_cand;  // (the host guarantees n_cand <= 64)
+    const EffView EV{T.cpu, T.mem, T.gpu, SZ.sched, SZ.sched + T.n_slots, SZ.sched + 2 * (size_t)T.n_slots};
+    const App app = load_app(apps, a);
+    const int64_t K = app.k;
+    for (uint32_t c = wave; c < n_cand; c += kFusedWaves) {
+        const ShardSums GS = shard_sums(all_part + (size_t)c * n_apps, all_drv + (size_t)c * n_apps, (size_t)n_cand * n_apps, a, 0,
+                                        n_shards);
+        const bool feasible = GS.pos != GF_NO_NODE;
+        // A wrong exchange (what the multi-device context's self-check exists to catch) may leave entries no shard wrote, or a bad
+        // driver record: such slots become the sentinel slot, so that the answer is wrong but every table read stays in bounds.
+        const uint32_t last = T.n_slots - 1u;
+        const uint32_t ds = GS.pos < last ? GS.pos : last;
+        double avg[4] = {0.0, 0.0, 0.0, 0.0};
+        if (feasible) {
+            uint32_t* out = exec2 + (size_t)c * half + app.exec_off;
+            for (int64_t i = lane; i < K; i += kWave) {  // slot + 1 -> slot
+                const uint32_t s = out[i] - 1u;
+                out[i] = s < last ? s : last;
+            }
+            if (c < n_zone_cand) {
+                // out[] was written by other lanes of this wave
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                bool done = false;
+                if (K >= 1 && K <= (int64_t)kRunBlocks * kWave)
+                    done = wave_avg_max_tight_runs(EV, app, ds, out, lane, (lds_u32r*)&sh.runs[wave][0], avg[3]);
+                if (!done) wave_avg_efficiency_runs<GF_ALGO_TIGHTLY_PACK>(EV, app, ds, out, lane, avg);
+            }
+        }
+        if (lane == 0) {
+            sh.feas[c] = feasible ? 1 : 0;
+            sh.ds[c] = ds;
+            sh.mx[c] = avg[3];
+        }
+    }
+    __syncthreads();  // every view's verdict (LDS) and placement (global, same compute unit) is visible to every wavefront
+    int32_t best = -1;
+    double best_max = 0.0;
+    for (uint32_t c = 0; c < n_zone_cand; ++c)
+        if (sh.feas[c] && best_max < sh.mx[c]) {
+            best = (int32_t)c;
+            best_max = sh.mx[c];
+        }
+    if (AZ_AWARE && best < 0 && sh.feas[n_zone_cand]) best = (int32_t)n_zone_cand;
+    const bool feasible = best >= 0;
+    uint32_t* dst = exec2 + app.exec_off;
+    if (feasible) {
+        const uint32_t* src = exec2 + (size_t)best * half + app.exec_off;  // (best == 0: each thread rewrites its own entries)
+        for (int64_t i = tid; i < K; i += kWave * kFusedWaves) dst[i] = T.slot_node[src[i]];
+    } else {
+        for (int64_t i = tid; i < K; i += kWave * kFusedWaves) dst[i] = 0u;
+    }
+    if (tid == 0) {
+        gf_result r;
+        r.has_capacity = feasible ? 1 : 0;
+        r.driver_node = feasible ? T.slot_node[sh.ds[best]] : GF_NO_NODE;
+        r.exec_len = feasible ? (uint32_t)K : 0u;
+        r.evaluated = 1;
+        results[a] = r;
     }
 }
 

@@ -55,7 +55,8 @@ class Context:
 
     def __init__(self, device: int = 0, devices=None, options=None):
         """devices: a list of device ids makes ONE context over several devices (gf_init with n_dev > 1: independent batches
-        of the plain packers are node-range sharded across them inside the library; an id may repeat).
+        of the plain packers and of the zone-aware tightly-pack packers are node-range sharded across them inside the library;
+        an id may repeat).
         options: {key: int} for gf_set_option (test switches: "fifo_generic", "lds_budget", "chain_cache", ...)."""
         self._lib = N.load()
         h = C.c_void_p()

@@ -14,6 +14,10 @@ only when one GPU's scan of the table is slower than ~3 collective latencies (50
 for the headline size the throughput path is app sharding with no collective (bench.py).  The FIFO chain does not shard
 (each commit must be visible to the next scan): it runs as replicas.
 
+The zone-aware tightly-pack packers (single-az-tightly-pack, az-aware-tightly-pack) run the same steps once per candidate view
+— every zone, plus the plain order for az-aware —, with records and placement regions per view; how many, and how much of
+the placement buffer the all-reduce sums, comes from the library (gf_shard_layout, HipShardEngine.layout).
+
 This file is orchestration only: no arithmetic on placements happens in Python, and there is no CPU fallback —
 `HipShardEngine` raises when libgangfit or the GPU is missing.  `Comm`/engine are small interfaces so that the N > 1 control
 flow is also exercised on CPU (tests/test_sharded_cpu.py: world_size-2 gloo with a numpy engine from tests/).
@@ -167,23 +171,31 @@ class HipShardEngine:
     def upload_apps(self, apps_off: np.ndarray):
         return self._torch.from_numpy(apps_off.view(np.uint8).copy()).to(self.device)
 
-    def partials(self, algo: int, d_apps, n_apps: int):
-        out = self._torch.empty((n_apps, 2), dtype=self._torch.int64, device=self.device)
+    def layout(self, algo: int, half: int):
+        """(records per application, words of the placement buffer, leading words of it the all-reduce sums) of a batch of
+        `algo` with sum of k = half - 1 on the context's installed snapshot, zones and orders (gf_shard_layout)."""
+        rec, words, red = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        c = self.ctx
+        c._check(c._lib.gf_shard_layout(c._h, algo, half, C.byref(rec), C.byref(words), C.byref(red)))
+        return int(rec.value), int(words.value), int(red.value)
+
+    def partials(self, algo: int, d_apps, n_apps: int, records: int = 1):
+        out = self._torch.empty((records * n_apps, 2), dtype=self._torch.int64, device=self.device)
         c = self.ctx
         c._check(c._lib.gf_shard_partials_dev(c._h, algo, n_apps, C.c_void_p(d_apps.data_ptr()),
                                               C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
-    def drivers(self, algo: int, d_apps, n_apps: int, all_part):
-        out = self._torch.empty((n_apps, 4), dtype=self._torch.int32, device=self.device)
+    def drivers(self, algo: int, d_apps, n_apps: int, all_part, records: int = 1):
+        out = self._torch.empty((records * n_apps, 4), dtype=self._torch.int32, device=self.device)
         c = self.ctx
         c._check(c._lib.gf_shard_drivers_dev(c._h, algo, n_apps, C.c_void_p(d_apps.data_ptr()),
                                              C.c_void_p(all_part.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
-    def emit(self, algo: int, d_apps, n_apps: int, all_part, all_drv, half: int):
+    def emit(self, algo: int, d_apps, n_apps: int, all_part, all_drv, half: int, words: Optional[int] = None):
         res = self._torch.empty(n_apps * 16, dtype=self._torch.uint8, device=self.device)
-        exec2 = self._torch.empty(2 * half, dtype=self._torch.int32, device=self.device)
+        exec2 = self._torch.empty(2 * half if words is None else words, dtype=self._torch.int32, device=self.device)
         c = self.ctx
         c._check(c._lib.gf_shard_emit_dev(c._h, algo, n_apps, C.c_void_p(d_apps.data_ptr()),
                                           C.c_void_p(all_part.data_ptr()), C.c_void_p(all_drv.data_ptr()),
@@ -199,34 +211,50 @@ class HipShardEngine:
 
 
 # ------------------------------------------------------------------------------------------------ orchestration
+SHARDED_ALGOS = (N.GF_ALGO_TIGHTLY_PACK, N.GF_ALGO_DISTRIBUTE_EVENLY, N.GF_ALGO_SINGLE_AZ_TIGHTLY_PACK,
+                 N.GF_ALGO_AZ_AWARE_TIGHTLY_PACK)
+
+
 class ShardedBatch:
     """One pending-app table prepared for repeated sharded evaluation (bench.py times `step`)."""
 
     def __init__(self, engine, comm: Comm, algo: int, apps: np.ndarray):
-        if algo not in (N.GF_ALGO_TIGHTLY_PACK, N.GF_ALGO_DISTRIBUTE_EVENLY):
-            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, "node-range sharding serves tightly-pack and distribute-evenly only")
+        if algo not in SHARDED_ALGOS:
+            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, "node-range sharding serves tightly-pack, distribute-evenly, "
+                                                      "single-az-tightly-pack and az-aware-tightly-pack only")
         self.engine, self.comm, self.algo = engine, comm, algo
         apps = np.ascontiguousarray(apps, dtype=N.APP_DTYPE)
         self.apps_off, self.total_k = with_offsets(apps)
         self.n_apps = len(apps)
         self.half = self.total_k + 1
+        # the buffers' layout from the library (HipShardEngine.layout); an engine without the query serves the plain packers, whose
+        # layout is fixed: one record per application, [0, half) placements + [half, 2 half) distribute-evenly's capacities
+        if hasattr(engine, "layout"):
+            self.records, words, self.reduce_words = engine.layout(algo, self.half)
+            self._rec_kw, self._emit_kw = {"records": self.records}, {"words": words}
+        elif algo in (N.GF_ALGO_TIGHTLY_PACK, N.GF_ALGO_DISTRIBUTE_EVENLY):
+            self.records = 1
+            self.reduce_words = 2 * self.half if algo == N.GF_ALGO_DISTRIBUTE_EVENLY else self.half
+            self._rec_kw, self._emit_kw = {}, {}
+        else:
+            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, "this shard engine serves the plain packers only")
         with engine.stream_context():
             self.d_apps = engine.upload_apps(self.apps_off)
         self.res = self.exec2 = None
 
     def _placements(self):
-        """What the all-reduce carries: the placement half of the buffer; the second half (the capacities of pass 1's nodes) is
-        only written and read by distribute-evenly (shard_emit_kernel / shard_finish_kernel)."""
-        return self.exec2 if self.algo == N.GF_ALGO_DISTRIBUTE_EVENLY else self.exec2[: self.half]
+        """What the all-reduce carries: the leading reduce_words of the buffer — tightly-pack's placements, distribute-evenly's
+        placements and pass-1 capacities, or every candidate view's placement region of a zone-aware packer."""
+        return self.exec2 if self.reduce_words >= len(self.exec2) else self.exec2[: self.reduce_words]
 
     def step(self):
         e, c, algo, n = self.engine, self.comm, self.algo, self.n_apps
         with e.stream_context():
-            part = e.partials(algo, self.d_apps, n)
+            part = e.partials(algo, self.d_apps, n, **self._rec_kw)
             all_part = c.all_gather(part)
-            drv = e.drivers(algo, self.d_apps, n, all_part)
+            drv = e.drivers(algo, self.d_apps, n, all_part, **self._rec_kw)
             all_drv = c.all_gather(drv)
-            self.res, self.exec2 = e.emit(algo, self.d_apps, n, all_part, all_drv, self.half)
+            self.res, self.exec2 = e.emit(algo, self.d_apps, n, all_part, all_drv, self.half, **self._emit_kw)
             c.all_reduce_sum_(self._placements())
             e.finish(algo, self.d_apps, n, all_part, all_drv, self.res, self.exec2, self.half)
 
@@ -239,15 +267,15 @@ class ShardedBatch:
         e, c, algo, n = self.engine, self.comm, self.algo, self.n_apps
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         with e.stream_context():
-            part = e.partials(algo, self.d_apps, n)
+            part = e.partials(algo, self.d_apps, n, **self._rec_kw)
             ev[0].record(e.stream)
             all_part = c.all_gather(part)
             ev[1].record(e.stream)
-            drv = e.drivers(algo, self.d_apps, n, all_part)
+            drv = e.drivers(algo, self.d_apps, n, all_part, **self._rec_kw)
             ev[2].record(e.stream)
             all_drv = c.all_gather(drv)
             ev[3].record(e.stream)
-            self.res, self.exec2 = e.emit(algo, self.d_apps, n, all_part, all_drv, self.half)
+            self.res, self.exec2 = e.emit(algo, self.d_apps, n, all_part, all_drv, self.half, **self._emit_kw)
             ev[4].record(e.stream)
             c.all_reduce_sum_(self._placements())
             ev[5].record(e.stream)

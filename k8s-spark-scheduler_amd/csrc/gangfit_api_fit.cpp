@@ -1,6 +1,7 @@
-// gangfit_api_fit.cpp — the decision side of the C ABI: table views, the launches of every packer (independent batches, FIFO chains on the LDS
-// kernels and their fallbacks), the incremental chain cache, gf_fit_batch / gf_fit_batch_dev / gf_spark_binpack, single
-// executors, findNodes and the packing efficiencies.
+// gangfit_api_fit.cpp — the decision side of the C ABI: table views; route_of, the one place that decides which kernels serve a
+// (mode, packer) on a context, and launch, which runs them (independent batches, FIFO chains on the LDS kernels
+// and their fallbacks); the incremental chain cache, gf_fit_batch / gf_fit_batch_dev / gf_fit_feasible / gf_spark_binpack,
+// single executors, findNodes and the packing efficiencies.
 #include "gangfit_ctx.h"
 
 using namespace gfapi;
@@ -67,6 +68,33 @@ bool reserves_executors(gf_algo algo) {
 bool is_zone_algo(gf_algo algo) {
     return algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK || algo == GF_ALGO_SINGLE_AZ_TIGHTLY_PACK ||
            algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION;
+}
+bool is_plain_algo(gf_algo algo) {
+    return algo == GF_ALGO_TIGHTLY_PACK || algo == GF_ALGO_DISTRIBUTE_EVENLY || algo == GF_ALGO_MINIMAL_FRAGMENTATION;
+}
+// candidate views of one application: every zone of the evaluation list (plus the plain order for az-aware), else one
+uint32_t candidate_views(const gf_ctx* ctx, gf_algo algo) {
+    return is_zone_algo(algo) ? ctx->n_zones + (algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u) : 1u;
+}
+
+// Checks the request records (k in [0, GF_MAX_K], every quantity in [0, 2^62)) and sums their executors into *total_k;
+// out (nullable) receives a copy of the records with exec_off set.
+int check_apps(gf_ctx* ctx, uint32_t n_apps, const gf_app* apps, gf_app* out, uint64_t* total_k) {
+    uint64_t t = 0;
+    for (uint32_t a = 0; a < n_apps; ++a) {
+        const gf_app& in = apps[a];
+        if (in.k < 0 || in.k > GF_MAX_K) return fail(ctx, GF_ERR_INVALID, "apps[%u].k = %d outside [0, %d]", a, in.k, GF_MAX_K);
+        for (int j = 0; j < 3; ++j)
+            if (in.drv[j] < 0 || in.drv[j] >= GF_MAX_ABS_QUANTITY || in.exe[j] < 0 || in.exe[j] >= GF_MAX_ABS_QUANTITY)
+                return fail(ctx, GF_ERR_INVALID, "apps[%u] request outside [0, 2^62)", a);
+        if (out != nullptr) {
+            out[a] = in;
+            out[a].exec_off = t;
+        }
+        t += (uint64_t)in.k;
+    }
+    *total_k = t;
+    return GF_OK;
 }
 
 // Rows of the per-wave multiplicity scratch: enough waves to fill the chip, bounded to 256 MiB.
@@ -257,10 +285,10 @@ uint32_t solo_lds_slots(const gf_ctx* ctx) {
 }
 
 // Geometry of the LDS-resident chains of the zone-aware tightly-pack packers (gangfit_fifo_zoned.inc) and of the
-// minimal-fragmentation packers (gangfit_fifo_minfrag.inc); false = the generic global-memory chain serves.
+// minimal-fragmentation packers (gangfit_fifo_minfrag.inc); false = the tables do not fit and the generic chain serves.
 bool zoned_lds_geometry(const gf_ctx* ctx, bool az_aware, uint32_t* n_shapes, uint32_t* lds_slots) {
     const uint32_t nz = ctx->n_zones;
-    if (!(ctx->merged && ctx->narrow_ok && !ctx->fifo_generic) || nz + (az_aware ? 1u : 0u) > 16) return false;
+    if (nz + (az_aware ? 1u : 0u) > 16) return false;
     // as many shape-index rows as LDS allows next to the masks (64 down to 4), then as much of the table as fits
     uint32_t ns = 64;
     const uint32_t n_cand = nz + (az_aware ? 1u : 0u);
@@ -274,7 +302,7 @@ bool zoned_lds_geometry(const gf_ctx* ctx, bool az_aware, uint32_t* n_shapes, ui
 }
 bool minfrag_lds_geometry(const gf_ctx* ctx, bool zoned, uint32_t* n_idx, uint32_t* lds_slots) {
     const uint32_t nz = ctx->n_zones;
-    if (!(ctx->merged && ctx->narrow_ok && !ctx->fifo_generic) || (zoned && (nz == 0 || nz > 16))) return false;
+    if (zoned && (nz == 0 || nz > 16)) return false;
     const uint32_t zviews = zoned ? nz : 0u;
     // 64 shape ids per role (rows of the capacity matrix, histograms); as many of them as LDS allows next to the masks also
     // get chunk-index rows (64 down to 0 — the histogram path does without), then as much of the table as fits
@@ -288,163 +316,94 @@ bool minfrag_lds_geometry(const gf_ctx* ctx, bool zoned, uint32_t* n_idx, uint32
     return true;
 }
 
-// The LDS-resident minimal-fragmentation chain when the layout is merged, the table has a narrow form and the tables fit;
-// *run_if is then set to the flag the generic kernel must test (it only runs when a request had no scaled form) and
-// *served to true.  d_apps / d_results: the arrays of the whole queue (a resumed chain is launched on their tail).
-int try_minfrag_lds(gf_ctx* ctx, bool zoned, const gangfit::ZoneTable& zt, uint32_t n_apps, const gf_app* h_apps,
-                    const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes, uint64_t half, int32_t* d_failed,
-                    hipStream_t stream, const ChainRun* run, const int32_t** run_if, bool* served) {
-    *run_if = nullptr;
-    *served = false;
-    uint32_t n_idx = 0, lds_slots = 0;
-    if (!minfrag_lds_geometry(ctx, zoned, &n_idx, &lds_slots)) return GF_OK;
-    const uint32_t nz = ctx->n_zones;
-    const uint32_t zviews = zoned ? nz : 0u;
-    const uint32_t n_shapes = 64;
-    GF_HIP(ctx, ctx->d_napps.reserve(n_apps));
-    GF_HIP(ctx, ctx->d_zexec.reserve(32 * half));
-    gangfit::NarrowTable nt{};
-    const int32_t* restore = nullptr;
-    const gangfit::ChainCkpt ck = chain_ckpt_args(ctx, run, &restore);
-    gangfit::ChainIo io;
-    if (const int irc = chain_io_begin(ctx, ck.a_base, run != nullptr && run->narrow_proven, stream, &io); irc != GF_OK) return irc;
-    if (const int nrc = narrow_begin(ctx, h_apps, n_apps, stream, &nt, &io, restore); nrc != GF_OK) return nrc;
-    // capacity matrix: one int32 per (request shape, slot); skipped (capacities recomputed per pass) beyond 1 GiB
-    int32_t* capmat = nullptr;
-    if ((uint64_t)n_shapes * ctx->n_slots * sizeof(int32_t) <= (UINT64_C(1) << 30) && ctx->fifo_minfrag_matrix) {
-        GF_HIP(ctx, ctx->d_capmat.reserve((size_t)n_shapes * ctx->n_slots + 2048));  // rows are read 2048 slots at a time
-        capmat = ctx->d_capmat.ptr;
-    }
-    int32_t* hist = nullptr;
-    if (capmat != nullptr && ctx->fifo_minfrag_hist) {
-        GF_HIP(ctx, ctx->d_mfhist.reserve(gangfit::fifo_minfrag_hist_words(zviews, n_shapes)));
-        hist = ctx->d_mfhist.ptr;
-    }
-    const uint32_t a0 = ck.a_base;
-    GF_HIP(ctx, gangfit::launch_fit_fifo_minfrag_lds(zoned, make_table(ctx, ctx->d_work.ptr), nt, zt, ctx->d_sched.ptr, lds_slots,
-                                                     n_shapes, n_idx, n_apps - a0, d_apps + a0, ctx->d_napps.ptr + a0,
-                                                     wide_flag(ctx), d_results + a0, d_exec_nodes, ctx->d_zexec.ptr, half,
-                                                     d_failed, capmat, hist, ck, io, ctx->stats_on ? ctx->d_stats.ptr : nullptr, stream));
-    *run_if = wide_flag(ctx);
-    chain_io_end(ctx, io);
-    *served = true;
-    return GF_OK;
-}
+// What serves a batch of (mode, packer) on this context: the kernel route and the geometry of its chain kernel.  It depends
+// on the context's state and options only, never on the batch (what a batch adds — the narrow proof, the resume point —
+// is ChainRun's).
+struct Route {
+    enum Kind {
+        kPlain,       // independent, plain packers: fit_independent_kernel
+        kZonedFused,  // independent, zone-aware packers in one launch: fit_zoned_fused_kernel
+        kZonedFour,   // ... in four: fit_independent_kernel (az-aware) -> fit_zoned_kernel -> avg_efficiency_kernel -> zone_select_kernel
+        kSolo,        // FIFO chain, tightly-pack / distribute-evenly: fit_fifo_solo_kernel, fit_fifo_chain_kernel as its wide twin
+        kWide,        // ... fit_fifo_chain_kernel alone
+        kZonedLds,    // FIFO chain, zone-aware tightly-pack: fit_fifo_zoned_lds_kernel, fit_fifo_generic_kernel as its wide twin
+        kMinfragLds,  // FIFO chain, minimal-fragmentation packers: fit_fifo_minfrag_lds_kernel, the same twin
+        kGeneric,     // FIFO chain of the zone-aware or minimal-fragmentation packers: fit_fifo_generic_kernel alone
+    } kind = kPlain;
+    int inner = GF_ALGO_TIGHTLY_PACK;  // the packer of one candidate view
+    bool zoned = false, az_aware = false;
+    uint32_t n_cand = 1;       // candidate views of an application
+    uint32_t lds_slots = 0;    // LDS chain kernels: table slots kept in LDS
+    uint32_t n_shapes = 0;     // kZonedLds: shape-index rows; kMinfragLds: shape ids with chunk-index rows (n_idx)
+    bool table_in_lds = false; // LDS chain kernels: the whole table
+    bool lds_chain() const { return kind == kSolo || kind == kZonedLds || kind == kMinfragLds; }
+};
 
-int launch_zoned(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const gf_app* h_apps, const gf_app* d_apps,
-                 gf_result* d_results,
-                 uint32_t* d_exec_nodes, uint64_t exec_nodes_len, int32_t* d_failed, hipStream_t stream, const ChainRun* run) {
-    if (!ctx->have_sched)
+// Refusals in order: no orders (GF_ERR_STATE), a packer without a device path, an unknown mode (GF_ERR_UNSUPPORTED),
+// a zone-aware packer without the schedulable columns (GF_ERR_STATE), a zone-aware FIFO chain with more than 63 zones
+// (GF_ERR_UNSUPPORTED).
+int route_of(gf_ctx* ctx, gf_mode mode, gf_algo algo, Route* r) {
+    *r = Route{};
+    if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a fit");
+    const bool zoned = is_zone_algo(algo);
+    if (!zoned && !is_plain_algo(algo)) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_algo %d is not served by the device path", (int)algo);
+    if (mode != GF_MODE_INDEPENDENT && mode != GF_MODE_FIFO_CHAIN) return fail(ctx, GF_ERR_UNSUPPORTED, "unknown gf_mode %d", (int)mode);
+    if (zoned && !ctx->have_sched)
         return fail(ctx, GF_ERR_STATE, "zone-aware packers compare packing efficiencies: gf_snapshot_set needs the schedulable columns");
-    const int inner = algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION ? GF_ALGO_MINIMAL_FRAGMENTATION : GF_ALGO_TIGHTLY_PACK;
-    const uint64_t half = exec_nodes_len + 1;
     const uint32_t nz = ctx->n_zones;
-    if (mode == GF_MODE_INDEPENDENT && ctx->zoned_fused && nz + 1 <= 64) {
-        // one launch: a workgroup per application decides every candidate view, chooses and writes the final answer
-        // (fit_zoned_fused_kernel) — d_apps / d_results / d_exec_nodes may be device-mapped host memory (gf_fit_batch)
-        GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * half));
-        gangfit::ZoneTable zt{ctx->d_zmasks.ptr, ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride, nz, ctx->zstride};
-        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
-        GF_HIP(ctx, gangfit::launch_fit_zoned_fused(inner, algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), zt,
-                                                    ctx->d_sched.ptr, ctx->d_zexec.ptr, half, n_apps, d_apps, d_results,
-                                                    d_exec_nodes, ctx->d_scratch.ptr, half, stream));
+    r->zoned = zoned;
+    r->az_aware = algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK;
+    r->inner = algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION ? GF_ALGO_MINIMAL_FRAGMENTATION : (zoned ? GF_ALGO_TIGHTLY_PACK : (int)algo);
+    r->n_cand = candidate_views(ctx, algo);
+    if (mode == GF_MODE_INDEPENDENT) {
+        r->kind = !zoned ? Route::kPlain : (ctx->zoned_fused && nz + 1 <= 64 ? Route::kZonedFused : Route::kZonedFour);
         return GF_OK;
     }
-    const uint64_t n_dec = (uint64_t)n_apps * (nz ? nz : 1);
-    GF_HIP(ctx, ctx->d_zres.reserve(n_dec));
-    GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * half));
-    GF_HIP(ctx, ctx->d_zavg.reserve(4 * n_dec));
-    GF_HIP(ctx, ctx->d_avg.reserve(4 * (size_t)n_apps));
-    int rc = ensure_cnt(ctx, n_dec < 16 ? 16 : n_dec, stream);
-    if (rc != GF_OK) return rc;
-    gangfit::ZoneTable zt{ctx->d_zmasks.ptr, ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride, nz, ctx->zstride};
-    gangfit::ZoneBuffers zb{ctx->d_zres.ptr, ctx->d_zexec.ptr, half, ctx->d_zavg.ptr, ctx->d_cnt.ptr, ctx->cnt_rows,
-                            ctx->d_avg.ptr};
-    if (mode == GF_MODE_FIFO_CHAIN) {
-        if (nz + 1 > 64) return fail(ctx, GF_ERR_UNSUPPORTED, "more than 63 zones in a FIFO chain");
-        if (ctx->cnt_rows < 16) return fail(ctx, GF_ERR_HIP, "multiplicity scratch too small");
-        const bool proven = run != nullptr && run->narrow_proven;  // the LDS chain serves for certain: no generic twin
-        // every chain starts from the snapshot: availableNodesSchedulingMetadata is rebuilt per request (resource.go:303);
-        // the LDS chains rewrite every real slot of the wide working table in their epilogue
-        if (!proven) {
-            if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;  // the generic kernel reads d_apps
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_work.ptr, ctx->d_snap.ptr, 3 * (size_t)ctx->n_slots * sizeof(int64_t),
-                                       hipMemcpyDeviceToDevice, stream));
-        }
-        ctx->work_valid = true;
-        const bool az_aware = algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK;
-        const int32_t* run_if = nullptr;
-        bool served = false;
-        // fast path: tightly-pack family, merged layout, narrow table, every candidate view gets its own wavefront
-        uint32_t n_shapes = 0, lds_slots = 0;
-        if (inner == GF_ALGO_TIGHTLY_PACK && zoned_lds_geometry(ctx, az_aware, &n_shapes, &lds_slots)) {
-            GF_HIP(ctx, ctx->d_napps.reserve(n_apps));
-            GF_HIP(ctx, ctx->d_zexec.reserve(32 * half));
-            gangfit::NarrowTable nt{};
-            const int32_t* restore = nullptr;
-            const gangfit::ChainCkpt ck = chain_ckpt_args(ctx, run, &restore);
-            gangfit::ChainIo io;
-            if (const int irc = chain_io_begin(ctx, ck.a_base, proven, stream, &io); irc != GF_OK) return irc;
-            if (const int nrc = narrow_begin(ctx, h_apps, n_apps, stream, &nt, &io, restore); nrc != GF_OK) return nrc;
-            const uint32_t a0 = ck.a_base;
-            GF_HIP(ctx, gangfit::launch_fit_fifo_zoned_lds(az_aware, make_table(ctx, ctx->d_work.ptr), nt, zt, ctx->d_sched.ptr,
-                                                           lds_slots, n_shapes, n_apps - a0, d_apps + a0, ctx->d_napps.ptr + a0,
-                                                           wide_flag(ctx), d_results + a0, d_exec_nodes,
-                                                           ctx->d_zexec.ptr, half, d_failed, ck, io,
-                                                           ctx->stats_on ? ctx->d_stats.ptr : nullptr, stream));
-            run_if = wide_flag(ctx);  // the generic kernel below only runs when a request had no scaled form
-            chain_io_end(ctx, io);
-            zb.zexec = ctx->d_zexec.ptr;
-            served = true;
-        }
-        if (inner == GF_ALGO_MINIMAL_FRAGMENTATION) {
-            const int rc2 = try_minfrag_lds(ctx, true, zt, n_apps, h_apps, d_apps, d_results, d_exec_nodes, half, d_failed, stream,
-                                            run, &run_if, &served);
-            if (rc2 != GF_OK) return rc2;
-            if (run_if) zb.zexec = ctx->d_zexec.ptr;
-        }
-        if (served && proven) return GF_OK;
-        if (proven) return fail(ctx, GF_ERR_HIP, "chain plan and launch disagree about the LDS chain");
-        GF_HIP(ctx, gangfit::launch_fit_fifo_generic(inner, true, az_aware,
-                                                     reserves_executors(algo), make_table(ctx, ctx->d_work.ptr), zt,
-                                                     ctx->d_sched.ptr, zb, n_apps, d_apps, d_results, d_exec_nodes,
-                                                     ctx->d_scratch.ptr, half, d_failed, run_if, stream));
-        return GF_OK;
+    if (zoned && nz + 1 > 64) return fail(ctx, GF_ERR_UNSUPPORTED, "more than 63 zones in a FIFO chain");
+    // the LDS chain kernels work on the narrow table of the merged layout
+    const bool lds = ctx->merged && ctx->narrow_ok && !ctx->fifo_generic;
+    if (r->inner != GF_ALGO_MINIMAL_FRAGMENTATION && !zoned) {
+        r->kind = lds ? Route::kSolo : Route::kWide;
+        if (lds) r->lds_slots = solo_lds_slots(ctx);
+    } else if (r->inner == GF_ALGO_TIGHTLY_PACK) {
+        r->kind = lds && zoned_lds_geometry(ctx, r->az_aware, &r->n_shapes, &r->lds_slots) ? Route::kZonedLds : Route::kGeneric;
+    } else {
+        r->kind = lds && minfrag_lds_geometry(ctx, zoned, &r->n_shapes, &r->lds_slots) ? Route::kMinfragLds : Route::kGeneric;
     }
-    if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
-    GF_HIP(ctx, gangfit::launch_fit_zoned(inner, algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK,
-                                          reserves_executors(algo), make_table(ctx, ctx->d_snap.ptr), zt,
-                                          slot_eff_tables(ctx, ctx->d_snap.ptr), zb, n_apps, d_apps, d_results,
-                                          d_exec_nodes, ctx->d_scratch.ptr, half, stream));
+    r->table_in_lds = r->lds_chain() && r->lds_slots >= ctx->n_slots;
     return GF_OK;
 }
 
-// Which chains resume: every packer, when its LDS-resident chain kernel serves (merged layout, narrow table, the kernel's
-// tables fit) and every request has a scaled form.  Returns false when the chain cache is not used for this call (run stays {0, false, false}).
-bool chain_plan(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const gf_app* h_apps, ChainRun* run) {
+gangfit::ZoneTable zone_table(const gf_ctx* ctx) {
+    return gangfit::ZoneTable{ctx->d_zmasks.ptr, ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride, ctx->n_zones, ctx->zstride};
+}
+
+// What every LDS chain kernel's launch starts with: the scaled records, the checkpoint arguments, the ChainIo and the narrow
+// working table (the copies themselves are left to the chain's first kernel).  chain_io_end(ctx, io) follows the launch.
+struct LdsChain {
+    gangfit::NarrowTable nt{};
+    gangfit::ChainCkpt ck{};
+    gangfit::ChainIo io;
+    int32_t* flag = nullptr;  // wide_flag of this chain: a request had no scaled form
+};
+int lds_chain_begin(gf_ctx* ctx, const ChainRun* run, uint32_t n_apps, const gf_app* h_apps, bool answers_final,
+                    bool restore_dirty_chunks, hipStream_t stream, LdsChain* c) {
+    GF_HIP(ctx, ctx->d_napps.reserve(n_apps));
+    const int32_t* restore = nullptr;
+    c->ck = chain_ckpt_args(ctx, run, &restore);
+    if (const int rc = chain_io_begin(ctx, c->ck.a_base, answers_final, stream, &c->io); rc != GF_OK) return rc;
+    c->flag = wide_flag(ctx);
+    return narrow_begin(ctx, h_apps, n_apps, stream, &c->nt, &c->io, restore, restore_dirty_chunks);
+}
+
+// Which chains resume: every packer, when its LDS-resident chain kernel serves (the route) and every request has a scaled
+// form.  Returns false when the chain cache is not used for this call (run stays {0, false, false}).
+bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, const gf_app* h_apps, ChainRun* run) {
     *run = ChainRun{};
     gf_ctx::ChainCache& C = ctx->chain;
-    if (mode != GF_MODE_FIFO_CHAIN || !ctx->chain_cache_on || ctx->stats_on || !ctx->have_orders) return false;
-    if (!(ctx->merged && ctx->narrow_ok) || ctx->fifo_generic) return false;
-    bool solo = false, table_in_lds = false;
-    {  // the LDS-resident chain kernel of this packer must be the one that serves (they dump and restore the checkpoints)
-        uint32_t g0 = 0, g1 = 0;
-        bool lds_chain = false;
-        switch (algo) {
-        case GF_ALGO_TIGHTLY_PACK:
-        case GF_ALGO_DISTRIBUTE_EVENLY:
-            lds_chain = solo = true;
-            g1 = solo_lds_slots(ctx);
-            break;
-        case GF_ALGO_SINGLE_AZ_TIGHTLY_PACK: lds_chain = ctx->have_sched && zoned_lds_geometry(ctx, false, &g0, &g1); break;
-        case GF_ALGO_AZ_AWARE_TIGHTLY_PACK: lds_chain = ctx->have_sched && zoned_lds_geometry(ctx, true, &g0, &g1); break;
-        case GF_ALGO_MINIMAL_FRAGMENTATION: lds_chain = minfrag_lds_geometry(ctx, false, &g0, &g1); break;
-        case GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION: lds_chain = ctx->have_sched && minfrag_lds_geometry(ctx, true, &g0, &g1); break;
-        default: break;
-        }
-        if (!lds_chain) return false;
-        table_in_lds = g1 >= ctx->n_slots;
-    }
+    // (the LDS chain kernels dump and restore the checkpoints)
+    if (!route.lds_chain() || !ctx->chain_cache_on || ctx->stats_on) return false;
+    const bool solo = route.kind == Route::kSolo, table_in_lds = route.table_in_lds;
     // The narrow units of the queue and the proof that every request has a scaled form.  A scan of the whole queue is twelve
     // 64-bit divisions per application — more host time than a resumed chain takes on the device —, so a queue that shares a
     // prefix with the cached one is only scanned behind it: the cached units divide the prefix by construction, and when they
@@ -588,96 +547,140 @@ void chain_commit(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, uint64_t total_k, 
     ctx->chain_stat[3] += run.a_begin;
 }
 
-// h_apps: the same records on the host when the caller has them (gf_fit_batch), nullptr for device-resident batches.
-// run (nullable): gf_fit_batch's plan for a FIFO chain; d_apps / d_results are always the arrays of the WHOLE queue.
-int launch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const gf_app* h_apps, const gf_app* d_apps,
-           gf_result* d_results, uint32_t* d_exec_nodes, uint64_t exec_nodes_len, int32_t* d_failed, hipStream_t stream,
-           const ChainRun* run = nullptr) {
-    if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a fit");
+// Launches the route's kernels.  h_apps: the same records on the host when the caller has them (gf_fit_batch), nullptr for
+// device-resident batches.  run (nullable): gf_fit_batch's plan for a FIFO chain; d_apps / d_results are always the arrays
+// of the WHOLE queue.
+int launch(gf_ctx* ctx, const Route& r, uint32_t n_apps, const gf_app* h_apps, const gf_app* d_apps, gf_result* d_results,
+           uint32_t* d_exec_nodes, uint64_t exec_nodes_len, int32_t* d_failed, hipStream_t stream, const ChainRun* run = nullptr) {
     const uint64_t half = exec_nodes_len + 1;
     GF_HIP(ctx, ctx->d_scratch.reserve(2 * half));
-    if (is_zone_algo(algo)) {
-        if (mode != GF_MODE_INDEPENDENT && mode != GF_MODE_FIFO_CHAIN)
-            return fail(ctx, GF_ERR_UNSUPPORTED, "unknown gf_mode %d", (int)mode);
-        return launch_zoned(ctx, mode, algo, n_apps, h_apps, d_apps, d_results, d_exec_nodes, exec_nodes_len, d_failed, stream, run);
-    }
-    if (algo != GF_ALGO_TIGHTLY_PACK && algo != GF_ALGO_DISTRIBUTE_EVENLY && algo != GF_ALGO_MINIMAL_FRAGMENTATION)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "gf_algo %d is not served by the device path", (int)algo);
-    if (algo == GF_ALGO_MINIMAL_FRAGMENTATION && mode == GF_MODE_FIFO_CHAIN) {
-        // the LDS chain; else (and as its guarded twin) the generic chain kernel: one candidate view, one wavefront, against
-        // the working table in global memory
-        const bool proven = run != nullptr && run->narrow_proven;
-        GF_HIP(ctx, ctx->d_zexec.reserve(half));
-        if (!proven) {
-            if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;  // the generic kernel reads d_apps
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_work.ptr, ctx->d_snap.ptr, 3 * (size_t)ctx->n_slots * sizeof(int64_t),
-                                       hipMemcpyDeviceToDevice, stream));
-        }
-        ctx->work_valid = true;
-        gangfit::ZoneTable zt{nullptr, nullptr, 0, 0};
-        const int32_t* run_if = nullptr;
-        bool served = false;
-        const int rc2 = try_minfrag_lds(ctx, false, zt, n_apps, h_apps, d_apps, d_results, d_exec_nodes, half, d_failed, stream, run,
-                                        &run_if, &served);
-        if (rc2 != GF_OK) return rc2;
-        if (served && proven) return GF_OK;
-        if (proven) return fail(ctx, GF_ERR_HIP, "chain plan and launch disagree about the LDS chain");
-        gangfit::ZoneBuffers zb{nullptr, ctx->d_zexec.ptr, half, nullptr, nullptr, 0, nullptr};
-        GF_HIP(ctx, gangfit::launch_fit_fifo_generic(GF_ALGO_MINIMAL_FRAGMENTATION, false, false, false,
-                                                     make_table(ctx, ctx->d_work.ptr), zt, nullptr, zb, n_apps, d_apps,
-                                                     d_results, d_exec_nodes, ctx->d_scratch.ptr, half, d_failed, run_if,
-                                                     stream));
+    const uint32_t nz = r.zoned ? ctx->n_zones : 0u;
+    const gangfit::ZoneTable zt = r.zoned ? zone_table(ctx) : gangfit::ZoneTable{nullptr, nullptr, 0, 0};
+    ScanStats* stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr;
+    switch (r.kind) {
+    case Route::kPlain:
+        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
+        GF_HIP(ctx, gangfit::launch_fit_independent((gf_algo)r.inner, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), n_apps,
+                                                    d_apps, d_results, d_exec_nodes, ctx->d_scratch.ptr, half, stats, stream));
+        return GF_OK;
+    case Route::kZonedFused:
+        // a workgroup per application decides every candidate view, chooses and writes the final answer — d_apps / d_results /
+        // d_exec_nodes may be device-mapped host memory (gf_fit_batch)
+        GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * half));
+        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
+        GF_HIP(ctx, gangfit::launch_fit_zoned_fused(r.inner, r.az_aware, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), zt,
+                                                    ctx->d_sched.ptr, ctx->d_zexec.ptr, half, n_apps, d_apps, d_results,
+                                                    d_exec_nodes, ctx->d_scratch.ptr, half, stream));
+        return GF_OK;
+    case Route::kZonedFour: {
+        const uint64_t n_dec = (uint64_t)n_apps * (nz ? nz : 1);
+        GF_HIP(ctx, ctx->d_zres.reserve(n_dec));
+        GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * half));
+        GF_HIP(ctx, ctx->d_zavg.reserve(4 * n_dec));
+        if (const int rc = ensure_cnt(ctx, n_dec < 16 ? 16 : n_dec, stream); rc != GF_OK) return rc;
+        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
+        const gangfit::ZoneBuffers zb{ctx->d_zres.ptr, ctx->d_zexec.ptr, half, ctx->d_zavg.ptr, ctx->d_cnt.ptr, ctx->cnt_rows};
+        GF_HIP(ctx, gangfit::launch_fit_zoned(r.inner, r.az_aware, r.inner != GF_ALGO_MINIMAL_FRAGMENTATION,
+                                              make_table(ctx, ctx->d_snap.ptr), zt, slot_eff_tables(ctx, ctx->d_snap.ptr), zb,
+                                              n_apps, d_apps, d_results, d_exec_nodes, ctx->d_scratch.ptr, half, stream));
         return GF_OK;
     }
-    ScanStats* stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr;
-    if (mode == GF_MODE_INDEPENDENT) {
-        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
-        GF_HIP(ctx, gangfit::launch_fit_independent(algo, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), n_apps, d_apps,
-                                                    d_results, d_exec_nodes, ctx->d_scratch.ptr, half, stats, stream));
-    } else if (mode == GF_MODE_FIFO_CHAIN) {
+    case Route::kSolo:
+    case Route::kWide: {
         gangfit::FifoPlan plan{};
-        plan.narrow = ctx->merged && ctx->narrow_ok && !ctx->fifo_generic;
+        plan.narrow = r.kind == Route::kSolo;
         plan.wide = !(plan.narrow && run != nullptr && run->narrow_proven);
-        const uint32_t a_begin = (plan.narrow && run != nullptr) ? run->a_begin : 0u;
         // every chain starts from the snapshot: availableNodesSchedulingMetadata is rebuilt per request (resource.go:303).
         // The solo kernel rewrites every real slot of the wide working table in its epilogue: the copy is only needed by the
         // wide kernel.  Like the narrow table's, the copy is made by the chain's first kernel (ChainIo).
-        gangfit::ChainIo io;
-        if (const int irc = chain_io_begin(ctx, a_begin, true, stream, &io); irc != GF_OK) return irc;
+        LdsChain c;
+        c.ck.shift = ctx->chain.shift;
+        if (plan.narrow) {
+            if (const int rc = lds_chain_begin(ctx, run, n_apps, h_apps, true, ctx->chain.dirty_format, stream, &c); rc != GF_OK)
+                return rc;
+        } else if (const int rc = chain_io_begin(ctx, 0, true, stream, &c.io); rc != GF_OK) {
+            return rc;
+        }
         if (plan.wide) {
-            io.copy_src[1] = reinterpret_cast<const uint32_t*>(ctx->d_snap.ptr);
-            io.copy_dst[1] = reinterpret_cast<uint32_t*>(ctx->d_work.ptr);
-            io.copy_words[1] = 3 * (size_t)ctx->n_slots * (sizeof(int64_t) / sizeof(uint32_t));
+            c.io.copy_src[1] = reinterpret_cast<const uint32_t*>(ctx->d_snap.ptr);
+            c.io.copy_dst[1] = reinterpret_cast<uint32_t*>(ctx->d_work.ptr);
+            c.io.copy_words[1] = 3 * (size_t)ctx->n_slots * (sizeof(int64_t) / sizeof(uint32_t));
         }
         ctx->work_valid = true;
-        // as much of the table front as fits next to each kernel's fixed LDS needs stays in LDS for the whole chain
-        auto front = [&](size_t fixed, size_t per_slot, uint32_t round) {
-            uint32_t n = ctx->lds_budget > fixed ? (uint32_t)((ctx->lds_budget - fixed) / per_slot) : 0;
-            const uint32_t whole = (ctx->n_slots + round - 1) / round * round;  // the whole table, padded to full steps
-            if (n >= whole) return whole;
-            return n / round * round;
-        };
-        plan.lds_slots_v2 = front(gangfit::fifo_v2_lds_bytes(0, ctx->n_chunks), 24, 64);
+        // as much of the table front as fits next to the wide kernel's fixed LDS needs stays in LDS for the whole chain
+        const size_t fixed = gangfit::fifo_v2_lds_bytes(0, ctx->n_chunks);
+        const uint32_t fit = ctx->lds_budget > fixed ? (uint32_t)((ctx->lds_budget - fixed) / 24) : 0;
+        const uint32_t whole = (ctx->n_slots + 63) / 64 * 64;  // the whole table, padded to full steps
+        plan.lds_slots_v2 = fit >= whole ? whole : fit / 64 * 64;
         if (plan.lds_slots_v2 > ctx->n_slots) plan.lds_slots_v2 = ctx->n_slots;
-        plan.lds_slots_solo = solo_lds_slots(ctx);
-        gangfit::NarrowTable nt{};
-        gangfit::ChainCkpt ck{nullptr, 0u, ctx->chain.shift};
-        if (plan.narrow) {
-            GF_HIP(ctx, ctx->d_napps.reserve(n_apps));
-            const int32_t* restore = nullptr;
-            ck = chain_ckpt_args(ctx, run, &restore);
-            if (const int nrc = narrow_begin(ctx, h_apps, n_apps, stream, &nt, &io, restore, ctx->chain.dirty_format); nrc != GF_OK)
-                return nrc;
-        }
+        plan.lds_slots_solo = r.lds_slots;
         // a resumed chain is launched on the tail of the queue: exec_off is absolute, so offset pointers are all it takes
-        const uint64_t heads_lo = a_begin > 0 ? h_apps[a_begin].exec_off : 0;
-        GF_HIP(ctx, gangfit::launch_fit_fifo(algo, plan, make_table(ctx, ctx->d_work.ptr), nt, n_apps - a_begin, d_apps + a_begin,
-                                             ctx->d_napps.ptr + a_begin, wide_flag(ctx), d_results + a_begin,
-                                             d_exec_nodes, ctx->d_scratch.ptr, half, heads_lo, d_failed, ck, io, stats, stream));
-        chain_io_end(ctx, io);
-    } else {
-        return fail(ctx, GF_ERR_UNSUPPORTED, "unknown gf_mode %d", (int)mode);
+        const uint32_t a0 = c.ck.a_base;
+        const uint64_t heads_lo = a0 > 0 ? h_apps[a0].exec_off : 0;
+        GF_HIP(ctx, gangfit::launch_fit_fifo((gf_algo)r.inner, plan, make_table(ctx, ctx->d_work.ptr), c.nt, n_apps - a0, d_apps + a0,
+                                             ctx->d_napps.ptr + a0, wide_flag(ctx), d_results + a0, d_exec_nodes,
+                                             ctx->d_scratch.ptr, half, heads_lo, d_failed, c.ck, c.io, stats, stream));
+        chain_io_end(ctx, c.io);
+        return GF_OK;
     }
+    default:
+        break;
+    }
+    // FIFO chains of the zone-aware and minimal-fragmentation packers: the LDS chain kernel, with the generic chain kernel as
+    // its guarded twin, or the generic kernel alone (one wavefront per candidate view, the working table in global memory)
+    const bool proven = run != nullptr && run->narrow_proven;  // the LDS chain serves for certain: no generic twin
+    GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * half));
+    if (r.zoned) {
+        const uint64_t n_dec = (uint64_t)n_apps * (nz ? nz : 1);
+        if (const int rc = ensure_cnt(ctx, n_dec < 16 ? 16 : n_dec, stream); rc != GF_OK) return rc;
+        if (ctx->cnt_rows < 16) return fail(ctx, GF_ERR_HIP, "multiplicity scratch too small");
+    }
+    // every chain starts from the snapshot: availableNodesSchedulingMetadata is rebuilt per request (resource.go:303);
+    // the LDS chains rewrite every real slot of the wide working table in their epilogue
+    if (!proven) {
+        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;  // the generic kernel reads d_apps
+        GF_HIP(ctx, hipMemcpyAsync(ctx->d_work.ptr, ctx->d_snap.ptr, 3 * (size_t)ctx->n_slots * sizeof(int64_t),
+                                   hipMemcpyDeviceToDevice, stream));
+    }
+    ctx->work_valid = true;
+    const int32_t* run_if = nullptr;  // the generic twin only runs when a request had no scaled form
+    if (r.kind != Route::kGeneric) {
+        GF_HIP(ctx, ctx->d_zexec.reserve(32 * half));
+        LdsChain c;
+        if (const int rc = lds_chain_begin(ctx, run, n_apps, h_apps, proven, false, stream, &c); rc != GF_OK) return rc;
+        const uint32_t a0 = c.ck.a_base;
+        if (r.kind == Route::kZonedLds) {
+            GF_HIP(ctx, gangfit::launch_fit_fifo_zoned_lds(r.az_aware, make_table(ctx, ctx->d_work.ptr), c.nt, zt, ctx->d_sched.ptr,
+                                                           r.lds_slots, r.n_shapes, n_apps - a0, d_apps + a0, ctx->d_napps.ptr + a0,
+                                                           c.flag, d_results + a0, d_exec_nodes, ctx->d_zexec.ptr, half, d_failed,
+                                                           c.ck, c.io, stats, stream));
+        } else {
+            const uint32_t n_shapes = 64;
+            // capacity matrix: one int32 per (request shape, slot); skipped (capacities recomputed per pass) beyond 1 GiB
+            int32_t* capmat = nullptr;
+            if ((uint64_t)n_shapes * ctx->n_slots * sizeof(int32_t) <= (UINT64_C(1) << 30) && ctx->fifo_minfrag_matrix) {
+                GF_HIP(ctx, ctx->d_capmat.reserve((size_t)n_shapes * ctx->n_slots + 2048));  // rows are read 2048 slots at a time
+                capmat = ctx->d_capmat.ptr;
+            }
+            int32_t* hist = nullptr;
+            if (capmat != nullptr && ctx->fifo_minfrag_hist) {
+                GF_HIP(ctx, ctx->d_mfhist.reserve(gangfit::fifo_minfrag_hist_words(nz, n_shapes)));
+                hist = ctx->d_mfhist.ptr;
+            }
+            GF_HIP(ctx, gangfit::launch_fit_fifo_minfrag_lds(r.zoned, make_table(ctx, ctx->d_work.ptr), c.nt, zt, ctx->d_sched.ptr,
+                                                             r.lds_slots, n_shapes, r.n_shapes, n_apps - a0, d_apps + a0,
+                                                             ctx->d_napps.ptr + a0, c.flag, d_results + a0, d_exec_nodes,
+                                                             ctx->d_zexec.ptr, half, d_failed, capmat, hist, c.ck, c.io, stats,
+                                                             stream));
+        }
+        chain_io_end(ctx, c.io);
+        if (proven) return GF_OK;
+        run_if = c.flag;
+    }
+    GF_HIP(ctx, gangfit::launch_fit_fifo_generic(r.inner, r.zoned, r.az_aware, make_table(ctx, ctx->d_work.ptr), zt,
+                                                 r.zoned ? ctx->d_sched.ptr : nullptr, ctx->d_zexec.ptr, half,
+                                                 r.zoned ? ctx->d_cnt.ptr : nullptr, n_apps, d_apps, d_results, d_exec_nodes,
+                                                 ctx->d_scratch.ptr, half, d_failed, run_if, stream));
     return GF_OK;
 }
 
@@ -710,20 +713,15 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     GF_HIP(ctx, hipSetDevice(ctx->device));
     GF_HIP(ctx, ctx->h_apps.reserve(n_apps));
     uint64_t total_k = 0;
-    for (uint32_t a = 0; a < n_apps; ++a) {
-        const gf_app& in = apps[a];
-        if (in.k < 0 || in.k > GF_MAX_K) return fail(ctx, GF_ERR_INVALID, "apps[%u].k = %d outside [0, %d]", a, in.k, GF_MAX_K);
-        for (int j = 0; j < 3; ++j)
-            if (in.drv[j] < 0 || in.drv[j] >= GF_MAX_ABS_QUANTITY || in.exe[j] < 0 || in.exe[j] >= GF_MAX_ABS_QUANTITY)
-                return fail(ctx, GF_ERR_INVALID, "apps[%u] request outside [0, 2^62)", a);
-        gf_app& o = ctx->h_apps.ptr[a];
-        o = in;
-        o.exec_off = total_k;
-        total_k += (uint64_t)in.k;
-    }
+    if (const int rc = check_apps(ctx, n_apps, apps, ctx->h_apps.ptr, &total_k); rc != GF_OK) return rc;
     if (total_k > exec_nodes_cap || (total_k > 0 && !exec_nodes))
         return fail(ctx, GF_ERR_CAPACITY, "exec_nodes holds %llu entries, %llu needed",
                     (unsigned long long)exec_nodes_cap, (unsigned long long)total_k);
+    Route route;
+    if (const int rc = route_of(ctx, mode, algo, &route); rc != GF_OK) {
+        ctx->chain.valid = false;
+        return rc;
+    }
     GF_HIP(ctx, ctx->d_apps.reserve(n_apps));
     GF_HIP(ctx, ctx->d_results.reserve(n_apps));
     GF_HIP(ctx, ctx->d_exec.reserve(total_k + 1));
@@ -733,14 +731,13 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     // Small independent batches of the plain packers skip the three staging copies: the kernel reads the app records from
     // the pinned staging buffer and writes results and placements straight into pinned host memory (posted PCIe writes,
     // visible when the kernel has completed).  A copy engine round trip costs more than the whole kernel at these sizes.
-    if (ctx->zero_copy && mode == GF_MODE_INDEPENDENT && ctx->have_orders &&
-        (!is_zone_algo(algo) || (ctx->zoned_fused && ctx->have_sched && ctx->n_zones + 1 <= 64)) &&
+    if (ctx->zero_copy && (route.kind == Route::kPlain || route.kind == Route::kZonedFused) &&
         (uint64_t)n_apps * sizeof(gf_app) + total_k * sizeof(uint32_t) <= (UINT64_C(4) << 20)) {
         void *da = ctx->h_apps.dev, *dr = ctx->h_results.dev, *de = ctx->h_exec.dev;
         if (da != nullptr && dr != nullptr && de != nullptr) {
             using clk = std::chrono::steady_clock;
             const auto t_staged = clk::now();
-            const int rc0 = launch(ctx, mode, algo, n_apps, ctx->h_apps.ptr, static_cast<const gf_app*>(da),
+            const int rc0 = launch(ctx, route, n_apps, ctx->h_apps.ptr, static_cast<const gf_app*>(da),
                                    static_cast<gf_result*>(dr), static_cast<uint32_t*>(de), total_k, ctx->d_failed.ptr, st);
             if (rc0 != GF_OK) return rc0;
             const auto t_launched = clk::now();
@@ -761,7 +758,7 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     // ---- FIFO chains of the plain packers on the solo kernel: resume from the last chain's checkpoints where the queues agree
     ChainRun run;
     ctx->planned_units.valid = false;
-    const bool use_cache = chain_plan(ctx, mode, algo, n_apps, ctx->h_apps.ptr, &run);
+    const bool use_cache = chain_plan(ctx, route, algo, n_apps, ctx->h_apps.ptr, &run);
     const uint32_t a0 = run.a_begin;
     const uint64_t k0 = a0 > 0 ? ctx->h_apps.ptr[a0].exec_off : 0;  // placements of the skipped prefix
     // The answers travel to the pinned host buffers by posted writes of a kernel when the buffers are device-mapped: three
@@ -784,7 +781,7 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
         GF_HIP(ctx, hipMemcpyAsync(ctx->d_apps.ptr + a0, ctx->h_apps.ptr + a0, (size_t)(n_apps - a0) * sizeof(gf_app),
                                    hipMemcpyHostToDevice, st));
     }
-    const int rc = launch(ctx, mode, algo, n_apps, ctx->h_apps.ptr, ctx->d_apps.ptr, ctx->d_results.ptr, ctx->d_exec.ptr,
+    const int rc = launch(ctx, route, n_apps, ctx->h_apps.ptr, ctx->d_apps.ptr, ctx->d_results.ptr, ctx->d_exec.ptr,
                           total_k, ctx->d_failed.ptr, st, use_cache ? &run : nullptr);
     const bool answers_sent = hio.active && hio.out_done;
     hio.active = false;
@@ -839,19 +836,13 @@ int gf_fit_feasible(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* ap
     if (!ctx) return GF_ERR_INVALID;
     if (n_apps > 0 && (!apps || !has_capacity)) return fail(ctx, GF_ERR_INVALID, "apps/has_capacity must not be NULL");
     if (n_apps == 0) return GF_OK;
-    const bool plain = algo == GF_ALGO_TIGHTLY_PACK || algo == GF_ALGO_DISTRIBUTE_EVENLY || algo == GF_ALGO_MINIMAL_FRAGMENTATION;
-    // the zone-aware packers as ONE launch (fit_zoned_fused_kernel: a workgroup per application decides every candidate view
-    // and chooses): served here too; their four-kernel route is not
-    const bool fused_zoned = is_zone_algo(algo) && ctx->zoned_fused && ctx->have_sched && ctx->n_zones + 1 <= 64;
-    if (!ctx->group.empty() || !(plain || fused_zoned)) {
-        // a multi-device context, or a route without a feasibility-only kernel: the full batch, of which only HasCapacity is
-        // handed on
+    // the plain packers and the one-launch zone route have a feasibility-only kernel.  A multi-device context, the four-kernel
+    // zone route or a refusal: the full batch, of which only HasCapacity is handed on (gf_fit_batch reports the refusal)
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    Route route;
+    if (!ctx->group.empty() || route_of(ctx, GF_MODE_INDEPENDENT, algo, &route) != GF_OK || route.kind == Route::kZonedFour) {
         uint64_t total_k = 0;
-        for (uint32_t a = 0; a < n_apps; ++a) {  // validated HERE: the sizes below come from it (gf_fit_batch checks the rest)
-            if (apps[a].k < 0 || apps[a].k > GF_MAX_K)
-                return fail(ctx, GF_ERR_INVALID, "apps[%u].k = %d outside [0, %d]", a, apps[a].k, GF_MAX_K);
-            total_k += (uint64_t)apps[a].k;
-        }
+        if (const int rc = check_apps(ctx, n_apps, apps, nullptr, &total_k); rc != GF_OK) return rc;  // the sizes below come from it
         std::vector<gf_result> res;
         std::vector<uint32_t> exec;
         try {  // no exception crosses the C ABI
@@ -866,26 +857,14 @@ int gf_fit_feasible(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* ap
         for (uint32_t a = 0; a < n_apps; ++a) has_capacity[a] = res[a].has_capacity ? 1 : 0;
         return GF_OK;
     }
-    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     GF_VIEW_ENTER(ctx)
     if (n_apps >= 0x80000000u) return fail(ctx, GF_ERR_INVALID, "n_apps = %u", n_apps);
-    if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a fit");
     using clk = std::chrono::steady_clock;
     const auto t_entry = clk::now();
     GF_HIP(ctx, hipSetDevice(ctx->device));
     GF_HIP(ctx, ctx->h_apps.reserve(n_apps));
-    uint64_t total_k = 0;
-    for (uint32_t a = 0; a < n_apps; ++a) {
-        const gf_app& in = apps[a];
-        if (in.k < 0 || in.k > GF_MAX_K) return fail(ctx, GF_ERR_INVALID, "apps[%u].k = %d outside [0, %d]", a, in.k, GF_MAX_K);
-        for (int j = 0; j < 3; ++j)
-            if (in.drv[j] < 0 || in.drv[j] >= GF_MAX_ABS_QUANTITY || in.exe[j] < 0 || in.exe[j] >= GF_MAX_ABS_QUANTITY)
-                return fail(ctx, GF_ERR_INVALID, "apps[%u] request outside [0, 2^62)", a);
-        gf_app& o = ctx->h_apps.ptr[a];
-        o = in;
-        o.exec_off = total_k;  // the placements are still made (same decision code): into device memory, where they stay
-        total_k += (uint64_t)in.k;
-    }
+    uint64_t total_k = 0;  // the placements are still made (same decision code): into device memory, where they stay
+    if (const int rc = check_apps(ctx, n_apps, apps, ctx->h_apps.ptr, &total_k); rc != GF_OK) return rc;
     const uint64_t half = total_k + 1;
     GF_HIP(ctx, ctx->d_feas_exec.reserve(total_k + 1));  // private to this entry point: see gf_ctx::d_feas_exec
     GF_HIP(ctx, ctx->d_feas_scratch.reserve(2 * half));
@@ -927,13 +906,10 @@ int gf_fit_feasible(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* ap
     if (announce) std::memset(ctx->h_feasible.ptr, kNotYet, n_apps);
     const auto t_staged = clk::now();
     hipError_t e;
-    if (fused_zoned) {
-        const uint32_t nz = ctx->n_zones;
-        const int inner = algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION ? GF_ALGO_MINIMAL_FRAGMENTATION : GF_ALGO_TIGHTLY_PACK;
-        e = ctx->d_feas_zexec.reserve(((uint64_t)nz + 1) * half);
-        gangfit::ZoneTable zt{ctx->d_zmasks.ptr, ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride, nz, ctx->zstride};
+    if (route.kind == Route::kZonedFused) {
+        e = ctx->d_feas_zexec.reserve(((uint64_t)ctx->n_zones + 1) * half);
         if (e == hipSuccess)
-            e = gangfit::launch_fit_zoned_fused(inner, algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), zt,
+            e = gangfit::launch_fit_zoned_fused(route.inner, route.az_aware, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), zone_table(ctx),
                                                 ctx->d_sched.ptr, ctx->d_feas_zexec.ptr, half, n_apps, d_apps, nullptr, nullptr,
                                                 ctx->d_feas_scratch.ptr, half, st, d_feas, ctx->d_feasible_sync.ptr, ctx->eff_nonneg);
     } else {
@@ -986,7 +962,9 @@ int gf_fit_batch_dev(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, c
     if (n_apps > 0 && (!d_apps || !d_results)) return fail(ctx, GF_ERR_INVALID, "device apps/results must not be NULL");
     if (mode == GF_MODE_FIFO_CHAIN && !d_chain_failed_at) d_chain_failed_at = ctx->d_failed.ptr;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    return launch(ctx, mode, algo, n_apps, nullptr, d_apps, d_results, d_exec_nodes, exec_nodes_len, d_chain_failed_at, st);
+    Route route;
+    if (const int rc = route_of(ctx, mode, algo, &route); rc != GF_OK) return rc;
+    return launch(ctx, route, n_apps, nullptr, d_apps, d_results, d_exec_nodes, exec_nodes_len, d_chain_failed_at, st);
 }
 
 

@@ -8,28 +8,31 @@ namespace gfapi {
 
 bool is_shard_zone_algo(gf_algo algo) { return algo == GF_ALGO_SINGLE_AZ_TIGHTLY_PACK || algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK; }
 
-// candidate views of a zone-aware batch: the zones of the evaluation list, plus the plain order for az-aware
-static uint32_t shard_views(const gf_ctx* ctx, gf_algo algo) {
-    return is_shard_zone_algo(algo) ? ctx->n_zones + (algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u) : 1u;
+// GF_OK when node-range sharding serves `algo` on this context (orders installed), else GF_ERR_UNSUPPORTED — with the reason
+// in ctx->err when `report` (the gf_shard_* steps; a multi-device context quietly runs the batch on its first device instead).
+static int shard_serves(gf_ctx* ctx, gf_algo algo, bool report) {
+    char why[256];
+    const uint32_t n_cand = candidate_views(ctx, algo);
+    if (!ctx->merged)
+        std::snprintf(why, sizeof why, "node-range sharding needs the merged slot layout (driver and executor orders must be "
+                                       "subsequences of one priority order)");
+    else if (algo != GF_ALGO_TIGHTLY_PACK && algo != GF_ALGO_DISTRIBUTE_EVENLY && !is_shard_zone_algo(algo))
+        std::snprintf(why, sizeof why, "node-range sharding serves tightly-pack, distribute-evenly, single-az-tightly-pack "
+                                       "and az-aware-tightly-pack only");
+    else if (is_shard_zone_algo(algo) && !ctx->have_sched)
+        std::snprintf(why, sizeof why, "zone-aware packers compare packing efficiencies: node-range sharding needs the "
+                                       "schedulable columns of gf_snapshot_set");
+    else if (is_shard_zone_algo(algo) && (n_cand == 0 || n_cand > 64))
+        std::snprintf(why, sizeof why, "node-range sharding of a zone-aware packer needs 1 to 64 candidate views (zones of "
+                                       "the evaluation list, plus one for az-aware), not %u", n_cand);
+    else
+        return GF_OK;
+    return report ? fail(ctx, GF_ERR_UNSUPPORTED, "%s", why) : GF_ERR_UNSUPPORTED;
 }
 
 int shard_ready(gf_ctx* ctx, gf_algo algo, gangfit::ShardRange* r) {
     if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a sharded fit");
-    if (!ctx->merged)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "node-range sharding needs the merged slot layout (driver and executor "
-                                             "orders must be subsequences of one priority order)");
-    if (algo != GF_ALGO_TIGHTLY_PACK && algo != GF_ALGO_DISTRIBUTE_EVENLY && !is_shard_zone_algo(algo))
-        return fail(ctx, GF_ERR_UNSUPPORTED, "node-range sharding serves tightly-pack, distribute-evenly, single-az-tightly-pack "
-                                             "and az-aware-tightly-pack only");
-    if (is_shard_zone_algo(algo)) {
-        if (!ctx->have_sched)
-            return fail(ctx, GF_ERR_UNSUPPORTED, "zone-aware packers compare packing efficiencies: node-range sharding needs the "
-                                                 "schedulable columns of gf_snapshot_set");
-        const uint32_t n_cand = shard_views(ctx, algo);
-        if (n_cand == 0 || n_cand > 64)
-            return fail(ctx, GF_ERR_UNSUPPORTED, "node-range sharding of a zone-aware packer needs 1 to 64 candidate views (zones of "
-                                                 "the evaluation list, plus one for az-aware), not %u", n_cand);
-    }
+    if (const int rc = shard_serves(ctx, algo, true); rc != GF_OK) return rc;
     const uint64_t xc = ((uint64_t)ctx->n_x + 63) / 64;  // chunks of the merged order (the sentinel slot hosts nothing)
     r->c_lo = (uint32_t)(xc * ctx->shard / ctx->n_shards);
     r->c_hi = (uint32_t)(xc * (ctx->shard + 1) / ctx->n_shards);
@@ -57,7 +60,7 @@ static const gangfit::ShardZones* shard_zones(gf_ctx* ctx, gf_algo algo, gangfit
     z->sched = ctx->d_sched.ptr;
     z->n_zones = ctx->n_zones;
     z->stride = ctx->zstride;
-    z->n_cand = shard_views(ctx, algo);
+    z->n_cand = candidate_views(ctx, algo);
     z->az_aware = algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u;
     return z;
 }
@@ -68,7 +71,7 @@ struct ShardLayout {
 };
 static ShardLayout shard_layout_of(const gf_ctx* ctx, gf_algo algo, uint64_t half) {
     if (is_shard_zone_algo(algo)) {
-        const uint32_t v = shard_views(ctx, algo);
+        const uint32_t v = candidate_views(ctx, algo);
         return ShardLayout{v, (uint64_t)v * half, (uint64_t)v * half};  // region c: view c's placement (slot + 1)
     }
     // [0, half) the placements, [half, 2 half) the capacities of distribute-evenly's pass 1
@@ -145,12 +148,8 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
     std::lock_guard<std::recursive_mutex> glock(g->mu);
     gf_ctx* const first = g->group[0];
     const bool zoned = is_shard_zone_algo(algo);
-    bool sharded = mode == GF_MODE_INDEPENDENT && (algo == GF_ALGO_TIGHTLY_PACK || algo == GF_ALGO_DISTRIBUTE_EVENLY || zoned) &&
-                   n_apps > 0 && !g->g_shard_off;
-    for (gf_ctx* s : g->group) {
-        sharded = sharded && s->have_orders && s->merged;
-        if (zoned) sharded = sharded && s->have_sched && shard_views(s, algo) >= 1 && shard_views(s, algo) <= 64;
-    }
+    bool sharded = mode == GF_MODE_INDEPENDENT && n_apps > 0 && !g->g_shard_off;
+    for (gf_ctx* s : g->group) sharded = sharded && s->have_orders && shard_serves(s, algo, false) == GF_OK;
     if (!sharded) {
         const int rc = gf_fit_batch(first, mode, algo, n_apps, apps, results, exec_nodes, exec_nodes_cap, chain_failed_at);
         if (rc != GF_OK) g->err = first->err;
@@ -163,17 +162,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
     GF_HIP(g, hipSetDevice(first->device));
     GF_HIP(g, g->h_apps.reserve(n_apps));
     uint64_t total_k = 0;
-    for (uint32_t a = 0; a < n_apps; ++a) {
-        const gf_app& in = apps[a];
-        if (in.k < 0 || in.k > GF_MAX_K) return fail(g, GF_ERR_INVALID, "apps[%u].k = %d outside [0, %d]", a, in.k, GF_MAX_K);
-        for (int j = 0; j < 3; ++j)
-            if (in.drv[j] < 0 || in.drv[j] >= GF_MAX_ABS_QUANTITY || in.exe[j] < 0 || in.exe[j] >= GF_MAX_ABS_QUANTITY)
-                return fail(g, GF_ERR_INVALID, "apps[%u] request outside [0, 2^62)", a);
-        gf_app& o = g->h_apps.ptr[a];
-        o = in;
-        o.exec_off = total_k;
-        total_k += (uint64_t)in.k;
-    }
+    if (const int rc = check_apps(g, n_apps, apps, g->h_apps.ptr, &total_k); rc != GF_OK) return rc;
     if (total_k > exec_nodes_cap || (total_k > 0 && !exec_nodes))
         return fail(g, GF_ERR_CAPACITY, "exec_nodes holds %llu entries, %llu needed", (unsigned long long)exec_nodes_cap,
                     (unsigned long long)total_k);

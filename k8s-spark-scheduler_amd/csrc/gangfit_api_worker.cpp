@@ -241,8 +241,7 @@ int worker_prepare(gf_ctx* ctx, gf_algo algo, uint64_t max_total_k, bool* need_l
     gf_ctx::Worker& w = ctx->worker;
     if (!ctx->group.empty() || ctx->view_of != nullptr)
         return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker serves plain contexts (no views, one device)");
-    if (algo != GF_ALGO_TIGHTLY_PACK && algo != GF_ALGO_DISTRIBUTE_EVENLY && algo != GF_ALGO_MINIMAL_FRAGMENTATION)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker serves the plain packers");
+    if (!is_plain_algo(algo)) return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker serves the plain packers");
     if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a fit");
     if (const int rc = worker_alloc(ctx); rc != GF_OK) return rc;
     if (const int rc = worker_revive(ctx); rc != GF_OK) return rc;
@@ -348,14 +347,7 @@ int gf_worker_fit(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* apps
     if (n_apps > 0 && (!apps || !results)) return fail(ctx, GF_ERR_INVALID, "apps/results must not be NULL");
     if (n_apps == 0) return GF_OK;
     uint64_t total_k = 0;
-    for (uint32_t a = 0; a < n_apps; ++a) {
-        const gf_app& in = apps[a];
-        if (in.k < 0 || in.k > GF_MAX_K) return fail(ctx, GF_ERR_INVALID, "apps[%u].k = %d outside [0, %d]", a, in.k, GF_MAX_K);
-        for (int j = 0; j < 3; ++j)
-            if (in.drv[j] < 0 || in.drv[j] >= GF_MAX_ABS_QUANTITY || in.exe[j] < 0 || in.exe[j] >= GF_MAX_ABS_QUANTITY)
-                return fail(ctx, GF_ERR_INVALID, "apps[%u] request outside [0, 2^62)", a);
-        total_k += (uint64_t)in.k;
-    }
+    if (const int rc = check_apps(ctx, n_apps, apps, nullptr, &total_k); rc != GF_OK) return rc;
     if (total_k > exec_nodes_cap || (total_k > 0 && !exec_nodes))
         return fail(ctx, GF_ERR_CAPACITY, "exec_nodes holds %llu entries, %llu needed", (unsigned long long)exec_nodes_cap,
                     (unsigned long long)total_k);

@@ -557,6 +557,9 @@ gangfit::SparseTable make_sparse(gf_ctx* ctx);
 gangfit::EffTables slot_eff_tables(gf_ctx* ctx, const int64_t* avail_base);
 bool reserves_executors(gf_algo algo);
 bool is_zone_algo(gf_algo algo);
+bool is_plain_algo(gf_algo algo);  // tightly-pack, distribute-evenly, minimal-fragmentation
+uint32_t candidate_views(const gf_ctx* ctx, gf_algo algo);
+int check_apps(gf_ctx* ctx, uint32_t n_apps, const gf_app* apps, gf_app* out, uint64_t* total_k);
 int ensure_cnt(gf_ctx* ctx, uint64_t n_decisions, hipStream_t stream);
 // gangfit_api_snapshot.cpp
 int materialize_host(gf_ctx* ctx);

@@ -281,7 +281,6 @@ struct ZoneBuffers {
     double* zavg;         // [n_apps * n_zones][4]
     uint32_t* cnt;        // [n_cnt_waves][n_slots] zero between launches: per-wave executor multiplicity scratch
     uint32_t n_cnt_waves;
-    double* avg_out;      // [n_apps][4] AvgPackingEfficiency of the chosen result (zeros when infeasible); nullable
 };
 hipError_t launch_fit_zoned(int inner_algo, bool az_aware, bool reserve_execs, const NodeTable& table,
                             const ZoneTable& zones, const EffTables& eff, const ZoneBuffers& buf, uint32_t n_apps,
@@ -298,11 +297,11 @@ hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const NodeTable
                                   uint32_t* d_feasible_sync = nullptr,  // (feasibility only: as launch_fit_independent)
                                   bool eff_nonneg = false);  // feasibility only: no node's efficiency can be negative (gf_ctx::eff_nonneg)
 
-// FIFO chain for any packer (zone-aware ones included): one workgroup, one wavefront per candidate view of the current
-// app (each zone, plus the plain pack for az-aware), working table in global memory.  buf.zexec needs
-// (n_zones + 1) rows, buf.cnt at least 16 rows.  Writes final results / placements as node indices.
-hipError_t launch_fit_fifo_generic(int inner_algo, bool zoned, bool az_aware, bool reserve_execs, const NodeTable& table,
-                                   const ZoneTable& zones, const int64_t* d_sched, const ZoneBuffers& buf,
+// FIFO chain of the zone-aware and minimal-fragmentation packers: one workgroup, one wavefront per candidate view of the
+// current app (each zone, plus the plain pack for az-aware), working table in global memory.  d_zexec needs (n_zones + 1)
+// rows of zexec_stride, d_cnt (zoned) at least 16 rows of ZoneBuffers::cnt.  Writes final results / placements as node indices.
+hipError_t launch_fit_fifo_generic(int inner_algo, bool zoned, bool az_aware, const NodeTable& table, const ZoneTable& zones,
+                                   const int64_t* d_sched, uint32_t* d_zexec, uint64_t zexec_stride, uint32_t* d_cnt,
                                    uint32_t n_apps, const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes,
                                    uint32_t* d_scratch, uint64_t scratch_half, int32_t* d_chain_failed_at,
                                    const int32_t* d_run_if, hipStream_t stream);

@@ -1776,17 +1776,24 @@ hipError_t raise_dynamic_lds(const void* kernel, size_t lds) {
     return e;
 }
 
+// Turns a run-time choice into a template argument: f(std::integral_constant<..., V>{}) for the V of the list that equals v,
+// hipErrorInvalidValue when none does.  with_value<true, false>(flag, f); nest the calls for several choices.
+template <auto... Vs, class T, class F>
+hipError_t with_value(T v, F&& f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Vs ? (e = f(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...);
+    return e;
+}
+
+// a wavefront per application
+inline dim3 app_grid(uint32_t n_apps) { return dim3((n_apps + kWavesPerBlock - 1) / kWavesPerBlock); }
+
 }  // namespace
 
 hipError_t worker_blocks_per_cu(gf_algo algo, int* out) {
-    const int threads = kWave * kWorkerWaves;
-    if (algo == GF_ALGO_TIGHTLY_PACK)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fit_worker_kernel<GF_ALGO_TIGHTLY_PACK>, threads, 0);
-    if (algo == GF_ALGO_DISTRIBUTE_EVENLY)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fit_worker_kernel<GF_ALGO_DISTRIBUTE_EVENLY>, threads, 0);
-    if (algo == GF_ALGO_MINIMAL_FRAGMENTATION)
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fit_worker_kernel<GF_ALGO_MINIMAL_FRAGMENTATION>, threads, 0);
-    return hipErrorInvalidValue;
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY, GF_ALGO_MINIMAL_FRAGMENTATION>(algo, [&](auto A) {
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fit_worker_kernel<A>, kWave * kWorkerWaves, 0);
+    });
 }
 
 hipError_t launch_fit_worker(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const WorkerArgs& args,
@@ -1794,15 +1801,10 @@ hipError_t launch_fit_worker(gf_algo algo, const NodeTable& table, const SparseT
     if (args.sets == 0 || args.blocks_per_set == 0 || args.host == nullptr || args.dev == nullptr) return hipErrorInvalidValue;
     const dim3 block(kWave * kWorkerWaves);
     const dim3 grid(1u + args.sets * args.blocks_per_set);
-    if (algo == GF_ALGO_TIGHTLY_PACK)
-        hipLaunchKernelGGL(fit_worker_kernel<GF_ALGO_TIGHTLY_PACK>, grid, block, 0, stream, table, gpu_view, args);
-    else if (algo == GF_ALGO_DISTRIBUTE_EVENLY)
-        hipLaunchKernelGGL(fit_worker_kernel<GF_ALGO_DISTRIBUTE_EVENLY>, grid, block, 0, stream, table, gpu_view, args);
-    else if (algo == GF_ALGO_MINIMAL_FRAGMENTATION)
-        hipLaunchKernelGGL(fit_worker_kernel<GF_ALGO_MINIMAL_FRAGMENTATION>, grid, block, 0, stream, table, gpu_view, args);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY, GF_ALGO_MINIMAL_FRAGMENTATION>(algo, [&](auto A) {
+        hipLaunchKernelGGL(fit_worker_kernel<A>, grid, block, 0, stream, table, gpu_view, args);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_fit_independent(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, uint32_t n_apps,
@@ -1814,25 +1816,18 @@ hipError_t launch_fit_independent(gf_algo algo, const NodeTable& table, const Sp
     const dim3 block(kWave * kWavesPerBlock);
     // (minimal-fragmentation: a workgroup per application — its wavefronts share the passes over the executor order)
     const bool team = algo == GF_ALGO_MINIMAL_FRAGMENTATION;
-    const dim3 grid(team ? n_apps : (n_apps + kWavesPerBlock - 1) / kWavesPerBlock);
+    const dim3 grid(team ? n_apps : app_grid(n_apps).x);
     const dim3 grid_feas(grid.x + 1);  // + the collecting workgroup
-#define GF_IND(ALGO)                                                                                                               \
-    if (d_feasible != nullptr)                                                                                                     \
-        hipLaunchKernelGGL((fit_independent_kernel<ALGO, true>), grid_feas, block, 0, stream, table, gpu_view, n_apps, d_apps,      \
-                           reinterpret_cast<gf_result*>(d_feasible), d_exec_nodes, d_scratch, scratch_half,                        \
-                           reinterpret_cast<ScanStats*>(d_feasible_sync));                                                         \
-    else                                                                                                                           \
-        hipLaunchKernelGGL((fit_independent_kernel<ALGO, false>), grid, block, 0, stream, table, gpu_view, n_apps, d_apps,          \
-                           d_results, d_exec_nodes, d_scratch, scratch_half, d_stats)
-    if (algo == GF_ALGO_TIGHTLY_PACK) {
-        GF_IND(GF_ALGO_TIGHTLY_PACK);
-    } else if (algo == GF_ALGO_MINIMAL_FRAGMENTATION) {
-        GF_IND(GF_ALGO_MINIMAL_FRAGMENTATION);
-    } else {
-        GF_IND(GF_ALGO_DISTRIBUTE_EVENLY);
-    }
-#undef GF_IND
-    return hipGetLastError();
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY, GF_ALGO_MINIMAL_FRAGMENTATION>(algo, [&](auto A) {
+        if (d_feasible != nullptr)
+            hipLaunchKernelGGL((fit_independent_kernel<A, true>), grid_feas, block, 0, stream, table, gpu_view, n_apps, d_apps,
+                               reinterpret_cast<gf_result*>(d_feasible), d_exec_nodes, d_scratch, scratch_half,
+                               reinterpret_cast<ScanStats*>(d_feasible_sync));
+        else
+            hipLaunchKernelGGL((fit_independent_kernel<A, false>), grid, block, 0, stream, table, gpu_view, n_apps, d_apps,
+                               d_results, d_exec_nodes, d_scratch, scratch_half, d_stats);
+        return hipGetLastError();
+    });
 }
 
 size_t fifo_v2_lds_bytes(uint32_t lds_slots, uint32_t n_chunks) {
@@ -1901,11 +1896,10 @@ hipError_t launch_v2(const FifoPlan& P, const NodeTable& T, uint32_t n_apps, con
                      const int32_t* guard, hipStream_t stream) {
     const size_t lds = fifo_v2_lds_bytes(P.lds_slots_v2, T.n_chunks);
     constexpr int NW = 16;
-    if (T.d_identity)
-        return launch_one_workgroup(fit_fifo_chain_kernel<ALGO, NW, true>, NW, lds, stream, T, P.lds_slots_v2, n_apps, d_apps,
+    return with_value<true, false>(T.d_identity != 0, [&](auto ID) {
+        return launch_one_workgroup(fit_fifo_chain_kernel<ALGO, NW, ID>, NW, lds, stream, T, P.lds_slots_v2, n_apps, d_apps,
                                     d_results, d_exec_nodes, d_scratch, half, d_failed, d_stats, guard);
-    return launch_one_workgroup(fit_fifo_chain_kernel<ALGO, NW, false>, NW, lds, stream, T, P.lds_slots_v2, n_apps, d_apps,
-                                d_results, d_exec_nodes, d_scratch, half, d_failed, d_stats, guard);
+    });
 }
 
 template <int ALGO>
@@ -1916,16 +1910,12 @@ hipError_t launch_solo(const FifoPlan& P, const NodeTable& T, const NarrowTable&
     const size_t lds = fifo_solo_lds_bytes(P.lds_slots_solo, T.n_chunks);
     constexpr int NW = kSoloWaves;  // wavefront 0 walks the chain; all of them share the prologue, the checkpoints and the epilogue
     const bool resident = P.lds_slots_solo >= T.n_slots;
-#define GF_SOLO(PR, RE)                                                                                                     \
-    return launch_one_workgroup(fit_fifo_solo_kernel<ALGO, NW, PR, RE>, NW, lds, stream, T, NT, P.lds_slots_solo, n_apps,    \
-                                d_napps, d_wide_needed, d_results, d_exec_nodes, d_scratch, half, d_failed, ck, F, d_stats)
-    if (d_stats != nullptr) {
-        if (resident) GF_SOLO(true, true);
-        GF_SOLO(true, false);
-    }
-    if (resident) GF_SOLO(false, true);
-    GF_SOLO(false, false);
-#undef GF_SOLO
+    return with_value<true, false>(d_stats != nullptr, [&](auto PR) {
+        return with_value<true, false>(resident, [&](auto RE) {
+            return launch_one_workgroup(fit_fifo_solo_kernel<ALGO, NW, PR, RE>, NW, lds, stream, T, NT, P.lds_slots_solo, n_apps,
+                                        d_napps, d_wide_needed, d_results, d_exec_nodes, d_scratch, half, d_failed, ck, F, d_stats);
+        });
+    });
 }
 
 template <int ALGO>
@@ -1967,9 +1957,7 @@ hipError_t launch_fifo_algo(const FifoPlan& P, const NodeTable& T, const NarrowT
         e = launch_v2<ALGO>(P, T, n_apps, d_apps, d_results, d_exec_nodes, d_scratch, half, d_failed, d_stats, guard, stream);
         if (e != hipSuccess) return e;
     }
-    const dim3 block(kWave * kWavesPerBlock);
-    const dim3 grid((n_apps + kWavesPerBlock - 1) / kWavesPerBlock);
-    hipLaunchKernelGGL(expand_translate_kernel, grid, block, 0, stream, T.slot_node, n_apps, d_apps, d_results,
+    hipLaunchKernelGGL(expand_translate_kernel, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, T.slot_node, n_apps, d_apps, d_results,
                        d_exec_nodes, d_scratch, chain_out_of(io, d_failed));
     return hipGetLastError();
 }
@@ -1982,13 +1970,10 @@ hipError_t launch_fit_fifo(gf_algo algo, const FifoPlan& plan, const NodeTable& 
                            ScanStats* d_stats, hipStream_t stream) {
     if (n_apps == 0) return hipSuccess;
     if (!plan.narrow && !plan.wide) return hipErrorInvalidValue;
-    if (algo == GF_ALGO_TIGHTLY_PACK)
-        return launch_fifo_algo<GF_ALGO_TIGHTLY_PACK>(plan, table, ntable, n_apps, d_apps, d_napps, d_wide_needed, d_results,
-                                                      d_exec_nodes, d_scratch, scratch_half, heads_lo, d_chain_failed_at, ckpt,
-                                                      io, d_stats, stream);
-    return launch_fifo_algo<GF_ALGO_DISTRIBUTE_EVENLY>(plan, table, ntable, n_apps, d_apps, d_napps, d_wide_needed, d_results,
-                                                       d_exec_nodes, d_scratch, scratch_half, heads_lo, d_chain_failed_at, ckpt,
-                                                       io, d_stats, stream);
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
+        return launch_fifo_algo<A>(plan, table, ntable, n_apps, d_apps, d_napps, d_wide_needed, d_results, d_exec_nodes, d_scratch,
+                                   scratch_half, heads_lo, d_chain_failed_at, ckpt, io, d_stats, stream);
+    });
 }
 
 hipError_t launch_fit_zoned(int inner_algo, bool az_aware, bool reserve_execs, const NodeTable& table,
@@ -1999,48 +1984,35 @@ hipError_t launch_fit_zoned(int inner_algo, bool az_aware, bool reserve_execs, c
     if (inner_algo != GF_ALGO_TIGHTLY_PACK && inner_algo != GF_ALGO_MINIMAL_FRAGMENTATION) return hipErrorInvalidValue;
     if (az_aware && inner_algo != GF_ALGO_TIGHTLY_PACK) return hipErrorInvalidValue;
     const dim3 block(kWave * kWavesPerBlock);
-    const dim3 app_grid((n_apps + kWavesPerBlock - 1) / kWavesPerBlock);
     hipError_t e = hipSuccess;
     if (az_aware) {  // the plain TightlyPack answer first; the select kernel overwrites it where a zone wins
         e = launch_fit_independent(GF_ALGO_TIGHTLY_PACK, table, SparseTable{}, n_apps, d_apps, d_results, d_exec_nodes,
                                    d_scratch, scratch_half, nullptr, stream);
         if (e != hipSuccess) return e;
-        if (buf.avg_out != nullptr) {
-            e = launch_avg_efficiency(true, table, eff, buf.cnt, buf.n_cnt_waves, n_apps, d_apps, d_results,
-                                      d_exec_nodes, buf.avg_out, stream);
-            if (e != hipSuccess) return e;
-        }
     }
     if (zones.n_zones > 0) {
         const uint64_t n_dec = (uint64_t)n_apps * zones.n_zones;
         const dim3 dec_grid((unsigned)((n_dec + kWavesPerBlock - 1) / kWavesPerBlock));
-        if (inner_algo == GF_ALGO_MINIMAL_FRAGMENTATION)
-            hipLaunchKernelGGL(fit_zoned_kernel<GF_ALGO_MINIMAL_FRAGMENTATION>, dec_grid, block, 0, stream, table, zones,
-                               n_apps, d_apps, buf.zres, buf.zexec, buf.zexec_stride, d_scratch, scratch_half);
-        else
-            hipLaunchKernelGGL(fit_zoned_kernel<GF_ALGO_TIGHTLY_PACK>, dec_grid, block, 0, stream, table, zones, n_apps,
-                               d_apps, buf.zres, buf.zexec, buf.zexec_stride, d_scratch, scratch_half);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        const dim3 eff_grid((buf.n_cnt_waves + kWavesPerBlock - 1) / kWavesPerBlock);
-        if (reserve_execs)
-            hipLaunchKernelGGL((avg_efficiency_kernel<true, true>), eff_grid, block, 0, stream, eff, table.node_slot,
+        e = with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_MINIMAL_FRAGMENTATION>(inner_algo, [&](auto A) {
+            hipLaunchKernelGGL(fit_zoned_kernel<A>, dec_grid, block, 0, stream, table, zones, n_apps, d_apps, buf.zres, buf.zexec,
+                               buf.zexec_stride, d_scratch, scratch_half);
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return e;
+        e = with_value<true, false>(reserve_execs, [&](auto RE) {
+            hipLaunchKernelGGL((avg_efficiency_kernel<RE, true>), app_grid(buf.n_cnt_waves), block, 0, stream, eff, table.node_slot,
                                table.n_slots, zones.n_zones, n_apps, d_apps, (const gf_result*)buf.zres,
                                (const uint32_t*)buf.zexec, buf.zexec_stride, buf.cnt, buf.n_cnt_waves, buf.zavg);
-        else
-            hipLaunchKernelGGL((avg_efficiency_kernel<false, true>), eff_grid, block, 0, stream, eff, table.node_slot,
-                               table.n_slots, zones.n_zones, n_apps, d_apps, (const gf_result*)buf.zres,
-                               (const uint32_t*)buf.zexec, buf.zexec_stride, buf.cnt, buf.n_cnt_waves, buf.zavg);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
+            return hipGetLastError();
+        });
+        if (e != hipSuccess) return e;
     }
-    if (az_aware)
-        hipLaunchKernelGGL(zone_select_kernel<true>, app_grid, block, 0, stream, table.slot_node, zones.n_zones, n_apps,
+    return with_value<true, false>(az_aware, [&](auto AZ) {
+        hipLaunchKernelGGL(zone_select_kernel<AZ>, app_grid(n_apps), block, 0, stream, table.slot_node, zones.n_zones, n_apps,
                            d_apps, (const gf_result*)buf.zres, (const uint32_t*)buf.zexec, buf.zexec_stride,
-                           (const double*)buf.zavg, d_results, d_exec_nodes, buf.avg_out);
-    else
-        hipLaunchKernelGGL(zone_select_kernel<false>, app_grid, block, 0, stream, table.slot_node, zones.n_zones, n_apps,
-                           d_apps, (const gf_result*)buf.zres, (const uint32_t*)buf.zexec, buf.zexec_stride,
-                           (const double*)buf.zavg, d_results, d_exec_nodes, buf.avg_out);
-    return hipGetLastError();
+                           (const double*)buf.zavg, d_results, d_exec_nodes, (double*)nullptr);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const NodeTable& table, const SparseTable& gpu_view, const ZoneTable& zones,
@@ -2057,27 +2029,24 @@ hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const NodeTable
     const dim3 grid(n_apps), grid_feas(n_apps + 1) /* + the collecting workgroup */, block(kWave * kFusedWaves);
     // feasibility only (gf_fit_feasible): d_results is not written, d_exec_nodes receives nothing; d_feasible / d_feasible_sync
     // as for launch_fit_independent
-#define GF_FUSED(ALGO, AZ)                                                                                                      \
-    if (d_feasible != nullptr)                                                                                                  \
-        hipLaunchKernelGGL((fit_zoned_fused_kernel<ALGO, AZ, true>), grid_feas, block, 0, stream, table, gpu_view, zones, d_sched, n_apps, \
-                           d_apps, reinterpret_cast<gf_result*>(d_feasible), d_feasible_sync, d_zexec, zexec_stride, d_scratch, \
-                           scratch_half, nonneg);                                                                               \
-    else                                                                                                                        \
-        hipLaunchKernelGGL((fit_zoned_fused_kernel<ALGO, AZ, false>), grid, block, 0, stream, table, gpu_view, zones, d_sched, n_apps,     \
-                           d_apps, d_results, d_exec_nodes, d_zexec, zexec_stride, d_scratch, scratch_half, 0u)
-    if (inner_algo == GF_ALGO_MINIMAL_FRAGMENTATION) {
-        GF_FUSED(GF_ALGO_MINIMAL_FRAGMENTATION, false);
-    } else if (az_aware) {
-        GF_FUSED(GF_ALGO_TIGHTLY_PACK, true);
-    } else {
-        GF_FUSED(GF_ALGO_TIGHTLY_PACK, false);
-    }
-#undef GF_FUSED
-    return hipGetLastError();
+    auto fused = [&](auto A, auto AZ) {
+        if (d_feasible != nullptr)
+            hipLaunchKernelGGL((fit_zoned_fused_kernel<A, AZ, true>), grid_feas, block, 0, stream, table, gpu_view, zones, d_sched,
+                               n_apps, d_apps, reinterpret_cast<gf_result*>(d_feasible), d_feasible_sync, d_zexec, zexec_stride,
+                               d_scratch, scratch_half, nonneg);
+        else
+            hipLaunchKernelGGL((fit_zoned_fused_kernel<A, AZ, false>), grid, block, 0, stream, table, gpu_view, zones, d_sched,
+                               n_apps, d_apps, d_results, d_exec_nodes, d_zexec, zexec_stride, d_scratch, scratch_half, 0u);
+        return hipGetLastError();
+    };
+    using TP = std::integral_constant<int, GF_ALGO_TIGHTLY_PACK>;
+    if (inner_algo == GF_ALGO_MINIMAL_FRAGMENTATION)
+        return fused(std::integral_constant<int, GF_ALGO_MINIMAL_FRAGMENTATION>{}, std::false_type{});
+    return az_aware ? fused(TP{}, std::true_type{}) : fused(TP{}, std::false_type{});
 }
 
-hipError_t launch_fit_fifo_generic(int inner_algo, bool zoned, bool az_aware, bool reserve_execs, const NodeTable& table,
-                                   const ZoneTable& zones, const int64_t* d_sched, const ZoneBuffers& buf,
+hipError_t launch_fit_fifo_generic(int inner_algo, bool zoned, bool az_aware, const NodeTable& table, const ZoneTable& zones,
+                                   const int64_t* d_sched, uint32_t* d_zexec, uint64_t zexec_stride, uint32_t* d_cnt,
                                    uint32_t n_apps, const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes,
                                    uint32_t* d_scratch, uint64_t scratch_half, int32_t* d_chain_failed_at,
                                    const int32_t* d_run_if, hipStream_t stream) {
@@ -2085,38 +2054,21 @@ hipError_t launch_fit_fifo_generic(int inner_algo, bool zoned, bool az_aware, bo
     const uint32_t n_cand = zoned ? zones.n_zones + (az_aware ? 1u : 0u) : 1u;
     if (n_cand > 64) return hipErrorInvalidValue;
     const uint32_t n_waves = n_cand < 1 ? 1 : (n_cand > 16 ? 16 : n_cand);
-    const dim3 grid(1), block(kWave * n_waves);
-#define GF_GEN(ALGO, ZO, AZ, RE)                                                                                        \
-    hipLaunchKernelGGL((fit_fifo_generic_kernel<ALGO, ZO, AZ, RE>), grid, block, 0, stream, table, zones, d_sched, n_apps, \
-                       d_apps, d_results, d_exec_nodes, buf.zexec, buf.zexec_stride, d_scratch, scratch_half, buf.cnt,  \
-                       d_chain_failed_at, d_run_if)
-    if (!zoned) {
-        if (inner_algo == GF_ALGO_TIGHTLY_PACK)
-            GF_GEN(GF_ALGO_TIGHTLY_PACK, false, false, true);
-        else if (inner_algo == GF_ALGO_DISTRIBUTE_EVENLY)
-            GF_GEN(GF_ALGO_DISTRIBUTE_EVENLY, false, false, true);
-        else if (inner_algo == GF_ALGO_MINIMAL_FRAGMENTATION)
-            GF_GEN(GF_ALGO_MINIMAL_FRAGMENTATION, false, false, false);
-        else
-            return hipErrorInvalidValue;
-    } else {
-        (void)reserve_execs;
-        if (inner_algo == GF_ALGO_MINIMAL_FRAGMENTATION && !az_aware)
-            GF_GEN(GF_ALGO_MINIMAL_FRAGMENTATION, true, false, false);  // minimalFragmentation reserves the driver only
-        else if (inner_algo != GF_ALGO_TIGHTLY_PACK)
-            return hipErrorInvalidValue;
-        else if (az_aware)
-            GF_GEN(GF_ALGO_TIGHTLY_PACK, true, true, true);
-        else
-            GF_GEN(GF_ALGO_TIGHTLY_PACK, true, false, true);
-    }
-#undef GF_GEN
-    return hipGetLastError();
+    auto gen = [&](auto A, auto ZO, auto AZ, auto RE) {
+        hipLaunchKernelGGL((fit_fifo_generic_kernel<A, ZO, AZ, RE>), dim3(1), dim3(kWave * n_waves), 0, stream, table, zones, d_sched,
+                           n_apps, d_apps, d_results, d_exec_nodes, d_zexec, zexec_stride, d_scratch, scratch_half, d_cnt,
+                           d_chain_failed_at, d_run_if);
+        return hipGetLastError();
+    };
+    using std::false_type, std::true_type;
+    using TP = std::integral_constant<int, GF_ALGO_TIGHTLY_PACK>;
+    using MF = std::integral_constant<int, GF_ALGO_MINIMAL_FRAGMENTATION>;
+    // minimal-fragmentation, plain or single-AZ (minimalFragmentation reserves the driver only); the zone-aware tightly-pack packers
+    if (inner_algo == GF_ALGO_MINIMAL_FRAGMENTATION && !az_aware)
+        return zoned ? gen(MF{}, true_type{}, false_type{}, false_type{}) : gen(MF{}, false_type{}, false_type{}, false_type{});
+    if (inner_algo != GF_ALGO_TIGHTLY_PACK || !zoned) return hipErrorInvalidValue;
+    return az_aware ? gen(TP{}, true_type{}, true_type{}, true_type{}) : gen(TP{}, true_type{}, false_type{}, true_type{});
 }
-
-namespace {
-inline dim3 app_grid_of(uint32_t n_apps) { return dim3((n_apps + kWavesPerBlock - 1) / kWavesPerBlock); }
-}  // namespace
 
 size_t fifo_zoned_lds_bytes(uint32_t lds_slots, uint32_t n_chunks, uint32_t n_zones, uint32_t n_cand, uint32_t n_shapes) {
     return fifo_zoned_fixed_lds(n_chunks, n_zones + 1, (uint32_t)fifo_zoned_waves(n_cand), n_shapes) + 12 * (size_t)lds_slots;
@@ -2140,36 +2092,17 @@ hipError_t launch_fit_fifo_zoned_lds(bool az_aware, const NodeTable& table, cons
     // ... plus one that expands the winner's placement next to the commit (none left with 16 views)
     const int wg_waves = fifo_zoned_waves(n_cand);
     const bool res = lds_slots >= table.n_slots;  // the whole table in LDS: the global-tail branch of every slot access compiles away
-#define GF_ZL2(AZ, NWV, RS)                                                                                                     \
-    e = launch_one_workgroup(fit_fifo_zoned_lds_kernel<AZ, NWV, RS>, NWV, lds, stream, table, ntable, zones, d_sched, lds_slots, \
-                             n_apps, n_shapes, d_apps, (const NApp*)d_napps, (const int32_t*)d_wide_needed, d_results,          \
-                             d_exec_nodes, d_spill, spill_stride, d_chain_failed_at, ck, d_stats)
-#define GF_ZL(AZ, NWV)       \
-    if (res)                 \
-        GF_ZL2(AZ, NWV, true); \
-    else                     \
-        GF_ZL2(AZ, NWV, false)
-    if (az_aware) {
-        if (wg_waves == 4) {
-            GF_ZL(true, 4);
-        } else if (wg_waves == 8) {
-            GF_ZL(true, 8);
-        } else {
-            GF_ZL(true, 16);
-        }
-    } else {
-        if (wg_waves == 4) {
-            GF_ZL(false, 4);
-        } else if (wg_waves == 8) {
-            GF_ZL(false, 8);
-        } else {
-            GF_ZL(false, 16);
-        }
-    }
-#undef GF_ZL
-#undef GF_ZL2
+    e = with_value<true, false>(az_aware, [&](auto AZ) {
+        return with_value<4, 8, 16>(wg_waves, [&](auto NWV) {
+            return with_value<true, false>(res, [&](auto RS) {
+                return launch_one_workgroup(fit_fifo_zoned_lds_kernel<AZ, NWV, RS>, NWV, lds, stream, table, ntable, zones, d_sched,
+                                            lds_slots, n_apps, n_shapes, d_apps, (const NApp*)d_napps, (const int32_t*)d_wide_needed,
+                                            d_results, d_exec_nodes, d_spill, spill_stride, d_chain_failed_at, ck, d_stats);
+            });
+        });
+    });
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(zoned_translate_kernel, app_grid_of(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, table.slot_node,
+    hipLaunchKernelGGL(zoned_translate_kernel, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, table.slot_node,
                        n_apps, d_apps, d_results, d_exec_nodes, (const int32_t*)d_wide_needed, chain_out_of(io, d_chain_failed_at));
     return hipGetLastError();
 }
@@ -2203,32 +2136,18 @@ hipError_t launch_fit_fifo_minfrag_lds(bool zoned, const NodeTable& table, const
     // ... and the whole table sits in LDS: on a 100 000-node table the block-cooperative parts (row fills, checkpoint dumps,
     // patches) want the sixteen (measured: 9.7 -> 10.2 ms plain, 15.0 -> 16.6 ms with three zones on eight)
     const bool eight = res && fifo_minfrag_waves(n_cand_mf) == 8u;
-#define GF_MFL2(ZO, RS, NWV)                                                                                                   \
-    e = launch_one_workgroup(fit_fifo_minfrag_lds_kernel<ZO, RS, NWV>, NWV, lds, stream, table, ntable, zones, d_sched,         \
-                             lds_slots, n_apps, n_shapes, n_idx, d_apps, (const NApp*)d_napps, (const int32_t*)d_wide_needed,  \
-                             d_results, d_exec_nodes, d_spill, spill_stride, d_chain_failed_at, d_capmat, d_hist, ck, d_stats)
-#define GF_MFL(ZO, RS)          \
-    if (eight)                  \
-        GF_MFL2(ZO, RS, 8);     \
-    else                        \
-        GF_MFL2(ZO, RS, (int)kMfNWmax)
-    if (zoned) {
-        if (res) {
-            GF_MFL(true, true);
-        } else {
-            GF_MFL(true, false);
-        }
-    } else {
-        if (res) {
-            GF_MFL(false, true);
-        } else {
-            GF_MFL(false, false);
-        }
-    }
-#undef GF_MFL2
-#undef GF_MFL
+    e = with_value<true, false>(zoned, [&](auto ZO) {
+        return with_value<true, false>(res, [&](auto RS) {
+            return with_value<8, (int)kMfNWmax>(eight ? 8 : (int)kMfNWmax, [&](auto NWV) {
+                return launch_one_workgroup(fit_fifo_minfrag_lds_kernel<ZO, RS, NWV>, NWV, lds, stream, table, ntable, zones, d_sched,
+                                            lds_slots, n_apps, n_shapes, n_idx, d_apps, (const NApp*)d_napps,
+                                            (const int32_t*)d_wide_needed, d_results, d_exec_nodes, d_spill, spill_stride,
+                                            d_chain_failed_at, d_capmat, d_hist, ck, d_stats);
+            });
+        });
+    });
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(zoned_translate_kernel, app_grid_of(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, table.slot_node,
+    hipLaunchKernelGGL(zoned_translate_kernel, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, table.slot_node,
                        n_apps, d_apps, d_results, d_exec_nodes, (const int32_t*)d_wide_needed, chain_out_of(io, d_chain_failed_at));
     return hipGetLastError();
 }
@@ -2238,17 +2157,12 @@ hipError_t launch_avg_efficiency(bool reserve_execs, const NodeTable& table, con
                                  const gf_result* d_results, const uint32_t* d_exec_nodes, double* d_avg_out,
                                  hipStream_t stream) {
     if (n_apps == 0) return hipSuccess;
-    const dim3 block(kWave * kWavesPerBlock);
-    const dim3 grid((n_cnt_waves + kWavesPerBlock - 1) / kWavesPerBlock);
-    if (reserve_execs)
-        hipLaunchKernelGGL((avg_efficiency_kernel<true, false>), grid, block, 0, stream, eff, table.node_slot,
-                           table.n_slots, 1u, n_apps, d_apps, d_results, d_exec_nodes, (uint64_t)0, d_cnt, n_cnt_waves,
-                           d_avg_out);
-    else
-        hipLaunchKernelGGL((avg_efficiency_kernel<false, false>), grid, block, 0, stream, eff, table.node_slot,
-                           table.n_slots, 1u, n_apps, d_apps, d_results, d_exec_nodes, (uint64_t)0, d_cnt, n_cnt_waves,
-                           d_avg_out);
-    return hipGetLastError();
+    return with_value<true, false>(reserve_execs, [&](auto RE) {
+        hipLaunchKernelGGL((avg_efficiency_kernel<RE, false>), app_grid(n_cnt_waves), dim3(kWave * kWavesPerBlock), 0, stream, eff,
+                           table.node_slot, table.n_slots, 1u, n_apps, d_apps, d_results, d_exec_nodes, (uint64_t)0, d_cnt,
+                           n_cnt_waves, d_avg_out);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_node_efficiencies(bool reserve_execs, const EffTables& eff_by_node, uint32_t n_nodes, int32_t k,
@@ -2271,16 +2185,10 @@ hipError_t launch_node_efficiencies(bool reserve_execs, const EffTables& eff_by_
 }
 
 // ---- node-range sharding (gangfit_shard.inc)
-namespace {
-inline dim3 app_grid(uint32_t n_apps) { return dim3((n_apps + kWavesPerBlock - 1) / kWavesPerBlock); }
-}  // namespace
-
-inline dim3 shard_grid(uint32_t n_apps, const ShardSet& set) { return dim3((n_apps + kWavesPerBlock - 1) / kWavesPerBlock, set.n); }
+inline dim3 shard_grid(uint32_t n_apps, const ShardSet& set) { return dim3(app_grid(n_apps).x, set.n); }
 
 // (zone-aware views: grid z = candidate view)
-inline dim3 shard_grid(uint32_t n_apps, const ShardSet& set, const ShardZones& z) {
-    return dim3((n_apps + kWavesPerBlock - 1) / kWavesPerBlock, set.n, z.n_cand);
-}
+inline dim3 shard_grid(uint32_t n_apps, const ShardSet& set, const ShardZones& z) { return dim3(app_grid(n_apps).x, set.n, z.n_cand); }
 inline bool shard_zones_ok(const ShardZones* z) { return z->n_cand >= 1 && z->n_cand <= 64 && z->n_zones + (z->az_aware ? 1u : 0u) == z->n_cand; }
 
 hipError_t launch_shard_partials(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
@@ -2292,13 +2200,13 @@ hipError_t launch_shard_partials(gf_algo algo, const NodeTable& table, const Spa
         if (!shard_zones_ok(zones)) return hipErrorInvalidValue;
         hipLaunchKernelGGL(shard_partials_zoned_kernel, shard_grid(n_apps, set, *zones), block, 0, stream, table, gpu_view, set, *zones,
                            n_apps, d_apps, d_out, dsts);
-    } else if (algo == GF_ALGO_TIGHTLY_PACK)
-        hipLaunchKernelGGL(shard_partials_kernel<GF_ALGO_TIGHTLY_PACK>, shard_grid(n_apps, set), block, 0, stream, table, gpu_view,
-                           set, n_apps, d_apps, d_out, dsts);
-    else
-        hipLaunchKernelGGL(shard_partials_kernel<GF_ALGO_DISTRIBUTE_EVENLY>, shard_grid(n_apps, set), block, 0, stream, table,
-                           gpu_view, set, n_apps, d_apps, d_out, dsts);
-    return hipGetLastError();
+        return hipGetLastError();
+    }
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
+        hipLaunchKernelGGL(shard_partials_kernel<A>, shard_grid(n_apps, set), block, 0, stream, table, gpu_view, set, n_apps, d_apps,
+                           d_out, dsts);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_shard_drivers(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
@@ -2325,16 +2233,16 @@ hipError_t launch_shard_emit(gf_algo algo, const NodeTable& table, const SparseT
     hipError_t e = hipMemsetAsync(d_exec2, 0, (zones != nullptr ? zones->n_cand : 2u) * half * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     const dim3 block(kWave * kWavesPerBlock);
-    if (zones != nullptr)
+    if (zones != nullptr) {
         hipLaunchKernelGGL(shard_emit_zoned_kernel, shard_grid(n_apps, set, *zones), block, 0, stream, table, gpu_view, set, *zones,
                            n_apps, d_apps, d_all_partials, d_all_drivers, d_exec2, half);
-    else if (algo == GF_ALGO_TIGHTLY_PACK)
-        hipLaunchKernelGGL(shard_emit_kernel<GF_ALGO_TIGHTLY_PACK>, shard_grid(n_apps, set), block, 0, stream, table, gpu_view,
-                           set, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
-    else
-        hipLaunchKernelGGL(shard_emit_kernel<GF_ALGO_DISTRIBUTE_EVENLY>, shard_grid(n_apps, set), block, 0, stream, table,
-                           gpu_view, set, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
-    return hipGetLastError();
+        return hipGetLastError();
+    }
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
+        hipLaunchKernelGGL(shard_emit_kernel<A>, shard_grid(n_apps, set), block, 0, stream, table, gpu_view, set, n_apps, d_apps,
+                           d_all_partials, d_all_drivers, d_results, d_exec2, half);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_shard_finish(gf_algo algo, uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps,
@@ -2344,22 +2252,17 @@ hipError_t launch_shard_finish(gf_algo algo, uint32_t n_shards, uint32_t n_apps,
     if (n_apps == 0) return hipSuccess;
     if (zones != nullptr) {
         if (table == nullptr || !shard_zones_ok(zones)) return hipErrorInvalidValue;
-        if (zones->az_aware)
-            hipLaunchKernelGGL(shard_finish_zoned_kernel<true>, dim3(n_apps), dim3(kWave * kFusedWaves), 0, stream, *table, *zones,
+        return with_value<true, false>(zones->az_aware != 0, [&](auto AZ) {
+            hipLaunchKernelGGL(shard_finish_zoned_kernel<AZ>, dim3(n_apps), dim3(kWave * kFusedWaves), 0, stream, *table, *zones,
                                n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
-        else
-            hipLaunchKernelGGL(shard_finish_zoned_kernel<false>, dim3(n_apps), dim3(kWave * kFusedWaves), 0, stream, *table, *zones,
-                               n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
-        return hipGetLastError();
+            return hipGetLastError();
+        });
     }
-    const dim3 block(kWave * kWavesPerBlock);
-    if (algo == GF_ALGO_TIGHTLY_PACK)
-        hipLaunchKernelGGL(shard_finish_kernel<GF_ALGO_TIGHTLY_PACK>, app_grid(n_apps), block, 0, stream, n_shards, n_apps,
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
+        hipLaunchKernelGGL(shard_finish_kernel<A>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, n_shards, n_apps,
                            d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
-    else
-        hipLaunchKernelGGL(shard_finish_kernel<GF_ALGO_DISTRIBUTE_EVENLY>, app_grid(n_apps), block, 0, stream, n_shards,
-                           n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
-    return hipGetLastError();
+        return hipGetLastError();
+    });
 }
 
 __global__ __launch_bounds__(256) void narrow_rescale_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst,
@@ -2403,14 +2306,11 @@ hipError_t launch_executor_fit(bool minimal_fragmentation, const NodeTable& tabl
                                const int64_t* d_exe, const uint32_t* d_hosts, uint32_t hosts_stride, const uint32_t* d_node_zone,
                                const uint32_t* d_req_zone, uint32_t* d_node_out, hipStream_t stream) {
     if (n_req == 0) return hipSuccess;
-    const dim3 block(kWave * kWavesPerBlock);
-    if (minimal_fragmentation)
-        hipLaunchKernelGGL(executor_fit_kernel<true>, app_grid(n_req), block, 0, stream, table, d_reserved, n_req, d_exe,
-                           d_hosts, hosts_stride, d_node_zone, d_req_zone, d_node_out);
-    else
-        hipLaunchKernelGGL(executor_fit_kernel<false>, app_grid(n_req), block, 0, stream, table, d_reserved, n_req, d_exe,
-                           d_hosts, hosts_stride, d_node_zone, d_req_zone, d_node_out);
-    return hipGetLastError();
+    return with_value<true, false>(minimal_fragmentation, [&](auto MF) {
+        hipLaunchKernelGGL(executor_fit_kernel<MF>, app_grid(n_req), dim3(kWave * kWavesPerBlock), 0, stream, table, d_reserved,
+                           n_req, d_exe, d_hosts, hosts_stride, d_node_zone, d_req_zone, d_node_out);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_find_nodes(bool chained, const NodeTable& table, uint32_t n_req, const int64_t* d_exe, const int32_t* d_k,

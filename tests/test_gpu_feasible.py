@@ -126,3 +126,22 @@ def test_feasible_without_mapped_staging(gf_ctx):
         c.set_orders(s.driver_order, s.exec_order)
         a = c.fit_feasible(0, apps)
         assert np.array_equal(a, c.fit_batch(IND, 0, apps).results["has_capacity"].astype(bool))
+
+
+@pytest.mark.parametrize("route", ["zoned_fused=0", "70 zones"])
+@pytest.mark.parametrize("algo", [3, 4, 5])
+def test_feasible_on_the_four_kernel_zone_route(algo, route):
+    """Without the one-launch zone kernel (option zoned_fused = 0, or more than 63 zones) gf_fit_feasible runs the full batch on
+    the four-kernel route and hands on its HasCapacity: against the oracle's."""
+    from test_gpu_zones import _setup, _zoned_problem_all_evaluated
+    oalgo = {3: ob.ALGO_AZ_AWARE_TIGHTLY_PACK, 4: ob.ALGO_SINGLE_AZ_TIGHTLY_PACK, 5: ob.ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION}[algo]
+    opts, n_zones = ({"zoned_fused": 0}, 3) if route == "zoned_fused=0" else ({}, 70)
+    rng = np.random.default_rng(4600 + algo + n_zones)
+    with gangfit.Context(0, options=opts) as ctx:
+        for layout in ("merged", "identical"):
+            avail, sched, zone, D, X, drv, exe, k = _zoned_problem_all_evaluated(rng, 300, 60, layout == "merged", layout, n_zones)
+            _setup(ctx, avail, sched, zone, D, X)
+            ref = ob.fit_independent(oalgo, avail, ob.make_apps(drv, exe, k), D, X, sched=sched, zone=zone)
+            fits = ctx.fit_feasible(algo, gangfit.make_apps(drv, exe, k))
+            assert np.array_equal(fits, np.asarray(ref.results["has_capacity"]).astype(bool))
+            assert fits.any()

@@ -379,3 +379,46 @@ def test_long_gangs_take_the_run_averages(gf_ctx, algo):
     _assert_same(gpu, ref, apps)
     assert np.array_equal(_bits(gf_ctx.avg_packing_efficiency(algo, apps, gpu)), _bits(ref.avg_eff))
     assert ref.results["has_capacity"].mean() > 0.5
+
+
+def _zoned_problem_all_evaluated(rng, n, a, tight_cluster, layout, n_zones):
+    """_zoned_problem whose n_zones zones are all on the evaluation list: each holds a node of both orders."""
+    avail, sched, zone, D, X, drv, exe, k = _zoned_problem(rng, n, a, tight_cluster, layout, n_zones)
+    both = np.intersect1d(D[D < n], X[X < n])
+    assert len(both) >= n_zones
+    zone[both] = (np.arange(len(both)) % n_zones).astype(np.uint32) * 7 + 3
+    return avail, sched, zone, D, X, drv, exe, k
+
+
+_ZONE_ALGOS = [(SAZ, O_ALGO[SAZ]), (AZA, O_ALGO[AZA]),
+               (gangfit.GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION, ob.ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION)]
+
+
+@pytest.mark.parametrize("route", ["zoned_fused=0", "70 zones"])
+@pytest.mark.parametrize("algo,oalgo", _ZONE_ALGOS, ids=["single-az", "az-aware", "single-az-minfrag"])
+def test_four_kernel_zone_route(algo, oalgo, route):
+    """The four-kernel independent zone route (fit_zoned_kernel -> avg_efficiency_kernel -> zone_select_kernel), reached by the
+    option zoned_fused = 0 and by more than 63 zones: results, placements and the averages against the oracle."""
+    opts, n_zones = ({"zoned_fused": 0}, 3) if route == "zoned_fused=0" else ({}, 70)
+    rng = np.random.default_rng(4400 + 3 * algo + n_zones)
+    with gangfit.Context(0, options=opts) as ctx:
+        for layout, tight_cluster in (("merged", True), ("identical", False)):
+            avail, sched, zone, D, X, drv, exe, k = _zoned_problem_all_evaluated(rng, 300, 60, tight_cluster, layout, n_zones)
+            _setup(ctx, avail, sched, zone, D, X)
+            apps = gangfit.make_apps(drv, exe, k)
+            ref = ob.fit_independent(oalgo, avail, ob.make_apps(drv, exe, k), D, X, closed_form=algo != _ZONE_ALGOS[2][0],
+                                     sched=sched, zone=zone)
+            gpu = ctx.fit_batch(IND, algo, apps)
+            _assert_same(gpu, ref, apps)
+            assert np.array_equal(_bits(ctx.avg_packing_efficiency(algo, apps, gpu)), _bits(ref.avg_eff))
+            assert ref.results["has_capacity"].any()
+
+
+@pytest.mark.parametrize("algo", [a for a, _ in _ZONE_ALGOS], ids=["single-az", "az-aware", "single-az-minfrag"])
+def test_fifo_chain_refuses_more_than_63_zones(gf_ctx, algo):
+    rng = np.random.default_rng(4500 + algo)
+    avail, sched, zone, D, X, drv, exe, k = _zoned_problem_all_evaluated(rng, 300, 20, False, "merged", 70)
+    _setup(gf_ctx, avail, sched, zone, D, X)
+    with pytest.raises(gangfit.GangfitError) as e:
+        gf_ctx.fit_batch(gangfit.GF_MODE_FIFO_CHAIN, algo, gangfit.make_apps(drv, exe, k))
+    assert e.value.code == gangfit._native.GF_ERR_UNSUPPORTED

@@ -77,16 +77,22 @@ uint32_t candidate_views(const gf_ctx* ctx, gf_algo algo) {
     return is_zone_algo(algo) ? ctx->n_zones + (algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u) : 1u;
 }
 
-// Checks the request records (k in [0, GF_MAX_K], every quantity in [0, 2^62)) and sums their executors into *total_k;
-// out (nullable) receives a copy of the records with exec_off set.
+// Checks request record a: k in [0, GF_MAX_K], every quantity in [0, 2^62).
+static int check_app(gf_ctx* ctx, uint32_t a, const gf_app& in) {
+    if (in.k < 0 || in.k > GF_MAX_K) return fail(ctx, GF_ERR_INVALID, "apps[%u].k = %d outside [0, %d]", a, in.k, GF_MAX_K);
+    for (int j = 0; j < 3; ++j)
+        if (in.drv[j] < 0 || in.drv[j] >= GF_MAX_ABS_QUANTITY || in.exe[j] < 0 || in.exe[j] >= GF_MAX_ABS_QUANTITY)
+            return fail(ctx, GF_ERR_INVALID, "apps[%u] request outside [0, 2^62)", a);
+    return GF_OK;
+}
+
+// Checks the request records (check_app) and sums their executors into *total_k; out (nullable) receives a copy of the
+// records with exec_off set.
 int check_apps(gf_ctx* ctx, uint32_t n_apps, const gf_app* apps, gf_app* out, uint64_t* total_k) {
     uint64_t t = 0;
     for (uint32_t a = 0; a < n_apps; ++a) {
         const gf_app& in = apps[a];
-        if (in.k < 0 || in.k > GF_MAX_K) return fail(ctx, GF_ERR_INVALID, "apps[%u].k = %d outside [0, %d]", a, in.k, GF_MAX_K);
-        for (int j = 0; j < 3; ++j)
-            if (in.drv[j] < 0 || in.drv[j] >= GF_MAX_ABS_QUANTITY || in.exe[j] < 0 || in.exe[j] >= GF_MAX_ABS_QUANTITY)
-                return fail(ctx, GF_ERR_INVALID, "apps[%u] request outside [0, 2^62)", a);
+        if (const int rc = check_app(ctx, a, in); rc != GF_OK) return rc;
         if (out != nullptr) {
             out[a] = in;
             out[a].exec_off = t;
@@ -1103,7 +1109,7 @@ int gf_avg_packing_efficiency(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const 
     for (uint32_t a = 0; a < n_apps; ++a) {
         gf_app& o = ctx->h_apps.ptr[a];
         o = apps[a];
-        if (o.k < 0 || o.k > GF_MAX_K) return fail(ctx, GF_ERR_INVALID, "apps[%u].k out of range", a);
+        if (const int rc = check_app(ctx, a, o); rc != GF_OK) return rc;
         o.exec_off = total_k;
         if (results[a].has_capacity) {
             const uint32_t d = results[a].driver_node;
@@ -1153,8 +1159,8 @@ int gf_packing_efficiencies(gf_ctx* ctx, gf_algo algo, const gf_app* app, const 
     if (!app || !result || !eff_out) return fail(ctx, GF_ERR_INVALID, "app/result/eff_out must not be NULL");
     if (!ctx->have_snapshot || !ctx->have_sched)
         return fail(ctx, GF_ERR_STATE, "efficiencies need gf_snapshot_set with the schedulable columns");
-    if (app->k < 0 || app->k > GF_MAX_K || (result->has_capacity && app->k > 0 && !exec_nodes))
-        return fail(ctx, GF_ERR_INVALID, "bad k / exec_nodes");
+    if (const int rc = check_app(ctx, 0, *app); rc != GF_OK) return rc;
+    if (result->has_capacity && app->k > 0 && !exec_nodes) return fail(ctx, GF_ERR_INVALID, "exec_nodes must not be NULL");
     const uint32_t n = ctx->n_nodes;
     if (n == 0) return GF_OK;
     GF_HIP(ctx, hipSetDevice(ctx->device));

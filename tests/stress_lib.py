@@ -7,6 +7,7 @@ hundred seeds under `-m gpu`) and by tools/stress_parity.py (as long as you like
 import numpy as np
 
 import gangfit
+import magnitudes
 from oracle import binding as ob
 from test_gpu_parity import _random_problem  # noqa: F401  (re-exported for the tool)
 from test_gpu_zones import _zoned_problem
@@ -44,15 +45,20 @@ def one_seed(ctxs, seed):
     tight = bool(rng.integers(0, 2))
     nz = int(rng.integers(1, 6))
     avail, sched, zone, D, X, drv, exe, k = _zoned_problem(rng, n, a, tight, layout, nz)
-    if rng.random() < 0.3:  # coarse units so that the narrow domain applies with non-trivial gcds
+    regime = None
+    if rng.random() < 0.15:  # the edges of the quantity contract (tests/magnitudes.py) instead of the small end
+        regime = str(rng.choice([r for r in magnitudes.REGIMES if r != "max-k"]))
+        avail, sched, zone, D, X, drv, exe, k, _ = magnitudes.problem(regime, rng, layout, nz)
+        n, a = len(avail), len(k)
+    if regime is None and rng.random() < 0.3:  # coarse units so that the narrow domain applies with non-trivial gcds
         for arr in (avail, sched, drv, exe):
             arr[:, 1] *= 1 << 20
-    if rng.random() < 0.4:  # gpu nodes a minority: the sparse gpu view of the independent batch
+    if regime is None and rng.random() < 0.4:  # gpu nodes a minority: the sparse gpu view of the independent batch
         frac = float(rng.choice([0.03, 0.1, 0.2]))
         avail[:, 2] = np.where(rng.random(n) < frac, rng.integers(1, 9, size=n), rng.integers(-1, 1, size=n))
         sched[:, 2] = np.maximum(avail[:, 2], 0) + rng.integers(0, 3, size=n)
         exe[:, 2] = np.where(rng.random(a) < 0.7, rng.integers(1, 4, size=a), 0)
-    if rng.random() < 0.3:  # requests finer than the table's gcd units: the per-batch unit refinement of the int32 chains
+    if regime is None and rng.random() < 0.3:  # requests finer than the table's gcd units: the per-batch unit refinement of the int32 chains
         f = int(rng.choice([2, 4, 6, 8]))
         avail[:, 1] *= f
         sched[:, 1] *= f
@@ -66,7 +72,7 @@ def one_seed(ctxs, seed):
     flags = (rng.random(a) < 0.85).astype(np.uint32)
     apps = gangfit.make_apps(drv, exe, k, flags)
     oapps = ob.make_apps(drv, exe, k, flags)
-    where = f"seed={seed} n={n} a={a} layout={layout} tight={tight} nz={nz} kcap={kcap}"
+    where = f"seed={seed} n={n} a={a} layout={layout} tight={tight} nz={nz} kcap={kcap} regime={regime}"
     cases = 0
     ind_refs = {}  # the literal oracle's answer for the independent batch, once per packer: the contexts share the inputs (its
     #                driver retry loop is O(|D| N) per gang that does not fit — seed 61038: 44 s per pass over the six packers)

@@ -217,8 +217,9 @@ int gf_snapshot_build(gf_ctx *ctx, uint32_t n_nodes, const int64_t *alloc_cpu_mi
                       const uint32_t *zone_of_node, uint32_t n_zones, const uint32_t *name_rank,
                       const uint32_t *driver_label_rank, const uint32_t *exec_label_rank, uint32_t *driver_order_out,
                       uint32_t *n_d_out, uint32_t *exec_order_out, uint32_t *n_x_out);
-/* The same in two steps, for hosts that keep the cluster resident: gf_cluster_set uploads the columns that change only when
- * the node set does (allocatable, overhead, zone ids, name ranks, default node flags — an informer event in the Go host);
+/* The same in two steps, for hosts that keep the cluster resident: gf_cluster_set uploads the node-side columns (allocatable,
+ * overhead, zone ids, name ranks, default node flags).  All but the overhead change only when the node set does — an informer
+ * event in the Go host; the overhead changes by rows whenever a pod without a reservation lands or leaves (gf_overhead_update);
  * gf_snapshot_build_resident then builds and installs a snapshot from them and this request's reservation entries, so that
  * a Filter moves only the reservations (and, when node_flags is not NULL, its own candidate flags: the driver candidates
  * are the request's NodeNames) across PCIe.  gf_snapshot_build is exactly gf_cluster_set followed by
@@ -246,10 +247,28 @@ int gf_snapshot_build_resident(gf_ctx *ctx, uint32_t n_res, const uint32_t *res_
 int gf_usage_reset(gf_ctx *ctx);
 int gf_usage_apply(gf_ctx *ctx, uint32_t n_entries, const uint32_t *res_node, const int64_t *res_cpu_milli,
                    const int64_t *res_mem_bytes, const int64_t *res_gpu, int sign /* +1 add, -1 remove */);
+/* The overhead rows of the resident cluster (internal/extender/overhead.go:91-153: per node, the summed requests of every pod
+ * that has no reservation — daemonsets and every non-Spark pod).  gf_overhead_update REPLACES the overhead of each named node in
+ * the columns gf_cluster_set uploaded as over_*; gf_snapshot_build_resident then computes available and schedulable from the new
+ * rows.  A replace is idempotent and cannot drive a sum negative; the host recomputes a node's sum anyway when a pod gains or
+ * loses its reservation (overhead.go:138).  The resident usage sums of gf_usage_apply are KEPT.
+ *   - gf_cluster_set must have been called (GF_ERR_STATE; GF_ERR_STATE on a view).  n_rows == 0 is GF_OK and changes nothing.
+ *   - values in [0, 2^61); node[i] < the cluster's n_nodes; no node twice in one call; no NULL column: else GF_ERR_INVALID.
+ *     An update under which (everything gf_usage_apply has added) + (a new row) could reach 2^62 is GF_ERR_INVALID too.
+ *     On any refusal nothing on the device has changed.
+ *   - a cluster installed with over_* == NULL gets zeroed columns on its first update.
+ *   - bumps the cluster generation (gf_generation out[1]) only: the installed snapshot, the chain cache and recorded graphs stay
+ *     valid until the next build, as after gf_usage_apply.
+ *   - multi-device context: every device gets the rows; when the update fails after the first device took it the resident
+ *     cluster is unusable (GF_ERR_STATE here and from gf_snapshot_build_resident) until the next gf_cluster_set.
+ * Blocking with respect to the caller's arrays. */
+int gf_overhead_update(gf_ctx *ctx, uint32_t n_rows, const uint32_t *node, const int64_t *over_cpu_milli,
+                       const int64_t *over_mem_bytes, const int64_t *over_gpu);
 /* Generations of the state a context keeps between calls, for hosts that decide from them what a Filter must resend:
  *   out[0]  snapshot epoch: bumped by every call that installs a snapshot, zones or orders (the chain cache and recorded
  *           graphs are tied to it)
- *   out[1]  cluster generation: bumped by gf_cluster_set (and gf_snapshot_build, which calls it)
+ *   out[1]  cluster generation: bumped by gf_cluster_set (and gf_snapshot_build, which calls it) and by every gf_overhead_update
+ *           that changed something
  *   out[2]  usage generation: bumped by gf_cluster_set, gf_usage_reset and every gf_usage_apply
  * A host that finds the generations it recorded after its own last call unchanged knows that no other user of the context
  * touched that state (internal/extender keeps one extender per context, but the UnschedulablePodMarker shares it). */

@@ -440,6 +440,37 @@ func (c *Context) UsageApply(nodes []uint32, requests []*resources.Resources, ad
 	return nil
 }
 
+// OverheadUpdate replaces the overhead rows of the named nodes in the resident cluster columns (gf_overhead_update): what
+// overheadComputer.GetOverhead (internal/extender/overhead.go:91-153) holds for a node — the summed requests of its pods that
+// have no reservation — changes on a pod add / delete with a node name and when a pod gains or loses its reservation
+// (overhead.go:138); the handler recomputes that node's sum and sends the one row.  Node INDICES in the order given to
+// gf_cluster_set, no index twice in one call.  The resident usage sums stay; the next gf_snapshot_build_resident reads the new rows.
+// Unverified here (no Go toolchain); the C entry point is exercised by tests/test_gpu_overhead_update.py.
+func (c *Context) OverheadUpdate(nodes []uint32, overhead []*resources.Resources) error {
+	if len(nodes) != len(overhead) {
+		return fmt.Errorf("gangfit: %d nodes, %d overhead rows", len(nodes), len(overhead))
+	}
+	if len(nodes) == 0 {
+		return nil
+	}
+	var cols [3][]int64
+	for _, r := range overhead {
+		v, err := canonical(r)
+		if err != nil {
+			return err
+		}
+		for j := 0; j < 3; j++ {
+			cols[j] = append(cols[j], v[j])
+		}
+	}
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	if rc := C.gf_overhead_update(c.ctx, C.uint32_t(len(nodes)), p32(nodes), p64(cols[0]), p64(cols[1]), p64(cols[2])); rc != C.GF_OK {
+		return c.err(rc)
+	}
+	return nil
+}
+
 // UsageReset zeroes the resident usage (gf_cluster_set does it too: a new node set starts from nothing).
 func (c *Context) UsageReset() error {
 	c.mu.Lock()

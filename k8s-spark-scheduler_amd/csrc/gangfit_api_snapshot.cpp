@@ -563,6 +563,7 @@ int gf_cluster_set(gf_ctx* ctx, uint32_t n_nodes, const int64_t* alloc_cpu_milli
     ctx->cl_default_flags = ctx->cl_flags;
     ctx->d_flags_default = true;
     ctx->usage_ok = true;
+    ctx->cl_over_ok = true;
     ++ctx->cluster_gen;
     ++ctx->usage_gen;
     if (zone_of_node)
@@ -680,6 +681,79 @@ int gf_usage_apply(gf_ctx* ctx, uint32_t n_entries, const uint32_t* res_node, co
     return GF_OK;
 }
 
+int gf_overhead_update(gf_ctx* ctx, uint32_t n_rows, const uint32_t* node, const int64_t* over_cpu_milli, const int64_t* over_mem_bytes,
+                       const int64_t* over_gpu) {
+    if (ctx != nullptr && !ctx->group.empty()) {
+        // every device keeps the same columns; an update that reaches some devices and fails on another leaves them apart:
+        // the resident cluster is then unusable everywhere until gf_cluster_set (the shape of usage_ok in gf_usage_apply)
+        gf_ctx* const g = ctx;
+        std::lock_guard<std::recursive_mutex> glock(g->mu);
+        for (size_t i = 0; i < g->group.size(); ++i) {
+            const int rc = gf_overhead_update(g->group[i], n_rows, node, over_cpu_milli, over_mem_bytes, over_gpu);
+            if (rc != GF_OK) {
+                g->err = g->group[i]->err;
+                if (i > 0)
+                    for (gf_ctx* sub : g->group) sub->cl_over_ok = false;
+                return rc;
+            }
+        }
+        return GF_OK;
+    }
+    if (!ctx) return GF_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    GF_NOT_ON_A_VIEW(ctx);
+    if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede gf_overhead_update");
+    if (!ctx->cl_over_ok)
+        return fail(ctx, GF_ERR_STATE, "an earlier update failed half way: gf_cluster_set must replace the resident cluster");
+    if (n_rows == 0) return GF_OK;
+    if (!node || !over_cpu_milli || !over_mem_bytes || !over_gpu) return fail(ctx, GF_ERR_INVALID, "row columns must not be NULL");
+    const int64_t* ocols[3] = {over_cpu_milli, over_mem_bytes, over_gpu};
+    const int64_t lim = GF_MAX_ABS_QUANTITY >> 1;
+    int64_t row_max[3] = {0, 0, 0};
+    for (int j = 0; j < 3; ++j) {
+        for (uint32_t i = 0; i < n_rows; ++i) {
+            if (ocols[j][i] < 0 || ocols[j][i] >= lim) return fail(ctx, GF_ERR_INVALID, "row %u out of range", i);
+            if (ocols[j][i] > row_max[j]) row_max[j] = ocols[j][i];
+        }
+        // what gf_usage_apply keeps true — (everything applied) + (the largest overhead) < 2^62 — must survive the new rows
+        if (ctx->usage_total[j] + (__int128)row_max[j] >= (__int128)GF_MAX_ABS_QUANTITY)
+            return fail(ctx, GF_ERR_INVALID, "the resident usage plus this overhead can sum past 2^62: not representable");
+    }
+    for (uint32_t i = 0; i < n_rows; ++i)
+        if (node[i] >= ctx->cl_n) return fail(ctx, GF_ERR_INVALID, "row %u names node %u of %u", i, node[i], ctx->cl_n);
+    if (ctx->cl_row_stamp.size() != ctx->cl_n || ctx->cl_row_call == UINT32_MAX) {
+        ctx->cl_row_stamp.assign(ctx->cl_n, 0);
+        ctx->cl_row_call = 0;
+    }
+    ++ctx->cl_row_call;
+    for (uint32_t i = 0; i < n_rows; ++i) {
+        if (ctx->cl_row_stamp[node[i]] == ctx->cl_row_call) return fail(ctx, GF_ERR_INVALID, "node %u is named twice in one update", node[i]);
+        ctx->cl_row_stamp[node[i]] = ctx->cl_row_call;
+    }
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t R = n_rows, N = ctx->cl_n;
+    GF_HIP(ctx, gf_wait_stream(st));  // an earlier update may still read the staging buffers that are about to grow
+    GF_HIP(ctx, ctx->d_delta_i64.reserve(3 * R));
+    GF_HIP(ctx, ctx->d_delta_u32.reserve(R));
+    // ---- from here on the device changes: a runtime failure leaves the columns unknown
+    ctx->cl_over_ok = false;
+    int64_t* d_over = ctx->d_cl_i64.ptr + 3 * N;
+    if (!ctx->cl_over)  // installed without overhead columns: the build read none; now it must, and the other rows are zero
+        GF_HIP(ctx, hipMemsetAsync(d_over, 0, 3 * N * sizeof(int64_t), st));
+    for (int j = 0; j < 3; ++j)
+        GF_HIP(ctx, hipMemcpyAsync(ctx->d_delta_i64.ptr + j * R, ocols[j], R * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    GF_HIP(ctx, hipMemcpyAsync(ctx->d_delta_u32.ptr, node, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    GF_HIP(ctx, gangfit::launch_overhead_update(n_rows, ctx->cl_n, ctx->d_delta_u32.ptr, ctx->d_delta_i64.ptr, d_over, st));
+    GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays are free again
+    ctx->cl_over = true;
+    ctx->cl_over_ok = true;
+    for (int j = 0; j < 3; ++j)
+        if (row_max[j] > ctx->cl_max_over[j]) ctx->cl_max_over[j] = row_max[j];  // a bound: a replaced row never lowers it
+    ++ctx->cluster_gen;
+    return GF_OK;
+}
+
 int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_node, const int64_t* res_cpu_milli,
                                const int64_t* res_mem_bytes, const int64_t* res_gpu, const uint32_t* node_flags,
                                const uint32_t* driver_label_rank, const uint32_t* exec_label_rank,
@@ -714,6 +788,8 @@ int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_
         return fail(ctx, GF_ERR_INVALID, "reservation columns must not be NULL");
     if (usage_resident && !ctx->usage_ok)
         return fail(ctx, GF_ERR_STATE, "the resident usage is unknown (a failed update): gf_usage_reset must rebuild it");
+    if (!ctx->cl_over_ok)
+        return fail(ctx, GF_ERR_STATE, "the resident overhead is unknown (a failed gf_overhead_update): gf_cluster_set must replace it");
     // this request's candidate flags; NULL = the flags of gf_cluster_set (not those of the previous request)
     if (node_flags)
         ctx->cl_flags.assign(node_flags, node_flags + n);

@@ -353,7 +353,7 @@ struct gf_ctx {
     // gf_cluster_set: the static columns of gf_snapshot_build, resident
     DeviceBuf<int64_t> d_cl_i64;   // allocatable (3n) | overhead (3n)
     DeviceBuf<int64_t> d_cl_usage;  // resident UsageForNodes sums (3n), maintained by gf_usage_apply
-    DeviceBuf<int64_t> d_delta_i64; // one gf_usage_apply call's entries
+    DeviceBuf<int64_t> d_delta_i64; // one gf_usage_apply call's entries / one gf_overhead_update call's rows
     DeviceBuf<uint32_t> d_delta_u32;
     __int128 usage_total[3] = {0, 0, 0};  // sum of everything applied: bounds every node's sum
     DeviceBuf<uint32_t> d_cl_u32;  // zone | name_rank | node_flags (n each)
@@ -361,12 +361,15 @@ struct gf_ctx {
     std::vector<uint32_t> cl_default_flags;   // the flags of gf_cluster_set: what node_flags == NULL selects
     bool d_flags_default = true;              // the device column holds cl_default_flags (not a request's candidate flags)
     bool usage_ok = true;                     // false after a failed update: the resident sums are unknown until gf_usage_reset
-    uint64_t cluster_gen = 0, usage_gen = 0;  // bumped by gf_cluster_set / gf_usage_reset + gf_usage_apply (gf_generation)
+    uint64_t cluster_gen = 0, usage_gen = 0;  // bumped by gf_cluster_set + gf_overhead_update / gf_usage_reset + gf_usage_apply (gf_generation)
     DeviceBuf<uint32_t> d_flag32;             // one device word for yes / no answers of small kernels
     DeviceBuf<uint32_t> d_sortwork;           // count tables, grid barrier and scalars of the priority sort (gangfit_snapshot.hip)
     uint32_t cl_n = 0, cl_zones = 1;
     bool cl_over = false, have_cluster = false;
-    int64_t cl_max_over[3] = {0, 0, 0};
+    int64_t cl_max_over[3] = {0, 0, 0};       // upper bound of every node's overhead (gf_overhead_update only ever raises it)
+    bool cl_over_ok = true;                   // false after a gf_overhead_update that reached only some devices: until gf_cluster_set
+    std::vector<uint32_t> cl_row_stamp;       // gf_overhead_update: [node] the call that last named it (a node twice in one call)
+    uint32_t cl_row_call = 0;
 
     // gf_snapshot_build
     DeviceBuf<int64_t> d_bi64;   // alloc | overhead | usage | avail | sched (3n each) | keys_a | keys_b (n each) | res_req (3r) | zone_sum

@@ -468,6 +468,11 @@ struct SnapshotBuild {
 // d_negative (nullable): after a removal (sign < 0) bit 0 is set when a touched node's sum went below zero.
 hipError_t launch_usage_apply(uint32_t n_entries, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_req, int sign,
                               int64_t* d_usage, uint32_t* d_negative, hipStream_t stream);
+// overhead[d_node[i]] = row i (columns cpu | memory | gpu of d_rows, n_rows each) for n_rows rows of the resident overhead columns
+// (d_overhead: 3 * n_nodes).  Every d_node[i] < n_nodes and no node twice (the caller checks): plain stores, stream-ordered
+// before any later build.
+hipError_t launch_overhead_update(uint32_t n_rows, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_rows, int64_t* d_overhead,
+                                  hipStream_t stream);
 // The slot tables of the merged layout built from the device-resident snapshot columns (what gf_orders_set builds on the
 // host): every node gets the slot of its position in the priority order.
 struct SnapshotFinalize {

@@ -44,6 +44,20 @@ __global__ void usage_negative_kernel(uint32_t n_res, uint32_t n_nodes, const ui
     if (usage[n] < 0 || usage[(size_t)n_nodes + n] < 0 || usage[2 * (size_t)n_nodes + n] < 0) atomicOr(negative, 1u);
 }
 
+// gf_overhead_update: row i of the update REPLACES the overhead of node row_node[i] in the resident SoA columns (cpu | memory | gpu,
+// n_nodes each).  The host has refused duplicate nodes and nodes outside the cluster, so no row is written twice: plain stores.
+__global__ __launch_bounds__(256) void overhead_update_kernel(uint32_t n_rows, uint32_t n_nodes, const uint32_t* __restrict__ row_node,
+                                                              const int64_t* __restrict__ r0, const int64_t* __restrict__ r1,
+                                                              const int64_t* __restrict__ r2, int64_t* __restrict__ over) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const uint32_t n = row_node[i];
+    if (n >= n_nodes) return;  // (never: checked on the host; a store outside the columns must not depend on that)
+    over[n] = r0[i];
+    over[(size_t)n_nodes + n] = r1[i];
+    over[2 * (size_t)n_nodes + n] = r2[i];
+}
+
 // order-preserving map of a signed quantity to unsigned
 __device__ __forceinline__ unsigned long long biased(int64_t v) { return (unsigned long long)v ^ 0x8000000000000000ull; }
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -878,6 +892,14 @@ hipError_t launch_usage_apply(uint32_t n_entries, uint32_t n_nodes, const uint32
     if (e != hipSuccess || sign > 0 || d_negative == nullptr) return e;
     hipLaunchKernelGGL(usage_negative_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, stream, n_entries, n_nodes, d_node,
                        (const int64_t*)d_usage, d_negative);
+    return hipGetLastError();
+}
+
+hipError_t launch_overhead_update(uint32_t n_rows, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_rows, int64_t* d_overhead,
+                                  hipStream_t stream) {
+    if (n_rows == 0 || n_nodes == 0) return hipSuccess;
+    hipLaunchKernelGGL(overhead_update_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, stream, n_rows, n_nodes, d_node, d_rows,
+                       d_rows + n_rows, d_rows + 2 * (size_t)n_rows, d_overhead);
     return hipGetLastError();
 }
 

@@ -49,7 +49,7 @@ EXPORTED_SYMBOLS = [
     "gf_shard_layout",
     "gf_find_nodes", "gf_ctx_lock", "gf_ctx_unlock", "gf_launch_floor",
     "gf_graph_begin", "gf_graph_end", "gf_graph_launch", "gf_graph_destroy", "gf_cluster_set", "gf_snapshot_build_resident",
-    "gf_usage_reset", "gf_usage_apply", "gf_set_option", "gf_chain_cache_stats", "gf_generation", "gf_shard_count", "gf_ctx_view",
+    "gf_usage_reset", "gf_usage_apply", "gf_overhead_update", "gf_set_option", "gf_chain_cache_stats", "gf_generation", "gf_shard_count", "gf_ctx_view",
     "gf_worker_fit", "gf_worker_submit_dev", "gf_worker_wait", "gf_worker_stop", "gf_worker_stats", "gf_worker_geometry", "gf_worker_kernel_time", "gf_call_phases",
 ]
 
@@ -151,6 +151,8 @@ def load() -> C.CDLL:
     L.gf_usage_reset.argtypes = [p]
     L.gf_usage_apply.restype = i32
     L.gf_usage_apply.argtypes = [p, u32, p, p, p, p, i32]
+    L.gf_overhead_update.restype = i32
+    L.gf_overhead_update.argtypes = [p, u32, p, p, p, p]
     L.gf_snapshot_build_resident.restype = i32
     L.gf_snapshot_build_resident.argtypes = [p, u32, p, p, p, p, p, p, p, p, p, p, p]
     L.gf_snapshot_get.restype = i32

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_PKG_ROOT, "libgangfit.so")
 HOST_LIB_PATH = os.path.join(_PKG_ROOT, "libgangfit_host.so")
 HOST_BENCH_PATH = os.path.join(_PKG_ROOT, "host_bench")  # end-to-end Filter timing through the host mirror
 HOST_TEST_PATH = os.path.join(_PKG_ROOT, "host_test")  # C++ tests of the host mirror (host/tests/host_test.cpp)
+HOST_OVERHEAD_TEST_PATH = os.path.join(_PKG_ROOT, "host_overhead_test")  # ... of its flat route with overhead (host_overhead_test.cpp)
 INCLUDE = os.path.join(_REPO_ROOT, "include")
 
 _SOURCES = ["gangfit_kernels.hip", "gangfit_snapshot.hip", "gangfit_api.cpp", "gangfit_api_snapshot.cpp", "gangfit_api_fit.cpp",
@@ -73,6 +74,11 @@ def build_host(force: bool = False) -> str:
     if os.path.exists(test_src) and (force or _stale(HOST_TEST_PATH, [test_src, HOST_LIB_PATH] + hdrs)):
         cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, test_src, "-L", _PKG_ROOT,
                "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_TEST_PATH]
+        subprocess.check_call(cmd)
+    over_src = os.path.join(host_dir, "tests", "host_overhead_test.cpp")
+    if os.path.exists(over_src) and (force or _stale(HOST_OVERHEAD_TEST_PATH, [over_src, HOST_LIB_PATH] + hdrs)):
+        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, over_src, "-L", _PKG_ROOT,
+               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_OVERHEAD_TEST_PATH]
         subprocess.check_call(cmd)
     bench_src = os.path.join(host_dir, "tests", "host_bench.cpp")
     if os.path.exists(bench_src) and (force or _stale(HOST_BENCH_PATH, [bench_src, HOST_LIB_PATH] + hdrs)):

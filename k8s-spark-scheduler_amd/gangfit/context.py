@@ -201,6 +201,18 @@ class Context:
             rcols = [np.ascontiguousarray(rr[:, j]) for j in range(3)]
         self._check(self._lib.gf_usage_apply(self._h, len(rn), N.ptr(rn), *[N.ptr(c) for c in rcols], int(sign)))
 
+    def overhead_update(self, nodes, rows=None, cols=None):
+        """gf_overhead_update: replace the overhead rows of the named nodes in the resident cluster columns (the resident
+        usage sums stay).  rows = (n, 3) rows or cols = (cpu, mem, gpu) columns, one per entry of nodes."""
+        nd = np.ascontiguousarray(nodes, dtype=np.uint32)
+        if cols is not None:
+            ocols = [np.ascontiguousarray(c, dtype=np.int64) for c in cols]
+        else:
+            rr = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 3)
+            ocols = [np.ascontiguousarray(rr[:, j]) for j in range(3)]
+        assert all(len(c) == len(nd) for c in ocols), "one row per named node"
+        self._check(self._lib.gf_overhead_update(self._h, len(nd), N.ptr(nd), *[N.ptr(c) for c in ocols]))
+
     def build_snapshot_resident(self, res_node=None, res_req=None, node_flags=None, driver_label_rank=None,
                                 exec_label_rank=None, want_orders: bool = True, res_cols=None, resident_usage: bool = False):
         """gf_snapshot_build_resident.  res_cols = (cpu, mem, gpu) contiguous int64 columns of the reservation entries, for

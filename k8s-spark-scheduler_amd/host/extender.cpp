@@ -461,9 +461,46 @@ bool FlatReservations::Build(const std::vector<ResourceReservation>& reservation
     return true;
 }
 
+bool FlatOverhead::Build(const NodeGroupResources& overhead, const FlatCluster& cluster, FlatOverhead* out, std::string* err) {
+    FlatOverhead f;
+    const size_t n = cluster.names.size();
+    if (!overhead.empty())
+        for (int j = 0; j < 3; ++j) f.over[j].assign(n, 0);
+    for (const auto& [node, r] : overhead) {
+        auto it = cluster.index.find(node);
+        if (it == cluster.index.end()) continue;
+        int64_t v[3];
+        if (!r.canonical(v) || v[0] < 0 || v[1] < 0 || v[2] < 0) {
+            if (err) *err = "overhead of " + node + " is not exactly representable";
+            return false;
+        }
+        for (int j = 0; j < 3; ++j) f.over[j][it->second] = v[j];
+    }
+    f.Touch();
+    *out = std::move(f);
+    return true;
+}
+
+void FlatOverhead::Touch() {
+    static std::atomic<uint64_t> next_version{1};
+    version = next_version.fetch_add(1);
+}
+
+void overheadRowDiff(const std::vector<int64_t> want[3], const std::vector<int64_t> have[3], uint32_t n, std::vector<uint32_t>* rows) {
+    rows->clear();
+    const bool w = want != nullptr && !want[0].empty(), h = have != nullptr && !have[0].empty();
+    if (!w && !h) return;
+    for (uint32_t i = 0; i < n; ++i) {
+        bool differs = false;
+        for (int j = 0; j < 3; ++j) differs = differs || (w ? want[j][i] : 0) != (h ? have[j][i] : 0);
+        if (differs) rows->push_back(i);
+    }
+}
+
 SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string& instanceGroup, const Pod& driver,
                                                               const std::vector<std::string>& nodeNames,
-                                                              const FlatCluster& cluster, const FlatReservations* flat) {
+                                                              const FlatCluster& cluster, const FlatReservations* flat,
+                                                              const FlatOverhead* flatOverhead) {
     SelectNodeResult out;
     auto not_served = [&](const std::string& why) {
         out.served = false;
@@ -489,17 +526,17 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
     }
     const std::vector<uint32_t>& rnode = flat->node;
     const std::vector<int64_t>* rreq = flat->req;
-    std::vector<int64_t> over[3];
-    if (!overhead.empty()) {
-        for (int j = 0; j < 3; ++j) over[j].assign(n, 0);
-        for (const auto& [node, r] : overhead) {
-            auto it = cluster.index.find(node);
-            if (it == cluster.index.end()) continue;
-            int64_t v[3];
-            if (!r.canonical(v) || v[0] < 0 || v[1] < 0 || v[2] < 0) return not_served("overhead of " + node + " is not exactly representable");
-            for (int j = 0; j < 3; ++j) over[j][it->second] = v[j];
-        }
+    FlatOverhead local_over;
+    if (flatOverhead == nullptr) {
+        std::string oerr;
+        if (!FlatOverhead::Build(overhead, cluster, &local_over, &oerr)) return not_served(oerr);
+        local_over.version = 0;  // this request's own: compared with the resident columns on every Filter
+        flatOverhead = &local_over;
+    } else if (!flatOverhead->over[0].empty() &&
+               (flatOverhead->over[0].size() != n || flatOverhead->over[1].size() != n || flatOverhead->over[2].size() != n)) {
+        return not_served("the flat overhead columns do not belong to this cluster");
     }
+    const std::vector<int64_t>* const over = flatOverhead->over;
     // ---- from here on this Filter reads and writes the extender's caches and its record of what sits on the device
     std::lock_guard<std::mutex> flat_lock(*flat_mu_);
     ++flat_calls_;
@@ -583,28 +620,69 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
     // ---- snapshot + orders on the device, then the chain
     gf_ctx* ctx = binpacker_.ctx;
     CtxSequence seq(ctx);
-    if (overhead.empty()) {
-        // the node-side columns change only when the node set does: they stay on the device (gf_cluster_set), a Filter moves
-        // its reservation entries and its own candidate flags only.  Another user of the context (the UnschedulablePodMarker
-        // shares it) may have replaced the resident cluster or usage in between: the context's generations say so.
+    // The node-side columns stay on the device (gf_cluster_set): all but the overhead change only when the node set does, and the
+    // overhead changes by rows (gf_overhead_update).  A Filter moves the overhead rows that differ from what is resident, its
+    // reservation entries and its own candidate flags only.  Another user of the context (the UnschedulablePodMarker shares it)
+    // may have replaced the resident cluster or usage in between: the context's generations say so.
+    bool resident_route = true;
+    {
+        const bool with_over = !over[0].empty();
+        const bool known_over = flatOverhead->version != 0 && flatOverhead->version == resident_over_version_;  // compared before
         uint64_t gen[3] = {0, 0, 0};
         (void)gf_generation(ctx, gen);
-        if (resident_cluster_ != cluster.version || cluster.version == 0 || gen[1] != seen_cluster_gen_) {
-            if (gf_cluster_set(ctx, n, cluster.alloc[0].data(), cluster.alloc[1].data(), cluster.alloc[2].data(), nullptr, nullptr,
-                               nullptr, cluster.base_flags.data(), cluster.zone.data(), (uint32_t)cluster.zone_labels.size(),
-                               cluster.name_rank.data()) != GF_OK)
+        const bool own_cluster = resident_cluster_ == cluster.version && cluster.version != 0;
+        bool set_cluster = !own_cluster || gen[1] != seen_cluster_gen_;
+        std::vector<uint32_t> rows;  // the rows in which this request's overhead differs from what this extender last sent
+        if (own_cluster && !known_over && (with_over || !resident_over_[0].empty())) {
+            overheadRowDiff(over, resident_over_, n, &rows);
+            if (rows.size() > (size_t)n / 2) set_cluster = true;  // most of the cluster: one upload of the columns is cheaper
+        }
+        if (set_cluster) {
+            ++cluster_set_calls_;
+            if (gf_cluster_set(ctx, n, cluster.alloc[0].data(), cluster.alloc[1].data(), cluster.alloc[2].data(),
+                               with_over ? over[0].data() : nullptr, with_over ? over[1].data() : nullptr,
+                               with_over ? over[2].data() : nullptr, cluster.base_flags.data(), cluster.zone.data(),
+                               (uint32_t)cluster.zone_labels.size(), cluster.name_rank.data()) != GF_OK) {
+                resident_cluster_ = 0;
                 return not_served(std::string("gf_cluster_set: ") + gf_last_error(ctx));
+            }
+            if (!own_cluster || !rows.empty()) built_epoch_ = 0;  // the installed snapshot was built from other columns
             resident_cluster_ = cluster.version;
             resident_usage_ = 0;  // gf_cluster_set zeroed the resident usage
+            for (int j = 0; j < 3; ++j) resident_over_[j] = over[j];  // (empty without overhead)
+            resident_over_version_ = flatOverhead->version;
             (void)gf_generation(ctx, gen);
             seen_cluster_gen_ = gen[1];
             seen_usage_gen_ = gen[2];
+        } else if (!rows.empty()) {
+            std::vector<int64_t> rcol[3];
+            for (int j = 0; j < 3; ++j) {
+                rcol[j].reserve(rows.size());
+                for (uint32_t r : rows) rcol[j].push_back(with_over ? over[j][r] : 0);
+            }
+            ++overhead_update_calls_;
+            overhead_rows_sent_ += rows.size();
+            built_epoch_ = 0;  // the installed snapshot was built from other rows
+            resident_over_version_ = 0;
+            if (gf_overhead_update(ctx, (uint32_t)rows.size(), rows.data(), rcol[0].data(), rcol[1].data(), rcol[2].data()) != GF_OK) {
+                resident_route = false;  // (a value out of range, a failed device call): the full build below decides
+            } else {
+                if (resident_over_[0].empty())
+                    for (int j = 0; j < 3; ++j) resident_over_[j].assign(n, 0);
+                for (size_t i = 0; i < rows.size(); ++i)
+                    for (int j = 0; j < 3; ++j) resident_over_[j][rows[i]] = rcol[j][i];
+                resident_over_version_ = flatOverhead->version;
+                (void)gf_generation(ctx, gen);
+                seen_cluster_gen_ = gen[1];
+            }
+        } else if (own_cluster) {
+            resident_over_version_ = flatOverhead->version;  // compared equal: the next Filter with this version need not look
         }
         // a caller that keeps its flattened reservations (flat->version != 0) gets the usage sums kept on the device too: they
         // are sent when the list changes, and a Filter between two changes moves no reservation at all.  (A host that tracks
         // its ResourceReservation events would send only the K + 1 entries of the object that changed: gf_usage_apply.)
         const bool keep_usage = flat != &local && flat->version != 0;
-        if (keep_usage && (resident_usage_ != flat->version || gen[2] != seen_usage_gen_)) {
+        if (resident_route && keep_usage && (resident_usage_ != flat->version || gen[2] != seen_usage_gen_)) {
             resident_usage_ = 0;
             if (gf_usage_reset(ctx) != GF_OK ||
                 gf_usage_apply(ctx, (uint32_t)rnode.size(), rnode.data(), rreq[0].data(), rreq[1].data(), rreq[2].data(), +1) != GF_OK)
@@ -613,10 +691,11 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
             (void)gf_generation(ctx, gen);
             seen_usage_gen_ = gen[2];
         }
-        // nothing changed since this extender's last Filter: the installed snapshot IS this request's snapshot
+        // nothing changed since this extender's last Filter (no overhead row differed either: a change above cleared built_epoch_):
+        // the installed snapshot IS this request's snapshot
         const bool same_snapshot = keep_usage && built_epoch_ != 0 && gen[0] == built_epoch_ && built_cluster_ == cluster.version &&
                                    built_usage_ == flat->version && built_flags_ == flags;
-        if (!same_snapshot) {
+        if (resident_route && !same_snapshot) {
             built_epoch_ = 0;
             const int brc = keep_usage
                                 ? gf_snapshot_build_resident(ctx, GF_RESIDENT_USAGE, nullptr, nullptr, nullptr, nullptr, flags.data(),
@@ -636,16 +715,15 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
                 built_flags_ = flags;
             }
         }
-    } else if (gf_snapshot_build(ctx, n, cluster.alloc[0].data(), cluster.alloc[1].data(), cluster.alloc[2].data(), over[0].data(),
-                                 over[1].data(), over[2].data(), (uint32_t)rnode.size(), rnode.data(), rreq[0].data(),
-                                 rreq[1].data(), rreq[2].data(), flags.data(), cluster.zone.data(),
-                                 (uint32_t)cluster.zone_labels.size(), cluster.name_rank.data(), nullptr, nullptr, nullptr, nullptr,
-                                 nullptr, nullptr) != GF_OK) {
+    }
+    if (!resident_route) {  // what the resident route could not take: everything travels, nothing stays
         resident_cluster_ = 0;
-        return not_served(std::string("gf_snapshot_build: ") + gf_last_error(ctx));
-    } else {
-        resident_cluster_ = 0;  // gf_snapshot_build replaced the resident cluster (with this request's overhead)
         built_epoch_ = 0;
+        if (gf_snapshot_build(ctx, n, cluster.alloc[0].data(), cluster.alloc[1].data(), cluster.alloc[2].data(), over[0].data(),
+                              over[1].data(), over[2].data(), (uint32_t)rnode.size(), rnode.data(), rreq[0].data(), rreq[1].data(),
+                              rreq[2].data(), flags.data(), cluster.zone.data(), (uint32_t)cluster.zone_labels.size(),
+                              cluster.name_rank.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != GF_OK)
+            return not_served(std::string("gf_snapshot_build: ") + gf_last_error(ctx));
     }
     uint64_t total_k = 0;
     for (const gf_app& a : apps) total_k += (uint64_t)a.k;

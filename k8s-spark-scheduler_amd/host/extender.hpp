@@ -85,6 +85,23 @@ struct FlatReservations {
                       const FlatCluster& cluster, FlatReservations* out, std::string* err);
 };
 
+// overheadComputer.GetOverhead in flat form: dense cpu | memory | gpu columns over the cluster's node order (nodes the map does
+// not name read zero; names outside the cluster are skipped).  A host keeps it next to its overhead cache and rebuilds — or
+// patches — it on the pod events that change a node's overhead; a Filter then neither walks the string-keyed map nor, while the
+// version stands, compares a column.
+#define GANGFIT_HOST_FLAT_OVERHEAD 1
+struct FlatOverhead {
+    std::vector<int64_t> over[3];  // empty: no overhead anywhere
+    uint64_t version = 0;          // unique per Build; a caller that patches the columns in place takes a new one (Touch)
+    static bool Build(const NodeGroupResources& overhead, const FlatCluster& cluster, FlatOverhead* out, std::string* err);
+    void Touch();
+};
+
+// The rows in which two dense overhead column sets differ (selectDriverNodeFlat: what gf_overhead_update must send).  `want` /
+// `have` are cpu | memory | gpu columns of n values each; an EMPTY column set stands for "no overhead anywhere" (all zero).
+// rows: the node indices in ascending order.
+void overheadRowDiff(const std::vector<int64_t> want[3], const std::vector<int64_t> have[3], uint32_t n, std::vector<uint32_t>* rows);
+
 class SparkSchedulerExtender {
 public:
     SparkSchedulerExtender(Binpacker binpacker, NodeSorter sorter, bool isFIFO, FifoConfig fifo)
@@ -111,11 +128,19 @@ public:
     // available / schedulable columns and NodeSorter.PotentialNodes never touch a string-keyed map.  `cluster` must
     // describe exactly the nodes the driver's affinity matches.  Label-priority re-sorts are not configured on this path.
     // `flat` (nullable) = the reservations already in flat form; when null they are flattened from `reservations` here.
+    // `flatOverhead` (nullable) = the overhead already in flat form, used INSTEAD of the `overhead` map; when null the map is
+    // canonicalised here on every Filter.
     SelectNodeResult selectDriverNodeFlat(const std::string& instanceGroup, const Pod& driver,
                                           const std::vector<std::string>& nodeNames, const FlatCluster& cluster,
-                                          const FlatReservations* flat = nullptr);
+                                          const FlatReservations* flat = nullptr, const FlatOverhead* flatOverhead = nullptr);
     // The next selectDriverNodeFlat rebuilds the snapshot even if nothing changed (host_bench times both).
     void forgetInstalledSnapshot() { built_epoch_ = 0; }
+    // What the flat route has sent so far (tests and host_bench read them): Filters served, gf_overhead_update calls and the rows
+    // they carried, gf_cluster_set calls.
+    uint64_t flatCalls() const { return flat_calls_; }
+    uint64_t overheadUpdateCalls() const { return overhead_update_calls_; }
+    uint64_t overheadRowsSent() const { return overhead_rows_sent_; }
+    uint64_t clusterSetCalls() const { return cluster_set_calls_; }
 
     // unschedulablepods.go:132-166: does the application fit an EMPTY cluster (usage = 0, the given overhead)?
     // nodes are used in lister order for both candidate lists.
@@ -159,10 +184,15 @@ public:
 private:
     uint64_t resident_cluster_ = 0;  // FlatCluster::version whose static columns sit on the device (selectDriverNodeFlat)
     uint64_t resident_usage_ = 0;    // FlatReservations::version whose usage sums sit on the device (for resident_cluster_)
+    // the dense overhead columns this extender last put on the device for resident_cluster_ (gf_cluster_set or
+    // gf_overhead_update); empty = none (a cluster set with NULL columns).  A Filter sends the rows in which its request differs.
+    std::vector<int64_t> resident_over_[3];
+    uint64_t resident_over_version_ = 0;  // FlatOverhead::version those columns came from (0: from the map, always compared)
+    uint64_t overhead_update_calls_ = 0, overhead_rows_sent_ = 0, cluster_set_calls_ = 0;
     // what the context held after this extender's last call (gf_generation): another user of the same gf_ctx that replaces the
-    // cluster, the usage or the snapshot moves these on, and the next Filter sends its own state again
+    // cluster, its overhead rows, the usage or the snapshot moves these on, and the next Filter sends its own state again
     uint64_t seen_cluster_gen_ = 0, seen_usage_gen_ = 0;
-    // the snapshot the last Filter installed: while cluster, usage and candidate flags are the same and nobody installed
+    // the snapshot the last Filter installed: while cluster, overhead rows, usage and candidate flags are the same and nobody installed
     // another one (snapshot epoch), the next Filter neither rebuilds nor re-sorts — and its chain resumes from the previous
     // chain's checkpoints (include/gangfit.h, "Incremental FIFO chains")
     uint64_t built_epoch_ = 0, built_cluster_ = 0, built_usage_ = 0;

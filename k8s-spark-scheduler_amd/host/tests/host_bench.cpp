@@ -5,7 +5,10 @@
 //   map   selectDriverNode      — UsageForNodes / NodeSchedulingMetadataForNodes / PotentialNodes on string-keyed maps
 //                                 like the Go host, then ONE FIFO-chain call
 //   flat  selectDriverNodeFlat  — flat columns -> gf_snapshot_build (replay + metadata + sort on the device) -> the chain
-// usage: host_bench [n_nodes] [n_pending] [n_reservations] [packer]
+// usage: host_bench [n_nodes] [n_pending] [n_reservations] [packer] [overhead]
+//   a fifth argument "overhead": ONLY the flat route on a cluster with overhead on every node (overhead.go:91-153: daemonsets and
+//   non-Spark pods) is timed, reservations kept in flat form — (a) overhead unchanged between Filters, (b) one node's overhead
+//   changes before every Filter, (c) 1 % of the nodes change — and one JSON line is printed (profiles/filter_with_overhead.txt)
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -121,6 +124,86 @@ int main(int argc, char** argv) {
     }
     const double flat_rr_ms = std::chrono::duration<double, std::milli>(Clock::now() - t0).count();
 
+    if (argc > 5 && std::strcmp(argv[5], "overhead") == 0) {
+        const int64_t Mi = 1024ll * 1024;
+        auto some_overhead = [&]() {  // a daemonset's worth: some cpu, some memory
+            return Resources{Quantity::FromMilli(100 + 50 * (int64_t)(next() % 20)), Quantity::FromInt((int64_t)(256 + 128 * (next() % 16)) * Mi),
+                             Quantity()};
+        };
+        for (const std::string& name : nodeNames) ext.overhead[name] = some_overhead();
+#ifdef GANGFIT_HOST_FLAT_OVERHEAD
+        FlatOverhead fo;  // the overhead kept in flat form next to the host's overhead cache, patched by the same events
+        if (!FlatOverhead::Build(ext.overhead, cluster, &fo, &err)) {
+            std::printf("FlatOverhead::Build: %s\n", err.c_str());
+            return 1;
+        }
+#endif
+        auto change = [&](int how_many) {  // (the informer's work: not part of the Filter)
+            for (int i = 0; i < how_many; ++i) {
+                const std::string& name = nodeNames[next() % (uint64_t)n_nodes];
+                Resources& o = ext.overhead[name];
+                const Resources was = o;
+                while (o.Eq(was)) o = some_overhead();
+#ifdef GANGFIT_HOST_FLAT_OVERHEAD
+                int64_t v[3];
+                o.canonical(v);
+                for (int j = 0; j < 3; ++j) fo.over[j][cluster.index.at(name)] = v[j];
+#endif
+            }
+#ifdef GANGFIT_HOST_FLAT_OVERHEAD
+            if (how_many) fo.Touch();
+#endif
+        };
+        auto same_answer = [](const SelectNodeResult& x, const SelectNodeResult& y) {
+            bool same = x.served && y.served && x.outcome == y.outcome && x.node == y.node && x.created.has_value() == y.created.has_value();
+            if (same && x.created)
+                for (const auto& [name, res] : x.created->Reservations)
+                    same = same && y.created->Reservations.count(name) && y.created->Reservations.at(name).Node == res.Node;
+            return same;
+        };
+        bool same = same_answer(ext.selectDriverNode("batch-medium-priority", driver, nodeNames, ext.nodes),
+                                ext.selectDriverNodeFlat("batch-medium-priority", driver, nodeNames, cluster, &flat));
+        const int calls = 40, warm = 4;  // the call count of every other case of this program
+        // [0]: the overhead map canonicalised by every Filter; [1]: the overhead handed over in flat form (FlatOverhead)
+        std::vector<double> ms[2][3];
+        const int changed[3] = {0, 1, n_nodes / 100 > 0 ? n_nodes / 100 : 1};
+        int variants = 1;
+#ifdef GANGFIT_HOST_FLAT_OVERHEAD
+        variants = 2;
+#endif
+        for (int v = 0; v < variants; ++v)
+            for (int c = 0; c < 3; ++c)
+                for (int i = 0; i < warm + calls; ++i) {
+                    change(changed[c]);
+                    t0 = Clock::now();
+#ifdef GANGFIT_HOST_FLAT_OVERHEAD
+                    SelectNodeResult r = ext.selectDriverNodeFlat("batch-medium-priority", driver, nodeNames, cluster, &flat, v ? &fo : nullptr);
+#else
+                    SelectNodeResult r = ext.selectDriverNodeFlat("batch-medium-priority", driver, nodeNames, cluster, &flat);
+#endif
+                    if (i >= warm) ms[v][c].push_back(std::chrono::duration<double, std::milli>(Clock::now() - t0).count());
+                    same = same && r.served;
+                }
+        // ... and the last answer, after all those changes, is still the map route's
+        same = same && same_answer(ext.selectDriverNode("batch-medium-priority", driver, nodeNames, ext.nodes),
+#ifdef GANGFIT_HOST_FLAT_OVERHEAD
+                                   ext.selectDriverNodeFlat("batch-medium-priority", driver, nodeNames, cluster, &flat, &fo));
+#else
+                                   ext.selectDriverNodeFlat("batch-medium-priority", driver, nodeNames, cluster, &flat));
+#endif
+        std::printf("{\"nodes\": %d, \"pending_drivers\": %d, \"resource_reservations\": %d, \"packer\": \"%s\", \"overhead_on_every_node\": true, "
+                    "\"calls\": %d, \"rows_changed_per_filter\": [0, 1, %d]", n_nodes, n_pending, n_rr, packer.c_str(), calls, changed[2]);
+        const char* vname[2] = {"overhead_map_per_filter", "overhead_kept_flat"};
+        for (int v = 0; v < variants; ++v)
+            std::printf(", \"%s\": {\"filter_overhead_unchanged_ms\": {\"p50\": %.3f, \"p99\": %.3f}, "
+                        "\"filter_one_node_changed_ms\": {\"p50\": %.3f, \"p99\": %.3f}, "
+                        "\"filter_one_percent_changed_ms\": {\"p50\": %.3f, \"p99\": %.3f}}",
+                        vname[v], pct(ms[v][0], 0.5), pct(ms[v][0], 0.99), pct(ms[v][1], 0.5), pct(ms[v][1], 0.99), pct(ms[v][2], 0.5),
+                        pct(ms[v][2], 0.99));
+        std::printf(", \"routes_agree\": %s}\n", same ? "true" : "false");
+        gf_destroy(ctx);
+        return same ? 0 : 1;
+    }
     SelectNodeResult a = ext.selectDriverNode("batch-medium-priority", driver, nodeNames, ext.nodes);
     SelectNodeResult b = ext.selectDriverNodeFlat("batch-medium-priority", driver, nodeNames, cluster);
     bool same = a.served && b.served && a.outcome == b.outcome && a.node == b.node && a.created.has_value() == b.created.has_value();

@@ -98,9 +98,28 @@ __device__ __forceinline__ void lds_barrier() {
 // ------------------------------------------------------------------------------------------------ app registers
 
 struct App {
+    typedef int64_t value_t;
     int64_t drv0, drv1, drv2;
     int64_t exe0, exe1, exe2;
     double rcp0, rcp1, rcp2;  // 1.0 / exe_j (only used when exe_j > 0)
+    int32_t k;
+    uint32_t flags;
+    uint64_t exec_off;
+};
+
+// The same record in the snapshot's scaled int32 domain (NodeTable::ncpu ..: value = scaled value * unit of its dimension), for
+// the decisions of the resident worker: every request is an exact multiple of its dimension's unit and scales below 2^30
+// (gangfit_worker.inc: scale_record decides that per application).  Comparisons, subtractions and floor divisions do not change
+// under a common exact factor, so the decision code below — one source, instantiated over App::value_t — gives the same answer
+// in either domain.  mag / sh: division by exe_j as a multiplication (narrow_magic); un_j = 0xFFFFFFFF for a zero request
+// dimension ("never limits"), else 0.
+struct NarrowApp {
+    typedef int32_t value_t;
+    int32_t drv0, drv1, drv2;
+    int32_t exe0, exe1, exe2;
+    uint32_t mag0, mag1, mag2;
+    uint32_t sh0, sh1, sh2;
+    uint32_t un0, un1, un2;
     int32_t k;
     uint32_t flags;
     uint64_t exec_off;
@@ -164,6 +183,18 @@ __device__ __forceinline__ int32_t cap3(int64_t a0, int64_t a1, int64_t a2, cons
     return c < g ? c : g;
 }
 
+// The scaled domain: three quotients by multiplication (Granlund & Montgomery, see narrow_magic), their minimum, the clamp to
+// K; a slot that is short in any dimension before the first executor (a_j < 0) holds none, whatever the request.
+__device__ __forceinline__ int32_t cap3(int32_t a0, int32_t a1, int32_t a2, const NarrowApp& app) {
+    const uint32_t q0 = (__umulhi(app.mag0, (uint32_t)a0 << 1) >> app.sh0) | app.un0;
+    const uint32_t q1 = (__umulhi(app.mag1, (uint32_t)a1 << 1) >> app.sh1) | app.un1;
+    const uint32_t q2 = (__umulhi(app.mag2, (uint32_t)a2 << 1) >> app.sh2) | app.un2;
+    uint32_t q = q0 < q1 ? q0 : q1;
+    q = q < q2 ? q : q2;
+    q = q < (uint32_t)app.k ? q : (uint32_t)app.k;
+    return ((a0 | a1 | a2) < 0) ? 0 : (int32_t)q;
+}
+
 // cap >= 1 without any division: base + exe <= avail in every dimension (the first add-then-compare step).
 // Lane masks in scalar registers (the compares write them there) instead of per-lane booleans that a __ballot turns back into a
 // mask by way of a select and a second compare: "every component at least r" for 64 lanes at once, ANDed with a wave-uniform
@@ -172,15 +203,21 @@ __device__ __forceinline__ uint64_t ge3_mask(int64_t a0, int64_t a1, int64_t a2,
     constexpr int kSGE = 39;  // signed >=
     return __builtin_amdgcn_sicmpl(a0, r0, kSGE) & __builtin_amdgcn_sicmpl(a1, r1, kSGE) & __builtin_amdgcn_sicmpl(a2, r2, kSGE);
 }
+__device__ __forceinline__ uint64_t ge3_mask(int32_t a0, int32_t a1, int32_t a2, int32_t r0, int32_t r1, int32_t r2) {
+    constexpr int kSGE = 39;  // signed >=
+    return __builtin_amdgcn_sicmp(a0, r0, kSGE) & __builtin_amdgcn_sicmp(a1, r1, kSGE) & __builtin_amdgcn_sicmp(a2, r2, kSGE);
+}
 __device__ __forceinline__ uint64_t low_lanes(uint32_t n) { return n >= 64u ? ~0ull : ((1ull << n) - 1ull); }
 __device__ __forceinline__ bool lane_in(uint64_t uniform_mask) { return __builtin_amdgcn_inverse_ballot_w64(uniform_mask); }
 
-__device__ __forceinline__ bool cap_ge1(int64_t a0, int64_t a1, int64_t a2, const App& app) {
+template <class A>
+__device__ __forceinline__ bool cap_ge1(typename A::value_t a0, typename A::value_t a1, typename A::value_t a2, const A& app) {
     return app.exe0 <= a0 && app.exe1 <= a1 && app.exe2 <= a2;
 }
 
 // !driverResources.GreaterThan(available)  (LIB/binpack/binpack.go:69, LIB/resources/resources.go:239-241)
-__device__ __forceinline__ bool driver_fits(int64_t a0, int64_t a1, int64_t a2, const App& app) {
+template <class A>
+__device__ __forceinline__ bool driver_fits(typename A::value_t a0, typename A::value_t a1, typename A::value_t a2, const A& app) {
     return app.drv0 <= a0 && app.drv1 <= a1 && app.drv2 <= a2;
 }
 
@@ -223,6 +260,48 @@ struct GlobalView {
         cpu[s] -= r0;
         mem[s] -= r1;
         gpu[s] -= r2;
+    }
+};
+
+// The snapshot's scaled int32 twin (NodeTable::ncpu / nmem / ngpu) behind the same interface: twelve bytes per slot, 32-bit
+// compares.  Read-only (the resident worker's tightly-pack decisions; gangfit_worker.inc).  The chunk maxima stay the wide ones:
+// group 0 of the index is scaled once per launch by its user (Group0T<int32_t>), the chunks behind it — rare on that path — are
+// compared in int64 against the request scaled back up.
+struct NarrowView {
+    const int32_t* cpu;
+    const int32_t* mem;
+    const int32_t* gpu;
+    const int64_t* cmax_cpu;
+    const int64_t* cmax_mem;
+    const int64_t* cmax_gpu;
+    const uint64_t* xm;
+    const uint64_t* dm;
+    uint32_t n_chunks;
+    int64_t unit0, unit1, unit2;
+    static constexpr bool kCompactScan = true;
+    // an upper bound of the chunk's scaled maxima: ceil(m / unit), kept inside (-2^31, 2^31) (a table with this form has no real
+    // value at or past 2^30 units; the sentinel's maximum is far below every request)
+    static __device__ __forceinline__ int32_t scale_max(int64_t m, int64_t unit) {
+        const int64_t q = m / unit + (m % unit > 0 ? 1 : 0);  // truncation towards zero is the ceiling of a negative quotient
+        return (int32_t)(q < -(INT64_C(1) << 30) ? -(INT64_C(1) << 30) : (q > (INT64_C(1) << 30) ? (INT64_C(1) << 30) : q));
+    }
+    __device__ __forceinline__ void chunk_maxima(uint32_t c, int32_t& m0, int32_t& m1, int32_t& m2) const {
+        m0 = scale_max(cmax_cpu[c], unit0);
+        m1 = scale_max(cmax_mem[c], unit1);
+        m2 = scale_max(cmax_gpu[c], unit2);
+    }
+    __device__ __forceinline__ bool chunk_may_hold(uint32_t c, int32_t r0, int32_t r1, int32_t r2) const {
+        const int64_t m0 = cmax_cpu[c], m1 = cmax_mem[c], m2 = cmax_gpu[c];
+        return (bool)((m0 >= (int64_t)r0 * unit0) & (m1 >= (int64_t)r1 * unit1) & (m2 >= (int64_t)r2 * unit2));
+    }
+    __device__ __forceinline__ uint64_t chunk_xmask(uint32_t c) const { return xm[c]; }
+    __device__ __forceinline__ uint64_t chunk_dmask(uint32_t c) const { return dm[c]; }
+    __device__ __forceinline__ bool xcand(uint32_t s) const { return (xm[s >> 6] >> (s & 63)) & 1ull; }
+    __device__ __forceinline__ bool dcand(uint32_t s) const { return (dm[s >> 6] >> (s & 63)) & 1ull; }
+    __device__ __forceinline__ void load(uint32_t s, int32_t& a0, int32_t& a1, int32_t& a2) const {
+        a0 = cpu[s];
+        a1 = mem[s];
+        a2 = gpu[s];
     }
 };
 
@@ -397,9 +476,9 @@ __device__ __forceinline__ uint32_t chunk_len(uint32_t n, uint32_t b, uint32_t w
 // DRV selects which candidate mask must be non-empty (driver scan vs executor scan).
 // cand receives lane l's candidate word of chunk 64g + l (0 beyond the limit): read_lane(cand, b) is the mask of the chunk
 // whose bit b is set, so the scans need not load it again.  The maxima and the mask are requested together (one round trip).
-template <bool DRV, class View>
-__device__ __forceinline__ uint64_t chunk_group_mask(const View& V, uint32_t g, uint32_t chunk_limit, int64_t r0,
-                                                     int64_t r1, int64_t r2, int lane, uint64_t& cand) {
+template <bool DRV, class View, class R>
+__device__ __forceinline__ uint64_t chunk_group_mask(const View& V, uint32_t g, uint32_t chunk_limit, R r0, R r1, R r2, int lane,
+                                                     uint64_t& cand) {
     const uint32_t c = g * kWave + lane;
     bool ok = false;
     cand = 0;
@@ -409,17 +488,17 @@ __device__ __forceinline__ uint64_t chunk_group_mask(const View& V, uint32_t g, 
     }
     return __ballot(ok);
 }
-template <bool DRV, class View>
-__device__ __forceinline__ uint64_t chunk_group_mask(const View& V, uint32_t g, uint32_t chunk_limit, int64_t r0,
-                                                     int64_t r1, int64_t r2, int lane) {
+template <bool DRV, class View, class R>
+__device__ __forceinline__ uint64_t chunk_group_mask(const View& V, uint32_t g, uint32_t chunk_limit, R r0, R r1, R r2, int lane) {
     uint64_t cand;
     return chunk_group_mask<DRV>(V, g, chunk_limit, r0, r1, r2, lane, cand);
 }
 
 // First position p in [from, n_d) of driverNodePriorityOrder whose node passes the driver-fit check, else -1.
-template <class View>
-__device__ __forceinline__ int64_t wave_first_fitting_driver(const View& V, const Orders& O, const App& app,
+template <class View, class A>
+__device__ __forceinline__ int64_t wave_first_fitting_driver(const View& V, const Orders& O, const A& app,
                                                              uint32_t from, int lane, unsigned long long& visited) {
+    typedef typename A::value_t val_t;
     if (O.d_identity) {  // position == slot: prune whole chunks with the maxima index
         const uint32_t dc = (O.n_d + kWave - 1) / kWave;
         for (uint32_t g = (from / kWave) / kWave; g * kWave < dc; ++g) {
@@ -434,7 +513,7 @@ __device__ __forceinline__ int64_t wave_first_fitting_driver(const View& V, cons
                 const uint64_t cdm = (uint64_t)read_lane((int64_t)cand, bit);
                 bool fit = false;
                 if (i < O.n_d && i >= from && ((cdm >> lane) & 1ull)) {
-                    int64_t a0, a1, a2;
+                    val_t a0, a1, a2;
                     V.load(i, a0, a1, a2);
                     fit = driver_fits(a0, a1, a2, app);
                 }
@@ -449,7 +528,7 @@ __device__ __forceinline__ int64_t wave_first_fitting_driver(const View& V, cons
         const uint32_t i = b + lane;
         bool fit = false;
         if (i < O.n_d && (!O.dpos_mask || V.dcand(i))) {
-            int64_t a0, a1, a2;
+            val_t a0, a1, a2;
             V.load(O.driver_slot(i), a0, a1, a2);
             fit = driver_fits(a0, a1, a2, app);
         }
@@ -463,16 +542,17 @@ __device__ __forceinline__ int64_t wave_first_fitting_driver(const View& V, cons
 // O(N) driver choice on the fallback path: first position p >= from in driver order with
 //   fit(p) && total(p) >= K,  total = S            if the node is not an executor candidate
 //                                   = S - c0 + cd   otherwise           (SURVEY.md section 8 "O(N) driver choice")
-template <class View>
-__device__ __forceinline__ int64_t wave_next_feasible_driver(const View& V, const Orders& O, const App& app,
+template <class View, class A>
+__device__ __forceinline__ int64_t wave_next_feasible_driver(const View& V, const Orders& O, const A& app,
                                                              uint32_t from, int64_t S, int lane,
                                                              unsigned long long& visited) {
+    typedef typename A::value_t val_t;
     for (uint32_t b = from; b < O.n_d; b += kWave) {
         const uint32_t i = b + lane;
         bool ok = false;
         if (i < O.n_d && ((!O.d_identity && !O.dpos_mask) || V.dcand(i))) {
             const uint32_t s = O.driver_slot(i);
-            int64_t a0, a1, a2;
+            val_t a0, a1, a2;
             V.load(s, a0, a1, a2);
             if (driver_fits(a0, a1, a2, app)) {
                 int64_t total = S;
@@ -494,14 +574,16 @@ __device__ __forceinline__ int64_t wave_next_feasible_driver(const View& V, cons
 // Lane l's view of chunk l (group 0 of the chunk index) for both roles: the three maxima and the two candidate words.
 // Nothing here depends on the application, so the independent kernel requests it BEFORE its app record: the two misses
 // overlap instead of following each other.
-struct Group0 {
-    int64_t m0 = 0, m1 = 0, m2 = 0;
+template <class VAL>
+struct Group0T {
+    VAL m0 = 0, m1 = 0, m2 = 0;
     uint64_t dcand = 0, xcand = 0;
     bool ind = false, inx = false;
 };
-template <class View>
-__device__ __forceinline__ Group0 load_group0(const View& V, const Orders& O, int lane) {
-    Group0 g;
+typedef Group0T<int64_t> Group0;
+template <class View, class VAL = int64_t>
+__device__ __forceinline__ Group0T<VAL> load_group0(const View& V, const Orders& O, int lane) {
+    Group0T<VAL> g;
     const uint32_t dc = (O.n_d + kWave - 1) / kWave, xc = (O.n_x + kWave - 1) / kWave;
     const uint32_t c = (uint32_t)lane;
     g.ind = c < dc && c < V.n_chunks;  // general layout: driver positions may outnumber the slots
@@ -526,14 +608,16 @@ struct HasCompactScan<View, decltype((void)View::kCompactScan)> {
 // What wave_decide_merged already holds when the executor scan starts: the chunk mask of group 0 and the slots of the
 // first candidate chunk, requested together with the driver's (a decision is a chain of dependent global round trips —
 // every launch starts with cold L2s — so requests that do not depend on each other must be in flight together).
-struct ScanPre {
+template <class VAL>
+struct ScanPreT {
     bool on = false;
     uint64_t m = 0;     // group 0: chunks that may hold an executor
     uint64_t cand = 0;  // lane l: executor-candidate word of chunk l
     int c = -1;         // preloaded chunk, -1 = none
-    int64_t a0 = 0, a1 = 0, a2 = 0;
+    VAL a0 = 0, a1 = 0, a2 = 0;
     uint32_t node = 0;  // slot_node of this lane's slot in chunk c (SLOTS = false)
 };
+typedef ScanPreT<int64_t> ScanPre;
 
 // tightlyPackExecutors with the driver reserved on slot ds.  Returns the sum of clamped capacities over the visited
 // prefix (>= K  <=>  feasible; the scan stops at the first chunk where K is reached).  Writes placements.
@@ -609,21 +693,23 @@ __device__ __forceinline__ int64_t wave_tight_scan(const View& V, const Orders& 
 // chunk.  A chunk with many such slots is its own batch and is not moved.  The batch is processed as soon as it holds
 // K - taken slots (each is good for at least one executor, so the scan ends there — as lazy as the reference's loop up
 // to the chunk it stops in), when the next chunk does not fit in, and at the end of the candidates.
-template <class View, bool SLOTS>
-__device__ __forceinline__ int64_t wave_tight_scan_compact(const View& V, const Orders& O, const App& app, uint32_t ds,
-                                                           uint32_t* __restrict__ out, int lane,
-                                                           unsigned long long& visited, const ScanPre& pre = ScanPre(),
+template <class View, bool SLOTS, class A>
+__device__ __forceinline__ int64_t wave_tight_scan_compact(const View& V, const Orders& O, const A& app, uint32_t ds,
+                                                           uint32_t* __restrict__ out, int lane, unsigned long long& visited,
+                                                           const ScanPreT<typename A::value_t>& pre = ScanPreT<typename A::value_t>(),
                                                            const bool wt = false) {
+    typedef typename A::value_t val_t;
+    constexpr bool kWide = sizeof(val_t) == 8;  // the gather moves a value as two dwords, or as one
     constexpr uint32_t kDenseLanes = 20;
     const int64_t K = app.k;
     const uint32_t xc = (O.n_x + kWave - 1) / kWave;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     int64_t taken = 0;
-    int64_t q0 = 0, q1 = 0, q2 = 0;  // the batch: table values (driver already reserved) and what a placement names
+    val_t q0 = 0, q1 = 0, q2 = 0;  // the batch: table values (driver already reserved) and what a placement names
     uint32_t qid = 0;
     uint32_t fill = 0;  // lanes [0, fill) of the batch are occupied (wave-uniform)
     // capacities, prefix, run emission for the lanes marked live; true when K is reached
-    auto process = [&](bool live, int64_t a0, int64_t a1, int64_t a2, uint32_t id) {
+    auto process = [&](bool live, val_t a0, val_t a1, val_t a2, uint32_t id) {
         const int32_t cp = live ? cap3(a0, a1, a2, app) : 0;
         const int32_t incl = wave_inclusive_scan(cp);
         const int32_t tot = read_lane(incl, kWave - 1);
@@ -653,7 +739,7 @@ __device__ __forceinline__ int64_t wave_tight_scan_compact(const View& V, const 
             const bool have = pre.on && (int)c == pre.c;  // wave-uniform
             const uint64_t in_m = cxm & low_lanes(chunk_len(O.n_x, c * kWave, kWave));  // candidate slots of the order in this chunk
             const bool in = lane_in(in_m);
-            int64_t a0 = 0, a1 = 0, a2 = 0;
+            val_t a0 = 0, a1 = 0, a2 = 0;
             uint32_t node = 0;
             if (in) {
                 if (have) {
@@ -690,19 +776,31 @@ __device__ __forceinline__ int64_t wave_tight_scan_compact(const View& V, const 
             const uint32_t rank = (uint32_t)__popcll((unsigned long long)(fm & lt_mask));
             const uint32_t dest = fit ? fill + rank : ((fill + n + ((uint32_t)lane - rank)) & 63u);
             const int addr = (int)(dest << 2);
-            const uint32_t r0l = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)a0);
-            const uint32_t r0h = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)((uint64_t)a0 >> 32));
-            const uint32_t r1l = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)a1);
-            const uint32_t r1h = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)((uint64_t)a1 >> 32));
-            const uint32_t r2l = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)a2);
-            const uint32_t r2h = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)((uint64_t)a2 >> 32));
             const uint32_t rid = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)id);
             const bool mine = (uint32_t)lane >= fill && (uint32_t)lane < fill + n;
-            if (mine) {
-                q0 = (int64_t)(((uint64_t)r0h << 32) | r0l);
-                q1 = (int64_t)(((uint64_t)r1h << 32) | r1l);
-                q2 = (int64_t)(((uint64_t)r2h << 32) | r2l);
-                qid = rid;
+            if constexpr (kWide) {
+                const uint32_t r0l = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)a0);
+                const uint32_t r0h = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)((uint64_t)a0 >> 32));
+                const uint32_t r1l = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)a1);
+                const uint32_t r1h = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)((uint64_t)a1 >> 32));
+                const uint32_t r2l = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)a2);
+                const uint32_t r2h = (uint32_t)__builtin_amdgcn_ds_permute(addr, (int)(uint32_t)((uint64_t)a2 >> 32));
+                if (mine) {
+                    q0 = (val_t)(((uint64_t)r0h << 32) | r0l);
+                    q1 = (val_t)(((uint64_t)r1h << 32) | r1l);
+                    q2 = (val_t)(((uint64_t)r2h << 32) | r2l);
+                    qid = rid;
+                }
+            } else {
+                const val_t r0 = (val_t)__builtin_amdgcn_ds_permute(addr, (int)a0);
+                const val_t r1 = (val_t)__builtin_amdgcn_ds_permute(addr, (int)a1);
+                const val_t r2 = (val_t)__builtin_amdgcn_ds_permute(addr, (int)a2);
+                if (mine) {
+                    q0 = r0;
+                    q1 = r1;
+                    q2 = r2;
+                    qid = rid;
+                }
             }
             fill += n;
             if (taken + (int64_t)fill >= K) {  // enough slots: each of them holds at least one executor
@@ -858,28 +956,31 @@ struct Decision {
     uint32_t ds_node = GF_NO_NODE;  // slot_node[ds] when the decision already holds it (requested with the driver's chunk)
 };
 
-template <int ALGO, class View, bool SLOTS>
-__device__ __forceinline__ int64_t wave_pack(const View& V, const Orders& O, const App& app, uint32_t ds,
+template <int ALGO, class View, bool SLOTS, class A>
+__device__ __forceinline__ int64_t wave_pack(const View& V, const Orders& O, const A& app, uint32_t ds,
                                              uint32_t* __restrict__ out, uint32_t* __restrict__ scratch_a,
-                                             uint32_t* __restrict__ scratch_b, int lane, int64_t& pass1,
-                                             unsigned long long& xvis, const ScanPre& pre = ScanPre(), const bool wt = false) {
-    if (ALGO == GF_ALGO_TIGHTLY_PACK) {  // (wt: tightly-pack only — the other packers' callers never set it)
+                                             uint32_t* __restrict__ scratch_b, int lane, int64_t& pass1, unsigned long long& xvis,
+                                             const ScanPreT<typename A::value_t>& pre = ScanPreT<typename A::value_t>(),
+                                             const bool wt = false) {
+    if constexpr (ALGO == GF_ALGO_TIGHTLY_PACK) {  // (wt: tightly-pack only — the other packers' callers never set it)
         if constexpr (HasCompactScan<View>::value)
             return wave_tight_scan_compact<View, SLOTS>(V, O, app, ds, out, lane, xvis, pre, wt);
         else
             return wave_tight_scan<View, SLOTS>(V, O, app, ds, out, lane, xvis, pre, wt);
+    } else if constexpr (ALGO == GF_ALGO_MINIMAL_FRAGMENTATION) {
+        return wave_minfrag<View, SLOTS>(V, O, app, ds, out, lane, xvis);
+    } else {
+        pass1 = wave_even_pass1<View, SLOTS>(V, O, app, ds, out, scratch_a, lane, xvis, pre);
+        if (pass1 >= (int64_t)app.k) return pass1;
+        return wave_even_general<View, SLOTS>(V, O, app, ds, out, scratch_a, scratch_b, pass1, lane);
     }
-    if (ALGO == GF_ALGO_MINIMAL_FRAGMENTATION) return wave_minfrag<View, SLOTS>(V, O, app, ds, out, lane, xvis);
-    pass1 = wave_even_pass1<View, SLOTS>(V, O, app, ds, out, scratch_a, lane, xvis, pre);
-    if (pass1 >= (int64_t)app.k) return pass1;
-    return wave_even_general<View, SLOTS>(V, O, app, ds, out, scratch_a, scratch_b, pass1, lane);
 }
 
 // Recovery after the first fitting candidate (position p0, slot ds0) could not host the gang: S_d is the exact
 // capacity total with the driver reserved on ds0 (< K).  Finds the first later candidate that works and packs with it.
 // Same answer as the reference's retry loop (binpack.go:67-85) in O(N) instead of O(|D| N).
-template <int ALGO, class View, bool SLOTS>
-__device__ __forceinline__ Decision wave_fallback(const View& V, const Orders& O, const App& app, int64_t p0,
+template <int ALGO, class View, bool SLOTS, class A>
+__device__ __forceinline__ Decision wave_fallback(const View& V, const Orders& O, const A& app, int64_t p0,
                                                   uint32_t ds0, int64_t S_d, uint32_t* __restrict__ out,
                                                   uint32_t* __restrict__ scratch_a, uint32_t* __restrict__ scratch_b,
                                                   int lane, unsigned long long& xvis, unsigned long long& dvis,
@@ -891,7 +992,7 @@ __device__ __forceinline__ Decision wave_fallback(const View& V, const Orders& O
     const int64_t K = app.k;
     int64_t S = S_d;
     if (ds0 < O.n_x && V.xcand(ds0)) {  // undo the driver reservation: S = S_d + cap(ds0, 0) - cap(ds0, drv)
-        int64_t a0, a1, a2;
+        typename A::value_t a0, a1, a2;
         V.load(ds0, a0, a1, a2);
         S = S_d + cap3(a0, a1, a2, app) - cap3(a0 - app.drv0, a1 - app.drv1, a2 - app.drv2, app);
     }
@@ -900,7 +1001,8 @@ __device__ __forceinline__ Decision wave_fallback(const View& V, const Orders& O
     if (p1 < 0) return dec;
     const uint32_t ds = O.driver_slot((uint32_t)p1);
     int64_t pass1 = 0;
-    const int64_t S1 = wave_pack<ALGO, View, SLOTS>(V, O, app, ds, out, scratch_a, scratch_b, lane, pass1, xvis, ScanPre(), wt);
+    const int64_t S1 = wave_pack<ALGO, View, SLOTS>(V, O, app, ds, out, scratch_a, scratch_b, lane, pass1, xvis,
+                                                    ScanPreT<typename A::value_t>(), wt);
     dec.feasible = S1 >= K;  // always true here; kept as a guard so a logic error shows up as a parity failure
     dec.ds = ds;
     dec.pass1 = pass1;
@@ -908,12 +1010,13 @@ __device__ __forceinline__ Decision wave_fallback(const View& V, const Orders& O
 }
 
 // SparkBinPack for one app by one wave.  out = exec_nodes + exec_off.  scratch_a / scratch_b: K uint32 each.
-template <int ALGO, class View, bool SLOTS>
-__device__ __forceinline__ Decision wave_decide(const View& V, const Orders& O, const App& app,
+template <int ALGO, class View, bool SLOTS, class A>
+__device__ __forceinline__ Decision wave_decide(const View& V, const Orders& O, const A& app,
                                                 uint32_t* __restrict__ out, uint32_t* __restrict__ scratch_a,
                                                 uint32_t* __restrict__ scratch_b, int lane, unsigned long long& xvis,
-                                                unsigned long long& dvis, const Group0* g0p = nullptr,
+                                                unsigned long long& dvis, const Group0T<typename A::value_t>* g0p = nullptr,
                                                 const SparseTable* gpu_view = nullptr, const bool wt = false) {
+    typedef typename A::value_t val_t;
     Decision dec;
     dec.feasible = false;
     dec.ds = 0;
@@ -921,7 +1024,7 @@ __device__ __forceinline__ Decision wave_decide(const View& V, const Orders& O, 
     const int64_t K = app.k;
     int64_t p0 = -1;
     uint32_t p0_node = GF_NO_NODE;
-    ScanPre pre;
+    ScanPreT<val_t> pre;
     // executors that need a gpu are packed from the compact table of gpu nodes (SparseTable); wave-uniform
     const bool sparse = gpu_view != nullptr && gpu_view->n_x != 0 && app.exe2 > 0 && K > 0 && O.d_identity &&
                         (ALGO == GF_ALGO_TIGHTLY_PACK || ALGO == GF_ALGO_DISTRIBUTE_EVENLY);
@@ -931,7 +1034,7 @@ __device__ __forceinline__ Decision wave_decide(const View& V, const Orders& O, 
         // Merged layout (driver position == slot): the chunk masks of group 0 for BOTH roles in one round trip (the
         // maxima are the same words), then the first candidate chunk of both roles — and the node ids — in one more.
         const uint32_t dc = (O.n_d + kWave - 1) / kWave;
-        const Group0 g0 = g0p != nullptr ? *g0p : load_group0(V, O, lane);
+        const Group0T<val_t> g0 = g0p != nullptr ? *g0p : load_group0<View, val_t>(V, O, lane);
         const uint64_t dcand = g0.dcand;
         pre.cand = g0.xcand;
         // (g0.ind / g0.inx = "lane < chunks of the order, and < chunks of the table": scalar masks)
@@ -948,7 +1051,7 @@ __device__ __forceinline__ Decision wave_decide(const View& V, const Orders& O, 
         const int bd = md ? __ffsll((unsigned long long)md) - 1 : -1;
         pre.c = (K > 0 && pre.m) ? __ffsll((unsigned long long)pre.m) - 1 : -1;
         const uint32_t limit = O.n_d > O.n_x ? O.n_d : O.n_x;
-        int64_t d0 = 0, d1 = 0, d2 = 0;
+        val_t d0 = 0, d1 = 0, d2 = 0;
         const uint32_t id = (uint32_t)(bd < 0 ? 0 : bd) * kWave + lane, ix = (uint32_t)(pre.c < 0 ? 0 : pre.c) * kWave + lane;
         uint32_t dnode = GF_NO_NODE, dsub = GF_NO_NODE;
         if (bd >= 0 && id < limit) {
@@ -997,7 +1100,7 @@ __device__ __forceinline__ Decision wave_decide(const View& V, const Orders& O, 
     int64_t pass1 = 0;
     // (SLOTS callers — the zone packers' one-launch kernel — hand in a view whose `slot_node` names SLOTS of the full table and whose
     //  candidate words are the zone's)
-    if constexpr (std::is_same<View, GlobalView>::value) {
+    if constexpr (std::is_same<View, GlobalView>::value && std::is_same<A, App>::value) {
         if (sparse) {
             // (2s) the same pack over the compact table of gpu nodes.  S_s = the capacity total with the driver reserved,
             //      exactly what the full order would give (every node left out has capacity 0 for this request).
@@ -1748,6 +1851,40 @@ __global__ __launch_bounds__(kWave) void selftest_kernel(uint64_t seed, uint32_t
                 q.mag1 = 0;
                 q.mag2 = mag;
                 if (ncap3_fit(na, 5, na, q, sh, 0u, sh, 0u, 0xFFFFFFFFu, 0u) != nwant) ++bad;
+            }
+            // (d) the resident worker's scaled decisions (gangfit_worker.inc): the multiplier without a 64-bit division against
+            //     narrow_magic, the scaled capacity (negative available values included) against the plain quotient, and the
+            //     lane-parallel scaling of a request word against a plain 64-bit divide: multiples and neighbours of multiples,
+            //     quotients of 2^30 - 1 and 2^30, negative words
+            if (narrow_magic_lane((uint32_t)ne) != mag || narrow_magic_lane(0u) != 0u) ++bad;
+            {
+                NarrowApp q{};
+                q.k = k;
+                q.exe0 = ne;
+                q.mag0 = mag;
+                q.sh0 = sh;
+                q.un1 = q.un2 = 0xFFFFFFFFu;
+                if (cap3(na, 5, 0, q) != nwant || cap3(na, -1, 0, q) != 0 || cap3(7, 0, na, q) != (na < 0 ? 0 : (7 / ne < k ? 7 / ne : k))) ++bad;
+            }
+            {
+                const uint64_t r2 = splitmix64(s), r3 = splitmix64(s);
+                const int64_t unit = (int64_t)(((r2 >> 2) >> (r2 % 61)) | 1ull) + (int64_t)(r2 & 1ull);  // 1 .. 2^62
+                int64_t quo;
+                switch (r3 % 5) {
+                case 0: quo = (int64_t)((r3 >> 8) & 0x3FFFFFFFull); break;
+                case 1: quo = (INT64_C(1) << 30) - 1; break;
+                case 2: quo = INT64_C(1) << 30; break;
+                case 3: quo = (int64_t)((r3 >> 8) % 3); break;
+                default: quo = (INT64_C(1) << 30) + (int64_t)((r3 >> 8) & 0xFFFFFull); break;
+                }
+                const int64_t off = (int64_t)((r3 >> 40) % 3) - 1;  // -1, 0, +1 byte off the multiple
+                const __int128 wide = (__int128)quo * unit + off;
+                int64_t word = wide > (__int128)INT64_MAX ? INT64_MAX : (int64_t)wide;
+                if ((r3 >> 44) % 9 == 0) word = -word;
+                const bool want = word >= 0 && word % unit == 0 && word / unit < (INT64_C(1) << 30);
+                uint32_t got_q = 0;
+                const bool got = scale_word((unsigned long long)word, unit, fast_rcp((double)unit), got_q);
+                if (got != want || (want && (int64_t)got_q != word / unit)) ++bad;
             }
         }
     }

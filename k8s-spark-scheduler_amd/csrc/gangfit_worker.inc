@@ -44,6 +44,16 @@
 // applications 16 .. 47 requested a round ahead) — no difference: the wavefronts of a CU are in different phases and hide each
 // other's record latency.
 
+// NARROW (tightly-pack instance; profiles/r7a_worker_narrow_summary.md): an application whose six requests are exact multiples of the
+// snapshot's units (scale_record below: one lane-parallel pass, one ballot) is decided on the snapshot's scaled int32 twin — the same
+// wave_decide, instantiated over NarrowApp / NarrowView: 12 bytes per slot instead of 24, 32-bit compares, capacities as three
+// multiply-highs, four ds_permute per gather instead of seven — and every other application (no scaled form, a gang of gpu executors,
+// a snapshot without the twin) on the int64 path by the same wavefront.  Same answers by construction: comparisons, subtractions
+// and floor divisions do not change under a common exact factor.  Measured against the int64-only kernel, interleaved on one
+// machine: 769.3 k -> 752.7 k instructions per ticket at K = 2 000 (vector -6.7 %, LDS -18 %, scalar +3.6 %), 922-931 M -> 937-983 M
+// decisions/s (medians +5.4 %, ranges apart); a window of twenty: unchanged.  94 VGPRs, code 31.9 -> 48.5 KB.
+// (The table itself resident in LDS was a different experiment — r6c above — and stays removed.)
+
 __device__ __forceinline__ unsigned long long sys_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -93,6 +103,68 @@ __device__ __forceinline__ App app_from_lanes(unsigned long long w, uint32_t i) 
     return r;
 }
 
+// narrow_magic's multiplier 2 * ceil(2^(30 + l) / e), l = ceil(log2 e), per LANE and without a 64-bit division (one of those is
+// ~800 cycles of a wavefront): the float64 estimate 2^(30 + l) * (1 / e) is within one of the quotient (fast_rcp: relative error
+// below 2^-40, the quotient below 2^31), an exact 64-bit multiply-subtract settles floor and remainder, the remainder the ceiling.
+// 0 for e == 0.  gf_selftest compares it with narrow_magic on the device.
+__device__ __forceinline__ uint32_t narrow_magic_lane(uint32_t e) {
+    const uint32_t d = e != 0u ? e : 1u;
+    const uint32_t l = narrow_shift((int32_t)d);
+    const uint64_t N = 1ull << (30u + l);
+    uint32_t m = (uint32_t)((double)N * fast_rcp((double)d));
+    int64_t rem = (int64_t)(N - (uint64_t)m * (uint64_t)d);
+    if (rem < 0) {
+        m -= 1u;
+        rem += (int64_t)d;
+    } else if (rem >= (int64_t)d) {
+        m += 1u;
+        rem -= (int64_t)d;
+    }
+    m += rem > 0 ? 1u : 0u;
+    return e != 0u ? 2u * m : 0u;
+}
+
+// One request word per lane, divided by its dimension's unit (unit >= 1, rcp = fast_rcp(unit)): true when the word is a
+// non-negative exact multiple of the unit and the quotient q is below 2^30.  The estimate w * rcp is within 2^-10 of an exact
+// quotient of that size, so rounding it to the nearest integer gives q, and q * unit == w (exact: the true product is below
+// 2^64) is the whole proof — for a word that is no multiple nothing passes it.
+__device__ __forceinline__ bool scale_word(unsigned long long w, int64_t unit, double rcp, uint32_t& q) {
+    const double qf = (double)(int64_t)w * rcp;
+    const bool in = (int64_t)w >= 0 && qf < 1073741823.5;
+    q = in ? (uint32_t)__builtin_rint(qf) : 0u;
+    return in && (unsigned long long)q * (unsigned long long)unit == w;
+}
+
+// The scaled record of the application in lanes 0 .. 7 of w (lanes 0 .. 5 = drv0..2, exe0..2), built lane-parallel: ONE pass
+// divides the six requests (lane l by unit_l = the unit of dimension l mod 3) and computes the executor request's multipliers
+// in lanes 3 .. 5, one ballot says whether the application has a scaled form, nine v_readlane hand the fields out.  False: the
+// caller decides this application on the int64 path (r is then not to be used).
+__device__ __forceinline__ bool scale_record(unsigned long long w, int lane, int64_t unit_l, double rcp_l, NarrowApp& r) {
+    uint32_t q;
+    const bool ok = scale_word(w, unit_l, rcp_l, q) || lane >= 6;
+    const uint32_t mag = narrow_magic_lane(q);
+    const uint64_t kf = (uint64_t)read_lane((int64_t)w, 6);
+    r.k = (int32_t)(uint32_t)kf;
+    r.flags = (uint32_t)(kf >> 32);
+    r.exec_off = (uint64_t)read_lane((int64_t)w, 7);
+    r.drv0 = (int32_t)read_lane(q, 0);
+    r.drv1 = (int32_t)read_lane(q, 1);
+    r.drv2 = (int32_t)read_lane(q, 2);
+    r.exe0 = (int32_t)read_lane(q, 3);
+    r.exe1 = (int32_t)read_lane(q, 4);
+    r.exe2 = (int32_t)read_lane(q, 5);
+    r.mag0 = read_lane(mag, 3);
+    r.mag1 = read_lane(mag, 4);
+    r.mag2 = read_lane(mag, 5);
+    r.sh0 = narrow_shift(r.exe0);
+    r.sh1 = narrow_shift(r.exe1);
+    r.sh2 = narrow_shift(r.exe2);
+    r.un0 = r.exe0 == 0 ? 0xFFFFFFFFu : 0u;
+    r.un1 = r.exe1 == 0 ? 0xFFFFFFFFu : 0u;
+    r.un2 = r.exe2 == 0 ? 0xFFFFFFFFu : 0u;
+    return __ballot(ok) == ~0ull && (uint32_t)r.k <= (uint32_t)GF_MAX_K;
+}
+
 // Block 0: the leader (one wavefront).  Blocks 1 ..: set (b - 1) / blocks_per_set, kWorkerWaves wavefronts = applications each.
 // Sixteen wavefronts per workgroup: (a) a ticket costs one counter update per workgroup, and those updates — read-modify-writes
 // of one word at device scope — queue behind each other (with four-wavefront workgroups, 250 per ticket, they were the floor:
@@ -110,6 +182,12 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     __shared__ unsigned long long s_next[8];    // (round << 32) | applications of that round handed out so far (kDynamic)
     // group 0 of the chunk index: lane l = chunk l (maxima x 3, dcand, xcand)
     __shared__ unsigned long long s_g0[5][kWave];
+    // NARROW (tightly-pack): a wavefront decides an application in the snapshot's scaled int32 domain (NarrowView, NarrowApp:
+    // 12 bytes per slot, 32-bit compares, capacities by multiplication, a four-dword gather) when the snapshot has that form
+    // and the application's requests do (scale_record) — wave-uniform per application; otherwise on the int64 path, as the
+    // other instances always do.  Gangs of gpu executors keep the int64 path: the compact SparseTable has wide columns only.
+    constexpr bool kNarrow = ALGO == GF_ALGO_TIGHTLY_PACK;
+    __shared__ int32_t s_g0n[kNarrow ? 3 : 1][kWave];  // the three maxima of s_g0 in units (upper bounds: rounded up)
     const int lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (blockIdx.x == 0) {
@@ -188,6 +266,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     if (threadIdx.x < kCountSlots) s_cnt[threadIdx.x] = 0;
     if (threadIdx.x < 8) s_next[threadIdx.x] = 0ull;
     if (threadIdx.x < (uint32_t)kWorkerWaves) s_round[threadIdx.x] = 0;
+    const bool narrow_table = kNarrow && T.ncpu != nullptr;
     if (wave == 0) {  // the tables do not change while the worker lives
         const Group0 g = load_group0(V, O, lane);
         s_g0[0][lane] = (unsigned long long)g.m0;
@@ -195,7 +274,19 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         s_g0[2][lane] = (unsigned long long)g.m2;
         s_g0[3][lane] = g.dcand;
         s_g0[4][lane] = g.xcand;
+        if constexpr (kNarrow) {
+            if (narrow_table) {
+                s_g0n[0][lane] = NarrowView::scale_max(g.m0, T.nunit[0]);
+                s_g0n[1][lane] = NarrowView::scale_max(g.m1, T.nunit[1]);
+                s_g0n[2][lane] = NarrowView::scale_max(g.m2, T.nunit[2]);
+            }
+        }
     }
+    const NarrowView VN{T.ncpu, T.nmem, T.ngpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, T.xmask, T.dmask,
+                        T.n_chunks, T.nunit[0], T.nunit[1], T.nunit[2]};
+    // lane l < 6 scales request word l of a record: dimension l mod 3
+    const int64_t unit_l = T.nunit[lane % 3 == 0 ? 0 : (lane % 3 == 1 ? 1 : 2)];
+    const double rcp_l = kNarrow ? fast_rcp((double)unit_l) : 0.0;
     __syncthreads();  // the only barrier of the kernel: the LDS words above
     typedef __attribute__((address_space(1))) const gf_app glb_app;
     typedef __attribute__((address_space(1))) gf_result glb_result;
@@ -251,7 +342,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     auto round_guard = [&](uint32_t r) {
         if (r < kCountSlots) return;
         for (;;) {
-            const uint32_t x = lane < kWorkerWaves ? s_round[lane] : kRoundGone;
+            const uint32_t x = lane < kWorkerWaves ? __hip_atomic_load(&s_round[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : kRoundGone;
             if (__ballot(x != kRoundGone && x + kCountSlots <= r) == 0ull) break;
             __builtin_amdgcn_s_sleep(4);
         }
@@ -345,44 +436,69 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                     continue;
                 }
             }
-            App app{};
-            Group0 g0{};
-            g0.m0 = (int64_t)s_g0[0][lane];
-            g0.m1 = (int64_t)s_g0[1][lane];
-            g0.m2 = (int64_t)s_g0[2][lane];
-            g0.dcand = s_g0[3][lane];
-            g0.xcand = s_g0[4][lane];
-            if constexpr (kDynamic) {
-                app = app_from_lanes(wrec, 0);
-            } else if constexpr (kRecords) {
-                if (it == 8u) {  // more than eight applications per wavefront and ticket: the next eight records
-                    wrec = load_records(apps, n_apps, a);
-                    it = 0;
-                }
-                app = app_from_lanes(wrec, it);
-                ++it;
-            } else {
-                app = load_app_uncached(apps, a, lane);  // (waits for its load: everything issued before it has returned)
-            }
             unsigned long long xvis = 0, dvis = 0;
-            Decision dec = wave_decide<ALGO, GlobalView, false>(V, O, app, (direct ? exec_nodes : priv) + app.exec_off,
-                                                                scratch + app.exec_off, scratch + half + app.exec_off, lane, xvis,
-                                                                dvis, merged ? &g0 : nullptr, &G, direct);
+            Decision dec;
+            int32_t app_k = 0;
+            uint64_t app_off = 0;
+            bool decided = false;
+            if constexpr (kNarrow) {
+                NarrowApp napp;
+                // (gangs of gpu executors are packed from the compact table of gpu nodes: wave_decide's `sparse`, int64 only)
+                if (narrow_table && scale_record(wrec, lane, unit_l, rcp_l, napp) &&
+                    !(G.n_x != 0u && napp.exe2 > 0 && napp.k > 0 && T.d_identity != 0)) {
+                    Group0T<int32_t> g0n{};
+                    g0n.m0 = s_g0n[0][lane];
+                    g0n.m1 = s_g0n[1][lane];
+                    g0n.m2 = s_g0n[2][lane];
+                    g0n.dcand = s_g0[3][lane];
+                    g0n.xcand = s_g0[4][lane];
+                    app_k = napp.k;
+                    app_off = napp.exec_off;
+                    dec = wave_decide<ALGO, NarrowView, false>(VN, O, napp, (direct ? exec_nodes : priv) + app_off, scratch + app_off,
+                                                               scratch + half + app_off, lane, xvis, dvis, &g0n, nullptr, direct);
+                    decided = true;
+                }
+            }
+            if (__builtin_expect(!decided, !kNarrow)) {
+                App app{};
+                Group0 g0{};
+                g0.m0 = (int64_t)s_g0[0][lane];
+                g0.m1 = (int64_t)s_g0[1][lane];
+                g0.m2 = (int64_t)s_g0[2][lane];
+                g0.dcand = s_g0[3][lane];
+                g0.xcand = s_g0[4][lane];
+                if constexpr (kDynamic) {
+                    app = app_from_lanes(wrec, 0);
+                } else if constexpr (kRecords) {
+                    if (it == 8u) {  // more than eight applications per wavefront and ticket: the next eight records
+                        wrec = load_records(apps, n_apps, a);
+                        it = 0;
+                    }
+                    app = app_from_lanes(wrec, it);
+                    ++it;
+                } else {
+                    app = load_app_uncached(apps, a, lane);  // (waits for its load: everything issued before it has returned)
+                }
+                app_k = app.k;
+                app_off = app.exec_off;
+                dec = wave_decide<ALGO, GlobalView, false>(V, O, app, (direct ? exec_nodes : priv) + app_off, scratch + app_off,
+                                                           scratch + half + app_off, lane, xvis, dvis, merged ? &g0 : nullptr, &G, direct);
+            }
             if (W.stats != nullptr && lane == 0) {
                 atomicAdd(&W.stats->exec_slots_visited, xvis);
                 atomicAdd(&W.stats->driver_slots_visited, dvis);
             }
             if (dec.feasible && !direct) {
                 // this wavefront's own stores, read back through its CU's L1 / L2 and sent out write-through
-                for (int32_t i = lane; i < app.k; i += kWave)
-                    __hip_atomic_store(exec_nodes + app.exec_off + i, priv[app.exec_off + i], __ATOMIC_RELAXED,
+                for (int32_t i = lane; i < app_k; i += kWave)
+                    __hip_atomic_store(exec_nodes + app_off + i, priv[app_off + i], __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_SYSTEM);
             }
             if (lane < 2) {  // the 16-byte result as two write-through words
                 if (dec.feasible && dec.ds_node == GF_NO_NODE) dec.ds_node = T.slot_node[dec.ds];
                 const unsigned long long lo = (unsigned long long)(uint32_t)(dec.feasible ? 1 : 0) |
                                               ((unsigned long long)(dec.feasible ? dec.ds_node : GF_NO_NODE) << 32);
-                const unsigned long long hi = (unsigned long long)(dec.feasible ? (uint32_t)app.k : 0u) | (1ull << 32);
+                const unsigned long long hi = (unsigned long long)(dec.feasible ? (uint32_t)app_k : 0u) | (1ull << 32);
                 __hip_atomic_store(reinterpret_cast<unsigned long long*>(results + a) + lane, lane == 0 ? lo : hi, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_SYSTEM);
             }
@@ -446,7 +562,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             }
         }
         ++round;
-        if (lane == 0) s_round[wave] = round;  // (rounds this wavefront has left behind: the guard above)
+        if (lane == 0) __hip_atomic_store(&s_round[wave], round, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // (rounds left behind: round_guard)
         t = t_next;
         w_cur = w_next;
         have_cur = have_next;
@@ -455,5 +571,5 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         i_cur = i_next;
         grabbed_cur = kDynamic && have_next;
     }
-    if (lane == 0) s_round[wave] = kRoundGone;  // never in anybody's way
+    if (lane == 0) __hip_atomic_store(&s_round[wave], kRoundGone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // never in anybody's way
 }

@@ -544,8 +544,16 @@ int gf_launch_floor(gf_ctx *ctx, void *stream, uint32_t iters, float *us_per_lau
  *     launched again by the next submit; gf_worker_stop makes it leave at once (a host that wants to hipDeviceSynchronize);
  *   - it reads the installed snapshot: every install (gf_snapshot_* / gf_orders_set / gf_cluster_set ...) first serves what
  *     was posted and makes it leave;
- *   - plain packers only (tightly-pack, distribute-evenly, minimal-fragmentation); plain contexts only (no views, one
- *     device); results are bit-identical to gf_fit_batch(GF_MODE_INDEPENDENT) — same wave-level code.
+ *   - it serves tightly-pack, distribute-evenly, minimal-fragmentation and the zone-aware tightly-pack packers
+ *     (single-az-tightly-pack, az-aware-tightly-pack: one wavefront walks an application's candidate views one after the
+ *     other); plain contexts only (no views, one device); results are bit-identical to gf_fit_batch(GF_MODE_INDEPENDENT) —
+ *     same wave-level code.  Refusals, in this order and before anything touches the device: a view or a multi-device
+ *     context (GF_ERR_UNSUPPORTED); a zone-aware packer without the schedulable columns (GF_ERR_STATE); a zone-aware packer
+ *     on a context whose snapshot has no zone assignment (gf_zones_set was not called, or no zone is evaluated), with more
+ *     than 64 candidate views (zones of the evaluation list, + 1 for az-aware), or single-az-minimal-fragmentation
+ *     (GF_ERR_UNSUPPORTED each; gf_fit_batch serves them all);
+ *   - for the zone-aware packers nothing is written before the choice among the views: d_exec_nodes of a record that ends
+ *     with has_capacity == 0 is left untouched;
  *   options: "worker_sets" (groups of wavefronts = batches in flight on the device, at most 16), "worker_blocks_per_set"
  *   (workgroups of sixteen wavefronts per group; each fills a CU), "worker_idle_us".  Both default to 0 = chosen at every
  *   launch of the worker from the first ticket it will serve: three applications per wavefront, one after the other, and as

@@ -609,7 +609,7 @@ func (c *Context) fitLocked(fifo bool, algo int, apps []App, capps []C.gf_app, t
 	return c.fitLockedVia(false, fifo, algo, apps, capps, total, names)
 }
 
-// fitLockedVia: viaWorker sends an INDEPENDENT batch of a plain packer through the resident worker (gf_worker_fit: no kernel
+// fitLockedVia: viaWorker sends an INDEPENDENT batch of a packer the worker serves (FitIndependentOnWorker) through the resident worker (gf_worker_fit: no kernel
 // launch, records and answers in pinned memory) instead of gf_fit_batch — same answers.
 func (c *Context) fitLockedVia(viaWorker, fifo bool, algo int, apps []App, capps []C.gf_app, total int, names []string) ([]Result, int, error) {
 	cres := make([]C.gf_result, len(apps))
@@ -673,7 +673,9 @@ func (c *Context) FitBatchOnInstalledSnapshot(fifo bool, algo int, apps []App) (
 // instance groups' pods (unschedulablepods.go:93-166), a capacity what-if sweep.  Calls on one context serialise on c.mu;
 // the worker stays on the device for gf_set_option("worker_idle_us") after a batch and is launched again by the next one
 // that finds it gone, so back-to-back batches pay no kernel launch.  (Its throughput shows with several tickets in flight:
-// gf_worker_submit_dev, device-resident batches.)  Plain packers only (algo 0, 1, 2); any install (ClusterSet, SnapshotBuildResident, FitBatch) first serves what was
+// gf_worker_submit_dev, device-resident batches.)  Served: the plain packers (algo 0, 1, 2) and the zone-aware tightly-pack packers
+// (az-aware-tightly-pack 3, single-az-tightly-pack 4) on a cluster installed with zones, at most 64 candidate views;
+// single-az-minimal-fragmentation (5) is refused (GF_ERR_UNSUPPORTED), as in include/gangfit.h.  Any install (ClusterSet, SnapshotBuildResident, FitBatch) first serves what was
 // posted and makes the worker leave.  Unverified here (no Go toolchain); tests/test_gpu_worker.py drives the C entry points.
 func (c *Context) FitIndependentOnWorker(algo int, apps []App) ([]Result, error) {
 	capps, total, err := flattenApps(apps)

@@ -380,6 +380,28 @@ int route_of(gf_ctx* ctx, gf_mode mode, gf_algo algo, Route* r) {
     return GF_OK;
 }
 
+// What the resident worker serves (gf_worker_fit, gf_worker_submit_dev): route_of's rules for an independent batch, then the
+// worker's own.  Refusals in order, all before anything touches the device: a view or a multi-device parent
+// (GF_ERR_UNSUPPORTED); route_of's — no orders, a zone-aware packer without the schedulable columns (GF_ERR_STATE), a packer
+// without a device path (GF_ERR_UNSUPPORTED) —; a zone-aware packer on a context without a zone assignment (gf_zones_set was not
+// called since the snapshot, or the evaluation list is empty), with more than 64 candidate views — the one-launch kernel's
+// bound —, or single-az-minimal-fragmentation, whose view code has no worker instance (GF_ERR_UNSUPPORTED each).
+int worker_route_of(gf_ctx* ctx, gf_algo algo) {
+    if (!ctx->group.empty() || ctx->view_of != nullptr)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker serves plain contexts (no views, one device)");
+    Route r;
+    if (const int rc = route_of(ctx, GF_MODE_INDEPENDENT, algo, &r); rc != GF_OK) return rc;
+    if (!r.zoned) return GF_OK;
+    if (ctx->zone.empty() || ctx->n_zones == 0)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker serves a zone-aware packer on installed zones (gf_zones_set)");
+    if (r.n_cand > 64)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker serves at most 64 candidate views (%u zones%s)", ctx->n_zones,
+                    r.az_aware ? " + the plain order" : "");
+    if (r.inner != GF_ALGO_TIGHTLY_PACK)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker does not serve single-az-minimal-fragmentation");
+    return GF_OK;
+}
+
 gangfit::ZoneTable zone_table(const gf_ctx* ctx) {
     return gangfit::ZoneTable{ctx->d_zmasks.ptr, ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride, ctx->n_zones, ctx->zstride};
 }

@@ -137,6 +137,8 @@ int worker_launch(gf_ctx* ctx, gf_algo algo, uint64_t first_ticket) {
         // ticket in a long stream, 61 against 74 us for a window of twenty (profiles/r5j_worker_sets.txt; two per wavefront
         // 1.56 us, four 1.41 us but 68 us for the window of twenty).  Sized by the first ticket this launch will serve.
         // (gf_worker_fit — one blocking ticket at a time — asks for one application per wavefront: nothing else is in flight.)
+        // (The zone-aware instances keep the three — an application costs about n_cand decisions plus the averages there —: 7.33 / 5.95 /
+        //  5.70 us per single-az ticket for 1 / 2 / 3 per wavefront at K = 2 000, 9.85 / 8.52 / 8.23 at K = 20; profiles/worker_zoned.txt.)
         if (bps == 0) {
             uint32_t n_first = w.hint_apps;
             if (first_ticket < w.posted)
@@ -160,6 +162,10 @@ int worker_launch(gf_ctx* ctx, gf_algo algo, uint64_t first_ticket) {
     w.cur_sets = sets;
     w.cur_blocks_per_set = bps;
     a.stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr;
+    if (is_zone_algo(algo)) {  // (worker_route_of admitted it: zones installed, at most 64 views, the schedulable columns)
+        a.zones = zone_table(ctx);
+        a.sched = ctx->d_sched.ptr;
+    }
     // the tickets already posted for this launch (at most one per set) ride in its arguments
     a.n_inline = 0;
     for (uint64_t t = first_ticket; t < w.posted && a.n_inline < gangfit::kWorkerInline && a.n_inline < sets; ++t, ++a.n_inline)
@@ -239,10 +245,7 @@ int worker_drain(gf_ctx* ctx) {
 // tickets first, so that the leader finds them at its first look (gf_worker_submit_dev).
 int worker_prepare(gf_ctx* ctx, gf_algo algo, uint64_t max_total_k, bool* need_launch = nullptr) {
     gf_ctx::Worker& w = ctx->worker;
-    if (!ctx->group.empty() || ctx->view_of != nullptr)
-        return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker serves plain contexts (no views, one device)");
-    if (!is_plain_algo(algo)) return fail(ctx, GF_ERR_UNSUPPORTED, "the resident worker serves the plain packers");
-    if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a fit");
+    if (const int rc = worker_route_of(ctx, algo); rc != GF_OK) return rc;
     if (const int rc = worker_alloc(ctx); rc != GF_OK) return rc;
     if (const int rc = worker_revive(ctx); rc != GF_OK) return rc;
     const bool grow = max_total_k + 1 > w.scratch_stride;

@@ -562,6 +562,8 @@ bool reserves_executors(gf_algo algo);
 bool is_zone_algo(gf_algo algo);
 bool is_plain_algo(gf_algo algo);  // tightly-pack, distribute-evenly, minimal-fragmentation
 uint32_t candidate_views(const gf_ctx* ctx, gf_algo algo);
+int worker_route_of(gf_ctx* ctx, gf_algo algo);  // what the resident worker serves and refuses (next to route_of)
+gangfit::ZoneTable zone_table(const gf_ctx* ctx);
 int check_apps(gf_ctx* ctx, uint32_t n_apps, const gf_app* apps, gf_app* out, uint64_t* total_k);
 int ensure_cnt(gf_ctx* ctx, uint64_t n_decisions, hipStream_t stream);
 // gangfit_api_snapshot.cpp

@@ -189,8 +189,14 @@ struct WorkerArgs {
     uint32_t n_inline;
     uint32_t pad_inline;
     unsigned long long inline_words[kWorkerInline][6];
+    // The zone-aware tightly-pack instances only (single-az-tightly-pack, az-aware-tightly-pack; behind everything the plain
+    // instances read, whose argument offsets stay where they were): the zone rows of the evaluation list — at most 64 candidate
+    // views, the plain order of az-aware included — and SchedulableResources in slot order (3 * n_slots), for the averages.
+    ZoneTable zones;
+    const int64_t* sched;
 };
 
+// tightly-pack, distribute-evenly, minimal-fragmentation, single-az-tightly-pack, az-aware-tightly-pack
 hipError_t worker_blocks_per_cu(gf_algo algo, int* out);
 // One launch: 1 + sets * blocks_per_set workgroups of sixteen wavefronts.
 hipError_t launch_fit_worker(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const WorkerArgs& args,

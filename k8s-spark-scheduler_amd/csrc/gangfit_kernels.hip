@@ -1927,8 +1927,15 @@ inline dim3 app_grid(uint32_t n_apps) { return dim3((n_apps + kWavesPerBlock - 1
 
 }  // namespace
 
+// the packers the resident worker has an instance for
+template <class F>
+hipError_t with_worker_algo(gf_algo algo, F&& f) {
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY, GF_ALGO_MINIMAL_FRAGMENTATION, GF_ALGO_SINGLE_AZ_TIGHTLY_PACK,
+                      GF_ALGO_AZ_AWARE_TIGHTLY_PACK>(algo, f);
+}
+
 hipError_t worker_blocks_per_cu(gf_algo algo, int* out) {
-    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY, GF_ALGO_MINIMAL_FRAGMENTATION>(algo, [&](auto A) {
+    return with_worker_algo(algo, [&](auto A) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fit_worker_kernel<A>, kWave * kWorkerWaves, 0);
     });
 }
@@ -1938,7 +1945,12 @@ hipError_t launch_fit_worker(gf_algo algo, const NodeTable& table, const SparseT
     if (args.sets == 0 || args.blocks_per_set == 0 || args.host == nullptr || args.dev == nullptr) return hipErrorInvalidValue;
     const dim3 block(kWave * kWorkerWaves);
     const dim3 grid(1u + args.sets * args.blocks_per_set);
-    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY, GF_ALGO_MINIMAL_FRAGMENTATION>(algo, [&](auto A) {
+    if (algo == GF_ALGO_SINGLE_AZ_TIGHTLY_PACK || algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK) {  // what wave_decide_zones indexes
+        const uint32_t n_cand = args.zones.n_zones + (algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u);
+        if (args.sched == nullptr || args.zones.xmask == nullptr || args.zones.dmask == nullptr || args.zones.n_zones == 0 || n_cand > 64u)
+            return hipErrorInvalidValue;
+    }
+    return with_worker_algo(algo, [&](auto A) {
         hipLaunchKernelGGL(fit_worker_kernel<A>, grid, block, 0, stream, table, gpu_view, args);
         return hipGetLastError();
     });

@@ -175,8 +175,21 @@ __device__ __forceinline__ bool scale_record(unsigned long long w, int lane, int
 // it does not, and a gf_fit_batch launched next to a resident worker then WAITED FOR THE WORKER TO IDLE OUT (500 ms with
 // worker_idle_us = 500 000) although 27 CUs were free: measured twice in round 5 when a change added two registers
 // (tools/micro/probe_worker_resident.py; tests/test_gpu_worker.py::test_a_fifo_chain_starts_next_to_a_resident_worker fails on it).
+// ZONE-AWARE (single-az-tightly-pack, az-aware-tightly-pack): the ticket protocol is the one above; what a wavefront does with one
+// application is wave_decide_zones (gangfit_zones.inc) — its candidate views one after the other, no barrier — on the int64 table
+// only.  Placements of candidate views are slot ids and the winner is known behind the last view, so nothing is emitted directly:
+// the slot's `priv` and first survivor slice (tightly-pack uses neither survivor list) are the "current" and the "best so far"
+// placements, and the copy-out translates slot -> node.  An infeasible record's placements are not touched at all.
+template <bool AZ_AWARE>
+__device__ __forceinline__ Decision wave_decide_zones(const NodeTable& T, const SparseTable& G, const ZoneTable& Z,
+                                                      const int64_t* __restrict__ sched, const GlobalView& plain, const App& app,
+                                                      uint32_t* cur, uint32_t* kept, int lane, unsigned long long& xvis,
+                                                      unsigned long long& dvis, const uint32_t*& placed);
+
 template <int ALGO>
 __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(NodeTable T, SparseTable G, WorkerArgs W) {
+    constexpr bool kZoned = ALGO == GF_ALGO_SINGLE_AZ_TIGHTLY_PACK || ALGO == GF_ALGO_AZ_AWARE_TIGHTLY_PACK;
+    constexpr int kInner = kZoned ? (int)GF_ALGO_TIGHTLY_PACK : ALGO;  // the packer of one candidate view
     __shared__ uint32_t s_cnt[8];               // applications the workgroup has finished, per round (recycled every eight rounds)
     __shared__ uint32_t s_round[kWorkerWaves];  // rounds each wavefront has finished
     __shared__ unsigned long long s_next[8];    // (round << 32) | applications of that round handed out so far (kDynamic)
@@ -260,7 +273,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     GlobalView V{T.cpu, T.mem, T.gpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, T.xmask, T.dmask,
                  T.n_chunks};
     Orders O{T.slot_node, T.dslot, T.n_x, T.n_d, T.d_identity != 0};
-    const bool merged = T.d_identity != 0 && ALGO != GF_ALGO_MINIMAL_FRAGMENTATION;
+    const bool merged = T.d_identity != 0 && kInner != GF_ALGO_MINIMAL_FRAGMENTATION;
     constexpr uint32_t kCountSlots = 8;
     constexpr uint32_t kRoundGone = 0xFFFFFFFFu;  // s_round of a wavefront that has left
     if (threadIdx.x < kCountSlots) s_cnt[threadIdx.x] = 0;
@@ -441,6 +454,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             int32_t app_k = 0;
             uint64_t app_off = 0;
             bool decided = false;
+            const uint32_t* placed = nullptr;  // kZoned: the winner's placement, slot ids
             if constexpr (kNarrow) {
                 NarrowApp napp;
                 // (gangs of gpu executors are packed from the compact table of gpu nodes: wave_decide's `sparse`, int64 only)
@@ -481,8 +495,14 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                 }
                 app_k = app.k;
                 app_off = app.exec_off;
-                dec = wave_decide<ALGO, GlobalView, false>(V, O, app, (direct ? exec_nodes : priv) + app_off, scratch + app_off,
-                                                           scratch + half + app_off, lane, xvis, dvis, merged ? &g0 : nullptr, &G, direct);
+                if constexpr (kZoned) {
+                    dec = wave_decide_zones<ALGO == GF_ALGO_AZ_AWARE_TIGHTLY_PACK>(T, G, W.zones, W.sched, V, app, priv + app_off,
+                                                                                   scratch + app_off, lane, xvis, dvis, placed);
+                } else {
+                    dec = wave_decide<kInner, GlobalView, false>(V, O, app, (direct ? exec_nodes : priv) + app_off, scratch + app_off,
+                                                                 scratch + half + app_off, lane, xvis, dvis, merged ? &g0 : nullptr, &G,
+                                                                 direct);
+                }
             }
             if (W.stats != nullptr && lane == 0) {
                 atomicAdd(&W.stats->exec_slots_visited, xvis);
@@ -490,9 +510,14 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             }
             if (dec.feasible && !direct) {
                 // this wavefront's own stores, read back through its CU's L1 / L2 and sent out write-through
-                for (int32_t i = lane; i < app_k; i += kWave)
-                    __hip_atomic_store(exec_nodes + app_off + i, priv[app_off + i], __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_SYSTEM);
+                if constexpr (kZoned) {  // (this wavefront's own stores again, as below; slot ids -> node indices; K == 0 writes nothing)
+                    for (int32_t i = lane; i < app_k; i += kWave)
+                        __hip_atomic_store(exec_nodes + app_off + i, T.slot_node[placed[i]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                } else {
+                    for (int32_t i = lane; i < app_k; i += kWave)
+                        __hip_atomic_store(exec_nodes + app_off + i, priv[app_off + i], __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_SYSTEM);
+                }
             }
             if (lane < 2) {  // the 16-byte result as two write-through words
                 if (dec.feasible && dec.ds_node == GF_NO_NODE) dec.ds_node = T.slot_node[dec.ds];

@@ -430,6 +430,79 @@ __device__ __forceinline__ bool wave_avg_max_tight_runs(const EffView& E, const 
     return true;
 }
 
+// A pointer that is the same for every lane, said so to the compiler (two v_readfirstlane): its address then lives in scalar registers.
+__device__ __forceinline__ uint32_t* uniform_ptr(uint32_t* p) {
+    const uint64_t u = (uint64_t)reinterpret_cast<uintptr_t>(p);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)u);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)(uint32_t)(u >> 32));
+    return reinterpret_cast<uint32_t*>((uintptr_t)(((uint64_t)hi << 32) | lo));
+}
+
+// The zone-aware tightly-pack packers by ONE wavefront (the resident worker, gangfit_worker.inc): what fit_zoned_fused_kernel's
+// wavefronts decide side by side and choose through LDS behind a barrier, one wavefront walks view after view — every zone of
+// the evaluation list in order, then (az-aware, and only when no zone won: az_aware_pack_tightly.go:33-37) the plain order —
+// with chooseBestResult's strict '<' from 0.0 applied as it goes (single_az.go:75-97).  Same wave_decide, same candidate
+// words, same compact gpu rows and the entry-wise average function of the one-launch kernel: same float64 bits, same answer.
+// Placements are SLOT ids and the winner is known only behind the last view: the view being decided writes slice `cur`, the
+// best so far stays in `kept`, and the two swap roles on a win — two slices however many zones.  Both are private to the
+// wavefront's application (K words each); `placed` names the winner's on return.
+template <bool AZ_AWARE>
+__device__ __forceinline__ Decision wave_decide_zones(const NodeTable& T, const SparseTable& G, const ZoneTable& Z,
+                                                      const int64_t* __restrict__ sched, const GlobalView& plain, const App& app,
+                                                      uint32_t* cur, uint32_t* kept, int lane, unsigned long long& xvis,
+                                                      unsigned long long& dvis, const uint32_t*& placed) {
+    const EffView EV{T.cpu, T.mem, T.gpu, sched, sched + T.n_slots, sched + 2 * (size_t)T.n_slots};
+    const int64_t K = app.k;
+    // (the two slices are the same for every lane: said so, or their addresses occupy vector registers through every view)
+    cur = uniform_ptr(cur);
+    kept = uniform_ptr(kept);
+    Decision best;
+    best.feasible = false;
+    best.ds = 0;
+    best.pass1 = 0;
+    double best_max = 0.0;
+    const uint32_t n_zone_cand = Z.n_zones;
+    const uint32_t n_cand = n_zone_cand + (AZ_AWARE ? 1u : 0u);  // the host guarantees n_cand <= 64
+    for (uint32_t c = 0; c < n_cand; ++c) {
+        const bool zone_view = c < n_zone_cand;
+        if (AZ_AWARE && !zone_view && best.feasible) break;  // a zone won: the plain order is not asked
+        GlobalView V = plain;
+        if (zone_view) {
+            V.xm = Z.xmask + (size_t)c * Z.stride;
+            V.dm = Z.dmask + (size_t)c * Z.stride;
+        }
+        const Orders O{T.slot_node, T.dslot, T.n_x, T.n_d, T.d_identity != 0, zone_view};
+        // gangs of gpu executors: the zone's row of the compact gpu table, exactly as fit_zoned_fused_kernel builds it
+        const SparseTable GV{G.cpu, G.mem, G.gpu, G.slot_of_sub, G.cmax, zone_view ? G.zmask + (size_t)c * G.n_chunks : G.xmask,
+                             G.sub_of_slot, G.n_x, G.n_chunks, G.zmask, G.slot_of_sub};
+        // (tightly-pack uses neither survivor list)
+        const Decision dec =
+            wave_decide<GF_ALGO_TIGHTLY_PACK, GlobalView, true>(V, O, app, cur, nullptr, nullptr, lane, xvis, dvis, nullptr, &GV);
+        if (!dec.feasible) continue;  // single_az.go:44-46
+        bool wins = !zone_view;
+        if (zone_view) {
+            // cur[] was written by other lanes of this wave
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            // the entry-wise form for every K (the same float64 bits as wave_avg_max_tight_runs, DESIGN section 4.3): the run form's
+            // eight blocks of entries in registers take this kernel past its register budget (127 VGPRs and scratch against 101)
+            double avg[4] = {0.0, 0.0, 0.0, 0.0};
+            wave_avg_efficiency_runs<GF_ALGO_TIGHTLY_PACK>(EV, app, dec.ds, cur, lane, avg);
+            wins = best_max < avg[3];  // AvgPackingEfficiency.LessThan, efficiency.go:37-39
+            if (wins) best_max = avg[3];
+        }
+        if (wins) {
+            best.feasible = true;
+            best.ds = dec.ds;
+            uint32_t* const t = cur;
+            cur = kept;
+            kept = t;
+        }
+    }
+    placed = kept;
+    return best;
+}
+
 // FEAS (gf_fit_feasible): `results` is an array of n_apps bytes that receives HasCapacity through the grid's last workgroup,
 // `exec_nodes` the collection words (feasible_announce / feasible_collect in gangfit_kernels.hip); the winner's placement is
 // not expanded and no result record is written.

@@ -1,7 +1,7 @@
 // gangfit_api_fit.cpp — the decision side of the C ABI: table views; route_of, the one place that decides which kernels serve a
-// (mode, packer) on a context, and launch, which runs them (independent batches, FIFO chains on the LDS kernels
-// and their fallbacks); the incremental chain cache, gf_fit_batch / gf_fit_batch_dev / gf_fit_feasible / gf_spark_binpack,
-// single executors, findNodes and the packing efficiencies.
+// (mode, packer) on a context, and launch, which runs them (one function per route family: independent batches,
+// the plain chain, the LDS chains with their generic twin, the generic chain); the incremental chain cache, gf_fit_batch /
+// gf_fit_batch_dev / gf_fit_feasible / gf_spark_binpack, single executors, findNodes and the packing efficiencies.
 #include "gangfit_ctx.h"
 
 using namespace gfapi;
@@ -169,21 +169,46 @@ void narrow_units(const gf_ctx* ctx, const gf_app* h_apps, uint32_t n_apps, int6
     }
 }
 
+// How one FIFO chain of gf_fit_batch uses the chain cache (decided by chain_plan before the launch).
+struct ChainRun {
+    uint32_t a_begin = 0;        // first application this launch evaluates (a multiple of 1 << shift); 0 = from the snapshot
+    bool record = false;         // dump checkpoints into ctx->chain.d_ckpt
+    bool narrow_proven = false;  // every request has a scaled form (checked on the host): the wide twin is not launched
+    uint32_t common = 0;         // leading applications identical to the cached queue's (>= a_begin): the cache keeps them
+    bool from_tip = false;       // the launch starts from the cached chain's tip (a_begin = its tip_at, any value) instead of a checkpoint
+    bool write_tip = false;      // the launch leaves its own tip in ctx->chain.d_tip
+    int64_t eff[3] = {0, 0, 0};  // the narrow units of the queue and their factors (narrow_units): narrow_begin does not scan it again
+    int32_t factor[3] = {1, 1, 1};
+};
+
+// One call's batch, as launch() and its helpers see it: the WHOLE queue on the device — q.n_apps, d_apps, d_results,
+// d_exec_nodes, half (= placements + 1), d_chain_failed_at and stream; the rest of q is the launch's own — and what the caller
+// knows beyond it.  gf_fit_batch_dev knows nothing: no records on the host, no plan, no offer.
+struct FitCall {
+    gangfit::ChainBatch q;
+    const gf_app* h_apps = nullptr;  // the same records on the host (with exec_off)
+    const ChainRun* run = nullptr;   // gf_fit_batch's plan for a FIFO chain that uses the chain cache
+    struct HostIo {  // gf_fit_batch's offer to a FIFO chain: the device addresses of the pinned h_apps / h_results / h_exec /
+                     // h_failed, where its first kernel may read the records and its last one write the answers (apps == nullptr: none)
+        const gf_app* apps = nullptr;
+        gf_result* results = nullptr;
+        uint32_t* exec = nullptr;
+        int32_t* failed = nullptr;
+        bool apps_done = false;  // a kernel of this call writes (or a copy wrote) the records to d_apps
+        bool out_done = false;   // the last kernel of this call writes the answers to the host buffers
+    } host;
+};
+
 // restore (nullable): a checkpoint of an earlier chain in the SAME units — the working copy starts from it instead of the
 // snapshot (incremental chains).
 // The copies themselves are left to the chain's first kernel (io).
-int narrow_begin(gf_ctx* ctx, const gf_app* h_apps, uint32_t n_apps, hipStream_t stream, gangfit::NarrowTable* nt,
-                 gangfit::ChainIo* io, const int32_t* restore = nullptr, bool restore_dirty_chunks = false) {
-    int64_t eff[3];
-    int32_t factor[3];
-    if (ctx->planned_units.valid) {
-        for (int j = 0; j < 3; ++j) {
-            eff[j] = ctx->planned_units.eff[j];
-            factor[j] = ctx->planned_units.factor[j];
-        }
-    } else {
-        narrow_units(ctx, h_apps, n_apps, eff, factor, nullptr);
-    }
+int narrow_begin(gf_ctx* ctx, const FitCall& call, gangfit::NarrowTable* nt, gangfit::ChainIo* io, const int32_t* restore = nullptr,
+                 bool restore_dirty_chunks = false) {
+    int64_t own_eff[3];
+    int32_t own_factor[3];
+    if (call.run == nullptr) narrow_units(ctx, call.h_apps, call.q.n_apps, own_eff, own_factor, nullptr);  // a call without a plan
+    const int64_t* eff = call.run != nullptr ? call.run->eff : own_eff;
+    const int32_t* factor = call.run != nullptr ? call.run->factor : own_factor;
     nt->cpu = ctx->d_nwork.ptr;
     nt->mem = nt->cpu + ctx->n_slots;
     nt->gpu = nt->mem + ctx->n_slots;
@@ -197,7 +222,7 @@ int narrow_begin(gf_ctx* ctx, const gf_app* h_apps, uint32_t n_apps, hipStream_t
     } else {
         GF_HIP(ctx, ctx->d_ncmax_w.reserve(3 * (size_t)ctx->n_chunks));
         GF_HIP(ctx, gangfit::launch_narrow_rescale(ctx->d_nsnap.ptr, ctx->d_nwork.ptr, ctx->n_slots, ctx->d_ncmax.ptr,
-                                                   ctx->d_ncmax_w.ptr, ctx->n_chunks, factor, stream));
+                                                   ctx->d_ncmax_w.ptr, ctx->n_chunks, factor, call.q.stream));
         if (whole) src = restore;
         nt->cmax = ctx->d_ncmax_w.ptr;
     }
@@ -217,16 +242,6 @@ int narrow_begin(gf_ctx* ctx, const gf_app* h_apps, uint32_t n_apps, hipStream_t
     }
     return GF_OK;
 }
-
-// How one FIFO chain of gf_fit_batch uses the chain cache (decided by chain_plan before the launch).
-struct ChainRun {
-    uint32_t a_begin = 0;        // first application this launch evaluates (a multiple of 1 << shift); 0 = from the snapshot
-    bool record = false;         // dump checkpoints into ctx->chain.d_ckpt
-    bool narrow_proven = false;  // every request has a scaled form (checked on the host): the wide twin is not launched
-    uint32_t common = 0;         // leading applications identical to the cached queue's (>= a_begin): the cache keeps them
-    bool from_tip = false;       // the launch starts from the cached chain's tip (a_begin = its tip_at, any value) instead of a checkpoint
-    bool write_tip = false;      // the launch leaves its own tip in ctx->chain.d_tip
-};
 
 // The checkpoint arguments of a chain kernel and the table it starts from.
 gangfit::ChainCkpt chain_ckpt_args(gf_ctx* ctx, const ChainRun* run, const int32_t** restore) {
@@ -250,15 +265,15 @@ gangfit::ChainCkpt chain_ckpt_args(gf_ctx* ctx, const ChainRun* run, const int32
 // the records [a0, n_apps): the records come from the pinned host buffer when gf_fit_batch offered it, the answers go to
 // the host buffers when the translate step is the last kernel to write them (answers_final).
 int32_t* wide_flag(gf_ctx* ctx) { return ctx->d_wide_needed.ptr + (ctx->wide_seq & 1u); }
-int chain_io_begin(gf_ctx* ctx, uint32_t a0, bool answers_final, hipStream_t stream, gangfit::ChainIo* io) {
+int chain_io_begin(gf_ctx* ctx, const FitCall& call, uint32_t a0, bool answers_final, gangfit::ChainIo* io) {
     if (ctx->wide_dirty) {
-        GF_HIP(ctx, hipMemsetAsync(ctx->d_wide_needed.ptr, 0, 2 * sizeof(int32_t), stream));
+        GF_HIP(ctx, hipMemsetAsync(ctx->d_wide_needed.ptr, 0, 2 * sizeof(int32_t), call.q.stream));
         ctx->wide_dirty = false;
     }
     io->wide_clear = ctx->d_wide_needed.ptr + ((ctx->wide_seq & 1u) ^ 1u);
-    gf_ctx::HostIo& h = ctx->hio;
-    if (h.active && !h.apps_done) io->apps_src = h.apps + a0;
-    if (h.active && answers_final) {
+    const FitCall::HostIo& h = call.host;
+    if (h.apps != nullptr && !h.apps_done) io->apps_src = h.apps + a0;
+    if (h.apps != nullptr && answers_final) {
         io->h_results = h.results + a0;
         io->h_exec = h.exec;
         io->h_failed = h.failed;
@@ -266,17 +281,18 @@ int chain_io_begin(gf_ctx* ctx, uint32_t a0, bool answers_final, hipStream_t str
     ctx->wide_dirty = true;  // until chain_io_end: a launch that fails half way leaves the flag words in an unknown state
     return GF_OK;
 }
-void chain_io_end(gf_ctx* ctx, const gangfit::ChainIo& io) {
+void chain_io_end(gf_ctx* ctx, FitCall* call, const gangfit::ChainIo& io) {
     ctx->wide_dirty = false;
     ++ctx->wide_seq;
-    if (io.apps_src != nullptr) ctx->hio.apps_done = true;
-    if (io.h_results != nullptr) ctx->hio.out_done = true;
+    if (io.apps_src != nullptr) call->host.apps_done = true;
+    if (io.h_results != nullptr) call->host.out_done = true;
 }
 // Launch paths whose first kernel does not take the records from the host: an ordinary copy, once per gf_fit_batch.
-int apps_to_device(gf_ctx* ctx, hipStream_t stream) {
-    gf_ctx::HostIo& h = ctx->hio;
-    if (!h.active || h.apps_done) return GF_OK;
-    GF_HIP(ctx, hipMemcpyAsync(ctx->d_apps.ptr, ctx->h_apps.ptr, (size_t)h.n_apps * sizeof(gf_app), hipMemcpyHostToDevice, stream));
+int apps_to_device(gf_ctx* ctx, FitCall* call) {
+    FitCall::HostIo& h = call->host;
+    if (h.apps == nullptr || h.apps_done) return GF_OK;
+    GF_HIP(ctx, hipMemcpyAsync(ctx->d_apps.ptr, ctx->h_apps.ptr, (size_t)call->q.n_apps * sizeof(gf_app), hipMemcpyHostToDevice,
+                               call->q.stream));
     h.apps_done = true;
     return GF_OK;
 }
@@ -288,6 +304,12 @@ uint32_t solo_lds_slots(const gf_ctx* ctx) {
     const size_t fit = ctx->lds_budget > fixed ? (ctx->lds_budget - fixed) / per_chunk : 0;
     const size_t whole = (ctx->n_slots + 63u) / 64u;
     return (uint32_t)((fit < whole ? fit : whole) * 64u);
+}
+// ... and the wide chain kernel: as much of the table front as fits next to its fixed LDS needs stays in LDS for the whole chain
+uint32_t wide_lds_slots(const gf_ctx* ctx) {
+    const size_t fixed = gangfit::fifo_v2_lds_bytes(0, ctx->n_chunks);
+    const uint32_t fit = ctx->lds_budget > fixed ? (uint32_t)((ctx->lds_budget - fixed) / 24) : 0;
+    return fit >= (ctx->n_slots + 63) / 64 * 64 ? ctx->n_slots : fit / 64 * 64;  // the whole table (padded to full steps), or whole steps
 }
 
 // Geometry of the LDS-resident chains of the zone-aware tightly-pack packers (gangfit_fifo_zoned.inc) and of the
@@ -321,6 +343,25 @@ bool minfrag_lds_geometry(const gf_ctx* ctx, bool zoned, uint32_t* n_idx, uint32
     *n_idx = ni;
     return true;
 }
+// The whole record of that chain: the route's geometry and its global-memory tables — 64 shape ids per role; the capacity matrix,
+// one int32 per (request shape, slot), unless it would exceed 1 GiB or option "minfrag_matrix" is off (capacities are then
+// recomputed per pass); with it, the capacity histograms (option "minfrag_hist").
+int minfrag_lds_chain(gf_ctx* ctx, bool zoned, uint32_t lds_slots, uint32_t n_idx, gangfit::MinfragLdsChain* m) {
+    m->zoned = zoned;
+    m->lds_slots = lds_slots;
+    m->n_shapes = 64;
+    m->n_idx = n_idx;
+    m->d_capmat = m->d_hist = nullptr;
+    if ((uint64_t)m->n_shapes * ctx->n_slots * sizeof(int32_t) <= (UINT64_C(1) << 30) && ctx->fifo_minfrag_matrix) {
+        GF_HIP(ctx, ctx->d_capmat.reserve((size_t)m->n_shapes * ctx->n_slots + 2048));  // rows are read 2048 slots at a time
+        m->d_capmat = ctx->d_capmat.ptr;
+    }
+    if (m->d_capmat != nullptr && ctx->fifo_minfrag_hist) {
+        GF_HIP(ctx, ctx->d_mfhist.reserve(gangfit::fifo_minfrag_hist_words(zoned ? ctx->n_zones : 0u, m->n_shapes)));
+        m->d_hist = ctx->d_mfhist.ptr;
+    }
+    return GF_OK;
+}
 
 // What serves a batch of (mode, packer) on this context: the kernel route and the geometry of its chain kernel.  It depends
 // on the context's state and options only, never on the batch (what a batch adds — the narrow proof, the resume point —
@@ -340,6 +381,7 @@ struct Route {
     bool zoned = false, az_aware = false;
     uint32_t n_cand = 1;       // candidate views of an application
     uint32_t lds_slots = 0;    // LDS chain kernels: table slots kept in LDS
+    uint32_t lds_slots_wide = 0;  // kSolo, kWide: ... by fit_fifo_chain_kernel
     uint32_t n_shapes = 0;     // kZonedLds: shape-index rows; kMinfragLds: shape ids with chunk-index rows (n_idx)
     bool table_in_lds = false; // LDS chain kernels: the whole table
     bool lds_chain() const { return kind == kSolo || kind == kZonedLds || kind == kMinfragLds; }
@@ -371,6 +413,7 @@ int route_of(gf_ctx* ctx, gf_mode mode, gf_algo algo, Route* r) {
     if (r->inner != GF_ALGO_MINIMAL_FRAGMENTATION && !zoned) {
         r->kind = lds ? Route::kSolo : Route::kWide;
         if (lds) r->lds_slots = solo_lds_slots(ctx);
+        r->lds_slots_wide = wide_lds_slots(ctx);
     } else if (r->inner == GF_ALGO_TIGHTLY_PACK) {
         r->kind = lds && zoned_lds_geometry(ctx, r->az_aware, &r->n_shapes, &r->lds_slots) ? Route::kZonedLds : Route::kGeneric;
     } else {
@@ -407,25 +450,19 @@ gangfit::ZoneTable zone_table(const gf_ctx* ctx) {
 }
 
 // What every LDS chain kernel's launch starts with: the scaled records, the checkpoint arguments, the ChainIo and the narrow
-// working table (the copies themselves are left to the chain's first kernel).  chain_io_end(ctx, io) follows the launch.
-struct LdsChain {
-    gangfit::NarrowTable nt{};
-    gangfit::ChainCkpt ck{};
-    gangfit::ChainIo io;
-    int32_t* flag = nullptr;  // wide_flag of this chain: a request had no scaled form
-};
-int lds_chain_begin(gf_ctx* ctx, const ChainRun* run, uint32_t n_apps, const gf_app* h_apps, bool answers_final,
-                    bool restore_dirty_chunks, hipStream_t stream, LdsChain* c) {
-    GF_HIP(ctx, ctx->d_napps.reserve(n_apps));
+// working table (the copies themselves are left to the chain's first kernel).  chain_io_end(ctx, call, b->io) follows the launch.
+int lds_chain_begin(gf_ctx* ctx, const FitCall& call, bool answers_final, bool restore_dirty_chunks, gangfit::ChainBatch* b,
+                    gangfit::NarrowTable* nt) {
+    GF_HIP(ctx, ctx->d_napps.reserve(call.q.n_apps));
     const int32_t* restore = nullptr;
-    c->ck = chain_ckpt_args(ctx, run, &restore);
-    if (const int rc = chain_io_begin(ctx, c->ck.a_base, answers_final, stream, &c->io); rc != GF_OK) return rc;
-    c->flag = wide_flag(ctx);
-    return narrow_begin(ctx, h_apps, n_apps, stream, &c->nt, &c->io, restore, restore_dirty_chunks);
+    b->ckpt = chain_ckpt_args(ctx, call.run, &restore);
+    if (const int rc = chain_io_begin(ctx, call, b->ckpt.a_base, answers_final, &b->io); rc != GF_OK) return rc;
+    return narrow_begin(ctx, call, nt, &b->io, restore, restore_dirty_chunks);
 }
 
 // Which chains resume: every packer, when its LDS-resident chain kernel serves (the route) and every request has a scaled
-// form.  Returns false when the chain cache is not used for this call (run stays {0, false, false}).
+// form.  Returns false when the chain cache is not used for this call (run is then not handed on; only its
+// a_begin = 0 is read).
 bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, const gf_app* h_apps, ChainRun* run) {
     *run = ChainRun{};
     gf_ctx::ChainCache& C = ctx->chain;
@@ -437,8 +474,8 @@ bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, 
     // prefix with the cached one is only scanned behind it: the cached units divide the prefix by construction, and when they
     // divide the new applications too they ARE a valid set of units for this queue (any common divisor keeps the chain exact;
     // the checkpoints are scaled in them).  Otherwise: the full scan, and the chain replays.
-    int64_t eff[3];
-    int32_t factor[3];
+    int64_t(&eff)[3] = run->eff;
+    int32_t(&factor)[3] = run->factor;
     bool proven = false;
     uint32_t common = 0;  // applications this queue shares with the cached one, from the front (the last of either excluded)
     bool units_from_cache = false;
@@ -537,11 +574,6 @@ bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, 
     run->from_tip = from_tip;
     run->write_tip = tip_possible;
     run->narrow_proven = true;
-    ctx->planned_units.valid = true;
-    for (int j = 0; j < 3; ++j) {
-        ctx->planned_units.eff[j] = eff[j];
-        ctx->planned_units.factor[j] = factor[j];
-    }
     return true;
 }
 
@@ -575,141 +607,165 @@ void chain_commit(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, uint64_t total_k, 
     ctx->chain_stat[3] += run.a_begin;
 }
 
-// Launches the route's kernels.  h_apps: the same records on the host when the caller has them (gf_fit_batch), nullptr for
-// device-resident batches.  run (nullable): gf_fit_batch's plan for a FIFO chain; d_apps / d_results are always the arrays
-// of the WHOLE queue.
-int launch(gf_ctx* ctx, const Route& r, uint32_t n_apps, const gf_app* h_apps, const gf_app* d_apps, gf_result* d_results,
-           uint32_t* d_exec_nodes, uint64_t exec_nodes_len, int32_t* d_failed, hipStream_t stream, const ChainRun* run = nullptr) {
-    const uint64_t half = exec_nodes_len + 1;
-    GF_HIP(ctx, ctx->d_scratch.reserve(2 * half));
-    const uint32_t nz = r.zoned ? ctx->n_zones : 0u;
-    const gangfit::ZoneTable zt = r.zoned ? zone_table(ctx) : gangfit::ZoneTable{nullptr, nullptr, 0, 0};
-    ScanStats* stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr;
-    switch (r.kind) {
-    case Route::kPlain:
-        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
-        GF_HIP(ctx, gangfit::launch_fit_independent((gf_algo)r.inner, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), n_apps,
-                                                    d_apps, d_results, d_exec_nodes, ctx->d_scratch.ptr, half, stats, stream));
-        return GF_OK;
-    case Route::kZonedFused:
-        // a workgroup per application decides every candidate view, chooses and writes the final answer — d_apps / d_results /
-        // d_exec_nodes may be device-mapped host memory (gf_fit_batch)
-        GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * half));
-        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
-        GF_HIP(ctx, gangfit::launch_fit_zoned_fused(r.inner, r.az_aware, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), zt,
-                                                    ctx->d_sched.ptr, ctx->d_zexec.ptr, half, n_apps, d_apps, d_results,
-                                                    d_exec_nodes, ctx->d_scratch.ptr, half, stream));
-        return GF_OK;
-    case Route::kZonedFour: {
-        const uint64_t n_dec = (uint64_t)n_apps * (nz ? nz : 1);
-        GF_HIP(ctx, ctx->d_zres.reserve(n_dec));
-        GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * half));
-        GF_HIP(ctx, ctx->d_zavg.reserve(4 * n_dec));
-        if (const int rc = ensure_cnt(ctx, n_dec < 16 ? 16 : n_dec, stream); rc != GF_OK) return rc;
-        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;
-        const gangfit::ZoneBuffers zb{ctx->d_zres.ptr, ctx->d_zexec.ptr, half, ctx->d_zavg.ptr, ctx->d_cnt.ptr, ctx->cnt_rows};
-        GF_HIP(ctx, gangfit::launch_fit_zoned(r.inner, r.az_aware, r.inner != GF_ALGO_MINIMAL_FRAGMENTATION,
-                                              make_table(ctx, ctx->d_snap.ptr), zt, slot_eff_tables(ctx, ctx->d_snap.ptr), zb,
-                                              n_apps, d_apps, d_results, d_exec_nodes, ctx->d_scratch.ptr, half, stream));
-        return GF_OK;
-    }
-    case Route::kSolo:
-    case Route::kWide: {
-        gangfit::FifoPlan plan{};
-        plan.narrow = r.kind == Route::kSolo;
-        plan.wide = !(plan.narrow && run != nullptr && run->narrow_proven);
-        // every chain starts from the snapshot: availableNodesSchedulingMetadata is rebuilt per request (resource.go:303).
-        // The solo kernel rewrites every real slot of the wide working table in its epilogue: the copy is only needed by the
-        // wide kernel.  Like the narrow table's, the copy is made by the chain's first kernel (ChainIo).
-        LdsChain c;
-        c.ck.shift = ctx->chain.shift;
-        if (plan.narrow) {
-            if (const int rc = lds_chain_begin(ctx, run, n_apps, h_apps, true, ctx->chain.dirty_format, stream, &c); rc != GF_OK)
-                return rc;
-        } else if (const int rc = chain_io_begin(ctx, 0, true, stream, &c.io); rc != GF_OK) {
-            return rc;
-        }
-        if (plan.wide) {
-            c.io.copy_src[1] = reinterpret_cast<const uint32_t*>(ctx->d_snap.ptr);
-            c.io.copy_dst[1] = reinterpret_cast<uint32_t*>(ctx->d_work.ptr);
-            c.io.copy_words[1] = 3 * (size_t)ctx->n_slots * (sizeof(int64_t) / sizeof(uint32_t));
-        }
-        ctx->work_valid = true;
-        // as much of the table front as fits next to the wide kernel's fixed LDS needs stays in LDS for the whole chain
-        const size_t fixed = gangfit::fifo_v2_lds_bytes(0, ctx->n_chunks);
-        const uint32_t fit = ctx->lds_budget > fixed ? (uint32_t)((ctx->lds_budget - fixed) / 24) : 0;
-        const uint32_t whole = (ctx->n_slots + 63) / 64 * 64;  // the whole table, padded to full steps
-        plan.lds_slots_v2 = fit >= whole ? whole : fit / 64 * 64;
-        if (plan.lds_slots_v2 > ctx->n_slots) plan.lds_slots_v2 = ctx->n_slots;
-        plan.lds_slots_solo = r.lds_slots;
-        // a resumed chain is launched on the tail of the queue: exec_off is absolute, so offset pointers are all it takes
-        const uint32_t a0 = c.ck.a_base;
-        const uint64_t heads_lo = a0 > 0 ? h_apps[a0].exec_off : 0;
-        GF_HIP(ctx, gangfit::launch_fit_fifo((gf_algo)r.inner, plan, make_table(ctx, ctx->d_work.ptr), c.nt, n_apps - a0, d_apps + a0,
-                                             ctx->d_napps.ptr + a0, wide_flag(ctx), d_results + a0, d_exec_nodes,
-                                             ctx->d_scratch.ptr, half, heads_lo, d_failed, c.ck, c.io, stats, stream));
-        chain_io_end(ctx, c.io);
-        return GF_OK;
-    }
-    default:
-        break;
-    }
-    // FIFO chains of the zone-aware and minimal-fragmentation packers: the LDS chain kernel, with the generic chain kernel as
-    // its guarded twin, or the generic kernel alone (one wavefront per candidate view, the working table in global memory)
-    const bool proven = run != nullptr && run->narrow_proven;  // the LDS chain serves for certain: no generic twin
+// The tables of a chain: the wide working table, nt — its scaled twin — and the zones.
+gangfit::ChainTables chain_tables(gf_ctx* ctx, const Route& r, const gangfit::NarrowTable& nt) {
+    return gangfit::ChainTables{make_table(ctx, ctx->d_work.ptr), nt, r.zoned ? zone_table(ctx) : gangfit::ZoneTable{nullptr, nullptr, 0, 0},
+                                r.zoned ? ctx->d_sched.ptr : nullptr};
+}
+// Makes b — the whole queue with its ckpt and io set — the batch of the queue's tail [b->ckpt.a_base, n_apps), once the context's
+// buffers have their sizes: exec_off is absolute, so the record, scaled-record and result pointers are all that moves.
+void chain_batch_tail(gf_ctx* ctx, gangfit::ChainBatch* b) {
+    const uint32_t a0 = b->ckpt.a_base;
+    b->n_apps -= a0;
+    b->d_apps += a0;
+    b->d_napps = ctx->d_napps.ptr + a0;
+    b->d_wide_needed = wide_flag(ctx);
+    b->d_results += a0;
+    b->d_scratch = ctx->d_scratch.ptr;
+    b->d_zexec = ctx->d_zexec.ptr;
+    b->d_stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr;
+}
+
+// Independent batches: every application against the snapshot.
+int launch_plain(gf_ctx* ctx, const Route& r, FitCall* call) {
+    if (const int arc = apps_to_device(ctx, call); arc != GF_OK) return arc;
+    GF_HIP(ctx, gangfit::launch_fit_independent((gf_algo)r.inner, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), call->q.n_apps,
+                                                call->q.d_apps, call->q.d_results, call->q.d_exec_nodes, ctx->d_scratch.ptr,
+                                                call->q.half, ctx->stats_on ? ctx->d_stats.ptr : nullptr, call->q.stream));
+    return GF_OK;
+}
+// ... of the zone-aware packers in one launch: a workgroup per application decides every candidate view, chooses and writes the
+// final answer — d_apps / d_results / d_exec_nodes may be device-mapped host memory (gf_fit_batch)
+int launch_zoned_fused(gf_ctx* ctx, const Route& r, FitCall* call) {
+    const uint64_t half = call->q.half;
+    GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)ctx->n_zones + 1) * half));
+    if (const int arc = apps_to_device(ctx, call); arc != GF_OK) return arc;
+    GF_HIP(ctx, gangfit::launch_fit_zoned_fused(r.inner, r.az_aware, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), zone_table(ctx),
+                                                ctx->d_sched.ptr, ctx->d_zexec.ptr, half, call->q.n_apps, call->q.d_apps, call->q.d_results,
+                                                call->q.d_exec_nodes, ctx->d_scratch.ptr, half, call->q.stream));
+    return GF_OK;
+}
+// ... in four
+int launch_zoned_four(gf_ctx* ctx, const Route& r, FitCall* call) {
+    const uint32_t nz = ctx->n_zones;
+    const uint64_t half = call->q.half, n_dec = (uint64_t)call->q.n_apps * (nz ? nz : 1);
+    GF_HIP(ctx, ctx->d_zres.reserve(n_dec));
     GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * half));
-    if (r.zoned) {
-        const uint64_t n_dec = (uint64_t)n_apps * (nz ? nz : 1);
-        if (const int rc = ensure_cnt(ctx, n_dec < 16 ? 16 : n_dec, stream); rc != GF_OK) return rc;
-        if (ctx->cnt_rows < 16) return fail(ctx, GF_ERR_HIP, "multiplicity scratch too small");
+    GF_HIP(ctx, ctx->d_zavg.reserve(4 * n_dec));
+    if (const int rc = ensure_cnt(ctx, n_dec < 16 ? 16 : n_dec, call->q.stream); rc != GF_OK) return rc;
+    if (const int arc = apps_to_device(ctx, call); arc != GF_OK) return arc;
+    const gangfit::ZoneBuffers zb{ctx->d_zres.ptr, ctx->d_zexec.ptr, half, ctx->d_zavg.ptr, ctx->d_cnt.ptr, ctx->cnt_rows};
+    GF_HIP(ctx, gangfit::launch_fit_zoned(r.inner, r.az_aware, r.inner != GF_ALGO_MINIMAL_FRAGMENTATION, make_table(ctx, ctx->d_snap.ptr),
+                                          zone_table(ctx), slot_eff_tables(ctx, ctx->d_snap.ptr), zb, call->q.n_apps, call->q.d_apps,
+                                          call->q.d_results, call->q.d_exec_nodes, ctx->d_scratch.ptr, half, call->q.stream));
+    return GF_OK;
+}
+
+// FIFO chain of tightly-pack / distribute-evenly: the solo kernel (kSolo) with the wide kernel as its guarded twin unless
+// the host has proven every request's scaled form, or the wide kernel alone (kWide).
+int launch_plain_chain(gf_ctx* ctx, const Route& r, FitCall* call) {
+    gangfit::FifoPlan plan{};
+    plan.narrow = r.kind == Route::kSolo;
+    plan.wide = !(plan.narrow && call->run != nullptr && call->run->narrow_proven);
+    plan.lds_slots_v2 = r.lds_slots_wide;
+    plan.lds_slots_solo = r.lds_slots;
+    // every chain starts from the snapshot: availableNodesSchedulingMetadata is rebuilt per request (resource.go:303).
+    // The solo kernel rewrites every real slot of the wide working table in its epilogue: the copy is only needed by the
+    // wide kernel.  Like the narrow table's, the copy is made by the chain's first kernel (ChainIo).
+    gangfit::ChainBatch b = call->q;
+    gangfit::NarrowTable nt{};
+    b.ckpt.shift = ctx->chain.shift;
+    if (plan.narrow) {
+        if (const int rc = lds_chain_begin(ctx, *call, true, ctx->chain.dirty_format, &b, &nt); rc != GF_OK) return rc;
+    } else if (const int rc = chain_io_begin(ctx, *call, 0, true, &b.io); rc != GF_OK) {
+        return rc;
     }
-    // every chain starts from the snapshot: availableNodesSchedulingMetadata is rebuilt per request (resource.go:303);
-    // the LDS chains rewrite every real slot of the wide working table in their epilogue
-    if (!proven) {
-        if (const int arc = apps_to_device(ctx, stream); arc != GF_OK) return arc;  // the generic kernel reads d_apps
-        GF_HIP(ctx, hipMemcpyAsync(ctx->d_work.ptr, ctx->d_snap.ptr, 3 * (size_t)ctx->n_slots * sizeof(int64_t),
-                                   hipMemcpyDeviceToDevice, stream));
+    if (plan.wide) {
+        b.io.copy_src[1] = reinterpret_cast<const uint32_t*>(ctx->d_snap.ptr);
+        b.io.copy_dst[1] = reinterpret_cast<uint32_t*>(ctx->d_work.ptr);
+        b.io.copy_words[1] = 3 * (size_t)ctx->n_slots * (sizeof(int64_t) / sizeof(uint32_t));
     }
     ctx->work_valid = true;
-    const int32_t* run_if = nullptr;  // the generic twin only runs when a request had no scaled form
-    if (r.kind != Route::kGeneric) {
-        GF_HIP(ctx, ctx->d_zexec.reserve(32 * half));
-        LdsChain c;
-        if (const int rc = lds_chain_begin(ctx, run, n_apps, h_apps, proven, false, stream, &c); rc != GF_OK) return rc;
-        const uint32_t a0 = c.ck.a_base;
-        if (r.kind == Route::kZonedLds) {
-            GF_HIP(ctx, gangfit::launch_fit_fifo_zoned_lds(r.az_aware, make_table(ctx, ctx->d_work.ptr), c.nt, zt, ctx->d_sched.ptr,
-                                                           r.lds_slots, r.n_shapes, n_apps - a0, d_apps + a0, ctx->d_napps.ptr + a0,
-                                                           c.flag, d_results + a0, d_exec_nodes, ctx->d_zexec.ptr, half, d_failed,
-                                                           c.ck, c.io, stats, stream));
-        } else {
-            const uint32_t n_shapes = 64;
-            // capacity matrix: one int32 per (request shape, slot); skipped (capacities recomputed per pass) beyond 1 GiB
-            int32_t* capmat = nullptr;
-            if ((uint64_t)n_shapes * ctx->n_slots * sizeof(int32_t) <= (UINT64_C(1) << 30) && ctx->fifo_minfrag_matrix) {
-                GF_HIP(ctx, ctx->d_capmat.reserve((size_t)n_shapes * ctx->n_slots + 2048));  // rows are read 2048 slots at a time
-                capmat = ctx->d_capmat.ptr;
-            }
-            int32_t* hist = nullptr;
-            if (capmat != nullptr && ctx->fifo_minfrag_hist) {
-                GF_HIP(ctx, ctx->d_mfhist.reserve(gangfit::fifo_minfrag_hist_words(nz, n_shapes)));
-                hist = ctx->d_mfhist.ptr;
-            }
-            GF_HIP(ctx, gangfit::launch_fit_fifo_minfrag_lds(r.zoned, make_table(ctx, ctx->d_work.ptr), c.nt, zt, ctx->d_sched.ptr,
-                                                             r.lds_slots, n_shapes, r.n_shapes, n_apps - a0, d_apps + a0,
-                                                             ctx->d_napps.ptr + a0, c.flag, d_results + a0, d_exec_nodes,
-                                                             ctx->d_zexec.ptr, half, d_failed, capmat, hist, c.ck, c.io, stats,
-                                                             stream));
-        }
-        chain_io_end(ctx, c.io);
-        if (proven) return GF_OK;
-        run_if = c.flag;
-    }
-    GF_HIP(ctx, gangfit::launch_fit_fifo_generic(r.inner, r.zoned, r.az_aware, make_table(ctx, ctx->d_work.ptr), zt,
-                                                 r.zoned ? ctx->d_sched.ptr : nullptr, ctx->d_zexec.ptr, half,
-                                                 r.zoned ? ctx->d_cnt.ptr : nullptr, n_apps, d_apps, d_results, d_exec_nodes,
-                                                 ctx->d_scratch.ptr, half, d_failed, run_if, stream));
+    chain_batch_tail(ctx, &b);
+    const uint64_t heads_lo = b.ckpt.a_base > 0 ? call->h_apps[b.ckpt.a_base].exec_off : 0;  // placements of the skipped prefix
+    GF_HIP(ctx, gangfit::launch_fit_fifo((gf_algo)r.inner, plan, chain_tables(ctx, r, nt), b, heads_lo));
+    chain_io_end(ctx, call, b.io);
     return GF_OK;
+}
+
+// FIFO chains of the zone-aware and minimal-fragmentation packers.  What the generic chain kernel needs before anything of
+// the chain is launched; twin_runs = false: the LDS chain serves for certain and rewrites every real slot of the wide working
+// table in its epilogue — no record copy, no table copy.
+int generic_chain_begin(gf_ctx* ctx, const Route& r, FitCall* call, bool twin_runs) {
+    const uint32_t nz = r.zoned ? ctx->n_zones : 0u;
+    GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)nz + 1) * (call->q.half)));
+    if (r.zoned) {
+        const uint64_t n_dec = (uint64_t)call->q.n_apps * (nz ? nz : 1);
+        if (const int rc = ensure_cnt(ctx, n_dec < 16 ? 16 : n_dec, call->q.stream); rc != GF_OK) return rc;
+        if (ctx->cnt_rows < 16) return fail(ctx, GF_ERR_HIP, "multiplicity scratch too small");
+    }
+    // every chain starts from the snapshot: availableNodesSchedulingMetadata is rebuilt per request (resource.go:303)
+    if (twin_runs) {
+        if (const int arc = apps_to_device(ctx, call); arc != GF_OK) return arc;  // the generic kernel reads d_apps
+        GF_HIP(ctx, hipMemcpyAsync(ctx->d_work.ptr, ctx->d_snap.ptr, 3 * (size_t)ctx->n_slots * sizeof(int64_t),
+                                   hipMemcpyDeviceToDevice, call->q.stream));
+    }
+    ctx->work_valid = true;
+    return GF_OK;
+}
+// The generic chain kernel on the whole queue (one wavefront per candidate view, the working table in global memory), behind
+// generic_chain_begin; run_if (nullable): the flag word of the LDS chain it is the twin of — it only runs when a request had no
+// scaled form.
+int launch_generic_chain(gf_ctx* ctx, const Route& r, FitCall* call, const int32_t* run_if) {
+    const gangfit::GenericChain g{r.inner, r.zoned, r.az_aware, r.zoned ? ctx->d_cnt.ptr : nullptr, run_if};
+    gangfit::ChainBatch b = call->q;
+    chain_batch_tail(ctx, &b);
+    GF_HIP(ctx, gangfit::launch_fit_fifo_generic(g, chain_tables(ctx, r, gangfit::NarrowTable{}), b));
+    return GF_OK;
+}
+
+// The LDS chain kernel (kZonedLds, kMinfragLds), with the generic chain kernel as its guarded twin unless the host has proven
+// every request's scaled form.
+int launch_lds_chain(gf_ctx* ctx, const Route& r, FitCall* call) {
+    const bool proven = call->run != nullptr && call->run->narrow_proven;
+    if (const int rc = generic_chain_begin(ctx, r, call, !proven); rc != GF_OK) return rc;
+    GF_HIP(ctx, ctx->d_zexec.reserve(32 * (call->q.half)));
+    gangfit::ChainBatch b = call->q;
+    gangfit::NarrowTable nt{};
+    if (const int rc = lds_chain_begin(ctx, *call, proven, false, &b, &nt); rc != GF_OK) return rc;
+    chain_batch_tail(ctx, &b);
+    if (r.kind == Route::kZonedLds) {
+        GF_HIP(ctx, gangfit::launch_fit_fifo_zoned_lds(r.az_aware, r.lds_slots, r.n_shapes, chain_tables(ctx, r, nt), b));
+    } else {
+        gangfit::MinfragLdsChain m;
+        if (const int rc = minfrag_lds_chain(ctx, r.zoned, r.lds_slots, /* n_idx */ r.n_shapes, &m); rc != GF_OK) return rc;
+        GF_HIP(ctx, gangfit::launch_fit_fifo_minfrag_lds(m, chain_tables(ctx, r, nt), b));
+    }
+    chain_io_end(ctx, call, b.io);
+    return proven ? GF_OK : launch_generic_chain(ctx, r, call, b.d_wide_needed);
+}
+
+// Launches the route's kernels.
+int launch(gf_ctx* ctx, const Route& r, FitCall* call) {
+    GF_HIP(ctx, ctx->d_scratch.reserve(2 * (call->q.half)));
+    switch (r.kind) {
+    case Route::kPlain:
+        return launch_plain(ctx, r, call);
+    case Route::kZonedFused:
+        return launch_zoned_fused(ctx, r, call);
+    case Route::kZonedFour:
+        return launch_zoned_four(ctx, r, call);
+    case Route::kSolo:
+    case Route::kWide:
+        return launch_plain_chain(ctx, r, call);
+    case Route::kZonedLds:
+    case Route::kMinfragLds:
+        return launch_lds_chain(ctx, r, call);
+    case Route::kGeneric:
+        if (const int rc = generic_chain_begin(ctx, r, call, true); rc != GF_OK) return rc;
+        return launch_generic_chain(ctx, r, call, nullptr);
+    }
+    return fail(ctx, GF_ERR_INVALID, "unknown kernel route %d", (int)r.kind);
 }
 
 }  // namespace gfapi
@@ -756,6 +812,12 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     GF_HIP(ctx, ctx->h_results.reserve(n_apps));
     GF_HIP(ctx, ctx->h_exec.reserve(total_k + 1));
     hipStream_t st = ctx->stream;
+    FitCall call;  // (the device arrays are chosen below)
+    call.q.n_apps = n_apps;
+    call.q.half = total_k + 1;
+    call.q.d_chain_failed_at = ctx->d_failed.ptr;
+    call.q.stream = st;
+    call.h_apps = ctx->h_apps.ptr;
     // Small independent batches of the plain packers skip the three staging copies: the kernel reads the app records from
     // the pinned staging buffer and writes results and placements straight into pinned host memory (posted PCIe writes,
     // visible when the kernel has completed).  A copy engine round trip costs more than the whole kernel at these sizes.
@@ -765,8 +827,10 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
         if (da != nullptr && dr != nullptr && de != nullptr) {
             using clk = std::chrono::steady_clock;
             const auto t_staged = clk::now();
-            const int rc0 = launch(ctx, route, n_apps, ctx->h_apps.ptr, static_cast<const gf_app*>(da),
-                                   static_cast<gf_result*>(dr), static_cast<uint32_t*>(de), total_k, ctx->d_failed.ptr, st);
+            call.q.d_apps = static_cast<const gf_app*>(da);
+            call.q.d_results = static_cast<gf_result*>(dr);
+            call.q.d_exec_nodes = static_cast<uint32_t*>(de);
+            const int rc0 = launch(ctx, route, &call);
             if (rc0 != GF_OK) return rc0;
             const auto t_launched = clk::now();
             GF_HIP(ctx, gf_wait_stream(st));
@@ -785,7 +849,6 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     }
     // ---- FIFO chains of the plain packers on the solo kernel: resume from the last chain's checkpoints where the queues agree
     ChainRun run;
-    ctx->planned_units.valid = false;
     const bool use_cache = chain_plan(ctx, route, algo, n_apps, ctx->h_apps.ptr, &run);
     const uint32_t a0 = run.a_begin;
     const uint64_t k0 = a0 > 0 ? ctx->h_apps.ptr[a0].exec_off : 0;  // placements of the skipped prefix
@@ -793,32 +856,28 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     // copy-engine transfers behind the last kernel are three hand-overs between the compute queue and a copy engine — a
     // visible part of a resumed chain, and what keeps chains on different streams from overlapping.  A FIFO chain goes
     // further: its first kernel reads the records from the pinned buffer and its last one writes the answers there
-    // (gf_ctx::HostIo), which makes a Filter three launches and no copy.
+    // (FitCall::HostIo), which makes a Filter three launches and no copy.
     void *da = ctx->h_apps.dev, *dr = ctx->h_results.dev, *de = ctx->h_exec.dev, *df = ctx->h_failed.dev;
     const bool mapped = ctx->zero_copy && dr != nullptr && de != nullptr && df != nullptr;
-    gf_ctx::HostIo& hio = ctx->hio;
-    hio = gf_ctx::HostIo{};
+    call.q.d_apps = ctx->d_apps.ptr;
+    call.q.d_results = ctx->d_results.ptr;
+    call.q.d_exec_nodes = ctx->d_exec.ptr;
+    call.run = use_cache ? &run : nullptr;
     if (mapped && mode == GF_MODE_FIFO_CHAIN && da != nullptr) {
-        hio.active = true;
-        hio.n_apps = n_apps;
-        hio.apps = static_cast<const gf_app*>(da);
-        hio.results = static_cast<gf_result*>(dr);
-        hio.exec = static_cast<uint32_t*>(de);
-        hio.failed = static_cast<int32_t*>(df);
+        call.host.apps = static_cast<const gf_app*>(da);
+        call.host.results = static_cast<gf_result*>(dr);
+        call.host.exec = static_cast<uint32_t*>(de);
+        call.host.failed = static_cast<int32_t*>(df);
     } else {
         GF_HIP(ctx, hipMemcpyAsync(ctx->d_apps.ptr + a0, ctx->h_apps.ptr + a0, (size_t)(n_apps - a0) * sizeof(gf_app),
                                    hipMemcpyHostToDevice, st));
     }
-    const int rc = launch(ctx, route, n_apps, ctx->h_apps.ptr, ctx->d_apps.ptr, ctx->d_results.ptr, ctx->d_exec.ptr,
-                          total_k, ctx->d_failed.ptr, st, use_cache ? &run : nullptr);
-    const bool answers_sent = hio.active && hio.out_done;
-    hio.active = false;
-    ctx->planned_units.valid = false;
+    const int rc = launch(ctx, route, &call);
     if (rc != GF_OK) {
         ctx->chain.valid = false;
         return rc;
     }
-    if (answers_sent) {
+    if (call.host.out_done) {
         // the chain's last kernel wrote results, placements and the abort index to the host buffers
     } else if (mapped) {
         gangfit::CopyOut co{};
@@ -992,7 +1051,15 @@ int gf_fit_batch_dev(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, c
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
     Route route;
     if (const int rc = route_of(ctx, mode, algo, &route); rc != GF_OK) return rc;
-    return launch(ctx, route, n_apps, nullptr, d_apps, d_results, d_exec_nodes, exec_nodes_len, d_chain_failed_at, st);
+    FitCall call;  // no host records, no plan, no offer
+    call.q.n_apps = n_apps;
+    call.q.d_apps = d_apps;
+    call.q.d_results = d_results;
+    call.q.d_exec_nodes = d_exec_nodes;
+    call.q.half = exec_nodes_len + 1;
+    call.q.d_chain_failed_at = d_chain_failed_at;
+    call.q.stream = st;
+    return launch(ctx, route, &call);
 }
 
 

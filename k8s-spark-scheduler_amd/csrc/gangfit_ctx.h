@@ -298,16 +298,6 @@ struct gf_ctx {
                                             // form; each prologue zeroes the word the NEXT chain will use (wide_flag)
     uint32_t wide_seq = 0;                  // chains launched: parity picks the word
     bool wide_dirty = false;                // a launch failed half way: both words are cleared before the next chain
-    struct HostIo {  // set by gf_fit_batch around launch(): where the first / last kernel of a chain may read and write directly
-        bool active = false;
-        uint32_t n_apps = 0;           // records of the whole queue in h_apps
-        const gf_app* apps = nullptr;  // device addresses of the pinned h_apps / h_results / h_exec / h_failed
-        gf_result* results = nullptr;
-        uint32_t* exec = nullptr;
-        int32_t* failed = nullptr;
-        bool apps_done = false;  // a kernel of this launch writes (or a copy wrote) the records to d_apps
-        bool out_done = false;   // the last kernel of this launch writes the answers to the host buffers
-    } hio;
     DeviceBuf<int32_t> d_capmat;            // minimal-fragmentation chain: capacity per (request shape, slot)
     bool fifo_minfrag_matrix = true;        // option "minfrag_matrix" = 0 recomputes capacities in every pass
     DeviceBuf<int32_t> d_mfhist;            // ... and the capacity histograms per (candidate view, request shape)
@@ -468,11 +458,6 @@ struct gf_ctx {
                                       // that lays checkpoints 1 .. i over the snapshot instead of a copy
     } chain;
     uint64_t chain_stat[4] = {0, 0, 0, 0};  // chains | resumed chains | applications evaluated | applications skipped
-    struct PlannedUnits {  // what chain_plan found for the call in progress: narrow_begin does not scan the queue again
-        bool valid = false;
-        int64_t eff[3] = {0, 0, 0};
-        int32_t factor[3] = {1, 1, 1};
-    } planned_units;
 };
 
 namespace gfapi {

@@ -267,14 +267,37 @@ struct ChainIo {
     uint32_t* h_exec = nullptr;        // indexed by the records' absolute exec_off
     int32_t* h_failed = nullptr;
 };
+// What every chain launcher receives: the records of ONE launch — the tail of the queue behind ckpt.a_base — and where its
+// answers go (exec_off is absolute: d_exec_nodes, d_scratch and d_zexec are those of the whole queue).
+struct ChainBatch {
+    uint32_t n_apps = 0;
+    const gf_app* d_apps = nullptr;
+    NApp* d_napps = nullptr;           // the scaled records (written by the chain's first kernel; LDS chain kernels)
+    int32_t* d_wide_needed = nullptr;  // the flag word of this chain: a request has no scaled form
+    gf_result* d_results = nullptr;
+    uint32_t* d_exec_nodes = nullptr;
+    uint32_t* d_scratch = nullptr;  // 2 * half uint32: run heads / survivor lists (plain and generic chains)
+    uint32_t* d_zexec = nullptr;    // rows of half uint32: the candidates' placements as slot ids (generic chain: n_zones + 1
+                                    // rows), run-list tails beyond the LDS capacity (zoned and minfrag LDS chains: 2 * 16 rows)
+    uint64_t half = 0;
+    int32_t* d_chain_failed_at = nullptr;
+    ChainCkpt ckpt{};
+    ChainIo io;
+    ScanStats* d_stats = nullptr;  // nullable
+    hipStream_t stream = nullptr;
+};
+// ... and its tables: the wide working table, its scaled twin (LDS chain kernels), the zones and SchedulableResources in slot
+// order (zone-aware packers; else empty / nullptr).
+struct ChainTables {
+    NodeTable table;
+    NarrowTable ntable;
+    ZoneTable zones;
+    const int64_t* d_sched;
+};
 size_t fifo_v2_lds_bytes(uint32_t lds_slots, uint32_t n_chunks);
 size_t fifo_solo_lds_bytes(uint32_t lds_slots, uint32_t n_chunks);
 // heads_lo: first entry of d_scratch this launch may write run heads to (the placements of a resumed chain start there)
-hipError_t launch_fit_fifo(gf_algo algo, const FifoPlan& plan, const NodeTable& table, const NarrowTable& ntable,
-                           uint32_t n_apps, const gf_app* d_apps, NApp* d_napps, int32_t* d_wide_needed,
-                           gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch, uint64_t scratch_half,
-                           uint64_t heads_lo, int32_t* d_chain_failed_at, const ChainCkpt& ckpt, const ChainIo& io,
-                           ScanStats* d_stats, hipStream_t stream);
+hipError_t launch_fit_fifo(gf_algo algo, const FifoPlan& plan, const ChainTables& tables, const ChainBatch& batch, uint64_t heads_lo);
 
 // Zone-aware packers on an independent batch: one wave per (app, zone) runs SparkBinPack on the zone's view, one wave
 // per decision averages the packing efficiencies of [driver] ++ executors in slice order (chooseBestResult,
@@ -305,41 +328,37 @@ hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const NodeTable
 
 // FIFO chain of the zone-aware and minimal-fragmentation packers: one workgroup, one wavefront per candidate view of the
 // current app (each zone, plus the plain pack for az-aware), working table in global memory.  d_zexec needs (n_zones + 1)
-// rows of zexec_stride, d_cnt (zoned) at least 16 rows of ZoneBuffers::cnt.  Writes final results / placements as node indices.
-hipError_t launch_fit_fifo_generic(int inner_algo, bool zoned, bool az_aware, const NodeTable& table, const ZoneTable& zones,
-                                   const int64_t* d_sched, uint32_t* d_zexec, uint64_t zexec_stride, uint32_t* d_cnt,
-                                   uint32_t n_apps, const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes,
-                                   uint32_t* d_scratch, uint64_t scratch_half, int32_t* d_chain_failed_at,
-                                   const int32_t* d_run_if, hipStream_t stream);
+// rows, d_cnt (zoned) at least 16 rows of ZoneBuffers::cnt.  Writes final results / placements as node indices.
+struct GenericChain {
+    int inner_algo;  // the packer of one candidate view
+    bool zoned, az_aware;
+    uint32_t* d_cnt;          // nullptr when not zoned
+    const int32_t* d_run_if;  // nullable: the kernel returns at once unless the word is set (the twin of an LDS chain)
+};
+hipError_t launch_fit_fifo_generic(const GenericChain& chain, const ChainTables& tables, const ChainBatch& batch);
 
 // LDS-resident chain for the zone-aware tightly-pack packers on the merged layout with a narrow table
 // (gangfit_fifo_zoned.inc).  Returns at once when a request of the batch has no scaled form (*d_wide_needed != 0 after
 // its own prepare step): the caller then launches launch_fit_fifo_generic with d_run_if = d_wide_needed.
-// d_spill: 2 * 16 rows of spill_stride uint32 (run-list tails beyond the LDS capacity).
 // n_cand = candidate views = zones (+ 1 for az-aware: the plain pack); the workgroup's size follows from it.
 size_t fifo_zoned_lds_bytes(uint32_t lds_slots, uint32_t n_chunks, uint32_t n_zones, uint32_t n_cand, uint32_t n_shapes);
-hipError_t launch_fit_fifo_zoned_lds(bool az_aware, const NodeTable& table, const NarrowTable& ntable, const ZoneTable& zones,
-                                     const int64_t* d_sched, uint32_t lds_slots, uint32_t n_shapes, uint32_t n_apps,
-                                     const gf_app* d_apps, NApp* d_napps, int32_t* d_wide_needed, gf_result* d_results,
-                                     uint32_t* d_exec_nodes, uint32_t* d_spill, uint64_t spill_stride,
-                                     int32_t* d_chain_failed_at, const ChainCkpt& ckpt, const ChainIo& io, ScanStats* d_stats,
-                                     hipStream_t stream);
+hipError_t launch_fit_fifo_zoned_lds(bool az_aware, uint32_t lds_slots /* table slots kept in LDS */, uint32_t n_shapes /* shape-index rows */,
+                                     const ChainTables& tables, const ChainBatch& batch);
 
 // LDS-resident, block-cooperative chain for minimal-fragmentation, plain (zoned = false) or single-AZ
 // (gangfit_fifo_minfrag.inc); same contract as launch_fit_fifo_zoned_lds.
+struct MinfragLdsChain {
+    bool zoned;
+    uint32_t lds_slots;  // table slots kept in LDS
+    uint32_t n_shapes;   // shape ids per role
+    uint32_t n_idx;      // ... of which with chunk-index rows in LDS
+    int32_t* d_capmat;   // n_shapes x n_slots, nullable
+    int32_t* d_hist;     // fifo_minfrag_hist_words, nullable: no histogram path
+};
 size_t fifo_minfrag_lds_bytes(uint32_t lds_slots, uint32_t n_chunks, uint32_t n_zones, uint32_t n_shapes);
 // int32 words of the capacity histograms (one per candidate view and executor shape; gangfit_fifo_minfrag.inc)
 size_t fifo_minfrag_hist_words(uint32_t n_zones, uint32_t n_shapes);
-hipError_t launch_fit_fifo_minfrag_lds(bool zoned, const NodeTable& table, const NarrowTable& ntable, const ZoneTable& zones,
-                                       const int64_t* d_sched, uint32_t lds_slots,
-                                       uint32_t n_shapes /* shape ids per role */, uint32_t n_idx /* ... with index rows in LDS */,
-                                       uint32_t n_apps,
-                                       const gf_app* d_apps, NApp* d_napps, int32_t* d_wide_needed, gf_result* d_results,
-                                       uint32_t* d_exec_nodes, uint32_t* d_spill, uint64_t spill_stride,
-                                       int32_t* d_chain_failed_at, int32_t* d_capmat /* n_shapes x n_slots, nullable */,
-                                       int32_t* d_hist /* fifo_minfrag_hist_words, nullable: no histogram path */,
-                                       const ChainCkpt& ckpt, const ChainIo& io, ScanStats* d_stats /* nullable */,
-                                       hipStream_t stream);
+hipError_t launch_fit_fifo_minfrag_lds(const MinfragLdsChain& chain, const ChainTables& tables, const ChainBatch& batch);
 
 // ComputeAvgPackingEfficiency over [driver] ++ executors of n_apps finished results whose placements are NODE indices
 // (efficiency.go:114-156); d_avg_out: n_apps x 4 doubles {CPU, Memory, GPU, Max}.

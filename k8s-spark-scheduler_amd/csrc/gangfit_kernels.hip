@@ -2040,42 +2040,15 @@ hipError_t launch_chain_prologue(const ChainIo& io, uint32_t n_apps, const gf_ap
 inline ChainOut chain_out_of(const ChainIo& io, const int32_t* d_failed) { return ChainOut{io.h_results, io.h_exec, d_failed, io.h_failed}; }
 
 template <int ALGO>
-hipError_t launch_v2(const FifoPlan& P, const NodeTable& T, uint32_t n_apps, const gf_app* d_apps, gf_result* d_results,
-                     uint32_t* d_exec_nodes, uint32_t* d_scratch, uint64_t half, int32_t* d_failed, ScanStats* d_stats,
-                     const int32_t* guard, hipStream_t stream) {
-    const size_t lds = fifo_v2_lds_bytes(P.lds_slots_v2, T.n_chunks);
-    constexpr int NW = 16;
-    return with_value<true, false>(T.d_identity != 0, [&](auto ID) {
-        return launch_one_workgroup(fit_fifo_chain_kernel<ALGO, NW, ID>, NW, lds, stream, T, P.lds_slots_v2, n_apps, d_apps,
-                                    d_results, d_exec_nodes, d_scratch, half, d_failed, d_stats, guard);
-    });
-}
-
-template <int ALGO>
-hipError_t launch_solo(const FifoPlan& P, const NodeTable& T, const NarrowTable& NT, uint32_t n_apps, NApp* d_napps,
-                       const int32_t* d_wide_needed, gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch,
-                       uint64_t half, int32_t* d_failed, const ChainCkpt& ck, const SoloFused& F, ScanStats* d_stats,
-                       hipStream_t stream) {
-    const size_t lds = fifo_solo_lds_bytes(P.lds_slots_solo, T.n_chunks);
-    constexpr int NW = kSoloWaves;  // wavefront 0 walks the chain; all of them share the prologue, the checkpoints and the epilogue
-    const bool resident = P.lds_slots_solo >= T.n_slots;
-    return with_value<true, false>(d_stats != nullptr, [&](auto PR) {
-        return with_value<true, false>(resident, [&](auto RE) {
-            return launch_one_workgroup(fit_fifo_solo_kernel<ALGO, NW, PR, RE>, NW, lds, stream, T, NT, P.lds_slots_solo, n_apps,
-                                        d_napps, d_wide_needed, d_results, d_exec_nodes, d_scratch, half, d_failed, ck, F, d_stats);
-        });
-    });
-}
-
-template <int ALGO>
-hipError_t launch_fifo_algo(const FifoPlan& P, const NodeTable& T, const NarrowTable& NT, uint32_t n_apps,
-                            const gf_app* d_apps, NApp* d_napps, int32_t* d_wide_needed, gf_result* d_results,
-                            uint32_t* d_exec_nodes, uint32_t* d_scratch, uint64_t half, uint64_t heads_lo, int32_t* d_failed,
-                            const ChainCkpt& ck, const ChainIo& io, ScanStats* d_stats, hipStream_t stream) {
+hipError_t launch_fifo_algo(const FifoPlan& P, const ChainTables& X, const ChainBatch& B, uint64_t heads_lo) {
+    const NodeTable& T = X.table;
+    const ChainIo& io = B.io;
     hipError_t e = hipSuccess;
     const int32_t* guard = nullptr;
     // run heads of the tightly-pack fast path: "no head here"
-    const bool heads = P.narrow && ALGO == GF_ALGO_TIGHTLY_PACK && half > 1 + heads_lo;
+    const bool heads = P.narrow && ALGO == GF_ALGO_TIGHTLY_PACK && B.half > 1 + heads_lo;
+    uint32_t* const fill_dst = heads ? B.d_scratch + heads_lo : nullptr;
+    const size_t fill_words = heads ? (size_t)(B.half - 1 - heads_lo) : 0;
     // The solo kernel is its own first kernel when the whole table lives in LDS, the host has proven every request's scaled
     // form (no wide twin) and nothing but a plain table copy was left to the prologue.
     SoloFused F{};
@@ -2085,44 +2058,63 @@ hipError_t launch_fifo_algo(const FifoPlan& P, const NodeTable& T, const NarrowT
                     : 0;
     if (F.enabled) {
         F.apps_src = io.apps_src;
-        F.apps_dst = const_cast<gf_app*>(d_apps);
+        F.apps_dst = const_cast<gf_app*>(B.d_apps);
         F.table_src = io.copy_words[0] ? reinterpret_cast<const int32_t*>(io.copy_src[0]) : nullptr;
-        for (int j = 0; j < 3; ++j) F.unit[j] = NT.unit[j];
-        F.fill_dst = heads ? d_scratch + heads_lo : nullptr;
-        F.fill_words = heads ? (size_t)(half - 1 - heads_lo) : 0;
+        for (int j = 0; j < 3; ++j) F.unit[j] = X.ntable.unit[j];
+        F.fill_dst = fill_dst;
+        F.fill_words = fill_words;
         F.wide_clear = io.wide_clear;
     } else {
-        e = launch_chain_prologue(io, n_apps, d_apps, P.narrow ? d_napps : nullptr, NT.unit, d_wide_needed,
-                                  heads ? d_scratch + heads_lo : nullptr, heads ? (size_t)(half - 1 - heads_lo) : 0, stream);
+        e = launch_chain_prologue(io, B.n_apps, B.d_apps, P.narrow ? B.d_napps : nullptr, X.ntable.unit, B.d_wide_needed, fill_dst,
+                                  fill_words, B.stream);
         if (e != hipSuccess) return e;
     }
     if (P.narrow) {
-        guard = d_wide_needed;
-        e = launch_solo<ALGO>(P, T, NT, n_apps, d_napps, d_wide_needed, d_results, d_exec_nodes, d_scratch, half, d_failed, ck,
-                              F, d_stats, stream);
+        guard = B.d_wide_needed;
+        constexpr int NW = kSoloWaves;  // wavefront 0 walks the chain; all of them share the prologue, the checkpoints and the epilogue
+        e = with_value<true, false>(B.d_stats != nullptr, [&](auto PR) {
+            return with_value<true, false>(P.lds_slots_solo >= T.n_slots, [&](auto RE) {  // the whole table in LDS
+                return launch_one_workgroup(fit_fifo_solo_kernel<ALGO, NW, PR, RE>, NW, fifo_solo_lds_bytes(P.lds_slots_solo, T.n_chunks),
+                                            B.stream, T, X.ntable, P.lds_slots_solo, B.n_apps, B.d_napps, guard, B.d_results,
+                                            B.d_exec_nodes, B.d_scratch, B.half, B.d_chain_failed_at, B.ckpt, F, B.d_stats);
+            });
+        });
         if (e != hipSuccess) return e;
     }
     if (P.wide) {
-        e = launch_v2<ALGO>(P, T, n_apps, d_apps, d_results, d_exec_nodes, d_scratch, half, d_failed, d_stats, guard, stream);
+        constexpr int NW = 16;
+        e = with_value<true, false>(T.d_identity != 0, [&](auto ID) {
+            return launch_one_workgroup(fit_fifo_chain_kernel<ALGO, NW, ID>, NW, fifo_v2_lds_bytes(P.lds_slots_v2, T.n_chunks), B.stream, T,
+                                        P.lds_slots_v2, B.n_apps, B.d_apps, B.d_results, B.d_exec_nodes, B.d_scratch, B.half,
+                                        B.d_chain_failed_at, B.d_stats, guard);
+        });
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(expand_translate_kernel, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, T.slot_node, n_apps, d_apps, d_results,
-                       d_exec_nodes, d_scratch, chain_out_of(io, d_failed));
+    hipLaunchKernelGGL(expand_translate_kernel, app_grid(B.n_apps), dim3(kWave * kWavesPerBlock), 0, B.stream, T.slot_node, B.n_apps,
+                       B.d_apps, B.d_results, B.d_exec_nodes, B.d_scratch, chain_out_of(io, B.d_chain_failed_at));
+    return hipGetLastError();
+}
+
+// An LDS chain of the zone-aware or minimal-fragmentation packers: the prologue, the chain kernel (`chain`), the translate
+// step with the host outputs.
+template <class Chain>
+hipError_t launch_lds_chain(const ChainTables& X, const ChainBatch& B, Chain chain) {
+    hipError_t e = launch_chain_prologue(B.io, B.n_apps, B.d_apps, B.d_napps, X.ntable.unit, B.d_wide_needed, nullptr, 0, B.stream);
+    if (e != hipSuccess) return e;
+    e = chain();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(zoned_translate_kernel, app_grid(B.n_apps), dim3(kWave * kWavesPerBlock), 0, B.stream, X.table.slot_node,
+                       B.n_apps, B.d_apps, B.d_results, B.d_exec_nodes, (const int32_t*)B.d_wide_needed,
+                       chain_out_of(B.io, B.d_chain_failed_at));
     return hipGetLastError();
 }
 }  // namespace
 
-hipError_t launch_fit_fifo(gf_algo algo, const FifoPlan& plan, const NodeTable& table, const NarrowTable& ntable,
-                           uint32_t n_apps, const gf_app* d_apps, NApp* d_napps, int32_t* d_wide_needed,
-                           gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch, uint64_t scratch_half,
-                           uint64_t heads_lo, int32_t* d_chain_failed_at, const ChainCkpt& ckpt, const ChainIo& io,
-                           ScanStats* d_stats, hipStream_t stream) {
-    if (n_apps == 0) return hipSuccess;
+hipError_t launch_fit_fifo(gf_algo algo, const FifoPlan& plan, const ChainTables& tables, const ChainBatch& batch, uint64_t heads_lo) {
+    if (batch.n_apps == 0) return hipSuccess;
     if (!plan.narrow && !plan.wide) return hipErrorInvalidValue;
-    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
-        return launch_fifo_algo<A>(plan, table, ntable, n_apps, d_apps, d_napps, d_wide_needed, d_results, d_exec_nodes, d_scratch,
-                                   scratch_half, heads_lo, d_chain_failed_at, ckpt, io, d_stats, stream);
-    });
+    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(
+        algo, [&](auto A) { return launch_fifo_algo<A>(plan, tables, batch, heads_lo); });
 }
 
 hipError_t launch_fit_zoned(int inner_algo, bool az_aware, bool reserve_execs, const NodeTable& table,
@@ -2194,19 +2186,17 @@ hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const NodeTable
     return az_aware ? fused(TP{}, std::true_type{}) : fused(TP{}, std::false_type{});
 }
 
-hipError_t launch_fit_fifo_generic(int inner_algo, bool zoned, bool az_aware, const NodeTable& table, const ZoneTable& zones,
-                                   const int64_t* d_sched, uint32_t* d_zexec, uint64_t zexec_stride, uint32_t* d_cnt,
-                                   uint32_t n_apps, const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes,
-                                   uint32_t* d_scratch, uint64_t scratch_half, int32_t* d_chain_failed_at,
-                                   const int32_t* d_run_if, hipStream_t stream) {
-    if (n_apps == 0) return hipSuccess;
-    const uint32_t n_cand = zoned ? zones.n_zones + (az_aware ? 1u : 0u) : 1u;
+hipError_t launch_fit_fifo_generic(const GenericChain& chain, const ChainTables& tables, const ChainBatch& B) {
+    if (B.n_apps == 0) return hipSuccess;
+    const int inner_algo = chain.inner_algo;
+    const bool zoned = chain.zoned, az_aware = chain.az_aware;
+    const uint32_t n_cand = zoned ? tables.zones.n_zones + (az_aware ? 1u : 0u) : 1u;
     if (n_cand > 64) return hipErrorInvalidValue;
     const uint32_t n_waves = n_cand < 1 ? 1 : (n_cand > 16 ? 16 : n_cand);
     auto gen = [&](auto A, auto ZO, auto AZ, auto RE) {
-        hipLaunchKernelGGL((fit_fifo_generic_kernel<A, ZO, AZ, RE>), dim3(1), dim3(kWave * n_waves), 0, stream, table, zones, d_sched,
-                           n_apps, d_apps, d_results, d_exec_nodes, d_zexec, zexec_stride, d_scratch, scratch_half, d_cnt,
-                           d_chain_failed_at, d_run_if);
+        hipLaunchKernelGGL((fit_fifo_generic_kernel<A, ZO, AZ, RE>), dim3(1), dim3(kWave * n_waves), 0, B.stream, tables.table,
+                           tables.zones, tables.d_sched, B.n_apps, B.d_apps, B.d_results, B.d_exec_nodes, B.d_zexec, B.half,
+                           B.d_scratch, B.half, chain.d_cnt, B.d_chain_failed_at, chain.d_run_if);
         return hipGetLastError();
     };
     using std::false_type, std::true_type;
@@ -2223,17 +2213,12 @@ size_t fifo_zoned_lds_bytes(uint32_t lds_slots, uint32_t n_chunks, uint32_t n_zo
     return fifo_zoned_fixed_lds(n_chunks, n_zones + 1, (uint32_t)fifo_zoned_waves(n_cand), n_shapes) + 12 * (size_t)lds_slots;
 }
 
-hipError_t launch_fit_fifo_zoned_lds(bool az_aware, const NodeTable& table, const NarrowTable& ntable, const ZoneTable& zones,
-                                     const int64_t* d_sched, uint32_t lds_slots, uint32_t n_shapes, uint32_t n_apps,
-                                     const gf_app* d_apps, NApp* d_napps, int32_t* d_wide_needed, gf_result* d_results,
-                                     uint32_t* d_exec_nodes, uint32_t* d_spill, uint64_t spill_stride,
-                                     int32_t* d_chain_failed_at, const ChainCkpt& ck, const ChainIo& io, ScanStats* d_stats,
-                                     hipStream_t stream) {
-    if (n_apps == 0) return hipSuccess;
+hipError_t launch_fit_fifo_zoned_lds(bool az_aware, uint32_t lds_slots, uint32_t n_shapes, const ChainTables& tables, const ChainBatch& B) {
+    const NodeTable& table = tables.table;
+    const ZoneTable& zones = tables.zones;
+    if (B.n_apps == 0) return hipSuccess;
     if (zones.n_zones + (az_aware ? 1u : 0u) > 16 || !table.d_identity) return hipErrorInvalidValue;
     if (n_shapes == 0 || n_shapes > kZShapes) return hipErrorInvalidValue;
-    hipError_t e = launch_chain_prologue(io, n_apps, d_apps, d_napps, ntable.unit, d_wide_needed, nullptr, 0, stream);
-    if (e != hipSuccess) return e;
     // one wavefront per candidate view; the rest of the workgroup only helps with the prologue and shares every barrier and
     // the per-app control flow, i.e. takes issue slots from the views' wavefronts: no more wavefronts than views need
     const uint32_t n_cand = zones.n_zones + (az_aware ? 1u : 0u);
@@ -2241,19 +2226,18 @@ hipError_t launch_fit_fifo_zoned_lds(bool az_aware, const NodeTable& table, cons
     // ... plus one that expands the winner's placement next to the commit (none left with 16 views)
     const int wg_waves = fifo_zoned_waves(n_cand);
     const bool res = lds_slots >= table.n_slots;  // the whole table in LDS: the global-tail branch of every slot access compiles away
-    e = with_value<true, false>(az_aware, [&](auto AZ) {
-        return with_value<4, 8, 16>(wg_waves, [&](auto NWV) {
-            return with_value<true, false>(res, [&](auto RS) {
-                return launch_one_workgroup(fit_fifo_zoned_lds_kernel<AZ, NWV, RS>, NWV, lds, stream, table, ntable, zones, d_sched,
-                                            lds_slots, n_apps, n_shapes, d_apps, (const NApp*)d_napps, (const int32_t*)d_wide_needed,
-                                            d_results, d_exec_nodes, d_spill, spill_stride, d_chain_failed_at, ck, d_stats);
+    return launch_lds_chain(tables, B, [&] {
+        return with_value<true, false>(az_aware, [&](auto AZ) {
+            return with_value<4, 8, 16>(wg_waves, [&](auto NWV) {
+                return with_value<true, false>(res, [&](auto RS) {
+                    return launch_one_workgroup(fit_fifo_zoned_lds_kernel<AZ, NWV, RS>, NWV, lds, B.stream, table, tables.ntable, zones,
+                                                tables.d_sched, lds_slots, B.n_apps, n_shapes, B.d_apps, (const NApp*)B.d_napps,
+                                                (const int32_t*)B.d_wide_needed, B.d_results, B.d_exec_nodes, B.d_zexec, B.half,
+                                                B.d_chain_failed_at, B.ckpt, B.d_stats);
+                });
             });
         });
     });
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(zoned_translate_kernel, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, table.slot_node,
-                       n_apps, d_apps, d_results, d_exec_nodes, (const int32_t*)d_wide_needed, chain_out_of(io, d_chain_failed_at));
-    return hipGetLastError();
 }
 
 size_t fifo_minfrag_hist_words(uint32_t n_zones, uint32_t n_shapes) {
@@ -2264,20 +2248,16 @@ size_t fifo_minfrag_lds_bytes(uint32_t lds_slots, uint32_t n_chunks, uint32_t n_
     return fifo_minfrag_fixed_lds(n_chunks, n_zones + 1, n_shapes) + 12 * (size_t)lds_slots;
 }
 
-hipError_t launch_fit_fifo_minfrag_lds(bool zoned, const NodeTable& table, const NarrowTable& ntable, const ZoneTable& zones,
-                                       const int64_t* d_sched, uint32_t lds_slots, uint32_t n_shapes, uint32_t n_idx,
-                                       uint32_t n_apps,
-                                       const gf_app* d_apps, NApp* d_napps, int32_t* d_wide_needed, gf_result* d_results,
-                                       uint32_t* d_exec_nodes, uint32_t* d_spill, uint64_t spill_stride,
-                                       int32_t* d_chain_failed_at, int32_t* d_capmat, int32_t* d_hist, const ChainCkpt& ck,
-                                       const ChainIo& io, ScanStats* d_stats, hipStream_t stream) {
-    if (n_apps == 0) return hipSuccess;
+hipError_t launch_fit_fifo_minfrag_lds(const MinfragLdsChain& chain, const ChainTables& tables, const ChainBatch& B) {
+    const NodeTable& table = tables.table;
+    const ZoneTable& zones = tables.zones;
+    const bool zoned = chain.zoned;
+    const uint32_t lds_slots = chain.lds_slots, n_shapes = chain.n_shapes, n_idx = chain.n_idx;
+    if (B.n_apps == 0) return hipSuccess;
     if ((zoned && zones.n_zones > 16) || !table.d_identity || n_shapes == 0 || n_shapes > kZShapes || n_idx > n_shapes)
         return hipErrorInvalidValue;
-    if (d_capmat == nullptr) d_hist = nullptr;  // the histograms are patched together with the matrix
+    int32_t* const d_hist = chain.d_capmat != nullptr ? chain.d_hist : nullptr;  // the histograms are patched together with the matrix
     // (no initialisation of d_hist: the row fill of a shape writes every bin of its histograms and first positions)
-    hipError_t e = launch_chain_prologue(io, n_apps, d_apps, d_napps, ntable.unit, d_wide_needed, nullptr, 0, stream);
-    if (e != hipSuccess) return e;
     const size_t lds = fifo_minfrag_lds_bytes(lds_slots, table.n_chunks, zoned ? zones.n_zones : 0u, n_idx);
     const bool res = lds_slots >= table.n_slots;
     // eight wavefronts (a 256-VGPR budget: no spills) when the candidate views, four patch helpers and the emitter fit, else sixteen
@@ -2285,20 +2265,18 @@ hipError_t launch_fit_fifo_minfrag_lds(bool zoned, const NodeTable& table, const
     // ... and the whole table sits in LDS: on a 100 000-node table the block-cooperative parts (row fills, checkpoint dumps,
     // patches) want the sixteen (measured: 9.7 -> 10.2 ms plain, 15.0 -> 16.6 ms with three zones on eight)
     const bool eight = res && fifo_minfrag_waves(n_cand_mf) == 8u;
-    e = with_value<true, false>(zoned, [&](auto ZO) {
-        return with_value<true, false>(res, [&](auto RS) {
-            return with_value<8, (int)kMfNWmax>(eight ? 8 : (int)kMfNWmax, [&](auto NWV) {
-                return launch_one_workgroup(fit_fifo_minfrag_lds_kernel<ZO, RS, NWV>, NWV, lds, stream, table, ntable, zones, d_sched,
-                                            lds_slots, n_apps, n_shapes, n_idx, d_apps, (const NApp*)d_napps,
-                                            (const int32_t*)d_wide_needed, d_results, d_exec_nodes, d_spill, spill_stride,
-                                            d_chain_failed_at, d_capmat, d_hist, ck, d_stats);
+    return launch_lds_chain(tables, B, [&] {
+        return with_value<true, false>(zoned, [&](auto ZO) {
+            return with_value<true, false>(res, [&](auto RS) {
+                return with_value<8, (int)kMfNWmax>(eight ? 8 : (int)kMfNWmax, [&](auto NWV) {
+                    return launch_one_workgroup(fit_fifo_minfrag_lds_kernel<ZO, RS, NWV>, NWV, lds, B.stream, table, tables.ntable, zones,
+                                                tables.d_sched, lds_slots, B.n_apps, n_shapes, n_idx, B.d_apps, (const NApp*)B.d_napps,
+                                                (const int32_t*)B.d_wide_needed, B.d_results, B.d_exec_nodes, B.d_zexec, B.half,
+                                                B.d_chain_failed_at, chain.d_capmat, d_hist, B.ckpt, B.d_stats);
+                });
             });
         });
     });
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(zoned_translate_kernel, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, table.slot_node,
-                       n_apps, d_apps, d_results, d_exec_nodes, (const int32_t*)d_wide_needed, chain_out_of(io, d_chain_failed_at));
-    return hipGetLastError();
 }
 
 hipError_t launch_avg_efficiency(bool reserve_execs, const NodeTable& table, const EffTables& eff, uint32_t* d_cnt,

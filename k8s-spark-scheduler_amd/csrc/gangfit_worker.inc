@@ -31,10 +31,12 @@
 // 1.37 -> 1.22 us in a long stream, a window of twenty 54.9 -> 51.2 us):
 //   direct     tightly-pack placements leave as write-through stores straight from the run emission (device-resident
 //              destinations: no private slice, no read-back of the wavefront's own stores)
-//   kRecords   the records of all applications a wavefront serves in a ticket (up to eight) in ONE load instruction
+//   records    the records of all applications a wavefront serves in a ticket (up to eight) in ONE load instruction —
+//              superseded by kRecords below, which requests each record when its application is handed out
 //   s_g0       group 0 of the chunk index (the same for every application while the worker lives) read once into LDS
-//   kDynamic   the applications of a ticket that a workgroup serves are HANDED OUT (an LDS counter per round) instead of
-//              belonging to fixed wavefronts: sixteen wavefronts finish a ticket within one application of each other.
+//   kRecords   the applications of a ticket that a workgroup serves are HANDED OUT one by one (an LDS counter per round) instead
+//              of belonging to fixed wavefronts: sixteen wavefronts finish a ticket within one application of each other.  The
+//              minimal-fragmentation instance, at its register budget, keeps the fixed mapping and reads each record uncached.
 // Leaving out the placement and result stores altogether (a measurement build with wrong answers, since retired) was 8 % faster:
 // the stores are not what a ticket waits for.
 // Measured and removed in the same round (profiles/r6c_worker_lds_table_not_kept.txt): the scaled int32 table resident in LDS
@@ -61,11 +63,8 @@ __device__ __forceinline__ void sys_store(unsigned long long* p, unsigned long l
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// A gf_app read around the caches: lanes 0..7 fetch one 8-byte word each, the fields are handed out with v_readlane.
-__device__ __forceinline__ App load_app_uncached(const gf_app* apps, uint32_t a, int lane) {
-    const unsigned long long* p = reinterpret_cast<const unsigned long long*>(apps + a);
-    unsigned long long w = 0;
-    if (lane < 8) w = sys_load(p + lane);
+// The fields of a gf_app from a register that holds the record (lane f < 8 = word f), handed out with v_readlane.
+__device__ __forceinline__ App app_from_lanes(unsigned long long w) {
     App r;
     r.drv0 = (int64_t)read_lane((int64_t)w, 0);
     r.drv1 = (int64_t)read_lane((int64_t)w, 1);
@@ -83,24 +82,12 @@ __device__ __forceinline__ App load_app_uncached(const gf_app* apps, uint32_t a,
     return r;
 }
 
-// The same fields from a register that holds eight records (lane 8 i + f = word f of record i): kRecords.
-__device__ __forceinline__ App app_from_lanes(unsigned long long w, uint32_t i) {
-    const int b = (int)(8u * i);
-    App r;
-    r.drv0 = (int64_t)read_lane((int64_t)w, b + 0);
-    r.drv1 = (int64_t)read_lane((int64_t)w, b + 1);
-    r.drv2 = (int64_t)read_lane((int64_t)w, b + 2);
-    r.exe0 = (int64_t)read_lane((int64_t)w, b + 3);
-    r.exe1 = (int64_t)read_lane((int64_t)w, b + 4);
-    r.exe2 = (int64_t)read_lane((int64_t)w, b + 5);
-    const uint64_t kf = (uint64_t)read_lane((int64_t)w, b + 6);
-    r.k = (int32_t)(uint32_t)kf;
-    r.flags = (uint32_t)(kf >> 32);
-    r.exec_off = (uint64_t)read_lane((int64_t)w, b + 7);
-    r.rcp0 = r.exe0 > 0 ? fast_rcp((double)r.exe0) : 0.0;
-    r.rcp1 = r.exe1 > 0 ? fast_rcp((double)r.exe1) : 0.0;
-    r.rcp2 = r.exe2 > 0 ? fast_rcp((double)r.exe2) : 0.0;
-    return r;
+// A gf_app read around the caches: lanes 0..7 fetch one 8-byte word each.
+__device__ __forceinline__ App load_app_uncached(const gf_app* apps, uint32_t a, int lane) {
+    const unsigned long long* p = reinterpret_cast<const unsigned long long*>(apps + a);
+    unsigned long long w = 0;
+    if (lane < 8) w = sys_load(p + lane);
+    return app_from_lanes(w);
 }
 
 // narrow_magic's multiplier 2 * ceil(2^(30 + l) / e), l = ceil(log2 e), per LANE and without a 64-bit division (one of those is
@@ -192,7 +179,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     constexpr int kInner = kZoned ? (int)GF_ALGO_TIGHTLY_PACK : ALGO;  // the packer of one candidate view
     __shared__ uint32_t s_cnt[8];               // applications the workgroup has finished, per round (recycled every eight rounds)
     __shared__ uint32_t s_round[kWorkerWaves];  // rounds each wavefront has finished
-    __shared__ unsigned long long s_next[8];    // (round << 32) | applications of that round handed out so far (kDynamic)
+    __shared__ unsigned long long s_next[8];    // (round << 32) | applications of that round handed out so far (kRecords)
     // group 0 of the chunk index: lane l = chunk l (maxima x 3, dcand, xcand)
     __shared__ unsigned long long s_g0[5][kWave];
     // NARROW (tightly-pack): a wavefront decides an application in the snapshot's scaled int32 domain (NarrowView, NarrowApp:
@@ -317,14 +304,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         const bool ok = lane >= 6 || (lane == 0 ? w == tt + 1ull : (w >> 48) == worker_tag(tt));
         return __ballot(ok) == ~0ull;
     };
-    // lane 8 i + f: word f of the record of this wavefront's i-th application behind a0 (up to eight records in one instruction)
-    auto load_records = [&](const gf_app* apps_, uint32_t n_apps_, uint32_t a0) {
-        const uint32_t ai = a0 + (uint32_t)(lane >> 3) * app_stride;
-        unsigned long long r = 0;
-        if (ai < n_apps_) r = sys_load(reinterpret_cast<const unsigned long long*>(apps_ + ai) + (lane & 7));
-        return r;
-    };
-    // kDynamic: the next application of round r of this workgroup (its i-th: wave-uniform).  The counter word carries the round
+    // kRecords: the next application of round r of this workgroup (its i-th: wave-uniform).  The counter word carries the round
     // it counts for: the first wavefront to arrive in a round turns the word over (compare-and-swap), nobody ever resets it.
     auto grab = [&](uint32_t r) {
         uint32_t got = 0;
@@ -360,8 +340,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             __builtin_amdgcn_s_sleep(4);
         }
     };
-    constexpr bool kDynamic = kRecords;
-    uint32_t i_cur = 0;  // kDynamic: the application grabbed for the start of this round (with its record in wrec), if grabbed_cur
+    uint32_t i_cur = 0;  // kRecords: the application grabbed for the start of this round (with its record in wrec), if grabbed_cur
     bool grabbed_cur = false;
     unsigned long long w_cur = 0;
     bool have_cur = false;
@@ -372,8 +351,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             have_cur = true;
         }
     }
-    unsigned long long wrec = 0;  // the records of this round (kRecords)
-    bool recs_loaded = false;
+    unsigned long long wrec = 0;  // the record of the application in hand (kRecords)
     uint32_t round = 0;
     for (;;) {
         // ---- the ticket: brought along by the launch, requested a round ago, or probed for now
@@ -391,7 +369,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                 if (!quit_seen) __builtin_amdgcn_s_sleep(16);
             }
             if (gone) break;  // every round this wavefront finished has been counted when it finished
-            recs_loaded = false;
         }
         // (a ticket's pointers name global memory — device or mapped pinned host memory —: said so, or every access through
         //  them is a flat instruction that counts against both wait counters)
@@ -413,17 +390,15 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         // the count words are recycled every kCountSlots rounds: not before every wavefront of the workgroup has left the round
         // that used this one (it practically never waits: the wavefronts serve the same tickets at the same pace)
         round_guard(round);
-        // kDynamic: the workgroup's applications of this ticket are i = 0 .. total - 1, application (i mod 16) of row (i div 16)
+        // kRecords: the workgroup's applications of this ticket are i = 0 .. total - 1, application (i mod 16) of row (i div 16)
         const uint32_t f0 = bsr * kWorkerWaves;
         const uint32_t total = f0 < n_apps ? ((n_apps - 1u - f0) / app_stride + 1u) * kWorkerWaves : 0u;
         auto app_index = [&](uint32_t i) { return f0 + (i % (uint32_t)kWorkerWaves) + (i / (uint32_t)kWorkerWaves) * app_stride; };
-        if constexpr (kDynamic) {
+        if constexpr (kRecords) {
             if (!grabbed_cur) {
                 i_cur = grab(round);
                 if (i_cur < total && app_index(i_cur) < n_apps) wrec = load_record(apps, app_index(i_cur));
             }
-        } else {
-            if (kRecords && !recs_loaded && first_app < n_apps) wrec = load_records(apps, n_apps, first_app);
         }
         // the set's next ticket, for the end of this round
         // (Measured and removed, profiles/r6i_worker_mailbox_not_kept.txt: ONE wavefront per workgroup asking device memory and
@@ -438,10 +413,10 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         // through; a destination in pinned host memory keeps the private slice and the coalesced copy-out (lone dwords over
         // the host link cost more than the read-back)
         const bool direct = ALGO == GF_ALGO_TIGHTLY_PACK && ((w5 >> 32) & 1ull) == 0;
-        uint32_t mine = 0, it = 0;
-        for (uint32_t a = kDynamic ? app_index(i_cur) : first_app; kDynamic ? i_cur < total : a < n_apps;
-             a = kDynamic ? a : a + app_stride) {
-            if constexpr (kDynamic) {
+        uint32_t mine = 0;
+        for (uint32_t a = kRecords ? app_index(i_cur) : first_app; kRecords ? i_cur < total : a < n_apps;
+             a = kRecords ? a : a + app_stride) {
+            if constexpr (kRecords) {
                 if (a >= n_apps) {  // (the last row is ragged)
                     i_cur = grab(round);
                     a = app_index(i_cur);
@@ -481,15 +456,8 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                 g0.m2 = (int64_t)s_g0[2][lane];
                 g0.dcand = s_g0[3][lane];
                 g0.xcand = s_g0[4][lane];
-                if constexpr (kDynamic) {
-                    app = app_from_lanes(wrec, 0);
-                } else if constexpr (kRecords) {
-                    if (it == 8u) {  // more than eight applications per wavefront and ticket: the next eight records
-                        wrec = load_records(apps, n_apps, a);
-                        it = 0;
-                    }
-                    app = app_from_lanes(wrec, it);
-                    ++it;
+                if constexpr (kRecords) {
+                    app = app_from_lanes(wrec);
                 } else {
                     app = load_app_uncached(apps, a, lane);  // (waits for its load: everything issued before it has returned)
                 }
@@ -528,7 +496,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                                    __HIP_MEMORY_SCOPE_SYSTEM);
             }
             ++mine;
-            if constexpr (kDynamic) {  // the next application of this round, whoever's it would have been
+            if constexpr (kRecords) {  // the next application of this round, whoever's it would have been
                 i_cur = grab(round);
                 a = app_index(i_cur);
                 if (i_cur < total && a < n_apps) wrec = load_record(apps, a);
@@ -540,7 +508,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         const bool have_next = words_valid(w_next, t_next);
         unsigned long long wrec_next = 0;
         uint32_t i_next = 0;
-        if (kDynamic && have_next) {  // the first application of the next round and its record, before this round's stores are drained
+        if (kRecords && have_next) {  // the first application of the next round and its record, before this round's stores are drained
             round_guard(round + 1u);
             const uint32_t f0n = ((bs + round + 1u) % W.blocks_per_set) * kWorkerWaves;
             const gf_app* apps_n = (const gf_app*)reinterpret_cast<glb_app*>((uint64_t)read_lane((int64_t)w_next, 1) & kPtrMask);
@@ -549,11 +517,6 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             i_next = grab(round + 1u);
             const uint32_t a_n = f0n + (i_next % (uint32_t)kWorkerWaves) + (i_next / (uint32_t)kWorkerWaves) * app_stride;
             if (i_next < total_n && a_n < n_apps_n) wrec_next = load_record(apps_n, a_n);
-        } else if (kRecords && have_next) {
-            const uint32_t first_app_n = ((bs + round + 1u) % W.blocks_per_set) * kWorkerWaves + (wave + round + 1u) % (uint32_t)kWorkerWaves;
-            const gf_app* apps_n = (const gf_app*)reinterpret_cast<glb_app*>((uint64_t)read_lane((int64_t)w_next, 1) & kPtrMask);
-            const uint32_t n_apps_n = (uint32_t)((uint64_t)read_lane((int64_t)w_next, 5) & 0xFFFFFFFFull);
-            if (first_app_n < n_apps_n) wrec_next = load_records(apps_n, n_apps_n, first_app_n);
         }
         // this round's stores acknowledged (and the next records in registers) before the round is counted
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -592,9 +555,8 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         w_cur = w_next;
         have_cur = have_next;
         wrec = wrec_next;
-        recs_loaded = have_next;
         i_cur = i_next;
-        grabbed_cur = kDynamic && have_next;
+        grabbed_cur = kRecords && have_next;
     }
     if (lane == 0) __hip_atomic_store(&s_round[wave], kRoundGone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // never in anybody's way
 }

@@ -1,5 +1,7 @@
-// gangfit_api_snapshot.cpp — the snapshot side of the C ABI: gf_snapshot_set / gf_zones_set / gf_orders_set (host-built slot tables), the resident
-// cluster columns and usage sums, gf_snapshot_build* (reservation replay + metadata + priority sort + slot tables on the device).
+// gangfit_api_snapshot.cpp — the snapshot side of the C ABI.  gf_snapshot_set / gf_zones_set record the snapshot; gf_orders_set plans
+// and fills the slot layout on the host (gangfit_slot_layout.h: pure code), uploads it and commits it through install_layout — the
+// one place a layout becomes current, shared with the on-device finalize of gf_snapshot_build*.  Then the resident cluster columns
+// and usage sums, and gf_snapshot_build* (reservation replay + metadata + priority sort, slot tables on the device or the host).
 #include "gangfit_ctx.h"
 
 using namespace gfapi;
@@ -28,6 +30,62 @@ int materialize_host(gf_ctx* ctx) {
 }
 
 }  // namespace gfapi
+
+namespace {
+
+// A call every device of a multi-device context repeats (each keeps the same resident data): the sub-contexts in order, under the
+// group's lock; the first failure stops the round and its error becomes the group's.  A failure past the first device leaves
+// the devices apart: `poison` (usage_ok, cl_over_ok or none) is then cleared on every one of them.
+template <class Call>
+int each_device(gf_ctx* g, bool gf_ctx::*poison, Call call) {
+    std::lock_guard<std::recursive_mutex> glock(g->mu);
+    for (size_t i = 0; i < g->group.size(); ++i) {
+        const int rc = call(g->group[i], i == 0);
+        if (rc == GF_OK) continue;
+        g->err = g->group[i]->err;
+        if (i > 0 && poison != nullptr)
+            for (gf_ctx* sub : g->group) sub->*poison = false;
+        return rc;
+    }
+    return GF_OK;
+}
+
+// Reserve the device buffer (never left NULL) and copy n elements from pinned memory behind the stream.
+template <typename T>
+hipError_t upload(DeviceBuf<T>& d, const T* src, size_t n, hipStream_t st) {
+    const hipError_t e = d.reserve(n + 1);
+    if (e != hipSuccess || n == 0) return e;
+    return hipMemcpyAsync(d.ptr, src, n * sizeof(T), hipMemcpyHostToDevice, st);
+}
+
+// The one place a layout becomes current: gf_orders_set's host-built tables and the on-device finalize both end here.
+void install_layout(gf_ctx* ctx, LayoutFacts&& f) {
+    ctx->n_x = f.n_x;
+    ctx->n_d = f.n_d;
+    ctx->n_slots = f.n_slots;
+    ctx->n_chunks = f.n_chunks;
+    ctx->merged = f.merged;
+    ctx->d_identity = f.identity;
+    ctx->narrow_ok = f.narrow_ok;
+    for (int j = 0; j < 3; ++j) {
+        ctx->unit[j] = f.unit[j];
+        ctx->nmax[j] = f.nmax[j];
+    }
+    ctx->n_g = f.n_g;
+    ctx->n_gpad = f.n_gpad;
+    ctx->g_prefix = std::move(f.g_prefix);
+    ctx->n_zones = f.n_zones;
+    ctx->zstride = f.zstride;
+    ctx->zd_row0 = f.zd_row0;
+    ctx->zspan_ok = f.zspan_ok;
+    ctx->host_stale = f.host_stale;
+    if (!f.host_stale) ctx->h_node_slot = std::move(f.node_slot);  // else materialize_host fetches it on demand
+    ctx->have_orders = true;
+    ctx->work_valid = false;
+    ++ctx->snap_epoch;  // drops the chain cache
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -114,385 +172,77 @@ int gf_orders_set(gf_ctx* ctx, const uint32_t* driver_order, uint32_t n_d, const
     if ((n_d > 0 && !driver_order) || (n_x > 0 && !exec_order))
         return fail(ctx, GF_ERR_INVALID, "order arrays must not be NULL");
     GF_HIP(ctx, hipSetDevice(ctx->device));
-    const uint32_t n_nodes = ctx->n_nodes;
-    std::vector<uint32_t>& node_slot = ctx->h_node_slot;
-    node_slot.assign(n_nodes, GF_NO_NODE);
-    // ---- positions of the known nodes in the two orders.  Unknown names (index >= n_nodes) never host anything
-    //      (binpack.go:68, pack_tightly.go:51, distribute_evenly.go:59) and a repeated driver candidate can only repeat
-    //      the failure of its first occurrence, so both are dropped from the slot space without changing any result.
-    std::vector<uint32_t> xpos(n_nodes, GF_NO_NODE), dpos(n_nodes, GF_NO_NODE);
-    std::vector<uint32_t> xs, ds;
-    xs.reserve(n_x);
-    ds.reserve(n_d);
-    for (uint32_t i = 0; i < n_x; ++i) {
-        const uint32_t n = exec_order[i];
-        if (n >= n_nodes) continue;
-        if (xpos[n] != GF_NO_NODE)
-            return fail(ctx, GF_ERR_INVALID, "node %u appears twice in the executor priority order", n);
-        xpos[n] = (uint32_t)xs.size();
-        xs.push_back(n);
+    // ---- plan: nothing of the context changes before the layout has been accepted
+    LayoutInput in;
+    in.n_nodes = ctx->n_nodes;
+    for (int j = 0; j < 3; ++j) {
+        in.avail[j] = ctx->avail[j].data();
+        in.sched[j] = ctx->have_sched ? ctx->sched[j].data() : nullptr;
     }
-    bool d_has_unknown_or_dup = false;
-    for (uint32_t i = 0; i < n_d; ++i) {
-        const uint32_t n = driver_order[i];
-        if (n >= n_nodes || dpos[n] != GF_NO_NODE) {
-            d_has_unknown_or_dup = true;
-            continue;
-        }
-        dpos[n] = (uint32_t)ds.size();
-        ds.push_back(n);
+    in.zone = ctx->zone.empty() ? nullptr : ctx->zone.data();
+    in.driver_order = driver_order;
+    in.n_d = n_d;
+    in.exec_order = exec_order;
+    in.n_x = n_x;
+    in.force_general_layout = ctx->force_general_layout;
+    in.sparse_gpu = ctx->sparse_gpu;
+    LayoutPlan plan = plan_layout(in);
+    if (plan.code != GF_OK) return fail(ctx, plan.code, "%s", plan.error.c_str());
+    const LayoutSizes& z = plan.sizes;
+    LayoutFacts& f = plan.facts;
+    // ---- reserve the pinned staging, fill it
+    GF_HIP(ctx, ctx->h_table.reserve(z.table + z.sched));
+    GF_HIP(ctx, ctx->h_index.reserve(z.index + z.zspan + 1));
+    GF_HIP(ctx, ctx->h_masks.reserve(z.masks));
+    GF_HIP(ctx, ctx->h_cmax.reserve(z.cmax));
+    GF_HIP(ctx, ctx->h_ntable.reserve(z.ntable));
+    GF_HIP(ctx, ctx->h_gtab.reserve(z.gtab));
+    GF_HIP(ctx, ctx->h_gidx.reserve(z.gidx));
+    GF_HIP(ctx, ctx->h_zmasks.reserve(z.zmasks + z.gmask + 1));
+    LayoutTables t;
+    t.table = ctx->h_table.ptr;
+    t.sched = t.table + z.table;
+    t.index = ctx->h_index.ptr;
+    t.zspan = t.index + z.index;
+    t.masks = ctx->h_masks.ptr;
+    t.cmax = ctx->h_cmax.ptr;
+    t.ntable = ctx->h_ntable.ptr;
+    t.gtab = ctx->h_gtab.ptr;
+    t.gidx = ctx->h_gidx.ptr;
+    t.zmasks = ctx->h_zmasks.ptr;
+    t.gmask = t.zmasks + z.zmasks;
+    fill_layout(in, plan, t);
+    // ---- upload
+    hipStream_t st = ctx->stream;
+    const size_t S = f.n_slots, C = f.n_chunks, G = f.n_gpad;
+    GF_HIP(ctx, gf_wait_stream(st));  // nothing in flight may still read the old tables
+    if (f.narrow_ok) {
+        GF_HIP(ctx, upload(ctx->d_nsnap, t.ntable, 3 * S, st));
+        GF_HIP(ctx, ctx->d_nwork.reserve(3 * S));
+        GF_HIP(ctx, upload(ctx->d_ncmax, t.ntable + 3 * S, 3 * C, st));
     }
-    (void)d_has_unknown_or_dup;
-    // ---- merged layout: one order that has both (cleaned) orders as subsequences, if it exists
-    std::vector<uint32_t> merged;
-    std::vector<uint8_t> mflags;  // bit 0: executor candidate, bit 1: driver candidate
-    bool mergeable = !ctx->force_general_layout;
-    if (mergeable) {
-        merged.reserve(xs.size() + ds.size());
-        size_t i = 0, j = 0;
-        while (i < ds.size() || j < xs.size()) {
-            if (i < ds.size() && j < xs.size() && ds[i] == xs[j]) {
-                merged.push_back(ds[i]);
-                mflags.push_back(3);
-                ++i;
-                ++j;
-            } else if (i < ds.size() && xpos[ds[i]] == GF_NO_NODE) {
-                merged.push_back(ds[i++]);
-                mflags.push_back(2);
-            } else if (j < xs.size() && dpos[xs[j]] == GF_NO_NODE) {
-                merged.push_back(xs[j++]);
-                mflags.push_back(1);
-            } else {  // two nodes present in both orders, in opposite relative order
-                mergeable = false;
-                break;
-            }
-        }
+    GF_HIP(ctx, upload(ctx->d_cmax, t.cmax, 3 * C, st));
+    GF_HIP(ctx, upload(ctx->d_masks, t.masks, 2 * C, st));
+    GF_HIP(ctx, upload(ctx->d_snap, t.table, 3 * S, st));
+    GF_HIP(ctx, ctx->d_work.reserve(3 * S));
+    GF_HIP(ctx, upload(ctx->d_slot_node, t.index, S, st));
+    GF_HIP(ctx, upload(ctx->d_dslot, t.index + S, f.n_d, st));
+    GF_HIP(ctx, upload(ctx->d_node_slot, t.index + S + f.n_d, in.n_nodes, st));
+    if (f.n_g != 0) {
+        GF_HIP(ctx, upload(ctx->d_gtab, t.gtab, 3 * G, st));
+        GF_HIP(ctx, upload(ctx->d_gcmax, t.gtab + 3 * G, 3 * (G / 64), st));
+        GF_HIP(ctx, upload(ctx->d_gidx, t.gidx, z.gidx, st));
+        GF_HIP(ctx, upload(ctx->d_gmask, t.gmask, z.gmask, st));
     }
-    uint32_t n_slots, n_x_slots, n_d_pos;
-    if (mergeable) {
-        n_x_slots = n_d_pos = (uint32_t)merged.size();
-        const uint64_t n_slots64 = (uint64_t)merged.size() + 1;
-        if (n_slots64 >= GF_NO_NODE) return fail(ctx, GF_ERR_INVALID, "order vectors too long");
-        n_slots = (uint32_t)n_slots64;
-        for (uint32_t sl = 0; sl < merged.size(); ++sl) node_slot[merged[sl]] = sl;
-    } else {
-        // general layout: executor order (with its unknown names, which stay empty slots), then driver-only nodes
-        for (uint32_t i = 0; i < n_x; ++i)
-            if (exec_order[i] < n_nodes) node_slot[exec_order[i]] = i;
-        uint32_t extra = 0;
-        for (uint32_t i = 0; i < n_d; ++i) {
-            const uint32_t n = driver_order[i];
-            if (n < n_nodes && node_slot[n] == GF_NO_NODE) node_slot[n] = n_x + extra++;
-        }
-        const uint64_t n_slots64 = (uint64_t)n_x + extra + 1;
-        if (n_slots64 >= GF_NO_NODE) return fail(ctx, GF_ERR_INVALID, "order vectors too long");
-        n_slots = (uint32_t)n_slots64;
-        n_x_slots = n_x;
-        n_d_pos = n_d;
-    }
-    const uint32_t sentinel = n_slots - 1;
-    const uint32_t n_chunks = (n_slots + 63) / 64;
-
-    GF_HIP(ctx, ctx->h_table.reserve(3 * (size_t)n_slots));
-    GF_HIP(ctx, ctx->h_index.reserve((size_t)n_slots + n_d_pos + n_nodes + 1));
-    GF_HIP(ctx, ctx->h_masks.reserve(2 * (size_t)n_chunks));
-    int64_t* tcpu = ctx->h_table.ptr;
-    int64_t* tmem = tcpu + n_slots;
-    int64_t* tgpu = tmem + n_slots;
-    uint32_t* slot_node = ctx->h_index.ptr;
-    uint32_t* dslot = slot_node + n_slots;
-    uint32_t* nslot = dslot + n_d_pos;
-    uint64_t* xmask = ctx->h_masks.ptr;
-    uint64_t* dmask = xmask + n_chunks;
-    for (uint32_t s = 0; s < n_slots; ++s) {
-        tcpu[s] = tmem[s] = tgpu[s] = kSentinelAvail;
-        slot_node[s] = GF_NO_NODE;
-    }
-    for (uint32_t c = 0; c < n_chunks; ++c) xmask[c] = dmask[c] = 0;
-    for (uint32_t n = 0; n < n_nodes; ++n) {
-        const uint32_t s = node_slot[n];
-        nslot[n] = s;
-        if (s == GF_NO_NODE) continue;
-        slot_node[s] = n;
-        tcpu[s] = ctx->avail[0][n];
-        tmem[s] = ctx->avail[1][n];
-        tgpu[s] = ctx->avail[2][n];
-    }
-    bool identity = true;
-    if (mergeable) {
-        for (uint32_t s = 0; s < merged.size(); ++s) {
-            dslot[s] = s;
-            if (mflags[s] & 1) xmask[s >> 6] |= 1ull << (s & 63);
-            if (mflags[s] & 2) dmask[s >> 6] |= 1ull << (s & 63);
-        }
-    } else {
-        for (uint32_t i = 0; i < n_d; ++i) {
-            const uint32_t n = driver_order[i];
-            dslot[i] = n < n_nodes ? node_slot[n] : sentinel;
-        }
-        identity = false;
-        for (uint32_t i = 0; i < n_x; ++i)
-            if (exec_order[i] < n_nodes) xmask[i >> 6] |= 1ull << (i & 63);
-        for (uint32_t c = 0; c < n_chunks; ++c) dmask[c] = ~0ull;  // not consulted: positions go through dslot[]
-    }
-    ctx->d_identity = identity;
-
-    // chunk-maxima index over all slots (see NodeTable::cmax)
-    GF_HIP(ctx, ctx->h_cmax.reserve(3 * (size_t)n_chunks));
-    {
-        const int64_t* cols[3] = {tcpu, tmem, tgpu};
-        for (int j = 0; j < 3; ++j)
-            for (uint32_t c = 0; c < n_chunks; ++c) {
-                int64_t m = INT64_MIN;
-                const uint32_t hi = (c + 1) * 64 < n_slots ? (c + 1) * 64 : n_slots;
-                for (uint32_t s2 = c * 64; s2 < hi; ++s2) m = cols[j][s2] > m ? cols[j][s2] : m;
-                ctx->h_cmax.ptr[(size_t)j * n_chunks + c] = m;
-            }
-    }
-    // narrow form: unit[j] = gcd of dimension j over the real slots; scaled magnitudes must stay below 2^30
-    {
-        const int64_t* cols[3] = {tcpu, tmem, tgpu};
-        bool ok = true;
-        for (int j = 0; j < 3; ++j) {
-            uint64_t g = 0;
-            for (uint32_t s2 = 0; s2 + 1 < n_slots; ++s2) {
-                if (slot_node[s2] == GF_NO_NODE) continue;
-                uint64_t v = (uint64_t)(cols[j][s2] < 0 ? -cols[j][s2] : cols[j][s2]);
-                while (v) {  // Euclid
-                    const uint64_t t = g % v;
-                    g = v;
-                    v = t;
-                }
-                if (g == 1) break;
-            }
-            ctx->unit[j] = g ? (int64_t)g : 1;
-        }
-        GF_HIP(ctx, ctx->h_ntable.reserve(3 * (size_t)n_slots + 3 * (size_t)n_chunks));
-        int32_t* nt = ctx->h_ntable.ptr;
-        int32_t* ncm = nt + 3 * (size_t)n_slots;
-        for (int j = 0; j < 3 && ok; ++j) {
-            ctx->nmax[j] = 0;
-            for (uint32_t c = 0; c < n_chunks; ++c) ncm[(size_t)j * n_chunks + c] = INT32_MIN;
-            for (uint32_t s2 = 0; s2 < n_slots; ++s2) {
-                int32_t v32 = INT32_MIN / 2;  // sentinel / empty slot: never fits, never hosts
-                if (s2 + 1 < n_slots && slot_node[s2] != GF_NO_NODE) {
-                    const int64_t q = cols[j][s2] / ctx->unit[j];
-                    if (q >= (INT64_C(1) << 30) || q <= -(INT64_C(1) << 30)) {
-                        ok = false;
-                        break;
-                    }
-                    v32 = (int32_t)q;
-                    const int64_t mag = q < 0 ? -q : q;
-                    if (mag > ctx->nmax[j]) ctx->nmax[j] = mag;
-                }
-                nt[(size_t)j * n_slots + s2] = v32;
-                int32_t& m = ncm[(size_t)j * n_chunks + (s2 >> 6)];
-                m = v32 > m ? v32 : m;
-            }
-        }
-        ctx->narrow_ok = ok;
-    }
-    GF_HIP(ctx, gf_wait_stream(ctx->stream));  // nothing in flight may still read the old tables
-    if (ctx->narrow_ok) {
-        GF_HIP(ctx, ctx->d_nsnap.reserve(3 * (size_t)n_slots));
-        GF_HIP(ctx, ctx->d_nwork.reserve(3 * (size_t)n_slots));
-        GF_HIP(ctx, ctx->d_ncmax.reserve(3 * (size_t)n_chunks));
-        GF_HIP(ctx, hipMemcpyAsync(ctx->d_nsnap.ptr, ctx->h_ntable.ptr, 3 * (size_t)n_slots * sizeof(int32_t),
-                                   hipMemcpyHostToDevice, ctx->stream));
-        GF_HIP(ctx, hipMemcpyAsync(ctx->d_ncmax.ptr, ctx->h_ntable.ptr + 3 * (size_t)n_slots,
-                                   3 * (size_t)n_chunks * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    }
-    GF_HIP(ctx, ctx->d_cmax.reserve(3 * (size_t)n_chunks));
-    GF_HIP(ctx, hipMemcpyAsync(ctx->d_cmax.ptr, ctx->h_cmax.ptr, 3 * (size_t)n_chunks * sizeof(int64_t),
-                               hipMemcpyHostToDevice, ctx->stream));
-    ctx->n_chunks = n_chunks;
-    GF_HIP(ctx, ctx->d_masks.reserve(2 * (size_t)n_chunks));
-    GF_HIP(ctx, hipMemcpyAsync(ctx->d_masks.ptr, ctx->h_masks.ptr, 2 * (size_t)n_chunks * sizeof(uint64_t),
-                               hipMemcpyHostToDevice, ctx->stream));
-    GF_HIP(ctx, ctx->d_snap.reserve(3 * (size_t)n_slots));
-    GF_HIP(ctx, ctx->d_work.reserve(3 * (size_t)n_slots));
-    GF_HIP(ctx, ctx->d_slot_node.reserve(n_slots));
-    GF_HIP(ctx, ctx->d_dslot.reserve(n_d_pos + 1));
-    GF_HIP(ctx, ctx->d_node_slot.reserve(n_nodes + 1));
-    GF_HIP(ctx, hipMemcpyAsync(ctx->d_snap.ptr, tcpu, 3 * (size_t)n_slots * sizeof(int64_t), hipMemcpyHostToDevice,
-                               ctx->stream));
-    GF_HIP(ctx, hipMemcpyAsync(ctx->d_slot_node.ptr, slot_node, (size_t)n_slots * sizeof(uint32_t),
-                               hipMemcpyHostToDevice, ctx->stream));
-    if (n_d_pos)
-        GF_HIP(ctx, hipMemcpyAsync(ctx->d_dslot.ptr, dslot, (size_t)n_d_pos * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                   ctx->stream));
-    if (n_nodes)
-        GF_HIP(ctx, hipMemcpyAsync(ctx->d_node_slot.ptr, nslot, (size_t)n_nodes * sizeof(uint32_t),
-                                   hipMemcpyHostToDevice, ctx->stream));
-    // ---- sparse gpu view (gangfit::SparseTable): the executor candidates with a free gpu as a compact table of their own,
-    //      when they are a minority of the order (merged layout only: the independent kernel's fast path)
-    ctx->n_g = ctx->n_gpad = 0;
-    ctx->g_prefix.clear();
-    if (mergeable && ctx->sparse_gpu) {
-        uint32_t n_g = 0;
-        for (uint32_t s2 = 0; s2 < merged.size(); ++s2)
-            if ((mflags[s2] & 1) && tgpu[s2] > 0) ++n_g;
-        if (n_g > 0 && (uint64_t)n_g * 4 <= merged.size()) {
-            const uint32_t n_gpad = (n_g + 63u) / 64u * 64u, gch = n_gpad / 64u;
-            GF_HIP(ctx, ctx->h_gtab.reserve(3 * (size_t)n_gpad + 3 * (size_t)gch));
-            GF_HIP(ctx, ctx->h_gidx.reserve(2 * (size_t)n_gpad + n_slots));
-            int64_t* g0 = ctx->h_gtab.ptr;
-            int64_t* gmax = g0 + 3 * (size_t)n_gpad;
-            uint32_t* gnode = ctx->h_gidx.ptr;
-            uint32_t* gsub = gnode + n_gpad;
-            uint32_t* gslot = gsub + n_slots;  // sub-slot -> slot (SparseTable::slot_of_sub; the padding names the sentinel slot)
-            for (uint32_t i = 0; i < 3 * n_gpad; ++i) g0[i] = kSentinelAvail;
-            for (uint32_t i = 0; i < n_gpad; ++i) gnode[i] = GF_NO_NODE;
-            for (uint32_t i = 0; i < n_gpad; ++i) gslot[i] = n_slots - 1u;
-            for (uint32_t s2 = 0; s2 < n_slots; ++s2) gsub[s2] = GF_NO_NODE;
-            uint32_t k = 0;
-            ctx->g_prefix.assign((size_t)n_slots / 64u + 2u, n_g);
-            for (uint32_t s2 = 0; s2 < merged.size(); ++s2) {
-                if ((s2 & 63u) == 0u) ctx->g_prefix[s2 >> 6] = k;
-                if ((mflags[s2] & 1) && tgpu[s2] > 0) {
-                    g0[k] = tcpu[s2];
-                    g0[n_gpad + k] = tmem[s2];
-                    g0[2 * (size_t)n_gpad + k] = tgpu[s2];
-                    gnode[k] = slot_node[s2];
-                    gslot[k] = s2;
-                    gsub[s2] = k++;
-                }
-            }
-            for (int j = 0; j < 3; ++j)
-                for (uint32_t c = 0; c < gch; ++c) {
-                    int64_t m = INT64_MIN;
-                    for (uint32_t i = c * 64; i < (c + 1) * 64; ++i) m = g0[(size_t)j * n_gpad + i] > m ? g0[(size_t)j * n_gpad + i] : m;
-                    gmax[(size_t)j * gch + c] = m;
-                }
-            GF_HIP(ctx, ctx->d_gtab.reserve(3 * (size_t)n_gpad));
-            GF_HIP(ctx, ctx->d_gcmax.reserve(3 * (size_t)gch));
-            GF_HIP(ctx, ctx->d_gidx.reserve(2 * (size_t)n_gpad + n_slots));
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_gtab.ptr, g0, 3 * (size_t)n_gpad * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_gcmax.ptr, gmax, 3 * (size_t)gch * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_gidx.ptr, gnode, (2 * (size_t)n_gpad + n_slots) * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                       ctx->stream));
-            // (the candidate words of the view — all sub-slots, then one row per zone of the evaluation list — follow the zone views below)
-            ctx->n_g = n_g;
-            ctx->n_gpad = n_gpad;
-        }
-    }
-    // ---- SchedulableResources in slot order (efficiencies); empty slots read 0
-    GF_HIP(ctx, ctx->d_sched.reserve(3 * (size_t)n_slots));
-    if (ctx->have_sched) {
-        // h_table is free again only after the snapshot copy above has completed
-        GF_HIP(ctx, gf_wait_stream(ctx->stream));
-        for (int j = 0; j < 3; ++j)
-            for (uint32_t s2 = 0; s2 < n_slots; ++s2)
-                ctx->h_table.ptr[(size_t)j * n_slots + s2] = slot_node[s2] == GF_NO_NODE ? 0 : ctx->sched[j][slot_node[s2]];
-        GF_HIP(ctx, hipMemcpyAsync(ctx->d_sched.ptr, ctx->h_table.ptr, 3 * (size_t)n_slots * sizeof(int64_t),
-                                   hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        GF_HIP(ctx, hipMemsetAsync(ctx->d_sched.ptr, 0, 3 * (size_t)n_slots * sizeof(int64_t), ctx->stream));
-    }
-    // ---- zone views (single_az.go:23-72): evaluation list = zones in order of first appearance in the driver order
-    //      that own at least one executor candidate; per zone, candidate masks over the same slot table
-    {
-        auto zone_of = [&](uint32_t n) { return ctx->zone.empty() ? 0u : ctx->zone[n]; };
-        std::vector<uint32_t> zlist;
-        for (uint32_t n : ds) {
-            const uint32_t z = zone_of(n);
-            bool seen = false;
-            for (uint32_t q : zlist) seen = seen || q == z;
-            if (!seen) zlist.push_back(z);
-        }
-        std::vector<uint32_t> eval;
-        for (uint32_t z : zlist) {
-            bool has_x = false;
-            for (uint32_t n : xs)
-                if (zone_of(n) == z) {
-                    has_x = true;
-                    break;
-                }
-            if (has_x) eval.push_back(z);
-        }
-        const uint32_t d_words = (n_d_pos + 63) / 64;
-        const uint32_t zstride = n_chunks > d_words ? n_chunks : d_words;
-        const uint32_t nz = (uint32_t)eval.size();
-        GF_HIP(ctx, ctx->h_zmasks.reserve(2 * (size_t)nz * zstride + 1));
-        GF_HIP(ctx, ctx->d_zmasks.reserve(2 * (size_t)nz * zstride + 1));
-        uint64_t* zx = ctx->h_zmasks.ptr;
-        uint64_t* zd = zx + (size_t)nz * zstride;
-        for (size_t i = 0; i < 2 * (size_t)nz * zstride; ++i) zx[i] = 0;
-        for (uint32_t zi = 0; zi < nz; ++zi) {
-            const uint32_t z = eval[zi];
-            uint64_t* rx = zx + (size_t)zi * zstride;
-            uint64_t* rd = zd + (size_t)zi * zstride;
-            if (mergeable) {
-                for (uint32_t s2 = 0; s2 < merged.size(); ++s2) {
-                    if (zone_of(merged[s2]) != z) continue;
-                    if (mflags[s2] & 1) rx[s2 >> 6] |= 1ull << (s2 & 63);
-                    if (mflags[s2] & 2) rd[s2 >> 6] |= 1ull << (s2 & 63);
-                }
-            } else {
-                for (uint32_t i = 0; i < n_x; ++i)
-                    if (exec_order[i] < n_nodes && zone_of(exec_order[i]) == z) rx[i >> 6] |= 1ull << (i & 63);
-                for (uint32_t i = 0; i < n_d; ++i)  // by driver POSITION (Orders::dpos_mask)
-                    if (driver_order[i] < n_nodes && zone_of(driver_order[i]) == z) rd[i >> 6] |= 1ull << (i & 63);
-            }
-        }
-        if (nz)
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_zmasks.ptr, zx, 2 * (size_t)nz * zstride * sizeof(uint64_t),
-                                       hipMemcpyHostToDevice, ctx->stream));
-        ctx->n_zones = nz;
-        ctx->zstride = zstride;
-        ctx->zd_row0 = nz;
-        // each zone's chunk span on the merged order (node-range shards skip the zones outside their range: gangfit_shard.inc)
-        std::vector<uint32_t> span(4 * (size_t)nz + 4, 0);
-        for (uint32_t zi = 0; zi < nz && mergeable; ++zi) {
-            uint32_t lo = n_chunks, hi = 0;
-            for (uint32_t c = 0; c < n_chunks; ++c)
-                if (zx[(size_t)zi * zstride + c] | zd[(size_t)zi * zstride + c]) {
-                    lo = c < lo ? c : lo;
-                    hi = c + 1;
-                }
-            span[4 * (size_t)zi] = lo < hi ? lo : 0;
-            span[4 * (size_t)zi + 1] = hi;
-        }
-        if (ctx->n_g != 0) {  // SparseTable::xmask (row 0: every sub-slot) and ::zmask (row 1 + zi: the sub-slots of zone eval[zi])
-            const uint32_t gch = ctx->n_gpad / 64u;
-            const uint32_t* gnode = ctx->h_gidx.ptr;
-            std::vector<uint64_t> gm((size_t)gch * (1u + nz), 0);
-            for (uint32_t i = 0; i < ctx->n_g; ++i) {
-                gm[i >> 6] |= 1ull << (i & 63);
-                const uint32_t z = zone_of(gnode[i]);
-                for (uint32_t zi = 0; zi < nz; ++zi)
-                    if (eval[zi] == z) gm[(size_t)gch * (1u + zi) + (i >> 6)] |= 1ull << (i & 63);
-            }
-            for (uint32_t zi = 0; zi < nz; ++zi) {  // ... and its span on the compact gpu table
-                uint32_t lo = gch, hi = 0;
-                for (uint32_t c = 0; c < gch; ++c)
-                    if (gm[(size_t)gch * (1u + zi) + c]) {
-                        lo = c < lo ? c : lo;
-                        hi = c + 1;
-                    }
-                span[4 * (size_t)zi + 2] = lo < hi ? lo : 0;
-                span[4 * (size_t)zi + 3] = hi;
-            }
-            GF_HIP(ctx, ctx->d_gmask.reserve(gm.size()));
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_gmask.ptr, gm.data(), gm.size() * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-            GF_HIP(ctx, gf_wait_stream(ctx->stream));  // gm is a local
-        }
-        ctx->zspan_ok = false;
-        if (mergeable && nz) {
-            GF_HIP(ctx, ctx->d_zspan.reserve(span.size()));
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_zspan.ptr, span.data(), span.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            GF_HIP(ctx, gf_wait_stream(ctx->stream));  // span is a local
-            ctx->zspan_ok = true;
-        }
-    }
-    GF_HIP(ctx, gf_wait_stream(ctx->stream));
-    ctx->n_x = n_x_slots;
-    ctx->n_d = n_d_pos;
-    ctx->n_slots = n_slots;
-    ctx->merged = mergeable;
-    ctx->have_orders = true;
-    ctx->work_valid = false;
-    ++ctx->snap_epoch;
+    GF_HIP(ctx, ctx->d_sched.reserve(3 * S));
+    if (z.sched != 0)
+        GF_HIP(ctx, upload(ctx->d_sched, t.sched, z.sched, st));
+    else
+        GF_HIP(ctx, hipMemsetAsync(ctx->d_sched.ptr, 0, 3 * S * sizeof(int64_t), st));
+    GF_HIP(ctx, upload(ctx->d_zmasks, t.zmasks, z.zmasks, st));
+    GF_HIP(ctx, upload(ctx->d_zspan, t.zspan, z.zspan, st));
+    GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays and the staging are free again
+    install_layout(ctx, std::move(f));
     return GF_OK;
 }
 
@@ -610,22 +360,12 @@ int gf_usage_reset(gf_ctx* ctx) {
 
 int gf_usage_apply(gf_ctx* ctx, uint32_t n_entries, const uint32_t* res_node, const int64_t* res_cpu_milli,
                    const int64_t* res_mem_bytes, const int64_t* res_gpu, int sign) {
-    if (ctx != nullptr && !ctx->group.empty()) {
-        // every device keeps the same sums; an update that reaches some devices and fails on another leaves them apart:
-        // the resident usage is then unusable everywhere until gf_usage_reset
-        gf_ctx* const g = ctx;
-        std::lock_guard<std::recursive_mutex> glock(g->mu);
-        for (size_t i = 0; i < g->group.size(); ++i) {
-            const int rc = gf_usage_apply(g->group[i], n_entries, res_node, res_cpu_milli, res_mem_bytes, res_gpu, sign);
-            if (rc != GF_OK) {
-                g->err = g->group[i]->err;
-                if (i > 0)
-                    for (gf_ctx* sub : g->group) sub->usage_ok = false;
-                return rc;
-            }
-        }
-        return GF_OK;
-    }
+    // every device keeps the same sums; an update that reaches some devices and fails on another leaves them apart:
+    // the resident usage is then unusable everywhere until gf_usage_reset
+    if (ctx != nullptr && !ctx->group.empty())
+        return each_device(ctx, &gf_ctx::usage_ok, [&](gf_ctx* sub, bool) {
+            return gf_usage_apply(sub, n_entries, res_node, res_cpu_milli, res_mem_bytes, res_gpu, sign);
+        });
     if (!ctx) return GF_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     GF_NOT_ON_A_VIEW(ctx);
@@ -683,22 +423,12 @@ int gf_usage_apply(gf_ctx* ctx, uint32_t n_entries, const uint32_t* res_node, co
 
 int gf_overhead_update(gf_ctx* ctx, uint32_t n_rows, const uint32_t* node, const int64_t* over_cpu_milli, const int64_t* over_mem_bytes,
                        const int64_t* over_gpu) {
-    if (ctx != nullptr && !ctx->group.empty()) {
-        // every device keeps the same columns; an update that reaches some devices and fails on another leaves them apart:
-        // the resident cluster is then unusable everywhere until gf_cluster_set (the shape of usage_ok in gf_usage_apply)
-        gf_ctx* const g = ctx;
-        std::lock_guard<std::recursive_mutex> glock(g->mu);
-        for (size_t i = 0; i < g->group.size(); ++i) {
-            const int rc = gf_overhead_update(g->group[i], n_rows, node, over_cpu_milli, over_mem_bytes, over_gpu);
-            if (rc != GF_OK) {
-                g->err = g->group[i]->err;
-                if (i > 0)
-                    for (gf_ctx* sub : g->group) sub->cl_over_ok = false;
-                return rc;
-            }
-        }
-        return GF_OK;
-    }
+    // every device keeps the same columns; an update that reaches some devices and fails on another leaves them apart:
+    // the resident cluster is then unusable everywhere until gf_cluster_set
+    if (ctx != nullptr && !ctx->group.empty())
+        return each_device(ctx, &gf_ctx::cl_over_ok, [&](gf_ctx* sub, bool) {
+            return gf_overhead_update(sub, n_rows, node, over_cpu_milli, over_mem_bytes, over_gpu);
+        });
     if (!ctx) return GF_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     GF_NOT_ON_A_VIEW(ctx);
@@ -754,34 +484,295 @@ int gf_overhead_update(gf_ctx* ctx, uint32_t n_rows, const uint32_t* node, const
     return GF_OK;
 }
 
-int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_node, const int64_t* res_cpu_milli,
-                               const int64_t* res_mem_bytes, const int64_t* res_gpu, const uint32_t* node_flags,
-                               const uint32_t* driver_label_rank, const uint32_t* exec_label_rank,
-                               uint32_t* driver_order_out, uint32_t* n_d_out, uint32_t* exec_order_out, uint32_t* n_x_out) {
-    if (ctx != nullptr && !ctx->group.empty()) {  // the caller's order lists come from the first device only
-        gf_ctx* const g = ctx;
-        std::lock_guard<std::recursive_mutex> glock(g->mu);
-        for (size_t i = 0; i < g->group.size(); ++i) {
-            const bool first = i == 0;
-            const int rc = gf_snapshot_build_resident(g->group[i], n_res, res_node, res_cpu_milli, res_mem_bytes, res_gpu, node_flags,
-                                                      driver_label_rank, exec_label_rank, first ? driver_order_out : nullptr,
-                                                      first ? n_d_out : nullptr, first ? exec_order_out : nullptr,
-                                                      first ? n_x_out : nullptr);
-            if (rc != GF_OK) {
-                g->err = g->group[i]->err;
-                return rc;
-            }
-        }
-        return GF_OK;
+}  // extern "C"
+
+namespace {
+
+// Where gf_snapshot_build_resident hands back the two candidate lists; every pointer may be NULL.
+struct OrderOuts {
+    uint32_t* driver_order;
+    uint32_t* n_d;
+    uint32_t* exec_order;
+    uint32_t* n_x;
+    bool any() const { return driver_order || n_d || exec_order || n_x; }
+    void counts(uint32_t nd, uint32_t nx) const {
+        if (n_d) *n_d = nd;
+        if (n_x) *n_x = nx;
     }
+};
+
+// The two candidate lists (nodesorting.go:47-63) from the sorted permutation and the node flags: written to the outputs that are
+// not NULL; returns the two counts through nd / nx.
+void candidate_lists(const uint32_t* perm, size_t n, const uint32_t* flags, uint32_t* drivers, uint32_t* execs, uint32_t* nd,
+                     uint32_t* nx) {
+    *nd = *nx = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const uint32_t node = perm[i], fl = flags[node];
+        if (fl & GF_NODE_DRIVER_CANDIDATE) {
+            if (drivers) drivers[*nd] = node;
+            ++*nd;
+        }
+        if (!(fl & GF_NODE_UNSCHEDULABLE) && (fl & GF_NODE_READY)) {
+            if (execs) execs[*nx] = node;
+            ++*nx;
+        }
+    }
+}
+
+// The reservation columns of one build: ranges, and the per-node sums (usage + overhead) must stay below 2^62 — the device
+// accumulates in 64 bits and would wrap silently.  Coarse bound first (every entry on one node); only when that fails, the real
+// per-node entry counts.
+int check_reservations(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_node, const int64_t* const rcols[3]) {
+    const int64_t lim = GF_MAX_ABS_QUANTITY >> 1;
+    int64_t max_res[3] = {0, 0, 0};
+    for (int j = 0; j < 3; ++j)
+        for (uint32_t i = 0; i < n_res; ++i) {
+            if (rcols[j][i] < 0 || rcols[j][i] >= lim) return fail(ctx, GF_ERR_INVALID, "reservation %u out of range", i);
+            if (rcols[j][i] > max_res[j]) max_res[j] = rcols[j][i];
+        }
+    if ((uint64_t)n_res >= (1ull << 32) - 1) return fail(ctx, GF_ERR_INVALID, "too many reservations");
+    auto fits = [&](uint64_t count) {
+        for (int j = 0; j < 3; ++j)
+            if ((unsigned __int128)count * (uint64_t)max_res[j] + (uint64_t)ctx->cl_max_over[j] >= (unsigned __int128)GF_MAX_ABS_QUANTITY)
+                return false;
+        return true;
+    };
+    if (fits(n_res)) return GF_OK;
+    std::vector<uint32_t> cnt(ctx->cl_n, 0);
+    uint32_t most = 0;
+    for (uint32_t i = 0; i < n_res; ++i)
+        if (res_node[i] < ctx->cl_n && ++cnt[res_node[i]] > most) most = cnt[res_node[i]];
+    if (fits(most)) return GF_OK;
+    return fail(ctx, GF_ERR_INVALID, "the reservations of one node (%u entries) can sum past 2^62: not representable", most);
+}
+
+// The device memory of one build: the resident cluster columns and the two scratch buffers, carved.
+struct BuildScratch {
+    int64_t *alloc, *over;                                                         // d_cl_i64
+    uint32_t *zone, *name_rank, *flags;                                            // d_cl_u32
+    int64_t *usage, *avail, *sched, *keys_a, *keys_b, *keys_c, *res_req, *zone_sum;  // d_bi64 ...
+    unsigned long long* gcd_part;  // gcd partials | magnitude partials
+    long long* units;
+    uint32_t *perm_a, *perm_b, *perm_c, *res_node, *zone_order, *zone_rank, *zfirst, *zhasx, *zeval, *scalars;  // d_bu32
+};
+
+int carve_build_scratch(gf_ctx* ctx, size_t R, BuildScratch* out) {
+    const size_t N = ctx->cl_n, Z = ctx->cl_zones;
+    const size_t NCH = (N + 1 + 63) / 64;  // chunks of the slot space (nodes + sentinel)
+    GF_HIP(ctx, ctx->d_bi64.reserve(9 * N + 3 * N + 3 * R + 3 * Z + 6 * NCH + 16));
+    GF_HIP(ctx, ctx->d_bu32.reserve(3 * N + R + 5 * Z + 16));
+    BuildScratch& s = *out;
+    s.alloc = ctx->d_cl_i64.ptr;
+    s.over = s.alloc + 3 * N;
+    s.zone = ctx->d_cl_u32.ptr;
+    s.name_rank = s.zone + N;
+    s.flags = s.name_rank + N;
+    s.usage = ctx->d_bi64.ptr;
+    s.avail = s.usage + 3 * N;
+    s.sched = s.avail + 3 * N;
+    s.keys_a = s.sched + 3 * N;
+    s.keys_b = s.keys_a + N;
+    s.keys_c = s.keys_b + N;
+    s.res_req = s.keys_c + N;
+    s.zone_sum = s.res_req + 3 * R;
+    s.gcd_part = reinterpret_cast<unsigned long long*>(s.zone_sum + 3 * Z);
+    s.units = reinterpret_cast<long long*>(s.gcd_part + 6 * NCH);
+    s.perm_a = ctx->d_bu32.ptr;
+    s.perm_b = s.perm_a + N;
+    s.perm_c = s.perm_b + N;
+    s.res_node = s.perm_c + N;
+    s.zone_order = s.res_node + R;
+    s.zone_rank = s.zone_order + Z;
+    s.zfirst = s.zone_rank + Z;
+    s.zhasx = s.zfirst + Z;
+    s.zeval = s.zhasx + Z;
+    s.scalars = s.zeval + Z;  // 16 words
+    return GF_OK;
+}
+
+gangfit::SnapshotBuild build_args(gf_ctx* ctx, const BuildScratch& s, uint32_t n_res, bool usage_resident) {
+    gangfit::SnapshotBuild b{};
+    b.n_nodes = ctx->cl_n;
+    b.n_res = n_res;
+    b.n_zones = ctx->cl_zones;
+    b.d_alloc = s.alloc;
+    b.d_overhead = ctx->cl_over ? s.over : nullptr;
+    b.d_res_node = s.res_node;
+    b.d_res_req = s.res_req;
+    b.d_zone = s.zone;
+    b.d_name_rank = s.name_rank;
+    b.d_usage = usage_resident ? ctx->d_cl_usage.ptr : s.usage;
+    b.usage_resident = usage_resident;
+    b.d_avail = s.avail;
+    b.d_sched = s.sched;
+    b.d_zone_sum = s.zone_sum;
+    b.d_zone_order = s.zone_order;
+    b.d_zone_rank = s.zone_rank;
+    b.d_perm_a = s.perm_a;
+    b.d_perm_b = s.perm_b;
+    b.d_keys_a = s.keys_a;
+    b.d_keys_b = s.keys_b;
+    b.d_keys_c = s.keys_c;
+    b.d_perm_c = s.perm_c;
+    b.sort_fault = ctx->sort_fault;
+    b.d_zfirst = s.zfirst;  // the finalize step's accumulators start clean with everything else (one clearing launch)
+    b.d_zhasx = s.zhasx;
+    b.zhasx_to_scalars_words = 2 * (size_t)ctx->cl_zones + 16;  // d_zhasx | d_zeval | d_scalars
+    b.d_sort_work = ctx->d_sortwork.ptr;
+    return b;
+}
+
+// The slot tables on the device too: nothing of size O(n_nodes) returns to the host unless the caller asks for the orders.
+int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out) {
+    hipStream_t st = ctx->stream;
+    const uint32_t n = ctx->cl_n, n_slots = n + 1, n_chunks = (n_slots + 63) / 64;
+    const size_t N = n, S = n_slots, C = n_chunks, Z = ctx->cl_zones;
+    GF_HIP(ctx, ctx->d_snap.reserve(3 * S));
+    GF_HIP(ctx, ctx->d_work.reserve(3 * S));
+    GF_HIP(ctx, ctx->d_sched.reserve(3 * S));
+    GF_HIP(ctx, ctx->d_slot_node.reserve(S));
+    GF_HIP(ctx, ctx->d_dslot.reserve(S + 1));
+    GF_HIP(ctx, ctx->d_node_slot.reserve(N + 1));
+    GF_HIP(ctx, ctx->d_cmax.reserve(3 * C));
+    GF_HIP(ctx, ctx->d_masks.reserve(2 * C));
+    GF_HIP(ctx, ctx->d_node_tab.reserve(6 * N + 1));
+    GF_HIP(ctx, ctx->d_zmasks.reserve(2 * Z * C + 1));
+    GF_HIP(ctx, ctx->d_nsnap.reserve(3 * S));
+    GF_HIP(ctx, ctx->d_nwork.reserve(3 * S));
+    GF_HIP(ctx, ctx->d_ncmax.reserve(3 * C));
+    gangfit::SnapshotFinalize f{};
+    f.n_nodes = n;
+    f.n_slots = n_slots;
+    f.n_chunks = n_chunks;
+    f.n_zones = ctx->cl_zones;
+    f.d_avail = s.avail;
+    f.d_sched = s.sched;
+    f.d_perm = s.perm_b;
+    f.d_zone = s.zone;
+    f.d_flags = s.flags;
+    f.d_snap = ctx->d_snap.ptr;
+    f.d_sched_slot = ctx->d_sched.ptr;
+    f.d_slot_node = ctx->d_slot_node.ptr;
+    f.d_node_slot = ctx->d_node_slot.ptr;
+    f.d_dslot = ctx->d_dslot.ptr;
+    f.d_masks = ctx->d_masks.ptr;
+    f.d_cmax = ctx->d_cmax.ptr;
+    f.d_node_tab = ctx->d_node_tab.ptr;
+    f.d_gcd_part = s.gcd_part;
+    f.d_units = s.units;
+    f.d_zfirst = s.zfirst;
+    f.d_zhasx = s.zhasx;
+    f.d_zeval = s.zeval;
+    f.d_scalars = s.scalars;
+    f.d_zmasks = ctx->d_zmasks.ptr;
+    f.d_nsnap = ctx->d_nsnap.ptr;
+    f.d_ncmax = ctx->d_ncmax.ptr;
+    GF_HIP(ctx, ctx->h_bcols.reserve(6 * N + 8));
+    GF_HIP(ctx, ctx->h_border.reserve(N + 16));
+    // everything the host needs back is one range of sixteen words (SnapshotFinalize::d_scalars): the kernels write it into
+    // pinned memory as they produce it (no copy on the stream), or ONE copy where that memory is not mapped to the device
+    uint32_t* h_scalars = ctx->h_border.ptr;
+    if (ctx->h_border.dev != nullptr) {
+        std::memset(h_scalars, 0, 16 * sizeof(uint32_t));
+        f.h_out = ctx->h_border.dev;
+    }
+    GF_HIP(ctx, gangfit::launch_snapshot_finalize(f, ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word(), st));
+    if (f.h_out == nullptr) GF_HIP(ctx, hipMemcpyAsync(h_scalars, s.scalars, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    GF_HIP(ctx, gf_wait_stream(st));
+    if (h_scalars[3] != 0) return fail(ctx, GF_ERR_HIP, "the priority sort's grid barrier gave up (device oversubscribed?)");
+    // ---- the snapshot itself (what gf_snapshot_set + gf_zones_set record on the host path) ...
+    ctx->have_sched = h_scalars[2] == 0;  // a negative schedulable value (overhead above allocatable) disables the efficiencies
+    ctx->n_nodes = n;
+    ctx->have_snapshot = true;
+    ctx->zone = ctx->cl_zone;
+    ctx->eff_nonneg = false;  // nothing compared available with schedulable
+    // ---- ... and its layout: every node has a slot, in the sorted order, and one sentinel
+    LayoutFacts lf;
+    lf.n_slots = n_slots;
+    lf.n_x = lf.n_d = n;
+    lf.n_chunks = n_chunks;
+    lf.merged = lf.identity = true;
+    lf.narrow_ok = h_scalars[1] == 0;
+    for (int j = 0; j < 3; ++j) {  // 3 units, then the 3 largest scaled magnitudes, as pairs of words
+        lf.unit[j] = (int64_t)((uint64_t)h_scalars[4 + 2 * j] | ((uint64_t)h_scalars[5 + 2 * j] << 32));
+        lf.nmax[j] = (int64_t)((uint64_t)h_scalars[10 + 2 * j] | ((uint64_t)h_scalars[11 + 2 * j] << 32));
+    }
+    // n_g = 0: the sparse gpu view is built by gf_orders_set only; the full order serves here
+    lf.n_zones = h_scalars[0];
+    lf.zstride = n_chunks;
+    lf.zd_row0 = ctx->cl_zones;  // the device lays the driver rows behind one row per zone of the cluster
+    lf.zspan_ok = false;         // the zone masks were built on the device: the shards scan every zone over their whole range
+    lf.host_stale = true;
+    install_layout(ctx, std::move(lf));
+    if (out.any()) {  // the two lists, for callers that want them
+        GF_HIP(ctx, hipMemcpyAsync(ctx->h_border.ptr, s.perm_b, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        GF_HIP(ctx, gf_wait_stream(st));
+        uint32_t nd, nx;
+        candidate_lists(ctx->h_border.ptr, N, ctx->cl_flags.data(), out.driver_order, out.exec_order, &nd, &nx);
+        out.counts(nd, nx);
+    }
+    return GF_OK;
+}
+
+// The sorted snapshot returns to the host and is installed through the public setters: the optional stable label re-sorts
+// (nodesorting.go:161-199) can break the merged layout, which only gf_orders_set handles.
+int finalize_on_host(gf_ctx* ctx, const BuildScratch& s, const uint32_t* driver_label_rank, const uint32_t* exec_label_rank,
+                     const OrderOuts& out) {
+    hipStream_t st = ctx->stream;
+    const uint32_t n = ctx->cl_n;
+    const size_t N = n;
+    GF_HIP(ctx, ctx->h_bcols.reserve(6 * N));
+    GF_HIP(ctx, ctx->h_border.reserve(N + 8));
+    GF_HIP(ctx, hipMemcpyAsync(ctx->h_bcols.ptr, s.avail, 6 * N * sizeof(int64_t), hipMemcpyDeviceToHost, st));  // avail | sched
+    GF_HIP(ctx, hipMemcpyAsync(ctx->h_border.ptr, s.perm_b, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    GF_HIP(ctx, hipMemcpyAsync(ctx->h_failed.ptr, ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word(), sizeof(uint32_t),
+                               hipMemcpyDeviceToHost, st));
+    GF_HIP(ctx, gf_wait_stream(st));
+    if (ctx->h_failed.ptr[0] != 0) return fail(ctx, GF_ERR_HIP, "the priority sort's grid barrier gave up (device oversubscribed?)");
+    const int64_t* h_avail = ctx->h_bcols.ptr;
+    const int64_t* h_sched = ctx->h_bcols.ptr + 3 * N;
+    bool sched_ok = true;
+    for (size_t i = 0; i < 3 * N && sched_ok; ++i) sched_ok = h_sched[i] >= 0;
+    std::vector<uint32_t> D(N), X(N);
+    uint32_t nd, nx;
+    candidate_lists(ctx->h_border.ptr, N, ctx->cl_flags.data(), D.data(), X.data(), &nd, &nx);
+    D.resize(nd);
+    X.resize(nx);
+    auto by_rank = [](std::vector<uint32_t>& v, const uint32_t* rank) {
+        std::stable_sort(v.begin(), v.end(), [rank](uint32_t a, uint32_t b) { return rank[a] < rank[b]; });
+    };
+    if (driver_label_rank) by_rank(D, driver_label_rank);
+    if (exec_label_rank) by_rank(X, exec_label_rank);
+    int rc = gf_snapshot_set(ctx, n, h_avail, h_avail + N, h_avail + 2 * N, sched_ok ? h_sched : nullptr,
+                             sched_ok ? h_sched + N : nullptr, sched_ok ? h_sched + 2 * N : nullptr);
+    if (rc != GF_OK) return rc;
+    if (!ctx->cl_zone.empty() && (rc = gf_zones_set(ctx, ctx->cl_zone.data())) != GF_OK) return rc;
+    if ((rc = gf_orders_set(ctx, D.data(), nd, X.data(), nx)) != GF_OK) return rc;
+    out.counts(nd, nx);
+    if (out.driver_order) std::memcpy(out.driver_order, D.data(), D.size() * sizeof(uint32_t));
+    if (out.exec_order) std::memcpy(out.exec_order, X.data(), X.size() * sizeof(uint32_t));
+    return GF_OK;
+}
+
+}  // namespace
+
+extern "C" int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_node, const int64_t* res_cpu_milli,
+                                          const int64_t* res_mem_bytes, const int64_t* res_gpu, const uint32_t* node_flags,
+                                          const uint32_t* driver_label_rank, const uint32_t* exec_label_rank,
+                                          uint32_t* driver_order_out, uint32_t* n_d_out, uint32_t* exec_order_out, uint32_t* n_x_out) {
+    if (ctx != nullptr && !ctx->group.empty())  // the caller's order lists come from the first device only
+        return each_device(ctx, nullptr, [&](gf_ctx* sub, bool first) {
+            return gf_snapshot_build_resident(sub, n_res, res_node, res_cpu_milli, res_mem_bytes, res_gpu, node_flags, driver_label_rank,
+                                              exec_label_rank, first ? driver_order_out : nullptr, first ? n_d_out : nullptr,
+                                              first ? exec_order_out : nullptr, first ? n_x_out : nullptr);
+        });
     if (!ctx) return GF_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     GF_NOT_ON_A_VIEW(ctx);
     InstallGuard install_guard(ctx);
     if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede gf_snapshot_build_resident");
+    const OrderOuts out{driver_order_out, n_d_out, exec_order_out, n_x_out};
     const uint32_t n = ctx->cl_n;
-    const uint32_t n_zones = ctx->cl_zones;
-    const bool with_over = ctx->cl_over;
     const bool usage_resident = n_res == GF_RESIDENT_USAGE;  // the sums gf_usage_apply maintains: no entry travels
     if (usage_resident) n_res = 0;
     if (n_res > 0 && (!res_node || !res_cpu_milli || !res_mem_bytes || !res_gpu))
@@ -796,254 +787,34 @@ int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_
     else
         ctx->cl_flags = ctx->cl_default_flags;
     const uint32_t* const flags_upload = node_flags ? node_flags : (ctx->d_flags_default ? nullptr : ctx->cl_default_flags.data());
-    const uint32_t* const zone_of_node = ctx->cl_zone.empty() ? nullptr : ctx->cl_zone.data();
-    const uint32_t* const flags_host = ctx->cl_flags.data();
-    const int64_t* rcols[3] = {res_cpu_milli, res_mem_bytes, res_gpu};
-    const int64_t lim = GF_MAX_ABS_QUANTITY >> 1;
-    int64_t max_res[3] = {0, 0, 0};
-    for (int j = 0; j < 3; ++j)
-        for (uint32_t i = 0; i < n_res; ++i) {
-            if (rcols[j][i] < 0 || rcols[j][i] >= lim) return fail(ctx, GF_ERR_INVALID, "reservation %u out of range", i);
-            if (rcols[j][i] > max_res[j]) max_res[j] = rcols[j][i];
-        }
-    if ((uint64_t)n_res >= (1ull << 32) - 1) return fail(ctx, GF_ERR_INVALID, "too many reservations");
-    {  // the per-node sums (usage + overhead) must stay below 2^62: the device accumulates in 64 bits and would wrap silently.
-        // Coarse bound first (every entry on one node); only when that fails, the real per-node entry counts.
-        auto fits = [&](uint64_t count) {
-            for (int j = 0; j < 3; ++j)
-                if ((unsigned __int128)count * (uint64_t)max_res[j] + (uint64_t)ctx->cl_max_over[j] >= (unsigned __int128)GF_MAX_ABS_QUANTITY)
-                    return false;
-            return true;
-        };
-        if (!fits(n_res)) {
-            std::vector<uint32_t> cnt(n, 0);
-            uint32_t most = 0;
-            for (uint32_t i = 0; i < n_res; ++i)
-                if (res_node[i] < n && ++cnt[res_node[i]] > most) most = cnt[res_node[i]];
-            if (!fits(most))
-                return fail(ctx, GF_ERR_INVALID, "the reservations of one node (%u entries) can sum past 2^62: not representable", most);
-        }
-    }
+    const int64_t* const rcols[3] = {res_cpu_milli, res_mem_bytes, res_gpu};
+    if (int rc = check_reservations(ctx, n_res, res_node, rcols); rc != GF_OK) return rc;
     if (n == 0) {
         int rc = gf_snapshot_set(ctx, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
         if (rc != GF_OK) return rc;
-        if (n_d_out) *n_d_out = 0;
-        if (n_x_out) *n_x_out = 0;
+        out.counts(0, 0);
         return gf_orders_set(ctx, nullptr, 0, nullptr, 0);
     }
     GF_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    // ---- device buffers (the static columns live in the resident cluster buffers)
-    const size_t N = n, R = n_res, Z = n_zones;
-    const size_t NCH = (N + 1 + 63) / 64;  // chunks of the slot space (nodes + sentinel)
+    const size_t N = n, R = n_res;
     GF_HIP(ctx, gf_wait_stream(st));  // nothing in flight may still read buffers that are about to grow
-    GF_HIP(ctx, ctx->d_bi64.reserve(9 * N + 3 * N + 3 * R + 3 * Z + 6 * NCH + 16));
-    GF_HIP(ctx, ctx->d_bu32.reserve(3 * N + R + 5 * Z + 16));
-    int64_t* d_alloc = ctx->d_cl_i64.ptr;
-    int64_t* d_over = d_alloc + 3 * N;
-    int64_t* d_usage = ctx->d_bi64.ptr;
-    int64_t* d_avail = d_usage + 3 * N;
-    int64_t* d_sched = d_avail + 3 * N;
-    int64_t* d_keys_a = d_sched + 3 * N;
-    int64_t* d_keys_b = d_keys_a + N;
-    int64_t* d_keys_c = d_keys_b + N;
-    int64_t* d_res_req = d_keys_c + N;
-    int64_t* d_zone_sum = d_res_req + 3 * R;
-    uint32_t* d_zone = ctx->d_cl_u32.ptr;
-    uint32_t* d_name_rank = d_zone + N;
-    uint32_t* d_flags = d_name_rank + N;
-    uint32_t* d_perm_a = ctx->d_bu32.ptr;
-    uint32_t* d_perm_b = d_perm_a + N;
-    uint32_t* d_perm_c = d_perm_b + N;
-    uint32_t* d_res_node = d_perm_c + N;
-    uint32_t* d_zone_order = d_res_node + R;
-    uint32_t* d_zone_rank = d_zone_order + Z;
-    uint32_t* d_zfirst = d_zone_rank + Z;
-    uint32_t* d_zhasx = d_zfirst + Z;
-    uint32_t* d_zeval = d_zhasx + Z;
-    uint32_t* d_scalars = d_zeval + Z;  // 4
-    unsigned long long* d_gcd_part = reinterpret_cast<unsigned long long*>(d_zone_sum + 3 * Z);
-    long long* d_units = reinterpret_cast<long long*>(d_gcd_part + 6 * NCH);  // gcd partials | magnitude partials | units
+    BuildScratch s;
+    if (int rc = carve_build_scratch(ctx, R, &s); rc != GF_OK) return rc;
     for (int j = 0; j < 3 && R; ++j)
-        GF_HIP(ctx, hipMemcpyAsync(d_res_req + j * R, rcols[j], R * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (R) GF_HIP(ctx, hipMemcpyAsync(d_res_node, res_node, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        GF_HIP(ctx, hipMemcpyAsync(s.res_req + j * R, rcols[j], R * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    if (R) GF_HIP(ctx, hipMemcpyAsync(s.res_node, res_node, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (flags_upload) {
-        GF_HIP(ctx, hipMemcpyAsync(d_flags, flags_upload, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        GF_HIP(ctx, hipMemcpyAsync(s.flags, flags_upload, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         ctx->d_flags_default = node_flags == nullptr;
     }
-    gangfit::SnapshotBuild b{};
-    b.n_nodes = n;
-    b.n_res = n_res;
-    b.n_zones = n_zones;
-    b.d_alloc = d_alloc;
-    b.d_overhead = with_over ? d_over : nullptr;
-    b.d_res_node = d_res_node;
-    b.d_res_req = d_res_req;
-    b.d_zone = d_zone;
-    b.d_name_rank = d_name_rank;
-    b.d_usage = usage_resident ? ctx->d_cl_usage.ptr : d_usage;
-    b.usage_resident = usage_resident;
-    b.d_avail = d_avail;
-    b.d_sched = d_sched;
-    b.d_zone_sum = d_zone_sum;
-    b.d_zone_order = d_zone_order;
-    b.d_zone_rank = d_zone_rank;
-    b.d_perm_a = d_perm_a;
-    b.d_perm_b = d_perm_b;
-    b.d_keys_a = d_keys_a;
-    b.d_keys_b = d_keys_b;
-    b.d_keys_c = d_keys_c;
-    b.d_perm_c = d_perm_c;
-    b.sort_fault = ctx->sort_fault;
-    b.d_zfirst = d_zfirst;  // the finalize step's accumulators start clean with everything else (one clearing launch)
-    b.d_zhasx = d_zhasx;
-    b.zhasx_to_scalars_words = 2 * Z + 16;  // d_zhasx | d_zeval | d_scalars
     GF_HIP(ctx, ctx->d_sortwork.reserve(gangfit::snapshot_sort_work_words()));
-    b.d_sort_work = ctx->d_sortwork.ptr;
-    GF_HIP(ctx, gangfit::launch_snapshot_build(b, st));
-    if (ctx->snapshot_finalize_on_device && !driver_label_rank && !exec_label_rank) {
-        // ---- the slot tables on the device too: nothing of size O(n_nodes) returns to the host unless the caller asks
-        //      for the orders.  (Label re-sorts can break the merged layout: those go through gf_orders_set below.)
-        const uint32_t n_slots = n + 1, n_chunks = (uint32_t)NCH;
-        GF_HIP(ctx, ctx->d_snap.reserve(3 * (size_t)n_slots));
-        GF_HIP(ctx, ctx->d_work.reserve(3 * (size_t)n_slots));
-        GF_HIP(ctx, ctx->d_sched.reserve(3 * (size_t)n_slots));
-        GF_HIP(ctx, ctx->d_slot_node.reserve(n_slots));
-        GF_HIP(ctx, ctx->d_dslot.reserve((size_t)n_slots + 1));
-        GF_HIP(ctx, ctx->d_node_slot.reserve(N + 1));
-        GF_HIP(ctx, ctx->d_cmax.reserve(3 * (size_t)n_chunks));
-        GF_HIP(ctx, ctx->d_masks.reserve(2 * (size_t)n_chunks));
-        GF_HIP(ctx, ctx->d_node_tab.reserve(6 * N + 1));
-        GF_HIP(ctx, ctx->d_zmasks.reserve(2 * Z * (size_t)n_chunks + 1));
-        GF_HIP(ctx, ctx->d_nsnap.reserve(3 * (size_t)n_slots));
-        GF_HIP(ctx, ctx->d_nwork.reserve(3 * (size_t)n_slots));
-        GF_HIP(ctx, ctx->d_ncmax.reserve(3 * (size_t)n_chunks));
-        gangfit::SnapshotFinalize f{};
-        f.n_nodes = n;
-        f.n_slots = n_slots;
-        f.n_chunks = n_chunks;
-        f.n_zones = n_zones;
-        f.d_avail = d_avail;
-        f.d_sched = d_sched;
-        f.d_perm = d_perm_b;
-        f.d_zone = d_zone;
-        f.d_flags = d_flags;
-        f.d_snap = ctx->d_snap.ptr;
-        f.d_sched_slot = ctx->d_sched.ptr;
-        f.d_slot_node = ctx->d_slot_node.ptr;
-        f.d_node_slot = ctx->d_node_slot.ptr;
-        f.d_dslot = ctx->d_dslot.ptr;
-        f.d_masks = ctx->d_masks.ptr;
-        f.d_cmax = ctx->d_cmax.ptr;
-        f.d_node_tab = ctx->d_node_tab.ptr;
-        f.d_gcd_part = d_gcd_part;
-        f.d_units = d_units;
-        f.d_zfirst = d_zfirst;
-        f.d_zhasx = d_zhasx;
-        f.d_zeval = d_zeval;
-        f.d_scalars = d_scalars;
-        f.d_zmasks = ctx->d_zmasks.ptr;
-        f.d_nsnap = ctx->d_nsnap.ptr;
-        f.d_ncmax = ctx->d_ncmax.ptr;
-        GF_HIP(ctx, ctx->h_bcols.reserve(6 * N + 8));
-        GF_HIP(ctx, ctx->h_border.reserve(N + 16));
-        // everything the host needs back is one range of sixteen words (SnapshotFinalize::d_scalars): the kernels write it into
-        // pinned memory as they produce it (no copy on the stream), or ONE copy where that memory is not mapped to the device
-        uint32_t* h_scalars = ctx->h_border.ptr;
-        if (ctx->h_border.dev != nullptr) {
-            std::memset(h_scalars, 0, 16 * sizeof(uint32_t));
-            f.h_out = ctx->h_border.dev;
-        }
-        GF_HIP(ctx, gangfit::launch_snapshot_finalize(f, ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word(), st));
-        if (f.h_out == nullptr) GF_HIP(ctx, hipMemcpyAsync(h_scalars, d_scalars, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        GF_HIP(ctx, gf_wait_stream(st));
-        if (h_scalars[3] != 0) return fail(ctx, GF_ERR_HIP, "the priority sort's grid barrier gave up (device oversubscribed?)");
-        const uint32_t nz = h_scalars[0];
-        for (int j = 0; j < 3; ++j) {  // 3 units, then the 3 largest scaled magnitudes, as pairs of words
-            ctx->unit[j] = (int64_t)((uint64_t)h_scalars[4 + 2 * j] | ((uint64_t)h_scalars[5 + 2 * j] << 32));
-            ctx->nmax[j] = (int64_t)((uint64_t)h_scalars[10 + 2 * j] | ((uint64_t)h_scalars[11 + 2 * j] << 32));
-        }
-        ctx->narrow_ok = h_scalars[1] == 0;
-        ctx->have_sched = h_scalars[2] == 0;  // a negative schedulable value (overhead above allocatable) disables the efficiencies
-        ctx->n_nodes = n;
-        ctx->have_snapshot = true;
-        ctx->zone.clear();
-        if (zone_of_node) ctx->zone.assign(zone_of_node, zone_of_node + N);
-        ctx->n_x = ctx->n_d = n;
-        ctx->n_g = ctx->n_gpad = 0;  // the sparse gpu view is built by gf_orders_set only; the full order serves here
-        ctx->g_prefix.clear();
-        ctx->n_slots = n_slots;
-        ctx->n_chunks = n_chunks;
-        ctx->d_identity = true;
-        ctx->merged = true;
-        ctx->n_zones = nz;
-        ctx->zstride = n_chunks;
-        ctx->zd_row0 = n_zones;
-        ctx->zspan_ok = false;  // (the zone masks were built on the device: the shards scan every zone over their whole range)
-        ctx->have_orders = true;
-        ctx->work_valid = false;
-        ++ctx->snap_epoch;
-        ctx->host_stale = true;
-        ctx->eff_nonneg = false;
-        if (driver_order_out || exec_order_out || n_d_out || n_x_out) {  // the two lists, for callers that want them
-            GF_HIP(ctx, hipMemcpyAsync(ctx->h_border.ptr, d_perm_b, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            GF_HIP(ctx, gf_wait_stream(st));
-            uint32_t nd = 0, nx = 0;
-            for (size_t i = 0; i < N; ++i) {
-                const uint32_t node = ctx->h_border.ptr[i];
-                const uint32_t fl = flags_host[node];
-                if (fl & GF_NODE_DRIVER_CANDIDATE) {
-                    if (driver_order_out) driver_order_out[nd] = node;
-                    ++nd;
-                }
-                if (!(fl & GF_NODE_UNSCHEDULABLE) && (fl & GF_NODE_READY)) {
-                    if (exec_order_out) exec_order_out[nx] = node;
-                    ++nx;
-                }
-            }
-            if (n_d_out) *n_d_out = nd;
-            if (n_x_out) *n_x_out = nx;
-        }
-        return GF_OK;
-    }
-    GF_HIP(ctx, ctx->h_bcols.reserve(6 * N));
-    GF_HIP(ctx, ctx->h_border.reserve(N + 8));
-    GF_HIP(ctx, hipMemcpyAsync(ctx->h_bcols.ptr, d_avail, 6 * N * sizeof(int64_t), hipMemcpyDeviceToHost, st));  // avail | sched
-    GF_HIP(ctx, hipMemcpyAsync(ctx->h_border.ptr, d_perm_b, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    GF_HIP(ctx, hipMemcpyAsync(ctx->h_failed.ptr, ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word(), sizeof(uint32_t),
-                               hipMemcpyDeviceToHost, st));
-    GF_HIP(ctx, gf_wait_stream(st));
-    if (ctx->h_failed.ptr[0] != 0) return fail(ctx, GF_ERR_HIP, "the priority sort's grid barrier gave up (device oversubscribed?)");
-    // ---- the two candidate lists (nodesorting.go:47-63) and the optional stable label re-sorts (:161-199)
-    const int64_t* h_avail = ctx->h_bcols.ptr;
-    const int64_t* h_sched = ctx->h_bcols.ptr + 3 * N;
-    bool sched_ok = true;
-    for (size_t i = 0; i < 3 * N && sched_ok; ++i) sched_ok = h_sched[i] >= 0;
-    std::vector<uint32_t> D, X;
-    D.reserve(N);
-    X.reserve(N);
-    for (size_t i = 0; i < N; ++i) {
-        const uint32_t node = ctx->h_border.ptr[i];
-        const uint32_t f = flags_host[node];
-        if (f & GF_NODE_DRIVER_CANDIDATE) D.push_back(node);
-        if (!(f & GF_NODE_UNSCHEDULABLE) && (f & GF_NODE_READY)) X.push_back(node);
-    }
-    auto by_rank = [](std::vector<uint32_t>& v, const uint32_t* rank) {
-        std::stable_sort(v.begin(), v.end(), [rank](uint32_t a, uint32_t b) { return rank[a] < rank[b]; });
-    };
-    if (driver_label_rank) by_rank(D, driver_label_rank);
-    if (exec_label_rank) by_rank(X, exec_label_rank);
-    int rc = gf_snapshot_set(ctx, n, h_avail, h_avail + N, h_avail + 2 * N, sched_ok ? h_sched : nullptr,
-                             sched_ok ? h_sched + N : nullptr, sched_ok ? h_sched + 2 * N : nullptr);
-    if (rc != GF_OK) return rc;
-    if (zone_of_node && (rc = gf_zones_set(ctx, zone_of_node)) != GF_OK) return rc;
-    if ((rc = gf_orders_set(ctx, D.data(), (uint32_t)D.size(), X.data(), (uint32_t)X.size())) != GF_OK) return rc;
-    if (n_d_out) *n_d_out = (uint32_t)D.size();
-    if (n_x_out) *n_x_out = (uint32_t)X.size();
-    if (driver_order_out) std::memcpy(driver_order_out, D.data(), D.size() * sizeof(uint32_t));
-    if (exec_order_out) std::memcpy(exec_order_out, X.data(), X.size() * sizeof(uint32_t));
-    return GF_OK;
+    GF_HIP(ctx, gangfit::launch_snapshot_build(build_args(ctx, s, n_res, usage_resident), st));
+    if (ctx->snapshot_finalize_on_device && !driver_label_rank && !exec_label_rank) return finalize_on_device(ctx, s, out);
+    return finalize_on_host(ctx, s, driver_label_rank, exec_label_rank, out);
 }
+
+extern "C" {
 
 int gf_snapshot_get(gf_ctx* ctx, int64_t* avail_out, int64_t* sched_out) {
     GF_DELEGATE(ctx, gf_snapshot_get(ctx, avail_out, sched_out));

@@ -29,14 +29,13 @@
 
 #include "gangfit.h"
 #include "gangfit_device.h"
+#include "gangfit_slot_layout.h"
 
 using gangfit::NodeTable;
 using gangfit::ScanStats;
 
 namespace gfapi {
 
-
-constexpr int64_t kSentinelAvail = -(INT64_C(1) << 62);  // "node is not in nodesSchedulingMetadata"
 
 // Completion waits.  hipStreamSynchronize / hipEventSynchronize park the calling thread and pay an interrupt + wake-up
 // (tens of microseconds) per call — more than a whole 1 000-application batch takes on the device, and a visible part of
@@ -272,8 +271,8 @@ struct gf_ctx {
     PinnedBuf<int64_t> h_cmax;
     uint32_t n_chunks = 0;
     std::vector<uint32_t> h_node_slot;  // kept for gf_residual_get
-    PinnedBuf<int64_t> h_table;
-    PinnedBuf<uint32_t> h_index;
+    PinnedBuf<int64_t> h_table;   // staging: the slot table | the schedulable table
+    PinnedBuf<uint32_t> h_index;  // staging: slot_node | dslot | node_slot | zone spans
     bool work_valid = false;
     bool d_identity = false;
     bool merged = false;       // slot space is the merged order (see NodeTable)
@@ -317,7 +316,7 @@ struct gf_ctx {
     DeviceBuf<int64_t> d_sched;        // 3 * n_slots SchedulableResources in slot order (0 on empty slots)
     DeviceBuf<int64_t> d_node_tab;     // 6 * n_nodes: avail cpu|mem|gpu, sched cpu|mem|gpu by node index
     DeviceBuf<uint64_t> d_zmasks;      // [2][n_zones][zstride]: executor masks, then driver masks
-    PinnedBuf<uint64_t> h_zmasks;
+    PinnedBuf<uint64_t> h_zmasks;      // staging: the zone masks | the candidate words of the sparse gpu view
     uint32_t n_zones = 0, zstride = 0;
     uint32_t zd_row0 = 0;              // row of d_zmasks where the driver masks start (n_zones, or the zone count of a device build)
     // [n_zones][4] the chunks [lo, hi) of the merged order holding each zone's candidates, then the chunks [lo, hi) of the compact gpu

@@ -413,6 +413,35 @@ def test_argument_errors(gf_ctx):
         gf_ctx.set_snapshot([[1 << 62, 1, 0]])
 
 
+def test_refused_orders_leave_the_installed_layout_alone(gf_ctx):
+    """gf_orders_set validates before it commits: a refused call (a node twice in the executor order) leaves decisions, the
+    residual of the last chain and the efficiencies exactly as they were."""
+    rng = np.random.default_rng(130)
+    n = 130
+    avail, D, X, _, _, _ = _random_problem(rng, n, 1, tight_cluster=False, layout="merged")
+    avail = np.abs(avail) + 1
+    sched = avail + rng.integers(0, 50, size=avail.shape)
+    apps = _gpu_apps(rng.integers(0, 9, size=(12, 3)), rng.integers(1, 7, size=(12, 3)), rng.integers(1, 40, size=12))
+    gf_ctx.set_snapshot(avail, sched)
+    gf_ctx.set_orders(D, X)
+
+    def observe():
+        ind = gf_ctx.fit_batch(IND, TIGHT, apps)
+        fifo = gf_ctx.fit_batch(FIFO, TIGHT, apps)
+        return (ind.results, ind.exec_nodes, fifo.results, fifo.exec_nodes, gf_ctx.residual(),
+                gf_ctx.avg_packing_efficiency(TIGHT, apps, ind), gf_ctx.avg_packing_efficiency(TIGHT, apps, fifo))
+
+    before = observe()
+    assert before[0]["has_capacity"].any() and before[2]["has_capacity"].any()
+    assert not np.array_equal(before[4], avail)  # the chain placed something: the residual is not the snapshot
+    with pytest.raises(gangfit.GangfitError) as e:
+        gf_ctx.set_orders(D, np.append(X, X[X < n][0]))
+    assert e.value.code == gangfit._native.GF_ERR_INVALID
+    assert np.array_equal(gf_ctx.residual(), before[4])  # ... of the chain that ran before the refused call
+    for was, now in zip(before, observe()):
+        assert np.array_equal(was, now)
+
+
 def test_recorded_graph_replays_the_same_batches(gf_ctx):
     """gf_graph_begin / end / launch: the recorded *_dev calls replay with the same results as the eager calls."""
     import torch

@@ -313,6 +313,28 @@ int gf_fit_batch(gf_ctx *ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
  * placements go to buffers no other entry point uses, so a call that follows on another stream never meets the tail of this one. */
 int gf_fit_feasible(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app *apps, uint8_t *has_capacity);
 
+/* The same question on the EMPTY cluster, answered next to the installed snapshot instead of in its place — what
+ * UnschedulablePodMarker asks once a minute for every stale pending driver (internal/extender/unschedulablepods.go:132-166: zero
+ * usage, the non-schedulable overhead, every node that matches the driver's required affinity).
+ *   over_*       n_nodes values each, the overhead of this question; all NULL = none
+ *   node_select  nullable, n_nodes bytes: 1 = the node matches the affinity; NULL = every node
+ * has_capacity[a] equals, byte for byte, what gf_fit_feasible(algo) returns on the snapshot gf_snapshot_build would install from the
+ * cluster's allocatable columns and zone ids (gf_cluster_set), these overhead columns, no reservation, and the selected nodes as
+ * driver candidates AND executor candidates (the reference hands nodeNames to both lists there, not the ready / unschedulable
+ * flags).  HasCapacity of an independent decision does not depend on the priority order, and on an empty cluster available equals
+ * schedulable: one order-free pass of cluster_scan_kernel over the resident columns, one wavefront per application — no sort, no slot
+ * layout, no install.  The call leaves untouched: the installed snapshot, zones and orders, all three words of gf_generation, the
+ * chain cache, recorded graphs, the resident usage and overhead, the resident worker, gf_residual_get's table.  Blocking; only
+ * n_apps bytes come back; its device buffers are its own.
+ * Refusals (nothing on the device changes, has_capacity stays untouched): no gf_cluster_set, or a view: GF_ERR_STATE; some but not
+ * all overhead columns NULL, an overhead value outside [0, 2^61), k outside [0, GF_MAX_K]: GF_ERR_INVALID; a zone-aware packer on a
+ * cluster of more than 64 zones, or when chooseBestResult's average could be 0 — an application whose driver asks for neither cpu
+ * nor memory, a node whose overhead exceeds its allocatable in some dimension —: GF_ERR_UNSUPPORTED (the caller installs and asks
+ * gf_fit_feasible, as before).  n_apps == 0 is GF_OK.  A multi-device context answers from its first device. */
+int gf_cluster_fit_feasible(gf_ctx *ctx, gf_algo algo, const int64_t *over_cpu_milli, const int64_t *over_mem_bytes,
+                            const int64_t *over_gpu, const uint8_t *node_select, uint32_t n_apps, const gf_app *apps,
+                            uint8_t *has_capacity);
+
 /* Incremental FIFO chains.  The reference replays every earlier driver on every Filter (internal/extender/resource.go:309-328);
  * with an unchanged snapshot, driver j + 1's chain is driver j's chain plus one application.  gf_fit_batch(GF_MODE_FIFO_CHAIN)
  * therefore keeps the last queue, its results and a checkpoint of the working table every 32 applications (more for tables

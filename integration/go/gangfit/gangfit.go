@@ -715,6 +715,47 @@ func (c *Context) FitFeasibleOnInstalledSnapshot(algo int, apps []App) ([]bool, 
 	return out, nil
 }
 
+// FitFeasibleOnEmptyCluster answers DoesPodExceedClusterCapacity where the UnschedulablePodMarker asks it
+// (internal/extender/unschedulablepods.go:132-166): HasCapacity of every application on the cluster as if nothing ran on it —
+// the allocatable columns and zones of the resident cluster (gf_cluster_set), minus nonSchedulableOverhead (dense cpu | memory |
+// gpu columns in the cluster's node order, nil = none), with the nodes of nodeSelect (one byte per node, nil = every node: the
+// nodes that match the driver's required affinity) as driver and executor candidates.  Unlike FitFeasibleOnInstalledSnapshot
+// nothing is installed (include/gangfit.h, gf_cluster_fit_feasible): the Filter's snapshot, its chain cache and the resident
+// usage stay, and the next Filter resumes.  ErrUnsupported (a zone-aware packer on more than 64 zones, a driver that asks for
+// neither cpu nor memory, an overhead above a node's allocatable): install the empty-cluster snapshot and call
+// FitFeasibleOnInstalledSnapshot, as before.  Unverified here (no Go toolchain); tests/test_gpu_cluster_scan.py drives the C
+// entry point.
+func (c *Context) FitFeasibleOnEmptyCluster(algo int, apps []App, nonSchedulableOverhead [3][]int64, nodeSelect []byte) ([]bool, error) {
+	capps, _, err := flattenApps(apps)
+	if err != nil {
+		return nil, err
+	}
+	if len(apps) == 0 {
+		return nil, nil
+	}
+	var over [3]*C.int64_t
+	if len(nonSchedulableOverhead[0]) > 0 {
+		for j := range over {
+			over[j] = (*C.int64_t)(unsafe.Pointer(&nonSchedulableOverhead[j][0]))
+		}
+	}
+	var sel *C.uint8_t
+	if len(nodeSelect) > 0 {
+		sel = (*C.uint8_t)(unsafe.Pointer(&nodeSelect[0]))
+	}
+	fits := make([]C.uint8_t, len(apps))
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	if rc := C.gf_cluster_fit_feasible(c.ctx, C.gf_algo(algo), over[0], over[1], over[2], sel, C.uint32_t(len(apps)), &capps[0], &fits[0]); rc != C.GF_OK {
+		return nil, c.err(rc)
+	}
+	out := make([]bool, len(apps))
+	for i := range fits {
+		out[i] = fits[i] != 0
+	}
+	return out, nil
+}
+
 // ExecutorFitOnInstalledSnapshot is the node choice of rescheduleExecutor (internal/extender/resource.go:594-673) for a batch
 // of executors against the installed snapshot and executor order: the first-fit loop (:658-662) or, minimalFragmentation = true,
 // rescheduleExecutorWithMinimalFragmentation (:675-703).  zones == nil: no zone step.  Otherwise nodeZone[n] is the id of node

@@ -306,6 +306,11 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->d_cl_i64.release();
     ctx->d_cl_u32.release();
     ctx->d_cl_usage.release();
+    ctx->d_scan_over.release();
+    ctx->d_scan_select.release();
+    ctx->d_scan_out.release();
+    ctx->d_scan_apps.release();
+    ctx->h_scan_out.release();
     ctx->d_delta_i64.release();
     ctx->d_delta_u32.release();
     ctx->d_bi64.release();

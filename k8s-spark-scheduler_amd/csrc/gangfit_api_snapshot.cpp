@@ -309,6 +309,8 @@ int gf_cluster_set(gf_ctx* ctx, uint32_t n_nodes, const int64_t* alloc_cpu_milli
     GF_HIP(ctx, hipMemsetAsync(ctx->d_cl_usage.ptr, 0, (3 * N + 1) * sizeof(int64_t), st));  // a new node set: no usage yet
     for (int j = 0; j < 3; ++j) ctx->usage_total[j] = 0;
     GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays are free again
+    ctx->cl_alloc.resize(3 * N);
+    for (int j = 0; j < 3 && N; ++j) std::copy(cols[j], cols[j] + N, ctx->cl_alloc.begin() + (size_t)j * N);
     ctx->cl_flags.assign(node_flags, node_flags + n);
     ctx->cl_default_flags = ctx->cl_flags;
     ctx->d_flags_default = true;

@@ -6,6 +6,7 @@
 //   gangfit_api_fit.cpp       the launches of every packer, the incremental chain cache, gf_fit_batch*, single executors,
 //                             findNodes, efficiencies
 //   gangfit_api_worker.cpp    the resident worker of the independent batch (gf_worker_*)
+//   gangfit_api_scan.cpp      gf_cluster_fit_feasible: the empty-cluster capacity scan on the resident cluster columns
 //   gangfit_api_group.cpp     node-range sharding: the gf_shard_* steps and the multi-device context (peer stores or RCCL)
 #pragma once
 #include <dlfcn.h>
@@ -357,8 +358,16 @@ struct gf_ctx {
     bool cl_over = false, have_cluster = false;
     int64_t cl_max_over[3] = {0, 0, 0};       // upper bound of every node's overhead (gf_overhead_update only ever raises it)
     bool cl_over_ok = true;                   // false after a gf_overhead_update that reached only some devices: until gf_cluster_set
+    std::vector<int64_t> cl_alloc;            // host copy of the allocatable columns (3n): gf_cluster_fit_feasible compares an overhead with them
     std::vector<uint32_t> cl_row_stamp;       // gf_overhead_update: [node] the call that last named it (a node twice in one call)
     uint32_t cl_row_call = 0;
+
+    // gf_cluster_fit_feasible (gangfit_api_scan.cpp): the call's overhead columns (3n), node selection (n), records and answers.
+    // Its own: no other entry point reads or writes them, so the scan runs next to whatever is installed
+    DeviceBuf<int64_t> d_scan_over;
+    DeviceBuf<uint8_t> d_scan_select, d_scan_out;
+    DeviceBuf<gf_app> d_scan_apps;
+    PinnedBuf<uint8_t> h_scan_out;
 
     // gf_snapshot_build
     DeviceBuf<int64_t> d_bi64;   // alloc | overhead | usage | avail | sched (3n each) | keys_a | keys_b (n each) | res_req (3r) | zone_sum

@@ -498,6 +498,13 @@ hipError_t launch_usage_apply(uint32_t n_entries, uint32_t n_nodes, const uint32
 // before any later build.
 hipError_t launch_overhead_update(uint32_t n_rows, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_rows, int64_t* d_overhead,
                                   hipStream_t stream);
+// The empty-cluster capacity scan (gangfit_scan.inc; gf_cluster_fit_feasible): d_out[a] = HasCapacity of application a on the
+// cluster columns in node-index order — available = d_alloc - d_over (d_over nullable: no overhead), driver and executor
+// candidates = the nodes with d_select[n] != 0 (nullable: every node), nothing reserved.  zoned: the single-AZ answer (some zone
+// fits by itself; d_zone: n_nodes ids below 64) without chooseBestResult's averages — the caller refuses what could make one 0.
+// One wavefront per application; reads nothing of the installed snapshot.
+hipError_t launch_cluster_scan(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
+                               const uint8_t* d_select, uint32_t n_apps, const gf_app* d_apps, uint8_t* d_out, hipStream_t stream);
 // The slot tables of the merged layout built from the device-resident snapshot columns (what gf_orders_set builds on the
 // host): every node gets the slot of its position in the priority order.
 struct SnapshotFinalize {

@@ -1748,6 +1748,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
 #include "gangfit_shard.inc"
 #include "gangfit_executor.inc"
 #include "gangfit_findnodes.inc"
+#include "gangfit_scan.inc"
 
 // ------------------------------------------------------------------------------------------------ self-test
 
@@ -1975,6 +1976,18 @@ hipError_t launch_fit_independent(gf_algo algo, const NodeTable& table, const Sp
         else
             hipLaunchKernelGGL((fit_independent_kernel<A, false>), grid, block, 0, stream, table, gpu_view, n_apps, d_apps,
                                d_results, d_exec_nodes, d_scratch, scratch_half, d_stats);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_cluster_scan(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
+                               const uint8_t* d_select, uint32_t n_apps, const gf_app* d_apps, uint8_t* d_out, hipStream_t stream) {
+    if (n_apps == 0) return hipSuccess;
+    if (d_apps == nullptr || d_out == nullptr || (n_nodes > 0 && (d_alloc == nullptr || (zoned && d_zone == nullptr))))
+        return hipErrorInvalidValue;
+    const ScanArgs args{d_alloc, d_over, d_zone, d_select, n_nodes, n_apps, d_apps, d_out};
+    return with_value<true, false>(zoned, [&](auto Z) {
+        hipLaunchKernelGGL(cluster_scan_kernel<Z>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, args);
         return hipGetLastError();
     });
 }

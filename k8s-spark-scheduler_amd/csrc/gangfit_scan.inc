@@ -1,0 +1,123 @@
+// gangfit_scan.inc — the empty-cluster capacity scan (gf_cluster_fit_feasible; included by gangfit_kernels.hip).
+//
+//   UnschedulablePodMarker.DoesPodExceedClusterCapacity   internal/extender/unschedulablepods.go:132-166
+//
+// The marker asks whether an application would fit the cluster if nothing ran on it: zero usage, the non-schedulable overhead,
+// every node that matches the driver's required affinity as driver AND executor candidate.  HasCapacity of an independent
+// decision does not depend on the priority order (SparkBinPack tries every driver candidate, LIB/binpack/binpack.go:60-87; a
+// packer places K executors iff the clamped capacities sum to K — what the node-range shards rest on, DESIGN 4.4):
+//     feasible  <=>  some selected node d the driver fits on has  S - cap(d) + cap'(d) >= K,
+//     S = sum over the selected nodes of min(cap, K),  cap' = the capacity of d with the driver on it.
+// So the scan reads the columns gf_cluster_set keeps on the device in NODE-INDEX order: no sort, no slot layout, no install.
+// One wavefront per application, 64 nodes per step; capacities through cap3 — negative available quantities, zero request
+// dimensions and K = 0 mean what they mean in every other kernel.
+//
+// The single-AZ packers (LIB/binpack/single_az.go:23-97) ask the same of every zone by itself: (S_z, best delta_z) per zone id
+// in wavefront-private LDS, at most 64 zones.  The caller guarantees what lets chooseBestResult's averages be skipped (available
+// equals schedulable and is nowhere negative, the driver asks for cpu or memory: gf_fit_feasible's `surely_positive`).
+
+constexpr int kScanZones = 64;
+constexpr int32_t kScanNoDriver = INT32_MIN;  // "no fitting driver candidate seen"
+
+struct ScanArgs {
+    const int64_t* alloc;         // 3 * n_nodes: cpu | mem | gpu (gf_cluster_set)
+    const int64_t* over;          // 3 * n_nodes, or nullptr: no overhead
+    const uint32_t* zone;         // n_nodes zone ids below kScanZones (ZONED only)
+    const uint8_t* select;        // n_nodes, or nullptr: every node
+    uint32_t n_nodes;
+    uint32_t n_apps;
+    const gf_app* apps;
+    uint8_t* out;                 // n_apps HasCapacity bytes
+};
+
+struct ScanShared {
+    unsigned long long s[kWavesPerBlock][kScanZones];  // S_z
+    int32_t best[kWavesPerBlock][kScanZones];          // the largest cap' - cap over the zone's fitting driver candidates
+};
+typedef __attribute__((address_space(3))) unsigned long long lds_scan_u64;
+typedef __attribute__((address_space(3))) int32_t lds_scan_i32;
+
+// Sum and maximum over every RUN of lanes that hold the same key (mf_run_heads' runs), left in the run's first lane; `end` = the
+// lane behind this lane's run.  Six steps of doubling reach: a lane takes its neighbour `off` ahead while that one is in the run.
+__device__ __forceinline__ void scan_run_reduce(int32_t& sum, int32_t& mx, int end, int lane) {
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const int32_t s = __shfl_down(sum, off, kWave);
+        const int32_t m = __shfl_down(mx, off, kWave);
+        if (lane + off < end) {
+            sum += s;
+            mx = m > mx ? m : mx;
+        }
+    }
+}
+
+template <bool ZONED>
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void cluster_scan_kernel(ScanArgs A) {
+    __shared__ ScanShared sh;
+    const int lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t a = blockIdx.x * kWavesPerBlock + wave;
+    if (a >= A.n_apps) return;  // (no workgroup barrier below: the LDS rows are private to a wavefront)
+    const App app = load_app(A.apps, a);
+    const int64_t K = app.k;
+    const size_t N = A.n_nodes;
+    lds_scan_u64* const zs = (lds_scan_u64*)&sh.s[wave][0];
+    lds_scan_i32* const zb = (lds_scan_i32*)&sh.best[wave][0];
+    if (ZONED) {
+        zs[lane] = 0ull;
+        zb[lane] = kScanNoDriver;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (the other lanes of this wavefront add to these rows)
+    }
+    int64_t S = 0;                    // (plain) the clamped capacities so far, wave-uniform
+    int32_t best = kScanNoDriver;     // (plain) this lane's best delta so far
+    bool feasible = false;
+    for (uint32_t base = 0; base < A.n_nodes; base += kWave) {
+        const uint32_t n = base + (uint32_t)lane;
+        const bool in = n < A.n_nodes;
+        const bool sel = in && (A.select == nullptr || A.select[n] != 0);
+        int64_t a0 = -1, a1 = -1, a2 = -1;  // (an unselected lane holds nothing and hosts no driver)
+        if (sel) {
+            a0 = A.alloc[n];
+            a1 = A.alloc[N + n];
+            a2 = A.alloc[2 * N + n];
+            if (A.over != nullptr) {
+                a0 -= A.over[n];
+                a1 -= A.over[N + n];
+                a2 -= A.over[2 * N + n];
+            }
+        }
+        const int32_t c0 = sel ? cap3(a0, a1, a2, app) : 0;
+        const bool fits = sel && driver_fits(a0, a1, a2, app);
+        // the same node with the driver on it (binpack.go:73-74: reserved[driverNode] = driverResources)
+        const int32_t delta = fits ? cap3(a0 - app.drv0, a1 - app.drv1, a2 - app.drv2, app) - c0 : kScanNoDriver;
+        if (!ZONED) {
+            S += (int64_t)read_lane(wave_inclusive_scan(c0), kWave - 1);
+            best = delta > best ? delta : best;
+            // S only grows: a candidate that passes against the sum so far passes against the whole
+            if (__ballot(best != kScanNoDriver && S + (int64_t)best >= K) != 0ull) {
+                feasible = true;
+                break;
+            }
+        } else {
+            // equal zone ids are mostly neighbours: a run's first lane speaks for it (one LDS atomic per run, not 64 on one address)
+            const uint32_t z = in ? A.zone[n] : 0u;
+            const uint32_t n_run = mf_run_heads(z, in, lane);
+            const uint64_t heads = __ballot(n_run != 0u) | __ballot(!in);
+            const uint64_t rest = lane == kWave - 1 ? 0ull : heads >> (lane + 1);
+            const int end = rest ? lane + (int)__ffsll((unsigned long long)rest) : kWave;
+            int32_t sum = c0, mx = delta;
+            scan_run_reduce(sum, mx, end, lane);
+            if (n_run != 0u && z < (uint32_t)kScanZones) {
+                if (sum != 0) __hip_atomic_fetch_add(zs + z, (unsigned long long)sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (mx != kScanNoDriver) __hip_atomic_fetch_max(zb + z, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+        }
+    }
+    if (ZONED) {  // lane z answers for zone z (LDS operations of a wavefront execute in order)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        const int64_t sz = (int64_t)zs[lane];
+        const int32_t bz = zb[lane];
+        feasible = __ballot(bz != kScanNoDriver && sz + (int64_t)bz >= K) != 0ull;
+    }
+    if (lane == 0) A.out[a] = feasible ? 1 : 0;
+}

@@ -14,10 +14,11 @@ HOST_LIB_PATH = os.path.join(_PKG_ROOT, "libgangfit_host.so")
 HOST_BENCH_PATH = os.path.join(_PKG_ROOT, "host_bench")  # end-to-end Filter timing through the host mirror
 HOST_TEST_PATH = os.path.join(_PKG_ROOT, "host_test")  # C++ tests of the host mirror (host/tests/host_test.cpp)
 HOST_OVERHEAD_TEST_PATH = os.path.join(_PKG_ROOT, "host_overhead_test")  # ... of its flat route with overhead (host_overhead_test.cpp)
+HOST_CLUSTER_SCAN_TEST_PATH = os.path.join(_PKG_ROOT, "host_cluster_scan_test")  # ... of the resident capacity scan (host_cluster_scan_test.cpp)
 INCLUDE = os.path.join(_REPO_ROOT, "include")
 
 _SOURCES = ["gangfit_kernels.hip", "gangfit_snapshot.hip", "gangfit_api.cpp", "gangfit_api_snapshot.cpp", "gangfit_api_fit.cpp",
-            "gangfit_api_worker.cpp", "gangfit_api_group.cpp"]
+            "gangfit_api_worker.cpp", "gangfit_api_group.cpp", "gangfit_api_scan.cpp"]
 _HEADERS = [os.path.join(CSRC, "gangfit_device.h"), os.path.join(CSRC, "gangfit_slot_layout.h"), os.path.join(INCLUDE, "gangfit.h")]
 
 
@@ -37,7 +38,7 @@ def _stale(target: str, deps) -> bool:
 
 def build_native(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 ... -> k8s-spark-scheduler_amd/libgangfit.so.  The translation units are compiled side by side
-    (one hipcc process each: the two kernel files take most of a minute, the five host files a few seconds), then linked."""
+    (one hipcc process each: the two kernel files take most of a minute, the six host files a few seconds), then linked."""
     srcs = [os.path.join(CSRC, s) for s in _SOURCES]
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + _HEADERS  # .inc files are #included by the .hip
     if force or _stale(LIB_PATH, deps):
@@ -79,6 +80,11 @@ def build_host(force: bool = False) -> str:
     if os.path.exists(over_src) and (force or _stale(HOST_OVERHEAD_TEST_PATH, [over_src, HOST_LIB_PATH] + hdrs)):
         cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, over_src, "-L", _PKG_ROOT,
                "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_OVERHEAD_TEST_PATH]
+        subprocess.check_call(cmd)
+    scan_src = os.path.join(host_dir, "tests", "host_cluster_scan_test.cpp")
+    if os.path.exists(scan_src) and (force or _stale(HOST_CLUSTER_SCAN_TEST_PATH, [scan_src, HOST_LIB_PATH] + hdrs)):
+        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, scan_src, "-L", _PKG_ROOT,
+               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_CLUSTER_SCAN_TEST_PATH]
         subprocess.check_call(cmd)
     bench_src = os.path.join(host_dir, "tests", "host_bench.cpp")
     if os.path.exists(bench_src) and (force or _stale(HOST_BENCH_PATH, [bench_src, HOST_LIB_PATH] + hdrs)):

@@ -276,6 +276,26 @@ class Context:
         self._check(self._lib.gf_fit_feasible(self._h, algo, len(apps), N.ptr(apps), N.ptr(out)))
         return out.astype(bool)
 
+    def cluster_fit_feasible(self, algo: int, apps: np.ndarray, overhead=None, node_select=None) -> np.ndarray:
+        """gf_cluster_fit_feasible: HasCapacity of every application (bool array) on the EMPTY resident cluster (set_cluster's
+        allocatable columns and zones, no usage) minus `overhead` ((n_nodes, 3), None = none), with the nodes of `node_select`
+        ((n_nodes,) truth values, None = every node) as driver and executor candidates.  Installs nothing: the snapshot, the
+        generations and the chain cache stay as they are."""
+        apps = np.ascontiguousarray(apps, dtype=N.APP_DTYPE)
+        ocols = [None] * 3
+        if overhead is not None:
+            overhead = np.ascontiguousarray(overhead, dtype=np.int64).reshape(-1, 3)
+            assert len(overhead) == self._cluster_n, "one overhead row per node of the cluster"
+            ocols = [np.ascontiguousarray(overhead[:, j]) for j in range(3)]
+        sel = None
+        if node_select is not None:
+            sel = np.ascontiguousarray(np.asarray(node_select) != 0, dtype=np.uint8)
+            assert len(sel) == self._cluster_n, "one selection byte per node of the cluster"
+        out = np.zeros(len(apps), dtype=np.uint8)
+        self._check(self._lib.gf_cluster_fit_feasible(self._h, algo, *[N.ptr(c) for c in ocols], N.ptr(sel), len(apps),
+                                                      N.ptr(apps), N.ptr(out)))
+        return out.astype(bool)
+
     def spark_binpack(self, algo: int, drv, exe, k: int):
         """One decision in the shape of binpack.SparkBinPackFunction. Returns (has_capacity, driver, exec_nodes)."""
         app = make_apps([drv], [exe], [k])

@@ -376,6 +376,69 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
     return out;
 }
 
+std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnschedulablePodsResident(
+    const std::vector<Pod>& allPods, int64_t timeoutNanos, const FlatCluster& cluster, const std::vector<Node>& availableNodes,
+    const NodeGroupResources& nonSchedulableOverhead, bool* served, std::string* err, bool* residentRoute) {
+    if (residentRoute) *residentRoute = false;
+    auto installs = [&] { return scanForUnschedulablePods(allPods, timeoutNanos, availableNodes, nonSchedulableOverhead, served, err); };
+    const uint32_t n = (uint32_t)cluster.names.size();
+    // the selection: the nodes the drivers' affinity matches, by the cluster's node index
+    std::vector<uint8_t> select(n, 0);
+    for (const Node& nd : availableNodes) {
+        auto it = cluster.index.find(nd.Name);
+        if (it == cluster.index.end()) return installs();
+        select[it->second] = 1;
+    }
+    FlatOverhead over;
+    if (!FlatOverhead::Build(nonSchedulableOverhead, cluster, &over, nullptr)) return installs();
+    // the stale pending drivers, as in scanForUnschedulablePods
+    if (timeoutNanos <= 0) timeoutNanos = 600ll * 1000000000;
+    std::vector<const Pod*> stale;
+    std::vector<gf_app> apps;
+    for (const Pod& pod : allPods) {
+        auto role = pod.labels.find(common::SparkRoleLabel);
+        if (pod.SchedulerName != common::SparkSchedulerName || !pod.NodeName.empty() || pod.Deleting ||
+            role == pod.labels.end() || role->second != common::Driver || pod.CreationTimestampNanos + timeoutNanos >= nowNanos)
+            continue;
+        auto r = sparkResources(pod, nullptr);
+        gf_app a{};
+        if (!r || !r->DriverResources.canonical(a.drv) || !r->ExecutorResources.canonical(a.exe) || r->MinExecutorCount < 0 ||
+            r->MinExecutorCount > GF_MAX_K)
+            return installs();  // (an unparsable or unrepresentable pod: the other route says what the reference says)
+        a.k = r->MinExecutorCount;
+        stale.push_back(&pod);
+        apps.push_back(a);
+    }
+    if (served) *served = true;
+    std::vector<std::pair<std::string, bool>> out;
+    if (apps.empty()) return out;
+    std::vector<uint8_t> fits(apps.size());
+    int rc = GF_ERR_UNSUPPORTED;
+    {
+        std::lock_guard<std::mutex> flat_lock(*flat_mu_);  // the record of what sits on the device; before the sequence lock
+        gf_ctx* ctx = binpacker_.ctx;
+        CtxSequence seq(ctx);
+        uint64_t gen[3] = {0, 0, 0};
+        (void)gf_generation(ctx, gen);
+        // the columns on the device must be this cluster's: put there by this extender's Filter and not replaced since
+        const bool resident = cluster.version != 0 && resident_cluster_ == cluster.version && gen[1] == seen_cluster_gen_;
+        const bool with_over = !over.over[0].empty();
+        if (resident)
+            rc = gf_cluster_fit_feasible(ctx, binpacker_.Algo, with_over ? over.over[0].data() : nullptr,
+                                         with_over ? over.over[1].data() : nullptr, with_over ? over.over[2].data() : nullptr,
+                                         select.data(), (uint32_t)apps.size(), apps.data(), fits.data());
+        if (rc != GF_OK && rc != GF_ERR_UNSUPPORTED) {
+            if (served) *served = false;
+            if (err) *err = std::string("gf_cluster_fit_feasible: ") + gf_last_error(ctx);
+            return {};
+        }
+    }
+    if (rc == GF_ERR_UNSUPPORTED) return installs();  // refused, or not resident (outside the locks: that route takes them itself)
+    if (residentRoute) *residentRoute = true;
+    for (size_t i = 0; i < stale.size(); ++i) out.emplace_back(stale[i]->Name, fits[i] == 0);
+    return out;
+}
+
 }  // namespace gangfit::host
 
 namespace gangfit::host {

@@ -179,6 +179,21 @@ public:
                                                                        const NodeGroupResources& nonSchedulableOverhead,
                                                                        bool* served, std::string* err);
 
+    // The same scan NEXT TO the Filter's installed snapshot instead of in its place (include/gangfit.h, gf_cluster_fit_feasible):
+    // `cluster` is the flat cluster of the Filter's flat route, whose columns selectDriverNodeFlat keeps on the device.  The scan
+    // sends the non-schedulable overhead as dense columns and availableNodes as a node selection, and asks the resident columns —
+    // no flatten, no upload, no install: the snapshot epoch, the chain cache and the resident usage stay, and the next Filter
+    // resumes.  Falls back to scanForUnschedulablePods (which installs) when the entry point refuses the question
+    // (GF_ERR_UNSUPPORTED: a zone-aware packer with a driver that asks for neither cpu nor memory, an overhead above a node's
+    // allocatable, more than 64 zones), when `cluster` is not what this extender's last Filter left on the device, or when
+    // availableNodes names a node outside it.  *residentRoute (nullable): true when the resident entry point answered.
+    std::vector<std::pair<std::string, bool>> scanForUnschedulablePodsResident(const std::vector<Pod>& allPods, int64_t timeoutNanos,
+                                                                               const FlatCluster& cluster,
+                                                                               const std::vector<Node>& availableNodes,
+                                                                               const NodeGroupResources& nonSchedulableOverhead,
+                                                                               bool* served, std::string* err,
+                                                                               bool* residentRoute = nullptr);
+
     bool shouldSkipDriverFifo(const Pod& pod, const std::string& instanceGroup) const;
 
 private:

@@ -335,6 +335,26 @@ int gf_cluster_fit_feasible(gf_ctx *ctx, gf_algo algo, const int64_t *over_cpu_m
                             const int64_t *over_gpu, const uint8_t *node_select, uint32_t n_apps, const gf_app *apps,
                             uint8_t *has_capacity);
 
+/* The same scan for drivers of many instance groups in one call.  scanForUnschedulablePods walks every stale pending driver of the
+ * scheduler and DoesPodExceedClusterCapacity builds the node list from that pod's own required affinity
+ * (internal/extender/unschedulablepods.go:93-166): G instance groups are G node sets.
+ *   set_words  n_sets rows of W = ceil(n_nodes / 64) words; bit (n & 63) of word n >> 6 of a row = node n belongs to the set
+ *   app_set    n_apps entries, each < n_sets: the set application a asks
+ * has_capacity[a] equals, byte for byte, what gf_cluster_fit_feasible returns for apps[a] alone with node_select = row app_set[a]
+ * expanded to bytes, under the same overhead columns (one overhead for all sets is exact: the overhead maps are per node,
+ * internal/extender/overhead.go:98-118).  Sets may overlap and may be empty; an empty set answers 0 for every application,
+ * whatever its k.  One launch of cluster_scan_sets_kernel, one wavefront per application: it walks its row 64 words at a time and
+ * reads the cluster columns only of the 64-node chunks whose word is not zero — never the nodes of the other sets.  Leaves
+ * untouched what gf_cluster_fit_feasible leaves untouched; blocking; only n_apps bytes come back; its device buffers are its own.
+ * Refusals (nothing on the device changes, has_capacity stays untouched): everything gf_cluster_fit_feasible refuses, with the
+ * same code — for a zone-aware packer ONE application whose driver asks for neither cpu nor memory refuses the whole call with
+ * GF_ERR_UNSUPPORTED —; and GF_ERR_INVALID for n_sets == 0, set_words or app_set NULL (each with n_apps > 0; set_words may be NULL on a
+ * cluster of no node, whose rows have no word), an app_set[a] >= n_sets, a bit at or beyond n_nodes in a row's last word.  n_apps == 0 is GF_OK with any pointers.  A multi-device context
+ * answers from its first device. */
+int gf_cluster_fit_feasible_sets(gf_ctx *ctx, gf_algo algo, const int64_t *over_cpu_milli, const int64_t *over_mem_bytes,
+                                 const int64_t *over_gpu, uint32_t n_sets, const uint64_t *set_words, const uint32_t *app_set,
+                                 uint32_t n_apps, const gf_app *apps, uint8_t *has_capacity);
+
 /* Incremental FIFO chains.  The reference replays every earlier driver on every Filter (internal/extender/resource.go:309-328);
  * with an unchanged snapshot, driver j + 1's chain is driver j's chain plus one application.  gf_fit_batch(GF_MODE_FIFO_CHAIN)
  * therefore keeps the last queue, its results and a checkpoint of the working table every 32 applications (more for tables

@@ -756,6 +756,48 @@ func (c *Context) FitFeasibleOnEmptyCluster(algo int, apps []App, nonSchedulable
 	return out, nil
 }
 
+// FitFeasibleOnEmptyClusterSets is FitFeasibleOnEmptyCluster for drivers of many instance groups in one call
+// (include/gangfit.h, gf_cluster_fit_feasible_sets): scanForUnschedulablePods walks every stale pending driver and
+// DoesPodExceedClusterCapacity takes the nodes of that pod's own affinity (internal/extender/unschedulablepods.go:93-166).
+// setWords holds nSets rows of ceil(nNodes / 64) words, bit (n & 63) of word n >> 6 of a row = node n is in the set; appSet[a]
+// is the row application a asks.  The answer of every application is what FitFeasibleOnEmptyCluster gives for it alone with
+// its row as nodeSelect; an empty set answers false.  Unverified here (no Go toolchain);
+// tests/test_gpu_cluster_scan_sets.py drives the C entry point.
+func (c *Context) FitFeasibleOnEmptyClusterSets(algo int, apps []App, nonSchedulableOverhead [3][]int64, nSets int, setWords []uint64, appSet []uint32) ([]bool, error) {
+	capps, _, err := flattenApps(apps)
+	if err != nil {
+		return nil, err
+	}
+	if len(apps) == 0 {
+		return nil, nil
+	}
+	if len(appSet) != len(apps) {
+		return nil, fmt.Errorf("gangfit: %d applications, %d set numbers", len(apps), len(appSet))
+	}
+	var over [3]*C.int64_t
+	if len(nonSchedulableOverhead[0]) > 0 {
+		for j := range over {
+			over[j] = (*C.int64_t)(unsafe.Pointer(&nonSchedulableOverhead[j][0]))
+		}
+	}
+	var words *C.uint64_t
+	if len(setWords) > 0 {
+		words = (*C.uint64_t)(unsafe.Pointer(&setWords[0]))
+	}
+	fits := make([]C.uint8_t, len(apps))
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	if rc := C.gf_cluster_fit_feasible_sets(c.ctx, C.gf_algo(algo), over[0], over[1], over[2], C.uint32_t(nSets), words,
+		(*C.uint32_t)(unsafe.Pointer(&appSet[0])), C.uint32_t(len(apps)), &capps[0], &fits[0]); rc != C.GF_OK {
+		return nil, c.err(rc)
+	}
+	out := make([]bool, len(apps))
+	for i := range fits {
+		out[i] = fits[i] != 0
+	}
+	return out, nil
+}
+
 // ExecutorFitOnInstalledSnapshot is the node choice of rescheduleExecutor (internal/extender/resource.go:594-673) for a batch
 // of executors against the installed snapshot and executor order: the first-fit loop (:658-662) or, minimalFragmentation = true,
 // rescheduleExecutorWithMinimalFragmentation (:675-703).  zones == nil: no zone step.  Otherwise nodeZone[n] is the id of node

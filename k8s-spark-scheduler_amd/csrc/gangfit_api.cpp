@@ -311,6 +311,8 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->d_scan_out.release();
     ctx->d_scan_apps.release();
     ctx->h_scan_out.release();
+    ctx->d_scan_sets.release();
+    ctx->d_scan_app_set.release();
     ctx->d_delta_i64.release();
     ctx->d_delta_u32.release();
     ctx->d_bi64.release();

@@ -1,21 +1,22 @@
-// gangfit_api_scan.cpp — gf_cluster_fit_feasible: the UnschedulablePodMarker's empty-cluster question answered from the resident
-// cluster columns (gangfit_scan.inc), next to the installed snapshot instead of in its place.  Nothing here installs: no
-// InstallGuard, no epoch, no generation, no chain cache, no worker_quiesce — the call only reads what gf_cluster_set uploaded and
-// writes buffers of its own (gf_ctx::d_scan_*).
+// gangfit_api_scan.cpp — gf_cluster_fit_feasible and gf_cluster_fit_feasible_sets: the UnschedulablePodMarker's empty-cluster
+// question answered from the resident cluster columns (gangfit_scan.inc), next to the installed snapshot instead of in its place.
+// Nothing here installs: no InstallGuard, no epoch, no generation, no chain cache, no worker_quiesce — the calls only read what
+// gf_cluster_set uploaded and write buffers of their own (gf_ctx::d_scan_*).
 #include "gangfit_ctx.h"
 
 using namespace gfapi;
 
-extern "C" {
+namespace {
 
-int gf_cluster_fit_feasible(gf_ctx* ctx, gf_algo algo, const int64_t* over_cpu_milli, const int64_t* over_mem_bytes,
-                            const int64_t* over_gpu, const uint8_t* node_select, uint32_t n_apps, const gf_app* apps,
-                            uint8_t* has_capacity) {
-    GF_DELEGATE(ctx, gf_cluster_fit_feasible(ctx, algo, over_cpu_milli, over_mem_bytes, over_gpu, node_select, n_apps, apps, has_capacity));
-    if (!ctx) return GF_ERR_INVALID;
-    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-    GF_NOT_ON_A_VIEW(ctx);
-    if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede gf_cluster_fit_feasible");
+struct ScanQuestion {
+    const int64_t* ocols[3];
+    bool with_over, zoned;
+};
+
+// What both entry points refuse, in one order; *q = what the launch needs.  `who` names the entry point in the messages.
+int scan_check(gf_ctx* ctx, const char* who, gf_algo algo, const int64_t* over_cpu_milli, const int64_t* over_mem_bytes,
+               const int64_t* over_gpu, uint32_t n_apps, const gf_app* apps, const uint8_t* has_capacity, ScanQuestion* q) {
+    if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede %s", who);
     const bool zone_aware = is_zone_algo(algo);
     if (!zone_aware && !is_plain_algo(algo)) return fail(ctx, GF_ERR_UNSUPPORTED, "gf_algo %d is not served by the device path", (int)algo);
     const bool with_over = over_cpu_milli || over_mem_bytes || over_gpu;
@@ -48,31 +49,101 @@ int gf_cluster_fit_feasible(gf_ctx* ctx, gf_algo algo, const int64_t* over_cpu_m
             if (apps[a].drv[0] == 0 && apps[a].drv[1] == 0)
                 return fail(ctx, GF_ERR_UNSUPPORTED, "apps[%u]'s driver asks for neither cpu nor memory: the zone-aware answer needs the averages", a);
     }
-    if (n_apps == 0) return GF_OK;
     if (n_apps >= 0x80000000u) return fail(ctx, GF_ERR_INVALID, "n_apps = %u", n_apps);
+    for (int j = 0; j < 3; ++j) q->ocols[j] = ocols[j];
+    q->with_over = with_over;
     // az-aware-tightly-pack falls back to the plain order when no single zone fits (az_aware_pack_tightly.go:33-37), and a gang
     // that fits one zone fits the plain order: its answer is the plain one
-    const bool zoned = zone_aware && algo != GF_ALGO_AZ_AWARE_TIGHTLY_PACK;
-    GF_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    // the call is blocking, so the previous scan has left these buffers; nothing else names them
+    q->zoned = zone_aware && algo != GF_ALGO_AZ_AWARE_TIGHTLY_PACK;
+    return GF_OK;
+}
+
+// The overhead columns and the records on their way to the device; the previous scan has left these buffers (the calls block).
+int scan_upload(gf_ctx* ctx, const ScanQuestion& q, uint32_t n_apps, const gf_app* apps, hipStream_t st) {
+    const size_t N = ctx->cl_n;
     GF_HIP(ctx, ctx->d_scan_over.reserve(3 * N + 1));
-    GF_HIP(ctx, ctx->d_scan_select.reserve(N + 1));
     GF_HIP(ctx, ctx->d_scan_apps.reserve(n_apps));
     GF_HIP(ctx, ctx->d_scan_out.reserve(n_apps));
     GF_HIP(ctx, ctx->h_scan_out.reserve(n_apps));
-    if (with_over)
+    if (q.with_over)
         for (int j = 0; j < 3 && N; ++j)
-            GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_over.ptr + (size_t)j * N, ocols[j], N * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (node_select != nullptr && N) GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_select.ptr, node_select, N, hipMemcpyHostToDevice, st));
+            GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_over.ptr + (size_t)j * N, q.ocols[j], N * sizeof(int64_t), hipMemcpyHostToDevice, st));
     GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_apps.ptr, apps, (size_t)n_apps * sizeof(gf_app), hipMemcpyHostToDevice, st));
-    GF_HIP(ctx, gangfit::launch_cluster_scan(zoned, n, ctx->d_cl_i64.ptr, with_over ? ctx->d_scan_over.ptr : nullptr, ctx->d_cl_u32.ptr,
-                                             node_select != nullptr ? ctx->d_scan_select.ptr : nullptr, n_apps, ctx->d_scan_apps.ptr,
-                                             ctx->d_scan_out.ptr, st));
+    return GF_OK;
+}
+
+int scan_answers(gf_ctx* ctx, uint32_t n_apps, uint8_t* has_capacity, hipStream_t st) {
     GF_HIP(ctx, hipMemcpyAsync(ctx->h_scan_out.ptr, ctx->d_scan_out.ptr, n_apps, hipMemcpyDeviceToHost, st));
     GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays are free again, the answers have arrived
     std::memcpy(has_capacity, ctx->h_scan_out.ptr, n_apps);
     return GF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gf_cluster_fit_feasible(gf_ctx* ctx, gf_algo algo, const int64_t* over_cpu_milli, const int64_t* over_mem_bytes,
+                            const int64_t* over_gpu, const uint8_t* node_select, uint32_t n_apps, const gf_app* apps,
+                            uint8_t* has_capacity) {
+    GF_DELEGATE(ctx, gf_cluster_fit_feasible(ctx, algo, over_cpu_milli, over_mem_bytes, over_gpu, node_select, n_apps, apps, has_capacity));
+    if (!ctx) return GF_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    GF_NOT_ON_A_VIEW(ctx);
+    ScanQuestion q{};
+    if (const int rc = scan_check(ctx, "gf_cluster_fit_feasible", algo, over_cpu_milli, over_mem_bytes, over_gpu, n_apps, apps, has_capacity, &q);
+        rc != GF_OK)
+        return rc;
+    if (n_apps == 0) return GF_OK;
+    const uint32_t n = ctx->cl_n;
+    const size_t N = n;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    GF_HIP(ctx, ctx->d_scan_select.reserve(N + 1));
+    if (const int rc = scan_upload(ctx, q, n_apps, apps, st); rc != GF_OK) return rc;
+    if (node_select != nullptr && N) GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_select.ptr, node_select, N, hipMemcpyHostToDevice, st));
+    GF_HIP(ctx, gangfit::launch_cluster_scan(q.zoned, n, ctx->d_cl_i64.ptr, q.with_over ? ctx->d_scan_over.ptr : nullptr, ctx->d_cl_u32.ptr,
+                                             node_select != nullptr ? ctx->d_scan_select.ptr : nullptr, n_apps, ctx->d_scan_apps.ptr,
+                                             ctx->d_scan_out.ptr, st));
+    return scan_answers(ctx, n_apps, has_capacity, st);
+}
+
+int gf_cluster_fit_feasible_sets(gf_ctx* ctx, gf_algo algo, const int64_t* over_cpu_milli, const int64_t* over_mem_bytes,
+                                 const int64_t* over_gpu, uint32_t n_sets, const uint64_t* set_words, const uint32_t* app_set,
+                                 uint32_t n_apps, const gf_app* apps, uint8_t* has_capacity) {
+    GF_DELEGATE(ctx, gf_cluster_fit_feasible_sets(ctx, algo, over_cpu_milli, over_mem_bytes, over_gpu, n_sets, set_words, app_set, n_apps, apps, has_capacity));
+    if (!ctx) return GF_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    GF_NOT_ON_A_VIEW(ctx);
+    ScanQuestion q{};
+    if (const int rc = scan_check(ctx, "gf_cluster_fit_feasible_sets", algo, over_cpu_milli, over_mem_bytes, over_gpu, n_apps, apps, has_capacity, &q);
+        rc != GF_OK)
+        return rc;
+    if (n_apps == 0) return GF_OK;
+    const uint32_t n = ctx->cl_n;
+    const size_t W = ((size_t)n + 63) / 64;
+    if (n_sets == 0) return fail(ctx, GF_ERR_INVALID, "n_sets = 0 with %u applications", n_apps);
+    // (a cluster of no node has rows of no word: nothing to point at, and every set is empty)
+    if ((!set_words && W > 0) || !app_set) return fail(ctx, GF_ERR_INVALID, "set_words/app_set must not be NULL");
+    for (uint32_t a = 0; a < n_apps; ++a)
+        if (app_set[a] >= n_sets) return fail(ctx, GF_ERR_INVALID, "app_set[%u] = %u names no set (%u sets)", a, app_set[a], n_sets);
+    if ((n & 63u) != 0u) {  // the kernel trusts a bit to name a node
+        const uint64_t beyond = ~UINT64_C(0) << (n & 63u);
+        for (uint32_t s = 0; s < n_sets; ++s)
+            if (set_words[(size_t)s * W + (W - 1)] & beyond) return fail(ctx, GF_ERR_INVALID, "set %u has a bit at or beyond node %u", s, n);
+    }
+    const size_t n_words = (size_t)n_sets * W;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    GF_HIP(ctx, ctx->d_scan_sets.reserve(n_words + 1));
+    GF_HIP(ctx, ctx->d_scan_app_set.reserve(n_apps));
+    if (const int rc = scan_upload(ctx, q, n_apps, apps, st); rc != GF_OK) return rc;
+    if (n_words) GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_sets.ptr, set_words, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_app_set.ptr, app_set, (size_t)n_apps * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    GF_HIP(ctx, gangfit::launch_cluster_scan_sets(q.zoned, n, ctx->d_cl_i64.ptr, q.with_over ? ctx->d_scan_over.ptr : nullptr,
+                                                  ctx->d_cl_u32.ptr, ctx->d_scan_sets.ptr, ctx->d_scan_app_set.ptr, n_apps,
+                                                  ctx->d_scan_apps.ptr, ctx->d_scan_out.ptr, st));
+    return scan_answers(ctx, n_apps, has_capacity, st);
 }
 
 }  // extern "C"

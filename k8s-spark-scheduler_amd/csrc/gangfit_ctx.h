@@ -6,7 +6,7 @@
 //   gangfit_api_fit.cpp       the launches of every packer, the incremental chain cache, gf_fit_batch*, single executors,
 //                             findNodes, efficiencies
 //   gangfit_api_worker.cpp    the resident worker of the independent batch (gf_worker_*)
-//   gangfit_api_scan.cpp      gf_cluster_fit_feasible: the empty-cluster capacity scan on the resident cluster columns
+//   gangfit_api_scan.cpp      gf_cluster_fit_feasible[_sets]: the empty-cluster capacity scan on the resident cluster columns
 //   gangfit_api_group.cpp     node-range sharding: the gf_shard_* steps and the multi-device context (peer stores or RCCL)
 #pragma once
 #include <dlfcn.h>
@@ -368,6 +368,8 @@ struct gf_ctx {
     DeviceBuf<uint8_t> d_scan_select, d_scan_out;
     DeviceBuf<gf_app> d_scan_apps;
     PinnedBuf<uint8_t> h_scan_out;
+    DeviceBuf<uint64_t> d_scan_sets;      // gf_cluster_fit_feasible_sets: the node sets, n_sets rows of ceil(n / 64) words
+    DeviceBuf<uint32_t> d_scan_app_set;   // ... and every application's row
 
     // gf_snapshot_build
     DeviceBuf<int64_t> d_bi64;   // alloc | overhead | usage | avail | sched (3n each) | keys_a | keys_b (n each) | res_req (3r) | zone_sum

@@ -505,6 +505,13 @@ hipError_t launch_overhead_update(uint32_t n_rows, uint32_t n_nodes, const uint3
 // One wavefront per application; reads nothing of the installed snapshot.
 hipError_t launch_cluster_scan(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
                                const uint8_t* d_select, uint32_t n_apps, const gf_app* d_apps, uint8_t* d_out, hipStream_t stream);
+// The same scan for applications of many node sets in one launch (gf_cluster_fit_feasible_sets): application a asks the nodes of
+// row d_app_set[a] of d_set_words — rows of ceil(n_nodes / 64) words, bit (n & 63) of word n >> 6 = node n, no bit at or beyond
+// n_nodes, every d_app_set[a] a row of the matrix (the entry point checks both).  A wavefront reads the columns only of the 64-node
+// chunks whose word of its row is not zero.
+hipError_t launch_cluster_scan_sets(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
+                                    const uint64_t* d_set_words, const uint32_t* d_app_set, uint32_t n_apps, const gf_app* d_apps,
+                                    uint8_t* d_out, hipStream_t stream);
 // The slot tables of the merged layout built from the device-resident snapshot columns (what gf_orders_set builds on the
 // host): every node gets the slot of its position in the priority order.
 struct SnapshotFinalize {

@@ -1992,6 +1992,21 @@ hipError_t launch_cluster_scan(bool zoned, uint32_t n_nodes, const int64_t* d_al
     });
 }
 
+hipError_t launch_cluster_scan_sets(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
+                                    const uint64_t* d_set_words, const uint32_t* d_app_set, uint32_t n_apps, const gf_app* d_apps,
+                                    uint8_t* d_out, hipStream_t stream) {
+    if (n_apps == 0) return hipSuccess;
+    if (d_apps == nullptr || d_out == nullptr || d_app_set == nullptr ||
+        (n_nodes > 0 && (d_alloc == nullptr || d_set_words == nullptr || (zoned && d_zone == nullptr))))
+        return hipErrorInvalidValue;
+    const uint32_t n_words = (uint32_t)(((uint64_t)n_nodes + kWave - 1) / kWave);
+    const ScanSetsArgs args{d_alloc, d_over, d_zone, d_set_words, d_app_set, n_nodes, n_words, n_apps, d_apps, d_out};
+    return with_value<true, false>(zoned, [&](auto Z) {
+        hipLaunchKernelGGL(cluster_scan_sets_kernel<Z>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, args);
+        return hipGetLastError();
+    });
+}
+
 size_t fifo_v2_lds_bytes(uint32_t lds_slots, uint32_t n_chunks) {
     return 24 * ((size_t)lds_slots + n_chunks) + 16 * (size_t)n_chunks + sizeof(Exchange) + sizeof(FifoShared) + 64 +
            ((n_chunks + 15) & ~15u);

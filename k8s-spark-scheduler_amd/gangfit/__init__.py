@@ -18,4 +18,4 @@ from ._native import (  # noqa: F401
     GF_NO_NODE,
     GangfitError,
 )
-from .context import BatchOut, Context, make_apps, with_offsets  # noqa: F401
+from .context import BatchOut, Context, make_apps, pack_node_sets, with_offsets  # noqa: F401

@@ -36,6 +36,22 @@ def with_offsets(apps: np.ndarray) -> Tuple[np.ndarray, int]:
     return apps, int(k.sum())
 
 
+def pack_node_sets(sets, n_nodes: int) -> np.ndarray:
+    """(n_sets, n_nodes) truth values -> (n_sets, W) uint64 rows, W = ceil(n_nodes / 64), as gf_cluster_fit_feasible_sets reads
+    them: bit (n & 63) of word n >> 6 of a row = node n is in the set; the padding bits of the last word are 0."""
+    sets = np.asarray(sets) != 0
+    if sets.ndim == 1:  # (np.asarray of no rows)
+        sets = sets.reshape(-1, n_nodes)
+    assert sets.ndim == 2 and sets.shape[1] == n_nodes, "one column per node of the cluster"
+    n_words = (n_nodes + 63) // 64
+    if n_words == 0:
+        return np.zeros((sets.shape[0], 0), dtype=np.uint64)
+    padded = np.zeros((sets.shape[0], n_words * 64), dtype=np.uint8)
+    padded[:, :n_nodes] = sets
+    packed = np.packbits(padded, axis=1, bitorder="little")  # byte b of a row: nodes 8b .. 8b + 7, node 8b in bit 0
+    return np.ascontiguousarray(packed.view("<u8").astype(np.uint64).reshape(sets.shape[0], n_words))
+
+
 @dataclass
 class BatchOut:
     results: np.ndarray  # RESULT_DTYPE
@@ -294,6 +310,24 @@ class Context:
         out = np.zeros(len(apps), dtype=np.uint8)
         self._check(self._lib.gf_cluster_fit_feasible(self._h, algo, *[N.ptr(c) for c in ocols], N.ptr(sel), len(apps),
                                                       N.ptr(apps), N.ptr(out)))
+        return out.astype(bool)
+
+    def cluster_fit_feasible_sets(self, algo: int, apps: np.ndarray, sets, app_set, overhead=None) -> np.ndarray:
+        """gf_cluster_fit_feasible_sets: cluster_fit_feasible for applications of many node sets in one call.  `sets` is an
+        (n_sets, n_nodes) truth array — one row per instance group —, `app_set[a]` the row application a asks; the answer of
+        every application is what cluster_fit_feasible(node_select=sets[app_set[a]]) gives for it alone."""
+        apps = np.ascontiguousarray(apps, dtype=N.APP_DTYPE)
+        ocols = [None] * 3
+        if overhead is not None:
+            overhead = np.ascontiguousarray(overhead, dtype=np.int64).reshape(-1, 3)
+            assert len(overhead) == self._cluster_n, "one overhead row per node of the cluster"
+            ocols = [np.ascontiguousarray(overhead[:, j]) for j in range(3)]
+        words = pack_node_sets(sets, self._cluster_n)
+        app_set = np.ascontiguousarray(app_set, dtype=np.uint32)
+        assert len(app_set) == len(apps), "one set per application"
+        out = np.zeros(len(apps), dtype=np.uint8)
+        self._check(self._lib.gf_cluster_fit_feasible_sets(self._h, algo, *[N.ptr(c) for c in ocols], len(words), N.ptr(words),
+                                                           N.ptr(app_set), len(apps), N.ptr(apps), N.ptr(out)))
         return out.astype(bool)
 
     def spark_binpack(self, algo: int, drv, exe, k: int):

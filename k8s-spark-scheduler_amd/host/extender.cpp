@@ -439,6 +439,122 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
     return out;
 }
 
+std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnschedulablePodsAllGroups(
+    const std::vector<Pod>& allPods, int64_t timeoutNanos, const FlatCluster& cluster,
+    const std::map<std::string, std::vector<Node>>& nodesByInstanceGroup, const NodeGroupResources& nonSchedulableOverhead,
+    bool* served, std::string* err, bool* residentRoute) {
+    if (residentRoute) *residentRoute = false;
+    if (served) *served = true;
+    if (timeoutNanos <= 0) timeoutNanos = 600ll * 1000000000;
+    // the stale pending drivers, as in scanForUnschedulablePodsResident; an unparsable one ends the listing there
+    // ("failed to check if pod was unschedulable": the reference returns from the scan, unschedulablepods.go:112-116)
+    std::vector<const Pod*> stale;
+    std::vector<gf_app> apps;
+    bool representable = true;
+    for (const Pod& pod : allPods) {
+        auto role = pod.labels.find(common::SparkRoleLabel);
+        if (pod.SchedulerName != common::SparkSchedulerName || !pod.NodeName.empty() || pod.Deleting ||
+            role == pod.labels.end() || role->second != common::Driver || pod.CreationTimestampNanos + timeoutNanos >= nowNanos)
+            continue;
+        std::string e;
+        auto r = sparkResources(pod, &e);
+        if (!r) {
+            if (err) *err = e;
+            break;
+        }
+        gf_app a{};
+        if (!r->DriverResources.canonical(a.drv) || !r->ExecutorResources.canonical(a.exe) || r->MinExecutorCount < 0 ||
+            r->MinExecutorCount > GF_MAX_K)
+            representable = false;  // (the other route says so)
+        a.k = r->MinExecutorCount;
+        stale.push_back(&pod);
+        apps.push_back(a);
+    }
+    std::vector<std::pair<std::string, bool>> out;
+    if (stale.empty()) return out;
+    static const std::vector<Node> kNoNodes;
+    auto nodes_of = [&](const std::string& group) -> const std::vector<Node>& {
+        auto it = nodesByInstanceGroup.find(group);
+        return it == nodesByInstanceGroup.end() ? kNoNodes : it->second;  // a group nobody names: an empty set
+    };
+    // one installing scan per instance group, merged back into listing order
+    auto per_group = [&]() -> std::vector<std::pair<std::string, bool>> {
+        std::vector<std::string> order;  // the groups by first appearance
+        std::map<std::string, std::vector<size_t>> members;
+        for (size_t i = 0; i < stale.size(); ++i) {
+            auto [it, fresh] = members.try_emplace(stale[i]->InstanceGroup);
+            if (fresh) order.push_back(stale[i]->InstanceGroup);
+            it->second.push_back(i);
+        }
+        std::vector<std::pair<std::string, bool>> merged(stale.size());
+        for (const std::string& group : order) {
+            const std::vector<size_t>& idx = members[group];
+            const std::vector<Node>& nodes = nodes_of(group);
+            if (nodes.empty()) {  // the reference packs onto no node: no driver candidate, the pod exceeds the capacity
+                for (size_t i : idx) merged[i] = {stale[i]->Name, true};
+                continue;
+            }
+            std::vector<Pod> pods;
+            for (size_t i : idx) pods.push_back(*stale[i]);
+            bool ok = true;
+            const auto part = scanForUnschedulablePods(pods, timeoutNanos, nodes, nonSchedulableOverhead, &ok, err);
+            if (!ok || part.size() != idx.size()) {
+                if (served) *served = false;
+                return {};
+            }
+            for (size_t j = 0; j < idx.size(); ++j) merged[idx[j]] = part[j];
+        }
+        return merged;
+    };
+    if (!representable) return per_group();
+    // the sets: one row of ceil(n / 64) words per instance group a stale driver asks, by the cluster's node index
+    const uint32_t n = (uint32_t)cluster.names.size();
+    const size_t W = ((size_t)n + 63) / 64;
+    std::map<std::string, uint32_t> row_of;
+    std::vector<uint64_t> words;
+    std::vector<uint32_t> app_set(stale.size());
+    for (size_t i = 0; i < stale.size(); ++i) {
+        auto [it, fresh] = row_of.try_emplace(stale[i]->InstanceGroup, (uint32_t)row_of.size());
+        app_set[i] = it->second;
+        if (!fresh) continue;
+        words.resize(words.size() + W, 0);
+        uint64_t* row = words.data() + (size_t)it->second * W;
+        for (const Node& nd : nodes_of(stale[i]->InstanceGroup)) {
+            auto at = cluster.index.find(nd.Name);
+            if (at == cluster.index.end()) return per_group();
+            row[at->second >> 6] |= UINT64_C(1) << (at->second & 63u);
+        }
+    }
+    FlatOverhead over;
+    if (!FlatOverhead::Build(nonSchedulableOverhead, cluster, &over, nullptr)) return per_group();
+    std::vector<uint8_t> fits(apps.size());
+    int rc = GF_ERR_UNSUPPORTED;
+    {
+        std::lock_guard<std::mutex> flat_lock(*flat_mu_);  // the record of what sits on the device; before the sequence lock
+        gf_ctx* ctx = binpacker_.ctx;
+        CtxSequence seq(ctx);
+        uint64_t gen[3] = {0, 0, 0};
+        (void)gf_generation(ctx, gen);
+        // the columns on the device must be this cluster's: put there by this extender's Filter and not replaced since
+        const bool resident = cluster.version != 0 && resident_cluster_ == cluster.version && gen[1] == seen_cluster_gen_;
+        const bool with_over = !over.over[0].empty();
+        if (resident)
+            rc = gf_cluster_fit_feasible_sets(ctx, binpacker_.Algo, with_over ? over.over[0].data() : nullptr,
+                                              with_over ? over.over[1].data() : nullptr, with_over ? over.over[2].data() : nullptr,
+                                              (uint32_t)row_of.size(), words.data(), app_set.data(), (uint32_t)apps.size(), apps.data(),
+                                              fits.data());
+        if (rc != GF_OK && rc != GF_ERR_UNSUPPORTED) {
+            if (served) *served = false;
+            if (err) *err = std::string("gf_cluster_fit_feasible_sets: ") + gf_last_error(ctx);
+            return {};
+        }
+    }
+    if (rc == GF_ERR_UNSUPPORTED) return per_group();  // refused, or not resident (outside the locks: that route takes them itself)
+    if (residentRoute) *residentRoute = true;
+    for (size_t i = 0; i < stale.size(); ++i) out.emplace_back(stale[i]->Name, fits[i] == 0);
+    return out;
+}
+
 }  // namespace gangfit::host
 
 namespace gangfit::host {

@@ -173,7 +173,7 @@ public:
     // scheduler that is older than timeoutNanos is checked against the EMPTY cluster (the per-pod BinpackFunc calls of the
     // reference batched into one launch).  Returns {pod name, exceedsCapacity} in listing order; like the reference the scan
     // stops at the first pod whose resources cannot be parsed (*err says why).  availableNodes = the nodes the drivers'
-    // node affinity matches (one instance group per call).
+    // node affinity matches (drivers of several instance groups: scanForUnschedulablePodsAllGroups, below).
     std::vector<std::pair<std::string, bool>> scanForUnschedulablePods(const std::vector<Pod>& allPods, int64_t timeoutNanos,
                                                                        const std::vector<Node>& availableNodes,
                                                                        const NodeGroupResources& nonSchedulableOverhead,
@@ -193,6 +193,19 @@ public:
                                                                                const NodeGroupResources& nonSchedulableOverhead,
                                                                                bool* served, std::string* err,
                                                                                bool* residentRoute = nullptr);
+
+    // The marker's whole minute in one call: scanForUnschedulablePods (unschedulablepods.go:93-129) walks EVERY stale pending
+    // driver of the scheduler, and DoesPodExceedClusterCapacity (:132-166) builds the node list from that pod's own required
+    // affinity.  Every stale driver asks the nodes nodesByInstanceGroup lists for its Pod::InstanceGroup (a group the map does not
+    // name: no node — the reference packs onto nothing and the pod exceeds the capacity); the groups travel as node sets of one
+    // gf_cluster_fit_feasible_sets call (include/gangfit.h), under the residency test of scanForUnschedulablePodsResident.  The
+    // result is in listing order.  One scanForUnschedulablePods per instance group (which installs), merged back into listing
+    // order, answers instead when the entry point refuses (GF_ERR_UNSUPPORTED), when `cluster` is not the resident one, or when a
+    // listed node is outside it.  An unparsable pod ends the scan there, as the reference does, and *err says why.
+    std::vector<std::pair<std::string, bool>> scanForUnschedulablePodsAllGroups(
+        const std::vector<Pod>& allPods, int64_t timeoutNanos, const FlatCluster& cluster,
+        const std::map<std::string, std::vector<Node>>& nodesByInstanceGroup, const NodeGroupResources& nonSchedulableOverhead,
+        bool* served, std::string* err, bool* residentRoute = nullptr);
 
     bool shouldSkipDriverFifo(const Pod& pod, const std::string& instanceGroup) const;
 

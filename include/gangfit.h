@@ -560,8 +560,10 @@ int gf_scan_stats(gf_ctx *ctx, int enable, int reset, uint64_t out[10]);
  * which XCD the one workgroup ran on).  Nothing in the reference corresponds to it. */
 int gf_chain_profile(gf_ctx *ctx, uint64_t out[12]);
 
-/* On-device self-test of the wave primitives (DPP prefix scan, exact clamped 64-bit division) against plain
- * reference code on n_cases adversarial inputs per lane.  *mismatches == 0 means pass. */
+/* On-device self-test of the wave primitives against plain reference code on n_cases adversarial inputs per lane: the DPP
+ * prefix scan and the DPP reductions (64-lane maximum of int64 and int32, 64-lane float64 sum, per-row unsigned minimum and
+ * float64 maximum) against serial loops, the exact clamped and unclamped 64-bit divisions, the scaled domain's division by
+ * multiplication and the resident worker's scaled arithmetic against plain divides.  *mismatches == 0 means pass. */
 int gf_selftest(gf_ctx *ctx, uint64_t seed, uint32_t n_cases, uint32_t *mismatches);
 
 /* Bandwidth probe: streams `bytes` (a multiple of 16; use far more than the 256 MiB of last-level cache) `iters` times and

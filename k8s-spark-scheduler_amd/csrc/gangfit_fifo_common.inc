@@ -180,27 +180,6 @@ struct ChainOut {
     int32_t* h_failed;
 };
 
-
-// Maximum over the wave of a per-lane int32, wave-uniform (DPP, no LDS).
-__device__ __forceinline__ int32_t wave_max_i32(int32_t v) {
-#define GF_MAX32_STEP(ctrl, rmask)                                                    \
-    {                                                                                 \
-        const int32_t t = __builtin_amdgcn_update_dpp(v, v, ctrl, rmask, 0xf, false); \
-        v = t > v ? t : v;                                                            \
-    }
-    GF_MAX32_STEP(GF_DPP_ROW_SHR(1), 0xf)
-    GF_MAX32_STEP(GF_DPP_ROW_SHR(2), 0xf)
-    GF_MAX32_STEP(GF_DPP_ROW_SHR(4), 0xf)
-    GF_MAX32_STEP(GF_DPP_ROW_SHR(8), 0xf)
-    GF_MAX32_STEP(GF_DPP_ROW_BCAST15, 0xa)
-    GF_MAX32_STEP(GF_DPP_ROW_BCAST31, 0xc)
-#undef GF_MAX32_STEP
-    return read_lane(v, kWave - 1);
-}
-
-typedef __attribute__((address_space(3))) int32_t lds_i32;
-typedef __attribute__((address_space(1))) int32_t glb_i32;
-
 // min(floor(a / e), k) for one dimension in the narrow domain.  |a| < 2^30, 0 <= e < 2^30, 0 <= k <= 2^20; mag / sh from
 // narrow_magic(e); a zero request takes any number of executors (e == 0: mag == 0 and the quotient is replaced by "unlimited").
 __device__ __forceinline__ int32_t ncap_dim(int32_t a, int32_t e, uint32_t mag, uint32_t sh, int32_t k) {

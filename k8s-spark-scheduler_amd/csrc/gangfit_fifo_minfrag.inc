@@ -275,10 +275,9 @@ __device__ __forceinline__ MfStats mf_pass(const ZView& Z, uint32_t n_x, const N
 
 // SparkBinPack with minimalFragmentation on one candidate view, by the whole workgroup.  Returns feasibility (uniform);
 // on success R holds the run list (ds_out, nruns_out).
-typedef __attribute__((address_space(3))) uint32_t lds_u32w;
 template <int NWV>
 __device__ __forceinline__ bool mf_block_decide(const ZView& Z, uint32_t n_d, uint32_t n_x, uint32_t n_chunks, const NAppR& p,
-                                                const RunList& R, lds_u32w* chunk_cnt, lds_u32w* chunk_pre, lds_u64* chunk_msk,
+                                                const RunList& R, lds_u32* chunk_cnt, lds_u32* chunk_pre, lds_u64* chunk_msk,
                                                 lds_mfshared* sh, uint32_t cand,
                                                 uint32_t wave, int lane, uint32_t tid, uint32_t& xpar, uint32_t& ds_out,
                                                 uint32_t& nruns_out) {
@@ -817,7 +816,6 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
 
     // ---- LDS carve
     size_t off = 0;
-    typedef __attribute__((address_space(3))) unsigned char lds_u8;
     lds_u8* stage = (lds_u8*)smem;
     off += (size_t)kMfStage * (sizeof(gf_app) + sizeof(NApp));
     lds_mfshared* sh = (lds_mfshared*)(smem + off);
@@ -828,9 +826,9 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
     off += 12 * (size_t)nc;
     lds_i32* lruns = (lds_i32*)(smem + off);   // [n_cand][2 = application parity][2][kZRunMax]
     off += 2 * 8 * (size_t)kZRunMax * n_cand;
-    lds_u32w* chunk_cnt = (lds_u32w*)(smem + off);
+    lds_u32* chunk_cnt = (lds_u32*)(smem + off);
     off += 4 * (size_t)nc;
-    lds_u32w* chunk_pre = (lds_u32w*)(smem + off);
+    lds_u32* chunk_pre = (lds_u32*)(smem + off);
     off += 4 * (size_t)nc;
     off = (off + 7) & ~(size_t)7;
     lds_u64* chunk_msk = (lds_u64*)(smem + off);
@@ -967,20 +965,14 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
     unsigned long long tph = stats != nullptr ? __builtin_readcyclecounter() : 0ull;
     const unsigned long long t0_cycles = tph;
     const unsigned long long t0_real = wall_clock64();
-#define GF_MPHASE(i)                                                 \
-    if (stats != nullptr) {                                          \
-        const unsigned long long now = __builtin_readcyclecounter(); \
-        ph[i] += now - tph;                                          \
-        tph = now;                                                   \
-    }
     for (; a < n_apps; ++a) {
         if ((a % kMfStage) == 0) {
             const uint32_t n_stage = (n_apps - a) < (uint32_t)kMfStage ? (n_apps - a) : (uint32_t)kMfStage;
             const uint32_t words = n_stage * (uint32_t)(sizeof(gf_app) / 4);
             const uint32_t* gw = reinterpret_cast<const uint32_t*>(apps + a);
             const uint32_t* gn = reinterpret_cast<const uint32_t*>(napps + a);
-            lds_u32w* sw = (lds_u32w*)stage;
-            lds_u32w* sn = (lds_u32w*)(stage + (size_t)kMfStage * sizeof(gf_app));
+            lds_u32* sw = (lds_u32*)stage;
+            lds_u32* sn = (lds_u32*)(stage + (size_t)kMfStage * sizeof(gf_app));
             for (uint32_t i = tid; i < words; i += BLOCK) {
                 sw[i] = gw[i];
                 sn[i] = gn[i];
@@ -991,7 +983,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
             if (chain_ckpt_due(ck, a) && wave != 0) chain_ckpt_dump(plain, T.n_slots, chain_ckpt_slot(ck, a, T.n_slots), tid, BLOCK);
             if (wave == 0) {
                 uint32_t nx = sh->n_shape_x, nd = sh->n_shape_d;
-                zshapes_assign((lds_u32z*)sn, n_stage, sh->shape_x, sh->shape_d, nx, nd, n_shapes, lane,
+                zshapes_assign((lds_u32*)sn, n_stage, sh->shape_x, sh->shape_d, nx, nd, n_shapes, lane,
                                [&](bool drv, uint32_t id, int32_t v0, int32_t v1, int32_t v2) {
                                    if (!drv) {  // the commit patch divides by every registered executor shape (lane = shape)
                                        uint32_t m0, m1, m2, l0, l1, l2;
@@ -1099,7 +1091,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
             }
             caprow = row;
         }
-        GF_MPHASE(0)
+        GF_TICK(stats != nullptr, ph, tph, 0)
         // one wavefront per candidate view, from the histograms (workgroup-uniform)
         const bool use_hist = hist != nullptr && caprow != nullptr && ((sh->row_big >> (app.shape_x & 63u)) & 1ull) == 0ull;
         if (use_hist) {
@@ -1120,7 +1112,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
                 int32_t* hrow = hist + ((size_t)c * n_shapes + app.shape_x) * kMfBins;
                 const bool feasible = mf_hist_decide(ZV, hrow, hrow + hist_words, T.n_d, T.n_x, app, R, sh, c, lane, ds, nruns, xvis,
                                                      sh->pl_seq == a && sh->pl_view == c);
-                GF_MPHASE(1)
+                GF_TICK(stats != nullptr, ph, tph, 1)
                 if (feasible && nruns > kZRunMax && ewv < NW)  // spilled runs (global stores): the emitting helper reads them
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 double mx = 0.0;
@@ -1177,9 +1169,9 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
             }
         }
         }
-        GF_MPHASE(2)
+        GF_TICK(stats != nullptr, ph, tph, 2)
         lds_barrier();
-        GF_MPHASE(3)
+        GF_TICK(stats != nullptr, ph, tph, 3)
         // ---- chooseBestResult (single_az.go:75-97) / the plain result
         int32_t best;
         {
@@ -1241,7 +1233,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
                     if (__ballot(c > 0 && s == my_ds)) driver_hosts_exec = true;
                 }
                 if (!last && !driver_hosts_exec && lane == 0) plain.sub32(my_ds, app.drv0, app.drv1, app.drv2);
-                GF_MPHASE(4)
+                GF_TICK(stats != nullptr, ph, tph, 4)
                 if (!last && capmat != nullptr) {
                     // the subtractions above are this wavefront's own LDS writes (in order); a workgroup fence here would also
                     // wait for the placement stores just issued
@@ -1285,7 +1277,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
             __syncthreads();
         else
             lds_barrier();
-        GF_MPHASE(5)
+        GF_TICK(stats != nullptr, ph, tph, 5)
         if (defer && wave == ewv) {
             if (lane == 0) {
                 gf_result r;
@@ -1317,7 +1309,6 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
             break;
         }
     }
-#undef GF_MPHASE
     if (tid == 0 && stats != nullptr) {  // wave 0: stage + row fill | decide | efficiency | barrier | select + emit + commit | patch + barrier
         stats->fifo_shader_cycles = __builtin_readcyclecounter() - t0_cycles;
         stats->fifo_realtime_ticks = wall_clock64() - t0_real;

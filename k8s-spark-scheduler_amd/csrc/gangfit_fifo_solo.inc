@@ -33,19 +33,6 @@ struct SoloShared {
     uint32_t pad;
 };
 
-__device__ __forceinline__ uint32_t uniform32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)v); }
-__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
-    const uint32_t lo = uniform32((uint32_t)v), hi = uniform32((uint32_t)(v >> 32));
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// The 64-bit value lane `src` holds (src wave-uniform): two v_readlane with a scalar lane select.
-__device__ __forceinline__ uint64_t read_lane64(unsigned long long v, uint32_t src) {
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)v, (int)src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)(v >> 32), (int)src);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 constexpr uint32_t kCkptDone = 0xFFFFFFFFu;
 
 // LDS layout of the table front: one 784-byte block per 64-slot chunk — cpu[64] | mem[64] | gpu[64] | xmask | dmask — so
@@ -122,21 +109,6 @@ struct NarrowBlockView {
 };
 
 constexpr int kSoloWaves = 16;  // wavefronts of the workgroup (launch bound = VGPR budget: 16 -> 128 per lane, 8 -> 256)
-
-// "This value is needed HERE": keeps the compiler from sinking an LDS load below a branch that does not always use it (it
-// would then pay one LDS round trip per use instead of one for the whole group of loads issued together).
-#define GF_PIN(x) asm volatile("" : "+v"(x))
-// A taken branch costs a lone wavefront ~30 cycles (tools/micro/probe_f64.hip: 47 cycles per trip of a loop around one
-// 8-cycle add), a branch that falls through one issue slot: the rare bodies of the chain loop are laid out out of line.
-#define GF_RARE(x) __builtin_expect(!!(x), 0)
-#define GF_OFTEN(x) __builtin_expect(!!(x), 1)
-#define GF_PIN4(v)   \
-    {                \
-        GF_PIN(v.x); \
-        GF_PIN(v.y); \
-        GF_PIN(v.z); \
-        GF_PIN(v.w); \
-    }
 
 // The staged record: K, the flags and the two shape ids become wave-uniform (SGPRs: they steer the scalar control flow);
 // the request vectors, the reciprocals and the placement offset stay in VGPRs (they are only ever VALU operands, and
@@ -726,12 +698,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
         constexpr bool prof = PROF;
         unsigned long long tp = prof ? __builtin_readcyclecounter() : 0;
         const unsigned long long t_chain_begin = tp;
-#define GF_PHASE(idx)                                               \
-    if (prof) {                                                     \
-        const unsigned long long tn = __builtin_readcyclecounter(); \
-        ph[idx] += tn - tp;                                         \
-        tp = tn;                                                    \
-    }
         // chunk c (wave-uniform): lane l <-> slot 64 c + l; xm / dm = the chunk's candidate masks (uniform values)
         // MOFF: dword offset of the candidate mask the visit needs inside the block (192 executor candidates, 194 driver
         // candidates); gmask: the same masks per chunk for the table's global tail
@@ -743,10 +709,10 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
             a1 = p_[64 + lane];                                                  \
             a2 = p_[128 + lane];                                                 \
             unsigned long long mk_ = *reinterpret_cast<const lds_u64*>(p_ + (MOFF)); \
-            GF_PIN(a0);                                                          \
-            GF_PIN(a1);                                                          \
-            GF_PIN(a2);                                                          \
-            asm volatile("" : "+v"(mk_));                                        \
+            GF_HERE(a0);                                                         \
+            GF_HERE(a1);                                                         \
+            GF_HERE(a2);                                                         \
+            GF_HERE(mk_);                                                        \
             mk = uniform64(mk_);                                                 \
         } else {                                                                 \
             const SoloTriple t_ = solo_tail_load(gcpu, gmem, ggpu, (c) * kWave + (uint32_t)lane, n_slots); \
@@ -859,7 +825,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                 const int32_t bound_v = read_lane(bound_l, (int)app.shape_x);
                 domx = read_lane64(dom_l, app.shape_x);
                 domd = read_lane64(dom_l, app.shape_d);
-                GF_PHASE(0)
+                GF_TICK(prof, ph, tp, 0)
 
                 // ---- bound test: the executor shape's total capacity is known to be below K (the bound starts at INT32_MAX)
                 if (GF_RARE(K > bound_v)) return kRareBound;
@@ -893,7 +859,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                         clear_family(domd, g, b);  // stale bit of the shape and of its dominators (bits only ever go 1 -> 0)
                     }
                 }
-                GF_PHASE(1)
+                GF_TICK(prof, ph, tp, 1)
                 const uint32_t pc = p0 >> 6;
                 const int pl = (int)(p0 & 63u);
                 // commit of one chunk from values in registers (sparkpods.go:139-146): hit lanes lose one executor request, the
@@ -993,7 +959,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                             // (computed in every lane and selected: a conditional block costs a lone wavefront two execution-mask
                             //  hand-overs, the fourteen instructions cost the same with any mask)
                             int32_t cq = ncap3_fit(r0, r1, r2, app, sh0, sh1, sh2, un0, un1, un2);
-                            GF_PIN(cq);
+                            GF_HERE(cq);
                             const int32_t c0 = fx ? cq : 0;
                             const int32_t incl = wave_inclusive_scan(c0);
                             const int32_t tot = read_lane(incl, kWave - 1);
@@ -1028,7 +994,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                         if (fin) break;
                     }
                 }
-                GF_PHASE(2)
+                GF_TICK(prof, ph, tp, 2)
                 // ---- K == 0 or every executor placed by the lazy scan
                 // (every lane stores the same sixteen bytes to the same address: one write, and no execution-mask save / restore
                 //  around it — with `lane == 0` the store and its mask hand-overs cost the chain 5 %)
@@ -1058,7 +1024,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                         commit_chunk(pc, e0, e1, e2, 0ull);
                     }
                 }
-                GF_PHASE(4)
+                GF_TICK(prof, ph, tp, 4)
                 return kSoloOk;
             }();
             if (GF_RARE(code != kSoloOk)) {
@@ -1082,7 +1048,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
                     row0 = sbits[(size_t)lane * nwp];
                     bound_l = sbound[lane];
                 }
-                GF_PHASE(3)
+                GF_TICK(prof, ph, tp, 3)
                 if (!goes_on) {
                     ++a;
                     break;
@@ -1091,7 +1057,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
         }
 #undef GF_SOLO_LOAD
 #undef GF_SOLO_STORE
-#undef GF_PHASE
         if (lane == 0) {
             sh->final_a = a;
             sh->failed_at = failed_at;

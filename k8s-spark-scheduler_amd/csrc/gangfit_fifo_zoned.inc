@@ -221,7 +221,7 @@ __device__ __forceinline__ int64_t nwave_tight_runs(const ZView& Z, uint32_t n_x
             }
             {  // in every lane, then selected: a conditional block is two execution-mask hand-overs for a lone wavefront
                 int32_t cq = ncap3_fit(a0, a1, a2, p, sh0, sh1, sh2, un0, un1, un2);
-                GF_PIN(cq);
+                GF_HERE(cq);
                 cp = lane_bit(fm) ? cq : 0;
             }
             const int32_t incl = wave_inclusive_scan(cp);
@@ -282,12 +282,11 @@ __device__ __forceinline__ void zshape_rows_init(lds_u64* rows, const lds_u64* l
 // record through LDS costs two dependent round trips: ~600 cycles per record, a third of the staging time).  A request
 // that is not in its table is appended while there is room; rows_init(is_driver, id, v0, v1, v2) prepares what the
 // caller keeps per shape.
-typedef __attribute__((address_space(3))) uint32_t lds_u32z;
 template <class RowsInit>
-__device__ __forceinline__ void zshapes_assign(lds_u32z* recs, uint32_t n_rec, lds_shape3* tab_x, lds_shape3* tab_d, uint32_t& nx,
+__device__ __forceinline__ void zshapes_assign(lds_u32* recs, uint32_t n_rec, lds_shape3* tab_x, lds_shape3* tab_d, uint32_t& nx,
                                                uint32_t& nd, uint32_t n_max, int lane, RowsInit rows_init) {
     int32_t e0 = 0, e1 = 0, e2 = 0, d0 = 0, d1 = 0, d2 = 0;
-    lds_u32z* mine = recs + (size_t)lane * (sizeof(NApp) / 4);
+    lds_u32* mine = recs + (size_t)lane * (sizeof(NApp) / 4);
     if ((uint32_t)lane < n_rec) {
         d0 = (int32_t)mine[0];
         d1 = (int32_t)mine[1];
@@ -365,22 +364,7 @@ __device__ __forceinline__ int32_t zoned_choose_best(int32_t feas, double mx, ui
     // the row (lanes without a source keep their own value) leaves the largest in lane 15 — straight-line code, one
     // scalar read; the candidate-by-candidate loop paid a VALU -> SGPR -> branch round trip per candidate.
     const bool cand = feas != 0 && (uint32_t)lane < n_zone_cand;
-    double x = cand ? mx : -1.0;  // a value that can never win
-#define GF_ROW_MAX_STEP(n)                                                                                              \
-    {                                                                                                                   \
-        const uint64_t u_ = (uint64_t)__double_as_longlong(x);                                                          \
-        const int32_t lo_ = (int32_t)(uint32_t)u_, hi_ = (int32_t)(uint32_t)(u_ >> 32);                                 \
-        const uint32_t l2_ = (uint32_t)__builtin_amdgcn_update_dpp(lo_, lo_, GF_DPP_ROW_SHR(n), 0xf, 0xf, false);       \
-        const uint32_t h2_ = (uint32_t)__builtin_amdgcn_update_dpp(hi_, hi_, GF_DPP_ROW_SHR(n), 0xf, 0xf, false);       \
-        const double y_ = __longlong_as_double((long long)(((uint64_t)h2_ << 32) | l2_));                               \
-        x = __builtin_fmax(y_, x);  /* (no NaN here: divisors are >= 1) one v_max_f64 */                                                                                            \
-    }
-    GF_ROW_MAX_STEP(1)
-    GF_ROW_MAX_STEP(2)
-    GF_ROW_MAX_STEP(4)
-    GF_ROW_MAX_STEP(8)
-#undef GF_ROW_MAX_STEP
-    const double top = bcast_f64(x, 15);
+    const double top = bcast_f64(row_max_f64(cand ? mx : -1.0), 15);  // (-1.0: a value that can never win)
     if (!(top > 0.0)) return -1;
     const uint64_t em = __ballot(cand && mx == top);
     return (int32_t)(__ffsll((unsigned long long)em) - 1);
@@ -393,22 +377,7 @@ constexpr int32_t kChooseUndecided = -2;
 __device__ __forceinline__ int32_t zoned_choose_bounded(int32_t feas, double mx, double err, uint32_t n_zone_cand, int lane) {
     const bool cand = feas != 0 && (uint32_t)lane < n_zone_cand;
     if (__ballot(cand) == 0) return -1;
-    double x = cand ? mx : -1.0;
-#define GF_ROW_MAX_STEP(n)                                                                                              \
-    {                                                                                                                   \
-        const uint64_t u_ = (uint64_t)__double_as_longlong(x);                                                          \
-        const int32_t lo_ = (int32_t)(uint32_t)u_, hi_ = (int32_t)(uint32_t)(u_ >> 32);                                 \
-        const uint32_t l2_ = (uint32_t)__builtin_amdgcn_update_dpp(lo_, lo_, GF_DPP_ROW_SHR(n), 0xf, 0xf, false);       \
-        const uint32_t h2_ = (uint32_t)__builtin_amdgcn_update_dpp(hi_, hi_, GF_DPP_ROW_SHR(n), 0xf, 0xf, false);       \
-        const double y_ = __longlong_as_double((long long)(((uint64_t)h2_ << 32) | l2_));                               \
-        x = __builtin_fmax(y_, x);  /* (no NaN here: divisors are >= 1) one v_max_f64 */                                                                                            \
-    }
-    GF_ROW_MAX_STEP(1)
-    GF_ROW_MAX_STEP(2)
-    GF_ROW_MAX_STEP(4)
-    GF_ROW_MAX_STEP(8)
-#undef GF_ROW_MAX_STEP
-    const double top = bcast_f64(x, 15);
+    const double top = bcast_f64(row_max_f64(cand ? mx : -1.0), 15);
     const uint64_t em = __ballot(cand && mx == top);
     if (em == 0) return kChooseUndecided;  // (a NaN: cannot happen, divisors are >= 1 — the exact round decides)
     const int w = __ffsll((unsigned long long)em) - 1;
@@ -425,25 +394,6 @@ __device__ __forceinline__ int32_t zoned_choose_bounded(int32_t feas, double mx,
     return (int32_t)w;
 }
 
-// Sum over the 64 lanes (wave-uniform result), a DPP tree: every term takes part in at most six additions.
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#define GF_SUM_STEP(ctrl, rmask)                                                                                   \
-    {                                                                                                              \
-        const uint64_t u_ = (uint64_t)__double_as_longlong(v);                                                     \
-        const uint32_t l2_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)(uint32_t)u_, ctrl, rmask, 0xf, false);         \
-        const uint32_t h2_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)(uint32_t)(u_ >> 32), ctrl, rmask, 0xf, false); \
-        v += __longlong_as_double((long long)(((uint64_t)h2_ << 32) | l2_));                                       \
-    }
-    GF_SUM_STEP(GF_DPP_ROW_SHR(1), 0xf)
-    GF_SUM_STEP(GF_DPP_ROW_SHR(2), 0xf)
-    GF_SUM_STEP(GF_DPP_ROW_SHR(4), 0xf)
-    GF_SUM_STEP(GF_DPP_ROW_SHR(8), 0xf)
-    GF_SUM_STEP(GF_DPP_ROW_BCAST15, 0xa)
-    GF_SUM_STEP(GF_DPP_ROW_BCAST31, 0xc)
-#undef GF_SUM_STEP
-    return bcast_f64(v, kWave - 1);
-}
-
 // carry + (v of lane 0, c of lane 0 times) + (v of lane 1, c of lane 1 times) + ... over the first n lanes, every addition
 // performed one after the other in exactly that order (float64 addition does not reassociate; the reference sums a slice).
 // A systolic pass instead of a loop over the runs: lane t owns the steps [start_t, start_t + c_t) — start = exclusive prefix
@@ -451,17 +401,13 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 // step.  What a lane holds outside its window is never read.  No scalar round trips and no branches per run: the looped
 // version (readlane, compare, branch per run and per addition) cost ~200 cycles per run, and the front of a tightly packed
 // order yields ~9 runs of mostly one executor per application.  Every count of the first n lanes must be >= 1.
-#define GF_DPP_WAVE_SHR1 0x138
 __device__ __forceinline__ double wave_serial_sum_runs(double carry, double v, uint32_t c, int n, int lane) {
     const int32_t incl = wave_inclusive_scan((int32_t)c);  // c = 0 beyond lane n - 1
     const uint32_t steps = (uint32_t)read_lane(incl, kWave - 1);
     const uint32_t start = lane == 0 ? 0xFFFFFFFFu : (uint32_t)incl - c;  // lane 0 starts from the carry it already holds
     double acc = carry;
     auto step = [&](uint32_t q) {
-        const uint64_t u = (uint64_t)__double_as_longlong(acc);
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)(uint32_t)u, GF_DPP_WAVE_SHR1, 0xf, 0xf, true);
-        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)(uint32_t)(u >> 32), GF_DPP_WAVE_SHR1, 0xf, 0xf, true);
-        const double prev = __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+        const double prev = dpp_mov<kDppWaveShr1, 0xf, true>(0.0, acc);
         acc = (start == q ? prev : acc) + v;
     };
     uint32_t q = 0;
@@ -528,12 +474,6 @@ __device__ __forceinline__ double wave_runs_avg_max(const View& V, const int64_t
         return avg;
     }
     unsigned long long tq = prof ? __builtin_readcyclecounter() : 0ull;
-#define GF_AVGP(i)                                                   \
-    if (prof) {                                                      \
-        const unsigned long long now = __builtin_readcyclecounter(); \
-        prof[i] += now - tq;                                         \
-        tq = now;                                                    \
-    }
     // element 0 (the driver) is handled as a pseudo run of length 1 in front of the list
     for (int64_t b = -1; b < (int64_t)nruns; b += kWave) {
         const int64_t i = b + lane;
@@ -565,7 +505,7 @@ __device__ __forceinline__ double wave_runs_avg_max(const View& V, const int64_t
         }
         if (prof) {
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            GF_AVGP(0)
+            GF_TICK(prof, prof, tq, 0)
         }
         // cpu quantities are milli-cpus: below 2^32 on any real cluster, but nothing in the ABI says so
         const bool small_cpu = __ballot(valid && ((((uint64_t)(s0 - a0 + r0)) | (uint64_t)s0) >> 32) != 0) == 0;
@@ -577,7 +517,7 @@ __device__ __forceinline__ double wave_runs_avg_max(const View& V, const int64_t
         }
         if (prof) {
             asm volatile("" : "+v"(mx));
-            GF_AVGP(1)
+            GF_TICK(prof, prof, tq, 1)
         }
         const int n = (int64_t)nruns - b < (int64_t)kWave ? (int)((int64_t)nruns - b) : kWave;
         if (!SERIAL) {
@@ -593,10 +533,9 @@ __device__ __forceinline__ double wave_runs_avg_max(const View& V, const int64_t
         }
         if (prof) {
             asm volatile("" : "+v"(max_sum));
-            GF_AVGP(2)
+            GF_TICK(prof, prof, tq, 2)
         }
     }
-#undef GF_AVGP
     const double avg = max_sum / (double)(K + 1);
     if (!SERIAL && err != nullptr)
         *err = unbounded ? __builtin_inf() : (double)(4 * K + 64) * 0x1p-53 * avg;
@@ -624,7 +563,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
 
     // ---- LDS carve
     size_t off = 0;
-    typedef __attribute__((address_space(3))) unsigned char lds_u8;
     lds_u8* stage = (lds_u8*)smem;
     off += (size_t)kZStage * (sizeof(gf_app) + sizeof(NApp));
     typedef __attribute__((address_space(3))) ZonedShared lds_zshared;  // typed: ds_* accesses, no flat/vmcnt waits
@@ -717,12 +655,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
     unsigned long long tph = stats != nullptr ? __builtin_readcyclecounter() : 0ull;
     const unsigned long long t0_cycles = tph;
     const unsigned long long t0_real = wall_clock64();
-#define GF_ZPHASE(i)                                            \
-    if (stats != nullptr) {                                     \
-        const unsigned long long now = __builtin_readcyclecounter(); \
-        ph[i] += now - tph;                                     \
-        tph = now;                                              \
-    }
     for (; a < n_apps; ++a) {
         if ((a % kZStage) == 0) {  // refill the staged app records
             // without the commit barrier a wavefront may still be behind the previous application's decision barrier
@@ -732,7 +664,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             const uint32_t words = n_stage * (uint32_t)(sizeof(gf_app) / 4);
             const uint32_t* gw = reinterpret_cast<const uint32_t*>(apps + a);
             const uint32_t* gn = reinterpret_cast<const uint32_t*>(napps + a);
-            typedef __attribute__((address_space(3))) uint32_t lds_u32;
             lds_u32* sw = (lds_u32*)stage;
             lds_u32* sn = (lds_u32*)(stage + (size_t)kZStage * sizeof(gf_app));
             for (uint32_t i = tid; i < words; i += BLOCK) {
@@ -745,7 +676,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             if (chain_ckpt_due(ck, a) && wave != 0) chain_ckpt_dump(plain, T.n_slots, chain_ckpt_slot(ck, a, T.n_slots), tid, BLOCK);
             if (wave == 0) {  // shape ids of the staged requests (NApp words 14 / 15 = {shape_x, shape_d})
                 uint32_t nx = sh->n_shape_x, nd = sh->n_shape_d;
-                zshapes_assign((lds_u32z*)sn, n_stage, sh->shape_x, sh->shape_d, nx, nd, n_shapes, lane,
+                zshapes_assign((lds_u32*)sn, n_stage, sh->shape_x, sh->shape_d, nx, nd, n_shapes, lane,
                                [&](bool drv, uint32_t id, int32_t v0, int32_t v1, int32_t v2) {
                                    zshape_rows_init(drv ? sbd : sbx, lmasks, lcm, nc, nw, n_views, n_shapes, id, drv, v0, v1, v2, lane);
                                });
@@ -788,7 +719,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
         R.g_slot = spill + (size_t)(2 * wave) * spill_stride + app.exec_off;
         R.g_cnt = spill + (size_t)(2 * wave + 1) * spill_stride + app.exec_off;
 
-        GF_ZPHASE(0)
+        GF_TICK(stats != nullptr, ph, tph, 0)
         if (wait_commit) {  // the helper's commit of the previous application ran next to this staging
             while (__hip_atomic_load(&sh->commit_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != a)
                 __builtin_amdgcn_s_sleep(1);
@@ -836,7 +767,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
                     }
                 }
             }
-            GF_ZPHASE(1)
+            GF_TICK(stats != nullptr, ph, tph, 1)
             double mx = 0.0, me = 0.0;
             my_feasible = feasible;
             if (feasible && zone_view) {
@@ -856,9 +787,9 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             if (feasible && my_nruns > kZRunMax && ew < (uint32_t)NW)  // spilled runs (global): the helper reads them
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         }
-        GF_ZPHASE(2)
+        GF_TICK(stats != nullptr, ph, tph, 2)
         lds_barrier();
-        GF_ZPHASE(3)
+        GF_TICK(stats != nullptr, ph, tph, 3)
         // ---- chooseBestResult (single_az.go:75-97), evaluated identically by every wave
         int32_t best;
         {
@@ -984,14 +915,14 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
                 if (lane == 0) __hip_atomic_store(&sh->commit_done, a + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
         }
-        GF_ZPHASE(4)
+        GF_TICK(stats != nullptr, ph, tph, 4)
         if (kCommitBarrier) {
             if (tail_in_global)
                 __syncthreads();  // commits to the global tail of the table must be visible to the next app's scans
             else
                 lds_barrier();
         }
-        GF_ZPHASE(5)
+        GF_TICK(stats != nullptr, ph, tph, 5)
         if (defer && wave == ew) {
             if (lane == 0) {
                 gf_result r;
@@ -1017,7 +948,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             break;
         }
     }
-#undef GF_ZPHASE
     for (uint32_t r = a + tid; r < n_apps; r += BLOCK) {  // apps behind an abort are reported as not evaluated
         gf_result z;
         z.has_capacity = 0;

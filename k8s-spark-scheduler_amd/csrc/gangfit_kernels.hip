@@ -35,65 +35,7 @@ constexpr int kMfHistBins = 256;  // minimal-fragmentation: capacities below thi
 constexpr int kWavesPerBlock = 4;  // independent-batch kernel: apps (= waves) per workgroup
 constexpr int kMfTeamMax = kWavesPerBlock;          // ... and the wavefronts of a minimal-fragmentation team
 
-// ------------------------------------------------------------------------------------------------ wave primitives
-
-__device__ __forceinline__ int lane_id() { return (int)__lane_id(); }
-
-// DPP control words (gfx9 family): row_shr:n = 0x110+n, row_bcast:15 = 0x142, row_bcast:31 = 0x143.
-#define GF_DPP_ROW_SHR(n) (0x110 + (n))
-#define GF_DPP_ROW_BCAST15 0x142
-#define GF_DPP_ROW_BCAST31 0x143
-
-// Inclusive prefix sum over the 64 lanes of a wave, 7 DPP adds, no LDS traffic.
-__device__ __forceinline__ int32_t wave_inclusive_scan(int32_t v) {
-    int32_t x = v;
-    x += __builtin_amdgcn_update_dpp(0, v, GF_DPP_ROW_SHR(1), 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, v, GF_DPP_ROW_SHR(2), 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, v, GF_DPP_ROW_SHR(3), 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_SHR(4), 0xf, 0xe, false);
-    x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_SHR(8), 0xf, 0xc, false);
-    x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_BCAST15, 0xa, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_BCAST31, 0xc, 0xf, false);
-    return x;
-}
-
-__device__ __forceinline__ int32_t read_lane(int32_t v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ uint32_t read_lane(uint32_t v, int src) {
-    return (uint32_t)__builtin_amdgcn_readlane((int32_t)v, src);
-}
-__device__ __forceinline__ int64_t read_lane(int64_t v, int src) {
-    uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)v, src);
-    uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)((uint64_t)v >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// Maximum of a signed 64-bit value over the 64 lanes (wave-uniform result): row-wise running max with row_shr 1/2/4/8,
-// then row_bcast15 / row_bcast31 carry the row maxima to lane 63.  ~30 VALU instructions, no LDS.
-__device__ __forceinline__ int64_t wave_max_i64(int64_t v) {
-#define GF_MAX_STEP(ctrl, rmask)                                                                              \
-    {                                                                                                         \
-        const int32_t lo = (int32_t)(uint32_t)v, hi = (int32_t)(v >> 32);                                     \
-        const uint32_t tlo = (uint32_t)__builtin_amdgcn_update_dpp(lo, lo, ctrl, rmask, 0xf, false);          \
-        const int32_t thi = __builtin_amdgcn_update_dpp(hi, hi, ctrl, rmask, 0xf, false);                     \
-        const int64_t t = (int64_t)(((uint64_t)(uint32_t)thi << 32) | tlo);                                   \
-        v = t > v ? t : v;                                                                                    \
-    }
-    GF_MAX_STEP(GF_DPP_ROW_SHR(1), 0xf)
-    GF_MAX_STEP(GF_DPP_ROW_SHR(2), 0xf)
-    GF_MAX_STEP(GF_DPP_ROW_SHR(4), 0xf)
-    GF_MAX_STEP(GF_DPP_ROW_SHR(8), 0xf)
-    GF_MAX_STEP(GF_DPP_ROW_BCAST15, 0xa)
-    GF_MAX_STEP(GF_DPP_ROW_BCAST31, 0xc)
-#undef GF_MAX_STEP
-    return read_lane(v, kWave - 1);
-}
-
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also waits for vmcnt(0): with placement stores in
-// flight every barrier would stall for a global-memory round trip (measured: ~2 us per app in the FIFO chain).
-// Data exchanged through this barrier must live in LDS.
-__device__ __forceinline__ void lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
+#include "gangfit_wave.inc"
 
 // ------------------------------------------------------------------------------------------------ app registers
 
@@ -207,8 +149,6 @@ __device__ __forceinline__ uint64_t ge3_mask(int32_t a0, int32_t a1, int32_t a2,
     constexpr int kSGE = 39;  // signed >=
     return __builtin_amdgcn_sicmp(a0, r0, kSGE) & __builtin_amdgcn_sicmp(a1, r1, kSGE) & __builtin_amdgcn_sicmp(a2, r2, kSGE);
 }
-__device__ __forceinline__ uint64_t low_lanes(uint32_t n) { return n >= 64u ? ~0ull : ((1ull << n) - 1ull); }
-__device__ __forceinline__ bool lane_in(uint64_t uniform_mask) { return __builtin_amdgcn_inverse_ballot_w64(uniform_mask); }
 
 template <class A>
 __device__ __forceinline__ bool cap_ge1(typename A::value_t a0, typename A::value_t a1, typename A::value_t a2, const A& app) {
@@ -307,11 +247,7 @@ struct NarrowView {
 
 // FIFO chain: the first `lds_slots` slots of the (mutable) working table live in LDS — the front of the executor
 // priority order is what every app of the chain scans — the tail stays in global memory.
-// The pointers carry explicit address spaces: with generic pointers the compiler folds the two arms into ONE flat_load
-// of a selected address, and every flat access waits on vmcnt(0) — i.e. on all placement stores still in flight.
-typedef __attribute__((address_space(3))) int64_t lds_i64;
-typedef __attribute__((address_space(1))) int64_t glb_i64;
-typedef __attribute__((address_space(3))) uint64_t lds_u64;
+// The pointers carry explicit address spaces (gangfit_wave.inc).
 struct HybridView {
     lds_i64* lcpu;  // LDS, SoA: consecutive lanes read consecutive 8-byte words (ds_read_b64, conflict-free)
     lds_i64* lmem;
@@ -380,7 +316,6 @@ struct HybridView {
 // Slot j's values together with its candidate bit: the mask word and the three values are requested in ONE round trip
 // (testing the bit first costs a second, dependent miss per chunk on a cold L2).  The asm keeps the compiler from sinking
 // the value loads below the bit test again.
-#define GF_KEEP(x) asm volatile("" : "+v"(x))
 template <bool DRV, class View>
 __device__ __forceinline__ bool load_with_cand(const View& V, uint32_t j, uint32_t limit, int64_t& a0, int64_t& a1,
                                                int64_t& a2) {
@@ -389,15 +324,14 @@ __device__ __forceinline__ bool load_with_cand(const View& V, uint32_t j, uint32
     if (j < limit) {
         V.load(j, a0, a1, a2);
         cand = DRV ? V.dcand(j) : V.xcand(j);
-        GF_KEEP(a0);
-        GF_KEEP(a1);
-        GF_KEEP(a2);
+        GF_HERE(a0);
+        GF_HERE(a1);
+        GF_HERE(a2);
     }
     return cand;
 }
 
 // Index tables that never change during a launch.
-typedef __attribute__((address_space(3))) uint32_t lds_u32h;
 struct Orders {
     const uint32_t* slot_node;
     const uint32_t* dslot;
@@ -409,18 +343,18 @@ struct Orders {
     // minimal-fragmentation, histogram form (gangfit_minfrag.inc: wave_minfrag_hist): 3 * kMfHistBins words of LDS private to the
     // calling wavefront, 16-byte aligned, and the snapshot's scaled int32 columns (NodeTable::ncpu ..); nullptr = the
     // pass-per-question walk on the wide table
-    lds_u32h* mf_hist = nullptr;
+    lds_u32* mf_hist = nullptr;
     // a TEAM of wavefronts on one application (gangfit_minfrag.inc: team_minfrag_hist): mf_team wavefronts, this one is mf_rank; the
     // rows of wavefront r start at mf_team_base + r * 3 * kMfHistBins (mf_hist = this wavefront's), mf_words: one word per wavefront
     uint32_t mf_team = 1, mf_rank = 0;
-    lds_u32h* mf_team_base = nullptr;
-    lds_u32h* mf_words = nullptr;
+    lds_u32* mf_team_base = nullptr;
+    lds_u32* mf_words = nullptr;
     bool mf_lent = false;  // (an LDS array may sit at LDS address 0, which compares equal to nullptr: the flag says whether mf_hist is lent)
     const int32_t* ncpu = nullptr;
     const int32_t* nmem = nullptr;
     const int32_t* ngpu = nullptr;
     int64_t nunit0 = 1, nunit1 = 1, nunit2 = 1;
-    __device__ __forceinline__ void lend_minfrag(lds_u32h* lds, const NodeTable& T) {
+    __device__ __forceinline__ void lend_minfrag(lds_u32* lds, const NodeTable& T) {
         mf_hist = lds;
         mf_lent = true;
         ncpu = T.ncpu;
@@ -1242,13 +1176,13 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void fit_independent_kernel(
     Orders O{T.slot_node, T.dslot, T.n_x, T.n_d, T.d_identity != 0};
     if constexpr (ALGO == GF_ALGO_MINIMAL_FRAGMENTATION) {  // the capacity histogram rows of this wavefront
         __shared__ __attribute__((aligned(16))) uint32_t mf_hist[kWavesPerBlock * 3 * kMfHistBins];
-        O.lend_minfrag((lds_u32h*)mf_hist + (size_t)wave * 3 * kMfHistBins, T);
+        O.lend_minfrag((lds_u32*)mf_hist + (size_t)wave * 3 * kMfHistBins, T);
         if constexpr (kMfTeam) {  // the workgroup is a team on ONE application (launch_fit_independent: a workgroup per application)
             __shared__ uint32_t mf_words[kMfTeamMax];
             O.mf_team = (uint32_t)kWavesPerBlock;
             O.mf_rank = wave;
-            O.mf_team_base = (lds_u32h*)mf_hist;
-            O.mf_words = (lds_u32h*)mf_words;
+            O.mf_team_base = (lds_u32*)mf_hist;
+            O.mf_words = (lds_u32*)mf_words;
         }
     }
     // every launch starts with cold L2s: the chunk index of group 0 and the app record are requested together
@@ -1297,19 +1231,9 @@ __device__ __forceinline__ uint32_t block_min(Exchange* X, int& xb, uint32_t wav
     if (NW == 1) return wave_value;
     if (lane == 0) X->first[xb][wave] = wave_value;
     lds_barrier();
-    int32_t x = (int32_t)X->first[xb][lane & 15];
-#define GF_MIN_STEP(n)                                                                                  \
-    {                                                                                                   \
-        const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp(-1, x, GF_DPP_ROW_SHR(n), 0xf, 0xf, false); \
-        x = (int32_t)(t < (uint32_t)x ? t : (uint32_t)x);                                               \
-    }
-    GF_MIN_STEP(1)
-    GF_MIN_STEP(2)
-    GF_MIN_STEP(4)
-    GF_MIN_STEP(8)
-#undef GF_MIN_STEP
+    const uint32_t x = row_min_u32(X->first[xb][lane & 15]);
     xb ^= 1;
-    return (uint32_t)read_lane(x, 15);
+    return read_lane(x, 15);
 }
 
 // Exclusive prefix over the waves (in wave order) and total of a wave-uniform count.
@@ -1324,10 +1248,10 @@ __device__ __forceinline__ void block_scan(Exchange* X, int& xb, int32_t wave_to
     if (lane == 0) X->tot[xb][wave] = wave_total;
     lds_barrier();
     int32_t x = X->tot[xb][lane & 15];
-    x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_SHR(1), 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_SHR(2), 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_SHR(4), 0xf, 0xf, false);
-    x += __builtin_amdgcn_update_dpp(0, x, GF_DPP_ROW_SHR(8), 0xf, 0xf, false);
+    x += dpp_mov<dpp_row_shr(1), 0xf>(0, x);
+    x += dpp_mov<dpp_row_shr(2), 0xf>(0, x);
+    x += dpp_mov<dpp_row_shr(4), 0xf>(0, x);
+    x += dpp_mov<dpp_row_shr(8), 0xf>(0, x);
     xb ^= 1;
     prefix = read_lane(x, wave) - wave_total;
     total = read_lane(x, 15);
@@ -1462,7 +1386,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
     lds_u64* lxm = (lds_u64*)(lmax + 3 * (size_t)T.n_chunks);  // [2][n_chunks] candidate masks
     Exchange* X = reinterpret_cast<Exchange*>(smem + 24 * ((size_t)lds_slots + T.n_chunks) + 16 * (size_t)T.n_chunks);
     FifoShared* sh = reinterpret_cast<FifoShared*>(X + 1);
-    typedef __attribute__((address_space(3))) unsigned char lds_u8;
     lds_u8* dirty = (lds_u8*)(sh + 1);  // [n_chunks] chunk touched by a commit since the last maxima refresh
     for (uint32_t s = tid; s < lds_slots; s += BLOCK) {
         lcpu[s] = T.cpu[s];
@@ -1495,12 +1418,6 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
     unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};  // per-phase cycle accounting (only when stats are requested)
     const bool prof = stats != nullptr;
     unsigned long long tp = prof ? __builtin_readcyclecounter() : 0;
-#define GF_PHASE(idx)                                             \
-    if (prof) {                                                   \
-        const unsigned long long tn = __builtin_readcyclecounter(); \
-        ph[idx] += tn - tp;                                       \
-        tp = tn;                                                  \
-    }
     int xb = 0;
     int32_t failed_at = -1;
     uint32_t a = 0;
@@ -1537,7 +1454,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
         uint32_t* out = exec_nodes + app.exec_off;
         uint32_t* surv = scratch + app.exec_off;
         const bool last = (a + 1 == n_apps);
-        GF_PHASE(0)
+        GF_TICK(prof, ph, tp, 0)
 
         // ---- (1) first fitting driver candidate, BLOCK candidates per step; steps whose chunks the maxima index
         //          rules out are skipped without a barrier (every wave evaluates the same 64-chunk mask)
@@ -1566,7 +1483,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
             }
             if (f != kNoPos) p0 = (int64_t)f;
         }
-        GF_PHASE(1)
+        GF_TICK(prof, ph, tp, 1)
 
         Decision dec;
         dec.feasible = false;
@@ -1604,7 +1521,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
                         if (st.taken >= K) break;
                     }
                 }
-                GF_PHASE(2)
+                GF_TICK(prof, ph, tp, 2)
                 if (st.taken >= K) {
                     dec.feasible = true;
                     dec.pass1 = st.taken;
@@ -1639,7 +1556,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
                     dec.ds = sh->slow_ds;
                     dec.pass1 = sh->slow_pass1;
                     commit = kCommitDone;
-                    GF_PHASE(3)
+                    GF_TICK(prof, ph, tp, 3)
                 }
             }
         }
@@ -1708,9 +1625,8 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
             lds_barrier();
         else
             __syncthreads();
-        GF_PHASE(4)
+        GF_TICK(prof, ph, tp, 4)
     }
-#undef GF_PHASE
     // apps behind an abort are reported as not evaluated
     for (uint32_t r = a + tid; r < n_apps; r += BLOCK) {
         gf_result z;
@@ -1760,10 +1676,16 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t& s) {
     return z ^ (z >> 31);
 }
 
-// Each lane checks (a) the DPP scan against a serial sum through LDS and (b) cap_dim against a plain 64-bit divide on
-// adversarial operands (values adjacent to exact multiples, huge/small divisors, clamp boundaries).
+// Each lane checks (a) the DPP scan against a serial sum through LDS, (b) cap_dim and cap_dim_full against a plain 64-bit divide
+// on adversarial operands (values adjacent to exact multiples, huge/small divisors, clamp boundaries), (c) the narrow domain's
+// division by multiplication, (d) the resident worker's scaled arithmetic and (e) the DPP reductions of gangfit_wave.inc —
+// wave_max_i64, wave_max_i32, row_min_u32, row_max_f64, wave_sum_f64 — against serial loops over the lane values in LDS.
 __global__ __launch_bounds__(kWave) void selftest_kernel(uint64_t seed, uint32_t n_cases, uint32_t* mismatch) {
     __shared__ int32_t vals[kWave];
+    __shared__ int64_t e_i64[kWave];
+    __shared__ int32_t e_i32[kWave];
+    __shared__ uint32_t e_u32[kWave];
+    __shared__ double e_max[kWave], e_sum[kWave];
     const int lane = lane_id();
     uint64_t s = seed + 0x1234567ull * (blockIdx.x * (uint64_t)kWave + lane + 1);
     uint32_t bad = 0;
@@ -1776,6 +1698,49 @@ __global__ __launch_bounds__(kWave) void selftest_kernel(uint64_t seed, uint32_t
         for (int i = 0; i <= lane; ++i) ref += vals[i];
         __syncthreads();
         if (wave_inclusive_scan(v) != ref) ++bad;
+        // (e) the reductions.  int64 of both signs up to 2^62 | int32 with INT32_MIN among them | uint32 with 0xFFFFFFFF among them
+        //     (block_min's "no position") | non-negative doubles, one lane of every row at -1.0 (the choosers' "can never win") |
+        //     integers below 2^40 as doubles: every order of addition is exact, the tree must equal the serial sum bit for bit
+        {
+            const uint64_t q0 = splitmix64(s), q1 = splitmix64(s);
+            int64_t v64 = (q1 >> 16) % 16 == 0 ? INT64_C(1) << 62 : (int64_t)((q0 >> 2) >> ((q1 >> 8) % 56));
+            if (q1 & 1ull) v64 = -v64;
+            const int32_t v32 = (q0 >> 3) % 8 == 0 ? INT32_MIN : (int32_t)(uint32_t)q1;
+            const uint32_t vu = (q1 >> 20) % 2 == 0 ? 0xFFFFFFFFu : (uint32_t)(q0 >> 32);
+            const double vmax = (uint32_t)(lane & 15) == (it & 15u) ? -1.0 : (double)((q1 >> 12) >> ((q0 >> 40) % 50)) * 0x1p-20;
+            const double vsum = (double)(q0 >> 24);
+            e_i64[lane] = v64;
+            e_i32[lane] = v32;
+            e_u32[lane] = vu;
+            e_max[lane] = vmax;
+            e_sum[lane] = vsum;
+            __syncthreads();
+            int64_t want64 = e_i64[0];
+            int32_t want32 = e_i32[0];
+            double want_sum = 0.0;
+            for (int i = 0; i < kWave; ++i) {
+                want64 = e_i64[i] > want64 ? e_i64[i] : want64;
+                want32 = e_i32[i] > want32 ? e_i32[i] : want32;
+                want_sum += e_sum[i];
+            }
+            if (wave_max_i64(v64) != want64) ++bad;
+            if (wave_max_i32(v32) != want32) ++bad;
+            if (__double_as_longlong(wave_sum_f64(vsum)) != __double_as_longlong(want_sum)) ++bad;
+            const uint32_t got_min = row_min_u32(vu);
+            const double got_max = row_max_f64(vmax);
+#pragma unroll
+            for (int row = 0; row < kWave / 16; ++row) {  // lane 15 of each row, as block_min and the choosers read it
+                uint32_t want_min = e_u32[16 * row];
+                double want_max = e_max[16 * row];
+                for (int i = 1; i < 16; ++i) {
+                    want_min = e_u32[16 * row + i] < want_min ? e_u32[16 * row + i] : want_min;
+                    want_max = e_max[16 * row + i] > want_max ? e_max[16 * row + i] : want_max;
+                }
+                if (read_lane(got_min, 16 * row + 15) != want_min) ++bad;
+                if (bcast_f64(got_max, 16 * row + 15) != want_max) ++bad;
+            }
+            __syncthreads();
+        }
         // (b) division
         const uint64_t r0 = splitmix64(s), r1 = splitmix64(s), r2 = splitmix64(s);
         const int ebits = 1 + (int)(r0 % 61);  // divisor magnitude 2^1 .. 2^61

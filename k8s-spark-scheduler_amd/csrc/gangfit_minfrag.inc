@@ -245,9 +245,9 @@ __device__ __forceinline__ void mf_for_each_chunk_narrow(const View& V, const Or
     const int32_t* pcpu = O.ncpu;
     const int32_t* pmem = O.nmem;
     const int32_t* pgpu = O.ngpu;
-    GF_KEEP(pcpu);
-    GF_KEEP(pmem);
-    GF_KEEP(pgpu);
+    GF_HERE(pcpu);
+    GF_HERE(pmem);
+    GF_HERE(pgpu);
     for (uint32_t g = c_lo / kWave; g * kWave < xc; ++g) {
         uint64_t m = chunk_group_mask<false>(V, g, xc, app.exe0, app.exe1, app.exe2, lane);
         if (g * kWave < c_lo) m &= ~low_lanes(c_lo - g * kWave);  // (the range's first group: chunks before c_lo are somebody else's)
@@ -331,9 +331,9 @@ __device__ __forceinline__ bool wave_minfrag_hist(const View& V, const Orders& O
     typedef __attribute__((address_space(3))) mf_u32x4 lds_mf4;
     const int64_t K = app.k;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
-    lds_u32h* const A = O.mf_hist;             // pass 1: count per capacity; plan: nodes a level gives completely
-    lds_u32h* const B = A + kMfHistBins;       // pass 1: first slot per capacity; plan: where the level's runs start in out[]
-    lds_u32h* const C = A + 2 * kMfHistBins;   // pass 2: nodes of the level seen so far
+    lds_u32* const A = O.mf_hist;             // pass 1: count per capacity; plan: nodes a level gives completely
+    lds_u32* const B = A + kMfHistBins;       // pass 1: first slot per capacity; plan: where the level's runs start in out[]
+    lds_u32* const C = A + 2 * kMfHistBins;   // pass 2: nodes of the level seen so far
     lds_mf4* const A4 = (lds_mf4*)A;
     lds_mf4* const B4 = (lds_mf4*)B;
     lds_mf4* const C4 = (lds_mf4*)C;
@@ -343,21 +343,21 @@ __device__ __forceinline__ bool wave_minfrag_hist(const View& V, const Orders& O
     // scalar registers, has none left and reloads every one of them from its spill lane at every use (nineteen v_readlane per
     // chunk of the pass); as vector operands they cost twelve registers and no instruction.
     MfNarrow nv = na;
-    GF_KEEP(nv.drv0);
-    GF_KEEP(nv.drv1);
-    GF_KEEP(nv.drv2);
-    GF_KEEP(nv.exe0);
-    GF_KEEP(nv.exe1);
-    GF_KEEP(nv.exe2);
-    GF_KEEP(nv.mag0);
-    GF_KEEP(nv.mag1);
-    GF_KEEP(nv.mag2);
-    GF_KEEP(nv.sh0);
-    GF_KEEP(nv.sh1);
-    GF_KEEP(nv.sh2);
-    GF_KEEP(nv.un0);
-    GF_KEEP(nv.un1);
-    GF_KEEP(nv.un2);
+    GF_HERE(nv.drv0);
+    GF_HERE(nv.drv1);
+    GF_HERE(nv.drv2);
+    GF_HERE(nv.exe0);
+    GF_HERE(nv.exe1);
+    GF_HERE(nv.exe2);
+    GF_HERE(nv.mag0);
+    GF_HERE(nv.mag1);
+    GF_HERE(nv.mag2);
+    GF_HERE(nv.sh0);
+    GF_HERE(nv.sh1);
+    GF_HERE(nv.sh2);
+    GF_HERE(nv.un0);
+    GF_HERE(nv.un1);
+    GF_HERE(nv.un2);
     int32_t cmax = 0;  // (the largest capacity seen: one comparison behind the pass instead of a branch per chunk)
     mf_for_each_chunk_narrow(V, O, app, nv, ds, lane, [&](uint32_t j, int32_t c) {
         cmax = c > cmax ? c : cmax;
@@ -522,30 +522,30 @@ __device__ __forceinline__ bool team_minfrag_hist(const View& V, const Orders& O
     const int64_t K = app.k;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     const uint32_t team = O.mf_team, rank = O.mf_rank;
-    lds_u32h* const A = O.mf_hist;             // OWN rows — pass 1: count per capacity; plan: nodes a level gives completely
-    lds_u32h* const B = A + kMfHistBins;       // pass 1: first slot per capacity; plan: where the level's runs start in out[]
-    lds_u32h* const C = A + 2 * kMfHistBins;   // pass 2: nodes of the level seen so far (starts at the prefix of the quarters before)
+    lds_u32* const A = O.mf_hist;             // OWN rows — pass 1: count per capacity; plan: nodes a level gives completely
+    lds_u32* const B = A + kMfHistBins;       // pass 1: first slot per capacity; plan: where the level's runs start in out[]
+    lds_u32* const C = A + 2 * kMfHistBins;   // pass 2: nodes of the level seen so far (starts at the prefix of the quarters before)
     lds_mf4* const A4 = (lds_mf4*)A;
     lds_mf4* const B4 = (lds_mf4*)B;
     lds_mf4* const C4 = (lds_mf4*)C;
     A4[lane] = mf_u32x4{0u, 0u, 0u, 0u};
     B4[lane] = mf_u32x4{GF_NO_NODE, GF_NO_NODE, GF_NO_NODE, GF_NO_NODE};
     MfNarrow nv = na;  // (as lane values: wave_minfrag_hist)
-    GF_KEEP(nv.drv0);
-    GF_KEEP(nv.drv1);
-    GF_KEEP(nv.drv2);
-    GF_KEEP(nv.exe0);
-    GF_KEEP(nv.exe1);
-    GF_KEEP(nv.exe2);
-    GF_KEEP(nv.mag0);
-    GF_KEEP(nv.mag1);
-    GF_KEEP(nv.mag2);
-    GF_KEEP(nv.sh0);
-    GF_KEEP(nv.sh1);
-    GF_KEEP(nv.sh2);
-    GF_KEEP(nv.un0);
-    GF_KEEP(nv.un1);
-    GF_KEEP(nv.un2);
+    GF_HERE(nv.drv0);
+    GF_HERE(nv.drv1);
+    GF_HERE(nv.drv2);
+    GF_HERE(nv.exe0);
+    GF_HERE(nv.exe1);
+    GF_HERE(nv.exe2);
+    GF_HERE(nv.mag0);
+    GF_HERE(nv.mag1);
+    GF_HERE(nv.mag2);
+    GF_HERE(nv.sh0);
+    GF_HERE(nv.sh1);
+    GF_HERE(nv.sh2);
+    GF_HERE(nv.un0);
+    GF_HERE(nv.un1);
+    GF_HERE(nv.un2);
     const uint32_t xc = (O.n_x + kWave - 1) / kWave;
     const uint32_t per = (xc + team - 1u) / team;
     const uint32_t c_lo = rank * per < xc ? rank * per : xc, c_hi = c_lo + per < xc ? c_lo + per : xc;

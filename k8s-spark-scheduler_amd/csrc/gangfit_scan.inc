@@ -35,8 +35,6 @@ struct ScanShared {
     unsigned long long s[kWavesPerBlock][kScanZones];  // S_z
     int32_t best[kWavesPerBlock][kScanZones];          // the largest cap' - cap over the zone's fitting driver candidates
 };
-typedef __attribute__((address_space(3))) unsigned long long lds_scan_u64;
-typedef __attribute__((address_space(3))) int32_t lds_scan_i32;
 
 // Sum and maximum over every RUN of lanes that hold the same key (mf_run_heads' runs), left in the run's first lane; `end` = the
 // lane behind this lane's run.  Six steps of doubling reach: a lane takes its neighbour `off` ahead while that one is in the run.
@@ -56,7 +54,7 @@ __device__ __forceinline__ void scan_run_reduce(int32_t& sum, int32_t& mx, int e
 // plain sum and best delta, or to its zone's LDS row.  Returns true (wave-uniform) when the plain answer is already 1.
 template <bool ZONED>
 __device__ __forceinline__ bool scan_chunk(const int64_t* alloc, const int64_t* over, const uint32_t* zone, size_t N, uint32_t n, bool in,
-                                           bool sel, const App& app, int64_t K, int lane, lds_scan_u64* zs, lds_scan_i32* zb, int64_t& S,
+                                           bool sel, const App& app, int64_t K, int lane, lds_ull* zs, lds_i32* zb, int64_t& S,
                                            int32_t& best) {
     int64_t a0 = -1, a1 = -1, a2 = -1;  // (an unselected lane holds nothing and hosts no driver)
     if (sel) {
@@ -95,12 +93,12 @@ __device__ __forceinline__ bool scan_chunk(const int64_t* alloc, const int64_t* 
 }
 
 // The zone rows of a wavefront, emptied / read back: lane z answers for zone z (LDS operations of a wavefront execute in order).
-__device__ __forceinline__ void scan_zones_clear(lds_scan_u64* zs, lds_scan_i32* zb, int lane) {
+__device__ __forceinline__ void scan_zones_clear(lds_ull* zs, lds_i32* zb, int lane) {
     zs[lane] = 0ull;
     zb[lane] = kScanNoDriver;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // (the other lanes of this wavefront add to these rows)
 }
-__device__ __forceinline__ bool scan_zones_answer(lds_scan_u64* zs, lds_scan_i32* zb, int64_t K, int lane) {
+__device__ __forceinline__ bool scan_zones_answer(lds_ull* zs, lds_i32* zb, int64_t K, int lane) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     const int64_t sz = (int64_t)zs[lane];
     const int32_t bz = zb[lane];
@@ -117,8 +115,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void cluster_scan_kernel(Sca
     const App app = load_app(A.apps, a);
     const int64_t K = app.k;
     const size_t N = A.n_nodes;
-    lds_scan_u64* const zs = (lds_scan_u64*)&sh.s[wave][0];
-    lds_scan_i32* const zb = (lds_scan_i32*)&sh.best[wave][0];
+    lds_ull* const zs = (lds_ull*)&sh.s[wave][0];
+    lds_i32* const zb = (lds_i32*)&sh.best[wave][0];
     if (ZONED) scan_zones_clear(zs, zb, lane);
     int64_t S = 0;                    // (plain) the clamped capacities so far, wave-uniform
     int32_t best = kScanNoDriver;     // (plain) this lane's best delta so far
@@ -167,8 +165,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void cluster_scan_sets_kerne
     const size_t N = A.n_nodes;
     const uint32_t W = A.n_words;
     const uint64_t* const row = A.set_words + (size_t)__builtin_amdgcn_readfirstlane(A.app_set[a]) * W;
-    lds_scan_u64* const zs = (lds_scan_u64*)&sh.s[wave][0];
-    lds_scan_i32* const zb = (lds_scan_i32*)&sh.best[wave][0];
+    lds_ull* const zs = (lds_ull*)&sh.s[wave][0];
+    lds_i32* const zb = (lds_i32*)&sh.best[wave][0];
     if (ZONED) scan_zones_clear(zs, zb, lane);
     int64_t S = 0;
     int32_t best = kScanNoDriver;

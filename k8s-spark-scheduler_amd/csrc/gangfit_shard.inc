@@ -577,7 +577,7 @@ __global__ __launch_bounds__(kWave* kFusedWaves) void shard_finish_zoned_kernel(
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 bool done = false;
                 if (K >= 1 && K <= (int64_t)kRunBlocks * kWave)
-                    done = wave_avg_max_tight_runs(EV, app, ds, out, lane, (lds_u32r*)&sh.runs[wave][0], avg[3]);
+                    done = wave_avg_max_tight_runs(EV, app, ds, out, lane, (lds_u32*)&sh.runs[wave][0], avg[3]);
                 if (!done) wave_avg_efficiency_runs<GF_ALGO_TIGHTLY_PACK>(EV, app, ds, out, lane, avg);
             }
         }

@@ -46,13 +46,6 @@ __device__ __forceinline__ bool node_efficiency(int64_t a0, int64_t a1, int64_t 
     return has_gpu;
 }
 
-__device__ __forceinline__ double bcast_f64(double v, int src) {
-    const uint64_t u = (uint64_t)__double_as_longlong(v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)u, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int32_t)(uint32_t)(u >> 32), src);
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
 struct EffView {  // SoA tables in the id space of the placement list
     const int64_t* a0;
     const int64_t* a1;
@@ -349,7 +342,6 @@ struct FusedShared {
     double mx[64];
     uint32_t runs[kFusedWaves][2 * kWave];  // per wavefront: slot and first index of every run of its placement
 };
-typedef __attribute__((address_space(3))) uint32_t lds_u32r;
 
 // avg.Max of a tightly-pack placement (what chooseBestResult compares, single_az.go:75-97) from the placement's RUNS instead of its
 // entries.  wave_avg_efficiency_runs walks the K + 1 entries 64 at a time, and every block of 64 is two dependent global round
@@ -361,7 +353,7 @@ typedef __attribute__((address_space(3))) uint32_t lds_u32r;
 // slice-order sum adds a run's value as many times as the run is long, in order: the same additions in the same order, bit for bit.
 // Returns false (nothing computed) when the placement has more than kRunMax nodes.  1 <= K <= kRunBlocks * 64.
 __device__ __forceinline__ bool wave_avg_max_tight_runs(const EffView& E, const App& app, uint32_t driver,
-                                                        const uint32_t* __restrict__ out, int lane, lds_u32r* rl, double& avg_max) {
+                                                        const uint32_t* __restrict__ out, int lane, lds_u32* rl, double& avg_max) {
     const uint32_t K = (uint32_t)app.k;
     const uint64_t lt_mask = (1ull << lane) - 1ull;
     uint32_t v[kRunBlocks];
@@ -538,7 +530,7 @@ __global__ __launch_bounds__(kWave* kFusedWaves, ALGO == GF_ALGO_MINIMAL_FRAGMEN
         Orders O{T.slot_node, T.dslot, T.n_x, T.n_d, T.d_identity != 0, zone_view};
         if constexpr (ALGO == GF_ALGO_MINIMAL_FRAGMENTATION) {  // the capacity histogram of this wavefront's view
             __shared__ __attribute__((aligned(16))) uint32_t mf_hist[kFusedWaves * 3 * kMfHistBins];
-            O.lend_minfrag((lds_u32h*)mf_hist + (size_t)wave * 3 * kMfHistBins, T);
+            O.lend_minfrag((lds_u32*)mf_hist + (size_t)wave * 3 * kMfHistBins, T);
         }
         unsigned long long xvis = 0, dvis = 0;
         uint32_t* out = zexec + (size_t)c * zexec_stride + app.exec_off;
@@ -568,7 +560,7 @@ __global__ __launch_bounds__(kWave* kFusedWaves, ALGO == GF_ALGO_MINIMAL_FRAGMEN
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
             bool done = false;
             if (ALGO == GF_ALGO_TIGHTLY_PACK && K >= 1 && K <= (int64_t)kRunBlocks * kWave)
-                done = wave_avg_max_tight_runs(EV, app, dec.ds, out, lane, (lds_u32r*)&sh.runs[wave][0], avg[3]);
+                done = wave_avg_max_tight_runs(EV, app, dec.ds, out, lane, (lds_u32*)&sh.runs[wave][0], avg[3]);
             if (!done) wave_avg_efficiency_runs<ALGO>(EV, app, dec.ds, out, lane, avg);
         }
         if (lane == 0) {

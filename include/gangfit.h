@@ -206,7 +206,16 @@ int gf_snapshot_set(gf_ctx *ctx, uint32_t n_nodes, const int64_t *avail_cpu_mill
  *     nodes flagged GF_NODE_DRIVER_CANDIDATE (the Filter request's NodeNames), executor candidates = ready and not
  *     unschedulable; *_label_rank (nullable): rank of the node's value of the configured priority label, UINT32_MAX for
  *     "not ranked" — a stable re-sort of the respective list (:161-199).
- * driver_order_out / exec_order_out (nullable, room for n_nodes entries each) receive the two orders. */
+ * driver_order_out / exec_order_out (nullable, room for n_nodes entries each) receive the two orders.
+ * Where the slot tables are built: on the device (nothing of size O(n_nodes) returns to the host) without label ranks, with
+ * rank arrays that re-sort nothing (NULL, or one value on every node), and with label ranks whose two re-sorted lists are still
+ * subsequences of ONE order — the priority order sorted stably by the driver ranks (by the executor ranks when the driver ranks
+ * re-sort nothing); the sort does that as one more key group and a check on the device decides.  That holds when both lists use
+ * the same label, and when the candidates of the list that is not re-sorted all carry one value of the other list's label
+ * (drivers confined to on-demand nodes while executors prefer spot).  The check is sufficient, not necessary: any other
+ * configuration — lists that conflict, or that would merge in an order this construction does not find — is finalized on the host
+ * through gf_snapshot_set / gf_zones_set / gf_orders_set, as with option "snapshot_finalize_host" = 1.  The installed snapshot,
+ * the two orders and every decision on them are identical either way; gf_snapshot_build_info tells which route a build took. */
 #define GF_NODE_UNSCHEDULABLE 1u
 #define GF_NODE_READY 2u
 #define GF_NODE_DRIVER_CANDIDATE 4u
@@ -232,6 +241,13 @@ int gf_snapshot_build_resident(gf_ctx *ctx, uint32_t n_res, const uint32_t *res_
                                const int64_t *res_mem_bytes, const int64_t *res_gpu, const uint32_t *node_flags,
                                const uint32_t *driver_label_rank, const uint32_t *exec_label_rank,
                                uint32_t *driver_order_out, uint32_t *n_d_out, uint32_t *exec_order_out, uint32_t *n_x_out);
+/* The route of the last gf_snapshot_build / gf_snapshot_build_resident that succeeded on this context:
+ *   out[0]  0 = none yet, 1 = slot tables finalized on the device, 2 = finalized on the host
+ *   out[1]  1 = the priority sort ran a label key group
+ *   out[2]  1 = the label merge check failed and the build fell back to the host
+ *   out[3]  bytes the build copied device -> host, not counting driver_order_out / exec_order_out (saturates at UINT32_MAX)
+ * GF_ERR_INVALID for NULL arguments.  A view reports its parent's build, a multi-device context its first device's. */
+int gf_snapshot_build_info(gf_ctx *ctx, uint32_t out[4]);
 /* The third step of keeping the snapshot resident ("keep snapshot resident on device across requests and
  * apply deltas"): the per-node usage sums of UsageForNodes (LIB/resources/resources.go:31-43) stay on the device next to the
  * cluster columns.  gf_cluster_set zeroes them (a new node set starts from nothing); gf_usage_apply adds (sign = +1: a

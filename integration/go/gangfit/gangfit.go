@@ -533,6 +533,19 @@ func (c *Context) buildResidentLocked(requestFlags []uint32) error {
 	return nil
 }
 
+// BuildInfo reports the route of the last snapshot build of this context (gf_snapshot_build_info): route 0 = none yet,
+// 1 = slot tables finalized on the device, 2 = on the host; whether the priority sort ran a label key group; whether the label
+// merge check failed and the build fell back; the bytes the build copied device -> host.
+func (c *Context) BuildInfo() (route int, labelGroup, mergeFailed bool, d2hBytes uint32, err error) {
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	var out [4]C.uint32_t
+	if rc := C.gf_snapshot_build_info(c.ctx, &out[0]); rc != C.GF_OK {
+		return 0, false, false, 0, c.err(rc)
+	}
+	return int(out[0]), out[1] != 0, out[2] != 0, uint32(out[3]), nil
+}
+
 // FilterResident is one driver Filter of the resident flow: build this request's snapshot from the resident cluster and
 // usage, then run the FIFO chain (or an independent batch) on it — under ONE hold of the context lock, so that a FitBatch,
 // FindNodes or ClusterSet of another goroutine (the UnschedulablePodMarker runs next to Predicate, cmd/server.go:230) can

@@ -3,6 +3,7 @@
 // one place a layout becomes current, shared with the on-device finalize of gf_snapshot_build*.  Then the resident cluster columns
 // and usage sums, and gf_snapshot_build* (reservation replay + metadata + priority sort, slot tables on the device or the host).
 #include "gangfit_ctx.h"
+#include "gangfit_label_plan.h"
 
 using namespace gfapi;
 
@@ -556,13 +557,15 @@ struct BuildScratch {
     unsigned long long* gcd_part;  // gcd partials | magnitude partials
     long long* units;
     uint32_t *perm_a, *perm_b, *perm_c, *res_node, *zone_order, *zone_rank, *zfirst, *zhasx, *zeval, *scalars;  // d_bu32
+    uint32_t *label_d, *label_x, *perm_p, *ppos;  // the request's label ranks | the priority order and its inverse (label group)
+    unsigned long long* merge_summary;            // LabelMerge::d_summary
 };
 
 int carve_build_scratch(gf_ctx* ctx, size_t R, BuildScratch* out) {
     const size_t N = ctx->cl_n, Z = ctx->cl_zones;
     const size_t NCH = (N + 1 + 63) / 64;  // chunks of the slot space (nodes + sentinel)
-    GF_HIP(ctx, ctx->d_bi64.reserve(9 * N + 3 * N + 3 * R + 3 * Z + 6 * NCH + 16));
-    GF_HIP(ctx, ctx->d_bu32.reserve(3 * N + R + 5 * Z + 16));
+    GF_HIP(ctx, ctx->d_bi64.reserve(9 * N + 3 * N + 3 * R + 3 * Z + 6 * NCH + 16 + 4 * (size_t)gangfit::kLabelMergeUnits));
+    GF_HIP(ctx, ctx->d_bu32.reserve(3 * N + R + 5 * Z + 16 + 4 * N));
     BuildScratch& s = *out;
     s.alloc = ctx->d_cl_i64.ptr;
     s.over = s.alloc + 3 * N;
@@ -589,10 +592,15 @@ int carve_build_scratch(gf_ctx* ctx, size_t R, BuildScratch* out) {
     s.zhasx = s.zfirst + Z;
     s.zeval = s.zhasx + Z;
     s.scalars = s.zeval + Z;  // 16 words
+    s.label_d = s.scalars + 16;
+    s.label_x = s.label_d + N;
+    s.perm_p = s.label_x + N;
+    s.ppos = s.perm_p + N;
+    s.merge_summary = reinterpret_cast<unsigned long long*>(s.units + 8);  // (units: 6 words)
     return GF_OK;
 }
 
-gangfit::SnapshotBuild build_args(gf_ctx* ctx, const BuildScratch& s, uint32_t n_res, bool usage_resident) {
+gangfit::SnapshotBuild build_args(gf_ctx* ctx, const BuildScratch& s, uint32_t n_res, bool usage_resident, const LabelPlan& lp) {
     gangfit::SnapshotBuild b{};
     b.n_nodes = ctx->cl_n;
     b.n_res = n_res;
@@ -621,11 +629,26 @@ gangfit::SnapshotBuild build_args(gf_ctx* ctx, const BuildScratch& s, uint32_t n
     b.d_zhasx = s.zhasx;
     b.zhasx_to_scalars_words = 2 * (size_t)ctx->cl_zones + 16;  // d_zhasx | d_zeval | d_scalars
     b.d_sort_work = ctx->d_sortwork.ptr;
+    if (lp.device_route && lp.which != 0) {  // the label key group: d_perm_b receives C, d_perm_p keeps the priority order
+        b.d_label = lp.which == 1 ? s.label_d : s.label_x;
+        b.label_max = lp.max_rank;
+        b.label_width = lp.width;
+        b.d_perm_p = s.perm_p;
+        b.d_ppos = s.ppos;
+    }
     return b;
 }
 
+// What gf_snapshot_build_info reports; a build commits it when it has succeeded.
+struct BuildInfo {
+    uint32_t route = 0, label_group = 0, merge_failed = 0;
+    uint64_t d2h_bytes = 0;
+};
+
 // The slot tables on the device too: nothing of size O(n_nodes) returns to the host unless the caller asks for the orders.
-int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out) {
+// Behind a label key group s.perm_b holds C, not the priority order: when the merge check has flagged it (the two lists are not
+// both subsequences of C) nothing is installed, info->merge_failed is set and the caller takes the host route.
+int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out, BuildInfo* info) {
     hipStream_t st = ctx->stream;
     const uint32_t n = ctx->cl_n, n_slots = n + 1, n_chunks = (n_slots + 63) / 64;
     const size_t N = n, S = n_slots, C = n_chunks, Z = ctx->cl_zones;
@@ -681,7 +704,12 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out)
     GF_HIP(ctx, gangfit::launch_snapshot_finalize(f, ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word(), st));
     if (f.h_out == nullptr) GF_HIP(ctx, hipMemcpyAsync(h_scalars, s.scalars, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     GF_HIP(ctx, gf_wait_stream(st));
-    if (h_scalars[3] != 0) return fail(ctx, GF_ERR_HIP, "the priority sort's grid barrier gave up (device oversubscribed?)");
+    info->d2h_bytes += 16 * sizeof(uint32_t);
+    if (h_scalars[3] & 1u) return fail(ctx, GF_ERR_HIP, "the priority sort's grid barrier gave up (device oversubscribed?)");
+    if (h_scalars[3] & 2u) {
+        info->merge_failed = 1;
+        return GF_OK;
+    }
     // ---- the snapshot itself (what gf_snapshot_set + gf_zones_set record on the host path) ...
     ctx->have_sched = h_scalars[2] == 0;  // a negative schedulable value (overhead above allocatable) disables the efficiencies
     ctx->n_nodes = n;
@@ -717,16 +745,20 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out)
 }
 
 // The sorted snapshot returns to the host and is installed through the public setters: the optional stable label re-sorts
-// (nodesorting.go:161-199) can break the merged layout, which only gf_orders_set handles.
-int finalize_on_host(gf_ctx* ctx, const BuildScratch& s, const uint32_t* driver_label_rank, const uint32_t* exec_label_rank,
-                     const OrderOuts& out) {
+// (nodesorting.go:161-199) can break the merged layout, which only gf_orders_set handles.  Taken when the label merge check has
+// failed (the re-sorted lists are not both subsequences of the sort's one order), with option "snapshot_finalize_host" = 1, and
+// never otherwise: label ranks whose lists still merge are finalized on the device (gangfit_label_plan.h).
+// d_order: the priority order on the device (s.perm_b, or s.perm_p behind a label key group).
+int finalize_on_host(gf_ctx* ctx, const BuildScratch& s, const uint32_t* d_order, const uint32_t* driver_label_rank,
+                     const uint32_t* exec_label_rank, const OrderOuts& out, BuildInfo* info) {
     hipStream_t st = ctx->stream;
     const uint32_t n = ctx->cl_n;
     const size_t N = n;
     GF_HIP(ctx, ctx->h_bcols.reserve(6 * N));
     GF_HIP(ctx, ctx->h_border.reserve(N + 8));
     GF_HIP(ctx, hipMemcpyAsync(ctx->h_bcols.ptr, s.avail, 6 * N * sizeof(int64_t), hipMemcpyDeviceToHost, st));  // avail | sched
-    GF_HIP(ctx, hipMemcpyAsync(ctx->h_border.ptr, s.perm_b, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    GF_HIP(ctx, hipMemcpyAsync(ctx->h_border.ptr, d_order, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    info->d2h_bytes += 6 * N * sizeof(int64_t) + N * sizeof(uint32_t) + sizeof(uint32_t);
     GF_HIP(ctx, hipMemcpyAsync(ctx->h_failed.ptr, ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word(), sizeof(uint32_t),
                                hipMemcpyDeviceToHost, st));
     GF_HIP(ctx, gf_wait_stream(st));
@@ -791,12 +823,23 @@ extern "C" int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uin
     const uint32_t* const flags_upload = node_flags ? node_flags : (ctx->d_flags_default ? nullptr : ctx->cl_default_flags.data());
     const int64_t* const rcols[3] = {res_cpu_milli, res_mem_bytes, res_gpu};
     if (int rc = check_reservations(ctx, n_res, res_node, rcols); rc != GF_OK) return rc;
+    BuildInfo info;
+    auto done = [&](int rc, uint32_t route) {  // what gf_snapshot_build_info reports: the last build that succeeded
+        if (rc != GF_OK) return rc;
+        ctx->build_info[0] = route;
+        ctx->build_info[1] = info.label_group;
+        ctx->build_info[2] = info.merge_failed;
+        ctx->build_info[3] = info.d2h_bytes > UINT32_MAX ? UINT32_MAX : (uint32_t)info.d2h_bytes;
+        return rc;
+    };
     if (n == 0) {
         int rc = gf_snapshot_set(ctx, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
         if (rc != GF_OK) return rc;
         out.counts(0, 0);
-        return gf_orders_set(ctx, nullptr, 0, nullptr, 0);
+        return done(gf_orders_set(ctx, nullptr, 0, nullptr, 0), 2);
     }
+    const LabelPlan lp = plan_labels(n, driver_label_rank, exec_label_rank, ctx->snapshot_finalize_on_device);
+    const bool label_group = lp.device_route && lp.which != 0;
     GF_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     const size_t N = n, R = n_res;
@@ -810,10 +853,32 @@ extern "C" int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uin
         GF_HIP(ctx, hipMemcpyAsync(s.flags, flags_upload, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         ctx->d_flags_default = node_flags == nullptr;
     }
+    if (label_group) {  // the rank arrays that re-sort something: 4 bytes per node each, like the flags
+        if (lp.driver_active)
+            GF_HIP(ctx, hipMemcpyAsync(s.label_d, driver_label_rank, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (lp.exec_active) GF_HIP(ctx, hipMemcpyAsync(s.label_x, exec_label_rank, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
     GF_HIP(ctx, ctx->d_sortwork.reserve(gangfit::snapshot_sort_work_words()));
-    GF_HIP(ctx, gangfit::launch_snapshot_build(build_args(ctx, s, n_res, usage_resident), st));
-    if (ctx->snapshot_finalize_on_device && !driver_label_rank && !exec_label_rank) return finalize_on_device(ctx, s, out);
-    return finalize_on_host(ctx, s, driver_label_rank, exec_label_rank, out);
+    GF_HIP(ctx, gangfit::launch_snapshot_build(build_args(ctx, s, n_res, usage_resident, lp), st));
+    if (lp.device_route) {
+        if (label_group) {
+            info.label_group = 1;
+            gangfit::LabelMerge m{};
+            m.n_nodes = n;
+            m.d_order = s.perm_b;
+            m.d_flags = s.flags;
+            m.d_ppos = s.ppos;
+            m.d_rank[0] = lp.driver_active ? s.label_d : nullptr;
+            m.d_rank[1] = lp.exec_active ? s.label_x : nullptr;
+            m.d_summary = s.merge_summary;
+            m.d_fail = ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word() + 1;
+            GF_HIP(ctx, gangfit::launch_label_merge_check(m, st));
+        }
+        const int rc = finalize_on_device(ctx, s, out, &info);
+        if (rc != GF_OK || !info.merge_failed) return done(rc, 1);
+    }
+    // (behind a label key group the sort left the priority order itself in perm_p)
+    return done(finalize_on_host(ctx, s, label_group ? s.perm_p : s.perm_b, driver_label_rank, exec_label_rank, out, &info), 2);
 }
 
 extern "C" {
@@ -851,6 +916,15 @@ int gf_residual_get(gf_ctx* ctx, int64_t* avail_out) {
         for (int j = 0; j < 3; ++j)
             avail_out[3 * (size_t)n + j] = (s == GF_NO_NODE) ? ctx->avail[j][n] : t[(size_t)j * ctx->n_slots + s];
     }
+    return GF_OK;
+}
+
+int gf_snapshot_build_info(gf_ctx* ctx, uint32_t out[4]) {
+    GF_DELEGATE(ctx, gf_snapshot_build_info(ctx, out));
+    if (!ctx || !out) return GF_ERR_INVALID;
+    gf_ctx* const src = ctx->view_of != nullptr ? ctx->view_of : ctx;  // a view fits on its parent's snapshot: its parent's build
+    std::lock_guard<std::recursive_mutex> lock(src->mu);
+    for (int i = 0; i < 4; ++i) out[i] = src->build_info[i];
     return GF_OK;
 }
 

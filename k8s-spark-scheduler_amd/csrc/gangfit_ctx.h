@@ -373,9 +373,10 @@ struct gf_ctx {
 
     // gf_snapshot_build
     DeviceBuf<int64_t> d_bi64;   // alloc | overhead | usage | avail | sched (3n each) | keys_a | keys_b (n each) | res_req (3r) | zone_sum
-    DeviceBuf<uint32_t> d_bu32;  // zone | name_rank | perm_a | perm_b (n each) | res_node (r) | zone_order | zone_rank
+    DeviceBuf<uint32_t> d_bu32;  // zone | name_rank | perm_a | perm_b (n each) | res_node (r) | zone_order | zone_rank | ... (BuildScratch)
     PinnedBuf<int64_t> h_bcols;  // avail | sched (3n each)
     PinnedBuf<uint32_t> h_border;
+    uint32_t build_info[4] = {0, 0, 0, 0};  // gf_snapshot_build_info: route | label group ran | merge check failed | bytes device -> host
 
     // single-executor requests (gf_executor_fit)
     DeviceBuf<int64_t> d_xexe, d_xreserved;

@@ -487,7 +487,31 @@ struct SnapshotBuild {
     uint32_t* d_zfirst = nullptr;  // n_zones words, set to all ones
     uint32_t* d_zhasx = nullptr;   // the range d_zhasx | d_zeval | d_scalars[0 .. 16), set to zero ...
     size_t zhasx_to_scalars_words = 0;  // ... this many words
+    // the label key group (nodesorting.go:161-199; gangfit_label_plan.h decides): one more most-significant group of the same
+    // sort, a stable sort by the node's label rank on top of the priority order.  d_label == nullptr or label_width == 0: none,
+    // d_perm_b holds the priority order P.  Otherwise d_perm_b holds C (all nodes by (rank, position in P)), d_perm_p holds P
+    // and d_ppos[node] = the node's position in P.
+    const uint32_t* d_label = nullptr;  // n_nodes: rank of the node's label value, UINT32_MAX = not ranked (behind every ranked one)
+    uint32_t label_max = 0;             // largest ranked value: the key is the rank itself, "not ranked" = label_max + 1
+    uint32_t label_width = 0;           // bits of label_max + 1
+    uint32_t* d_perm_p = nullptr;       // n_nodes
+    uint32_t* d_ppos = nullptr;         // n_nodes
 };
+// The merge check behind a label key group: the reference's list of a role R (driver candidates / executor candidates) is
+// stable_sort(filter(P, R), rank_R); it equals filter(C, R) exactly when the pairs (rank_R[n], ppos[n]) of R's candidates are
+// strictly increasing along C.  One pass over C; a violation sets *d_fail (never cleared here).  SUFFICIENT, not necessary, for
+// the two lists to fit one slot order: lists that merge in an order this construction does not find are flagged too.
+constexpr uint32_t kLabelMergeUnits = 1024;  // wavefronts of the pass = rows of d_summary
+struct LabelMerge {
+    uint32_t n_nodes;
+    const uint32_t* d_order;    // C: n_nodes
+    const uint32_t* d_flags;    // n_nodes: GF_NODE_*
+    const uint32_t* d_ppos;     // n_nodes
+    const uint32_t* d_rank[2];  // driver | executor label ranks by node; nullptr = every rank equal
+    unsigned long long* d_summary;  // 4 * kLabelMergeUnits words: per wavefront and role, its first and last candidate's pair
+    uint32_t* d_fail;
+};
+hipError_t launch_label_merge_check(const LabelMerge& m, hipStream_t stream);
 // usage[node] += sign * entry for n_entries reservation entries (columns cpu | memory | gpu of d_req); entries on nodes
 // >= n_nodes are ignored.
 // d_negative (nullable): after a removal (sign < 0) bit 0 is set when a touched node's sum went below zero.
@@ -535,7 +559,8 @@ struct SnapshotFinalize {
     uint32_t* d_zhasx;          // n_zones
     uint32_t* d_zeval;          // n_zones: zone -> index in the evaluation list, GF_NO_NODE = not evaluated
     uint32_t* d_scalars;        // 16 words: [0] = zones in the evaluation list, [1] = no narrow form, [2] = negative schedulable
-                                // value, [3] = the sort's error word, [4 .. 16) = d_units as pairs of words (one read-back)
+                                // value, [3] = the sort's error word (bit 0) | the label merge check failed (bit 1), [4 .. 16) = d_units as pairs of words
+                                // (one read-back)
     uint32_t* h_out = nullptr;  // nullable: the device's address of sixteen pinned host words, ZEROED BY THE HOST before the launch, that
                                 // receive d_scalars as the kernels produce it (no read-back copy on the stream)
     uint64_t* d_zmasks;         // 2 * n_zones * n_chunks: executor rows, then (from row n_zones) driver rows
@@ -553,7 +578,8 @@ hipError_t launch_stream_copy(const void* src, void* dst, size_t bytes, hipStrea
 hipError_t launch_stream_read(const void* src, size_t bytes, uint32_t* sink, hipStream_t stream);
 hipError_t launch_empty(uint32_t* sink, hipStream_t stream);
 size_t snapshot_sort_work_words();     // uint32 words of SnapshotBuild::d_sort_work
-uint32_t snapshot_sort_error_word();   // index of the word that is non-zero when the sort's grid barrier gave up
+uint32_t snapshot_sort_error_word();   // index of the word that is non-zero when the sort's grid barrier gave up; the word behind
+                                       // it is LabelMerge::d_fail of the same build (launch_snapshot_finalize reads both)
 hipError_t launch_snapshot_build(const SnapshotBuild& b, hipStream_t stream);
 
 // Device self-test of the wave primitives (DPP scan, exact clamped division) against plain reference code.

@@ -230,6 +230,9 @@ __global__ void zone_rank_kernel(uint32_t n_zones, const long long* __restrict__
 //      scatter — and count the NEXT pass's digit into the destination segment's row while the key is in a register
 //      (order-free atomic adds).  A pass therefore costs ONE grid barrier, the key build (which counts the first digit) one,
 //      and the last pass none: three rotating buffers are walked so that it lands in the output array.
+//   4. the optional label key group (nodesorting.go:161-199, a stable sort by a small rank on top of the order): one more
+//      most-significant group of the same sort — at most four passes, one for any real configuration.  Its key build walks P,
+//      the priority order the groups before it produced, and keeps it: P itself in perm_p, every node's position in ppos.
 // A wavefront alone on its SIMD issues at its full rate; 64 of them sort 100 000 nodes in a fraction of the millisecond one
 // workgroup needed (860 us measured) and of the two dozen launches of a sorting library.  What is left is the barrier: the
 // XCDs' L2s are not coherent with each other, so each one is a write-back, an invalidate and a round trip to memory.
@@ -239,7 +242,7 @@ constexpr int kSortKeyTile = 8;           // ... in the key build (a node id, th
 constexpr int kSortRowBatch = 32;         // rows of the count table requested together (behind a grid barrier every one of them
                                           // is a round trip to memory: eight at a time made a pass of 64 rows eight round trips)
 constexpr uint32_t kSortHistWords = 3u * kSortWG * 256u;  // three rotating count tables [segment][digit]
-constexpr uint32_t kSortStateWords = 4u;  // barrier count | barrier generation | error | spare
+constexpr uint32_t kSortStateWords = 4u;  // barrier count | barrier generation | error | the label merge check failed
 constexpr uint32_t kSortScalars = 16u;    // 64-bit words behind the state (the first six: metadata_kernel's ranges)
 
 struct PrioritySort {
@@ -253,6 +256,12 @@ struct PrioritySort {
     uint32_t* perm[3];         // [0] holds the name order at launch, [1] receives the result: position -> node
     uint32_t* work;            // kSortHistWords + kSortStateWords uint32 + kSortScalars uint64; zero at launch but the ranges
     uint32_t spin_limit;       // probes of the barrier word before a wavefront gives up (2^24: about half a second)
+    // the label key group (SnapshotBuild::d_label): runs behind the others when label != nullptr and label_width != 0
+    const uint32_t* label;     // label rank by node, UINT32_MAX = not ranked
+    uint32_t label_max;        // largest ranked value; key = the rank, "not ranked" = label_max + 1
+    uint32_t label_width;      // bits_of(label_max + 1)
+    uint32_t* perm_p;          // receives P, the order before the label group (the rotating buffers are reused by its passes)
+    uint32_t* ppos;            // ppos[node] = position in P
 };
 
 __device__ __forceinline__ uint32_t bits_of(unsigned long long v) { return v ? 64u - (uint32_t)__clzll(v) : 0u; }
@@ -336,11 +345,17 @@ __global__ __launch_bounds__(64) void priority_sort_kernel(PrioritySort A) {
     const uint32_t wz = bits_of((unsigned long long)A.n_zones);  // unknown zone ids rank behind every zone (value n_zones)
     // ---- 2. key groups, least significant first: {cpu, mem, zone} | {cpu} {mem, zone} | {cpu} {mem} {zone}
     const uint32_t n_groups = (wc + wm + wz <= 64u) ? 1u : ((wm + wz <= 64u) ? 2u : 3u);
-    uint32_t gw[3] = {0, 0, 0}, total_passes = 0;
+    uint32_t gw[4] = {0, 0, 0, 0}, total_passes = 0;
     for (uint32_t g = 0; g < n_groups; ++g) {
         const bool has_c = g == 0, has_m = n_groups == 1 || g == 1, has_z = g + 1 == n_groups;
         gw[g] = (has_c ? wc : 0u) + (has_m ? wm : 0u) + (has_z ? wz : 0u);
         total_passes += (gw[g] + 7u) / 8u;
+    }
+    // ... and the label group behind them (group n_groups)
+    const uint32_t n_all = n_groups + ((A.label != nullptr && A.label_width != 0u) ? 1u : 0u);
+    if (n_all > n_groups) {
+        gw[n_groups] = A.label_width;
+        total_passes += (A.label_width + 7u) / 8u;
     }
     // segments: a power of two of elements (whole chunks) so that the segment of an output position is a shift
     uint32_t seg_log = 6;
@@ -351,8 +366,9 @@ __global__ __launch_bounds__(64) void priority_sort_kernel(PrioritySort A) {
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     uint32_t src = 0;  // buffer that holds the current order
     uint32_t P = 0;    // passes done so far (all groups): pass P reads count table P % 3, feeds (P + 1) % 3, clears (P + 2) % 3
-    for (uint32_t g = 0; g < n_groups; ++g) {
-        const bool has_c = g == 0, has_m = n_groups == 1 || g == 1, has_z = g + 1 == n_groups;
+    for (uint32_t g = 0; g < n_all; ++g) {
+        const bool is_l = g == n_groups;
+        const bool has_c = !is_l && g == 0, has_m = !is_l && (n_groups == 1 || g == 1), has_z = !is_l && g + 1 == n_groups;
         const uint32_t width = gw[g];
         if (width == 0) continue;  // every key of the group equal: the order stands (uniform over the grid)
         // ---- keys of this group in the current order (this wavefront's segment) + the counts of their first digit
@@ -377,6 +393,11 @@ __global__ __launch_bounds__(64) void priority_sort_kernel(PrioritySort A) {
                     vc[t] = (has_c && i < hi) ? A.cpu[node[t]] : 0;
                     vm[t] = (has_m && i < hi) ? A.mem[node[t]] : 0;
                     zid[t] = (has_z && i < hi) ? A.zone[node[t]] : 0u;
+                    if (is_l && i < hi) {  // (zid carries the label rank; the current order is P: keep it)
+                        zid[t] = A.label[node[t]];
+                        A.perm_p[i] = node[t];
+                        A.ppos[node[t]] = i;
+                    }
                 }
 #pragma unroll
                 for (int t = 0; t < kSortKeyTile; ++t) {
@@ -399,6 +420,7 @@ __global__ __launch_bounds__(64) void priority_sort_kernel(PrioritySort A) {
                             const unsigned long long zr = z < A.n_zones ? (zr_local ? zrank_l[z] : A.zrank[z]) : A.n_zones;
                             if (sft < 64u) key |= zr << sft;
                         }
+                        if (is_l) key = zid[t] > A.label_max ? (unsigned long long)A.label_max + 1ull : zid[t];
                         kin[i] = key;
                     }
                     const uint32_t d = (uint32_t)key & 255u;
@@ -503,7 +525,88 @@ __global__ __launch_bounds__(64) void priority_sort_kernel(PrioritySort A) {
         for (uint32_t i = lo + lane; i < hi; i += 64u) A.perm[1][i] = A.perm[0][i];
 }
 
+// ------------------------------------------------------------------------------------------------ the label merge check
+// LabelMerge (gangfit_device.h): along C the pairs (rank_R[n], ppos[n]) of a role's candidates must be strictly increasing.
+// A pair travels as one 64-bit word + 1 (rank high, position low: never 0, never all ones), so 0 stands for "no candidate
+// before" and all ones for "no candidate at all".  A wavefront walks a contiguous run of 64-element chunks of C: every
+// candidate lane compares with the candidate lane before it in the chunk, the first one with the carry of the chunks before.
+// What crosses a wavefront's run — its first and its last pair per role — goes to d_summary for label_merge_carry_kernel.
+__global__ __launch_bounds__(64) void label_merge_check_kernel(LabelMerge m) {
+    const uint32_t lane = threadIdx.x, unit = blockIdx.x, units = gridDim.x;
+    const uint32_t n = m.n_nodes, n_chunks = (n + 63u) / 64u;
+    const uint32_t per = (n_chunks + units - 1u) / units;
+    const uint32_t c0 = unit * per < n_chunks ? unit * per : n_chunks, c1 = c0 + per < n_chunks ? c0 + per : n_chunks;
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    unsigned long long carry[2] = {0ull, 0ull}, first[2] = {~0ull, ~0ull};
+    bool bad = false;
+    for (uint32_t c = c0; c < c1; ++c) {
+        const uint32_t i = c * 64u + lane;
+        const bool valid = i < n;
+        const uint32_t node = valid ? m.d_order[i] : 0u;
+        const uint32_t fl = valid ? m.d_flags[node] : 0u;
+        const uint32_t pp = valid ? m.d_ppos[node] : 0u;
+#pragma unroll
+        for (int role = 0; role < 2; ++role) {
+            const bool cand = valid && (role == 0 ? (fl & GF_NODE_DRIVER_CANDIDATE) != 0u
+                                                  : (!(fl & GF_NODE_UNSCHEDULABLE) && (fl & GF_NODE_READY)));
+            const uint32_t r = (cand && m.d_rank[role] != nullptr) ? m.d_rank[role][node] : 0u;
+            const unsigned long long key = (((unsigned long long)r << 32) | pp) + 1ull;
+            const unsigned long long mask = __ballot(cand);
+            if (mask == 0ull) continue;  // wave-uniform
+            const unsigned long long before = mask & lt_mask;
+            const int prev_lane = before ? 63 - __clzll((long long)before) : (int)lane;
+            const unsigned long long pk = __shfl(key, prev_lane, 64);
+            const unsigned long long prev = before ? pk : carry[role];
+            bad = bad || (cand && key <= prev);
+            const unsigned long long head = __shfl(key, __ffsll((long long)mask) - 1, 64);
+            if (first[role] == ~0ull) first[role] = head;
+            carry[role] = __shfl(key, 63 - __clzll((long long)mask), 64);
+        }
+    }
+    if (__ballot(bad) != 0ull && lane == 0) atomicOr(m.d_fail, 1u);
+    if (lane < 4u) m.d_summary[4u * unit + lane] = (lane & 1u) ? carry[lane >> 1] : first[lane >> 1];
+}
+
+// The wavefronts' runs against each other: a run's first pair must lie above every last pair before it (with the runs
+// themselves increasing, that is the last pair of the nearest run that has a candidate).  One wavefront, 64 runs per step.
+__global__ __launch_bounds__(64) void label_merge_carry_kernel(const unsigned long long* __restrict__ summary, uint32_t units,
+                                                               uint32_t* __restrict__ fail) {
+    const uint32_t lane = threadIdx.x;
+    bool bad = false;
+    for (uint32_t role = 0; role < 2u; ++role) {
+        unsigned long long carry = 0ull;
+        for (uint32_t base = 0; base < units; base += 64u) {
+            const uint32_t u = base + lane;
+            const unsigned long long f = u < units ? summary[4u * u + 2u * role] : ~0ull;
+            const unsigned long long l = u < units ? summary[4u * u + 2u * role + 1u] : 0ull;
+            unsigned long long incl = l;  // inclusive prefix maximum of the last pairs
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned long long t = __shfl_up(incl, o, 64);
+                if ((int)lane >= o && t > incl) incl = t;
+            }
+            unsigned long long excl = __shfl_up(incl, 1, 64);
+            if (lane == 0) excl = 0ull;
+            if (carry > excl) excl = carry;
+            bad = bad || f <= excl;  // (a run without candidates: all ones, above everything)
+            const unsigned long long top = __shfl(incl, 63, 64);
+            carry = top > carry ? top : carry;
+        }
+    }
+    if (__ballot(bad) != 0ull && lane == 0) atomicOr(fail, 1u);
+}
+
 }  // namespace
+
+hipError_t launch_label_merge_check(const LabelMerge& m, hipStream_t stream) {
+    if (m.n_nodes == 0) return hipSuccess;
+    const uint32_t n_chunks = (m.n_nodes + 63u) / 64u;
+    const uint32_t units = n_chunks < kLabelMergeUnits ? n_chunks : kLabelMergeUnits;
+    hipLaunchKernelGGL(label_merge_check_kernel, dim3(units), dim3(64), 0, stream, m);
+    if (units > 1u)
+        hipLaunchKernelGGL(label_merge_carry_kernel, dim3(1), dim3(64), 0, stream, (const unsigned long long*)m.d_summary, units,
+                           m.d_fail);
+    return hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------------------------------- slot tables
 // What gf_orders_set builds on the host for the merged layout, built from the device-resident columns instead: slot s
@@ -676,7 +779,7 @@ __device__ __forceinline__ uint64_t gcd_fast(uint64_t a, uint64_t b) {
 // One workgroup: the per-dimension units (gcd over the chunk gcds) and the zone evaluation list.  Four groups of 256 threads
 // side by side — the three dimensions' gcd trees and the three magnitude maxima — instead of one after the other: the trees are
 // chains of dependent gcds, and this kernel sits between two grid-wide ones on the build's critical path.
-// Thread 0 also gathers what the host reads back into ONE range: d_scalars[3] = the priority sort's error word,
+// Thread 0 also gathers what the host reads back into ONE range: d_scalars[3] = the priority sort's error word | 2 x the label merge check's,
 // d_scalars[4 .. 15] = the three units and the three largest scaled magnitudes as pairs of 32-bit words (one copy, not three).
 constexpr uint32_t kReduceGroup = 256;
 __global__ __launch_bounds__(4 * kReduceGroup) void finalize_reduce_kernel(SnapshotFinalize f, const uint32_t* __restrict__ sort_error) {
@@ -721,7 +824,8 @@ __global__ __launch_bounds__(4 * kReduceGroup) void finalize_reduce_kernel(Snaps
             f.d_scalars[10 + 2 * j] = (uint32_t)(unsigned long long)top;
             f.d_scalars[11 + 2 * j] = (uint32_t)((unsigned long long)top >> 32);
         }
-        f.d_scalars[3] = sort_error != nullptr ? *sort_error : 0u;
+        // (the word behind the sort's error word: the label merge check of the same build, LabelMerge::d_fail)
+        f.d_scalars[3] = sort_error != nullptr ? ((sort_error[0] ? 1u : 0u) | (sort_error[1] ? 2u : 0u)) : 0u;
         if (f.h_out != nullptr) {  // the host's copy, written in place (pinned, device-mapped; complete when the build's last kernel is)
             for (int k = 3; k < 16; ++k) f.h_out[k] = f.d_scalars[k];
         }
@@ -950,7 +1054,8 @@ hipError_t launch_snapshot_build(const SnapshotBuild& b, hipStream_t stream) {
     PrioritySort ps{n, b.n_zones, b.d_avail, b.d_avail + n, b.d_zone, b.d_zone_rank, (const long long*)b.d_zone_sum,
                     {reinterpret_cast<unsigned long long*>(b.d_keys_a), reinterpret_cast<unsigned long long*>(b.d_keys_b),
                      reinterpret_cast<unsigned long long*>(b.d_keys_c)},
-                    {b.d_perm_a, b.d_perm_b, b.d_perm_c}, b.d_sort_work, b.sort_fault ? (1u << 12) : (1u << 24)};
+                    {b.d_perm_a, b.d_perm_b, b.d_perm_c}, b.d_sort_work, b.sort_fault ? (1u << 12) : (1u << 24),
+                    b.d_label, b.label_max, b.label_width, b.d_perm_p, b.d_ppos};
     // An ordinary launch: sixty-four one-wavefront workgroups become resident as soon as sixty-four wave slots are free (every
     // other kernel of this library terminates on its own), and the grid barrier gives up with an error flag instead of
     // spinning forever.  (hipLaunchCooperativeKernel would also promise residency, but rocprofv3 crashes at process exit
@@ -962,6 +1067,6 @@ hipError_t launch_snapshot_build(const SnapshotBuild& b, hipStream_t stream) {
 }
 
 size_t snapshot_sort_work_words() { return kSortHistWords + kSortStateWords + 2u * kSortScalars; }
-uint32_t snapshot_sort_error_word() { return kSortHistWords + 2u; }
+uint32_t snapshot_sort_error_word() { return kSortHistWords + 2u; }  // (+ 1: the label merge check's word)
 
 }  // namespace gangfit

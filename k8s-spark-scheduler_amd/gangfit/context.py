@@ -110,6 +110,13 @@ class Context:
         self._check(self._lib.gf_generation(self._h, N.ptr(out)))
         return tuple(int(v) for v in out)
 
+    def build_info(self):
+        """gf_snapshot_build_info: (route of the last build: 0 none / 1 device / 2 host, a label key group ran, the label merge
+        check failed and the build fell back, bytes copied device -> host without the order outputs)"""
+        out = np.zeros(4, dtype=np.uint32)
+        self._check(self._lib.gf_snapshot_build_info(self._h, N.ptr(out)))
+        return tuple(int(v) for v in out)
+
     def chain_cache_stats(self, reset: bool = False):
         """(chains with the cache armed, chains resumed from a checkpoint, applications evaluated, applications skipped)"""
         out = np.zeros(4, dtype=np.uint64)

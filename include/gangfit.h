@@ -110,13 +110,13 @@ int gf_version(void);
  *   n_dev == 1 (or device_ids NULL, n_dev 0 = device 0): everything runs on that device.
  *   n_dev  > 1 (<= 16): ONE context over several devices of the box — the node table shards by range of the priority order
  *     (SURVEY.md section 8e).  gf_snapshot_set / gf_zones_set / gf_orders_set / gf_snapshot_build install the snapshot on
- *     every device; gf_fit_batch(GF_MODE_INDEPENDENT) with tightly-pack, distribute-evenly, single-az-tightly-pack or
- *     az-aware-tightly-pack then evaluates every application on every device's range (four device steps per device; the
- *     zone-aware packers once per candidate view: every zone, plus the plain order for az-aware — they need the schedulable
- *     columns and at most 64 views) and stitches the result with three exchanges done by peer access over xGMI inside the
- *     call: two all-gathers of 16 B per application and view (written straight into the peers' tables) and one reduction of
- *     the placement buffer onto the first device.  Same gf_result / ExecutorNodes as on one device, bit for bit.  Everything
- *     else (FIFO chains — each commit must be visible to the next scan —, the minimal-fragmentation packers, orders that do
+ *     every device; gf_fit_batch(GF_MODE_INDEPENDENT) with any packer then evaluates every application on every device's
+ *     range (four device steps per device; the zone-aware packers once per candidate view: every zone, plus the plain order
+ *     for az-aware — they need the schedulable columns and at most 64 views) and stitches the result with three exchanges done
+ *     by peer access over xGMI inside the call: two all-gathers of 16 B per application and view (written straight into the
+ *     peers' tables; the minimal-fragmentation packers add a 512-byte row of capacity counts to the first) and one reduction
+ *     of the placement buffer onto the first device.  Same gf_result / ExecutorNodes as on one device, bit for bit.  Everything
+ *     else (FIFO chains — each commit must be visible to the next scan —, orders that do
  *     not merge into one, single executors, findNodes, efficiencies, the *_dev entry points) runs on the first device.  One submitting thread per device issues that device's launches
  *     (the calling thread is the first device's; the others park between batches), so a batch costs the host about what
  *     one device's half a dozen runtime calls cost.  A device id may repeat (several shards on one GPU): that is how the
@@ -125,7 +125,8 @@ int gf_version(void);
  *     sub-context, a stream and a submitting thread of its own instead).  gf_shard_count returns the number of listed ids.  When two distinct devices cannot access each other's memory the context DEGRADES
  *     to the first device (GF_OK; gf_shard_count returns 1, gf_last_error says why): a host must not lose the accelerator
  *     because a topology lacks peer access.  The exchange buffers live in fine-grained memory.  Self-check: the first
- *     sharded batch on every newly installed snapshot is also answered by the first device alone; on a mismatch the
+ *     sharded batch of each packer family (plain, zone-aware tightly-pack, minimal-fragmentation) on every newly installed
+ *     snapshot is also answered by the first device alone; on a mismatch the
  *     context stops sharding (gf_shard_count 1, gf_last_error set) and serves the first device's answer — a wrong exchange
  *     never decides a Filter.  gf_set_option(ctx, "group_exchange", 1) moves the three exchanges onto RCCL collectives
  *     (librccl bound at run time, ncclCommInitAll over the context's devices: two all-gathers and one reduce per batch, each
@@ -503,7 +504,8 @@ int gf_find_nodes(gf_ctx *ctx, int chained, uint32_t n_req, const int64_t *exe, 
  *     -> all-reduce(SUM, uint32) of the leading reduce_words of d_exec2 -> gf_shard_finish_dev
  * after which EVERY rank holds the complete results: the same gf_result / ExecutorNodes as gf_fit_batch_dev on one GPU.
  * Tightly-pack, distribute-evenly, single-az-tightly-pack and az-aware-tightly-pack (the zone-aware two need the schedulable
- * columns of gf_snapshot_set and at most 64 candidate views); the minimal-fragmentation packers return GF_ERR_UNSUPPORTED.
+ * columns of gf_snapshot_set and at most 64 candidate views); the minimal-fragmentation packers return GF_ERR_UNSUPPORTED
+ * here: they have entry points of their own (gf_shard_mf_*, further down).
  * The FIFO chain does not shard (each commit must be visible to the next scan): it runs as replicas.  All pointers are
  * device pointers; calls are asynchronous on `stream`.
  * Layout (gf_shard_layout gives the numbers for a context, packer and batch):
@@ -549,6 +551,36 @@ int gf_shard_finish_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app
  * shard steps would: GF_ERR_UNSUPPORTED for a packer or layout they do not serve. */
 int gf_shard_layout(gf_ctx *ctx, gf_algo algo, uint64_t half, uint32_t *records_per_app, uint64_t *exec2_words,
                     uint64_t *reduce_words);
+
+/* ---- the same for the minimal-fragmentation packers (minimal-fragmentation, single-az-minimal-fragmentation) ----
+ * "The smallest capacity >= K" is a minimum over every candidate, so these packers walk the whole executor order for every
+ * application, and that walk divides by the number of shards.  A family of entry points of its own, because its first
+ * exchange carries a table of capacity counts next to the 16-byte records:
+ *     gf_shard_mf_counts_dev -> all-gather of the records AND of the count rows -> gf_shard_mf_drivers_dev -> all-gather
+ *     -> gf_shard_mf_emit_dev -> all-reduce(SUM, uint32) of the leading reduce_words of d_exec2 -> gf_shard_mf_finish_dev
+ * after which every rank holds the same gf_result / ExecutorNodes as gf_fit_batch_dev on one GPU, for every application
+ * (requests or ranges whose capacities have no histogram form — a capacity of 256 or more, a request that is no multiple of
+ * the table's units — are decided by one designated shard inside the same steps).
+ * Layout (gf_shard_mf_layout): records = 1, or the zones of the evaluation list for single-AZ; d_part_out / d_out hold
+ * records * n_apps records ([view][app]) and d_counts_out records * n_apps rows of count_bytes_per_record bytes in the same
+ * order (row: uint16 counts of the range's executor candidates per capacity 0 .. 255 with nothing reserved; fit_count of the
+ * record is 1 when the range has no such row); the gathered tables are [n_shards][records][n_apps].  d_exec2 = records * half
+ * words, all of them reduced (region c = view c's placement as node index + 1, slot + 1 for single-AZ, whose finish step
+ * chooses the zone, writes d_results and leaves the winner's node ids in [0, half)).
+ * GF_ERR_UNSUPPORTED: any other packer, orders that do not merge, more than 64 (or no) zones, a multi-device context;
+ * GF_ERR_STATE: single-AZ without the schedulable columns of gf_snapshot_set. */
+int gf_shard_mf_layout(gf_ctx *ctx, gf_algo algo, uint64_t half, uint32_t *records_per_app, uint32_t *count_bytes_per_record,
+                       uint64_t *exec2_words, uint64_t *reduce_words);
+int gf_shard_mf_counts_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app *d_apps, gf_shard_partial *d_part_out,
+                           void *d_counts_out, void *stream);
+int gf_shard_mf_drivers_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app *d_apps,
+                            const gf_shard_partial *d_all_partials, gf_shard_driver *d_out, void *stream);
+int gf_shard_mf_emit_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app *d_apps,
+                         const gf_shard_partial *d_all_partials, const gf_shard_driver *d_all_drivers, const void *d_all_counts,
+                         gf_result *d_results, uint32_t *d_exec2, uint64_t half, void *stream);
+int gf_shard_mf_finish_dev(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const gf_app *d_apps,
+                           const gf_shard_partial *d_all_partials, const gf_shard_driver *d_all_drivers, gf_result *d_results,
+                           uint32_t *d_exec2, uint64_t half, void *stream);
 
 /* Working copy of the available table after the last GF_MODE_FIFO_CHAIN call (n_nodes x 3, row-major) — lets tests
  * compare the replayed residuals with availableNodesSchedulingMetadata after fitEarlierDrivers. */

@@ -115,7 +115,7 @@ int gf_init(const int* device_ids, int n_dev, gf_ctx** out) {
                 host->n_shards = (uint32_t)n_dev;
                 // what the other devices store into / read from lives in fine-grained memory: a posted peer store must not
                 // depend on what a kernel boundary does to this device's caches
-                host->g_part_all.fine = host->g_drv_all.fine = host->g_exec2.fine = true;
+                host->g_part_all.fine = host->g_drv_all.fine = host->g_cnt_all.fine = host->g_exec2.fine = true;
                 g->group.push_back(host);
                 g->g_devices.push_back(device_ids[i]);
                 bool ok = hipSetDevice(host->device) == hipSuccess;
@@ -329,6 +329,8 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->g_part_all.release();
     ctx->g_drv_loc.release();
     ctx->g_drv_all.release();
+    ctx->g_cnt_loc.release();
+    ctx->g_cnt_all.release();
     ctx->g_exec2.release();
     for (hipEvent_t& e : ctx->g_ev)
         if (e) (void)hipEventDestroy(e);
@@ -398,19 +400,19 @@ int gf_set_option(gf_ctx* ctx, const char* key, int64_t value) {
         }
         if (gk == "group_fault") {
             ctx->g_fault = (int)value;
-            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = 0;
+            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = ctx->g_verified_epoch[2] = 0;
             return GF_OK;
         }
         if (gk == "group_shard_off") {  // read-back for tests: 1 sets, 0 clears (and re-arms the self-check)
             ctx->g_shard_off = value != 0;
-            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = 0;
+            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = ctx->g_verified_epoch[2] = 0;
             return GF_OK;
         }
         if (gk == "group_exchange") {
             for (void* c : ctx->g_comms)
                 if (c) (void)rccl().CommDestroy(c);
             ctx->g_comms.clear();
-            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = 0;  // the other exchange proves itself on its first batch
+            ctx->g_verified_epoch[0] = ctx->g_verified_epoch[1] = ctx->g_verified_epoch[2] = 0;  // the other exchange proves itself on its first batch
             if (value == 0) return GF_OK;
             if (ctx->g_total_shards != ctx->group.size())
                 return fail(ctx, GF_ERR_UNSUPPORTED, "a device hosts several shards: the RCCL exchange wants one rank per physical device");

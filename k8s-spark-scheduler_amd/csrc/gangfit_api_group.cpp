@@ -30,9 +30,46 @@ static int shard_serves(gf_ctx* ctx, gf_algo algo, bool report) {
     return report ? fail(ctx, GF_ERR_UNSUPPORTED, "%s", why) : GF_ERR_UNSUPPORTED;
 }
 
+static void shard_range_of(gf_ctx* ctx, gangfit::ShardRange* r);
+
 int shard_ready(gf_ctx* ctx, gf_algo algo, gangfit::ShardRange* r) {
     if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a sharded fit");
     if (const int rc = shard_serves(ctx, algo, true); rc != GF_OK) return rc;
+    shard_range_of(ctx, r);
+    return GF_OK;
+}
+
+// The minimal-fragmentation family of shard steps (gf_shard_mf_*): which packers, and when they are served.
+static bool is_shard_mf_algo(gf_algo algo) { return algo == GF_ALGO_MINIMAL_FRAGMENTATION || algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION; }
+static int shard_mf_serves(gf_ctx* ctx, gf_algo algo, bool report) {
+    char why[256];
+    int rc = GF_ERR_UNSUPPORTED;
+    const bool zoned = algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION;
+    const uint32_t n_cand = candidate_views(ctx, algo);
+    if (!is_shard_mf_algo(algo))
+        std::snprintf(why, sizeof why, "the gf_shard_mf_* steps serve minimal-fragmentation and single-az-minimal-fragmentation only");
+    else if (!ctx->merged)
+        std::snprintf(why, sizeof why, "node-range sharding needs the merged slot layout (driver and executor orders must be "
+                                       "subsequences of one priority order)");
+    else if (zoned && !ctx->have_sched) {
+        rc = GF_ERR_STATE;
+        std::snprintf(why, sizeof why, "single-az-minimal-fragmentation compares packing efficiencies: node-range sharding needs the "
+                                       "schedulable columns of gf_snapshot_set");
+    } else if (zoned && (n_cand == 0 || n_cand > 64))
+        std::snprintf(why, sizeof why, "node-range sharding of single-az-minimal-fragmentation needs 1 to 64 candidate views (zones "
+                                       "of the evaluation list), not %u", n_cand);
+    else
+        return GF_OK;
+    return report ? fail(ctx, rc, "%s", why) : rc;
+}
+static int shard_mf_ready(gf_ctx* ctx, gf_algo algo, gangfit::ShardRange* r) {
+    if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a sharded fit");
+    if (const int rc = shard_mf_serves(ctx, algo, true); rc != GF_OK) return rc;
+    shard_range_of(ctx, r);
+    return GF_OK;
+}
+
+static void shard_range_of(gf_ctx* ctx, gangfit::ShardRange* r) {
     const uint64_t xc = ((uint64_t)ctx->n_x + 63) / 64;  // chunks of the merged order (the sentinel slot hosts nothing)
     r->c_lo = (uint32_t)(xc * ctx->shard / ctx->n_shards);
     r->c_hi = (uint32_t)(xc * (ctx->shard + 1) / ctx->n_shards);
@@ -45,7 +82,6 @@ int shard_ready(gf_ctx* ctx, gf_algo algo, gangfit::ShardRange* r) {
         r->g_lo = ctx->g_prefix[r->c_lo < last ? r->c_lo : last];
         r->g_hi = ctx->g_prefix[r->c_hi < last ? r->c_hi : last];
     }
-    return GF_OK;
 }
 // (a context without the prefix table — a view — takes the full order)
 static gangfit::SparseTable shard_sparse(gf_ctx* ctx) {
@@ -53,7 +89,7 @@ static gangfit::SparseTable shard_sparse(gf_ctx* ctx) {
 }
 // the candidate views of a zone-aware packer (after shard_ready); nullptr for the plain packers
 static const gangfit::ShardZones* shard_zones(gf_ctx* ctx, gf_algo algo, gangfit::ShardZones* z) {
-    if (!is_shard_zone_algo(algo)) return nullptr;
+    if (!is_shard_zone_algo(algo) && algo != GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION) return nullptr;
     z->xmask = ctx->d_zmasks.ptr;
     z->dmask = ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride;
     z->span = ctx->zspan_ok ? ctx->d_zspan.ptr : nullptr;
@@ -76,6 +112,11 @@ static ShardLayout shard_layout_of(const gf_ctx* ctx, gf_algo algo, uint64_t hal
     }
     // [0, half) the placements, [half, 2 half) the capacities of distribute-evenly's pass 1
     return ShardLayout{1u, 2 * half, algo == GF_ALGO_DISTRIBUTE_EVENLY ? 2 * half : half};
+}
+// ... of the minimal-fragmentation family (gf_shard_mf_layout): region c of the buffer = view c's placement, all of it reduced
+static ShardLayout shard_mf_layout_of(const gf_ctx* ctx, gf_algo algo, uint64_t half) {
+    const uint32_t v = candidate_views(ctx, algo);
+    return ShardLayout{v, (uint64_t)v * half, (uint64_t)v * half};
 }
 
 // ---- the submitting threads (GroupPool, gangfit_ctx.h)
@@ -132,12 +173,12 @@ void GroupPool::barrier() {
     }
 }
 
-// gf_fit_batch on a multi-device context.  Independent batches of the two plain packers and of the zone-aware tightly-pack
-// packers are node-range sharded across the sub-contexts (the four steps of gangfit_shard.inc with the
-// three exchanges done by peer access — the producing kernels write straight into every device's gathered table,
-// shard_reduce_pull_kernel collects the placements — or by RCCL); everything else — FIFO chains (each commit must be visible to
-// the next scan), the minimal-fragmentation packers, orders that do not merge, zone-aware batches without the schedulable
-// columns or with more than 64 candidate views — runs on the first device.
+// gf_fit_batch on a multi-device context.  Independent batches of the two plain packers, of the zone-aware tightly-pack
+// packers and of the two minimal-fragmentation packers are node-range sharded across the sub-contexts (the
+// four steps of gangfit_shard.inc with the three exchanges done by peer access — the producing kernels write straight into every
+// device's gathered table, the minimal-fragmentation packers' count rows like their records, shard_reduce_pull_kernel collects
+// the placements — or by RCCL); everything else — FIFO chains (each commit must be visible to the next scan), orders that do not
+// merge, zone-aware batches without the schedulable columns or with more than 64 candidate views — runs on the first device.
 //
 // One sub-context = one DEVICE and the shards it hosts: per step ONE launch per device (a grid row per hosted shard), one
 // upload of the records, one gathered table and one placement buffer per device.  With several devices device d's calls are
@@ -147,9 +188,10 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
                     uint32_t* exec_nodes, uint64_t exec_nodes_cap, int32_t* chain_failed_at) {
     std::lock_guard<std::recursive_mutex> glock(g->mu);
     gf_ctx* const first = g->group[0];
-    const bool zoned = is_shard_zone_algo(algo);
+    const bool zoned = is_shard_zone_algo(algo), minfrag = is_shard_mf_algo(algo);
     bool sharded = mode == GF_MODE_INDEPENDENT && n_apps > 0 && !g->g_shard_off;
-    for (gf_ctx* s : g->group) sharded = sharded && s->have_orders && shard_serves(s, algo, false) == GF_OK;
+    for (gf_ctx* s : g->group)
+        sharded = sharded && s->have_orders && (minfrag ? shard_mf_serves(s, algo, false) : shard_serves(s, algo, false)) == GF_OK;
     if (!sharded) {
         const int rc = gf_fit_batch(first, mode, algo, n_apps, apps, results, exec_nodes, exec_nodes_cap, chain_failed_at);
         if (rc != GF_OK) g->err = first->err;
@@ -168,8 +210,9 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
                     (unsigned long long)total_k);
     const uint64_t half = total_k + 1;
     // records per application and view, the placement buffer and what the reduce of it carries (shard_layout_of)
-    const ShardLayout lay = shard_layout_of(first, algo, half);
+    const ShardLayout lay = minfrag ? shard_mf_layout_of(first, algo, half) : shard_layout_of(first, algo, half);
     const uint32_t rec = lay.records;
+    const size_t row_words = gangfit::kShardMfRowBytes / sizeof(uint32_t);  // (minimal-fragmentation: a count row per record)
     const size_t reduce_words = (size_t)lay.reduce_words;
     GF_HIP(g, g->h_results.reserve(n_apps));
     GF_HIP(g, g->h_exec.reserve(total_k + 1));
@@ -178,7 +221,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
     gangfit::ShardSet set[gangfit::kMaxGroupDevices];
     gangfit::ShardZones zones[gangfit::kMaxGroupDevices];
     const gangfit::ShardZones* zv[gangfit::kMaxGroupDevices] = {};
-    gangfit::PeerPtrs part_all{}, drv_all{}, exec_others{};
+    gangfit::PeerPtrs part_all{}, drv_all{}, cnt_all{}, exec_others{};
     for (uint32_t d = 0; d < D; ++d) {
         gf_ctx* c = g->group[d];
         GF_HIP(g, hipSetDevice(c->device));
@@ -188,7 +231,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
             c->shard = sh;
             c->n_shards = S;
             gangfit::ShardRange r{};
-            if (const int rc = shard_ready(c, algo, &r); rc != GF_OK) {
+            if (const int rc = minfrag ? shard_mf_ready(c, algo, &r) : shard_ready(c, algo, &r); rc != GF_OK) {
                 g->err = c->err;
                 return rc;
             }
@@ -207,11 +250,16 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         GF_HIP(g, c->g_part_all.reserve((size_t)S * rec * n_apps));
         GF_HIP(g, c->g_drv_all.reserve((size_t)S * rec * n_apps));
         GF_HIP(g, c->g_exec2.reserve(lay.exec2_words));
+        if (minfrag) {
+            GF_HIP(g, c->g_cnt_loc.reserve((size_t)c->my_shards.size() * rec * n_apps * row_words));
+            GF_HIP(g, c->g_cnt_all.reserve((size_t)S * rec * n_apps * row_words));
+            cnt_all.p[d] = c->g_cnt_all.ptr;
+        }
         part_all.p[d] = c->g_part_all.ptr;
         drv_all.p[d] = c->g_drv_all.ptr;
         if (d > 0) exec_others.p[exec_others.n++] = c->g_exec2.ptr;
     }
-    part_all.n = drv_all.n = D;
+    part_all.n = drv_all.n = cnt_all.n = D;
     const bool use_rccl = g->g_comms.size() == D && D == S;
     const gangfit::PeerPtrs no_peers{};
     std::vector<int> rc_of(D, GF_OK);
@@ -226,8 +274,13 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         gf_ctx* c = g->group[d];
         if (!GF_STEP(d, hipSetDevice(c->device))) return;
         if (!GF_STEP(d, hipMemcpyAsync(c->d_apps.ptr, g->h_apps.ptr, (size_t)n_apps * sizeof(gf_app), hipMemcpyHostToDevice, c->stream))) return;
-        if (!GF_STEP(d, gangfit::launch_shard_partials(algo, make_table(c, c->d_snap.ptr), shard_sparse(c), set[d], n_apps, c->d_apps.ptr, c->g_part_loc.ptr,
-                                                       use_rccl ? no_peers : part_all, c->stream, zv[d])))
+        if (minfrag) {
+            if (!GF_STEP(d, gangfit::launch_shard_mf_counts(make_table(c, c->d_snap.ptr), set[d], n_apps, c->d_apps.ptr, c->g_part_loc.ptr,
+                                                            c->g_cnt_loc.ptr, use_rccl ? no_peers : part_all,
+                                                            use_rccl ? no_peers : cnt_all, c->stream, zv[d])))
+                return;
+        } else if (!GF_STEP(d, gangfit::launch_shard_partials(algo, make_table(c, c->d_snap.ptr), shard_sparse(c), set[d], n_apps, c->d_apps.ptr,
+                                                              c->g_part_loc.ptr, use_rccl ? no_peers : part_all, c->stream, zv[d])))
             return;
         if (g->g_fault == 2 && d > 0 && !use_rccl) {  // fault injection: this device's capacity sums arrive as zeros everywhere
             for (uint32_t t = 0; t < D; ++t)
@@ -257,8 +310,14 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         gf_ctx* c = g->group[d];
         if (rc_of[d] != GF_OK || !GF_STEP(d, hipSetDevice(c->device))) return;
         if (D > 1 && !use_rccl) wait_others(d, 1);
-        if (!GF_STEP(d, gangfit::launch_shard_emit(algo, make_table(c, c->d_snap.ptr), shard_sparse(c), set[d], n_apps, c->d_apps.ptr, c->g_part_all.ptr,
-                                                   c->g_drv_all.ptr, c->d_results.ptr, c->g_exec2.ptr, half, c->stream, zv[d])))
+        if (minfrag) {
+            if (!GF_STEP(d, gangfit::launch_shard_mf_emit(make_table(c, c->d_snap.ptr), set[d], n_apps, c->d_apps.ptr, c->g_part_all.ptr,
+                                                          c->g_drv_all.ptr, c->g_cnt_all.ptr, c->d_results.ptr, c->g_exec2.ptr, half,
+                                                          c->stream, zv[d])))
+                return;
+        } else if (!GF_STEP(d, gangfit::launch_shard_emit(algo, make_table(c, c->d_snap.ptr), shard_sparse(c), set[d], n_apps, c->d_apps.ptr,
+                                                          c->g_part_all.ptr, c->g_drv_all.ptr, c->d_results.ptr, c->g_exec2.ptr, half,
+                                                          c->stream, zv[d])))
             return;
         if (D > 1) (void)GF_STEP(d, hipEventRecord(c->g_ev[2], c->stream));
     };
@@ -271,8 +330,12 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
                 if (!GF_STEP(0, gangfit::launch_shard_reduce_pull(exec_others, first->g_exec2.ptr, reduce_words, first->stream))) return;
         }
         const gangfit::NodeTable ft = make_table(first, first->d_snap.ptr);
-        if (!GF_STEP(0, gangfit::launch_shard_finish(algo, S, n_apps, first->d_apps.ptr, first->g_part_all.ptr, first->g_drv_all.ptr,
-                                                     first->d_results.ptr, first->g_exec2.ptr, half, first->stream, &ft, zv[0])))
+        if (minfrag) {
+            if (!GF_STEP(0, gangfit::launch_shard_mf_finish(S, n_apps, first->d_apps.ptr, first->g_part_all.ptr, first->g_drv_all.ptr,
+                                                            first->d_results.ptr, first->g_exec2.ptr, half, first->stream, ft, zv[0])))
+                return;
+        } else if (!GF_STEP(0, gangfit::launch_shard_finish(algo, S, n_apps, first->d_apps.ptr, first->g_part_all.ptr, first->g_drv_all.ptr,
+                                                            first->d_results.ptr, first->g_exec2.ptr, half, first->stream, &ft, zv[0])))
             return;
         if (!GF_STEP(0, hipMemcpyAsync(g->h_results.ptr, first->d_results.ptr, (size_t)n_apps * sizeof(gf_result), hipMemcpyDeviceToHost, first->stream))) return;
         if (total_k && !GF_STEP(0, hipMemcpyAsync(g->h_exec.ptr, first->g_exec2.ptr, (size_t)total_k * sizeof(uint32_t), hipMemcpyDeviceToHost, first->stream))) return;
@@ -298,19 +361,23 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
     if (use_rccl) {
         // RCCL exchange (one shard per device): every device's collective is enqueued on its own stream inside one group call
         // issued by THIS thread; the library orders the streams against each other
-        auto rccl_all_gather = [&](auto loc, auto all, size_t bytes_each) -> int {
+        // (with_rows: the minimal-fragmentation packers' count rows travel in the same grouped call as their records)
+        auto rccl_all_gather = [&](auto loc, auto all, size_t bytes_each, bool with_rows = false) -> int {
             if (rccl().GroupStart() != 0) return -1;
             int bad = 0;
             for (uint32_t s2 = 0; s2 < D; ++s2) {
                 gf_ctx* c = g->group[s2];
                 if (hipSetDevice(c->device) != hipSuccess) bad = 1;
                 bad |= rccl().AllGather(loc(c), all(c), bytes_each, Rccl::kChar, g->g_comms[s2], c->stream);
+                if (with_rows)
+                    bad |= rccl().AllGather(c->g_cnt_loc.ptr, c->g_cnt_all.ptr, (size_t)rec * n_apps * gangfit::kShardMfRowBytes, Rccl::kChar,
+                                            g->g_comms[s2], c->stream);
             }
             return rccl().GroupEnd() | bad;
         };
         for (uint32_t d = 0; d < D; ++d) step_partials(d);
         if (rccl_all_gather([](gf_ctx* c) { return (const void*)c->g_part_loc.ptr; }, [](gf_ctx* c) { return (void*)c->g_part_all.ptr; },
-                            (size_t)rec * n_apps * sizeof(gf_shard_partial)) != 0)
+                            (size_t)rec * n_apps * sizeof(gf_shard_partial), minfrag) != 0)
             return fail_drained("ncclAllGather of the capacity sums failed");
         for (uint32_t d = 0; d < D; ++d) step_drivers(d);
         if (rccl_all_gather([](gf_ctx* c) { return (const void*)c->g_drv_loc.ptr; }, [](gf_ctx* c) { return (void*)c->g_drv_all.ptr; },
@@ -355,11 +422,11 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         }
     std::memcpy(results, g->h_results.ptr, (size_t)n_apps * sizeof(gf_result));
     if (total_k) std::memcpy(exec_nodes, g->h_exec.ptr, (size_t)total_k * sizeof(uint32_t));
-    // ---- self-check: the first sharded batch of each packer family (plain, zone-aware) on every newly installed snapshot is
+    // ---- self-check: the first sharded batch of each packer family (plain, zone-aware, minimal-fragmentation) on every newly installed snapshot is
     //      also answered by the first device alone.  A wrong exchange (peer stores that did not land, a collective that reduced
     //      something else) must not decide a Filter: on a mismatch the context stops sharding, says why, and serves the first
     //      device's answer.
-    uint64_t& verified = g->g_verified_epoch[zoned ? 1 : 0];
+    uint64_t& verified = g->g_verified_epoch[minfrag ? 2 : (zoned ? 1 : 0)];
     if (g->g_verify && first->snap_epoch != verified) {
         std::vector<gf_result> ref_res(n_apps);
         std::vector<uint32_t> ref_exec((size_t)total_k + 1);
@@ -488,5 +555,85 @@ int gf_shard_layout(gf_ctx* ctx, gf_algo algo, uint64_t half, uint32_t* records_
     if (reduce_words) *reduce_words = lay.reduce_words;
     return GF_OK;
 }
+
+// ---- the minimal-fragmentation family (gangfit_shard.inc: the shard_mf_* kernels)
+#define GF_SHARD_MF_SINGLE(ctx)                                                                                                    \
+    if ((ctx) != nullptr && !(ctx)->group.empty())                                                                                 \
+        return fail((ctx), GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)"); \
+    if (!(ctx)) return GF_ERR_INVALID
+
+int gf_shard_mf_layout(gf_ctx* ctx, gf_algo algo, uint64_t half, uint32_t* records_per_app, uint32_t* count_bytes_per_record,
+                       uint64_t* exec2_words, uint64_t* reduce_words) {
+    GF_SHARD_MF_SINGLE(ctx);
+    if (half == 0) return fail(ctx, GF_ERR_INVALID, "half must be at least 1 (sum of k + 1)");
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    gangfit::ShardRange r{};
+    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
+    const ShardLayout lay = shard_mf_layout_of(ctx, algo, half);
+    if (records_per_app) *records_per_app = lay.records;
+    if (count_bytes_per_record) *count_bytes_per_record = gangfit::kShardMfRowBytes;
+    if (exec2_words) *exec2_words = lay.exec2_words;
+    if (reduce_words) *reduce_words = lay.reduce_words;
+    return GF_OK;
+}
+
+int gf_shard_mf_counts_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps, gf_shard_partial* d_part_out,
+                           void* d_counts_out, void* stream) {
+    GF_SHARD_MF_SINGLE(ctx);
+    if (n_apps > 0 && (!d_apps || !d_part_out || !d_counts_out)) return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
+    gangfit::ShardRange r{};
+    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    gangfit::ShardZones z{};
+    GF_HIP(ctx, gangfit::launch_shard_mf_counts(make_table(ctx, ctx->d_snap.ptr), gangfit::shard_set_of(r), n_apps, d_apps, d_part_out,
+                                                static_cast<uint32_t*>(d_counts_out), gangfit::PeerPtrs{}, gangfit::PeerPtrs{}, st,
+                                                shard_zones(ctx, algo, &z)));
+    return GF_OK;
+}
+
+int gf_shard_mf_drivers_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps,
+                            const gf_shard_partial* d_all_partials, gf_shard_driver* d_out, void* stream) {
+    GF_SHARD_MF_SINGLE(ctx);
+    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_out)) return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
+    gangfit::ShardRange r{};
+    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    gangfit::ShardZones z{};
+    GF_HIP(ctx, gangfit::launch_shard_drivers(make_table(ctx, ctx->d_snap.ptr), gangfit::shard_set_of(r), n_apps, d_apps, d_all_partials,
+                                              d_out, gangfit::PeerPtrs{}, st, shard_zones(ctx, algo, &z)));
+    return GF_OK;
+}
+
+int gf_shard_mf_emit_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
+                         const gf_shard_driver* d_all_drivers, const void* d_all_counts, gf_result* d_results, uint32_t* d_exec2,
+                         uint64_t half, void* stream) {
+    GF_SHARD_MF_SINGLE(ctx);
+    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_all_drivers || !d_all_counts || !d_results || !d_exec2 || half == 0))
+        return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
+    gangfit::ShardRange r{};
+    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    gangfit::ShardZones z{};
+    GF_HIP(ctx, gangfit::launch_shard_mf_emit(make_table(ctx, ctx->d_snap.ptr), gangfit::shard_set_of(r), n_apps, d_apps, d_all_partials,
+                                              d_all_drivers, static_cast<const uint32_t*>(d_all_counts), d_results, d_exec2, half, st,
+                                              shard_zones(ctx, algo, &z)));
+    return GF_OK;
+}
+
+int gf_shard_mf_finish_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps,
+                           const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers, gf_result* d_results,
+                           uint32_t* d_exec2, uint64_t half, void* stream) {
+    GF_SHARD_MF_SINGLE(ctx);
+    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_all_drivers || !d_results || !d_exec2 || half == 0))
+        return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
+    gangfit::ShardRange r{};
+    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    gangfit::ShardZones z{};
+    GF_HIP(ctx, gangfit::launch_shard_mf_finish(ctx->n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half,
+                                                st, make_table(ctx, ctx->d_snap.ptr), shard_zones(ctx, algo, &z)));
+    return GF_OK;
+}
+#undef GF_SHARD_MF_SINGLE
 
 }  // extern "C"

@@ -390,12 +390,14 @@ struct gf_ctx {
     gfapi::GroupPool* g_pool = nullptr;       // (in the routing object) one submitting thread per device but the first
     DeviceBuf<gf_shard_partial> g_part_loc, g_part_all;  // this shard's records | [n_shards][n_apps] gathered
     DeviceBuf<gf_shard_driver> g_drv_loc, g_drv_all;
+    DeviceBuf<uint32_t> g_cnt_loc, g_cnt_all;            // the minimal-fragmentation packers' count rows, laid out like the records
     DeviceBuf<uint32_t> g_exec2;                         // 2 * half: placements (node + 1) | capacities
     hipEvent_t g_ev[3] = {nullptr, nullptr, nullptr};    // behind partials+push | drivers+push | emit
     // ... and these in the routing object
     // snapshot epoch whose first sharded batch agreed with the first device's own answer, per packer family: [0] the plain packers,
-    // [1] the zone-aware ones (their steps differ, so each family proves itself on its first batch of a snapshot)
-    uint64_t g_verified_epoch[2] = {0, 0};
+    // [1] the zone-aware ones, [2] the minimal-fragmentation ones (their steps differ, so each family proves itself on its first
+    // batch of a snapshot)
+    uint64_t g_verified_epoch[3] = {0, 0, 0};
     bool g_verify = true;           // option "group_verify"
     bool g_shard_off = false;       // a sharded batch disagreed: every batch is served by the first device from then on
     int g_fault = 0;                // option "group_fault" (tests): 1 = the placement reduction is skipped, 2 = zeroed capacity sums

@@ -439,6 +439,21 @@ hipError_t launch_shard_finish(gf_algo algo, uint32_t n_shards, uint32_t n_apps,
                                const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
                                gf_result* d_results, uint32_t* d_exec2, uint64_t half, hipStream_t stream,
                                const NodeTable* table = nullptr, const ShardZones* zones = nullptr);
+// The minimal-fragmentation packers on the shard steps (gangfit_shard.inc: the shard_mf_* kernels; zones == nullptr: the plain
+// packer, else the views of single-az-minimal-fragmentation).  The drivers step is launch_shard_drivers.  A count row is
+// kShardMfRowBytes per record, laid out like the records ([shard][view][app]); count_dsts like part_dsts.
+constexpr uint32_t kShardMfRowBytes = 512;
+hipError_t launch_shard_mf_counts(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
+                                  gf_shard_partial* d_part, uint32_t* d_counts, const PeerPtrs& part_dsts, const PeerPtrs& count_dsts,
+                                  hipStream_t stream, const ShardZones* zones = nullptr);
+// (zeroes d_exec2 first: views * half words)
+hipError_t launch_shard_mf_emit(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
+                                const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
+                                const uint32_t* d_all_counts, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
+                                hipStream_t stream, const ShardZones* zones = nullptr);
+hipError_t launch_shard_mf_finish(uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
+                                  const gf_shard_driver* d_all_drivers, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
+                                  hipStream_t stream, const NodeTable& table, const ShardZones* zones = nullptr);
 // d_dst[i] += sum over srcs of src[i], n uint32 entries (only the first device finishes a batch: the all-reduce is a reduce)
 hipError_t launch_shard_reduce_pull(const PeerPtrs& srcs, uint32_t* d_dst, size_t n, hipStream_t stream);
 

@@ -2385,6 +2385,52 @@ hipError_t launch_shard_finish(gf_algo algo, uint32_t n_shards, uint32_t n_apps,
     });
 }
 
+// ---- the minimal-fragmentation packers on the shard steps (zones == nullptr: the plain packer, one view)
+inline dim3 shard_mf_grid(uint32_t n_apps, const ShardSet& set, const ShardZones* z) {
+    return dim3(app_grid(n_apps).x, set.n, z != nullptr ? z->n_cand : 1u);
+}
+inline bool shard_mf_zones_ok(const ShardZones* z) { return z == nullptr || (shard_zones_ok(z) && z->az_aware == 0u); }
+
+hipError_t launch_shard_mf_counts(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
+                                  gf_shard_partial* d_part, uint32_t* d_counts, const PeerPtrs& part_dsts, const PeerPtrs& count_dsts,
+                                  hipStream_t stream, const ShardZones* zones) {
+    if (n_apps == 0 || set.n == 0) return hipSuccess;
+    if (!shard_mf_zones_ok(zones)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(shard_mf_counts_kernel, shard_mf_grid(n_apps, set, zones), dim3(kWave * kWavesPerBlock), 0, stream, table, set,
+                       zones != nullptr ? *zones : ShardZones{}, n_apps, d_apps, d_part, d_counts, part_dsts, count_dsts);
+    return hipGetLastError();
+}
+
+hipError_t launch_shard_mf_emit(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
+                                const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
+                                const uint32_t* d_all_counts, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
+                                hipStream_t stream, const ShardZones* zones) {
+    if (n_apps == 0 || set.n == 0) return hipSuccess;
+    if (!shard_mf_zones_ok(zones)) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(d_exec2, 0, (zones != nullptr ? zones->n_cand : 1u) * half * sizeof(uint32_t), stream);
+    if (e != hipSuccess) return e;
+    return with_value<true, false>(zones != nullptr, [&](auto Z) {
+        hipLaunchKernelGGL(shard_mf_emit_kernel<Z>, shard_mf_grid(n_apps, set, zones), dim3(kWave * kWavesPerBlock), 0, stream, table,
+                           set, zones != nullptr ? *zones : ShardZones{}, n_apps, d_apps, d_all_partials, d_all_drivers, d_all_counts,
+                           d_results, d_exec2, half);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_shard_mf_finish(uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
+                                  const gf_shard_driver* d_all_drivers, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
+                                  hipStream_t stream, const NodeTable& table, const ShardZones* zones) {
+    if (n_apps == 0) return hipSuccess;
+    if (!shard_mf_zones_ok(zones)) return hipErrorInvalidValue;
+    if (zones != nullptr)
+        hipLaunchKernelGGL((shard_finish_zoned_kernel<false, GF_ALGO_MINIMAL_FRAGMENTATION>), dim3(n_apps), dim3(kWave * kFusedWaves), 0,
+                           stream, table, *zones, n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
+    else  // node + 1 -> node: tightly-pack's finish
+        hipLaunchKernelGGL(shard_finish_kernel<GF_ALGO_TIGHTLY_PACK>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, n_shards,
+                           n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
+    return hipGetLastError();
+}
+
 __global__ __launch_bounds__(256) void narrow_rescale_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst,
                                                              uint32_t n_slots, const int32_t* __restrict__ cm_src,
                                                              int32_t* __restrict__ cm_dst, uint32_t n_chunks, int32_t f0,

@@ -36,6 +36,9 @@
 // zone's average Max packing efficiency, a float64 sum in slice order that shards cannot split, so the finish step
 // (shard_finish_zoned_kernel) computes the averages from the reduced placements — every rank holds the replicated snapshot and
 // schedulable columns — with the device functions of fit_zoned_fused_kernel, chooses and writes the result.
+//
+// The minimal-fragmentation packers (minimal-fragmentation, single-az-minimal-fragmentation) are a family of their own further
+// down (the shard_mf_* kernels): their first exchange carries a table of capacity counts next to the 16-byte records.
 
 template <bool DRV, class View>
 __device__ __forceinline__ uint64_t range_group_mask(const View& V, uint32_t g, uint32_t c_lo, uint32_t c_hi, int64_t r0,
@@ -541,7 +544,9 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void shard_emit_zoned_kernel
 // then chooseBestResult (single_az.go:75-97: strict < from 0.0, the first zone of the evaluation list on a tie), the az-aware
 // fallback to the plain view (az_aware_pack_tightly.go:33-37), the result record, and the winner's slots translated to node
 // ids into region 0 = [exec_off, exec_off + K) of the buffer (zeros when nothing won).
-template <bool AZ_AWARE>
+// (ALGO: the packer that made the views' placements — minimal-fragmentation leaves the executors out of the `reserved` map the
+// averages are taken on, minimal_fragmentation.go:59-91)
+template <bool AZ_AWARE, int ALGO = GF_ALGO_TIGHTLY_PACK>
 __global__ __launch_bounds__(kWave* kFusedWaves) void shard_finish_zoned_kernel(
     NodeTable T, ShardZones SZ, uint32_t n_shards, uint32_t n_apps, const gf_app* __restrict__ apps,
     const gf_shard_partial* __restrict__ all_part, const gf_shard_driver* __restrict__ all_drv, gf_result* __restrict__ results,
@@ -576,9 +581,9 @@ __global__ __launch_bounds__(kWave* kFusedWaves) void shard_finish_zoned_kernel(
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
                 bool done = false;
-                if (K >= 1 && K <= (int64_t)kRunBlocks * kWave)
+                if (ALGO == GF_ALGO_TIGHTLY_PACK && K >= 1 && K <= (int64_t)kRunBlocks * kWave)
                     done = wave_avg_max_tight_runs(EV, app, ds, out, lane, (lds_u32*)&sh.runs[wave][0], avg[3]);
-                if (!done) wave_avg_efficiency_runs<GF_ALGO_TIGHTLY_PACK>(EV, app, ds, out, lane, avg);
+                if (!done) wave_avg_efficiency_runs<ALGO>(EV, app, ds, out, lane, avg);
             }
         }
         if (lane == 0) {
@@ -613,6 +618,355 @@ __global__ __launch_bounds__(kWave* kFusedWaves) void shard_finish_zoned_kernel(
         results[a] = r;
     }
 }
+
+// ---- the minimal-fragmentation packers (minimal_fragmentation.go:59-137; single_az.go:23-97 with it as the inner packer)
+// "The smallest capacity >= K" is a minimum over every candidate: the packer cannot stop early, every application walks the
+// whole executor order, and that walk divides by the number of shards.  team_minfrag_hist (gangfit_minfrag.inc) already has the
+// shape — a quarter of the order per wavefront, per-quarter count rows, one plan from their sum, every quarter emits its runs
+// from "how many nodes of every capacity precede my quarter" —; a shard is a quarter whose rows travel through the first exchange
+// instead of LDS:
+//
+//   counts   (kernel 1)  tightly-pack's S_s over the range, with no early stop (feasibility and the driver rule are tightly-pack's:
+//                        internalMinimalFragmentation succeeds <=> sum of min(cap, K) >= K), and a COUNT ROW: for every capacity
+//                        c in 1 .. 255 the executor candidates of the range with cap(n, nothing reserved) = c, counted in the
+//                        snapshot's scaled int32 domain as pass 1 of wave_minfrag_hist does.  kMfRowWords words: uint16 counts,
+//                        lane l's bins 4l .. 4l+3 in words 2l, 2l+1.  fit_count of the record = 1 says "no histogram form": a
+//                        capacity >= 256 in the range, a request or a snapshot without scaled form, a range of 65 536 slots or more
+//       -- all-gather [n_shards][views][n_apps] x (16 B + 512 B) --
+//   drivers  (kernel 2)  shard_drivers_kernel / shard_drivers_zoned_kernel as they are
+//       -- all-gather x 16 B --
+//   emit     (kernel 3)  the winning driver slot d is the minimum over shards; every shard holds the whole table, reads slot d
+//                        itself, c0 = cap(d, 0), c1 = cap(d, drv), and patches [c0]--, [c1]++ into the summed rows when d is an
+//                        executor candidate of the view — and into its prefix (the rows of the shards before it) when d lies in an
+//                        earlier range.  The plan is team_minfrag_hist's; pass 2 runs over the shard's own range with the driver
+//                        reserved at d, a node's rank in its level = prefix + running count, and the shard writes only its own
+//                        runs (node + 1; slot + 1 for the zone views).  The ONE node that takes everything, or what the drained
+//                        levels leave, is named by the plan as (level, rank): the shard whose range holds it emits it.
+//                        Applications some shard flagged "no histogram form" are decided by shard  a mod n_shards  alone, over
+//                        the FULL order with wave_minfrag's walk and the known driver; the other shards write nothing.
+//       -- all-reduce(SUM) of the placement buffer --
+//   finish   (kernel 4)  plain: shard_finish_kernel<tightly-pack> (node + 1 -> node); single-AZ: shard_finish_zoned_kernel with
+//                        minimal-fragmentation's averages.
+// Gangs of gpu executors take the full range (the scaled columns exist for the full table only; the compact gpu view would give
+// the same answers).
+constexpr uint32_t kMfRowWords = kMfHistBins / 2;    // a count row: kMfHistBins uint16 counts
+constexpr uint32_t kMfRowMaxSlots = 65536;           // ... exact below this many slots in the range
+static_assert(kMfRowWords * sizeof(uint32_t) == kShardMfRowBytes, "the count row of gf_shard_mf_layout");
+
+// MfNarrow's fields as LANE values for a pass (wave_minfrag_hist says why)
+#define GF_MF_PIN(nv)  \
+    GF_HERE(nv.drv0);  \
+    GF_HERE(nv.drv1);  \
+    GF_HERE(nv.drv2);  \
+    GF_HERE(nv.exe0);  \
+    GF_HERE(nv.exe1);  \
+    GF_HERE(nv.exe2);  \
+    GF_HERE(nv.mag0);  \
+    GF_HERE(nv.mag1);  \
+    GF_HERE(nv.mag2);  \
+    GF_HERE(nv.sh0);   \
+    GF_HERE(nv.sh1);   \
+    GF_HERE(nv.sh2);   \
+    GF_HERE(nv.un0);   \
+    GF_HERE(nv.un1);   \
+    GF_HERE(nv.un2)
+
+// Counts of view c = blockIdx.z (the plain packer: the one view): the range's capacity sum and count row.
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void shard_mf_counts_kernel(NodeTable T, ShardSet SS, ShardZones SZ, uint32_t n_apps,
+                                                                               const gf_app* __restrict__ apps,
+                                                                               gf_shard_partial* __restrict__ part,
+                                                                               uint32_t* __restrict__ counts, PeerPtrs part_dsts,
+                                                                               PeerPtrs cnt_dsts) {
+    typedef uint32_t mf_u32x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) mf_u32x4 lds_mf4;
+    __shared__ __attribute__((aligned(16))) uint32_t hist[kWavesPerBlock * kMfHistBins];
+    const int lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t a = blockIdx.x * kWavesPerBlock + wave;
+    if (a >= n_apps) return;
+    const uint32_t q = blockIdx.y, c = blockIdx.z;
+    const ShardView zv = shard_view(T, SparseTable{}, SS, SZ, q, c);
+    const App app = load_app(apps, a);
+    const int64_t K = app.k;
+    const GlobalView V{T.cpu, T.mem, T.gpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, zv.xm, zv.dm, T.n_chunks};
+    Orders O{T.slot_node, T.dslot, T.n_x, T.n_d, true};
+    lds_u32* const A = (lds_u32*)hist + (size_t)wave * kMfHistBins;
+    O.lend_minfrag(A, T);
+    lds_mf4* const A4 = (lds_mf4*)A;
+    A4[lane] = mf_u32x4{0u, 0u, 0u, 0u};
+    MfNarrow na;
+    // (wave-uniform) the request and the snapshot have a scaled form, and uint16 counts cannot wrap
+    bool hist_ok = T.ncpu != nullptr && mf_narrow_app(app, O, na) && (zv.c_hi - zv.c_lo) * (uint32_t)kWave < kMfRowMaxSlots;
+    const bool walk = K != 0 && zv.c_lo < zv.c_hi;
+    if (hist_ok && walk) {
+        MfNarrow nv = na;
+        GF_MF_PIN(nv);
+        int32_t cmax = 0;
+        mf_for_each_chunk_narrow(V, O, app, nv, GF_NO_NODE, lane, [&](uint32_t, int32_t cp) {
+            cmax = cp > cmax ? cp : cmax;
+            const bool binned = cp > 0 && cp < kMfHistBins;
+            const uint32_t n_run = mf_run_heads((uint32_t)cp, binned, lane);  // (pass 1 of wave_minfrag_hist: a run speaks through its first lane)
+            if (n_run != 0u) __hip_atomic_fetch_add(A + (uint32_t)cp, n_run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            return true;
+        }, zv.c_lo, zv.c_hi);
+        if (__ballot(cmax >= kMfHistBins) != 0ull) hist_ok = false;
+    }
+    int64_t S = 0;
+    uint32_t cn[4] = {0u, 0u, 0u, 0u};
+    if (hist_ok) {
+        const mf_u32x4 c4 = A4[lane];  // (LDS operations of a wavefront execute in order)
+        cn[0] = c4.x;
+        cn[1] = c4.y;
+        cn[2] = c4.z;
+        cn[3] = c4.w;
+        int64_t lsum = 0;  // (the range holds fewer than 2^16 slots of capacity below 2^8: the sum stays below 2^24)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t cp = 4 * lane + i;
+            lsum += (int64_t)cn[i] * (cp < K ? cp : K);
+        }
+        S = wave_sum_small(lsum);
+    } else if (walk) {  // the wide table, as shard_partials_zoned_kernel
+        shard_scan_range(V, zv.c_lo * kWave, zv.c_hi * kWave, app.exe0, app.exe1, app.exe2, lane, [&](uint32_t j, bool in) {
+            int32_t cp = 0;
+            int64_t a0, a1, a2;
+            if (load_with_cand<false>(V, j, T.n_x, a0, a1, a2) && in) {
+                if (cap_ge1(a0, a1, a2, app)) cp = cap3(a0, a1, a2, app);
+            }
+            S += read_lane(wave_inclusive_scan(cp), kWave - 1);
+            return S < 2 * K;
+        });
+    }
+    const uint32_t n_cand = gridDim.z;
+    const size_t rec_loc = (size_t)(q * n_cand + c) * n_apps + a, rec_all = (size_t)(SS.shard[q] * n_cand + c) * n_apps + a;
+    const uint2 w = make_uint2(cn[0] | (cn[1] << 16), cn[2] | (cn[3] << 16));
+    if (cnt_dsts.n == 0) {
+        reinterpret_cast<uint2*>(counts + rec_loc * kMfRowWords)[lane] = w;
+    } else {
+        for (uint32_t t = 0; t < cnt_dsts.n; ++t)
+            reinterpret_cast<uint2*>(reinterpret_cast<uint32_t*>(cnt_dsts.p[t]) + rec_all * kMfRowWords)[lane] = w;
+    }
+    if (lane == 0) {
+        gf_shard_partial p;
+        p.cap_sum = S;
+        p.fit_count = hist_ok ? 0 : 1;  // "no histogram form"
+        shard_publish(p, part_dsts, part, q * n_cand + c, SS.shard[q] * n_cand + c, n_apps, a);
+    }
+}
+
+// Emit of view c: the shard's slice of the view's minimal-fragmentation placement into region c of the buffer (node + 1 for the
+// plain packer, which also gets its result record here; slot + 1 for the zone views, whose finish step chooses).
+template <bool ZONED>
+__global__ __launch_bounds__(kWave* kWavesPerBlock) void shard_mf_emit_kernel(
+    NodeTable T, ShardSet SS, ShardZones SZ, uint32_t n_apps, const gf_app* __restrict__ apps,
+    const gf_shard_partial* __restrict__ all_part, const gf_shard_driver* __restrict__ all_drv,
+    const uint32_t* __restrict__ all_cnt, gf_result* __restrict__ results, uint32_t* __restrict__ exec2, uint64_t half) {
+    typedef uint32_t mf_u32x4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) mf_u32x4 lds_mf4;
+    __shared__ __attribute__((aligned(16))) uint32_t hist[kWavesPerBlock * 3 * kMfHistBins];
+    const int lane = lane_id();
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t a = blockIdx.x * kWavesPerBlock + wave;
+    if (a >= n_apps) return;
+    const uint32_t q = blockIdx.y, c = blockIdx.z, n_cand = gridDim.z, shard = SS.shard[q], n_shards = SS.n_shards;
+    const ShardView zv = shard_view(T, SparseTable{}, SS, SZ, q, c);
+    const App app = load_app(apps, a);
+    const int64_t K = app.k;
+    const size_t row = (size_t)n_cand * n_apps, rec = (size_t)c * n_apps + a;  // records between two shards' rows | this view's
+    uint32_t pos = GF_NO_NODE;
+    bool flagged = false;
+    for (uint32_t t = 0; t < n_shards; ++t) {  // (wave-uniform scalar loops over shards, as shard_sums)
+        const uint32_t p = all_drv[(size_t)t * row + rec].pos;
+        pos = p < pos ? p : pos;
+        flagged = flagged || all_part[(size_t)t * row + rec].fit_count != 0;
+    }
+    const bool feasible = pos < T.n_slots;  // (GF_NO_NODE, or what a wrong exchange left: no table read goes out of bounds)
+    if (!ZONED && lane == 0 && q == 0) {  // (every hosted shard derives the same record: the first grid row stores it)
+        gf_result r;
+        r.has_capacity = feasible ? 1 : 0;
+        r.driver_node = feasible ? T.slot_node[pos] : GF_NO_NODE;
+        r.exec_len = feasible ? (uint32_t)K : 0u;
+        r.evaluated = 1;
+        results[a] = r;
+    }
+    if (!feasible || K == 0) return;
+    uint32_t* out = exec2 + (size_t)c * half + app.exec_off;
+    const GlobalView V{T.cpu, T.mem, T.gpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, zv.xm, zv.dm, T.n_chunks};
+    Orders O{T.slot_node, T.dslot, T.n_x, T.n_d, true};
+    if (flagged) {  // no histogram form in some range: ONE shard decides over the full order with the walk, the others write nothing
+        if (shard != a % n_shards) return;
+        unsigned long long visited = 0;
+        (void)wave_minfrag<GlobalView, true>(V, O, app, pos, out, lane, visited);  // (no LDS lent: the walk) slots into out[0, K)
+        // out[] was written by other lanes of this wave
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        const uint32_t last = T.n_slots - 1u;
+        for (int64_t i = lane; i < K; i += kWave) {
+            const uint32_t s = out[i] < last ? out[i] : last;
+            out[i] = (ZONED ? s : T.slot_node[s]) + 1u;
+        }
+        return;
+    }
+    lds_u32* const A = (lds_u32*)hist + (size_t)wave * 3 * kMfHistBins;  // plan: nodes a level gives completely
+    lds_u32* const B = A + kMfHistBins;                                  // plan: where the level's runs start in out[]
+    lds_u32* const C = A + 2 * kMfHistBins;                              // pass 2: nodes of the level seen so far (starts at the prefix)
+    O.lend_minfrag(A, T);
+    MfNarrow na;
+    if (T.ncpu == nullptr || !mf_narrow_app(app, O, na)) return;  // (every shard would have flagged it)
+    // ---- the driver's node before and after the reservation (every shard holds the whole table)
+    const bool d_x = pos < T.n_x && V.xcand(pos);
+    int32_t c0 = 0, c1 = 0;
+    if (d_x) {
+        const int32_t a0 = T.ncpu[pos], a1 = T.nmem[pos], a2 = T.ngpu[pos];
+        c0 = mf_ncap_of(true, a0, a1, a2, na, GF_NO_NODE, pos);
+        c1 = mf_ncap_of(true, a0, a1, a2, na, pos, pos);
+        if (c0 >= kMfHistBins || c1 >= kMfHistBins) return;  // (its range flagged it, unless a wrong exchange lost the flag: see below)
+    }
+    const uint32_t d_chunk = pos / kWave;
+    const bool d_before = d_x && d_chunk < SS.c_lo[q], d_mine = d_x && d_chunk >= SS.c_lo[q] && d_chunk < SS.c_hi[q];
+    // ---- the global counts, this range's prefix and its own counts (lane l: bins 4l .. 4l+3), with the driver's node moved
+    uint32_t cn[4] = {0u, 0u, 0u, 0u}, pre[4] = {0u, 0u, 0u, 0u}, own[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t t = 0; t < n_shards; ++t) {
+        const uint2 w = reinterpret_cast<const uint2*>(all_cnt + ((size_t)t * row + rec) * kMfRowWords)[lane];
+        const uint32_t cv[4] = {w.x & 0xFFFFu, w.x >> 16, w.y & 0xFFFFu, w.y >> 16};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            cn[i] += cv[i];
+            if (t < shard) pre[i] += cv[i];
+            if (t == shard) own[i] = cv[i];
+        }
+    }
+    // (a wrong exchange — what the multi-device context's self-check exists to catch — may leave rows that do not hold the driver's
+    // node: the counts then stay at zero instead of wrapping, the answer is wrong, and every store stays inside out[0, K))
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int32_t bin = 4 * lane + i;
+        const uint32_t add = (c1 > 0 && bin == c1) ? 1u : 0u, sub = (c0 > 0 && bin == c0) ? 1u : 0u;
+        cn[i] += add;
+        cn[i] -= sub < cn[i] ? sub : cn[i];
+        if (d_before) {
+            pre[i] += add;
+            pre[i] -= sub < pre[i] ? sub : pre[i];
+        }
+        if (d_mine) {
+            own[i] += add;
+            own[i] -= sub < own[i] ? sub : own[i];
+        }
+    }
+    // ---- the plan, by every shard alike: team_minfrag_hist's, on registers
+    int64_t lmax = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (cn[i] != 0u) lmax = 4 * lane + i;
+    const int64_t max_cap = wave_max_i64(lmax);
+    int64_t top = kMfHistBins;  // admitted: 0 < capacity < top
+    if (K < max_cap) {          // "avoid mostly empty nodes" (:68-78)
+        const int64_t target = (K + max_cap) / 2;
+        int64_t lsub = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t cp = 4 * lane + i, cc = cp < K ? cp : K;
+            const int64_t add = cp < target ? (int64_t)cn[i] * cc : 0;
+            lsub = lsub + add < K ? lsub + add : K;
+        }
+        if (wave_sum_small(lsub) >= K) top = target;
+    }
+    auto smallest_at_least = [&](int64_t need, int64_t below) {
+        int64_t l = kCapInf;
+#pragma unroll
+        for (int i = 3; i >= 0; --i) {
+            const int64_t cp = 4 * lane + i;
+            if (cn[i] != 0u && cp < below && cp >= need) l = cp;
+        }
+        return wave_min_i64(l);
+    };
+    auto largest_below = [&](int64_t below) {
+        int64_t l = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int64_t cp = 4 * lane + i;
+            if (cn[i] != 0u && cp < below) l = cp;
+        }
+        return wave_max_i64(l);
+    };
+    lds_mf4* const A4 = (lds_mf4*)A;
+    lds_mf4* const B4 = (lds_mf4*)B;
+    lds_mf4* const C4 = (lds_mf4*)C;
+    A4[lane] = mf_u32x4{0u, 0u, 0u, 0u};
+    B4[lane] = mf_u32x4{0u, 0u, 0u, 0u};
+    C4[lane] = mf_u32x4{pre[0], pre[1], pre[2], pre[3]};
+    int64_t R = K;
+    // the ONE node that takes everything (:103-110) or what the drained levels leave: the node of rank tgt_rank of level tgt_level
+    int64_t tgt_level = -1;
+    uint32_t tgt_rank = 0;
+    {
+        const int64_t cf = smallest_at_least(R, top);
+        if (cf != kCapInf) tgt_level = cf;
+    }
+    while (tgt_level < 0) {  // several nodes: the level walk (:113-130)
+        const int64_t m = largest_below(top);
+        if (m <= 0) return;  // unreachable for a feasible gang; guards against a non-terminating walk
+        const uint32_t cnt = mf_bin(cn, (uint32_t)m);
+        const uint32_t qn = (uint32_t)R / (uint32_t)m;
+        const uint32_t drained = cnt < qn ? cnt : qn;
+        A[(uint32_t)m] = drained;  // (every lane stores the same word)
+        B[(uint32_t)m] = (uint32_t)(K - R);
+        R -= (int64_t)drained * m;
+        if (R == 0) break;
+        if (drained < cnt) {  // R < m: the smallest capacity >= R among the lower levels, else the first undrained node of this level
+            const int64_t cf = smallest_at_least(R, m);
+            tgt_level = cf != kCapInf ? cf : m;
+            tgt_rank = cf != kCapInf ? 0u : drained;
+            break;
+        }
+        top = m;  // :130 the drained level leaves the list
+        const int64_t cf = smallest_at_least(R, top);
+        if (cf != kCapInf) tgt_level = cf;
+    }
+    // what the plan wants from THIS range: of every drained level the nodes with ranks [pre, pre + own) below `taken`, and the
+    // target when its rank lies in here
+    uint32_t left;
+    {
+        const mf_u32x4 t4 = A4[lane];  // (behind the stores above: LDS operations of a wavefront execute in order)
+        const uint32_t tk[4] = {t4.x, t4.y, t4.z, t4.w};
+        int64_t want = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t ahead = tk[i] > pre[i] ? tk[i] - pre[i] : 0u;
+            want += (int64_t)(ahead < own[i] ? ahead : own[i]);
+            if ((int64_t)(4 * lane + i) == tgt_level && tgt_rank >= pre[i] && tgt_rank < pre[i] + own[i]) want += 1;
+        }
+        left = (uint32_t)wave_sum_small(want);
+    }
+    if (left == 0u || zv.c_lo >= zv.c_hi) return;
+    // ---- pass 2 over the own range, the driver reserved at d
+    const uint64_t lt_mask = (1ull << lane) - 1ull;
+    MfNarrow nv = na;
+    GF_MF_PIN(nv);
+    mf_for_each_chunk_narrow(V, O, app, nv, pos, lane, [&](uint32_t j, int32_t cp) {
+        const bool binned = cp > 0 && cp < kMfHistBins;
+        const uint32_t cb = binned ? (uint32_t)cp : 0u;  // (bin 0 is nobody's level: its words are zero)
+        const uint32_t take = A[cb], base = B[cb], seen = C[cb];
+        const bool act = binned && (take != 0u || (int64_t)cp == tgt_level);
+        if (__ballot(act) == 0ull) return true;
+        const uint64_t peers = mf_peers8((uint32_t)cp, act);
+        const uint32_t rk = seen + (uint32_t)__popcll((unsigned long long)(peers & lt_mask));
+        if (act && (peers & lt_mask) == 0ull) C[cb] = seen + (uint32_t)__popcll((unsigned long long)peers);  // the peers' leader
+        const bool drain = act && rk < take;
+        const bool tgt = act && (int64_t)cp == tgt_level && rk == tgt_rank;
+        uint32_t id = 0;
+        if (drain || tgt) id = (ZONED ? j : T.slot_node[j]) + 1u;
+        emit_runs(out, (int64_t)base + (int64_t)rk * cp, drain ? cp : 0, id, lane);  // :122
+        const uint64_t tm = __ballot(tgt);
+        if (tm) {  // :106-109 R copies behind the drained levels' runs
+            const uint32_t tid = read_lane(id, __ffsll((unsigned long long)tm) - 1);
+            for (int64_t i = lane; i < R; i += kWave) out[K - R + i] = tid;
+        }
+        left -= (uint32_t)__popcll((unsigned long long)__ballot(drain)) + (tm ? 1u : 0u);
+        return left != 0u;
+    }, zv.c_lo, zv.c_hi);
+}
+#undef GF_MF_PIN
 
 // ---- the exchanges of the in-process multi-device context (gf_init with n_dev > 1): peer access over xGMI instead of a
 // collective library.  The messages are KB-sized, so what matters is the number of round trips, not bandwidth:

@@ -46,7 +46,8 @@ EXPORTED_SYMBOLS = [
     "gf_fit_batch_dev", "gf_spark_binpack", "gf_residual_get", "gf_timer_begin", "gf_timer_end", "gf_scan_stats", "gf_chain_profile",
     "gf_selftest", "gf_device_info_get", "gf_zones_set", "gf_avg_packing_efficiency", "gf_packing_efficiencies",
     "gf_hbm_probe", "gf_executor_fit", "gf_executor_fit_zoned", "gf_snapshot_build", "gf_snapshot_get", "gf_shard_set", "gf_shard_partials_dev", "gf_shard_drivers_dev", "gf_shard_emit_dev", "gf_shard_finish_dev",
-    "gf_shard_layout",
+    "gf_shard_layout", "gf_shard_mf_layout", "gf_shard_mf_counts_dev", "gf_shard_mf_drivers_dev", "gf_shard_mf_emit_dev",
+    "gf_shard_mf_finish_dev",
     "gf_find_nodes", "gf_ctx_lock", "gf_ctx_unlock", "gf_launch_floor",
     "gf_graph_begin", "gf_graph_end", "gf_graph_launch", "gf_graph_destroy", "gf_cluster_set", "gf_snapshot_build_resident",
     "gf_usage_reset", "gf_usage_apply", "gf_overhead_update", "gf_set_option", "gf_chain_cache_stats", "gf_generation", "gf_shard_count", "gf_ctx_view",
@@ -180,6 +181,16 @@ def load() -> C.CDLL:
     L.gf_shard_finish_dev.argtypes = [p, i32, u32, p, p, p, p, p, u64, p]
     L.gf_shard_layout.restype = i32
     L.gf_shard_layout.argtypes = [p, i32, u64, p, p, p]
+    L.gf_shard_mf_layout.restype = i32
+    L.gf_shard_mf_layout.argtypes = [p, i32, u64, p, p, p, p]
+    L.gf_shard_mf_counts_dev.restype = i32
+    L.gf_shard_mf_counts_dev.argtypes = [p, i32, u32, p, p, p, p]
+    L.gf_shard_mf_drivers_dev.restype = i32
+    L.gf_shard_mf_drivers_dev.argtypes = [p, i32, u32, p, p, p, p]
+    L.gf_shard_mf_emit_dev.restype = i32
+    L.gf_shard_mf_emit_dev.argtypes = [p, i32, u32, p, p, p, p, p, p, u64, p]
+    L.gf_shard_mf_finish_dev.restype = i32
+    L.gf_shard_mf_finish_dev.argtypes = [p, i32, u32, p, p, p, p, p, u64, p]
     L.gf_residual_get.restype = i32
     L.gf_residual_get.argtypes = [p, p]
     L.gf_timer_begin.restype = i32

@@ -18,6 +18,12 @@ The zone-aware tightly-pack packers (single-az-tightly-pack, az-aware-tightly-pa
 — every zone, plus the plain order for az-aware —, with records and placement regions per view; how many, and how much of
 the placement buffer the all-reduce sums, comes from the library (gf_shard_layout, HipShardEngine.layout).
 
+The minimal-fragmentation packers (minimal-fragmentation, single-az-minimal-fragmentation) walk the whole executor order for
+every application — "the smallest capacity >= K" is a minimum over every candidate —, so theirs is the walk that divides by the
+number of shards.  They are a family of steps of their own (gf_shard_mf_*, ShardedMinfragBatch, sharded_fit_minfrag): the first
+exchange carries, next to the 16-byte records, a row of capacity counts per application and view (512 B), from which every
+rank makes the same plan and emits its own range's runs.  Still three exchanges per batch.
+
 This file is orchestration only: no arithmetic on placements happens in Python, and there is no CPU fallback —
 `HipShardEngine` raises when libgangfit or the GPU is missing.  `Comm`/engine are small interfaces so that the N > 1 control
 flow is also exercised on CPU (tests/test_sharded_cpu.py: world_size-2 gloo with a numpy engine from tests/).
@@ -209,6 +215,53 @@ class HipShardEngine:
                                             C.c_void_p(res.data_ptr()), C.c_void_p(exec2.data_ptr()), half,
                                             self._stream()))
 
+    # ---- the minimal-fragmentation family (gf_shard_mf_*)
+    def mf_layout(self, algo: int, half: int):
+        """(records per application, bytes of a count row, words of the placement buffer, leading words of it the all-reduce
+        sums) of a minimal-fragmentation batch with sum of k = half - 1 (gf_shard_mf_layout)."""
+        rec, row, words, red = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+        c = self.ctx
+        c._check(c._lib.gf_shard_mf_layout(c._h, algo, half, C.byref(rec), C.byref(row), C.byref(words), C.byref(red)))
+        return int(rec.value), int(row.value), int(words.value), int(red.value)
+
+    def mf_counts(self, algo: int, d_apps, n_apps: int, records: int, row_bytes: int):
+        """This shard's records and count rows in ONE buffer (what the first exchange carries): records * n_apps 16-byte records,
+        then records * n_apps rows."""
+        n = records * n_apps
+        out = self._torch.empty(n * (16 + row_bytes), dtype=self._torch.uint8, device=self.device)
+        c = self.ctx
+        c._check(c._lib.gf_shard_mf_counts_dev(c._h, algo, n_apps, C.c_void_p(d_apps.data_ptr()), C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(out.data_ptr() + n * 16), self._stream()))
+        return out
+
+    def mf_split(self, gathered, n_apps: int, records: int):
+        """The gathered [world, bytes] buffers of mf_counts as the two tables the later steps read: [world][records][n_apps]
+        records, and the rows in the same order."""
+        n = records * n_apps
+        return gathered[:, : n * 16].contiguous(), gathered[:, n * 16:].contiguous()
+
+    def mf_drivers(self, algo: int, d_apps, n_apps: int, all_part, records: int):
+        out = self._torch.empty((records * n_apps, 4), dtype=self._torch.int32, device=self.device)
+        c = self.ctx
+        c._check(c._lib.gf_shard_mf_drivers_dev(c._h, algo, n_apps, C.c_void_p(d_apps.data_ptr()),
+                                                C.c_void_p(all_part.data_ptr()), C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def mf_emit(self, algo: int, d_apps, n_apps: int, all_part, all_drv, all_cnt, half: int, words: int):
+        res = self._torch.empty(n_apps * 16, dtype=self._torch.uint8, device=self.device)
+        exec2 = self._torch.empty(words, dtype=self._torch.int32, device=self.device)
+        c = self.ctx
+        c._check(c._lib.gf_shard_mf_emit_dev(c._h, algo, n_apps, C.c_void_p(d_apps.data_ptr()), C.c_void_p(all_part.data_ptr()),
+                                             C.c_void_p(all_drv.data_ptr()), C.c_void_p(all_cnt.data_ptr()),
+                                             C.c_void_p(res.data_ptr()), C.c_void_p(exec2.data_ptr()), half, self._stream()))
+        return res, exec2
+
+    def mf_finish(self, algo: int, d_apps, n_apps: int, all_part, all_drv, res, exec2, half: int):
+        c = self.ctx
+        c._check(c._lib.gf_shard_mf_finish_dev(c._h, algo, n_apps, C.c_void_p(d_apps.data_ptr()),
+                                               C.c_void_p(all_part.data_ptr()), C.c_void_p(all_drv.data_ptr()),
+                                               C.c_void_p(res.data_ptr()), C.c_void_p(exec2.data_ptr()), half, self._stream()))
+
 
 # ------------------------------------------------------------------------------------------------ orchestration
 SHARDED_ALGOS = (N.GF_ALGO_TIGHTLY_PACK, N.GF_ALGO_DISTRIBUTE_EVENLY, N.GF_ALGO_SINGLE_AZ_TIGHTLY_PACK,
@@ -293,5 +346,80 @@ class ShardedBatch:
 def sharded_fit(engine, comm: Comm, algo: int, apps: np.ndarray) -> BatchOut:
     """gf_fit_batch(GF_MODE_INDEPENDENT) with the node table sharded by priority-order range over comm.world GPUs."""
     b = ShardedBatch(engine, comm, algo, apps)
+    b.step()
+    return b.fetch()
+
+
+# ------------------------------------------------------------------------------------------------ minimal-fragmentation
+MINFRAG_ALGOS = (N.GF_ALGO_MINIMAL_FRAGMENTATION, N.GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION)
+
+
+class ShardedMinfragBatch:
+    """ShardedBatch for the minimal-fragmentation packers: counts -> all-gather (records and count rows, one buffer) -> drivers
+    -> all-gather -> emit -> all-reduce(SUM) of the placement buffer -> finish."""
+
+    def __init__(self, engine, comm: Comm, algo: int, apps: np.ndarray):
+        if algo not in MINFRAG_ALGOS:
+            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, "the minimal-fragmentation shard steps serve minimal-fragmentation and "
+                                                      "single-az-minimal-fragmentation only")
+        self.engine, self.comm, self.algo = engine, comm, algo
+        apps = np.ascontiguousarray(apps, dtype=N.APP_DTYPE)
+        self.apps_off, self.total_k = with_offsets(apps)
+        self.n_apps = len(apps)
+        self.half = self.total_k + 1
+        self.records, self.row_bytes, self.words, self.reduce_words = engine.mf_layout(algo, self.half)
+        with engine.stream_context():
+            self.d_apps = engine.upload_apps(self.apps_off)
+        self.res = self.exec2 = None
+
+    def first_exchange_bytes_per_app(self) -> int:
+        """What one rank contributes to the first all-gather per application (every view's record and count row)."""
+        return self.records * (16 + self.row_bytes)
+
+    def _placements(self):
+        return self.exec2 if self.reduce_words >= len(self.exec2) else self.exec2[: self.reduce_words]
+
+    def _steps(self, mark):
+        e, c, algo, n, rec = self.engine, self.comm, self.algo, self.n_apps, self.records
+        with e.stream_context():
+            mine = e.mf_counts(algo, self.d_apps, n, rec, self.row_bytes)
+            mark(0)
+            gathered = c.all_gather(mine)
+            mark(1)
+            all_part, all_cnt = e.mf_split(gathered, n, rec)
+            drv = e.mf_drivers(algo, self.d_apps, n, all_part, rec)
+            mark(2)
+            all_drv = c.all_gather(drv)
+            mark(3)
+            self.res, self.exec2 = e.mf_emit(algo, self.d_apps, n, all_part, all_drv, all_cnt, self.half, self.words)
+            mark(4)
+            c.all_reduce_sum_(self._placements())
+            mark(5)
+            e.mf_finish(algo, self.d_apps, n, all_part, all_drv, self.res, self.exec2, self.half)
+
+    def step(self):
+        self._steps(lambda i: None)
+
+    def step_timed(self):
+        """step(), with a pair of events on the engine's stream around each of the three exchanges (GPU engines only).  Returns
+        [all-gather of the records and count rows, all-gather of the drivers, all-reduce of the placements] in microseconds."""
+        import torch
+
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        self._steps(lambda i: ev[i].record(self.engine.stream))
+        self.engine.stream.synchronize()
+        return [ev[2 * i].elapsed_time(ev[2 * i + 1]) * 1e3 for i in range(3)]
+
+    def fetch(self) -> BatchOut:
+        with self.engine.stream_context():
+            res = self.res.cpu().numpy().view(N.RESULT_DTYPE).copy()
+            ex = self.exec2[: self.total_k].cpu().numpy().view(np.uint32).copy()
+        return BatchOut(res, self.apps_off["exec_off"].copy(), ex, -1)
+
+
+def sharded_fit_minfrag(engine, comm: Comm, algo: int, apps: np.ndarray) -> BatchOut:
+    """gf_fit_batch(GF_MODE_INDEPENDENT) of a minimal-fragmentation packer with the node table sharded by priority-order range
+    over comm.world GPUs."""
+    b = ShardedMinfragBatch(engine, comm, algo, apps)
     b.step()
     return b.fetch()

@@ -159,6 +159,11 @@ int worker_launch(gf_ctx* ctx, gf_algo algo, uint64_t first_ticket) {
     }
     a.sets = sets;
     a.blocks_per_set = bps;
+    {   // the rounds' one quotient, by app_stride = 16 * bps, as a multiplication (gangfit_worker_rounds.h)
+        const gangfit::rounds::StrideDiv d = gangfit::rounds::make_stride_div(bps);
+        a.stride_mul = d.mul;
+        a.stride_shift = d.shift;
+    }
     w.cur_sets = sets;
     w.cur_blocks_per_set = bps;
     a.stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr;

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "gangfit.h"
+#include "gangfit_worker_rounds.h"
 
 namespace gangfit {
 
@@ -187,13 +188,15 @@ struct WorkerArgs {
     // (two round trips, ~4 us of a 60 us window of twenty tickets).  The leader relays them all the same (the ring is what
     // later rounds and the completion accounting index).
     uint32_t n_inline;
-    uint32_t pad_inline;
+    uint32_t stride_mul;  // rounds::make_stride_div(blocks_per_set).mul: the launch's quotient by app_stride (gangfit_worker_rounds.h)
     unsigned long long inline_words[kWorkerInline][6];
     // The zone-aware tightly-pack instances only (single-az-tightly-pack, az-aware-tightly-pack; behind everything the plain
     // instances read, whose argument offsets stay where they were): the zone rows of the evaluation list — at most 64 candidate
     // views, the plain order of az-aware included — and SchedulableResources in slot order (3 * n_slots), for the averages.
     ZoneTable zones;
     const int64_t* sched;
+    uint32_t stride_shift;  // ... and its shift (behind everything else: no earlier argument moves)
+    uint32_t pad_stride;
 };
 
 // tightly-pack, distribute-evenly, minimal-fragmentation, single-az-tightly-pack, az-aware-tightly-pack

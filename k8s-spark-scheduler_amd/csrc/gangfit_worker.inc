@@ -56,6 +56,19 @@
 // decisions/s (medians +5.4 %, ranges apart); a window of twenty: unchanged.  94 VGPRs, code 31.9 -> 48.5 KB.
 // (The table itself resident in LDS was a different experiment — r6c above — and stays removed.)
 
+// ROUND BOOKKEEPING (profiles/r8a_worker_rounds_summary.md): what a wavefront executes around its decisions.  The round arithmetic
+// lives in gangfit_worker_rounds.h (no runtime division: the rotation advances by one and wraps by compare, the one quotient by
+// app_stride is a multiplication by a constant of the launch, the workgroup's share of a ticket is a closed form instead of a
+// per-lane division and a wave scan); the hand-out word is taken with ONE LDS operation (fetch-and-add first, compare-and-swap only
+// on a stale word); what the round's end extracts from the next ticket is carried into the next round instead of being read apart
+// again; the narrow path keeps its lane's group 0 in seven registers instead of five LDS reads per application.  Measured against
+// the parent, interleaved on one machine: 752.8 k -> 724.9 k instructions per ticket at K = 2 000 (scalar -21.5 k, LDS -4.1 k,
+// vector -2.2 k), 968-978 M -> 997-1 016 M decisions/s (medians +4.0 %, ranges apart); a window of twenty: unchanged.  94 -> 98
+// VGPRs (92 before group 0 moved into registers; budget 104).
+// Measured and dropped: the carried ticket values forced into scalar registers (v_readfirstlane at the round's top) — 735.2 k
+// instructions per ticket and 994 M decisions/s against 728.8 k and 1 007 M without: more spilled scalar registers than it saves
+// vector compares.
+
 __device__ __forceinline__ unsigned long long sys_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -255,6 +268,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     const uint32_t b = blockIdx.x - 1u;
     const uint32_t set = b / W.blocks_per_set, bs = b % W.blocks_per_set;
     const uint32_t app_stride = W.blocks_per_set * kWorkerWaves;
+    const rounds::StrideDiv sdiv{W.stride_mul, W.stride_shift};  // x / app_stride without a division (gangfit_worker_rounds.h)
     // the first ticket of this set at or behind first_ticket
     unsigned long long t = W.first_ticket + (unsigned long long)((set + W.sets - (uint32_t)(W.first_ticket % W.sets)) % W.sets);
     GlobalView V{T.cpu, T.mem, T.gpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, T.xmask, T.dmask,
@@ -288,6 +302,20 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     const int64_t unit_l = T.nunit[lane % 3 == 0 ? 0 : (lane % 3 == 1 ? 1 : 2)];
     const double rcp_l = kNarrow ? fast_rcp((double)unit_l) : 0.0;
     __syncthreads();  // the only barrier of the kernel: the LDS words above
+    // NARROW: this lane's group 0 in units stays in registers (seven) — it is the same for every application while the worker lives,
+    // and reading it back per application put five LDS reads and their wait at the head of every decision.  (The int64 path keeps
+    // the LDS words: ten registers more would not fit the budget.)
+    constexpr bool kG0Regs = kNarrow;
+    Group0T<int32_t> g0n_regs{};
+    if constexpr (kG0Regs) {
+        if (narrow_table) {
+            g0n_regs.m0 = s_g0n[0][lane];
+            g0n_regs.m1 = s_g0n[1][lane];
+            g0n_regs.m2 = s_g0n[2][lane];
+            g0n_regs.dcand = s_g0[3][lane];
+            g0n_regs.xcand = s_g0[4][lane];
+        }
+    }
     typedef __attribute__((address_space(1))) const gf_app glb_app;
     typedef __attribute__((address_space(1))) gf_result glb_result;
     typedef __attribute__((address_space(1))) uint32_t glb_u32w;
@@ -306,21 +334,32 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     };
     // kRecords: the next application of round r of this workgroup (its i-th: wave-uniform).  The counter word carries the round
     // it counts for: the first wavefront to arrive in a round turns the word over (compare-and-swap), nobody ever resets it.
+    // ONE LDS operation on the common path: the fetch-and-add comes first and stands when the word it returns carries round r
+    // (the word cannot turn over under a wavefront of round r: nobody is eight rounds ahead).  A word that carries another round
+    // is a stale one — of round r - 8 k, or the zero of the start — and the add has left a stray increment in it.  That is
+    // harmless: the caller has passed round_guard(r), so every wavefront of the workgroup has left round r - 8 and all before it —
+    // nobody reads that count any more —, no wavefront can be in round r + 8 before this one has finished round r, and the
+    // turn-over below replaces the whole word, strays included.  A compare-and-swap that fails has lost either to another
+    // stray (try again) or to the turn-over (the word is round r's now: add).
     auto grab = [&](uint32_t r) {
         uint32_t got = 0;
         if (lane == 0) {
             unsigned long long* word = (unsigned long long*)&s_next[r % 8u];
-            for (;;) {
-                unsigned long long w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if ((uint32_t)(w >> 32) == r) {
-                    w = __hip_atomic_fetch_add(word, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    got = (uint32_t)w;  // (the word cannot turn over under a wavefront of round r: nobody is eight rounds ahead)
-                    break;
-                }
-                const unsigned long long fresh = ((unsigned long long)r << 32) | 1ull;
-                if (__hip_atomic_compare_exchange_strong(word, &w, fresh, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
-                    got = 0;
-                    break;
+            unsigned long long w = __hip_atomic_fetch_add(word, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            got = (uint32_t)w;
+            if (__builtin_expect((uint32_t)(w >> 32) != r, 0)) {
+                w += 1ull;  // (what this wavefront left there)
+                for (;;) {
+                    if ((uint32_t)(w >> 32) == r) {
+                        w = __hip_atomic_fetch_add(word, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        got = (uint32_t)w;
+                        break;
+                    }
+                    const unsigned long long fresh = ((unsigned long long)r << 32) | 1ull;
+                    if (__hip_atomic_compare_exchange_strong(word, &w, fresh, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
+                        got = 0;
+                        break;
+                    }
                 }
             }
         }
@@ -353,6 +392,13 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     }
     unsigned long long wrec = 0;  // the record of the application in hand (kRecords)
     uint32_t round = 0;
+    // What a round needs of its ticket to hand applications out, extracted ONCE per ticket: by the round before (kRecords, when the
+    // ticket had arrived by then: grabbed_cur) or at the round's top (a ticket probed for, brought along by the launch, and every
+    // ticket of the minimal-fragmentation instance).  bsr: the workgroup this one acts as in the round — it rotates, see below.
+    const gf_app* apps = nullptr;
+    uint64_t w5 = 0;    // n_apps | flags << 32
+    uint32_t rows = 0;  // rows of the workgroup's first lane (rounds::rows_of)
+    uint32_t bsr = bs;
     for (;;) {
         // ---- the ticket: brought along by the launch, requested a round ago, or probed for now
         if (W.leave_after != 0ull && t >= W.leave_after) break;  // a bounded stream: nothing behind its last ticket will come
@@ -372,11 +418,14 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         }
         // (a ticket's pointers name global memory — device or mapped pinned host memory —: said so, or every access through
         //  them is a flat instruction that counts against both wait counters)
-        const gf_app* apps = (const gf_app*)reinterpret_cast<glb_app*>((uint64_t)read_lane((int64_t)w_cur, 1) & kPtrMask);
+        if (!grabbed_cur) {
+            apps = (const gf_app*)reinterpret_cast<glb_app*>((uint64_t)read_lane((int64_t)w_cur, 1) & kPtrMask);
+            w5 = (uint64_t)read_lane((int64_t)w_cur, 5);
+            rows = rounds::rows_of((uint32_t)(w5 & 0xFFFFFFFFull), rounds::first_app(bsr), sdiv);
+        }
         gf_result* results = (gf_result*)reinterpret_cast<glb_result*>((uint64_t)read_lane((int64_t)w_cur, 2) & kPtrMask);
         uint32_t* exec_nodes = (uint32_t*)reinterpret_cast<glb_u32w*>((uint64_t)read_lane((int64_t)w_cur, 3) & kPtrMask);
         const unsigned long long half = ((uint64_t)read_lane((int64_t)w_cur, 4) & kPtrMask) + 1ull;
-        const uint64_t w5 = (uint64_t)read_lane((int64_t)w_cur, 5);
         const uint32_t n_apps = (uint32_t)(w5 & 0xFFFFFFFFull);
         const uint32_t slot = (uint32_t)(t % kWorkerRing);
         // Which applications of the ticket this wavefront takes ROTATES with the ticket: workgroup bs acts as workgroup
@@ -384,16 +433,15 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         // and again (bench.py does; a scan over instance groups does not) would otherwise hand the same wavefront the heaviest
         // applications every time, and — a ticket is complete when its slowest wavefront is, the ring admits ticket t + 64 when
         // ticket t is complete — the whole stream would run at that wavefront's pace (profiles/r6g_worker_async_phases_static_mapping.txt:
-        // rounds of 20 k cycles, then 13 k waiting for the next ticket).
-        const uint32_t bsr = (bs + round) % W.blocks_per_set, wvr = (wave + round) % (uint32_t)kWorkerWaves;
-        const uint32_t first_app = bsr * kWorkerWaves + wvr;
+        // rounds of 20 k cycles, then 13 k waiting for the next ticket).  (bsr advances by one per round and wraps by compare.)
+        const uint32_t first_app = rounds::first_app(bsr) + rounds::wave_of_round(wave, round);
         // the count words are recycled every kCountSlots rounds: not before every wavefront of the workgroup has left the round
         // that used this one (it practically never waits: the wavefronts serve the same tickets at the same pace)
         round_guard(round);
         // kRecords: the workgroup's applications of this ticket are i = 0 .. total - 1, application (i mod 16) of row (i div 16)
-        const uint32_t f0 = bsr * kWorkerWaves;
-        const uint32_t total = f0 < n_apps ? ((n_apps - 1u - f0) / app_stride + 1u) * kWorkerWaves : 0u;
-        auto app_index = [&](uint32_t i) { return f0 + (i % (uint32_t)kWorkerWaves) + (i / (uint32_t)kWorkerWaves) * app_stride; };
+        const uint32_t f0 = rounds::first_app(bsr);
+        const uint32_t total = rounds::total_of(rows);
+        auto app_index = [&](uint32_t i) { return rounds::app_index(f0, i, app_stride); };
         if constexpr (kRecords) {
             if (!grabbed_cur) {
                 i_cur = grab(round);
@@ -435,12 +483,14 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                 // (gangs of gpu executors are packed from the compact table of gpu nodes: wave_decide's `sparse`, int64 only)
                 if (narrow_table && scale_record(wrec, lane, unit_l, rcp_l, napp) &&
                     !(G.n_x != 0u && napp.exe2 > 0 && napp.k > 0 && T.d_identity != 0)) {
-                    Group0T<int32_t> g0n{};
-                    g0n.m0 = s_g0n[0][lane];
-                    g0n.m1 = s_g0n[1][lane];
-                    g0n.m2 = s_g0n[2][lane];
-                    g0n.dcand = s_g0[3][lane];
-                    g0n.xcand = s_g0[4][lane];
+                    Group0T<int32_t> g0n = g0n_regs;
+                    if constexpr (!kG0Regs) {
+                        g0n.m0 = s_g0n[0][lane];
+                        g0n.m1 = s_g0n[1][lane];
+                        g0n.m2 = s_g0n[2][lane];
+                        g0n.dcand = s_g0[3][lane];
+                        g0n.xcand = s_g0[4][lane];
+                    }
                     app_k = napp.k;
                     app_off = napp.exec_off;
                     dec = wave_decide<ALGO, NarrowView, false>(VN, O, napp, (direct ? exec_nodes : priv) + app_off, scratch + app_off,
@@ -508,26 +558,27 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         const bool have_next = words_valid(w_next, t_next);
         unsigned long long wrec_next = 0;
         uint32_t i_next = 0;
+        const uint32_t bsr_n = rounds::next_block(bsr, W.blocks_per_set);
+        const gf_app* apps_n = nullptr;
+        uint64_t w5_n = 0;
+        uint32_t rows_n = 0;
         if (kRecords && have_next) {  // the first application of the next round and its record, before this round's stores are drained
             round_guard(round + 1u);
-            const uint32_t f0n = ((bs + round + 1u) % W.blocks_per_set) * kWorkerWaves;
-            const gf_app* apps_n = (const gf_app*)reinterpret_cast<glb_app*>((uint64_t)read_lane((int64_t)w_next, 1) & kPtrMask);
-            const uint32_t n_apps_n = (uint32_t)((uint64_t)read_lane((int64_t)w_next, 5) & 0xFFFFFFFFull);
-            const uint32_t total_n = f0n < n_apps_n ? ((n_apps_n - 1u - f0n) / app_stride + 1u) * kWorkerWaves : 0u;
+            // (the next round starts from what is extracted here: it does not read the words apart again)
+            const uint32_t f0n = rounds::first_app(bsr_n);
+            apps_n = (const gf_app*)reinterpret_cast<glb_app*>((uint64_t)read_lane((int64_t)w_next, 1) & kPtrMask);
+            w5_n = (uint64_t)read_lane((int64_t)w_next, 5);
+            const uint32_t n_apps_n = (uint32_t)(w5_n & 0xFFFFFFFFull);
+            rows_n = rounds::rows_of(n_apps_n, f0n, sdiv);
             i_next = grab(round + 1u);
-            const uint32_t a_n = f0n + (i_next % (uint32_t)kWorkerWaves) + (i_next / (uint32_t)kWorkerWaves) * app_stride;
-            if (i_next < total_n && a_n < n_apps_n) wrec_next = load_record(apps_n, a_n);
+            const uint32_t a_n = rounds::app_index(f0n, i_next, app_stride);
+            if (i_next < rounds::total_of(rows_n) && a_n < n_apps_n) wrec_next = load_record(apps_n, a_n);
         }
         // this round's stores acknowledged (and the next records in registers) before the round is counted
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // ---- completion.  The workgroup's applications of this ticket: wavefront j serves first_j, first_j + stride, ...
+        // ---- completion.  The workgroup's applications of this ticket (lane j: first_j, first_j + stride, ...) in closed form
         {
-            uint32_t cnt_l = 0;
-            if (lane < kWorkerWaves) {
-                const uint32_t f = bsr * kWorkerWaves + (uint32_t)lane;
-                cnt_l = f < n_apps ? (n_apps - 1u - f) / app_stride + 1u : 0u;
-            }
-            const uint32_t share = (uint32_t)read_lane(wave_inclusive_scan((int32_t)cnt_l), kWave - 1);
+            const uint32_t share = rounds::share_of(n_apps, f0, app_stride, rows);
             // (a wavefront without an application in this ticket adds nothing: its zero, arriving between the last share and the
             //  reset of the word, would complete the workgroup a second time)
             if (share != 0u && mine != 0u) {
@@ -557,6 +608,10 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         wrec = wrec_next;
         i_cur = i_next;
         grabbed_cur = kRecords && have_next;
+        bsr = bsr_n;
+        apps = apps_n;
+        w5 = w5_n;
+        rows = rows_n;
     }
     if (lane == 0) __hip_atomic_store(&s_round[wave], kRoundGone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // never in anybody's way
 }

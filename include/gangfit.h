@@ -258,7 +258,9 @@ int gf_snapshot_build_info(gf_ctx *ctx, uint32_t out[4]);
  * all.  Sums of 64-bit integers: the result equals the replay of the full entry list bit for bit, whatever the order of the
  * updates.  Entries on nodes outside the cluster are ignored like the replay ignores them (resources.go:72). */
 /* gf_usage_apply(sign = -1) returns GF_ERR_INVALID and leaves the sums as they were when an entry is removed from a node
- * that does not carry it (the node's sum would go negative: available above allocatable).  When an update fails half way
+ * that does not carry it (the node's sum would go negative: available above allocatable; or its count of entries would — one
+ * uint32 per node kept next to the sums, +1 / -1 per entry, zeroed with them: what gf_cluster_executor_fit reads as "the node
+ * carries a reservation", which an entry of all zeros decides too).  When an update fails half way
  * on a multi-device context the resident usage is unusable (GF_ERR_STATE) until gf_usage_reset. */
 #define GF_RESIDENT_USAGE 0xFFFFFFFFu
 int gf_usage_reset(gf_ctx *ctx);
@@ -471,6 +473,42 @@ int gf_executor_fit(gf_ctx *ctx, int minimal_fragmentation, uint32_t n_req, cons
 #define GF_ANY_ZONE 0xFFFFFFFFu
 int gf_executor_fit_zoned(gf_ctx *ctx, int minimal_fragmentation, uint32_t n_req, const int64_t *exe, const int64_t *reserved,
                           const uint32_t *hosts_app, const uint32_t *node_zone, const uint32_t *req_zone, uint32_t *node_out);
+
+/* The executor Filter answered from the RESIDENT cluster, next to the installed snapshot instead of in its place.  rescheduleExecutor
+ * builds its metadata from getNodes(nodeNames) narrowed by filterNodesToZone (resource.go:604-632): the zone ranks of
+ * getNodeNamesInPriorityOrder are sums over THAT subset, so the installed driver snapshot's order cannot serve the call, and an install
+ * per executor throws away the driver Filter's chain cache.  The loop's answer needs no order: first-fit over a sorted list is the
+ * smallest key among the nodes that fit, and the minimal-fragmentation variant (:675-703) only replaces `best` strictly — the
+ * lexicographic minimum of (not hosting the application, capacity, position).  One launch of cluster_executor_fit_kernel (a workgroup
+ * per request) over the columns gf_cluster_set, gf_overhead_update and gf_usage_apply keep on the device: no sort, no install.
+ *   n_sets, set_words  rows as in gf_cluster_fit_feasible_sets (the request's NodeNames as a bit row); n_sets 0 + NULL = every node
+ *   exe                n_req x 3 executor requests in [0, 2^62)
+ *   req_set            n_req rows, each < n_sets; NULL when n_sets == 0
+ *   hosts_app          as gf_executor_fit: ceil(n_nodes / 32) words per request, nullable (read by the minimal-fragmentation variant)
+ *   node_zone, req_zone  as gf_executor_fit_zoned; node_zone NULL + req_zone given = the cluster's own zone ids
+ *   exec_label_rank    nullable, n_nodes, UINT32_MAX = not ranked
+ * Definition.  Q = req_zone[q] (GF_ANY_ZONE when req_zone is NULL); S = the nodes of row req_set[q] with node_zone[n] == Q (every node
+ * of the row when Q is GF_ANY_ZONE).  node_out[q] is the cluster index of the node gf_snapshot_build + gf_executor_fit return when
+ * they are given only the rows of S: available = allocatable - (resident usage sum + resident overhead); the cluster's zones ranked by
+ * their (memory, cpu) sums of available over S in wrapping 64-bit arithmetic, ties by zone id; executor candidates = GF_NODE_READY set
+ * and GF_NODE_UNSCHEDULABLE clear in the flags of gf_cluster_set; their order = (executor label rank when given, zone rank, available
+ * memory, available cpu, name_rank).  Subtracted from available before the fit test: first-fit — the node's overhead once more if at
+ * least one reservation entry names the node (`usage.Add(overhead)`, :642; gf_usage_apply keeps an entry count per
+ * node next to the sums, because an entry of all zeros still makes the node a key); minimal fragmentation — every node's overhead
+ * (GetNodeCapacities' reservedResources, :682).  First-fit: the candidate with the smallest key that the executor fits; minimal
+ * fragmentation: the smallest (not in hosts_app, capacity, key) among capacity >= 1; GF_NO_NODE when there is none or S is empty.
+ * A chained burst is deliberately not offered: the reference re-sorts between two executor Filters.
+ * Leaves untouched: the installed snapshot, zones and orders, all three words of gf_generation, the chain cache, recorded graphs,
+ * gf_residual_get's table, the resident worker.  Blocking; n_req x 4 bytes come back; its device buffers are its own; moves no
+ * O(n_nodes) array but node_zone / exec_label_rank when given.  n_req == 0 is GF_OK.  A multi-device context answers from its first
+ * device.
+ * Refusals (nothing changes, node_out stays untouched): no gf_cluster_set, a view, resident usage or overhead unusable after a failed
+ * update: GF_ERR_STATE; a cluster of more than 64 zones: GF_ERR_UNSUPPORTED; a request value outside [0, 2^62), req_set[q] >= n_sets,
+ * a set bit at or beyond n_nodes, req_set (or set_words) NULL with n_sets > 0, node_zone without req_zone, a node_zone entry equal to
+ * GF_ANY_ZONE, exe or node_out NULL: GF_ERR_INVALID. */
+int gf_cluster_executor_fit(gf_ctx *ctx, int minimal_fragmentation, uint32_t n_sets, const uint64_t *set_words, uint32_t n_req,
+                            const int64_t *exe, const uint32_t *req_set, const uint32_t *hosts_app, const uint32_t *node_zone,
+                            const uint32_t *req_zone, const uint32_t *exec_label_rank, uint32_t *node_out);
 
 /* findNodes of the failover reconciler (internal/extender/failover.go:412-436; call site :368): reserve space for k
  * executors of each of n_req stale applications by walking the executor order of gf_orders_set (the reconciler's

@@ -859,6 +859,73 @@ func (c *Context) ExecutorFitOnInstalledSnapshot(minimalFragmentation bool, exec
 	return names, nil
 }
 
+// ExecutorFitOnResidentCluster is the node choice of rescheduleExecutor (internal/extender/resource.go:594-703) answered from the
+// RESIDENT cluster (ClusterSet / OverheadUpdate / UsageApply) instead of an installed snapshot (include/gangfit.h,
+// gf_cluster_executor_fit): nothing is installed, so the driver Filter's snapshot and chain cache stay and its next Filter resumes.
+// setWords holds nSets rows of ceil(nNodes / 64) words, bit (n & 63) of word n >> 6 of a row = node n is one of the request's
+// NodeNames (nSets == 0, setWords nil: every node); reqSet[q] is the row request q asks.  zones == nil: no zone step; otherwise
+// zones[q] is the id of the zone getCommonZoneForExecutorsApplication (:493-519) found for request q, or AnyZone, compared with
+// nodeZone[n] — the ids of the topology.kubernetes.io/zone label (SURVEY.md quirk 7); nodeZone nil = the cluster's own zone ids.
+// hostsApp (nil, or ceil(nNodes / 32) words per request) marks the nodes that host executors of the application (read with
+// minimalFragmentation), execLabelRank (nil, or one rank per node, ^uint32(0) = not ranked) an executor-prioritized-node-label.
+// The zone ranks are those of the request's own subset of nodes, as in the reference, which is why no chained burst is offered:
+// the reference re-sorts between two executor Filters.  Returns node names, "" = "not enough capacity to reschedule the
+// executor".  On any error (ErrUnsupported for more than 64 zones, a state or argument error) install with
+// SnapshotBuildResident and call ExecutorFitOnInstalledSnapshot, as before.  Unverified here (no Go toolchain);
+// tests/test_gpu_cluster_executor.py drives the C entry point.
+func (c *Context) ExecutorFitOnResidentCluster(minimalFragmentation bool, executors []*resources.Resources, nSets int, setWords []uint64,
+	reqSet []uint32, hostsApp []uint32, nodeZone, zones []uint32, execLabelRank []uint32) ([]string, error) {
+	if len(executors) == 0 {
+		return nil, nil
+	}
+	if nSets > 0 && len(reqSet) != len(executors) {
+		return nil, fmt.Errorf("gangfit: %d executors, %d set numbers", len(executors), len(reqSet))
+	}
+	if zones != nil && len(zones) != len(executors) {
+		return nil, fmt.Errorf("gangfit: %d executors, %d zones", len(executors), len(zones))
+	}
+	exe := make([]int64, 0, 3*len(executors))
+	for _, r := range executors {
+		v, err := canonical(r)
+		if err != nil {
+			return nil, err
+		}
+		exe = append(exe, v[0], v[1], v[2])
+	}
+	mf := C.int(0)
+	if minimalFragmentation {
+		mf = 1
+	}
+	opt32 := func(v []uint32) *C.uint32_t {
+		if len(v) == 0 {
+			return nil
+		}
+		return (*C.uint32_t)(unsafe.Pointer(&v[0]))
+	}
+	var words *C.uint64_t
+	if nSets > 0 && len(setWords) > 0 {
+		words = (*C.uint64_t)(unsafe.Pointer(&setWords[0]))
+	}
+	var sets *C.uint32_t
+	if nSets > 0 {
+		sets = opt32(reqSet)
+	}
+	out := make([]uint32, len(executors))
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	if rc := C.gf_cluster_executor_fit(c.ctx, mf, C.uint32_t(nSets), words, C.uint32_t(len(executors)), p64(exe), sets, opt32(hostsApp),
+		opt32(nodeZone), opt32(zones), opt32(execLabelRank), p32(out)); rc != C.GF_OK {
+		return nil, c.err(rc)
+	}
+	names := make([]string, len(out))
+	for i, n := range out {
+		if n != ^uint32(0) && int(n) < len(c.names) {
+			names[i] = c.names[n]
+		}
+	}
+	return names, nil
+}
+
 // WorkerStop makes the resident worker leave the device now (it leaves by itself when idle).
 func (c *Context) WorkerStop() error {
 	c.mu.Lock()

@@ -313,6 +313,14 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->h_scan_out.release();
     ctx->d_scan_sets.release();
     ctx->d_scan_app_set.release();
+    ctx->d_cl_x32.release();
+    ctx->d_xs_req.release();
+    ctx->d_xs_sets.release();
+    ctx->d_xs_hosts.release();
+    ctx->d_xs_cols.release();
+    ctx->d_xs_out.release();
+    ctx->h_xs_req.release();
+    ctx->h_xs_out.release();
     ctx->d_delta_i64.release();
     ctx->d_delta_u32.release();
     ctx->d_bi64.release();

@@ -1,7 +1,9 @@
 // gangfit_api_scan.cpp — gf_cluster_fit_feasible and gf_cluster_fit_feasible_sets: the UnschedulablePodMarker's empty-cluster
 // question answered from the resident cluster columns (gangfit_scan.inc), next to the installed snapshot instead of in its place.
 // Nothing here installs: no InstallGuard, no epoch, no generation, no chain cache, no worker_quiesce — the calls only read what
-// gf_cluster_set uploaded and write buffers of their own (gf_ctx::d_scan_*).
+// gf_cluster_set uploaded and write buffers of their own (gf_ctx::d_scan_*).  gf_cluster_executor_fit: the executor Filter answered
+// the same way (gangfit_exec_scan.inc) from the columns, the resident overhead rows, the usage sums and the per-node entry counts;
+// its buffers are gf_ctx::d_xs_*.
 #include "gangfit_ctx.h"
 
 using namespace gfapi;
@@ -144,6 +146,107 @@ int gf_cluster_fit_feasible_sets(gf_ctx* ctx, gf_algo algo, const int64_t* over_
                                                   ctx->d_cl_u32.ptr, ctx->d_scan_sets.ptr, ctx->d_scan_app_set.ptr, n_apps,
                                                   ctx->d_scan_apps.ptr, ctx->d_scan_out.ptr, st));
     return scan_answers(ctx, n_apps, has_capacity, st);
+}
+
+// The executor Filter next to the installed snapshot: reads the resident columns, the usage sums and the entry counts; writes the
+// d_xs_* buffers only.
+int gf_cluster_executor_fit(gf_ctx* ctx, int minimal_fragmentation, uint32_t n_sets, const uint64_t* set_words, uint32_t n_req,
+                            const int64_t* exe, const uint32_t* req_set, const uint32_t* hosts_app, const uint32_t* node_zone,
+                            const uint32_t* req_zone, const uint32_t* exec_label_rank, uint32_t* node_out) {
+    GF_DELEGATE(ctx, gf_cluster_executor_fit(ctx, minimal_fragmentation, n_sets, set_words, n_req, exe, req_set, hosts_app, node_zone,
+                                             req_zone, exec_label_rank, node_out));
+    if (!ctx) return GF_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    GF_NOT_ON_A_VIEW(ctx);
+    if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede gf_cluster_executor_fit");
+    if (!ctx->usage_ok) return fail(ctx, GF_ERR_STATE, "the resident usage is unknown (a failed gf_usage_apply): gf_usage_reset must rebuild it");
+    if (!ctx->cl_over_ok)
+        return fail(ctx, GF_ERR_STATE, "the resident overhead is unknown (a failed gf_overhead_update): gf_cluster_set must replace it");
+    if (ctx->cl_zones > 64u)
+        return fail(ctx, GF_ERR_UNSUPPORTED, "the resident executor Filter ranks at most 64 zones (%u)", ctx->cl_zones);
+    if (n_req == 0) return GF_OK;
+    if (!exe || !node_out) return fail(ctx, GF_ERR_INVALID, "exe/node_out must not be NULL");
+    if (n_req >= 0x80000000u) return fail(ctx, GF_ERR_INVALID, "n_req = %u", n_req);
+    for (size_t i = 0; i < 3 * (size_t)n_req; ++i)
+        if (exe[i] < 0 || exe[i] >= GF_MAX_ABS_QUANTITY) return fail(ctx, GF_ERR_INVALID, "executor request outside [0, 2^62)");
+    const uint32_t n = ctx->cl_n;
+    const size_t N = n, W = (N + 63) / 64;
+    if (n_sets > 0) {
+        if (!req_set) return fail(ctx, GF_ERR_INVALID, "req_set must not be NULL with %u sets", n_sets);
+        if (!set_words && W > 0) return fail(ctx, GF_ERR_INVALID, "set_words must not be NULL with %u sets", n_sets);
+        for (uint32_t q = 0; q < n_req; ++q)
+            if (req_set[q] >= n_sets) return fail(ctx, GF_ERR_INVALID, "req_set[%u] = %u names no set (%u sets)", q, req_set[q], n_sets);
+        if ((n & 63u) != 0u) {  // the kernel trusts a bit to name a node
+            const uint64_t beyond = ~UINT64_C(0) << (n & 63u);
+            for (uint32_t s = 0; s < n_sets; ++s)
+                if (set_words[(size_t)s * W + (W - 1)] & beyond) return fail(ctx, GF_ERR_INVALID, "set %u has a bit at or beyond node %u", s, n);
+        }
+    }
+    if (node_zone != nullptr && req_zone == nullptr) return fail(ctx, GF_ERR_INVALID, "node_zone comes with req_zone");
+    if (node_zone)
+        for (uint32_t i = 0; i < n; ++i)
+            if (node_zone[i] == GF_ANY_ZONE) return fail(ctx, GF_ERR_INVALID, "node_zone[%u] is GF_ANY_ZONE: a node has a zone", i);
+    const bool with_sets = n_sets > 0 && W > 0;
+    const uint32_t hosts_stride = (n + 31) / 32;
+    const bool with_hosts = minimal_fragmentation && hosts_app && hosts_stride > 0;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    // ---- the requests: exe | set row | zone, one copy from pinned staging (the previous call has left these buffers: it blocked)
+    const size_t R = n_req, req_words = 3 * R + (R + 1) / 2 * 2;
+    GF_HIP(ctx, ctx->h_xs_req.reserve(req_words));
+    GF_HIP(ctx, ctx->d_xs_req.reserve(req_words));
+    GF_HIP(ctx, ctx->d_xs_out.reserve(R));
+    GF_HIP(ctx, ctx->h_xs_out.reserve(R));
+    std::memcpy(ctx->h_xs_req.ptr, exe, 3 * R * sizeof(int64_t));
+    uint32_t* const h_set = reinterpret_cast<uint32_t*>(ctx->h_xs_req.ptr + 3 * R);
+    uint32_t* const h_zone = h_set + (R + 1) / 2 * 2;
+    for (size_t q = 0; q < R; ++q) {
+        h_set[q] = with_sets ? req_set[q] : 0u;
+        h_zone[q] = req_zone ? req_zone[q] : GF_ANY_ZONE;
+    }
+    GF_HIP(ctx, hipMemcpyAsync(ctx->d_xs_req.ptr, ctx->h_xs_req.ptr, req_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    const uint32_t* const d_set = reinterpret_cast<const uint32_t*>(ctx->d_xs_req.ptr + 3 * R);
+    const uint32_t* const d_zone = d_set + (R + 1) / 2 * 2;
+    if (with_sets) {
+        const size_t n_words = (size_t)n_sets * W;
+        GF_HIP(ctx, ctx->d_xs_sets.reserve(n_words));
+        GF_HIP(ctx, hipMemcpyAsync(ctx->d_xs_sets.ptr, set_words, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    }
+    if (with_hosts) {
+        GF_HIP(ctx, ctx->d_xs_hosts.reserve(R * hosts_stride));
+        GF_HIP(ctx, hipMemcpyAsync(ctx->d_xs_hosts.ptr, hosts_app, R * hosts_stride * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    if ((node_zone || exec_label_rank) && N) {  // the only O(n_nodes) arrays this call ever moves
+        GF_HIP(ctx, ctx->d_xs_cols.reserve(2 * N));
+        if (node_zone) GF_HIP(ctx, hipMemcpyAsync(ctx->d_xs_cols.ptr, node_zone, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (exec_label_rank)
+            GF_HIP(ctx, hipMemcpyAsync(ctx->d_xs_cols.ptr + N, exec_label_rank, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    gangfit::ClusterExecutorFit f{};
+    f.n_nodes = n;
+    f.n_zones = ctx->cl_zones;
+    f.d_alloc = ctx->d_cl_i64.ptr;
+    f.d_over = ctx->cl_over ? ctx->d_cl_i64.ptr + 3 * N : nullptr;
+    f.d_usage = ctx->d_cl_usage.ptr;
+    f.d_res_count = ctx->d_cl_x32.ptr;
+    f.d_zone = ctx->d_cl_u32.ptr;
+    f.d_name_rank = ctx->d_cl_u32.ptr + N;
+    f.d_flags = ctx->d_cl_x32.ptr + N;
+    f.d_node_zone = node_zone && N ? ctx->d_xs_cols.ptr : nullptr;
+    f.d_label_rank = exec_label_rank && N ? ctx->d_xs_cols.ptr + N : nullptr;
+    f.d_set_words = with_sets ? ctx->d_xs_sets.ptr : nullptr;
+    f.d_req_set = with_sets ? d_set : nullptr;
+    f.d_req_zone = req_zone ? d_zone : nullptr;
+    f.d_hosts = with_hosts ? ctx->d_xs_hosts.ptr : nullptr;
+    f.hosts_stride = hosts_stride;
+    f.n_req = n_req;
+    f.d_exe = reinterpret_cast<const int64_t*>(ctx->d_xs_req.ptr);
+    f.d_out = ctx->d_xs_out.ptr;
+    GF_HIP(ctx, gangfit::launch_cluster_executor_fit(minimal_fragmentation != 0, f, st));
+    GF_HIP(ctx, hipMemcpyAsync(ctx->h_xs_out.ptr, ctx->d_xs_out.ptr, R * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays are free again, the answers have arrived
+    std::memcpy(node_out, ctx->h_xs_out.ptr, R * sizeof(uint32_t));
+    return GF_OK;
 }
 
 }  // extern "C"

@@ -308,6 +308,9 @@ int gf_cluster_set(gf_ctx* ctx, uint32_t n_nodes, const int64_t* alloc_cpu_milli
     }
     GF_HIP(ctx, ctx->d_cl_usage.reserve(3 * N + 1));
     GF_HIP(ctx, hipMemsetAsync(ctx->d_cl_usage.ptr, 0, (3 * N + 1) * sizeof(int64_t), st));  // a new node set: no usage yet
+    GF_HIP(ctx, ctx->d_cl_x32.reserve(2 * N + 1));
+    if (N) GF_HIP(ctx, hipMemsetAsync(ctx->d_cl_x32.ptr, 0, N * sizeof(uint32_t), st));  // ... and no reservation entry
+    if (N) GF_HIP(ctx, hipMemcpyAsync(ctx->d_cl_x32.ptr + N, node_flags, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     for (int j = 0; j < 3; ++j) ctx->usage_total[j] = 0;
     GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays are free again
     ctx->cl_alloc.resize(3 * N);
@@ -355,6 +358,7 @@ int gf_usage_reset(gf_ctx* ctx) {
     if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede gf_usage_reset");
     GF_HIP(ctx, hipSetDevice(ctx->device));
     GF_HIP(ctx, hipMemsetAsync(ctx->d_cl_usage.ptr, 0, (3 * (size_t)ctx->cl_n + 1) * sizeof(int64_t), ctx->stream));
+    if (ctx->cl_n) GF_HIP(ctx, hipMemsetAsync(ctx->d_cl_x32.ptr, 0, (size_t)ctx->cl_n * sizeof(uint32_t), ctx->stream));  // the entry counts
     for (int j = 0; j < 3; ++j) ctx->usage_total[j] = 0;
     ctx->usage_ok = true;
     ++ctx->usage_gen;
@@ -406,7 +410,7 @@ int gf_usage_apply(gf_ctx* ctx, uint32_t n_entries, const uint32_t* res_node, co
     ++ctx->usage_gen;
     ctx->usage_ok = false;  // until the update is known to have been applied in full
     GF_HIP(ctx, gangfit::launch_usage_apply(n_entries, ctx->cl_n, ctx->d_delta_u32.ptr, ctx->d_delta_i64.ptr, sign,
-                                            ctx->d_cl_usage.ptr, ctx->d_flag32.ptr, st));
+                                            ctx->d_cl_usage.ptr, ctx->d_cl_x32.ptr, ctx->d_flag32.ptr, st));
     if (sign < 0)
         GF_HIP(ctx, hipMemcpyAsync(ctx->h_failed.ptr, ctx->d_flag32.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays are free again
@@ -414,7 +418,7 @@ int gf_usage_apply(gf_ctx* ctx, uint32_t n_entries, const uint32_t* res_node, co
         // an entry was removed from a node that never carried it: the node's sum went negative (the snapshot would report
         // available > allocatable).  Put the update back and refuse it.
         GF_HIP(ctx, gangfit::launch_usage_apply(n_entries, ctx->cl_n, ctx->d_delta_u32.ptr, ctx->d_delta_i64.ptr, +1,
-                                                ctx->d_cl_usage.ptr, nullptr, st));
+                                                ctx->d_cl_usage.ptr, ctx->d_cl_x32.ptr, nullptr, st));
         GF_HIP(ctx, gf_wait_stream(st));
         ctx->usage_ok = true;
         return fail(ctx, GF_ERR_INVALID, "an entry was removed from a node that never carried it (a node's usage went negative)");

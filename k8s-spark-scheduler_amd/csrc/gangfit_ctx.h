@@ -6,7 +6,8 @@
 //   gangfit_api_fit.cpp       the launches of every packer, the incremental chain cache, gf_fit_batch*, single executors,
 //                             findNodes, efficiencies
 //   gangfit_api_worker.cpp    the resident worker of the independent batch (gf_worker_*)
-//   gangfit_api_scan.cpp      gf_cluster_fit_feasible[_sets]: the empty-cluster capacity scan on the resident cluster columns
+//   gangfit_api_scan.cpp      gf_cluster_fit_feasible[_sets]: the empty-cluster capacity scan on the resident cluster columns;
+//                             gf_cluster_executor_fit: the executor Filter on the same columns plus the resident usage
 //   gangfit_api_group.cpp     node-range sharding: the gf_shard_* steps and the multi-device context (peer stores or RCCL)
 #pragma once
 #include <dlfcn.h>
@@ -343,6 +344,9 @@ struct gf_ctx {
     // gf_cluster_set: the static columns of gf_snapshot_build, resident
     DeviceBuf<int64_t> d_cl_i64;   // allocatable (3n) | overhead (3n)
     DeviceBuf<int64_t> d_cl_usage;  // resident UsageForNodes sums (3n), maintained by gf_usage_apply
+    // reservation entries per node (n, next to the sums: gf_usage_apply adds sign per entry) | the flags of gf_cluster_set (n; the
+    // flags column of d_cl_u32 may hold a request's candidate flags): what gf_cluster_executor_fit reads beside the columns above
+    DeviceBuf<uint32_t> d_cl_x32;
     DeviceBuf<int64_t> d_delta_i64; // one gf_usage_apply call's entries / one gf_overhead_update call's rows
     DeviceBuf<uint32_t> d_delta_u32;
     __int128 usage_total[3] = {0, 0, 0};  // sum of everything applied: bounds every node's sum
@@ -371,8 +375,15 @@ struct gf_ctx {
     DeviceBuf<uint64_t> d_scan_sets;      // gf_cluster_fit_feasible_sets: the node sets, n_sets rows of ceil(n / 64) words
     DeviceBuf<uint32_t> d_scan_app_set;   // ... and every application's row
 
+    // gf_cluster_executor_fit (gangfit_api_scan.cpp): the requests (exe 3r | set row and zone r each, staged in pinned memory and
+    // sent as one copy), the set rows, the hosting bits, the optional node_zone | exec_label_rank columns and the answers.  Its own.
+    DeviceBuf<uint64_t> d_xs_req, d_xs_sets;
+    DeviceBuf<uint32_t> d_xs_hosts, d_xs_cols, d_xs_out;
+    PinnedBuf<uint64_t> h_xs_req;
+    PinnedBuf<uint32_t> h_xs_out;
+
     // gf_snapshot_build
-    DeviceBuf<int64_t> d_bi64;   // alloc | overhead | usage | avail | sched (3n each) | keys_a | keys_b (n each) | res_req (3r) | zone_sum
+    DeviceBuf<int64_t> d_bi64;  // alloc | overhead | usage | avail | sched (3n each) | keys_a | keys_b (n each) | res_req (3r) | zone_sum
     DeviceBuf<uint32_t> d_bu32;  // zone | name_rank | perm_a | perm_b (n each) | res_node (r) | zone_order | zone_rank | ... (BuildScratch)
     PinnedBuf<int64_t> h_bcols;  // avail | sched (3n each)
     PinnedBuf<uint32_t> h_border;

@@ -532,9 +532,11 @@ struct LabelMerge {
 hipError_t launch_label_merge_check(const LabelMerge& m, hipStream_t stream);
 // usage[node] += sign * entry for n_entries reservation entries (columns cpu | memory | gpu of d_req); entries on nodes
 // >= n_nodes are ignored.
-// d_negative (nullable): after a removal (sign < 0) bit 0 is set when a touched node's sum went below zero.
+// d_count (nullable): n_nodes entry counts, count[node] += sign per entry — "carries a reservation" is a map-key question the
+// sums cannot answer (an entry of all zeros still makes the node a key).
+// d_negative (nullable): after a removal (sign < 0) bit 0 is set when a touched node's sum or count went below zero.
 hipError_t launch_usage_apply(uint32_t n_entries, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_req, int sign,
-                              int64_t* d_usage, uint32_t* d_negative, hipStream_t stream);
+                              int64_t* d_usage, uint32_t* d_count, uint32_t* d_negative, hipStream_t stream);
 // overhead[d_node[i]] = row i (columns cpu | memory | gpu of d_rows, n_rows each) for n_rows rows of the resident overhead columns
 // (d_overhead: 3 * n_nodes).  Every d_node[i] < n_nodes and no node twice (the caller checks): plain stores, stream-ordered
 // before any later build.
@@ -554,6 +556,31 @@ hipError_t launch_cluster_scan(bool zoned, uint32_t n_nodes, const int64_t* d_al
 hipError_t launch_cluster_scan_sets(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
                                     const uint64_t* d_set_words, const uint32_t* d_app_set, uint32_t n_apps, const gf_app* d_apps,
                                     uint8_t* d_out, hipStream_t stream);
+// The executor Filter on the resident cluster (gangfit_exec_scan.inc; gf_cluster_executor_fit): d_out[q] = the node the
+// installing route (gf_snapshot_build + gf_executor_fit) returns for request q when it is given only the nodes of row d_req_set[q]
+// that pass the zone test — as an order-free minimum over the columns in node-index order.  One workgroup of four wavefronts per
+// request; reads nothing of the installed snapshot.
+struct ClusterExecutorFit {
+    uint32_t n_nodes, n_zones;       // n_zones <= 64
+    const int64_t* d_alloc;          // 3 * n_nodes
+    const int64_t* d_over;           // 3 * n_nodes, or nullptr: no overhead
+    const int64_t* d_usage;          // 3 * n_nodes resident usage sums
+    const uint32_t* d_res_count;     // n_nodes reservation entries per node
+    const uint32_t* d_zone;          // n_nodes cluster zone ids
+    const uint32_t* d_name_rank;     // n_nodes
+    const uint32_t* d_flags;         // n_nodes default GF_NODE_* flags
+    const uint32_t* d_node_zone;     // n_nodes ids of the zone test, or nullptr: d_zone
+    const uint32_t* d_label_rank;    // n_nodes, or nullptr
+    const uint64_t* d_set_words;     // rows of ceil(n_nodes / 64) words, or nullptr: every node
+    const uint32_t* d_req_set;       // n_req rows (with d_set_words)
+    const uint32_t* d_req_zone;      // n_req, or nullptr: GF_ANY_ZONE
+    const uint32_t* d_hosts;         // n_req * hosts_stride, or nullptr
+    uint32_t hosts_stride;
+    uint32_t n_req;
+    const int64_t* d_exe;            // n_req * 3
+    uint32_t* d_out;                 // n_req
+};
+hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ClusterExecutorFit& f, hipStream_t stream);
 // The slot tables of the merged layout built from the device-resident snapshot columns (what gf_orders_set builds on the
 // host): every node gets the slot of its position in the priority order.
 struct SnapshotFinalize {

@@ -1665,6 +1665,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
 #include "gangfit_executor.inc"
 #include "gangfit_findnodes.inc"
 #include "gangfit_scan.inc"
+#include "gangfit_exec_scan.inc"
 
 // ------------------------------------------------------------------------------------------------ self-test
 
@@ -1679,7 +1680,7 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t& s) {
 // Each lane checks (a) the DPP scan against a serial sum through LDS, (b) cap_dim and cap_dim_full against a plain 64-bit divide
 // on adversarial operands (values adjacent to exact multiples, huge/small divisors, clamp boundaries), (c) the narrow domain's
 // division by multiplication, (d) the resident worker's scaled arithmetic and (e) the DPP reductions of gangfit_wave.inc —
-// wave_max_i64, wave_max_i32, row_min_u32, row_max_f64, wave_sum_f64 — against serial loops over the lane values in LDS.
+// wave_max_i64, wave_min_any_i64, wave_sum_i64, wave_max_i32, row_min_u32, row_max_f64, wave_sum_f64 — against serial loops over the lane values in LDS.
 __global__ __launch_bounds__(kWave) void selftest_kernel(uint64_t seed, uint32_t n_cases, uint32_t* mismatch) {
     __shared__ int32_t vals[kWave];
     __shared__ int64_t e_i64[kWave];
@@ -1715,15 +1716,20 @@ __global__ __launch_bounds__(kWave) void selftest_kernel(uint64_t seed, uint32_t
             e_max[lane] = vmax;
             e_sum[lane] = vsum;
             __syncthreads();
-            int64_t want64 = e_i64[0];
+            int64_t want64 = e_i64[0], want_min64 = e_i64[0];
+            uint64_t want_sum64 = 0;
             int32_t want32 = e_i32[0];
             double want_sum = 0.0;
             for (int i = 0; i < kWave; ++i) {
                 want64 = e_i64[i] > want64 ? e_i64[i] : want64;
+                want_min64 = e_i64[i] < want_min64 ? e_i64[i] : want_min64;
+                want_sum64 += (uint64_t)e_i64[i];
                 want32 = e_i32[i] > want32 ? e_i32[i] : want32;
                 want_sum += e_sum[i];
             }
             if (wave_max_i64(v64) != want64) ++bad;
+            if (wave_min_any_i64(v64) != want_min64) ++bad;
+            if ((uint64_t)wave_sum_i64(v64) != want_sum64) ++bad;
             if (wave_max_i32(v32) != want32) ++bad;
             if (__double_as_longlong(wave_sum_f64(vsum)) != __double_as_longlong(want_sum)) ++bad;
             const uint32_t got_min = row_min_u32(vu);
@@ -1968,6 +1974,22 @@ hipError_t launch_cluster_scan_sets(bool zoned, uint32_t n_nodes, const int64_t*
     const ScanSetsArgs args{d_alloc, d_over, d_zone, d_set_words, d_app_set, n_nodes, n_words, n_apps, d_apps, d_out};
     return with_value<true, false>(zoned, [&](auto Z) {
         hipLaunchKernelGGL(cluster_scan_sets_kernel<Z>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, args);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ClusterExecutorFit& f, hipStream_t stream) {
+    if (f.n_req == 0) return hipSuccess;
+    if (f.d_exe == nullptr || f.d_out == nullptr || (f.d_set_words != nullptr && f.d_req_set == nullptr) || f.n_zones > (uint32_t)kExecZones ||
+        (f.n_nodes > 0 && (f.d_alloc == nullptr || f.d_usage == nullptr || f.d_res_count == nullptr || f.d_zone == nullptr ||
+                           f.d_name_rank == nullptr || f.d_flags == nullptr)))
+        return hipErrorInvalidValue;
+    const uint32_t n_words = (uint32_t)(((uint64_t)f.n_nodes + kWave - 1) / kWave);
+    const ExecScanArgs args{f.d_alloc,     f.d_over,      f.d_usage,    f.d_res_count, f.d_zone,  f.d_name_rank, f.d_flags,
+                            f.d_node_zone, f.d_label_rank, f.d_set_words, f.d_req_set,  f.d_req_zone, f.d_hosts,  f.d_exe,
+                            f.n_nodes,     n_words,       f.n_zones,    f.n_req,       f.hosts_stride, f.d_out};
+    return with_value<true, false>(minimal_fragmentation, [&](auto MF) {
+        hipLaunchKernelGGL(cluster_executor_fit_kernel<MF>, dim3(f.n_req), dim3(kWave * kWavesPerBlock), 0, stream, args);
         return hipGetLastError();
     });
 }

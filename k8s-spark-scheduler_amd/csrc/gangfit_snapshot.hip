@@ -20,7 +20,8 @@ namespace {
 // sign = +1 / -1: two's-complement addition, so removing an entry is adding its negation
 __global__ void usage_scatter_kernel(uint32_t n_res, uint32_t n_nodes, const uint32_t* __restrict__ res_node,
                                      const int64_t* __restrict__ r0, const int64_t* __restrict__ r1,
-                                     const int64_t* __restrict__ r2, unsigned long long* __restrict__ usage, int sign = 1) {
+                                     const int64_t* __restrict__ r2, unsigned long long* __restrict__ usage, int sign = 1,
+                                     uint32_t* __restrict__ count = nullptr) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_res) return;
     const uint32_t n = res_node[i];
@@ -28,20 +29,23 @@ __global__ void usage_scatter_kernel(uint32_t n_res, uint32_t n_nodes, const uin
     atomicAdd(&usage[n], (unsigned long long)(r0[i] * sign));
     atomicAdd(&usage[(size_t)n_nodes + n], (unsigned long long)(r1[i] * sign));
     atomicAdd(&usage[2 * (size_t)n_nodes + n], (unsigned long long)(r2[i] * sign));
+    if (count != nullptr) atomicAdd(&count[n], (uint32_t)sign);  // the resident entry count: one more / one fewer entry names n
 }
 
 // available = allocatable - (usage + overhead), schedulable = allocatable - overhead (resources.go:76, 89-90);
 // zone sums of the available memory / cpu feed the AZ order (nodesorting.go:124-134).
 constexpr uint32_t kZoneLdsMax = 512;  // zones whose sums are first combined in LDS (one global atomic per block and zone)
 
-// After a removal: a node of the update whose sum went negative had an entry removed that was never added there.
+// After a removal: a node of the update whose sum (or entry count) went negative had an entry removed that was never added there.
 __global__ void usage_negative_kernel(uint32_t n_res, uint32_t n_nodes, const uint32_t* __restrict__ res_node,
-                                      const int64_t* __restrict__ usage, uint32_t* __restrict__ negative) {
+                                      const int64_t* __restrict__ usage, const uint32_t* __restrict__ count,
+                                      uint32_t* __restrict__ negative) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_res) return;
     const uint32_t n = res_node[i];
     if (n >= n_nodes) return;
     if (usage[n] < 0 || usage[(size_t)n_nodes + n] < 0 || usage[2 * (size_t)n_nodes + n] < 0) atomicOr(negative, 1u);
+    if (count != nullptr && (int32_t)count[n] < 0) atomicOr(negative, 1u);
 }
 
 // gf_overhead_update: row i of the update REPLACES the overhead of node row_node[i] in the resident SoA columns (cpu | memory | gpu,
@@ -987,15 +991,15 @@ hipError_t launch_empty(uint32_t* sink, hipStream_t stream) {
 }
 
 hipError_t launch_usage_apply(uint32_t n_entries, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_req, int sign,
-                              int64_t* d_usage, uint32_t* d_negative, hipStream_t stream) {
+                              int64_t* d_usage, uint32_t* d_count, uint32_t* d_negative, hipStream_t stream) {
     if (n_entries == 0 || n_nodes == 0) return hipSuccess;
     hipLaunchKernelGGL(usage_scatter_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, stream, n_entries, n_nodes, d_node,
                        d_req, d_req + n_entries, d_req + 2 * (size_t)n_entries, reinterpret_cast<unsigned long long*>(d_usage),
-                       sign < 0 ? -1 : 1);
+                       sign < 0 ? -1 : 1, d_count);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || sign > 0 || d_negative == nullptr) return e;
     hipLaunchKernelGGL(usage_negative_kernel, dim3((n_entries + 255) / 256), dim3(256), 0, stream, n_entries, n_nodes, d_node,
-                       (const int64_t*)d_usage, d_negative);
+                       (const int64_t*)d_usage, (const uint32_t*)d_count, d_negative);
     return hipGetLastError();
 }
 

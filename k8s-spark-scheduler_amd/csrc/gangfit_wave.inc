@@ -116,6 +116,10 @@ struct OpSumF64 {
     static __device__ __forceinline__ double old(double) { return 0.0; }
     static __device__ __forceinline__ double combine(double t, double v) { return v + t; }
 };
+struct OpSumI64 {  // wrapping: two's-complement addition, whatever the order
+    static __device__ __forceinline__ int64_t old(int64_t) { return 0; }
+    static __device__ __forceinline__ int64_t combine(int64_t t, int64_t v) { return (int64_t)((uint64_t)v + (uint64_t)t); }
+};
 struct OpMinU32 {
     static __device__ __forceinline__ uint32_t old(uint32_t) { return 0xFFFFFFFFu; }
     static __device__ __forceinline__ uint32_t combine(uint32_t t, uint32_t v) { return t < v ? t : v; }
@@ -146,6 +150,9 @@ __device__ __forceinline__ T wave_reduce(T v) {
 __device__ __forceinline__ int64_t wave_max_i64(int64_t v) { return read_lane(wave_reduce<OpMax>(v), kWave - 1); }
 __device__ __forceinline__ int32_t wave_max_i32(int32_t v) { return read_lane(wave_reduce<OpMax>(v), kWave - 1); }
 __device__ __forceinline__ double wave_sum_f64(double v) { return bcast_f64(wave_reduce<OpSumF64>(v), kWave - 1); }
+__device__ __forceinline__ int64_t wave_sum_i64(int64_t v) { return read_lane(wave_reduce<OpSumI64>(v), kWave - 1); }
+// The minimum as the complement of a maximum: no value is out of range (negation would lose INT64_MIN).
+__device__ __forceinline__ int64_t wave_min_any_i64(int64_t v) { return ~read_lane(wave_reduce<OpMax>(~v), kWave - 1); }
 // Per row of 16 lanes, in the row's lane 15.
 __device__ __forceinline__ double row_max_f64(double v) { return row_reduce<OpMaxF64>(v); }
 __device__ __forceinline__ uint32_t row_min_u32(uint32_t v) { return row_reduce<OpMinU32>(v); }

@@ -17,6 +17,7 @@ HOST_OVERHEAD_TEST_PATH = os.path.join(_PKG_ROOT, "host_overhead_test")  # ... o
 HOST_CLUSTER_SCAN_TEST_PATH = os.path.join(_PKG_ROOT, "host_cluster_scan_test")  # ... of the resident capacity scan (host_cluster_scan_test.cpp)
 HOST_CLUSTER_SCAN_SETS_TEST_PATH = os.path.join(_PKG_ROOT, "host_cluster_scan_sets_test")  # ... of the all-groups scan (host_cluster_scan_sets_test.cpp)
 HOST_SNAPSHOT_LABELS_TEST_PATH = os.path.join(_PKG_ROOT, "host_snapshot_labels_test")  # ... of builds with a prioritized label (host_snapshot_labels_test.cpp)
+HOST_EXECUTOR_RESIDENT_TEST_PATH = os.path.join(_PKG_ROOT, "host_executor_resident_test")  # ... of the resident executor Filter (host_executor_resident_test.cpp)
 INCLUDE = os.path.join(_REPO_ROOT, "include")
 
 _SOURCES = ["gangfit_kernels.hip", "gangfit_snapshot.hip", "gangfit_api.cpp", "gangfit_api_snapshot.cpp", "gangfit_api_fit.cpp",
@@ -99,6 +100,11 @@ def build_host(force: bool = False) -> str:
     if os.path.exists(labels_src) and (force or _stale(HOST_SNAPSHOT_LABELS_TEST_PATH, [labels_src, HOST_LIB_PATH] + hdrs)):
         cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, labels_src, "-L", _PKG_ROOT,
                "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_SNAPSHOT_LABELS_TEST_PATH]
+        subprocess.check_call(cmd)
+    exec_src = os.path.join(host_dir, "tests", "host_executor_resident_test.cpp")
+    if os.path.exists(exec_src) and (force or _stale(HOST_EXECUTOR_RESIDENT_TEST_PATH, [exec_src, HOST_LIB_PATH] + hdrs)):
+        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, exec_src, "-L", _PKG_ROOT,
+               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_EXECUTOR_RESIDENT_TEST_PATH]
         subprocess.check_call(cmd)
     bench_src = os.path.join(host_dir, "tests", "host_bench.cpp")
     if os.path.exists(bench_src) and (force or _stale(HOST_BENCH_PATH, [bench_src, HOST_LIB_PATH] + hdrs)):

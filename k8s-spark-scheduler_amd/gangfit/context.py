@@ -394,6 +394,38 @@ class Context:
                                               N.ptr(bits), N.ptr(out)))
         return out
 
+    def cluster_executor_fit(self, exe, minimal_fragmentation: bool = False, sets=None, req_set=None, hosts=None,
+                             node_zone=None, req_zone=None, exec_label_rank=None) -> np.ndarray:
+        """gf_cluster_executor_fit: one node index of the RESIDENT cluster (GF_NO_NODE = no capacity) per executor request —
+        rescheduleExecutor's answer on the nodes of row req_set[q] of `sets` ((n_sets, n_nodes) truth values; None = every
+        node) that lie in zone req_zone[q] (node_zone: (n_nodes,) ids, None = the cluster's; GF_ANY_ZONE = anywhere), from the
+        columns of set_cluster / overhead_update / usage_apply.  hosts: (n_req, n_nodes) booleans.  Installs nothing."""
+        exe = np.ascontiguousarray(exe, dtype=np.int64).reshape(-1, 3)
+        n = self._cluster_n
+        words, rs, n_sets = None, None, 0
+        if sets is not None:
+            words = pack_node_sets(sets, n)
+            n_sets = len(words)
+            rs = np.ascontiguousarray(req_set, dtype=np.uint32).reshape(-1)
+            assert len(rs) == len(exe), "one set per request"
+        bits = None
+        if hosts is not None:
+            h = np.asarray(hosts, dtype=bool).reshape(len(exe), n)
+            w32 = (n + 31) // 32
+            pad = np.zeros((len(exe), w32 * 32), dtype=bool)
+            pad[:, :n] = h
+            bits = np.ascontiguousarray(np.packbits(pad.reshape(len(exe), w32, 32), axis=2, bitorder="little").view("<u4").reshape(len(exe), w32))
+        nz = None if node_zone is None else np.ascontiguousarray(node_zone, dtype=np.uint32).reshape(-1)
+        qz = None if req_zone is None else np.ascontiguousarray(req_zone, dtype=np.uint32).reshape(-1)
+        el = None if exec_label_rank is None else np.ascontiguousarray(exec_label_rank, dtype=np.uint32).reshape(-1)
+        assert nz is None or len(nz) == n
+        assert qz is None or len(qz) == len(exe)
+        assert el is None or len(el) == n
+        out = np.zeros(len(exe), dtype=np.uint32)
+        self._check(self._lib.gf_cluster_executor_fit(self._h, int(minimal_fragmentation), n_sets, N.ptr(words), len(exe), N.ptr(exe),
+                                                      N.ptr(rs), N.ptr(bits), N.ptr(nz), N.ptr(qz), N.ptr(el), N.ptr(out)))
+        return out
+
     def find_nodes(self, exe, k, chained: bool = True, want_adds: bool = True):
         """findNodes (failover.go:412-436) for n_req requests.  Returns (placed, last_node, exec_off, exec_nodes, adds):
         placed / last_node per request, the concatenated partial placements, and the `reserved` map in units of exe."""

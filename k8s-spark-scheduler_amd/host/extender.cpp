@@ -676,6 +676,84 @@ void overheadRowDiff(const std::vector<int64_t> want[3], const std::vector<int64
     }
 }
 
+// What selectDriverNodeFlat and rescheduleExecutorFlat keep on the device, brought up to this request: the node-side columns
+// (gf_cluster_set), the overhead rows that differ from what is resident (gf_overhead_update) and, with `usage`, the usage sums of
+// that entry list (gf_usage_reset + gf_usage_apply when the list's version changed).  Called under flat_mu_ and the context's
+// sequence lock.  gen: the context's generations afterwards.
+SparkSchedulerExtender::ResidentSync SparkSchedulerExtender::syncResident(gf_ctx* ctx, const FlatCluster& cluster, const FlatOverhead& fo,
+                                                                          const FlatReservations* usage, uint64_t gen[3], std::string* err) {
+    const uint32_t n = (uint32_t)cluster.names.size();
+    const std::vector<int64_t>* const over = fo.over;
+    bool resident_route = true;
+    const bool with_over = !over[0].empty();
+    const bool known_over = fo.version != 0 && fo.version == resident_over_version_;  // compared before
+    (void)gf_generation(ctx, gen);
+    const bool own_cluster = resident_cluster_ == cluster.version && cluster.version != 0;
+    bool set_cluster = !own_cluster || gen[1] != seen_cluster_gen_;
+    std::vector<uint32_t> rows;  // the rows in which this request's overhead differs from what this extender last sent
+    if (own_cluster && !known_over && (with_over || !resident_over_[0].empty())) {
+        overheadRowDiff(over, resident_over_, n, &rows);
+        if (rows.size() > (size_t)n / 2) set_cluster = true;  // most of the cluster: one upload of the columns is cheaper
+    }
+    if (set_cluster) {
+        ++cluster_set_calls_;
+        if (gf_cluster_set(ctx, n, cluster.alloc[0].data(), cluster.alloc[1].data(), cluster.alloc[2].data(),
+                           with_over ? over[0].data() : nullptr, with_over ? over[1].data() : nullptr,
+                           with_over ? over[2].data() : nullptr, cluster.base_flags.data(), cluster.zone.data(),
+                           (uint32_t)cluster.zone_labels.size(), cluster.name_rank.data()) != GF_OK) {
+            resident_cluster_ = 0;
+            *err = std::string("gf_cluster_set: ") + gf_last_error(ctx);
+            return ResidentSync::failed;
+        }
+        if (!own_cluster || !rows.empty()) built_epoch_ = 0;  // the installed snapshot was built from other columns
+        resident_cluster_ = cluster.version;
+        resident_usage_ = 0;  // gf_cluster_set zeroed the resident usage
+        for (int j = 0; j < 3; ++j) resident_over_[j] = over[j];  // (empty without overhead)
+        resident_over_version_ = fo.version;
+        (void)gf_generation(ctx, gen);
+        seen_cluster_gen_ = gen[1];
+        seen_usage_gen_ = gen[2];
+    } else if (!rows.empty()) {
+        std::vector<int64_t> rcol[3];
+        for (int j = 0; j < 3; ++j) {
+            rcol[j].reserve(rows.size());
+            for (uint32_t r : rows) rcol[j].push_back(with_over ? over[j][r] : 0);
+        }
+        ++overhead_update_calls_;
+        overhead_rows_sent_ += rows.size();
+        built_epoch_ = 0;  // the installed snapshot was built from other rows
+        resident_over_version_ = 0;
+        if (gf_overhead_update(ctx, (uint32_t)rows.size(), rows.data(), rcol[0].data(), rcol[1].data(), rcol[2].data()) != GF_OK) {
+            resident_route = false;  // (a value out of range, a failed device call): the full build below decides
+        } else {
+            if (resident_over_[0].empty())
+                for (int j = 0; j < 3; ++j) resident_over_[j].assign(n, 0);
+            for (size_t i = 0; i < rows.size(); ++i)
+                for (int j = 0; j < 3; ++j) resident_over_[j][rows[i]] = rcol[j][i];
+            resident_over_version_ = fo.version;
+            (void)gf_generation(ctx, gen);
+            seen_cluster_gen_ = gen[1];
+        }
+    } else if (own_cluster) {
+        resident_over_version_ = fo.version;  // compared equal: the next Filter with this version need not look
+    }
+    // a caller that keeps its flattened reservations (version != 0) gets the usage sums kept on the device too: they
+    // are sent when the list changes, and a Filter between two changes moves no reservation at all.  (A host that tracks
+    // its ResourceReservation events would send only the K + 1 entries of the object that changed: gf_usage_apply.)
+    if (resident_route && usage != nullptr && (resident_usage_ != usage->version || gen[2] != seen_usage_gen_)) {
+        resident_usage_ = 0;
+        if (gf_usage_reset(ctx) != GF_OK || gf_usage_apply(ctx, (uint32_t)usage->node.size(), usage->node.data(), usage->req[0].data(),
+                                                           usage->req[1].data(), usage->req[2].data(), +1) != GF_OK) {
+            *err = std::string("gf_usage_apply: ") + gf_last_error(ctx);
+            return ResidentSync::failed;
+        }
+        resident_usage_ = usage->version;
+        (void)gf_generation(ctx, gen);
+        seen_usage_gen_ = gen[2];
+    }
+    return resident_route ? ResidentSync::ok : ResidentSync::no_resident_route;
+}
+
 SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string& instanceGroup, const Pod& driver,
                                                               const std::vector<std::string>& nodeNames,
                                                               const FlatCluster& cluster, const FlatReservations* flat,
@@ -803,73 +881,15 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
     // overhead changes by rows (gf_overhead_update).  A Filter moves the overhead rows that differ from what is resident, its
     // reservation entries and its own candidate flags only.  Another user of the context (the UnschedulablePodMarker shares it)
     // may have replaced the resident cluster or usage in between: the context's generations say so.
-    bool resident_route = true;
+    // (syncResident, above: the cluster columns, the overhead rows that differ and — for a caller that keeps its flattened
+    //  reservations — the usage sums, each sent only when it changed)
+    const bool keep_usage = flat != &local && flat->version != 0;
+    uint64_t gen[3] = {0, 0, 0};
+    std::string sync_err;
+    const ResidentSync synced = syncResident(ctx, cluster, *flatOverhead, keep_usage ? flat : nullptr, gen, &sync_err);
+    if (synced == ResidentSync::failed) return not_served(sync_err);
+    bool resident_route = synced == ResidentSync::ok;
     {
-        const bool with_over = !over[0].empty();
-        const bool known_over = flatOverhead->version != 0 && flatOverhead->version == resident_over_version_;  // compared before
-        uint64_t gen[3] = {0, 0, 0};
-        (void)gf_generation(ctx, gen);
-        const bool own_cluster = resident_cluster_ == cluster.version && cluster.version != 0;
-        bool set_cluster = !own_cluster || gen[1] != seen_cluster_gen_;
-        std::vector<uint32_t> rows;  // the rows in which this request's overhead differs from what this extender last sent
-        if (own_cluster && !known_over && (with_over || !resident_over_[0].empty())) {
-            overheadRowDiff(over, resident_over_, n, &rows);
-            if (rows.size() > (size_t)n / 2) set_cluster = true;  // most of the cluster: one upload of the columns is cheaper
-        }
-        if (set_cluster) {
-            ++cluster_set_calls_;
-            if (gf_cluster_set(ctx, n, cluster.alloc[0].data(), cluster.alloc[1].data(), cluster.alloc[2].data(),
-                               with_over ? over[0].data() : nullptr, with_over ? over[1].data() : nullptr,
-                               with_over ? over[2].data() : nullptr, cluster.base_flags.data(), cluster.zone.data(),
-                               (uint32_t)cluster.zone_labels.size(), cluster.name_rank.data()) != GF_OK) {
-                resident_cluster_ = 0;
-                return not_served(std::string("gf_cluster_set: ") + gf_last_error(ctx));
-            }
-            if (!own_cluster || !rows.empty()) built_epoch_ = 0;  // the installed snapshot was built from other columns
-            resident_cluster_ = cluster.version;
-            resident_usage_ = 0;  // gf_cluster_set zeroed the resident usage
-            for (int j = 0; j < 3; ++j) resident_over_[j] = over[j];  // (empty without overhead)
-            resident_over_version_ = flatOverhead->version;
-            (void)gf_generation(ctx, gen);
-            seen_cluster_gen_ = gen[1];
-            seen_usage_gen_ = gen[2];
-        } else if (!rows.empty()) {
-            std::vector<int64_t> rcol[3];
-            for (int j = 0; j < 3; ++j) {
-                rcol[j].reserve(rows.size());
-                for (uint32_t r : rows) rcol[j].push_back(with_over ? over[j][r] : 0);
-            }
-            ++overhead_update_calls_;
-            overhead_rows_sent_ += rows.size();
-            built_epoch_ = 0;  // the installed snapshot was built from other rows
-            resident_over_version_ = 0;
-            if (gf_overhead_update(ctx, (uint32_t)rows.size(), rows.data(), rcol[0].data(), rcol[1].data(), rcol[2].data()) != GF_OK) {
-                resident_route = false;  // (a value out of range, a failed device call): the full build below decides
-            } else {
-                if (resident_over_[0].empty())
-                    for (int j = 0; j < 3; ++j) resident_over_[j].assign(n, 0);
-                for (size_t i = 0; i < rows.size(); ++i)
-                    for (int j = 0; j < 3; ++j) resident_over_[j][rows[i]] = rcol[j][i];
-                resident_over_version_ = flatOverhead->version;
-                (void)gf_generation(ctx, gen);
-                seen_cluster_gen_ = gen[1];
-            }
-        } else if (own_cluster) {
-            resident_over_version_ = flatOverhead->version;  // compared equal: the next Filter with this version need not look
-        }
-        // a caller that keeps its flattened reservations (flat->version != 0) gets the usage sums kept on the device too: they
-        // are sent when the list changes, and a Filter between two changes moves no reservation at all.  (A host that tracks
-        // its ResourceReservation events would send only the K + 1 entries of the object that changed: gf_usage_apply.)
-        const bool keep_usage = flat != &local && flat->version != 0;
-        if (resident_route && keep_usage && (resident_usage_ != flat->version || gen[2] != seen_usage_gen_)) {
-            resident_usage_ = 0;
-            if (gf_usage_reset(ctx) != GF_OK ||
-                gf_usage_apply(ctx, (uint32_t)rnode.size(), rnode.data(), rreq[0].data(), rreq[1].data(), rreq[2].data(), +1) != GF_OK)
-                return not_served(std::string("gf_usage_apply: ") + gf_last_error(ctx));
-            resident_usage_ = flat->version;
-            (void)gf_generation(ctx, gen);
-            seen_usage_gen_ = gen[2];
-        }
         // nothing changed since this extender's last Filter (no overhead row differed either: a change above cleared built_epoch_):
         // the installed snapshot IS this request's snapshot
         const bool same_snapshot = keep_usage && built_epoch_ != 0 && gen[0] == built_epoch_ && built_cluster_ == cluster.version &&
@@ -930,6 +950,105 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
     out.outcome = outcome::success;
     out.created = newResourceReservation(out.node, executorNodes, driver, resources->DriverResources,
                                          resources->ExecutorResources);
+    return out;
+}
+
+SelectNodeResult SparkSchedulerExtender::rescheduleExecutorFlat(const Pod& executor, const Pod& driver, const std::vector<Pod>& allPods,
+                                                                const std::vector<std::string>& nodeNames,
+                                                                const std::set<std::string>& nodesHostingApp, bool isExtraExecutor,
+                                                                const FlatCluster& cluster, const FlatReservations* flat,
+                                                                const FlatOverhead* flatOverhead, bool* residentRoute) {
+    if (residentRoute) *residentRoute = false;
+    auto installs = [&] { return rescheduleExecutor(executor, driver, allPods, nodeNames, nodesHostingApp, isExtraExecutor); };
+    SelectNodeResult out;
+    std::string err;
+    auto resources = sparkResources(driver, &err);  // first in the reference (:599-602)
+    if (!resources) {
+        out.outcome = outcome::failureInternal;
+        out.error = err;
+        return out;
+    }
+    int64_t exe[3];
+    if (!resources->ExecutorResources.canonical(exe) || exe[0] < 0 || exe[1] < 0 || exe[2] < 0) return installs();
+    if (sorter_.hasExecutorLabelPriority() || cluster.version == 0) return installs();
+    const uint32_t n = (uint32_t)cluster.names.size();
+    // ---- the zone step on the host, as rescheduleExecutor does it (:606-632); its errors are the reference's
+    bool narrow = false;
+    std::string zone;
+    if (binpacker_.IsSingleAz && shouldScheduleDynamicallyAllocatedExecutorsInSameAZ) {
+        auto [z, allPodsInSameAz] = getCommonZoneForExecutorsApplication(executor, allPods, &err);
+        if (!err.empty()) {
+            out.outcome = "";
+            out.error = err;
+            return out;
+        }
+        narrow = allPodsInSameAz;
+        zone = z;
+    }
+    // ---- nodeNames as a bit row over the cluster's node index: getNodes (:448-460) skips names the lister does not know
+    std::unordered_map<std::string, const Node*> listed;
+    listed.reserve(nodes.size());
+    for (const Node& nd : nodes) listed.emplace(nd.Name, &nd);
+    std::vector<uint64_t> row(((size_t)n + 63) / 64, 0);
+    for (const std::string& name : nodeNames) {
+        auto nd = listed.find(name);
+        if (nd == listed.end()) continue;
+        auto at = cluster.index.find(name);
+        if (at == cluster.index.end()) return installs();  // `cluster` does not describe this request's nodes
+        if (narrow) {  // filterNodesToZone (:462-478)
+            auto z = nd->second->labels.find(kLabelTopologyZone);
+            if (z == nd->second->labels.end()) {
+                out.outcome = outcome::failureInternal;
+                out.error = "Could not read zone label from node, unable to make scheduling decisions based on AZ";
+                return out;
+            }
+            if (z->second != zone) continue;
+        }
+        row[at->second >> 6] |= UINT64_C(1) << (at->second & 63u);
+    }
+    const bool minfrag = binpacker_.Name == "single-az-minimal-fragmentation";
+    std::vector<uint32_t> hosts(((size_t)n + 31) / 32, 0u);
+    for (const std::string& name : nodesHostingApp)
+        if (auto it = cluster.index.find(name); it != cluster.index.end()) hosts[it->second >> 5] |= 1u << (it->second & 31);
+    // ---- the per-request columns, as in selectDriverNodeFlat; the device reads the RESIDENT usage, so an entry list always travels
+    // by version (a caller that keeps none gets this request's own, with a version of its own)
+    FlatReservations local;
+    if (flat == nullptr || flat->version == 0) {
+        if (!FlatReservations::Build(reservations, softReservationUsage, cluster, &local, nullptr)) return installs();
+        flat = &local;
+    }
+    FlatOverhead local_over;
+    if (flatOverhead == nullptr) {
+        if (!FlatOverhead::Build(overhead, cluster, &local_over, nullptr)) return installs();
+        local_over.version = 0;  // this request's own: compared with the resident columns
+        flatOverhead = &local_over;
+    } else if (!flatOverhead->over[0].empty() &&
+               (flatOverhead->over[0].size() != n || flatOverhead->over[1].size() != n || flatOverhead->over[2].size() != n)) {
+        return installs();
+    }
+    uint32_t node = GF_NO_NODE;
+    int rc = GF_ERR_UNSUPPORTED;
+    {
+        std::lock_guard<std::mutex> flat_lock(*flat_mu_);  // the record of what sits on the device; before the sequence lock
+        gf_ctx* ctx = binpacker_.ctx;
+        CtxSequence seq(ctx);
+        uint64_t gen[3] = {0, 0, 0};
+        std::string sync_err;
+        if (syncResident(ctx, cluster, *flatOverhead, flat, gen, &sync_err) == ResidentSync::ok) {
+            const uint32_t row0 = 0;
+            rc = gf_cluster_executor_fit(ctx, minfrag ? 1 : 0, 1, row.data(), 1, exe, &row0, minfrag ? hosts.data() : nullptr, nullptr,
+                                         nullptr, nullptr, &node);
+        }
+    }
+    if (rc != GF_OK) return installs();  // refused, or not resident (outside the locks: that route takes them itself)
+    if (residentRoute) *residentRoute = true;
+    if (node == GF_NO_NODE) {
+        out.outcome = outcome::failureFit;
+        out.error = "not enough capacity to reschedule the executor";
+        return out;
+    }
+    out.node = cluster.names[node];
+    out.outcome = isExtraExecutor ? outcome::successScheduledExtraExecutor : outcome::successRescheduled;
     return out;
 }
 

@@ -165,6 +165,18 @@ public:
     SelectNodeResult rescheduleExecutor(const Pod& executor, const Pod& driver, const std::vector<Pod>& allPods,
                                         const std::vector<std::string>& nodeNames, const std::set<std::string>& nodesHostingApp,
                                         bool isExtraExecutor);
+    // The same Filter answered from the RESIDENT cluster (include/gangfit.h, gf_cluster_executor_fit): `cluster` is the flat cluster of
+    // the driver Filter's flat route.  Overhead rows and usage entries are synced the way selectDriverNodeFlat syncs them (`flat` /
+    // `flatOverhead` nullable: flattened here from `reservations` / `overhead`), nodeNames — narrowed to the common zone on the host,
+    // as above — travels as one bit row, and the device answers from its columns: no string-keyed map, no sort, no install, so the
+    // snapshot epoch and the driver Filter's chain cache stay.  Outcomes and error strings are rescheduleExecutor's.  Whatever the
+    // resident route cannot take — a refusal of the entry point, a name the lister knows and `cluster` does not, an executor label
+    // priority, quantities that are not exactly representable — is answered by rescheduleExecutor (which installs).
+    // *residentRoute (nullable): true when the resident entry point answered.
+    SelectNodeResult rescheduleExecutorFlat(const Pod& executor, const Pod& driver, const std::vector<Pod>& allPods,
+                                            const std::vector<std::string>& nodeNames, const std::set<std::string>& nodesHostingApp,
+                                            bool isExtraExecutor, const FlatCluster& cluster, const FlatReservations* flat = nullptr,
+                                            const FlatOverhead* flatOverhead = nullptr, bool* residentRoute = nullptr);
     // getCommonZoneForExecutorsApplication (resource.go:493-519): {zone, all pods in one zone}; *err set = the reference's error
     std::pair<std::string, bool> getCommonZoneForExecutorsApplication(const Pod& executor, const std::vector<Pod>& allPods,
                                                                       std::string* err) const;
@@ -210,6 +222,9 @@ public:
     bool shouldSkipDriverFifo(const Pod& pod, const std::string& instanceGroup) const;
 
 private:
+    enum class ResidentSync { ok, no_resident_route, failed };
+    ResidentSync syncResident(gf_ctx* ctx, const FlatCluster& cluster, const FlatOverhead& fo, const FlatReservations* usage,
+                              uint64_t gen[3], std::string* err);
     uint64_t resident_cluster_ = 0;  // FlatCluster::version whose static columns sit on the device (selectDriverNodeFlat)
     uint64_t resident_usage_ = 0;    // FlatReservations::version whose usage sums sit on the device (for resident_cluster_)
     // the dense overhead columns this extender last put on the device for resident_cluster_ (gf_cluster_set or

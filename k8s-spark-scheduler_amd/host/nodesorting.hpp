@@ -48,6 +48,7 @@ public:
     // -> {driverNodes, executorNodes}
     std::pair<std::vector<std::string>, std::vector<std::string>> PotentialNodes(
         const NodeGroupSchedulingMetadata& metadata, const std::vector<std::string>& nodeNames) const;
+    bool hasExecutorLabelPriority() const { return executor_.has_value(); }
 
 private:
     std::optional<LabelPriorityOrder> driver_, executor_;

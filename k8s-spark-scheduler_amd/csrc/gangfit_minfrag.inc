@@ -54,7 +54,11 @@ __device__ __forceinline__ int64_t cap_dim_full(int64_t a, int64_t e, double rcp
 
 __device__ __forceinline__ int64_t wave_min_i64(int64_t v) { return -wave_max_i64(-v); }  // callers keep v > INT64_MIN
 
-// Sum over the wave of per-lane values in [0, 2^20] (saturated partial sums), wave-uniform.
+// Sum over the wave of non-negative per-lane values, wave-uniform.  An int32 scan: the TOTAL must stay below 2^31.  The callers
+// pass partial sums saturated at K <= 2^20 (64 lanes: below 2^27), how many nodes a part of the order gives (its slots at
+// most) and, unsaturated, the capacity sum of a count row (shard_mf_counts_kernel: below 2^24 for the whole wave, possibly all
+// of it in one lane).  tests/test_gpu_sharded_minfrag.py::test_range_of_1023_and_1024_chunks holds the largest of each: K = 2^20
+// against 130 944 nodes, ranges of 65 472 nodes, and 65 472 x 255.
 __device__ __forceinline__ int64_t wave_sum_small(int64_t v) {
     return (int64_t)read_lane(wave_inclusive_scan((int32_t)v), kWave - 1);
 }

@@ -719,7 +719,9 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void shard_mf_counts_kernel(
         cn[1] = c4.y;
         cn[2] = c4.z;
         cn[3] = c4.w;
-        int64_t lsum = 0;  // (the range holds fewer than 2^16 slots of capacity below 2^8: the sum stays below 2^24)
+        // (the range holds fewer than 2^16 slots of capacity below 2^8: the sum stays below 2^24 — 65 472 x 255 at most, the second
+        // range of tests/test_gpu_sharded_minfrag.py::test_range_of_1023_and_1024_chunks[2046-255]; 1024 chunks are flagged: [2047-1])
+        int64_t lsum = 0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int64_t cp = 4 * lane + i;

@@ -131,15 +131,18 @@ def test_single_executors_and_find_nodes(ctxs, regime):
 
 @pytest.mark.parametrize("regime", mg.REGIMES)
 def test_two_shards_of_one_device(regime):
-    """A context over device 0 twice: the node-range sharded steps of the four shardable packers (gangfit_shard.inc) —
-    their partial capacity sums and int32 deltas — at these magnitudes."""
+    """A context over device 0 twice: the node-range sharded steps of all six packers (gangfit_shard.inc) — the partial
+    capacity sums and int32 deltas of the tightly-pack family, the count rows, the scaled-domain capacities and the
+    designated-shard walk of the minimal-fragmentation family — at these magnitudes.  The context must still be sharding
+    afterwards: a self-check that "disagreed" is answered right by the first device and would otherwise hide there."""
     with gangfit.Context(devices=[0, 0]) as g:
         assert g.shard_count() == 2
         for name, p, _, refs in _cases(regime):
             _install(g, p)
             apps = gangfit.make_apps(*p[5:9])
-            for algo in (0, 1, 3, 4):
+            for algo in ALGOS:
                 assert stress_lib.same(g.fit_batch(IND, algo, apps), refs[algo][0], False) is None, f"{regime} {name} algo={algo}"
+        assert g.shard_count() == 2, g.last_error()
 
 
 def test_snapshot_build_near_2_62(gf_ctx):

@@ -17,6 +17,7 @@ from oracle import binding as ob
 from test_gpu_group import split  # noqa: F401  (fixture: both GANGFIT_TEST_GROUP_SPLIT modes)
 from test_gpu_parity import _assert_same, _random_problem
 from test_gpu_zones import _setup, _zoned_problem
+from test_sharded_minfrag_cpu import last_bin_expect, last_bin_flags, last_bin_model, last_bin_tables
 
 pytestmark = pytest.mark.gpu
 IND = gangfit.GF_MODE_INDEPENDENT
@@ -51,6 +52,26 @@ def _run(world, algo, avail, sched, zone, D, X, apps):
     return outs
 
 
+def _flags(world, avail, D, X, apps):
+    """The verdict of the counts step itself, [shard][application]: True where shard_mf_counts_kernel published "no histogram
+    form" (fit_count of its record) for the plain packer's one view.  One context takes every shard's range in turn."""
+    import torch
+
+    torch.cuda.init()
+    out = []
+    with gangfit.Context(0) as ctx:
+        _setup(ctx, avail, None, None, D, X)
+        for r in range(world):
+            eng = sharded.HipShardEngine(ctx, r, world, "cuda:0")
+            b = sharded.ShardedMinfragBatch(eng, sharded.SingleComm(), MF, apps)
+            assert b.records == 1
+            with eng.stream_context():
+                mine = eng.mf_counts(MF, b.d_apps, b.n_apps, b.records, b.row_bytes)
+                part = mine[: b.n_apps * 16].cpu().numpy().view(np.int64).reshape(b.n_apps, 2)
+            out.append(part[:, 1] != 0)
+    return np.stack(out)
+
+
 def _ref(algo, avail, sched, zone, D, X, drv, exe, k):
     return ob.fit_independent(O_ALGO[algo], avail, ob.make_apps(drv, exe, k), D, X, sched=sched, zone=zone)
 
@@ -67,9 +88,14 @@ def _check(world, algo, avail, sched, zone, D, X, drv, exe, k, ref=None):
 
 # ---- 1. crafted clusters: 192 executor nodes in identity order, node i = [caps[i], 99, 0]; executor (1, 1, 0).  With a
 #      driver-only node 192 (it merges in ahead of the executors: node i sits at slot i + 1) or D = X (node i at slot i).
+#      The scaled table's units are the gcds of its columns (fill_narrow, csrc/gangfit_slot_layout.h) and a request that is not a
+#      multiple of them has no histogram form: node 192 = [1, 1, 0] keeps them at 1, and without it nodes 1 = [0, 1, 0] and
+#      2 = [1, 0, 0] do, which hold no executor and no driver that asks for cpu.  _hist_form asserts the kernel's verdict.
 def _crafted(caps_at, driver_only=True, extra=None):
     avail = np.zeros((193 if driver_only else 192, 3), dtype=np.int64)
     avail[:192, 1] = 99
+    if not driver_only:
+        avail[1], avail[2] = [0, 1, 0], [1, 0, 0]
     for s, c in caps_at.items():
         avail[s, 0] = c
     for s, row in (extra or {}).items():
@@ -81,9 +107,19 @@ def _crafted(caps_at, driver_only=True, extra=None):
     return avail, X.copy(), X
 
 
-def _crafted_batch(world, avail, D, X, ks, drv=(1, 1, 0), exe=(1, 1, 0)):
+def _hist_form(world, avail, D, X, drv, exe, k, want=False):
+    """The counts step flags the ranges `want` says (one flag for all: a bool; per shard: a list) for every gang with executors:
+    a crafted case that means the histogram form must not walk for a reason of its own making, and the other way round."""
+    k = np.asarray(k)
+    got = _flags(world, avail, D, X, gangfit.make_apps(drv, exe, k))[:, k > 0]
+    want = np.broadcast_to(np.asarray(want, dtype=bool).reshape(-1, 1), got.shape)
+    assert np.array_equal(got, want), got.astype(int).tolist()
+
+
+def _crafted_batch(world, avail, D, X, ks, drv=(1, 1, 0), exe=(1, 1, 0), flagged=False):
     a = len(ks)
     drv, exe = np.tile(np.array(drv, dtype=np.int64), (a, 1)), np.tile(np.array(exe, dtype=np.int64), (a, 1))
+    _hist_form(world, avail, D, X, drv, exe, ks, flagged)
     ref = _check(world, MF, avail, None, None, D, X, drv, exe, np.array(ks, dtype=np.int32))
     return [(bool(ref.results["has_capacity"][i]), int(ref.results["driver_node"][i]), ref.placement(i)[2].tolist()) for i in range(a)]
 
@@ -130,13 +166,140 @@ def test_k_zero_big_capacities_and_unscaled_requests(world):
     # a capacity of 256 or more in ONE shard's range only: every shard must take the designated-shard route, for every
     # application index (the designated shard is a mod n_shards)
     avail, D, X = _crafted({10: 5, 130: 5}, extra={70: [300, 999, 0]})
-    got = _crafted_batch(world, avail, D, X, [4, 7, 290, 305, 4, 7, 311])
+    got = _crafted_batch(world, avail, D, X, [4, 7, 290, 305, 4, 7, 311], flagged=[s == (0 if world == 2 else 1) for s in range(world)])
     assert [g[0] for g in got] == [True] * 6 + [False]
     assert got[0][2] == [10] * 4 and got[2][2] == [70] * 290
-    # a request that is not a multiple of the table's units (every cpu value is a multiple of 30, the executor asks for 4)
+    # a request that is not a multiple of the table's units: every cpu value is a multiple of 30 — the driver-only node's and the
+    # driver's request as well —, the executor asks for 4.  Every range says so, whatever its capacities
     avail, D, X = _crafted({10: 30, 70: 30, 130: 30})
-    got = _crafted_batch(world, avail, D, X, [3, 7, 15, 21, 22], exe=(4, 1, 0))  # capacities 7, 7, 7
+    avail[192] = [30, 1, 0]
+    got = _crafted_batch(world, avail, D, X, [3, 7, 15, 21, 22], drv=(30, 1, 0), exe=(4, 1, 0), flagged=True)  # capacities 7, 7, 7
     assert [g[0] for g in got] == [True] * 4 + [False] and got[1][2] == [10] * 7
+
+
+# ---- 1b. the last bin of a count row: the tables of tests/test_sharded_minfrag_cpu.py::last_bin_tables — a node of 255 (histogram
+#      form) or 256 executors (its range flags every gang: the designated shard walks) in ONE range, with the driver on a node of
+#      its own or on that very node, 256 -> 255 (still flagged) and 255 -> 254 (c0 = 255 patched out of the row's last bin)
+def _last_bin_problem(table):
+    avail, D, X, drv, ks, plain = table
+    a = len(ks)
+    drv_a, exe_a = np.tile(np.array(drv, dtype=np.int64), (a, 1)), np.tile(np.array([1, 1, 0], dtype=np.int64), (a, 1))
+    return (np.array(avail, dtype=np.int64), np.array(D, dtype=np.uint32), np.array(X, dtype=np.uint32), drv_a, exe_a,
+            np.array(ks, dtype=np.int32))
+
+
+def _last_bin_batch(run, table):
+    """`run(avail, D, X, drv, exe, k) -> the oracle's answer` after comparing a route with it; then what the table expects."""
+    ref = run(*_last_bin_problem(table))
+    last_bin_expect([ref.placement(i) for i in range(len(table[4]))], table[1][0], table[5])
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_capacity_255_and_256_in_one_range(world):
+    """With the kernel's own verdict per range: 255 keeps the histogram form in every range, with the driver's node at 255 -> 254
+    too; 256 flags the ranges that hold such a node and no other, 256 -> 255 included."""
+    for table in last_bin_tables():
+        flags = last_bin_flags(last_bin_model(table), world)  # (the model lays the slots out as the device does)
+        assert any(flags) == (table[0][70][0] == 256) and not all(flags)
+        _hist_form(world, *_last_bin_problem(table), flags)
+        _last_bin_batch(lambda avail, D, X, drv, exe, k: _check(world, MF, avail, None, None, D, X, drv, exe, k), table)
+
+
+def _group_batch(g, avail, D, X, drv, exe, k, ref=None):
+    """The batch on the multi-device context `g`, against the oracle; the context is still sharding afterwards."""
+    apps = gangfit.make_apps(drv, exe, k)
+    if ref is None:
+        ref = _ref(MF, avail, None, None, D, X, drv, exe, k)
+    _setup(g, avail, None, None, D, X)
+    _assert_same(g.fit_batch(IND, MF, apps), ref, apps)  # (the first batch of a snapshot: self-checked)
+    _assert_same(g.fit_batch(IND, MF, apps), ref, apps)
+    assert g.shard_count() == 2, g.last_error()
+    return ref
+
+
+def test_capacity_255_and_256_in_one_range_in_library(split):
+    with gangfit.Context(devices=[0, 0]) as g:
+        for table in last_bin_tables():
+            _last_bin_batch(lambda *problem: _group_batch(g, *problem), table)
+
+
+# ---- 1c. the size of a range: thin tables of 2046 and 2047 chunks, two shards.  Identity executor order; four driver candidates
+#      (slots 0, 65 471, 65 472, 130 943: the first slot, either side of the boundary between the ranges, the last slot of 2046
+#      chunks) that a driver's MEMORY request chooses between — candidate i holds i + 1, every other node 1 — while executors ask
+#      for cpu only; a driver that asks for its node's whole cpu drops the node's capacity to 0.
+#        2046 chunks   both ranges are 1023 chunks and keep the histogram form.  Every node holds 1: a uint16 bin of 65 472, a
+#                      summed bin of 130 944.  Every node holds 255 (node 1: 254, so that the cpu column's unit stays 1): the
+#                      second range's capacity sum is 65 472 x 255, the bound shard_mf_counts_kernel's comment claims.
+#        2047 chunks   the second range is 1024 chunks = 65 536 slots: flagged, every gang goes to the designated shard although
+#                      every capacity is 1.
+RANGE_DRIVERS = (0, 65471, 65472, 130943)
+GF_MAX_K = 1 << 20
+
+
+@functools.lru_cache(maxsize=None)
+def _range_table(chunks, cap):
+    """(avail, D, X, drv, exe, k, the oracle's answer: computed once per table, shared by the routes).  Gangs of 65 472 executors
+    (a range's worth at capacity 1), 65 473 (the first node of the next range), 70 000, 130 944 and 130 945 (one more than 2046
+    chunks of capacity 1 hold), and 2^20 where the table holds them; drivers on each of the four candidates, keeping their
+    node's capacity (cpu 0) or taking it.  The oracle is the literal packer; for the gang that does not fit, the closed form
+    as well."""
+    n = chunks * 64
+    avail = np.zeros((n, 3), dtype=np.int64)
+    avail[:, 0], avail[:, 1] = cap, 1
+    if cap > 1:
+        avail[1, 0] = cap - 1
+    avail[list(RANGE_DRIVERS), 1] = np.arange(1, 5)
+    X = np.arange(n, dtype=np.uint32)
+    D = np.array(RANGE_DRIVERS, dtype=np.uint32)
+    total = int(avail[:, 0].sum())
+    # (k, the driver's candidate, whether the driver takes its node's cpu)
+    gangs = [(65472, 0, False), (65473, 0, False), (70000, 0, True), (65472, 1, True), (65472, 2, True), (65473, 1, True),
+             (70000, 3, True), (130944, 0, False), (130943, 2, True), (130945, 3, False)]
+    if total > GF_MAX_K:
+        gangs += [(GF_MAX_K, 0, False), (GF_MAX_K, 0, True), (GF_MAX_K, 3, True)]
+    drv = np.array([[cap if takes else 0, cand + 1, 0] for _, cand, takes in gangs], dtype=np.int64)
+    exe = np.tile(np.array([1, 0, 0], dtype=np.int64), (len(gangs), 1))
+    k = np.array([g[0] for g in gangs], dtype=np.int32)
+    ref = _ref(MF, avail, None, None, D, X, drv, exe, k)
+    misfit = [i for i in range(len(gangs)) if not ref.results["has_capacity"][i]]
+    assert misfit == ([9] if total < 130945 else [])
+    for i in misfit:
+        cf = ob.fit_independent(O_ALGO[MF], avail, ob.make_apps(drv[i:i + 1], exe[i:i + 1], k[i:i + 1]), D, X, closed_form=True)
+        assert not cf.results["has_capacity"][0]
+    fits = np.nonzero(ref.results["has_capacity"])[0]
+    assert [int(ref.results["driver_node"][i]) for i in fits] == [RANGE_DRIVERS[gangs[i][1]] for i in fits]
+    return avail, D, X, drv, exe, k, ref
+
+
+def _range_rows(avail, chunks, world=2):
+    """The count rows of the ranges as the counts step takes them (nothing reserved; executors ask for one cpu)."""
+    cuts = [chunks * s // world * 64 for s in range(world + 1)]
+    return np.stack([np.bincount(np.clip(avail[lo:hi, 0], 0, 256), minlength=257) for lo, hi in zip(cuts, cuts[1:])])
+
+
+RANGE_TABLES = [(2046, 1), (2046, 255), (2047, 1)]
+
+
+@pytest.mark.parametrize("chunks,cap", RANGE_TABLES)
+def test_range_of_1023_and_1024_chunks(chunks, cap):
+    avail, D, X, drv, exe, k, ref = _range_table(chunks, cap)
+    rows = _range_rows(avail, chunks)
+    if chunks == 2046:  # what the rows hold: the largest uint16 bin, the largest summed bin, the largest capacity sum of a range
+        assert rows[:, 1:256].max() == 65472 and rows.sum(axis=0)[1:256].max() == (130944 if cap == 1 else 130943)
+        assert max(int((r[:256] * np.arange(256)).sum()) for r in rows) == 65472 * cap
+    else:
+        assert chunks * 64 - chunks // 2 * 64 == 65536  # the second range: one chunk too many for uint16 counts
+    _hist_form(2, avail, D, X, drv, exe, k, [False, chunks == 2047])  # (the kernel's verdict: 1024 chunks are flagged, 1023 not)
+    apps = gangfit.make_apps(drv, exe, k)
+    for out in _run(2, MF, avail, None, None, D, X, apps):
+        _assert_same(out, ref, apps)
+
+
+@pytest.mark.parametrize("chunks,cap", RANGE_TABLES)
+def test_range_of_1023_and_1024_chunks_in_library(chunks, cap, split):
+    avail, D, X, drv, exe, k, ref = _range_table(chunks, cap)
+    with gangfit.Context(devices=[0, 0]) as g:
+        _group_batch(g, avail, D, X, drv, exe, k, ref)
 
 
 # ---- 2. random parity: the generator of tests/test_gpu_minfrag.py::test_histogram_form_level_walks

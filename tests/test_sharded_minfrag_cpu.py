@@ -39,6 +39,29 @@ class Table:
         return all(int(v) % u == 0 for v, u in zip(list(drv) + list(exe), list(self.units) * 2))
 
 
+def merged_slots(D, X):
+    """plan_layout's merged order (csrc/gangfit_slot_layout.h) of a driver and an executor order without unknown or repeated
+    names: (node of slot, executor candidate flags, driver candidate flags).  A driver-only node goes in ahead of the executors
+    it precedes."""
+    slots, xcand, dcand, i, j = [], [], [], 0, 0
+    while i < len(D) or j < len(X):
+        if i < len(D) and j < len(X) and D[i] == X[j]:
+            slots, xcand, dcand, i, j = slots + [D[i]], xcand + [True], dcand + [True], i + 1, j + 1
+        elif i < len(D) and D[i] not in X:
+            slots, xcand, dcand, i = slots + [D[i]], xcand + [False], dcand + [True], i + 1
+        else:
+            assert j < len(X) and X[j] not in D, "the orders do not merge"
+            slots, xcand, dcand, j = slots + [X[j]], xcand + [True], dcand + [False], j + 1
+    return slots, xcand, dcand
+
+
+def column_units(avail, slots):
+    """fill_narrow's units of the scaled table: per dimension the gcd of the slots' values (1 for a column of zeros).  A request
+    that is not a multiple of them has no histogram form on the device, whatever its capacities are."""
+    cols = np.abs(np.asarray(avail, dtype=np.int64)[list(slots)])
+    return tuple(int(np.gcd.reduce(cols[:, j])) or 1 for j in range(3))
+
+
 def counts_step(T, shard, world, drv, exe, K):
     """-> (S, flag, row): S = sum over the range of min(cap, K), row[c] = nodes of the range with capacity c."""
     lo, hi = T.range_of(shard, world)
@@ -178,6 +201,8 @@ def _crafted(caps_at, driver_only=True, extra=None):
     for s, c in caps_at.items():
         caps[s] = c
     avail = [[int(c), 99, 0] for c in caps]
+    if not driver_only:  # (as tests/test_gpu_sharded_minfrag.py::_crafted: nodes that keep the scaled table's units at 1)
+        avail[1], avail[2] = [0, 1, 0], [1, 0, 0]
     for s, row in (extra or {}).items():
         avail[s] = row
     X = list(range(192))
@@ -240,6 +265,95 @@ def test_k_zero_big_capacities_and_unscaled_requests():
     T.units = (2, 1, 1)
     for K in (3, 7):
         assert _check(avail, D, X, T, DRV, [3, 1, 0], K, WORLDS, a=1)[0]
+
+
+# ---- the last bin of a count row (tests/test_gpu_sharded_minfrag.py runs the same tables through the kernels)
+def last_bin_tables():
+    """[(avail, D, X, driver request, gang sizes, plain)]: the crafted cluster with nodes 10 and 130 at 5 and node 70 at 255 —
+    the row's last bin — or 256, which flags node 70's range alone.  The driver sits on node 192, or on node 70 itself (D = [70]):
+    256 -> 255 is still flagged (the counts are taken with nothing reserved), 255 -> 254 patches c0 = 255 out of the last bin, a
+    driver that asks for no cpu patches it out and in again.  Gangs that land on node 70 alone, that drain it and go on, the
+    cluster's sum, and (last) one more.  plain = False: nodes 140 and 150 hold cap - 1 and cap as well, in a later range than
+    node 70: their ranks in their levels depend on the prefix patch for a driver in an EARLIER range.
+    Nodes 0 = [0, 1, 0] and 1 = [1, 0, 0] hold no executor and keep every column's unit at 1 (column_units): without them the
+    requests of 1 would have no scaled form and every gang would walk, 255 or 256."""
+    out = []
+
+    def cluster(caps):
+        avail = [[0, 99, 0] for _ in range(192)]
+        avail[0], avail[1] = [0, 1, 0], [1, 0, 0]
+        for node, c in caps.items():
+            avail[node] = [c, 99 if c == 5 else 999, 0]
+        return avail
+
+    for cap in (255, 256):
+        for on_70, drv in ((False, [1, 1, 0]), (True, [1, 1, 0]), (True, [0, 1, 0])):
+            avail = cluster({10: 5, 130: 5, 70: cap})
+            if not on_70:
+                avail.append([1, 1, 0])
+            total = cap + 10 - (1 if on_70 and drv[0] else 0)
+            ks = [4, 100, cap - 2, cap - 1, cap, cap + 1, cap + 5, total - 1, total, total + 1]
+            out.append((avail, [70] if on_70 else [192], list(range(192)), drv, ks, True))
+        avail = cluster({10: 5, 130: 5, 70: cap, 140: cap - 1, 150: cap})
+        total = 3 * cap - 2 + 10  # node 70 gives cap - 1 with the driver on it
+        ks = [cap - 1, cap, 2 * cap - 2, 2 * cap - 1, 2 * cap, 3 * cap - 2, 3 * cap - 1, total - 1, total, total + 1]
+        out.append((avail, [70], list(range(192)), [1, 1, 0], ks, False))
+    return out
+
+
+def last_bin_expect(got, driver, plain):
+    """got[i] = (feasible, driver node, executor nodes) of gang i of a table of last_bin_tables, already compared with the oracle."""
+    assert [bool(g[0]) for g in got] == [True] * (len(got) - 1) + [False]
+    assert all(g[1] == driver for g in got[:-1])
+    if plain:  # (K + max) / 2 admits the fives for the small gang only
+        assert list(got[0][2]) == [10] * 4 and list(got[1][2]) == [70] * 100 and sorted(set(got[-2][2])) == [10, 70, 130]
+    else:
+        assert sorted(set(got[-2][2])) == [10, 70, 130, 140, 150]
+
+
+def last_bin_model(table):
+    """The table as the device lays it out — the merged order, the scaled table's units — and the verdict that is the point of
+    it: the requests have a scaled form, so only a capacity of 256 can flag a range."""
+    avail, D, X, drv, ks, plain = table
+    slots, xcand, dcand = merged_slots(D, X)
+    T = Table(avail, slots, xcand, dcand, units=column_units(avail, slots))
+    assert T.units == (1, 1, 1) and T.scaled(drv, EXE)
+    return T
+
+
+def last_bin_flags(T, world):
+    """Which ranges must say "no histogram form": those with an executor candidate of 256 or more, nothing reserved."""
+    return [any(T.cap(j, EXE) >= BINS for j in range(*T.range_of(s, world))) for s in range(world)]
+
+
+def test_capacity_255_and_256_in_one_range():
+    for table in last_bin_tables():
+        avail, D, X, drv, ks, plain = table
+        T = last_bin_model(table)
+        for world in (2, 3):  # 256 flags exactly the ranges that hold such a node, 255 none — whatever the driver will reserve
+            flags = last_bin_flags(T, world)
+            assert [counts_step(T, s, world, drv, EXE, 100)[1] for s in range(world)] == flags
+            assert any(flags) == (avail[70][0] == 256) and not all(flags)
+        last_bin_expect([_check(avail, D, X, T, drv, EXE, K, WORLDS, a=i) for i, K in enumerate(ks)], D[0], plain)
+
+
+# ---- the size of a range: 2047 chunks in two shards = 1023 and 1024 chunks; 65 536 slots are one too many for uint16 counts
+def test_range_of_65536_slots_is_flagged():
+    n = 2047 * 64
+    avail = np.ones((n, 3), dtype=np.int64)
+    X = list(range(n))
+    T = Table(avail, X, [True] * n, [j in (0, 65471, 65472, n - 1) for j in range(n)])
+    exe, drv = [1, 0, 0], [1, 1, 0]
+    assert T.range_of(0, 2) == (0, 65472) and T.range_of(1, 2) == (65472, n)
+    S, flag, row = counts_step(T, 0, 2, drv, exe, 70000)
+    assert (S, flag) == (65472, False) and row[1] == 65472 and row.sum() == 65472
+    S, flag, row = counts_step(T, 1, 2, drv, exe, 70000)
+    assert (S, flag) == (65536, True) and not row.any()
+    assert [counts_step(T, s, 3, drv, exe, 70000)[1] for s in range(3)] == [False] * 3  # 682, 682 and 683 chunks
+    # a few gangs through the whole model: the flag of ONE range sends them to the designated shard, capacities of 1 or not
+    for a, K in enumerate((3, 70)):
+        ok, rd, rex = _check(avail, [0, 65471, 65472, n - 1], X, T, drv, exe, K, (2,), a=a)
+        assert ok and rd == 0 and rex.tolist() == list(range(1, K + 1))
 
 
 def _merged_problem(rng, n, cap_hi):

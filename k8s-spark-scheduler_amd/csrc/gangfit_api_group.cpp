@@ -6,65 +6,50 @@ using namespace gfapi;
 
 namespace gfapi {
 
-bool is_shard_zone_algo(gf_algo algo) { return algo == GF_ALGO_SINGLE_AZ_TIGHTLY_PACK || algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK; }
+using gangfit::ShardFamily;
 
-// GF_OK when node-range sharding serves `algo` on this context (orders installed), else GF_ERR_UNSUPPORTED — with the reason
-// in ctx->err when `report` (the gf_shard_* steps; a multi-device context quietly runs the batch on its first device instead).
-static int shard_serves(gf_ctx* ctx, gf_algo algo, bool report) {
-    char why[256];
-    const uint32_t n_cand = candidate_views(ctx, algo);
-    if (!ctx->merged)
-        std::snprintf(why, sizeof why, "node-range sharding needs the merged slot layout (driver and executor orders must be "
-                                       "subsequences of one priority order)");
-    else if (algo != GF_ALGO_TIGHTLY_PACK && algo != GF_ALGO_DISTRIBUTE_EVENLY && !is_shard_zone_algo(algo))
-        std::snprintf(why, sizeof why, "node-range sharding serves tightly-pack, distribute-evenly, single-az-tightly-pack "
-                                       "and az-aware-tightly-pack only");
-    else if (is_shard_zone_algo(algo) && !ctx->have_sched)
-        std::snprintf(why, sizeof why, "zone-aware packers compare packing efficiencies: node-range sharding needs the "
-                                       "schedulable columns of gf_snapshot_set");
-    else if (is_shard_zone_algo(algo) && (n_cand == 0 || n_cand > 64))
-        std::snprintf(why, sizeof why, "node-range sharding of a zone-aware packer needs 1 to 64 candidate views (zones of "
-                                       "the evaluation list, plus one for az-aware), not %u", n_cand);
-    else
-        return GF_OK;
-    return report ? fail(ctx, GF_ERR_UNSUPPORTED, "%s", why) : GF_ERR_UNSUPPORTED;
+// the packer has zone views (after shard_serves): the zoned family and single-az-minimal-fragmentation
+static bool shard_has_zones(gf_algo algo) {
+    return gangfit::shard_family_of(algo) == ShardFamily::zoned || algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION;
 }
 
-static void shard_range_of(gf_ctx* ctx, gangfit::ShardRange* r);
-
-int shard_ready(gf_ctx* ctx, gf_algo algo, gangfit::ShardRange* r) {
-    if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a sharded fit");
-    if (const int rc = shard_serves(ctx, algo, true); rc != GF_OK) return rc;
-    shard_range_of(ctx, r);
-    return GF_OK;
-}
-
-// The minimal-fragmentation family of shard steps (gf_shard_mf_*): which packers, and when they are served.
-static bool is_shard_mf_algo(gf_algo algo) { return algo == GF_ALGO_MINIMAL_FRAGMENTATION || algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION; }
-static int shard_mf_serves(gf_ctx* ctx, gf_algo algo, bool report) {
+// GF_OK when node-range sharding serves `algo` on this context (orders installed) through the steps asked for — mf_steps: the
+// gf_shard_mf_* entry points, which serve the minfrag family; else gf_shard_*, which serve the other two —, else why not, in
+// ctx->err when `report` (the entry points; a multi-device context quietly runs the batch on its first device instead).  The two
+// sets of steps are part of the ABI as they answer today: gf_shard_mf_* look at the packer before the layout and call missing
+// schedulable columns a GF_ERR_STATE, gf_shard_* look at the layout first and call them GF_ERR_UNSUPPORTED.
+static int shard_serves(gf_ctx* ctx, gf_algo algo, bool mf_steps, bool report) {
     char why[256];
     int rc = GF_ERR_UNSUPPORTED;
-    const bool zoned = algo == GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION;
+    const std::optional<ShardFamily> family = gangfit::shard_family_of(algo);
+    const bool served = family && (*family == ShardFamily::minfrag) == mf_steps;
+    const bool views = served && shard_has_zones(algo);
     const uint32_t n_cand = candidate_views(ctx, algo);
-    if (!is_shard_mf_algo(algo))
+    if (mf_steps && !served)
         std::snprintf(why, sizeof why, "the gf_shard_mf_* steps serve minimal-fragmentation and single-az-minimal-fragmentation only");
     else if (!ctx->merged)
         std::snprintf(why, sizeof why, "node-range sharding needs the merged slot layout (driver and executor orders must be "
                                        "subsequences of one priority order)");
-    else if (zoned && !ctx->have_sched) {
-        rc = GF_ERR_STATE;
-        std::snprintf(why, sizeof why, "single-az-minimal-fragmentation compares packing efficiencies: node-range sharding needs the "
-                                       "schedulable columns of gf_snapshot_set");
-    } else if (zoned && (n_cand == 0 || n_cand > 64))
-        std::snprintf(why, sizeof why, "node-range sharding of single-az-minimal-fragmentation needs 1 to 64 candidate views (zones "
-                                       "of the evaluation list), not %u", n_cand);
+    else if (!served)
+        std::snprintf(why, sizeof why, "node-range sharding serves tightly-pack, distribute-evenly, single-az-tightly-pack "
+                                       "and az-aware-tightly-pack only");
+    else if (views && !ctx->have_sched) {
+        if (mf_steps) rc = GF_ERR_STATE;
+        std::snprintf(why, sizeof why, "%s packing efficiencies: node-range sharding needs the schedulable columns of gf_snapshot_set",
+                      mf_steps ? "single-az-minimal-fragmentation compares" : "zone-aware packers compare");
+    } else if (views && (n_cand == 0 || n_cand > 64))
+        std::snprintf(why, sizeof why, "node-range sharding of %s needs 1 to 64 candidate views (zones of the evaluation list%s), not %u",
+                      mf_steps ? "single-az-minimal-fragmentation" : "a zone-aware packer", mf_steps ? "" : ", plus one for az-aware", n_cand);
     else
         return GF_OK;
     return report ? fail(ctx, rc, "%s", why) : rc;
 }
-static int shard_mf_ready(gf_ctx* ctx, gf_algo algo, gangfit::ShardRange* r) {
+
+static void shard_range_of(gf_ctx* ctx, gangfit::ShardRange* r);
+
+static int shard_ready(gf_ctx* ctx, gf_algo algo, bool mf_steps, gangfit::ShardRange* r) {
     if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a sharded fit");
-    if (const int rc = shard_mf_serves(ctx, algo, true); rc != GF_OK) return rc;
+    if (const int rc = shard_serves(ctx, algo, mf_steps, true); rc != GF_OK) return rc;
     shard_range_of(ctx, r);
     return GF_OK;
 }
@@ -87,36 +72,34 @@ static void shard_range_of(gf_ctx* ctx, gangfit::ShardRange* r) {
 static gangfit::SparseTable shard_sparse(gf_ctx* ctx) {
     return (ctx->n_g != 0 && !ctx->g_prefix.empty()) ? make_sparse(ctx) : gangfit::SparseTable{};
 }
-// the candidate views of a zone-aware packer (after shard_ready); nullptr for the plain packers
-static const gangfit::ShardZones* shard_zones(gf_ctx* ctx, gf_algo algo, gangfit::ShardZones* z) {
-    if (!is_shard_zone_algo(algo) && algo != GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION) return nullptr;
-    z->xmask = ctx->d_zmasks.ptr;
-    z->dmask = ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride;
-    z->span = ctx->zspan_ok ? ctx->d_zspan.ptr : nullptr;
-    z->sched = ctx->d_sched.ptr;
-    z->n_zones = ctx->n_zones;
-    z->stride = ctx->zstride;
-    z->n_cand = candidate_views(ctx, algo);
-    z->az_aware = algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u;
-    return z;
+// What of a ShardBatch comes from the context alone (after shard_ready): the tables and the packer's candidate views.  The
+// caller adds the shards, the records and the stream.
+static void shard_batch_of(gf_ctx* ctx, gf_algo algo, gangfit::ShardBatch* b) {
+    b->table = make_table(ctx, ctx->d_snap.ptr);
+    b->gpu_view = shard_sparse(ctx);
+    b->has_zones = shard_has_zones(algo);
+    if (!b->has_zones) return;
+    gangfit::ShardZones& z = b->zones;
+    z.xmask = ctx->d_zmasks.ptr;
+    z.dmask = ctx->d_zmasks.ptr + (size_t)ctx->zd_row0 * ctx->zstride;
+    z.span = ctx->zspan_ok ? ctx->d_zspan.ptr : nullptr;
+    z.sched = ctx->d_sched.ptr;
+    z.n_zones = ctx->n_zones;
+    z.stride = ctx->zstride;
+    z.n_cand = candidate_views(ctx, algo);
+    z.az_aware = algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u;
 }
-// What a batch's buffers hold (gf_shard_layout): records per application and view, placement buffer words, words to reduce
+// What a batch's buffers hold (gf_shard_layout, gf_shard_mf_layout): records per application and view, placement buffer words,
+// words to reduce
 struct ShardLayout {
     uint32_t records;
     uint64_t exec2_words, reduce_words;
 };
 static ShardLayout shard_layout_of(const gf_ctx* ctx, gf_algo algo, uint64_t half) {
-    if (is_shard_zone_algo(algo)) {
-        const uint32_t v = candidate_views(ctx, algo);
-        return ShardLayout{v, (uint64_t)v * half, (uint64_t)v * half};  // region c: view c's placement (slot + 1)
-    }
-    // [0, half) the placements, [half, 2 half) the capacities of distribute-evenly's pass 1
-    return ShardLayout{1u, 2 * half, algo == GF_ALGO_DISTRIBUTE_EVENLY ? 2 * half : half};
-}
-// ... of the minimal-fragmentation family (gf_shard_mf_layout): region c of the buffer = view c's placement, all of it reduced
-static ShardLayout shard_mf_layout_of(const gf_ctx* ctx, gf_algo algo, uint64_t half) {
+    // plain: [0, half) the placements, [half, 2 half) the capacities of distribute-evenly's pass 1
+    if (gangfit::shard_family_of(algo) == ShardFamily::plain) return ShardLayout{1u, 2 * half, algo == GF_ALGO_DISTRIBUTE_EVENLY ? 2 * half : half};
     const uint32_t v = candidate_views(ctx, algo);
-    return ShardLayout{v, (uint64_t)v * half, (uint64_t)v * half};
+    return ShardLayout{v, (uint64_t)v * half, (uint64_t)v * half};  // region c: view c's placement, all of it reduced
 }
 
 // ---- the submitting threads (GroupPool, gangfit_ctx.h)
@@ -188,10 +171,10 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
                     uint32_t* exec_nodes, uint64_t exec_nodes_cap, int32_t* chain_failed_at) {
     std::lock_guard<std::recursive_mutex> glock(g->mu);
     gf_ctx* const first = g->group[0];
-    const bool zoned = is_shard_zone_algo(algo), minfrag = is_shard_mf_algo(algo);
+    const std::optional<ShardFamily> family = gangfit::shard_family_of(algo);
+    const bool minfrag = family == ShardFamily::minfrag;  // (the gf_shard_mf_* steps: count rows travel with the records)
     bool sharded = mode == GF_MODE_INDEPENDENT && n_apps > 0 && !g->g_shard_off;
-    for (gf_ctx* s : g->group)
-        sharded = sharded && s->have_orders && (minfrag ? shard_mf_serves(s, algo, false) : shard_serves(s, algo, false)) == GF_OK;
+    for (gf_ctx* s : g->group) sharded = sharded && s->have_orders && shard_serves(s, algo, minfrag, false) == GF_OK;
     if (!sharded) {
         const int rc = gf_fit_batch(first, mode, algo, n_apps, apps, results, exec_nodes, exec_nodes_cap, chain_failed_at);
         if (rc != GF_OK) g->err = first->err;
@@ -210,7 +193,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
                     (unsigned long long)total_k);
     const uint64_t half = total_k + 1;
     // records per application and view, the placement buffer and what the reduce of it carries (shard_layout_of)
-    const ShardLayout lay = minfrag ? shard_mf_layout_of(first, algo, half) : shard_layout_of(first, algo, half);
+    const ShardLayout lay = shard_layout_of(first, algo, half);
     const uint32_t rec = lay.records;
     const size_t row_words = gangfit::kShardMfRowBytes / sizeof(uint32_t);  // (minimal-fragmentation: a count row per record)
     const size_t reduce_words = (size_t)lay.reduce_words;
@@ -218,31 +201,29 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
     GF_HIP(g, g->h_exec.reserve(total_k + 1));
     // ---- buffers on every device (growth only: no-ops from the second batch of a size on) and what each device's kernels
     //      must know about the others: every gathered table, every placement buffer
-    gangfit::ShardSet set[gangfit::kMaxGroupDevices];
-    gangfit::ShardZones zones[gangfit::kMaxGroupDevices];
-    const gangfit::ShardZones* zv[gangfit::kMaxGroupDevices] = {};
+    std::vector<gangfit::ShardBatch> batch(D);  // what the steps of each device receive
     gangfit::PeerPtrs part_all{}, drv_all{}, cnt_all{}, exec_others{};
     for (uint32_t d = 0; d < D; ++d) {
         gf_ctx* c = g->group[d];
         GF_HIP(g, hipSetDevice(c->device));
-        set[d] = gangfit::ShardSet{};
-        set[d].n_shards = S;
+        gangfit::ShardSet& set = batch[d].set;
+        set.n_shards = S;
         for (uint32_t sh : c->my_shards) {
             c->shard = sh;
             c->n_shards = S;
             gangfit::ShardRange r{};
-            if (const int rc = minfrag ? shard_mf_ready(c, algo, &r) : shard_ready(c, algo, &r); rc != GF_OK) {
+            if (const int rc = shard_ready(c, algo, minfrag, &r); rc != GF_OK) {
                 g->err = c->err;
                 return rc;
             }
-            const uint32_t q = set[d].n++;
-            set[d].c_lo[q] = r.c_lo;
-            set[d].c_hi[q] = r.c_hi;
-            set[d].shard[q] = sh;
-            set[d].g_lo[q] = r.g_lo;
-            set[d].g_hi[q] = r.g_hi;
+            const uint32_t q = set.n++;
+            set.c_lo[q] = r.c_lo;
+            set.c_hi[q] = r.c_hi;
+            set.shard[q] = sh;
+            set.g_lo[q] = r.g_lo;
+            set.g_hi[q] = r.g_hi;
         }
-        zv[d] = shard_zones(c, algo, &zones[d]);
+        shard_batch_of(c, algo, &batch[d]);
         GF_HIP(g, c->d_apps.reserve(n_apps));
         GF_HIP(g, c->d_results.reserve(n_apps));
         GF_HIP(g, c->g_part_loc.reserve((size_t)c->my_shards.size() * rec * n_apps));
@@ -258,10 +239,29 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         part_all.p[d] = c->g_part_all.ptr;
         drv_all.p[d] = c->g_drv_all.ptr;
         if (d > 0) exec_others.p[exec_others.n++] = c->g_exec2.ptr;
+        gangfit::ShardBatch& b = batch[d];
+        b.n_apps = n_apps;
+        b.d_apps = c->d_apps.ptr;
+        b.d_part = c->g_part_loc.ptr;
+        b.d_all_part = c->g_part_all.ptr;
+        b.d_drv = c->g_drv_loc.ptr;
+        b.d_all_drv = c->g_drv_all.ptr;
+        b.d_counts = minfrag ? c->g_cnt_loc.ptr : nullptr;
+        b.d_all_counts = minfrag ? c->g_cnt_all.ptr : nullptr;
+        b.d_results = c->d_results.ptr;
+        b.d_exec2 = c->g_exec2.ptr;
+        b.half = half;
+        b.n_shards = S;
+        b.stream = c->stream;
     }
     part_all.n = drv_all.n = cnt_all.n = D;
     const bool use_rccl = g->g_comms.size() == D && D == S;
-    const gangfit::PeerPtrs no_peers{};
+    if (!use_rccl)  // the producing kernels write into every device's gathered table
+        for (gangfit::ShardBatch& b : batch) {
+            b.part_dsts = part_all;
+            b.drv_dsts = drv_all;
+            if (minfrag) b.count_dsts = cnt_all;
+        }
     std::vector<int> rc_of(D, GF_OK);
     auto hip_ok = [&](uint32_t d, hipError_t e, const char* what) {
         if (e == hipSuccess || rc_of[d] != GF_OK) return e == hipSuccess;
@@ -274,14 +274,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         gf_ctx* c = g->group[d];
         if (!GF_STEP(d, hipSetDevice(c->device))) return;
         if (!GF_STEP(d, hipMemcpyAsync(c->d_apps.ptr, g->h_apps.ptr, (size_t)n_apps * sizeof(gf_app), hipMemcpyHostToDevice, c->stream))) return;
-        if (minfrag) {
-            if (!GF_STEP(d, gangfit::launch_shard_mf_counts(make_table(c, c->d_snap.ptr), set[d], n_apps, c->d_apps.ptr, c->g_part_loc.ptr,
-                                                            c->g_cnt_loc.ptr, use_rccl ? no_peers : part_all,
-                                                            use_rccl ? no_peers : cnt_all, c->stream, zv[d])))
-                return;
-        } else if (!GF_STEP(d, gangfit::launch_shard_partials(algo, make_table(c, c->d_snap.ptr), shard_sparse(c), set[d], n_apps, c->d_apps.ptr,
-                                                              c->g_part_loc.ptr, use_rccl ? no_peers : part_all, c->stream, zv[d])))
-            return;
+        if (!GF_STEP(d, gangfit::launch_shard_first(algo, batch[d]))) return;
         if (g->g_fault == 2 && d > 0 && !use_rccl) {  // fault injection: this device's capacity sums arrive as zeros everywhere
             for (uint32_t t = 0; t < D; ++t)
                 for (uint32_t sh : c->my_shards)
@@ -301,24 +294,14 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
         gf_ctx* c = g->group[d];
         if (rc_of[d] != GF_OK || !GF_STEP(d, hipSetDevice(c->device))) return;
         if (D > 1 && !use_rccl) wait_others(d, 0);
-        if (!GF_STEP(d, gangfit::launch_shard_drivers(make_table(c, c->d_snap.ptr), set[d], n_apps, c->d_apps.ptr, c->g_part_all.ptr,
-                                                      c->g_drv_loc.ptr, use_rccl ? no_peers : drv_all, c->stream, zv[d])))
-            return;
+        if (!GF_STEP(d, gangfit::launch_shard_drivers(algo, batch[d]))) return;
         if (D > 1 && !use_rccl) (void)GF_STEP(d, hipEventRecord(c->g_ev[1], c->stream));
     };
     auto step_emit = [&](uint32_t d) {
         gf_ctx* c = g->group[d];
         if (rc_of[d] != GF_OK || !GF_STEP(d, hipSetDevice(c->device))) return;
         if (D > 1 && !use_rccl) wait_others(d, 1);
-        if (minfrag) {
-            if (!GF_STEP(d, gangfit::launch_shard_mf_emit(make_table(c, c->d_snap.ptr), set[d], n_apps, c->d_apps.ptr, c->g_part_all.ptr,
-                                                          c->g_drv_all.ptr, c->g_cnt_all.ptr, c->d_results.ptr, c->g_exec2.ptr, half,
-                                                          c->stream, zv[d])))
-                return;
-        } else if (!GF_STEP(d, gangfit::launch_shard_emit(algo, make_table(c, c->d_snap.ptr), shard_sparse(c), set[d], n_apps, c->d_apps.ptr,
-                                                          c->g_part_all.ptr, c->g_drv_all.ptr, c->d_results.ptr, c->g_exec2.ptr, half,
-                                                          c->stream, zv[d])))
-            return;
+        if (!GF_STEP(d, gangfit::launch_shard_emit(algo, batch[d]))) return;
         if (D > 1) (void)GF_STEP(d, hipEventRecord(c->g_ev[2], c->stream));
     };
     auto step_finish = [&]() {  // the first device only: sum of the slices (each entry written by exactly one shard), finish, D2H
@@ -329,14 +312,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
             if (g->g_fault != 1 && D > 1)  // fault injection: the other devices' placement slices never arrive
                 if (!GF_STEP(0, gangfit::launch_shard_reduce_pull(exec_others, first->g_exec2.ptr, reduce_words, first->stream))) return;
         }
-        const gangfit::NodeTable ft = make_table(first, first->d_snap.ptr);
-        if (minfrag) {
-            if (!GF_STEP(0, gangfit::launch_shard_mf_finish(S, n_apps, first->d_apps.ptr, first->g_part_all.ptr, first->g_drv_all.ptr,
-                                                            first->d_results.ptr, first->g_exec2.ptr, half, first->stream, ft, zv[0])))
-                return;
-        } else if (!GF_STEP(0, gangfit::launch_shard_finish(algo, S, n_apps, first->d_apps.ptr, first->g_part_all.ptr, first->g_drv_all.ptr,
-                                                            first->d_results.ptr, first->g_exec2.ptr, half, first->stream, &ft, zv[0])))
-            return;
+        if (!GF_STEP(0, gangfit::launch_shard_finish(algo, batch[0]))) return;
         if (!GF_STEP(0, hipMemcpyAsync(g->h_results.ptr, first->d_results.ptr, (size_t)n_apps * sizeof(gf_result), hipMemcpyDeviceToHost, first->stream))) return;
         if (total_k && !GF_STEP(0, hipMemcpyAsync(g->h_exec.ptr, first->g_exec2.ptr, (size_t)total_k * sizeof(uint32_t), hipMemcpyDeviceToHost, first->stream))) return;
         (void)GF_STEP(0, gf_wait_stream(first->stream));
@@ -426,7 +402,7 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
     //      also answered by the first device alone.  A wrong exchange (peer stores that did not land, a collective that reduced
     //      something else) must not decide a Filter: on a mismatch the context stops sharding, says why, and serves the first
     //      device's answer.
-    uint64_t& verified = g->g_verified_epoch[minfrag ? 2 : (zoned ? 1 : 0)];
+    uint64_t& verified = g->g_verified_epoch[(int)*family];  // (plain, zoned, minfrag)
     if (g->g_verify && first->snap_epoch != verified) {
         std::vector<gf_result> ref_res(n_apps);
         std::vector<uint32_t> ref_exec((size_t)total_k + 1);
@@ -452,14 +428,80 @@ int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, cons
     return GF_OK;
 }
 
+// ---- the entry points of one process per GPU
+// Every one of them begins here: a multi-device context runs the steps itself.
+static int shard_single_device(gf_ctx* ctx) {
+    if (ctx != nullptr && !ctx->group.empty())
+        return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
+    return ctx ? GF_OK : GF_ERR_INVALID;
+}
+// The preamble of a step (mf_steps: one of gf_shard_mf_*): the context, then the step's own pointer check — made by the caller,
+// which knows its pointers, and judged here, where its place among the checks is —, then whether the packer is served; on GF_OK
+// *b holds everything that does not depend on the step: tables, views, the context's shard and the stream.
+static int shard_step_begin(gf_ctx* ctx, gf_algo algo, bool mf_steps, bool pointers_ok, void* stream, gangfit::ShardBatch* b) {
+    if (const int rc = shard_single_device(ctx); rc != GF_OK) return rc;
+    if (!pointers_ok) return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
+    gangfit::ShardRange r{};
+    if (const int rc = shard_ready(ctx, algo, mf_steps, &r); rc != GF_OK) return rc;
+    shard_batch_of(ctx, algo, b);
+    b->set = gangfit::shard_set_of(r);
+    b->n_shards = ctx->n_shards;
+    b->stream = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    return GF_OK;
+}
+// ... and of a layout query
+static int shard_layout_begin(gf_ctx* ctx, gf_algo algo, bool mf_steps, uint64_t half, ShardLayout* lay) {
+    if (const int rc = shard_single_device(ctx); rc != GF_OK) return rc;
+    if (half == 0) return fail(ctx, GF_ERR_INVALID, "half must be at least 1 (sum of k + 1)");
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    gangfit::ShardRange r{};
+    if (const int rc = shard_ready(ctx, algo, mf_steps, &r); rc != GF_OK) return rc;
+    *lay = shard_layout_of(ctx, algo, half);
+    return GF_OK;
+}
+
+// (both families: the packer's family decides which steps serve it, the search is the same)
+static int shard_drivers_dev(gf_ctx* ctx, gf_algo algo, bool mf_steps, uint32_t n_apps, const gf_app* d_apps,
+                             const gf_shard_partial* d_all_partials, gf_shard_driver* d_out, void* stream) {
+    gangfit::ShardBatch b;
+    if (const int rc = shard_step_begin(ctx, algo, mf_steps, n_apps == 0 || (d_apps && d_all_partials && d_out), stream, &b); rc != GF_OK)
+        return rc;
+    b.n_apps = n_apps;
+    b.d_apps = d_apps;
+    b.d_all_part = d_all_partials;
+    b.d_drv = d_out;
+    GF_HIP(ctx, gangfit::launch_shard_drivers(algo, b));
+    return GF_OK;
+}
+// emit and finish of both families take the same buffers (d_all_counts: gf_shard_mf_emit_dev alone)
+static int shard_emit_or_finish_dev(gf_ctx* ctx, gf_algo algo, bool mf_steps, bool emit, uint32_t n_apps, const gf_app* d_apps,
+                                    const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
+                                    const void* d_all_counts, gf_result* d_results, uint32_t* d_exec2, uint64_t half, void* stream) {
+    const bool counts_ok = !(mf_steps && emit) || d_all_counts;
+    gangfit::ShardBatch b;
+    if (const int rc = shard_step_begin(ctx, algo, mf_steps,
+                                        n_apps == 0 || (d_apps && d_all_partials && d_all_drivers && counts_ok && d_results && d_exec2 && half != 0),
+                                        stream, &b);
+        rc != GF_OK)
+        return rc;
+    b.n_apps = n_apps;
+    b.d_apps = d_apps;
+    b.d_all_part = d_all_partials;
+    b.d_all_drv = d_all_drivers;
+    b.d_all_counts = static_cast<const uint32_t*>(d_all_counts);
+    b.d_results = d_results;
+    b.d_exec2 = d_exec2;
+    b.half = half;
+    GF_HIP(ctx, emit ? gangfit::launch_shard_emit(algo, b) : gangfit::launch_shard_finish(algo, b));
+    return GF_OK;
+}
+
 }  // namespace gfapi
 
 extern "C" {
 
 int gf_shard_set(gf_ctx* ctx, uint32_t shard, uint32_t n_shards) {
-    if (ctx != nullptr && !ctx->group.empty())
-        return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
-    if (!ctx) return GF_ERR_INVALID;
+    if (const int rc = shard_single_device(ctx); rc != GF_OK) return rc;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     GF_NOT_ON_A_VIEW(ctx);
     if (n_shards == 0 || shard >= n_shards || n_shards > 1024)
@@ -471,85 +513,37 @@ int gf_shard_set(gf_ctx* ctx, uint32_t shard, uint32_t n_shards) {
 
 int gf_shard_partials_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps, gf_shard_partial* d_out,
                           void* stream) {
-    if (ctx != nullptr && !ctx->group.empty())
-        return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
-    if (!ctx) return GF_ERR_INVALID;
-    if (n_apps > 0 && (!d_apps || !d_out)) return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
-    gangfit::ShardRange r{};
-    const int rc = shard_ready(ctx, algo, &r);
-    if (rc != GF_OK) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    gangfit::ShardZones z{};
-    GF_HIP(ctx, gangfit::launch_shard_partials(algo, make_table(ctx, ctx->d_snap.ptr), shard_sparse(ctx), gangfit::shard_set_of(r), n_apps, d_apps, d_out,
-                                               gangfit::PeerPtrs{}, st, shard_zones(ctx, algo, &z)));
+    gangfit::ShardBatch b;
+    if (const int rc = shard_step_begin(ctx, algo, false, n_apps == 0 || (d_apps && d_out), stream, &b); rc != GF_OK) return rc;
+    b.n_apps = n_apps;
+    b.d_apps = d_apps;
+    b.d_part = d_out;
+    GF_HIP(ctx, gangfit::launch_shard_first(algo, b));
     return GF_OK;
 }
 
 int gf_shard_drivers_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps,
                          const gf_shard_partial* d_all_partials, gf_shard_driver* d_out, void* stream) {
-    if (ctx != nullptr && !ctx->group.empty())
-        return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
-    if (!ctx) return GF_ERR_INVALID;
-    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_out))
-        return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
-    gangfit::ShardRange r{};
-    const int rc = shard_ready(ctx, algo, &r);
-    if (rc != GF_OK) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    gangfit::ShardZones z{};
-    GF_HIP(ctx, gangfit::launch_shard_drivers(make_table(ctx, ctx->d_snap.ptr), gangfit::shard_set_of(r), n_apps, d_apps, d_all_partials,
-                                              d_out, gangfit::PeerPtrs{}, st, shard_zones(ctx, algo, &z)));
-    return GF_OK;
+    return shard_drivers_dev(ctx, algo, false, n_apps, d_apps, d_all_partials, d_out, stream);
 }
 
 int gf_shard_emit_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps,
                       const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers, gf_result* d_results,
                       uint32_t* d_exec2, uint64_t half, void* stream) {
-    if (ctx != nullptr && !ctx->group.empty())
-        return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
-    if (!ctx) return GF_ERR_INVALID;
-    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_all_drivers || !d_results || !d_exec2 || half == 0))
-        return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
-    gangfit::ShardRange r{};
-    const int rc = shard_ready(ctx, algo, &r);
-    if (rc != GF_OK) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    gangfit::ShardZones z{};
-    GF_HIP(ctx, gangfit::launch_shard_emit(algo, make_table(ctx, ctx->d_snap.ptr), shard_sparse(ctx), gangfit::shard_set_of(r), n_apps, d_apps, d_all_partials,
-                                           d_all_drivers, d_results, d_exec2, half, st, shard_zones(ctx, algo, &z)));
-    return GF_OK;
+    return shard_emit_or_finish_dev(ctx, algo, false, true, n_apps, d_apps, d_all_partials, d_all_drivers, nullptr, d_results, d_exec2, half,
+                                    stream);
 }
-
 int gf_shard_finish_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps,
                         const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
                         gf_result* d_results, uint32_t* d_exec2, uint64_t half, void* stream) {
-    if (ctx != nullptr && !ctx->group.empty())
-        return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
-    if (!ctx) return GF_ERR_INVALID;
-    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_all_drivers || !d_results || !d_exec2 || half == 0))
-        return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
-    gangfit::ShardRange r{};
-    const int rc = shard_ready(ctx, algo, &r);
-    if (rc != GF_OK) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    gangfit::ShardZones z{};
-    const gangfit::NodeTable t = make_table(ctx, ctx->d_snap.ptr);
-    GF_HIP(ctx, gangfit::launch_shard_finish(algo, ctx->n_shards, n_apps, d_apps, d_all_partials, d_all_drivers,
-                                             d_results, d_exec2, half, st, &t, shard_zones(ctx, algo, &z)));
-    return GF_OK;
+    return shard_emit_or_finish_dev(ctx, algo, false, false, n_apps, d_apps, d_all_partials, d_all_drivers, nullptr, d_results, d_exec2, half,
+                                    stream);
 }
 
 int gf_shard_layout(gf_ctx* ctx, gf_algo algo, uint64_t half, uint32_t* records_per_app, uint64_t* exec2_words,
                     uint64_t* reduce_words) {
-    if (ctx != nullptr && !ctx->group.empty())
-        return fail(ctx, GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)");
-    if (!ctx) return GF_ERR_INVALID;
-    if (half == 0) return fail(ctx, GF_ERR_INVALID, "half must be at least 1 (sum of k + 1)");
-    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-    gangfit::ShardRange r{};
-    const int rc = shard_ready(ctx, algo, &r);
-    if (rc != GF_OK) return rc;
-    const ShardLayout lay = shard_layout_of(ctx, algo, half);
+    ShardLayout lay{};
+    if (const int rc = shard_layout_begin(ctx, algo, false, half, &lay); rc != GF_OK) return rc;
     if (records_per_app) *records_per_app = lay.records;
     if (exec2_words) *exec2_words = lay.exec2_words;
     if (reduce_words) *reduce_words = lay.reduce_words;
@@ -557,19 +551,10 @@ int gf_shard_layout(gf_ctx* ctx, gf_algo algo, uint64_t half, uint32_t* records_
 }
 
 // ---- the minimal-fragmentation family (gangfit_shard.inc: the shard_mf_* kernels)
-#define GF_SHARD_MF_SINGLE(ctx)                                                                                                    \
-    if ((ctx) != nullptr && !(ctx)->group.empty())                                                                                 \
-        return fail((ctx), GF_ERR_UNSUPPORTED, "a multi-device context runs the shard steps and their exchanges itself (gf_fit_batch)"); \
-    if (!(ctx)) return GF_ERR_INVALID
-
 int gf_shard_mf_layout(gf_ctx* ctx, gf_algo algo, uint64_t half, uint32_t* records_per_app, uint32_t* count_bytes_per_record,
                        uint64_t* exec2_words, uint64_t* reduce_words) {
-    GF_SHARD_MF_SINGLE(ctx);
-    if (half == 0) return fail(ctx, GF_ERR_INVALID, "half must be at least 1 (sum of k + 1)");
-    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
-    gangfit::ShardRange r{};
-    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
-    const ShardLayout lay = shard_mf_layout_of(ctx, algo, half);
+    ShardLayout lay{};
+    if (const int rc = shard_layout_begin(ctx, algo, true, half, &lay); rc != GF_OK) return rc;
     if (records_per_app) *records_per_app = lay.records;
     if (count_bytes_per_record) *count_bytes_per_record = gangfit::kShardMfRowBytes;
     if (exec2_words) *exec2_words = lay.exec2_words;
@@ -579,61 +564,34 @@ int gf_shard_mf_layout(gf_ctx* ctx, gf_algo algo, uint64_t half, uint32_t* recor
 
 int gf_shard_mf_counts_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps, gf_shard_partial* d_part_out,
                            void* d_counts_out, void* stream) {
-    GF_SHARD_MF_SINGLE(ctx);
-    if (n_apps > 0 && (!d_apps || !d_part_out || !d_counts_out)) return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
-    gangfit::ShardRange r{};
-    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    gangfit::ShardZones z{};
-    GF_HIP(ctx, gangfit::launch_shard_mf_counts(make_table(ctx, ctx->d_snap.ptr), gangfit::shard_set_of(r), n_apps, d_apps, d_part_out,
-                                                static_cast<uint32_t*>(d_counts_out), gangfit::PeerPtrs{}, gangfit::PeerPtrs{}, st,
-                                                shard_zones(ctx, algo, &z)));
+    gangfit::ShardBatch b;
+    if (const int rc = shard_step_begin(ctx, algo, true, n_apps == 0 || (d_apps && d_part_out && d_counts_out), stream, &b); rc != GF_OK)
+        return rc;
+    b.n_apps = n_apps;
+    b.d_apps = d_apps;
+    b.d_part = d_part_out;
+    b.d_counts = static_cast<uint32_t*>(d_counts_out);
+    GF_HIP(ctx, gangfit::launch_shard_first(algo, b));
     return GF_OK;
 }
 
 int gf_shard_mf_drivers_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps,
                             const gf_shard_partial* d_all_partials, gf_shard_driver* d_out, void* stream) {
-    GF_SHARD_MF_SINGLE(ctx);
-    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_out)) return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
-    gangfit::ShardRange r{};
-    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    gangfit::ShardZones z{};
-    GF_HIP(ctx, gangfit::launch_shard_drivers(make_table(ctx, ctx->d_snap.ptr), gangfit::shard_set_of(r), n_apps, d_apps, d_all_partials,
-                                              d_out, gangfit::PeerPtrs{}, st, shard_zones(ctx, algo, &z)));
-    return GF_OK;
+    return shard_drivers_dev(ctx, algo, true, n_apps, d_apps, d_all_partials, d_out, stream);
 }
 
 int gf_shard_mf_emit_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
                          const gf_shard_driver* d_all_drivers, const void* d_all_counts, gf_result* d_results, uint32_t* d_exec2,
                          uint64_t half, void* stream) {
-    GF_SHARD_MF_SINGLE(ctx);
-    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_all_drivers || !d_all_counts || !d_results || !d_exec2 || half == 0))
-        return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
-    gangfit::ShardRange r{};
-    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    gangfit::ShardZones z{};
-    GF_HIP(ctx, gangfit::launch_shard_mf_emit(make_table(ctx, ctx->d_snap.ptr), gangfit::shard_set_of(r), n_apps, d_apps, d_all_partials,
-                                              d_all_drivers, static_cast<const uint32_t*>(d_all_counts), d_results, d_exec2, half, st,
-                                              shard_zones(ctx, algo, &z)));
-    return GF_OK;
+    return shard_emit_or_finish_dev(ctx, algo, true, true, n_apps, d_apps, d_all_partials, d_all_drivers, d_all_counts, d_results, d_exec2, half,
+                                    stream);
 }
 
 int gf_shard_mf_finish_dev(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* d_apps,
                            const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers, gf_result* d_results,
                            uint32_t* d_exec2, uint64_t half, void* stream) {
-    GF_SHARD_MF_SINGLE(ctx);
-    if (n_apps > 0 && (!d_apps || !d_all_partials || !d_all_drivers || !d_results || !d_exec2 || half == 0))
-        return fail(ctx, GF_ERR_INVALID, "device pointers must not be NULL");
-    gangfit::ShardRange r{};
-    if (const int rc = shard_mf_ready(ctx, algo, &r); rc != GF_OK) return rc;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    gangfit::ShardZones z{};
-    GF_HIP(ctx, gangfit::launch_shard_mf_finish(ctx->n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half,
-                                                st, make_table(ctx, ctx->d_snap.ptr), shard_zones(ctx, algo, &z)));
-    return GF_OK;
+    return shard_emit_or_finish_dev(ctx, algo, true, false, n_apps, d_apps, d_all_partials, d_all_drivers, nullptr, d_results, d_exec2, half,
+                                    stream);
 }
-#undef GF_SHARD_MF_SINGLE
 
 }  // extern "C"

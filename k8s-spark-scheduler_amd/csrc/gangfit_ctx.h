@@ -560,7 +560,6 @@ int view_refresh(gf_ctx* v);
 
 // ---- what the translation units offer each other
 // gangfit_api_group.cpp
-bool is_shard_zone_algo(gf_algo algo);  // single-az-tightly-pack, az-aware-tightly-pack: node-range sharded by candidate views
 int group_fit_batch(gf_ctx* g, gf_mode mode, gf_algo algo, uint32_t n_apps, const gf_app* apps, gf_result* results,
                     uint32_t* exec_nodes, uint64_t exec_nodes_cap, int32_t* chain_failed_at);
 // gangfit_api_fit.cpp

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <optional>
+
 #include "gangfit.h"
 #include "gangfit_worker_rounds.h"
 
@@ -423,40 +425,53 @@ struct ShardZones {
     uint32_t n_cand;        // n_zones (+ 1 for az-aware); 1 <= n_cand <= 64
     uint32_t az_aware;
 };
-// gpu_view (n_x == 0: none): gangs whose executors need a gpu are summed / emitted from the range's part of the compact table.
-// zones == nullptr: the plain packers (one record per application); otherwise the zone-aware ones (algo is then ignored).
-hipError_t launch_shard_partials(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
-                                 uint32_t n_apps, const gf_app* d_apps, gf_shard_partial* d_out, const PeerPtrs& dsts,
-                                 hipStream_t stream, const ShardZones* zones = nullptr);
-hipError_t launch_shard_drivers(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
-                                const gf_shard_partial* d_all_partials, gf_shard_driver* d_out, const PeerPtrs& dsts,
-                                hipStream_t stream, const ShardZones* zones = nullptr);
-// (zeroes d_exec2 first — 2 * half words, n_cand * half for the zone-aware packers; every hosted shard writes its slice of the ONE
-// buffer, row 0 also the results of the plain packers: the zone-aware ones leave every choice to the finish step)
-hipError_t launch_shard_emit(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
-                             uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
-                             const gf_shard_driver* d_all_drivers, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
-                             hipStream_t stream, const ShardZones* zones = nullptr);
-// (zone-aware packers: d_results is written here, from the table's slot_node / columns and zones->sched)
-hipError_t launch_shard_finish(gf_algo algo, uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps,
-                               const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
-                               gf_result* d_results, uint32_t* d_exec2, uint64_t half, hipStream_t stream,
-                               const NodeTable* table = nullptr, const ShardZones* zones = nullptr);
-// The minimal-fragmentation packers on the shard steps (gangfit_shard.inc: the shard_mf_* kernels; zones == nullptr: the plain
-// packer, else the views of single-az-minimal-fragmentation).  The drivers step is launch_shard_drivers.  A count row is
-// kShardMfRowBytes per record, laid out like the records ([shard][view][app]); count_dsts like part_dsts.
+// The packers the shard steps serve, by what a step has to do for them: plain (tightly-pack, distribute-evenly: one record per
+// application), zoned (single-az-tightly-pack, az-aware-tightly-pack: a record per candidate view, the finish step chooses) and
+// minfrag (minimal-fragmentation, single-az-minimal-fragmentation: a count row next to every record of the first exchange).
+enum class ShardFamily { plain, zoned, minfrag };
+inline std::optional<ShardFamily> shard_family_of(gf_algo algo) {  // (nothing: no shard step serves the packer)
+    switch (algo) {
+        case GF_ALGO_TIGHTLY_PACK:
+        case GF_ALGO_DISTRIBUTE_EVENLY: return ShardFamily::plain;
+        case GF_ALGO_SINGLE_AZ_TIGHTLY_PACK:
+        case GF_ALGO_AZ_AWARE_TIGHTLY_PACK: return ShardFamily::zoned;
+        case GF_ALGO_MINIMAL_FRAGMENTATION:
+        case GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION: return ShardFamily::minfrag;
+        default: return std::nullopt;
+    }
+}
+// A count row of the minimal-fragmentation packers: kShardMfRowBytes per record, laid out like the records ([shard][view][app]).
 constexpr uint32_t kShardMfRowBytes = 512;
-hipError_t launch_shard_mf_counts(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
-                                  gf_shard_partial* d_part, uint32_t* d_counts, const PeerPtrs& part_dsts, const PeerPtrs& count_dsts,
-                                  hipStream_t stream, const ShardZones* zones = nullptr);
-// (zeroes d_exec2 first: views * half words)
-hipError_t launch_shard_mf_emit(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
-                                const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
-                                const uint32_t* d_all_counts, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
-                                hipStream_t stream, const ShardZones* zones = nullptr);
-hipError_t launch_shard_mf_finish(uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
-                                  const gf_shard_driver* d_all_drivers, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
-                                  hipStream_t stream, const NodeTable& table, const ShardZones* zones = nullptr);
+// What every shard step receives: one device's part of one batch.  A step reads what it needs and leaves the rest alone, so
+// an entry point sets only its own pointers.
+struct ShardBatch {
+    NodeTable table{};
+    SparseTable gpu_view{};  // n_x == 0: none; else gangs whose executors need a gpu are summed / emitted from the range's part of it
+    ShardSet set{};          // the shards this device hosts
+    ShardZones zones{nullptr, nullptr, nullptr, nullptr, 0, 0, 1, 0};  // the candidate views; without zones the one plain view
+    bool has_zones = false;  // the packer has zone views (the zoned family, single-az-minimal-fragmentation)
+    uint32_t n_apps = 0;
+    const gf_app* d_apps = nullptr;
+    gf_shard_partial* d_part = nullptr;            // first: this device's records, [hosted shard][view][app] (part_dsts empty)
+    const gf_shard_partial* d_all_part = nullptr;  // the gathered records, [shard][view][app]
+    gf_shard_driver* d_drv = nullptr;              // drivers: as d_part
+    const gf_shard_driver* d_all_drv = nullptr;    // ... and d_all_part
+    uint32_t* d_counts = nullptr;                  // first, minimal-fragmentation only (else nullptr): the count rows, as d_part
+    const uint32_t* d_all_counts = nullptr;        // ... gathered
+    gf_result* d_results = nullptr;  // emit (plain packers, plain minimal-fragmentation) or finish (packers with zone views)
+    uint32_t* d_exec2 = nullptr;     // the placement buffer: zeroed by emit, every hosted shard writes its slice of it
+    uint64_t half = 0;               // words of one region of it (sum of k + 1)
+    uint32_t n_shards = 0;           // finish: shards of the gathered tables
+    hipStream_t stream = nullptr;
+    // The pushed exchanges of the in-process multi-device context (empty: the one-process-per-GPU path and the RCCL exchange)
+    PeerPtrs part_dsts{}, count_dsts{}, drv_dsts{};
+};
+// first: the capacity sums of the hosted ranges (minimal-fragmentation: and their count rows).
+hipError_t launch_shard_first(gf_algo algo, const ShardBatch& batch);
+hipError_t launch_shard_drivers(gf_algo algo, const ShardBatch& batch);
+// (zeroes d_exec2 first: 2 * half words for the plain packers, a region of half words per view otherwise)
+hipError_t launch_shard_emit(gf_algo algo, const ShardBatch& batch);
+hipError_t launch_shard_finish(gf_algo algo, const ShardBatch& batch);
 // d_dst[i] += sum over srcs of src[i], n uint32 entries (only the first device finishes a batch: the all-reduce is a reduce)
 hipError_t launch_shard_reduce_pull(const PeerPtrs& srcs, uint32_t* d_dst, size_t n, hipStream_t stream);
 

@@ -1867,7 +1867,6 @@ __global__ __launch_bounds__(kWave) void selftest_kernel(uint64_t seed, uint32_t
 
 // ------------------------------------------------------------------------------------------------ launchers
 
-// Workgroups of the worker kernel one CU holds at a time (what the runtime reports; the caller keeps a margin).
 namespace {
 // hipFuncAttributeMaxDynamicSharedMemorySize is per kernel and per device and only ever needs raising: the runtime call is
 // made when a launch asks for more than any launch before it (one call less per chain otherwise).
@@ -1906,6 +1905,7 @@ hipError_t with_worker_algo(gf_algo algo, F&& f) {
                       GF_ALGO_AZ_AWARE_TIGHTLY_PACK>(algo, f);
 }
 
+// Workgroups of the worker kernel one CU holds at a time (what the runtime reports; the caller keeps a margin).
 hipError_t worker_blocks_per_cu(gf_algo algo, int* out) {
     return with_worker_algo(algo, [&](auto A) {
         return hipOccupancyMaxActiveBlocksPerMultiprocessor(out, fit_worker_kernel<A>, kWave * kWorkerWaves, 0);
@@ -2326,131 +2326,110 @@ hipError_t launch_node_efficiencies(bool reserve_execs, const EffTables& eff_by_
     return hipGetLastError();
 }
 
-// ---- node-range sharding (gangfit_shard.inc)
-inline dim3 shard_grid(uint32_t n_apps, const ShardSet& set) { return dim3(app_grid(n_apps).x, set.n); }
-
-// (zone-aware views: grid z = candidate view)
-inline dim3 shard_grid(uint32_t n_apps, const ShardSet& set, const ShardZones& z) { return dim3(app_grid(n_apps).x, set.n, z.n_cand); }
-inline bool shard_zones_ok(const ShardZones* z) { return z->n_cand >= 1 && z->n_cand <= 64 && z->n_zones + (z->az_aware ? 1u : 0u) == z->n_cand; }
-
-hipError_t launch_shard_partials(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
-                                 uint32_t n_apps, const gf_app* d_apps, gf_shard_partial* d_out, const PeerPtrs& dsts,
-                                 hipStream_t stream, const ShardZones* zones) {
-    if (n_apps == 0 || set.n == 0) return hipSuccess;
-    const dim3 block(kWave * kWavesPerBlock);
-    if (zones != nullptr) {
-        if (!shard_zones_ok(zones)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(shard_partials_zoned_kernel, shard_grid(n_apps, set, *zones), block, 0, stream, table, gpu_view, set, *zones,
-                           n_apps, d_apps, d_out, dsts);
-        return hipGetLastError();
-    }
-    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
-        hipLaunchKernelGGL(shard_partials_kernel<A>, shard_grid(n_apps, set), block, 0, stream, table, gpu_view, set, n_apps, d_apps,
-                           d_out, dsts);
-        return hipGetLastError();
-    });
+// ---- node-range sharding (gangfit_shard.inc): four steps, each given the packer and one ShardBatch
+// (grid y = hosted shard, grid z = candidate view)
+inline dim3 shard_grid(const ShardBatch& b) { return dim3(app_grid(b.n_apps).x, b.set.n, b.zones.n_cand); }
+// The views are what the family's kernels index: the one plain view without zones (never for the zoned family), else 1 to 64 of
+// them, the plain order behind the zones only for az-aware-tightly-pack.
+inline bool shard_zones_ok(ShardFamily family, const ShardBatch& b) {
+    const ShardZones& z = b.zones;
+    if (!b.has_zones) return family != ShardFamily::zoned && z.n_zones == 0 && z.n_cand == 1;
+    return family != ShardFamily::plain && z.n_cand >= 1 && z.n_cand <= 64 && z.n_zones + (z.az_aware ? 1u : 0u) == z.n_cand &&
+           (family != ShardFamily::minfrag || z.az_aware == 0u);
 }
 
-hipError_t launch_shard_drivers(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
-                                const gf_shard_partial* d_all_partials, gf_shard_driver* d_out, const PeerPtrs& dsts,
-                                hipStream_t stream, const ShardZones* zones) {
-    if (n_apps == 0 || set.n == 0) return hipSuccess;
-    if (zones != nullptr) {
-        if (!shard_zones_ok(zones)) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(shard_drivers_zoned_kernel, shard_grid(n_apps, set, *zones), dim3(kWave * kWavesPerBlock), 0, stream, table,
-                           set, *zones, n_apps, d_apps, d_all_partials, d_out, dsts);
-    } else {
-        hipLaunchKernelGGL(shard_drivers_kernel, shard_grid(n_apps, set), dim3(kWave * kWavesPerBlock), 0, stream, table, set,
-                           n_apps, d_apps, d_all_partials, d_out, dsts);
+hipError_t launch_shard_first(gf_algo algo, const ShardBatch& b) {
+    if (b.n_apps == 0 || b.set.n == 0) return hipSuccess;
+    const std::optional<ShardFamily> family = shard_family_of(algo);
+    if (!family || !shard_zones_ok(*family, b)) return hipErrorInvalidValue;
+    const dim3 grid = shard_grid(b), block(kWave * kWavesPerBlock);
+    switch (*family) {
+        case ShardFamily::plain:
+            return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
+                hipLaunchKernelGGL(shard_partials_kernel<A>, grid, block, 0, b.stream, b.table, b.gpu_view, b.set, b.n_apps, b.d_apps,
+                                   b.d_part, b.part_dsts);
+                return hipGetLastError();
+            });
+        case ShardFamily::zoned:
+            hipLaunchKernelGGL(shard_partials_zoned_kernel, grid, block, 0, b.stream, b.table, b.gpu_view, b.set, b.zones, b.n_apps,
+                               b.d_apps, b.d_part, b.part_dsts);
+            break;
+        case ShardFamily::minfrag:
+            hipLaunchKernelGGL(shard_mf_counts_kernel, grid, block, 0, b.stream, b.table, b.set, b.zones, b.n_apps, b.d_apps, b.d_part,
+                               b.d_counts, b.part_dsts, b.count_dsts);
+            break;
     }
     return hipGetLastError();
 }
 
-hipError_t launch_shard_emit(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, const ShardSet& set,
-                             uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
-                             const gf_shard_driver* d_all_drivers, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
-                             hipStream_t stream, const ShardZones* zones) {
-    if (n_apps == 0 || set.n == 0) return hipSuccess;
-    if (zones != nullptr && !shard_zones_ok(zones)) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(d_exec2, 0, (zones != nullptr ? zones->n_cand : 2u) * half * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-    const dim3 block(kWave * kWavesPerBlock);
-    if (zones != nullptr) {
-        hipLaunchKernelGGL(shard_emit_zoned_kernel, shard_grid(n_apps, set, *zones), block, 0, stream, table, gpu_view, set, *zones,
-                           n_apps, d_apps, d_all_partials, d_all_drivers, d_exec2, half);
-        return hipGetLastError();
-    }
-    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
-        hipLaunchKernelGGL(shard_emit_kernel<A>, shard_grid(n_apps, set), block, 0, stream, table, gpu_view, set, n_apps, d_apps,
-                           d_all_partials, d_all_drivers, d_results, d_exec2, half);
-        return hipGetLastError();
-    });
+hipError_t launch_shard_drivers(gf_algo algo, const ShardBatch& b) {
+    if (b.n_apps == 0 || b.set.n == 0) return hipSuccess;
+    const std::optional<ShardFamily> family = shard_family_of(algo);
+    if (!family || !shard_zones_ok(*family, b)) return hipErrorInvalidValue;
+    const dim3 grid = shard_grid(b), block(kWave * kWavesPerBlock);
+    if (b.has_zones)  // (the same search in every family: per view, or over the plain order)
+        hipLaunchKernelGGL(shard_drivers_zoned_kernel, grid, block, 0, b.stream, b.table, b.set, b.zones, b.n_apps, b.d_apps,
+                           b.d_all_part, b.d_drv, b.drv_dsts);
+    else
+        hipLaunchKernelGGL(shard_drivers_kernel, grid, block, 0, b.stream, b.table, b.set, b.n_apps, b.d_apps, b.d_all_part, b.d_drv,
+                           b.drv_dsts);
+    return hipGetLastError();
 }
 
-hipError_t launch_shard_finish(gf_algo algo, uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps,
-                               const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
-                               gf_result* d_results, uint32_t* d_exec2, uint64_t half, hipStream_t stream,
-                               const NodeTable* table, const ShardZones* zones) {
-    if (n_apps == 0) return hipSuccess;
-    if (zones != nullptr) {
-        if (table == nullptr || !shard_zones_ok(zones)) return hipErrorInvalidValue;
-        return with_value<true, false>(zones->az_aware != 0, [&](auto AZ) {
-            hipLaunchKernelGGL(shard_finish_zoned_kernel<AZ>, dim3(n_apps), dim3(kWave * kFusedWaves), 0, stream, *table, *zones,
-                               n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
+hipError_t launch_shard_emit(gf_algo algo, const ShardBatch& b) {
+    if (b.n_apps == 0 || b.set.n == 0) return hipSuccess;
+    const std::optional<ShardFamily> family = shard_family_of(algo);
+    if (!family || !shard_zones_ok(*family, b)) return hipErrorInvalidValue;
+    // plain: [0, half) the placements, [half, 2 half) distribute-evenly's capacities; else region c = view c's placement
+    const uint64_t regions = *family == ShardFamily::plain ? 2u : b.zones.n_cand;
+    const hipError_t e = hipMemsetAsync(b.d_exec2, 0, regions * b.half * sizeof(uint32_t), b.stream);
+    if (e != hipSuccess) return e;
+    const dim3 grid = shard_grid(b), block(kWave * kWavesPerBlock);
+    switch (*family) {
+        case ShardFamily::plain:
+            return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
+                hipLaunchKernelGGL(shard_emit_kernel<A>, grid, block, 0, b.stream, b.table, b.gpu_view, b.set, b.n_apps, b.d_apps,
+                                   b.d_all_part, b.d_all_drv, b.d_results, b.d_exec2, b.half);
+                return hipGetLastError();
+            });
+        case ShardFamily::zoned:
+            hipLaunchKernelGGL(shard_emit_zoned_kernel, grid, block, 0, b.stream, b.table, b.gpu_view, b.set, b.zones, b.n_apps, b.d_apps,
+                               b.d_all_part, b.d_all_drv, b.d_exec2, b.half);
             return hipGetLastError();
-        });
+        case ShardFamily::minfrag:
+            return with_value<true, false>(b.has_zones, [&](auto Z) {
+                hipLaunchKernelGGL(shard_mf_emit_kernel<Z>, grid, block, 0, b.stream, b.table, b.set, b.zones, b.n_apps, b.d_apps,
+                                   b.d_all_part, b.d_all_drv, b.d_all_counts, b.d_results, b.d_exec2, b.half);
+                return hipGetLastError();
+            });
     }
-    return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, [&](auto A) {
-        hipLaunchKernelGGL(shard_finish_kernel<A>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, n_shards, n_apps,
-                           d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_shard_finish(gf_algo algo, const ShardBatch& b) {
+    if (b.n_apps == 0) return hipSuccess;
+    const std::optional<ShardFamily> family = shard_family_of(algo);
+    if (!family || !shard_zones_ok(*family, b)) return hipErrorInvalidValue;
+    // without zone views: node + 1 -> node (and distribute-evenly's later passes); minimal-fragmentation takes tightly-pack's
+    auto plain = [&](auto A) {
+        hipLaunchKernelGGL(shard_finish_kernel<A>, app_grid(b.n_apps), dim3(kWave * kWavesPerBlock), 0, b.stream, b.n_shards, b.n_apps,
+                           b.d_apps, b.d_all_part, b.d_all_drv, b.d_results, b.d_exec2, b.half);
         return hipGetLastError();
-    });
-}
-
-// ---- the minimal-fragmentation packers on the shard steps (zones == nullptr: the plain packer, one view)
-inline dim3 shard_mf_grid(uint32_t n_apps, const ShardSet& set, const ShardZones* z) {
-    return dim3(app_grid(n_apps).x, set.n, z != nullptr ? z->n_cand : 1u);
-}
-inline bool shard_mf_zones_ok(const ShardZones* z) { return z == nullptr || (shard_zones_ok(z) && z->az_aware == 0u); }
-
-hipError_t launch_shard_mf_counts(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
-                                  gf_shard_partial* d_part, uint32_t* d_counts, const PeerPtrs& part_dsts, const PeerPtrs& count_dsts,
-                                  hipStream_t stream, const ShardZones* zones) {
-    if (n_apps == 0 || set.n == 0) return hipSuccess;
-    if (!shard_mf_zones_ok(zones)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(shard_mf_counts_kernel, shard_mf_grid(n_apps, set, zones), dim3(kWave * kWavesPerBlock), 0, stream, table, set,
-                       zones != nullptr ? *zones : ShardZones{}, n_apps, d_apps, d_part, d_counts, part_dsts, count_dsts);
-    return hipGetLastError();
-}
-
-hipError_t launch_shard_mf_emit(const NodeTable& table, const ShardSet& set, uint32_t n_apps, const gf_app* d_apps,
-                                const gf_shard_partial* d_all_partials, const gf_shard_driver* d_all_drivers,
-                                const uint32_t* d_all_counts, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
-                                hipStream_t stream, const ShardZones* zones) {
-    if (n_apps == 0 || set.n == 0) return hipSuccess;
-    if (!shard_mf_zones_ok(zones)) return hipErrorInvalidValue;
-    hipError_t e = hipMemsetAsync(d_exec2, 0, (zones != nullptr ? zones->n_cand : 1u) * half * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-    return with_value<true, false>(zones != nullptr, [&](auto Z) {
-        hipLaunchKernelGGL(shard_mf_emit_kernel<Z>, shard_mf_grid(n_apps, set, zones), dim3(kWave * kWavesPerBlock), 0, stream, table,
-                           set, zones != nullptr ? *zones : ShardZones{}, n_apps, d_apps, d_all_partials, d_all_drivers, d_all_counts,
-                           d_results, d_exec2, half);
+    };
+    // with them: a workgroup per application chooses between the views, by the averages of the packer that placed them
+    auto zoned = [&](auto AZ, auto INNER) {
+        hipLaunchKernelGGL((shard_finish_zoned_kernel<AZ, INNER>), dim3(b.n_apps), dim3(kWave * kFusedWaves), 0, b.stream, b.table, b.zones,
+                           b.n_shards, b.n_apps, b.d_apps, b.d_all_part, b.d_all_drv, b.d_results, b.d_exec2, b.half);
         return hipGetLastError();
-    });
-}
-
-hipError_t launch_shard_mf_finish(uint32_t n_shards, uint32_t n_apps, const gf_app* d_apps, const gf_shard_partial* d_all_partials,
-                                  const gf_shard_driver* d_all_drivers, gf_result* d_results, uint32_t* d_exec2, uint64_t half,
-                                  hipStream_t stream, const NodeTable& table, const ShardZones* zones) {
-    if (n_apps == 0) return hipSuccess;
-    if (!shard_mf_zones_ok(zones)) return hipErrorInvalidValue;
-    if (zones != nullptr)
-        hipLaunchKernelGGL((shard_finish_zoned_kernel<false, GF_ALGO_MINIMAL_FRAGMENTATION>), dim3(n_apps), dim3(kWave * kFusedWaves), 0,
-                           stream, table, *zones, n_shards, n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
-    else  // node + 1 -> node: tightly-pack's finish
-        hipLaunchKernelGGL(shard_finish_kernel<GF_ALGO_TIGHTLY_PACK>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, n_shards,
-                           n_apps, d_apps, d_all_partials, d_all_drivers, d_results, d_exec2, half);
-    return hipGetLastError();
+    };
+    using Tight = std::integral_constant<int, GF_ALGO_TIGHTLY_PACK>;
+    using Minfrag = std::integral_constant<int, GF_ALGO_MINIMAL_FRAGMENTATION>;
+    switch (*family) {
+        case ShardFamily::plain: return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY>(algo, plain);
+        case ShardFamily::zoned: return with_value<true, false>(b.zones.az_aware != 0, [&](auto AZ) { return zoned(AZ, Tight{}); });
+        case ShardFamily::minfrag: return b.has_zones ? zoned(std::false_type{}, Minfrag{}) : plain(Tight{});
+    }
+    return hipErrorInvalidValue;
 }
 
 __global__ __launch_bounds__(256) void narrow_rescale_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst,

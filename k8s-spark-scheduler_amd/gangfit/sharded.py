@@ -20,9 +20,13 @@ the placement buffer the all-reduce sums, comes from the library (gf_shard_layou
 
 The minimal-fragmentation packers (minimal-fragmentation, single-az-minimal-fragmentation) walk the whole executor order for
 every application — "the smallest capacity >= K" is a minimum over every candidate —, so theirs is the walk that divides by the
-number of shards.  They are a family of steps of their own (gf_shard_mf_*, ShardedMinfragBatch, sharded_fit_minfrag): the first
-exchange carries, next to the 16-byte records, a row of capacity counts per application and view (512 B), from which every
-rank makes the same plan and emits its own range's runs.  Still three exchanges per batch.
+number of shards.  Their first exchange carries, next to the 16-byte records, a row of capacity counts per application and
+view (512 B), from which every rank makes the same plan and emits its own range's runs: the C ABI has entry points of their own
+for that (gf_shard_mf_*; ShardedMinfragBatch, sharded_fit_minfrag).  Still three exchanges per batch.
+
+Both batches are one class (_Batch: the records' offsets, the upload, `step`, `step_timed`, `fetch`); ShardedBatch and
+ShardedMinfragBatch add the packers they serve, their layout query and their four steps.  Below the C ABI it is the same
+shape: every step receives one record (ShardBatch, csrc/gangfit_device.h) and picks its kernel by the packer's family.
 
 This file is orchestration only: no arithmetic on placements happens in Python, and there is no CPU fallback —
 `HipShardEngine` raises when libgangfit or the GPU is missing.  `Comm`/engine are small interfaces so that the N > 1 control
@@ -264,76 +268,45 @@ class HipShardEngine:
 
 
 # ------------------------------------------------------------------------------------------------ orchestration
-SHARDED_ALGOS = (N.GF_ALGO_TIGHTLY_PACK, N.GF_ALGO_DISTRIBUTE_EVENLY, N.GF_ALGO_SINGLE_AZ_TIGHTLY_PACK,
-                 N.GF_ALGO_AZ_AWARE_TIGHTLY_PACK)
+class _Batch:
+    """One pending-app table prepared for repeated sharded evaluation (bench.py times `step`).  A family of packers adds which
+    ones it serves (ALGOS, REFUSAL), its layout query (_layout: records, reduce_words and what its steps need besides) and its
+    steps (_steps(mark): the four device steps and the three exchanges, mark(2 i) before and mark(2 i + 1) behind exchange i)."""
 
-
-class ShardedBatch:
-    """One pending-app table prepared for repeated sharded evaluation (bench.py times `step`)."""
+    ALGOS: tuple = ()
+    REFUSAL = ""
 
     def __init__(self, engine, comm: Comm, algo: int, apps: np.ndarray):
-        if algo not in SHARDED_ALGOS:
-            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, "node-range sharding serves tightly-pack, distribute-evenly, "
-                                                      "single-az-tightly-pack and az-aware-tightly-pack only")
+        if algo not in self.ALGOS:
+            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, self.REFUSAL)
         self.engine, self.comm, self.algo = engine, comm, algo
         apps = np.ascontiguousarray(apps, dtype=N.APP_DTYPE)
         self.apps_off, self.total_k = with_offsets(apps)
         self.n_apps = len(apps)
         self.half = self.total_k + 1
-        # the buffers' layout from the library (HipShardEngine.layout); an engine without the query serves the plain packers, whose
-        # layout is fixed: one record per application, [0, half) placements + [half, 2 half) distribute-evenly's capacities
-        if hasattr(engine, "layout"):
-            self.records, words, self.reduce_words = engine.layout(algo, self.half)
-            self._rec_kw, self._emit_kw = {"records": self.records}, {"words": words}
-        elif algo in (N.GF_ALGO_TIGHTLY_PACK, N.GF_ALGO_DISTRIBUTE_EVENLY):
-            self.records = 1
-            self.reduce_words = 2 * self.half if algo == N.GF_ALGO_DISTRIBUTE_EVENLY else self.half
-            self._rec_kw, self._emit_kw = {}, {}
-        else:
-            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, "this shard engine serves the plain packers only")
+        self._layout()
         with engine.stream_context():
             self.d_apps = engine.upload_apps(self.apps_off)
         self.res = self.exec2 = None
 
     def _placements(self):
         """What the all-reduce carries: the leading reduce_words of the buffer — tightly-pack's placements, distribute-evenly's
-        placements and pass-1 capacities, or every candidate view's placement region of a zone-aware packer."""
+        placements and pass-1 capacities, or every candidate view's placement region."""
         return self.exec2 if self.reduce_words >= len(self.exec2) else self.exec2[: self.reduce_words]
 
     def step(self):
-        e, c, algo, n = self.engine, self.comm, self.algo, self.n_apps
-        with e.stream_context():
-            part = e.partials(algo, self.d_apps, n, **self._rec_kw)
-            all_part = c.all_gather(part)
-            drv = e.drivers(algo, self.d_apps, n, all_part, **self._rec_kw)
-            all_drv = c.all_gather(drv)
-            self.res, self.exec2 = e.emit(algo, self.d_apps, n, all_part, all_drv, self.half, **self._emit_kw)
-            c.all_reduce_sum_(self._placements())
-            e.finish(algo, self.d_apps, n, all_part, all_drv, self.res, self.exec2, self.half)
+        self._steps(lambda i: None)
 
     def step_timed(self):
         """step(), with a pair of events on the engine's stream around each of the three exchanges (GPU engines only).  Returns
-        [all-gather of the partials, all-gather of the drivers, all-reduce of the placements] in microseconds of device time —
-        what the data-path collectives of one batch cost (bench.py: config.node_sharded.exchange_us)."""
+        [first all-gather (the partials, or the records and count rows), all-gather of the drivers, all-reduce of the placements]
+        in microseconds of device time — what the data-path collectives of one batch cost (bench.py:
+        config.node_sharded.exchange_us)."""
         import torch
 
-        e, c, algo, n = self.engine, self.comm, self.algo, self.n_apps
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
-        with e.stream_context():
-            part = e.partials(algo, self.d_apps, n, **self._rec_kw)
-            ev[0].record(e.stream)
-            all_part = c.all_gather(part)
-            ev[1].record(e.stream)
-            drv = e.drivers(algo, self.d_apps, n, all_part, **self._rec_kw)
-            ev[2].record(e.stream)
-            all_drv = c.all_gather(drv)
-            ev[3].record(e.stream)
-            self.res, self.exec2 = e.emit(algo, self.d_apps, n, all_part, all_drv, self.half, **self._emit_kw)
-            ev[4].record(e.stream)
-            c.all_reduce_sum_(self._placements())
-            ev[5].record(e.stream)
-            e.finish(algo, self.d_apps, n, all_part, all_drv, self.res, self.exec2, self.half)
-        e.stream.synchronize()
+        self._steps(lambda i: ev[i].record(self.engine.stream))
+        self.engine.stream.synchronize()
         return [ev[2 * i].elapsed_time(ev[2 * i + 1]) * 1e3 for i in range(3)]
 
     def fetch(self) -> BatchOut:
@@ -343,6 +316,49 @@ class ShardedBatch:
         return BatchOut(res, self.apps_off["exec_off"].copy(), ex, -1)
 
 
+SHARDED_ALGOS = (N.GF_ALGO_TIGHTLY_PACK, N.GF_ALGO_DISTRIBUTE_EVENLY, N.GF_ALGO_SINGLE_AZ_TIGHTLY_PACK,
+                 N.GF_ALGO_AZ_AWARE_TIGHTLY_PACK)
+
+
+class ShardedBatch(_Batch):
+    """The plain and the zone-aware tightly-pack packers: partials -> all-gather -> drivers -> all-gather -> emit ->
+    all-reduce(SUM) of the placement buffer -> finish."""
+
+    ALGOS = SHARDED_ALGOS
+    REFUSAL = ("node-range sharding serves tightly-pack, distribute-evenly, single-az-tightly-pack and az-aware-tightly-pack "
+               "only")
+
+    def _layout(self):
+        # from the library (HipShardEngine.layout); an engine without the query serves the plain packers, whose layout is
+        # fixed: one record per application, [0, half) placements + [half, 2 half) distribute-evenly's capacities
+        if hasattr(self.engine, "layout"):
+            self.records, words, self.reduce_words = self.engine.layout(self.algo, self.half)
+            self._rec_kw, self._emit_kw = {"records": self.records}, {"words": words}
+        elif self.algo in (N.GF_ALGO_TIGHTLY_PACK, N.GF_ALGO_DISTRIBUTE_EVENLY):
+            self.records = 1
+            self.reduce_words = 2 * self.half if self.algo == N.GF_ALGO_DISTRIBUTE_EVENLY else self.half
+            self._rec_kw, self._emit_kw = {}, {}
+        else:
+            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, "this shard engine serves the plain packers only")
+
+    def _steps(self, mark):
+        e, c, algo, n = self.engine, self.comm, self.algo, self.n_apps
+        with e.stream_context():
+            part = e.partials(algo, self.d_apps, n, **self._rec_kw)
+            mark(0)
+            all_part = c.all_gather(part)
+            mark(1)
+            drv = e.drivers(algo, self.d_apps, n, all_part, **self._rec_kw)
+            mark(2)
+            all_drv = c.all_gather(drv)
+            mark(3)
+            self.res, self.exec2 = e.emit(algo, self.d_apps, n, all_part, all_drv, self.half, **self._emit_kw)
+            mark(4)
+            c.all_reduce_sum_(self._placements())
+            mark(5)
+            e.finish(algo, self.d_apps, n, all_part, all_drv, self.res, self.exec2, self.half)
+
+
 def sharded_fit(engine, comm: Comm, algo: int, apps: np.ndarray) -> BatchOut:
     """gf_fit_batch(GF_MODE_INDEPENDENT) with the node table sharded by priority-order range over comm.world GPUs."""
     b = ShardedBatch(engine, comm, algo, apps)
@@ -350,34 +366,22 @@ def sharded_fit(engine, comm: Comm, algo: int, apps: np.ndarray) -> BatchOut:
     return b.fetch()
 
 
-# ------------------------------------------------------------------------------------------------ minimal-fragmentation
 MINFRAG_ALGOS = (N.GF_ALGO_MINIMAL_FRAGMENTATION, N.GF_ALGO_SINGLE_AZ_MINIMAL_FRAGMENTATION)
 
 
-class ShardedMinfragBatch:
-    """ShardedBatch for the minimal-fragmentation packers: counts -> all-gather (records and count rows, one buffer) -> drivers
-    -> all-gather -> emit -> all-reduce(SUM) of the placement buffer -> finish."""
+class ShardedMinfragBatch(_Batch):
+    """The minimal-fragmentation packers: counts -> all-gather (records and count rows, one buffer) -> drivers -> all-gather ->
+    emit -> all-reduce(SUM) of the placement buffer -> finish."""
 
-    def __init__(self, engine, comm: Comm, algo: int, apps: np.ndarray):
-        if algo not in MINFRAG_ALGOS:
-            raise N.GangfitError(N.GF_ERR_UNSUPPORTED, "the minimal-fragmentation shard steps serve minimal-fragmentation and "
-                                                      "single-az-minimal-fragmentation only")
-        self.engine, self.comm, self.algo = engine, comm, algo
-        apps = np.ascontiguousarray(apps, dtype=N.APP_DTYPE)
-        self.apps_off, self.total_k = with_offsets(apps)
-        self.n_apps = len(apps)
-        self.half = self.total_k + 1
-        self.records, self.row_bytes, self.words, self.reduce_words = engine.mf_layout(algo, self.half)
-        with engine.stream_context():
-            self.d_apps = engine.upload_apps(self.apps_off)
-        self.res = self.exec2 = None
+    ALGOS = MINFRAG_ALGOS
+    REFUSAL = "the minimal-fragmentation shard steps serve minimal-fragmentation and single-az-minimal-fragmentation only"
+
+    def _layout(self):
+        self.records, self.row_bytes, self.words, self.reduce_words = self.engine.mf_layout(self.algo, self.half)
 
     def first_exchange_bytes_per_app(self) -> int:
         """What one rank contributes to the first all-gather per application (every view's record and count row)."""
         return self.records * (16 + self.row_bytes)
-
-    def _placements(self):
-        return self.exec2 if self.reduce_words >= len(self.exec2) else self.exec2[: self.reduce_words]
 
     def _steps(self, mark):
         e, c, algo, n, rec = self.engine, self.comm, self.algo, self.n_apps, self.records
@@ -396,25 +400,6 @@ class ShardedMinfragBatch:
             c.all_reduce_sum_(self._placements())
             mark(5)
             e.mf_finish(algo, self.d_apps, n, all_part, all_drv, self.res, self.exec2, self.half)
-
-    def step(self):
-        self._steps(lambda i: None)
-
-    def step_timed(self):
-        """step(), with a pair of events on the engine's stream around each of the three exchanges (GPU engines only).  Returns
-        [all-gather of the records and count rows, all-gather of the drivers, all-reduce of the placements] in microseconds."""
-        import torch
-
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
-        self._steps(lambda i: ev[i].record(self.engine.stream))
-        self.engine.stream.synchronize()
-        return [ev[2 * i].elapsed_time(ev[2 * i + 1]) * 1e3 for i in range(3)]
-
-    def fetch(self) -> BatchOut:
-        with self.engine.stream_context():
-            res = self.res.cpu().numpy().view(N.RESULT_DTYPE).copy()
-            ex = self.exec2[: self.total_k].cpu().numpy().view(np.uint32).copy()
-        return BatchOut(res, self.apps_off["exec_off"].copy(), ex, -1)
 
 
 def sharded_fit_minfrag(engine, comm: Comm, algo: int, apps: np.ndarray) -> BatchOut:

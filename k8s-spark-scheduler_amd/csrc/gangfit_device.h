@@ -201,6 +201,20 @@ struct WorkerArgs {
     uint32_t pad_stride;
 };
 
+// The argument segment of fit_worker_kernel(NodeTable, SparseTable, WorkerArgs) as the kernel itself reads it back: the three
+// arguments lie in it one behind the other (each is a multiple of eight bytes, aligned to eight), so a pointer to the segment
+// is a pointer to this record.  The tightly-pack worker reads operands that its narrow decision seldom touches from here, with
+// scalar loads at the point of use (gangfit_worker.inc, OPERANDS), instead of holding them in registers across its round loop.
+struct WorkerKernargs {
+    NodeTable T;
+    SparseTable G;
+    WorkerArgs W;
+};
+static_assert(sizeof(NodeTable) % 8 == 0 && sizeof(SparseTable) % 8 == 0 && sizeof(WorkerArgs) % 8 == 0 && alignof(NodeTable) == 8 &&
+                  alignof(SparseTable) == 8 && alignof(WorkerArgs) == 8 &&
+                  sizeof(WorkerKernargs) == sizeof(NodeTable) + sizeof(SparseTable) + sizeof(WorkerArgs),
+              "WorkerKernargs must mirror the kernel's argument segment");
+
 // tightly-pack, distribute-evenly, minimal-fragmentation, single-az-tightly-pack, az-aware-tightly-pack
 hipError_t worker_blocks_per_cu(gf_algo algo, int* out);
 // One launch: 1 + sets * blocks_per_set workgroups of sixteen wavefronts.

@@ -203,22 +203,51 @@ struct GlobalView {
     }
 };
 
+// The argument segment of fit_worker_kernel as a record in the constant address space (WorkerKernargs, gangfit_device.h).  The
+// empty asm makes the pointer a new value where it stands: the scalar loads through it are issued THERE — inside the rare branch
+// that wants the operand — and can neither be hoisted to the kernel's entry nor be kept in a register (that is: in a lane of a
+// spill VGPR) across the worker's round loop.  Reads only; the segment lives as long as the launch.  Worker kernel only.
+typedef __attribute__((address_space(4))) const WorkerKernargs worker_kernargs_t;
+__device__ __forceinline__ worker_kernargs_t* worker_kernargs_here() {
+    worker_kernargs_t* p = (worker_kernargs_t*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+// What a view that reads the segment asks of whoever builds it: an object only fit_worker_kernel creates (nothing else in the
+// library names the type), so the dependency on that kernel's argument layout stands at the construction site.
+struct InWorkerKernel {
+    explicit constexpr InWorkerKernel() = default;
+};
+
 // The snapshot's scaled int32 twin (NodeTable::ncpu / nmem / ngpu) behind the same interface: twelve bytes per slot, 32-bit
 // compares.  Read-only (the resident worker's tightly-pack decisions; gangfit_worker.inc).  The chunk maxima stay the wide ones:
-// group 0 of the index is scaled once per launch by its user (Group0T<int32_t>), the chunks behind it — rare on that path — are
-// compared in int64 against the request scaled back up.
+// group 0 of the index is scaled once per launch by its user (Group0T<int32_t>); a chunk that is asked on its own (chunk_may_hold)
+// is compared in int64 against the request scaled back up.
 struct NarrowView {
     const int32_t* cpu;
     const int32_t* mem;
     const int32_t* gpu;
-    const int64_t* cmax_cpu;
-    const int64_t* cmax_mem;
-    const int64_t* cmax_gpu;
     const uint64_t* xm;
     const uint64_t* dm;
     uint32_t n_chunks;
-    int64_t unit0, unit1, unit2;
     static constexpr bool kCompactScan = true;
+    // ONLY inside fit_worker_kernel (wide_here reads THAT kernel's argument segment): the constructor wants the kernel's token.
+    __device__ __forceinline__ NarrowView(const InWorkerKernel&, const int32_t* cpu_, const int32_t* mem_, const int32_t* gpu_,
+                                          const uint64_t* xm_, const uint64_t* dm_, uint32_t n_chunks_)
+        : cpu(cpu_), mem(mem_), gpu(gpu_), xm(xm_), dm(dm_), n_chunks(n_chunks_) {}
+    // The wide maxima and the units are no members (eight scalar registers held through every decision) but read from the worker's
+    // argument segment where a chunk asks for them (NodeTable::cmax: [3][n_chunks]).  Not cold, only less often read than the
+    // columns: chunk_may_hold runs for the chunks behind group 0 (the headline's 157 chunks are three groups, so that is every
+    // application there) and, inside group 0 too, on the general layout (wave_pack without the pre-computed mask), in wave_fallback
+    // and in wave_first_fitting_driver behind a stale maximum.  What is saved is carrying them through the rest of the decision.
+    struct Wide {
+        const int64_t* cmax;
+        int64_t unit0, unit1, unit2;
+    };
+    static __device__ __forceinline__ Wide wide_here() {
+        worker_kernargs_t* K = worker_kernargs_here();
+        return Wide{K->T.cmax, K->T.nunit[0], K->T.nunit[1], K->T.nunit[2]};
+    }
     // an upper bound of the chunk's scaled maxima: ceil(m / unit), kept inside (-2^31, 2^31) (a table with this form has no real
     // value at or past 2^30 units; the sentinel's maximum is far below every request)
     static __device__ __forceinline__ int32_t scale_max(int64_t m, int64_t unit) {
@@ -226,13 +255,15 @@ struct NarrowView {
         return (int32_t)(q < -(INT64_C(1) << 30) ? -(INT64_C(1) << 30) : (q > (INT64_C(1) << 30) ? (INT64_C(1) << 30) : q));
     }
     __device__ __forceinline__ void chunk_maxima(uint32_t c, int32_t& m0, int32_t& m1, int32_t& m2) const {
-        m0 = scale_max(cmax_cpu[c], unit0);
-        m1 = scale_max(cmax_mem[c], unit1);
-        m2 = scale_max(cmax_gpu[c], unit2);
+        const Wide w = wide_here();
+        m0 = scale_max(w.cmax[c], w.unit0);
+        m1 = scale_max(w.cmax[c + n_chunks], w.unit1);
+        m2 = scale_max(w.cmax[c + 2 * (size_t)n_chunks], w.unit2);
     }
     __device__ __forceinline__ bool chunk_may_hold(uint32_t c, int32_t r0, int32_t r1, int32_t r2) const {
-        const int64_t m0 = cmax_cpu[c], m1 = cmax_mem[c], m2 = cmax_gpu[c];
-        return (bool)((m0 >= (int64_t)r0 * unit0) & (m1 >= (int64_t)r1 * unit1) & (m2 >= (int64_t)r2 * unit2));
+        const Wide w = wide_here();
+        const int64_t m0 = w.cmax[c], m1 = w.cmax[c + n_chunks], m2 = w.cmax[c + 2 * (size_t)n_chunks];
+        return (bool)((m0 >= (int64_t)r0 * w.unit0) & (m1 >= (int64_t)r1 * w.unit1) & (m2 >= (int64_t)r2 * w.unit2));
     }
     __device__ __forceinline__ uint64_t chunk_xmask(uint32_t c) const { return xm[c]; }
     __device__ __forceinline__ uint64_t chunk_dmask(uint32_t c) const { return dm[c]; }

@@ -69,6 +69,28 @@
 // instructions per ticket and 994 M decisions/s against 728.8 k and 1 007 M without: more spilled scalar registers than it saves
 // vector compares.
 
+// OPERANDS (profiles/r9a_worker_operands_summary.md): where the launch constants of the tightly-pack instance live.  The instance keeps
+// more wave-uniform values alive across its round loop than there are scalar registers; the compiler parks the surplus in lanes of
+// spill VGPRs and fetches it back with v_readlane — a VECTOR instruction, on the pipe the kernel is bound by (tools/worker_spills.py
+// lists them per basic block).  Two groups of operands that the narrow decision carried through its whole body and seldom reads are
+// therefore not held at all but read from the kernel's own argument segment with scalar loads where they are used
+// (worker_kernargs_here, gangfit_kernels.hip; the segment lives as long as the launch):
+//   argument segment, at use   the wide chunk maxima and the three units of the NARROW view (NarrowView::wide_here: three row pointers
+//                              and three 64-bit units before) — read by chunk_may_hold / chunk_maxima, that is for the chunks behind
+//                              group 0 (every application of a 10 000-node cluster gets there), and inside group 0 on the general
+//                              layout, in the fallback and behind a stale maximum: less often read than the columns, not cold;
+//                              the sparse view's size, asked only for a gang of gpu executors (sparse_serves)
+//   registers                  everything else: the narrow columns, xmask, dmask, n_chunks, slot_node, dslot, n_x, n_d, dev, sets,
+//                              leave_after, blocks_per_set, the stride constants, stats, and the operands of the int64 decision,
+//                              the sparse table, scratch, host, generation
+// Measured on this code, parent and result alternately on one machine, seven runs each: spilled scalar registers 171 -> 112,
+// v_readlane on spill lanes inside the loop 510 -> 284; 724.9 k -> 696.5 k instructions per ticket at K = 2 000 (vector -17.6 k,
+// scalar -13.6 k, scalar-memory +2.8 k); 1 000-1 016 M -> 1 029-1 045 M decisions/s (medians +3.1 %, ranges apart); a window of
+// twenty: 404-428 M -> 431-440 M (no loss).
+// Measured and dropped: reading the int64 decision's operands (wide columns, SparseTable, scratch, host, generation) at their use
+// as well — that variant had 145 spilled registers and 437 in-loop spill reads, 3.8 k vector and 2.3 k scalar instructions per
+// ticket more than the same code without that part, and was no faster; on its own it was 1.2 % slower than the parent.
+
 __device__ __forceinline__ unsigned long long sys_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -296,8 +318,8 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             }
         }
     }
-    const NarrowView VN{T.ncpu, T.nmem, T.ngpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, T.xmask, T.dmask,
-                        T.n_chunks, T.nunit[0], T.nunit[1], T.nunit[2]};
+    // (the wide maxima and the units are no members of the narrow view: OPERANDS above)
+    const NarrowView VN(InWorkerKernel{}, T.ncpu, T.nmem, T.ngpu, T.xmask, T.dmask, T.n_chunks);
     // lane l < 6 scales request word l of a record: dimension l mod 3
     const int64_t unit_l = T.nunit[lane % 3 == 0 ? 0 : (lane % 3 == 1 ? 1 : 2)];
     const double rcp_l = kNarrow ? fast_rcp((double)unit_l) : 0.0;
@@ -481,8 +503,11 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             if constexpr (kNarrow) {
                 NarrowApp napp;
                 // (gangs of gpu executors are packed from the compact table of gpu nodes: wave_decide's `sparse`, int64 only)
+                // (asked in this order, the sparse view's size is wanted only for a gang of gpu executors — and read there, from the
+                //  argument segment: OPERANDS)
+                auto sparse_serves = [&]() { return worker_kernargs_here()->G.n_x != 0u && O.d_identity; };
                 if (narrow_table && scale_record(wrec, lane, unit_l, rcp_l, napp) &&
-                    !(G.n_x != 0u && napp.exe2 > 0 && napp.k > 0 && T.d_identity != 0)) {
+                    !(napp.exe2 > 0 && napp.k > 0 && sparse_serves())) {
                     Group0T<int32_t> g0n = g0n_regs;
                     if constexpr (!kG0Regs) {
                         g0n.m0 = s_g0n[0][lane];

@@ -626,23 +626,30 @@ void chain_batch_tail(gf_ctx* ctx, gangfit::ChainBatch* b) {
     b->d_stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr;
 }
 
-// Independent batches: every application against the snapshot.
+// Independent batches: every application against the snapshot.  The FitBatch of n_apps records and their answers on the context's
+// tables and buffers as they stand — of a FitCall's queue, or (gf_fit_feasible, which then puts its own buffers in) of records alone.
+gangfit::FitBatch fit_batch_of(gf_ctx* ctx, const Route& r, uint32_t n_apps, const gf_app* d_apps, gf_result* d_results,
+                               uint32_t* d_exec_nodes, uint64_t half, hipStream_t stream) {
+    return gangfit::FitBatch{.table = make_table(ctx, ctx->d_snap.ptr), .gpu_view = make_sparse(ctx),
+                             .zones = r.zoned ? zone_table(ctx) : gangfit::ZoneTable{nullptr, nullptr, 0, 0},
+                             .d_sched = r.zoned ? ctx->d_sched.ptr : nullptr, .n_apps = n_apps, .d_apps = d_apps, .d_results = d_results,
+                             .d_exec_nodes = d_exec_nodes, .d_scratch = ctx->d_scratch.ptr, .half = half, .d_zexec = ctx->d_zexec.ptr,
+                             .d_stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr, .stream = stream};
+}
+gangfit::FitBatch fit_batch_of(gf_ctx* ctx, const Route& r, const FitCall& c) {
+    return fit_batch_of(ctx, r, c.q.n_apps, c.q.d_apps, c.q.d_results, c.q.d_exec_nodes, c.q.half, c.q.stream);
+}
 int launch_plain(gf_ctx* ctx, const Route& r, FitCall* call) {
     if (const int arc = apps_to_device(ctx, call); arc != GF_OK) return arc;
-    GF_HIP(ctx, gangfit::launch_fit_independent((gf_algo)r.inner, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), call->q.n_apps,
-                                                call->q.d_apps, call->q.d_results, call->q.d_exec_nodes, ctx->d_scratch.ptr,
-                                                call->q.half, ctx->stats_on ? ctx->d_stats.ptr : nullptr, call->q.stream));
+    GF_HIP(ctx, gangfit::launch_fit_independent((gf_algo)r.inner, fit_batch_of(ctx, r, *call)));
     return GF_OK;
 }
 // ... of the zone-aware packers in one launch: a workgroup per application decides every candidate view, chooses and writes the
 // final answer — d_apps / d_results / d_exec_nodes may be device-mapped host memory (gf_fit_batch)
 int launch_zoned_fused(gf_ctx* ctx, const Route& r, FitCall* call) {
-    const uint64_t half = call->q.half;
-    GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)ctx->n_zones + 1) * half));
+    GF_HIP(ctx, ctx->d_zexec.reserve(((uint64_t)ctx->n_zones + 1) * call->q.half));
     if (const int arc = apps_to_device(ctx, call); arc != GF_OK) return arc;
-    GF_HIP(ctx, gangfit::launch_fit_zoned_fused(r.inner, r.az_aware, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), zone_table(ctx),
-                                                ctx->d_sched.ptr, ctx->d_zexec.ptr, half, call->q.n_apps, call->q.d_apps, call->q.d_results,
-                                                call->q.d_exec_nodes, ctx->d_scratch.ptr, half, call->q.stream));
+    GF_HIP(ctx, gangfit::launch_fit_zoned_fused(r.inner, r.az_aware, fit_batch_of(ctx, r, *call)));
     return GF_OK;
 }
 // ... in four
@@ -654,10 +661,9 @@ int launch_zoned_four(gf_ctx* ctx, const Route& r, FitCall* call) {
     GF_HIP(ctx, ctx->d_zavg.reserve(4 * n_dec));
     if (const int rc = ensure_cnt(ctx, n_dec < 16 ? 16 : n_dec, call->q.stream); rc != GF_OK) return rc;
     if (const int arc = apps_to_device(ctx, call); arc != GF_OK) return arc;
-    const gangfit::ZoneBuffers zb{ctx->d_zres.ptr, ctx->d_zexec.ptr, half, ctx->d_zavg.ptr, ctx->d_cnt.ptr, ctx->cnt_rows};
-    GF_HIP(ctx, gangfit::launch_fit_zoned(r.inner, r.az_aware, r.inner != GF_ALGO_MINIMAL_FRAGMENTATION, make_table(ctx, ctx->d_snap.ptr),
-                                          zone_table(ctx), slot_eff_tables(ctx, ctx->d_snap.ptr), zb, call->q.n_apps, call->q.d_apps,
-                                          call->q.d_results, call->q.d_exec_nodes, ctx->d_scratch.ptr, half, call->q.stream));
+    const gangfit::ZoneBuffers zb{ctx->d_zres.ptr, ctx->d_zavg.ptr, ctx->d_cnt.ptr, ctx->cnt_rows};
+    GF_HIP(ctx, gangfit::launch_fit_zoned(r.inner, r.az_aware, r.inner != GF_ALGO_MINIMAL_FRAGMENTATION, slot_eff_tables(ctx, ctx->d_snap.ptr),
+                                          zb, fit_batch_of(ctx, r, *call)));
     return GF_OK;
 }
 
@@ -768,6 +774,15 @@ int launch(gf_ctx* ctx, const Route& r, FitCall* call) {
     return fail(ctx, GF_ERR_INVALID, "unknown kernel route %d", (int)r.kind);
 }
 
+// gf_call_phases of a blocking call, from its five time stamps: stage | launch | wait | copy-out | total
+using call_clock = std::chrono::steady_clock;
+void set_call_phases(gf_ctx* ctx, call_clock::time_point entry, call_clock::time_point staged, call_clock::time_point launched,
+                     call_clock::time_point done, call_clock::time_point out) {
+    const call_clock::time_point t[5] = {entry, staged, launched, done, out};
+    for (int i = 0; i < 4; ++i) ctx->call_phase_us[i] = std::chrono::duration<double, std::micro>(t[i + 1] - t[i]).count();
+    ctx->call_phase_us[4] = std::chrono::duration<double, std::micro>(out - entry).count();
+}
+
 }  // namespace gfapi
 
 extern "C" {
@@ -793,7 +808,7 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     if (n_apps > 0 && (!apps || !results)) return fail(ctx, GF_ERR_INVALID, "apps/results must not be NULL");
     if (chain_failed_at) *chain_failed_at = -1;
     if (n_apps == 0) return GF_OK;
-    const auto t_entry = std::chrono::steady_clock::now();
+    const auto t_entry = call_clock::now();
     GF_HIP(ctx, hipSetDevice(ctx->device));
     GF_HIP(ctx, ctx->h_apps.reserve(n_apps));
     uint64_t total_k = 0;
@@ -825,25 +840,18 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
         (uint64_t)n_apps * sizeof(gf_app) + total_k * sizeof(uint32_t) <= (UINT64_C(4) << 20)) {
         void *da = ctx->h_apps.dev, *dr = ctx->h_results.dev, *de = ctx->h_exec.dev;
         if (da != nullptr && dr != nullptr && de != nullptr) {
-            using clk = std::chrono::steady_clock;
-            const auto t_staged = clk::now();
+            const auto t_staged = call_clock::now();
             call.q.d_apps = static_cast<const gf_app*>(da);
             call.q.d_results = static_cast<gf_result*>(dr);
             call.q.d_exec_nodes = static_cast<uint32_t*>(de);
             const int rc0 = launch(ctx, route, &call);
             if (rc0 != GF_OK) return rc0;
-            const auto t_launched = clk::now();
+            const auto t_launched = call_clock::now();
             GF_HIP(ctx, gf_wait_stream(st));
-            const auto t_done = clk::now();
+            const auto t_done = call_clock::now();
             std::memcpy(results, ctx->h_results.ptr, (size_t)n_apps * sizeof(gf_result));
             if (total_k) std::memcpy(exec_nodes, ctx->h_exec.ptr, (size_t)total_k * sizeof(uint32_t));
-            const auto t_out = clk::now();
-            auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-            ctx->call_phase_us[0] = us(t_entry, t_staged);
-            ctx->call_phase_us[1] = us(t_staged, t_launched);
-            ctx->call_phase_us[2] = us(t_launched, t_done);
-            ctx->call_phase_us[3] = us(t_done, t_out);
-            ctx->call_phase_us[4] = us(t_entry, t_out);
+            set_call_phases(ctx, t_entry, t_staged, t_launched, t_done, call_clock::now());
             return GF_OK;
         }
     }
@@ -946,8 +954,7 @@ int gf_fit_feasible(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* ap
     }
     GF_VIEW_ENTER(ctx)
     if (n_apps >= 0x80000000u) return fail(ctx, GF_ERR_INVALID, "n_apps = %u", n_apps);
-    using clk = std::chrono::steady_clock;
-    const auto t_entry = clk::now();
+    const auto t_entry = call_clock::now();
     GF_HIP(ctx, hipSetDevice(ctx->device));
     GF_HIP(ctx, ctx->h_apps.reserve(n_apps));
     uint64_t total_k = 0;  // the placements are still made (same decision code): into device memory, where they stay
@@ -991,22 +998,21 @@ int gf_fit_feasible(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* ap
     // (GANGFIT_WAIT=block: the host cannot spare a core for the duration of a call — no spinning on the answers either)
     const bool announce = mapped && ctx->feasible_announce && !wait_blocking();
     if (announce) std::memset(ctx->h_feasible.ptr, kNotYet, n_apps);
-    const auto t_staged = clk::now();
-    hipError_t e;
-    if (route.kind == Route::kZonedFused) {
-        e = ctx->d_feas_zexec.reserve(((uint64_t)ctx->n_zones + 1) * half);
-        if (e == hipSuccess)
-            e = gangfit::launch_fit_zoned_fused(route.inner, route.az_aware, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), zone_table(ctx),
-                                                ctx->d_sched.ptr, ctx->d_feas_zexec.ptr, half, n_apps, d_apps, nullptr, nullptr,
-                                                ctx->d_feas_scratch.ptr, half, st, d_feas, ctx->d_feasible_sync.ptr, ctx->eff_nonneg);
-    } else {
-        e = gangfit::launch_fit_independent(algo, make_table(ctx, ctx->d_snap.ptr), make_sparse(ctx), n_apps, d_apps, nullptr,
-                                            ctx->d_feas_exec.ptr, ctx->d_feas_scratch.ptr, half, nullptr, st, d_feas,
-                                            ctx->d_feasible_sync.ptr);
+    const auto t_staged = call_clock::now();
+    hipError_t e = route.kind == Route::kZonedFused ? ctx->d_feas_zexec.reserve(((uint64_t)ctx->n_zones + 1) * half) : hipSuccess;
+    if (e == hipSuccess) {
+        // no result records; the placements stay in this entry point's own buffers
+        gangfit::FitBatch b = fit_batch_of(ctx, route, n_apps, d_apps, nullptr, ctx->d_feas_exec.ptr, half, st);
+        b.d_scratch = ctx->d_feas_scratch.ptr;
+        b.d_zexec = ctx->d_feas_zexec.ptr;
+        b.d_stats = nullptr;
+        b.feasible = gangfit::FeasibleOut{d_feas, ctx->d_feasible_sync.ptr, ctx->eff_nonneg};
+        e = route.kind == Route::kZonedFused ? gangfit::launch_fit_zoned_fused(route.inner, route.az_aware, b)
+                                             : gangfit::launch_fit_independent((gf_algo)route.inner, b);
     }
     if (e == hipSuccess && !mapped)
         e = hipMemcpyAsync(ctx->h_feasible.ptr, staged.ptr, n_apps, hipMemcpyDeviceToHost, st);
-    const auto t_launched = clk::now();
+    const auto t_launched = call_clock::now();
     bool arrived = false;
     if (e == hipSuccess && announce) {
         const volatile uint8_t* f = ctx->h_feasible.ptr;
@@ -1019,23 +1025,17 @@ int gf_fit_feasible(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* ap
             }
             __builtin_ia32_pause();
             // a kernel that faulted never writes: after 2 ms the stream is asked (it reports the error, or completes)
-            if ((spin & 255u) == 255u && clk::now() - t_launched > std::chrono::milliseconds(2)) break;
+            if ((spin & 255u) == 255u && call_clock::now() - t_launched > std::chrono::milliseconds(2)) break;
         }
         std::atomic_thread_fence(std::memory_order_acquire);
     }
     if (e == hipSuccess && !arrived) e = gf_wait_stream(st);
     if (e != hipSuccess) ctx->feasible_sync_dirty = true;  // the collection may have stopped anywhere
-    const auto t_done = clk::now();
+    const auto t_done = call_clock::now();
     staged.release();
     if (e != hipSuccess) return fail(ctx, GF_ERR_HIP, "gf_fit_feasible failed: %s", hipGetErrorString(e));
     std::memcpy(has_capacity, ctx->h_feasible.ptr, n_apps);
-    const auto t_out = clk::now();
-    auto us = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    ctx->call_phase_us[0] = us(t_entry, t_staged);  // gf_call_phases: stage | launch | wait | copy-out | total
-    ctx->call_phase_us[1] = us(t_staged, t_launched);
-    ctx->call_phase_us[2] = us(t_launched, t_done);
-    ctx->call_phase_us[3] = us(t_done, t_out);
-    ctx->call_phase_us[4] = us(t_entry, t_out);
+    set_call_phases(ctx, t_entry, t_staged, t_launched, t_done, call_clock::now());
     return GF_OK;
 }
 

@@ -104,9 +104,10 @@ int gf_cluster_fit_feasible(gf_ctx* ctx, gf_algo algo, const int64_t* over_cpu_m
     GF_HIP(ctx, ctx->d_scan_select.reserve(N + 1));
     if (const int rc = scan_upload(ctx, q, n_apps, apps, st); rc != GF_OK) return rc;
     if (node_select != nullptr && N) GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_select.ptr, node_select, N, hipMemcpyHostToDevice, st));
-    GF_HIP(ctx, gangfit::launch_cluster_scan(q.zoned, n, ctx->d_cl_i64.ptr, q.with_over ? ctx->d_scan_over.ptr : nullptr, ctx->d_cl_u32.ptr,
-                                             node_select != nullptr ? ctx->d_scan_select.ptr : nullptr, n_apps, ctx->d_scan_apps.ptr,
-                                             ctx->d_scan_out.ptr, st));
+    const gangfit::ScanArgs args{.alloc = ctx->d_cl_i64.ptr, .over = q.with_over ? ctx->d_scan_over.ptr : nullptr, .zone = ctx->d_cl_u32.ptr,
+                                 .select = node_select != nullptr ? ctx->d_scan_select.ptr : nullptr, .n_nodes = n, .n_apps = n_apps,
+                                 .apps = ctx->d_scan_apps.ptr, .out = ctx->d_scan_out.ptr};
+    GF_HIP(ctx, gangfit::launch_cluster_scan(q.zoned, args, st));
     return scan_answers(ctx, n_apps, has_capacity, st);
 }
 
@@ -142,9 +143,10 @@ int gf_cluster_fit_feasible_sets(gf_ctx* ctx, gf_algo algo, const int64_t* over_
     if (const int rc = scan_upload(ctx, q, n_apps, apps, st); rc != GF_OK) return rc;
     if (n_words) GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_sets.ptr, set_words, n_words * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     GF_HIP(ctx, hipMemcpyAsync(ctx->d_scan_app_set.ptr, app_set, (size_t)n_apps * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    GF_HIP(ctx, gangfit::launch_cluster_scan_sets(q.zoned, n, ctx->d_cl_i64.ptr, q.with_over ? ctx->d_scan_over.ptr : nullptr,
-                                                  ctx->d_cl_u32.ptr, ctx->d_scan_sets.ptr, ctx->d_scan_app_set.ptr, n_apps,
-                                                  ctx->d_scan_apps.ptr, ctx->d_scan_out.ptr, st));
+    const gangfit::ScanSetsArgs args{.alloc = ctx->d_cl_i64.ptr, .over = q.with_over ? ctx->d_scan_over.ptr : nullptr, .zone = ctx->d_cl_u32.ptr,
+                                     .set_words = ctx->d_scan_sets.ptr, .app_set = ctx->d_scan_app_set.ptr, .n_nodes = n, .n_apps = n_apps,
+                                     .apps = ctx->d_scan_apps.ptr, .out = ctx->d_scan_out.ptr};
+    GF_HIP(ctx, gangfit::launch_cluster_scan_sets(q.zoned, args, st));
     return scan_answers(ctx, n_apps, has_capacity, st);
 }
 
@@ -222,27 +224,14 @@ int gf_cluster_executor_fit(gf_ctx* ctx, int minimal_fragmentation, uint32_t n_s
         if (exec_label_rank)
             GF_HIP(ctx, hipMemcpyAsync(ctx->d_xs_cols.ptr + N, exec_label_rank, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     }
-    gangfit::ClusterExecutorFit f{};
-    f.n_nodes = n;
-    f.n_zones = ctx->cl_zones;
-    f.d_alloc = ctx->d_cl_i64.ptr;
-    f.d_over = ctx->cl_over ? ctx->d_cl_i64.ptr + 3 * N : nullptr;
-    f.d_usage = ctx->d_cl_usage.ptr;
-    f.d_res_count = ctx->d_cl_x32.ptr;
-    f.d_zone = ctx->d_cl_u32.ptr;
-    f.d_name_rank = ctx->d_cl_u32.ptr + N;
-    f.d_flags = ctx->d_cl_x32.ptr + N;
-    f.d_node_zone = node_zone && N ? ctx->d_xs_cols.ptr : nullptr;
-    f.d_label_rank = exec_label_rank && N ? ctx->d_xs_cols.ptr + N : nullptr;
-    f.d_set_words = with_sets ? ctx->d_xs_sets.ptr : nullptr;
-    f.d_req_set = with_sets ? d_set : nullptr;
-    f.d_req_zone = req_zone ? d_zone : nullptr;
-    f.d_hosts = with_hosts ? ctx->d_xs_hosts.ptr : nullptr;
-    f.hosts_stride = hosts_stride;
-    f.n_req = n_req;
-    f.d_exe = reinterpret_cast<const int64_t*>(ctx->d_xs_req.ptr);
-    f.d_out = ctx->d_xs_out.ptr;
-    GF_HIP(ctx, gangfit::launch_cluster_executor_fit(minimal_fragmentation != 0, f, st));
+    const gangfit::ExecScanArgs args{
+        .alloc = ctx->d_cl_i64.ptr, .over = ctx->cl_over ? ctx->d_cl_i64.ptr + 3 * N : nullptr, .usage = ctx->d_cl_usage.ptr,
+        .res_count = ctx->d_cl_x32.ptr, .zone = ctx->d_cl_u32.ptr, .name_rank = ctx->d_cl_u32.ptr + N, .flags = ctx->d_cl_x32.ptr + N,
+        .node_zone = node_zone && N ? ctx->d_xs_cols.ptr : nullptr, .label_rank = exec_label_rank && N ? ctx->d_xs_cols.ptr + N : nullptr,
+        .set_words = with_sets ? ctx->d_xs_sets.ptr : nullptr, .req_set = with_sets ? d_set : nullptr, .req_zone = req_zone ? d_zone : nullptr,
+        .hosts = with_hosts ? ctx->d_xs_hosts.ptr : nullptr, .exe = reinterpret_cast<const int64_t*>(ctx->d_xs_req.ptr), .n_nodes = n,
+        .n_zones = ctx->cl_zones, .n_req = n_req, .hosts_stride = hosts_stride, .out = ctx->d_xs_out.ptr};
+    GF_HIP(ctx, gangfit::launch_cluster_executor_fit(minimal_fragmentation != 0, args, st));
     GF_HIP(ctx, hipMemcpyAsync(ctx->h_xs_out.ptr, ctx->d_xs_out.ptr, R * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays are free again, the answers have arrived
     std::memcpy(node_out, ctx->h_xs_out.ptr, R * sizeof(uint32_t));

@@ -130,14 +130,31 @@ struct ScanStats {
     unsigned long long fifo_hw_id;            // HW_ID of the chain's controlling wavefront (CU, SE, ...) | XCC_ID << 32
 };
 
-// Launchers (defined in gangfit_kernels.hip).  scratch: 2 * total_k uint32 (DistributeEvenly survivor lists).
-// d_feasible != nullptr: feasibility only (gf_fit_feasible) — n_apps bytes (padded to a multiple of four; device-mapped pinned
-// memory or a device buffer) receive HasCapacity, d_results is not written, no counters.  d_feasible_sync: ceil(n_apps / 4)
-// words of device memory, zero between launches (the kernel's collecting workgroup clears them again).
-hipError_t launch_fit_independent(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, uint32_t n_apps,
-                                  const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch,
-                                  uint64_t scratch_half, ScanStats* d_stats, hipStream_t stream, uint8_t* d_feasible = nullptr,
-                                  uint32_t* d_feasible_sync = nullptr);
+// What a feasibility-only launch (gf_fit_feasible) writes instead of result records and counters; d_bytes == nullptr: the full batch.
+struct FeasibleOut {
+    uint8_t* d_bytes = nullptr;   // n_apps HasCapacity bytes (padded to a multiple of four; device-mapped pinned memory or a device
+                                  // buffer), written in whole words by the kernel's collecting workgroup
+    uint32_t* d_words = nullptr;  // the collection words: ceil(n_apps / 4) of device memory, zero between launches (cleared by the same)
+    bool eff_nonneg = false;      // zone-aware packers: no node's efficiency can be negative (gf_ctx::eff_nonneg)
+};
+// What every launcher of an independent batch (gangfit_kernels.hip) receives; it reads what it needs and leaves the rest alone.
+struct FitBatch {
+    NodeTable table{};
+    SparseTable gpu_view{};                  // n_x == 0: none
+    ZoneTable zones{nullptr, nullptr, 0, 0};  // zone-aware packers (else empty) ...
+    const int64_t* d_sched = nullptr;        // ... and SchedulableResources in slot order (3 * n_slots)
+    uint32_t n_apps = 0;
+    const gf_app* d_apps = nullptr;
+    gf_result* d_results = nullptr;
+    uint32_t* d_exec_nodes = nullptr;
+    uint32_t* d_scratch = nullptr;  // 2 * half uint32 (DistributeEvenly survivor lists)
+    uint64_t half = 0;              // the ONE stride of d_scratch, of d_zexec and of the placements (total_k + 1)
+    uint32_t* d_zexec = nullptr;    // (n_zones + 1) rows of half uint32: the candidate views' placements as SLOT ids (both zone routes)
+    ScanStats* d_stats = nullptr;   // nullable
+    FeasibleOut feasible{};
+    hipStream_t stream = nullptr;
+};
+hipError_t launch_fit_independent(gf_algo algo, const FitBatch& batch);
 
 // ---- the resident worker of the independent batch (gangfit_worker.inc; host side: gangfit_api_worker.cpp)
 constexpr uint32_t kWorkerRing = 64;  // tickets in flight at most (a power of two: the host waits for ticket t - 64 before it posts t)
@@ -324,26 +341,17 @@ hipError_t launch_fit_fifo(gf_algo algo, const FifoPlan& plan, const ChainTables
 // result.  az_aware: apps without a single-zone fit keep the plain tightly-pack answer already in d_results.
 struct ZoneBuffers {
     gf_result* zres;      // [n_apps * n_zones]
-    uint32_t* zexec;      // [n_zones][zexec_stride] placements as SLOT ids
-    uint64_t zexec_stride;
     double* zavg;         // [n_apps * n_zones][4]
     uint32_t* cnt;        // [n_cnt_waves][n_slots] zero between launches: per-wave executor multiplicity scratch
     uint32_t n_cnt_waves;
 };
-hipError_t launch_fit_zoned(int inner_algo, bool az_aware, bool reserve_execs, const NodeTable& table,
-                            const ZoneTable& zones, const EffTables& eff, const ZoneBuffers& buf, uint32_t n_apps,
-                            const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch,
-                            uint64_t scratch_half, hipStream_t stream);
+hipError_t launch_fit_zoned(int inner_algo, bool az_aware, bool reserve_execs, const EffTables& eff, const ZoneBuffers& buf,
+                            const FitBatch& batch);
 
 // The same as ONE launch (fit_zoned_fused_kernel): a workgroup per application, a wavefront per candidate view, the choice
 // through LDS, the winner's placements written as node indices to d_exec_nodes / d_results — which may be device-mapped host
-// memory.  d_zexec: (n_zones + 1) rows of zexec_stride uint32 (the candidates' placements as slot ids).  At most 64 views.
-hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const NodeTable& table, const SparseTable& gpu_view, const ZoneTable& zones,
-                                  const int64_t* d_sched, uint32_t* d_zexec, uint64_t zexec_stride, uint32_t n_apps,
-                                  const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch,
-                                  uint64_t scratch_half, hipStream_t stream, uint8_t* d_feasible = nullptr,
-                                  uint32_t* d_feasible_sync = nullptr,  // (feasibility only: as launch_fit_independent)
-                                  bool eff_nonneg = false);  // feasibility only: no node's efficiency can be negative (gf_ctx::eff_nonneg)
+// memory.  At most 64 views.
+hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const FitBatch& batch);
 
 // FIFO chain of the zone-aware and minimal-fragmentation packers: one workgroup, one wavefront per candidate view of the
 // current app (each zone, plus the plain pack for az-aware), working table in global memory.  d_zexec needs (n_zones + 1)
@@ -576,40 +584,58 @@ hipError_t launch_overhead_update(uint32_t n_rows, uint32_t n_nodes, const uint3
 // candidates = the nodes with d_select[n] != 0 (nullable: every node), nothing reserved.  zoned: the single-AZ answer (some zone
 // fits by itself; d_zone: n_nodes ids below 64) without chooseBestResult's averages — the caller refuses what could make one 0.
 // One wavefront per application; reads nothing of the installed snapshot.
-hipError_t launch_cluster_scan(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
-                               const uint8_t* d_select, uint32_t n_apps, const gf_app* d_apps, uint8_t* d_out, hipStream_t stream);
+// The records below are the kernels' own arguments (taken by value): an entry point fills one, the launcher sets n_words on its copy.
+struct ScanArgs {
+    const int64_t* alloc;         // 3 * n_nodes: cpu | mem | gpu (gf_cluster_set)
+    const int64_t* over;          // 3 * n_nodes, or nullptr: no overhead
+    const uint32_t* zone;         // n_nodes zone ids below kScanZones (ZONED only)
+    const uint8_t* select;        // n_nodes, or nullptr: every node
+    uint32_t n_nodes;
+    uint32_t n_apps;
+    const gf_app* apps;
+    uint8_t* out;                 // n_apps HasCapacity bytes
+};
+hipError_t launch_cluster_scan(bool zoned, const ScanArgs& args, hipStream_t stream);
 // The same scan for applications of many node sets in one launch (gf_cluster_fit_feasible_sets): application a asks the nodes of
-// row d_app_set[a] of d_set_words — rows of ceil(n_nodes / 64) words, bit (n & 63) of word n >> 6 = node n, no bit at or beyond
-// n_nodes, every d_app_set[a] a row of the matrix (the entry point checks both).  A wavefront reads the columns only of the 64-node
+// row app_set[a] of set_words — rows of ceil(n_nodes / 64) words, bit (n & 63) of word n >> 6 = node n, no bit at or beyond
+// n_nodes, every app_set[a] a row of the matrix (the entry point checks both).  A wavefront reads the columns only of the 64-node
 // chunks whose word of its row is not zero.
-hipError_t launch_cluster_scan_sets(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
-                                    const uint64_t* d_set_words, const uint32_t* d_app_set, uint32_t n_apps, const gf_app* d_apps,
-                                    uint8_t* d_out, hipStream_t stream);
-// The executor Filter on the resident cluster (gangfit_exec_scan.inc; gf_cluster_executor_fit): d_out[q] = the node the
-// installing route (gf_snapshot_build + gf_executor_fit) returns for request q when it is given only the nodes of row d_req_set[q]
+struct ScanSetsArgs {
+    const int64_t* alloc;         // 3 * n_nodes: cpu | mem | gpu (gf_cluster_set)
+    const int64_t* over;          // 3 * n_nodes, or nullptr: no overhead
+    const uint32_t* zone;         // n_nodes zone ids below kScanZones (ZONED only)
+    const uint64_t* set_words;    // n_sets * n_words; no bit at or beyond n_nodes (the entry point checks)
+    const uint32_t* app_set;      // n_apps row numbers below n_sets (the entry point checks)
+    uint32_t n_nodes;
+    uint32_t n_words;             // W = ceil(n_nodes / 64): set by the launcher
+    uint32_t n_apps;
+    const gf_app* apps;
+    uint8_t* out;                 // n_apps HasCapacity bytes
+};
+hipError_t launch_cluster_scan_sets(bool zoned, const ScanSetsArgs& args, hipStream_t stream);
+// The executor Filter on the resident cluster (gangfit_exec_scan.inc; gf_cluster_executor_fit): out[q] = the node the
+// installing route (gf_snapshot_build + gf_executor_fit) returns for request q when it is given only the nodes of row req_set[q]
 // that pass the zone test — as an order-free minimum over the columns in node-index order.  One workgroup of four wavefronts per
 // request; reads nothing of the installed snapshot.
-struct ClusterExecutorFit {
-    uint32_t n_nodes, n_zones;       // n_zones <= 64
-    const int64_t* d_alloc;          // 3 * n_nodes
-    const int64_t* d_over;           // 3 * n_nodes, or nullptr: no overhead
-    const int64_t* d_usage;          // 3 * n_nodes resident usage sums
-    const uint32_t* d_res_count;     // n_nodes reservation entries per node
-    const uint32_t* d_zone;          // n_nodes cluster zone ids
-    const uint32_t* d_name_rank;     // n_nodes
-    const uint32_t* d_flags;         // n_nodes default GF_NODE_* flags
-    const uint32_t* d_node_zone;     // n_nodes ids of the zone test, or nullptr: d_zone
-    const uint32_t* d_label_rank;    // n_nodes, or nullptr
-    const uint64_t* d_set_words;     // rows of ceil(n_nodes / 64) words, or nullptr: every node
-    const uint32_t* d_req_set;       // n_req rows (with d_set_words)
-    const uint32_t* d_req_zone;      // n_req, or nullptr: GF_ANY_ZONE
-    const uint32_t* d_hosts;         // n_req * hosts_stride, or nullptr
-    uint32_t hosts_stride;
-    uint32_t n_req;
-    const int64_t* d_exe;            // n_req * 3
-    uint32_t* d_out;                 // n_req
+struct ExecScanArgs {
+    const int64_t* alloc;         // 3 * n_nodes: cpu | mem | gpu (gf_cluster_set)
+    const int64_t* over;          // 3 * n_nodes resident overhead, or nullptr: none
+    const int64_t* usage;         // 3 * n_nodes resident usage sums (gf_usage_apply)
+    const uint32_t* res_count;    // n_nodes: reservation entries that name the node
+    const uint32_t* zone;         // n_nodes cluster zone ids below kExecZones
+    const uint32_t* name_rank;    // n_nodes, a permutation
+    const uint32_t* flags;        // n_nodes: the cluster's default GF_NODE_* flags
+    const uint32_t* node_zone;    // n_nodes ids the zone test compares, or nullptr: the cluster's
+    const uint32_t* label_rank;   // n_nodes executor label ranks, or nullptr
+    const uint64_t* set_words;    // n_sets * n_words, or nullptr: every node.  No bit at or beyond n_nodes (the entry point checks)
+    const uint32_t* req_set;      // n_req rows (with set_words)
+    const uint32_t* req_zone;     // n_req, or nullptr: GF_ANY_ZONE
+    const uint32_t* hosts;        // n_req * hosts_stride words (32 nodes each), or nullptr
+    const int64_t* exe;           // n_req * 3
+    uint32_t n_nodes, n_words /* set by the launcher */, n_zones /* <= 64 */, n_req, hosts_stride;
+    uint32_t* out;                // n_req node indices
 };
-hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ClusterExecutorFit& f, hipStream_t stream);
+hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ExecScanArgs& args, hipStream_t stream);
 // The slot tables of the merged layout built from the device-resident snapshot columns (what gf_orders_set builds on the
 // host): every node gets the slot of its position in the priority order.
 struct SnapshotFinalize {

@@ -28,25 +28,6 @@ constexpr int kExecZones = 64;
 constexpr int kExecFields = 6;  // not hosting | capacity | label rank, zone rank | memory | cpu | name rank, node
 constexpr int64_t kExecBias = INT64_MIN;  // x ^ kExecBias: unsigned order as signed order
 
-struct ExecScanArgs {
-    const int64_t* alloc;         // 3 * n_nodes: cpu | mem | gpu (gf_cluster_set)
-    const int64_t* over;          // 3 * n_nodes resident overhead, or nullptr: none
-    const int64_t* usage;         // 3 * n_nodes resident usage sums (gf_usage_apply)
-    const uint32_t* res_count;    // n_nodes: reservation entries that name the node
-    const uint32_t* zone;         // n_nodes cluster zone ids below kExecZones
-    const uint32_t* name_rank;    // n_nodes, a permutation
-    const uint32_t* flags;        // n_nodes: the cluster's default GF_NODE_* flags
-    const uint32_t* node_zone;    // n_nodes ids the zone test compares, or nullptr: the cluster's
-    const uint32_t* label_rank;   // n_nodes executor label ranks, or nullptr
-    const uint64_t* set_words;    // n_sets * n_words, or nullptr: every node.  No bit at or beyond n_nodes (the entry point checks)
-    const uint32_t* req_set;      // n_req rows (with set_words)
-    const uint32_t* req_zone;     // n_req, or nullptr: GF_ANY_ZONE
-    const uint32_t* hosts;        // n_req * hosts_stride words (32 nodes each), or nullptr
-    const int64_t* exe;           // n_req * 3
-    uint32_t n_nodes, n_words, n_zones, n_req, hosts_stride;
-    uint32_t* out;                // n_req node indices
-};
-
 struct ExecScanShared {
     unsigned long long zsum[2][kExecZones];       // memory | cpu of available over S, per cluster zone
     int64_t rec[kWavesPerBlock][kExecFields];     // every wavefront's smallest candidate

@@ -1148,7 +1148,7 @@ __device__ __forceinline__ void wave_commit_from_list(const View& V, const App& 
 // stores and announces its own completion there — arrival counters, a sequence word the caller polls — instead of the stream
 // wait: 30.3 us per blocking 1 000-application call against 23.3 us; 13 000 dword write-through stores over the host link and
 // their acknowledgement cost more than the kernel-end write-back and the completion signal they replace; removed.)
-// gf_fit_feasible, device side (fit_independent_kernel<.., true>, fit_zoned_fused_kernel<.., true>): how HasCapacity of every
+// gf_fit_feasible, device side (fit_independent_kernel<.., true>, fit_zoned_fused_feasible_kernel): how HasCapacity of every
 // application reaches the caller without the kernel having to end first.  `words`: ceil(n_apps / 4) words of DEVICE memory, zero
 // between launches, one byte per application.
 // feasible_announce: a deciding wavefront leaves 0x80 | HasCapacity in its byte with an atomic OR that returns nothing — it waits
@@ -1177,9 +1177,31 @@ __device__ __forceinline__ void feasible_collect(uint32_t* words, uint32_t* dst,
     }
 }
 
-// FEAS (gf_fit_feasible): feasibility only.  `results` is then an array of n_apps BYTES (device-mapped pinned host memory, or a
-// device buffer) that receives HasCapacity and nothing else, and `stats` carries the call's collection words instead of
-// counters (feasible_announce / feasible_collect above): the caller watches the bytes arrive in pinned memory instead of
+// What the kernels of an independent batch write per application: the result record and, where counted, the slots visited — or,
+// feasibility only, HasCapacity through the collection words.  fit_independent_kernel declares the two in the same two places of
+// its arguments (Answers, Aux); fit_zoned_fused_kernel, whose two lists differ in more than that, is two kernels around one body.
+template <bool FEAS>
+struct FitOut {
+    using Answers = gf_result*;
+    using Aux = ScanStats*;
+    Answers results;
+    Aux stats;  // nullable (fit_zoned_fused_kernel counts nothing)
+};
+template <>
+struct FitOut<true> {
+    using Answers = uint8_t*;
+    using Aux = uint32_t*;
+    Answers bytes;  // FeasibleOut::d_bytes
+    Aux words;      // FeasibleOut::d_words
+};
+// (the one place the byte array is seen as the words the collecting wavefront stores: it is padded and aligned for that)
+__device__ __forceinline__ void feasible_collect(const FitOut<true>& out, uint32_t n_apps, int lane) {
+    feasible_collect(out.words, reinterpret_cast<uint32_t*>(out.bytes), n_apps, lane);
+}
+
+// FEAS (gf_fit_feasible): feasibility only.  answers.bytes — n_apps BYTES of device-mapped pinned host memory, or of a device
+// buffer — receive HasCapacity and nothing else, through the call's collection words answers.words (feasible_announce /
+// feasible_collect above): the caller watches the bytes arrive in pinned memory instead of
 // waiting for the kernel-end write-back and the stream's completion signal.  Measured on the way
 // (profiles/r5g_feasible_call_byte_stores.txt, r5h_feasible_call_last_wavefront.txt): one system-scope byte store per wavefront
 // straight into pinned memory — 1 000 lone bytes over the host link cost 10 us more than they save —; an arrival counter whose
@@ -1188,19 +1210,21 @@ __device__ __forceinline__ void feasible_collect(uint32_t* words, uint32_t* dst,
 // decision code — and stay in device memory.  A separate instantiation: the batch kernel proper carries none of this.
 template <int ALGO, bool FEAS>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void fit_independent_kernel(
-    NodeTable T, SparseTable G, uint32_t n_apps, const gf_app* __restrict__ apps, gf_result* __restrict__ results,
+    NodeTable T, SparseTable G, uint32_t n_apps, const gf_app* __restrict__ apps, typename FitOut<FEAS>::Answers __restrict__ out_answers,
     uint32_t* __restrict__ exec_nodes, uint32_t* __restrict__ scratch, uint64_t scratch_half,
-    ScanStats* __restrict__ stats) {
+    typename FitOut<FEAS>::Aux __restrict__ out_aux) {
+    const FitOut<FEAS> answers{out_answers, out_aux};  // results, stats — or bytes, words
     const int lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     constexpr bool kMfTeam = ALGO == GF_ALGO_MINIMAL_FRAGMENTATION;
     const uint32_t a = kMfTeam ? blockIdx.x : blockIdx.x * kWavesPerBlock + wave;
     const bool reports = !kMfTeam || wave == 0u;  // (a team's wavefronts reach the same decision: one of them reports it)
     const uint32_t n_waves = n_apps;
-    if (FEAS && blockIdx.x == gridDim.x - 1u) {  // the collecting workgroup (launch_fit_independent appends it)
-        if (wave == 0) feasible_collect(reinterpret_cast<uint32_t*>(stats), reinterpret_cast<uint32_t*>(results), n_apps, lane);
-        return;
-    }
+    if constexpr (FEAS)
+        if (blockIdx.x == gridDim.x - 1u) {  // the collecting workgroup (launch_fit_independent appends it)
+            if (wave == 0) feasible_collect(answers, n_apps, lane);
+            return;
+        }
     if (a >= n_waves) return;
     GlobalView V{T.cpu, T.mem, T.gpu, T.cmax, T.cmax + T.n_chunks, T.cmax + 2 * (size_t)T.n_chunks, T.xmask, T.dmask,
                  T.n_chunks};
@@ -1226,8 +1250,8 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void fit_independent_kernel(
         Decision dec = wave_decide<ALGO, GlobalView, false>(V, O, app, exec_nodes + app.exec_off, scratch + app.exec_off,
                                                             scratch + scratch_half + app.exec_off, lane, xvis, dvis,
                                                             merged ? &g0 : nullptr, &G);
-        if (FEAS) {
-            if (lane == 0 && reports) feasible_announce(reinterpret_cast<uint32_t*>(stats), ai, dec.feasible);
+        if constexpr (FEAS) {
+            if (lane == 0 && reports) feasible_announce(answers.words, ai, dec.feasible);
         } else if (lane == 0 && reports) {
             gf_result r;
             r.has_capacity = dec.feasible ? 1 : 0;
@@ -1235,14 +1259,15 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void fit_independent_kernel(
             r.driver_node = dec.feasible ? dec.ds_node : GF_NO_NODE;
             r.exec_len = dec.feasible ? (uint32_t)app.k : 0u;
             r.evaluated = 1;
-            results[ai] = r;
+            answers.results[ai] = r;
         }
     };
     decide(load_app(apps, a), a);
-    if (!FEAS && stats != nullptr && lane == 0 && reports) {
-        atomicAdd(&stats->exec_slots_visited, xvis);
-        atomicAdd(&stats->driver_slots_visited, dvis);
-    }
+    if constexpr (!FEAS)
+        if (answers.stats != nullptr && lane == 0 && reports) {
+            atomicAdd(&answers.stats->exec_slots_visited, xvis);
+            atomicAdd(&answers.stats->driver_slots_visited, dvis);
+        }
 }
 
 // ------------------------------------------------------------------------------------------------ FIFO chain
@@ -1959,68 +1984,60 @@ hipError_t launch_fit_worker(gf_algo algo, const NodeTable& table, const SparseT
     });
 }
 
-hipError_t launch_fit_independent(gf_algo algo, const NodeTable& table, const SparseTable& gpu_view, uint32_t n_apps,
-                                  const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch,
-                                  uint64_t scratch_half, ScanStats* d_stats, hipStream_t stream, uint8_t* d_feasible,
-                                  uint32_t* d_feasible_sync) {
-    if (n_apps == 0) return hipSuccess;
-    if (d_feasible != nullptr && d_feasible_sync == nullptr) return hipErrorInvalidValue;
+hipError_t launch_fit_independent(gf_algo algo, const FitBatch& B) {
+    if (B.n_apps == 0) return hipSuccess;
+    const FeasibleOut& F = B.feasible;
+    if (F.d_bytes != nullptr && F.d_words == nullptr) return hipErrorInvalidValue;
     const dim3 block(kWave * kWavesPerBlock);
     // (minimal-fragmentation: a workgroup per application — its wavefronts share the passes over the executor order)
     const bool team = algo == GF_ALGO_MINIMAL_FRAGMENTATION;
-    const dim3 grid(team ? n_apps : app_grid(n_apps).x);
+    const dim3 grid(team ? B.n_apps : app_grid(B.n_apps).x);
     const dim3 grid_feas(grid.x + 1);  // + the collecting workgroup
     return with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_DISTRIBUTE_EVENLY, GF_ALGO_MINIMAL_FRAGMENTATION>(algo, [&](auto A) {
-        if (d_feasible != nullptr)
-            hipLaunchKernelGGL((fit_independent_kernel<A, true>), grid_feas, block, 0, stream, table, gpu_view, n_apps, d_apps,
-                               reinterpret_cast<gf_result*>(d_feasible), d_exec_nodes, d_scratch, scratch_half,
-                               reinterpret_cast<ScanStats*>(d_feasible_sync));
+        if (F.d_bytes != nullptr)
+            hipLaunchKernelGGL((fit_independent_kernel<A, true>), grid_feas, block, 0, B.stream, B.table, B.gpu_view, B.n_apps, B.d_apps,
+                               F.d_bytes, B.d_exec_nodes, B.d_scratch, B.half, F.d_words);
         else
-            hipLaunchKernelGGL((fit_independent_kernel<A, false>), grid, block, 0, stream, table, gpu_view, n_apps, d_apps,
-                               d_results, d_exec_nodes, d_scratch, scratch_half, d_stats);
+            hipLaunchKernelGGL((fit_independent_kernel<A, false>), grid, block, 0, B.stream, B.table, B.gpu_view, B.n_apps, B.d_apps, B.d_results,
+                               B.d_exec_nodes, B.d_scratch, B.half, B.d_stats);
         return hipGetLastError();
     });
 }
 
-hipError_t launch_cluster_scan(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
-                               const uint8_t* d_select, uint32_t n_apps, const gf_app* d_apps, uint8_t* d_out, hipStream_t stream) {
-    if (n_apps == 0) return hipSuccess;
-    if (d_apps == nullptr || d_out == nullptr || (n_nodes > 0 && (d_alloc == nullptr || (zoned && d_zone == nullptr))))
+// The resident-cluster scans: the launcher's record is the kernel's; n_words is set here, on a copy (no caller can set it wrongly).
+hipError_t launch_cluster_scan(bool zoned, const ScanArgs& args, hipStream_t stream) {
+    if (args.n_apps == 0) return hipSuccess;
+    if (args.apps == nullptr || args.out == nullptr || (args.n_nodes > 0 && (args.alloc == nullptr || (zoned && args.zone == nullptr))))
         return hipErrorInvalidValue;
-    const ScanArgs args{d_alloc, d_over, d_zone, d_select, n_nodes, n_apps, d_apps, d_out};
     return with_value<true, false>(zoned, [&](auto Z) {
-        hipLaunchKernelGGL(cluster_scan_kernel<Z>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, args);
+        hipLaunchKernelGGL(cluster_scan_kernel<Z>, app_grid(args.n_apps), dim3(kWave * kWavesPerBlock), 0, stream, args);
         return hipGetLastError();
     });
 }
 
-hipError_t launch_cluster_scan_sets(bool zoned, uint32_t n_nodes, const int64_t* d_alloc, const int64_t* d_over, const uint32_t* d_zone,
-                                    const uint64_t* d_set_words, const uint32_t* d_app_set, uint32_t n_apps, const gf_app* d_apps,
-                                    uint8_t* d_out, hipStream_t stream) {
-    if (n_apps == 0) return hipSuccess;
-    if (d_apps == nullptr || d_out == nullptr || d_app_set == nullptr ||
-        (n_nodes > 0 && (d_alloc == nullptr || d_set_words == nullptr || (zoned && d_zone == nullptr))))
+hipError_t launch_cluster_scan_sets(bool zoned, const ScanSetsArgs& a, hipStream_t stream) {
+    if (a.n_apps == 0) return hipSuccess;
+    if (a.apps == nullptr || a.out == nullptr || a.app_set == nullptr ||
+        (a.n_nodes > 0 && (a.alloc == nullptr || a.set_words == nullptr || (zoned && a.zone == nullptr))))
         return hipErrorInvalidValue;
-    const uint32_t n_words = (uint32_t)(((uint64_t)n_nodes + kWave - 1) / kWave);
-    const ScanSetsArgs args{d_alloc, d_over, d_zone, d_set_words, d_app_set, n_nodes, n_words, n_apps, d_apps, d_out};
+    ScanSetsArgs args = a;
+    args.n_words = (uint32_t)(((uint64_t)a.n_nodes + kWave - 1) / kWave);
     return with_value<true, false>(zoned, [&](auto Z) {
-        hipLaunchKernelGGL(cluster_scan_sets_kernel<Z>, app_grid(n_apps), dim3(kWave * kWavesPerBlock), 0, stream, args);
+        hipLaunchKernelGGL(cluster_scan_sets_kernel<Z>, app_grid(args.n_apps), dim3(kWave * kWavesPerBlock), 0, stream, args);
         return hipGetLastError();
     });
 }
 
-hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ClusterExecutorFit& f, hipStream_t stream) {
-    if (f.n_req == 0) return hipSuccess;
-    if (f.d_exe == nullptr || f.d_out == nullptr || (f.d_set_words != nullptr && f.d_req_set == nullptr) || f.n_zones > (uint32_t)kExecZones ||
-        (f.n_nodes > 0 && (f.d_alloc == nullptr || f.d_usage == nullptr || f.d_res_count == nullptr || f.d_zone == nullptr ||
-                           f.d_name_rank == nullptr || f.d_flags == nullptr)))
+hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ExecScanArgs& a, hipStream_t stream) {
+    if (a.n_req == 0) return hipSuccess;
+    if (a.exe == nullptr || a.out == nullptr || (a.set_words != nullptr && a.req_set == nullptr) || a.n_zones > (uint32_t)kExecZones ||
+        (a.n_nodes > 0 && (a.alloc == nullptr || a.usage == nullptr || a.res_count == nullptr || a.zone == nullptr ||
+                           a.name_rank == nullptr || a.flags == nullptr)))
         return hipErrorInvalidValue;
-    const uint32_t n_words = (uint32_t)(((uint64_t)f.n_nodes + kWave - 1) / kWave);
-    const ExecScanArgs args{f.d_alloc,     f.d_over,      f.d_usage,    f.d_res_count, f.d_zone,  f.d_name_rank, f.d_flags,
-                            f.d_node_zone, f.d_label_rank, f.d_set_words, f.d_req_set,  f.d_req_zone, f.d_hosts,  f.d_exe,
-                            f.n_nodes,     n_words,       f.n_zones,    f.n_req,       f.hosts_stride, f.d_out};
+    ExecScanArgs args = a;
+    args.n_words = (uint32_t)(((uint64_t)a.n_nodes + kWave - 1) / kWave);
     return with_value<true, false>(minimal_fragmentation, [&](auto MF) {
-        hipLaunchKernelGGL(cluster_executor_fit_kernel<MF>, dim3(f.n_req), dim3(kWave * kWavesPerBlock), 0, stream, args);
+        hipLaunchKernelGGL(cluster_executor_fit_kernel<MF>, dim3(args.n_req), dim3(kWave * kWavesPerBlock), 0, stream, args);
         return hipGetLastError();
     });
 }
@@ -2163,67 +2180,61 @@ hipError_t launch_fit_fifo(gf_algo algo, const FifoPlan& plan, const ChainTables
         algo, [&](auto A) { return launch_fifo_algo<A>(plan, tables, batch, heads_lo); });
 }
 
-hipError_t launch_fit_zoned(int inner_algo, bool az_aware, bool reserve_execs, const NodeTable& table,
-                            const ZoneTable& zones, const EffTables& eff, const ZoneBuffers& buf, uint32_t n_apps,
-                            const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch,
-                            uint64_t scratch_half, hipStream_t stream) {
-    if (n_apps == 0) return hipSuccess;
+hipError_t launch_fit_zoned(int inner_algo, bool az_aware, bool reserve_execs, const EffTables& eff, const ZoneBuffers& buf,
+                            const FitBatch& B) {
+    if (B.n_apps == 0) return hipSuccess;
     if (inner_algo != GF_ALGO_TIGHTLY_PACK && inner_algo != GF_ALGO_MINIMAL_FRAGMENTATION) return hipErrorInvalidValue;
     if (az_aware && inner_algo != GF_ALGO_TIGHTLY_PACK) return hipErrorInvalidValue;
+    const NodeTable& table = B.table;
+    const ZoneTable& zones = B.zones;
     const dim3 block(kWave * kWavesPerBlock);
     hipError_t e = hipSuccess;
     if (az_aware) {  // the plain TightlyPack answer first; the select kernel overwrites it where a zone wins
-        e = launch_fit_independent(GF_ALGO_TIGHTLY_PACK, table, SparseTable{}, n_apps, d_apps, d_results, d_exec_nodes,
-                                   d_scratch, scratch_half, nullptr, stream);
+        FitBatch plain = B;  // (no sparse view, no counters, never feasibility only)
+        plain.gpu_view = SparseTable{}, plain.d_stats = nullptr, plain.feasible = FeasibleOut{};
+        e = launch_fit_independent(GF_ALGO_TIGHTLY_PACK, plain);
         if (e != hipSuccess) return e;
     }
     if (zones.n_zones > 0) {
-        const uint64_t n_dec = (uint64_t)n_apps * zones.n_zones;
+        const uint64_t n_dec = (uint64_t)B.n_apps * zones.n_zones;
         const dim3 dec_grid((unsigned)((n_dec + kWavesPerBlock - 1) / kWavesPerBlock));
         e = with_value<GF_ALGO_TIGHTLY_PACK, GF_ALGO_MINIMAL_FRAGMENTATION>(inner_algo, [&](auto A) {
-            hipLaunchKernelGGL(fit_zoned_kernel<A>, dec_grid, block, 0, stream, table, zones, n_apps, d_apps, buf.zres, buf.zexec,
-                               buf.zexec_stride, d_scratch, scratch_half);
+            hipLaunchKernelGGL(fit_zoned_kernel<A>, dec_grid, block, 0, B.stream, table, zones, B.n_apps, B.d_apps, buf.zres, B.d_zexec,
+                               B.half, B.d_scratch, B.half);
             return hipGetLastError();
         });
         if (e != hipSuccess) return e;
         e = with_value<true, false>(reserve_execs, [&](auto RE) {
-            hipLaunchKernelGGL((avg_efficiency_kernel<RE, true>), app_grid(buf.n_cnt_waves), block, 0, stream, eff, table.node_slot,
-                               table.n_slots, zones.n_zones, n_apps, d_apps, (const gf_result*)buf.zres,
-                               (const uint32_t*)buf.zexec, buf.zexec_stride, buf.cnt, buf.n_cnt_waves, buf.zavg);
+            hipLaunchKernelGGL((avg_efficiency_kernel<RE, true>), app_grid(buf.n_cnt_waves), block, 0, B.stream, eff, table.node_slot,
+                               table.n_slots, zones.n_zones, B.n_apps, B.d_apps, (const gf_result*)buf.zres,
+                               (const uint32_t*)B.d_zexec, B.half, buf.cnt, buf.n_cnt_waves, buf.zavg);
             return hipGetLastError();
         });
         if (e != hipSuccess) return e;
     }
     return with_value<true, false>(az_aware, [&](auto AZ) {
-        hipLaunchKernelGGL(zone_select_kernel<AZ>, app_grid(n_apps), block, 0, stream, table.slot_node, zones.n_zones, n_apps,
-                           d_apps, (const gf_result*)buf.zres, (const uint32_t*)buf.zexec, buf.zexec_stride,
-                           (const double*)buf.zavg, d_results, d_exec_nodes, (double*)nullptr);
+        hipLaunchKernelGGL(zone_select_kernel<AZ>, app_grid(B.n_apps), block, 0, B.stream, table.slot_node, zones.n_zones, B.n_apps,
+                           B.d_apps, (const gf_result*)buf.zres, (const uint32_t*)B.d_zexec, B.half,
+                           (const double*)buf.zavg, B.d_results, B.d_exec_nodes, (double*)nullptr);
         return hipGetLastError();
     });
 }
 
-hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const NodeTable& table, const SparseTable& gpu_view, const ZoneTable& zones,
-                                  const int64_t* d_sched, uint32_t* d_zexec, uint64_t zexec_stride, uint32_t n_apps,
-                                  const gf_app* d_apps, gf_result* d_results, uint32_t* d_exec_nodes, uint32_t* d_scratch,
-                                  uint64_t scratch_half, hipStream_t stream, uint8_t* d_feasible, uint32_t* d_feasible_sync,
-                                  bool eff_nonneg) {
-    if (n_apps == 0) return hipSuccess;
-    if (d_feasible != nullptr && d_feasible_sync == nullptr) return hipErrorInvalidValue;
-    const uint32_t nonneg = eff_nonneg ? 1u : 0u;
+hipError_t launch_fit_zoned_fused(int inner_algo, bool az_aware, const FitBatch& B) {
+    if (B.n_apps == 0) return hipSuccess;
+    const FeasibleOut& F = B.feasible;
+    if (F.d_bytes != nullptr && F.d_words == nullptr) return hipErrorInvalidValue;
     if (inner_algo != GF_ALGO_TIGHTLY_PACK && inner_algo != GF_ALGO_MINIMAL_FRAGMENTATION) return hipErrorInvalidValue;
     if (az_aware && inner_algo != GF_ALGO_TIGHTLY_PACK) return hipErrorInvalidValue;
-    if (zones.n_zones + (az_aware ? 1u : 0u) > 64u) return hipErrorInvalidValue;
-    const dim3 grid(n_apps), grid_feas(n_apps + 1) /* + the collecting workgroup */, block(kWave * kFusedWaves);
-    // feasibility only (gf_fit_feasible): d_results is not written, d_exec_nodes receives nothing; d_feasible / d_feasible_sync
-    // as for launch_fit_independent
+    if (B.zones.n_zones + (az_aware ? 1u : 0u) > 64u) return hipErrorInvalidValue;
+    const dim3 grid(B.n_apps), grid_feas(B.n_apps + 1) /* + the collecting workgroup */, block(kWave * kFusedWaves);
     auto fused = [&](auto A, auto AZ) {
-        if (d_feasible != nullptr)
-            hipLaunchKernelGGL((fit_zoned_fused_kernel<A, AZ, true>), grid_feas, block, 0, stream, table, gpu_view, zones, d_sched,
-                               n_apps, d_apps, reinterpret_cast<gf_result*>(d_feasible), d_feasible_sync, d_zexec, zexec_stride,
-                               d_scratch, scratch_half, nonneg);
+        if (F.d_bytes != nullptr)  // (no result record, no expanded placement: d_results and d_exec_nodes are not read)
+            hipLaunchKernelGGL((fit_zoned_fused_feasible_kernel<A, AZ>), grid_feas, block, 0, B.stream, B.table, B.gpu_view, B.zones, B.d_sched,
+                               B.n_apps, B.d_apps, F.d_bytes, F.d_words, B.d_zexec, B.half, B.d_scratch, B.half, F.eff_nonneg ? 1u : 0u);
         else
-            hipLaunchKernelGGL((fit_zoned_fused_kernel<A, AZ, false>), grid, block, 0, stream, table, gpu_view, zones, d_sched,
-                               n_apps, d_apps, d_results, d_exec_nodes, d_zexec, zexec_stride, d_scratch, scratch_half, 0u);
+            hipLaunchKernelGGL((fit_zoned_fused_kernel<A, AZ>), grid, block, 0, B.stream, B.table, B.gpu_view, B.zones, B.d_sched, B.n_apps,
+                               B.d_apps, B.d_results, B.d_exec_nodes, B.d_zexec, B.half, B.d_scratch, B.half);
         return hipGetLastError();
     };
     using TP = std::integral_constant<int, GF_ALGO_TIGHTLY_PACK>;

@@ -20,17 +20,6 @@
 constexpr int kScanZones = 64;
 constexpr int32_t kScanNoDriver = INT32_MIN;  // "no fitting driver candidate seen"
 
-struct ScanArgs {
-    const int64_t* alloc;         // 3 * n_nodes: cpu | mem | gpu (gf_cluster_set)
-    const int64_t* over;          // 3 * n_nodes, or nullptr: no overhead
-    const uint32_t* zone;         // n_nodes zone ids below kScanZones (ZONED only)
-    const uint8_t* select;        // n_nodes, or nullptr: every node
-    uint32_t n_nodes;
-    uint32_t n_apps;
-    const gf_app* apps;
-    uint8_t* out;                 // n_apps HasCapacity bytes
-};
-
 struct ScanShared {
     unsigned long long s[kWavesPerBlock][kScanZones];  // S_z
     int32_t best[kWavesPerBlock][kScanZones];          // the largest cap' - cap over the zone's fitting driver candidates
@@ -139,19 +128,6 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void cluster_scan_kernel(Sca
 // 64 words (4 096 nodes) at a time — lane l loads the word of chunk 64 g + l, one coalesced 512-byte load — and visits the chunks
 // whose word is not zero, in ascending order; the chunk's word reaches every lane through read_lane.  A zero word costs nothing
 // beyond that load: the columns of the other instance groups are never read.
-
-struct ScanSetsArgs {
-    const int64_t* alloc;         // 3 * n_nodes: cpu | mem | gpu (gf_cluster_set)
-    const int64_t* over;          // 3 * n_nodes, or nullptr: no overhead
-    const uint32_t* zone;         // n_nodes zone ids below kScanZones (ZONED only)
-    const uint64_t* set_words;    // n_sets * n_words; no bit at or beyond n_nodes (the entry point checks)
-    const uint32_t* app_set;      // n_apps row numbers below n_sets (the entry point checks)
-    uint32_t n_nodes;
-    uint32_t n_words;             // W
-    uint32_t n_apps;
-    const gf_app* apps;
-    uint8_t* out;                 // n_apps HasCapacity bytes
-};
 
 template <bool ZONED>
 __global__ __launch_bounds__(kWave* kWavesPerBlock) void cluster_scan_sets_kernel(ScanSetsArgs A) {

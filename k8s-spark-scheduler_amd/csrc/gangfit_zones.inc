@@ -495,23 +495,24 @@ __device__ __forceinline__ Decision wave_decide_zones(const NodeTable& T, const 
     return best;
 }
 
-// FEAS (gf_fit_feasible): `results` is an array of n_apps bytes that receives HasCapacity through the grid's last workgroup,
-// `exec_nodes` the collection words (feasible_announce / feasible_collect in gangfit_kernels.hip); the winner's placement is
-// not expanded and no result record is written.
+// FEAS (gf_fit_feasible; fit_zoned_fused_feasible_kernel): answers.bytes receive HasCapacity through the grid's last workgroup
+// and the collection words answers.words (FitOut, feasible_announce / feasible_collect in gangfit_kernels.hip); the winner's
+// placement is not expanded — exec_nodes is not read — and no result record is written.
 template <int ALGO, bool AZ_AWARE, bool FEAS>
-__global__ __launch_bounds__(kWave* kFusedWaves, ALGO == GF_ALGO_MINIMAL_FRAGMENTATION ? 4 : 1) void fit_zoned_fused_kernel(
-    NodeTable T, SparseTable G, ZoneTable Z, const int64_t* __restrict__ sched, uint32_t n_apps, const gf_app* __restrict__ apps,
-    gf_result* __restrict__ results, uint32_t* __restrict__ exec_nodes, uint32_t* __restrict__ zexec, uint64_t zexec_stride,
-    uint32_t* __restrict__ scratch, uint64_t scratch_half, uint32_t eff_nonneg) {
+__device__ __forceinline__ void fit_zoned_fused_body(NodeTable T, SparseTable G, ZoneTable Z, const int64_t* sched,
+                                                     uint32_t n_apps, const gf_app* apps, const FitOut<FEAS>& answers,
+                                                     uint32_t* exec_nodes, uint32_t* zexec, uint64_t zexec_stride, uint32_t* scratch,
+                                                     uint64_t scratch_half, uint32_t eff_nonneg) {
     __shared__ FusedShared sh;
     const uint32_t tid = threadIdx.x;
     const int lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t a = blockIdx.x;
-    if (FEAS && a == n_apps) {  // the collecting workgroup (launch_fit_zoned_fused appends it)
-        if (wave == 0) feasible_collect(exec_nodes, reinterpret_cast<uint32_t*>(results), n_apps, lane);
-        return;
-    }
+    if constexpr (FEAS)
+        if (a == n_apps) {  // the collecting workgroup (launch_fit_zoned_fused appends it)
+            if (wave == 0) feasible_collect(answers, n_apps, lane);
+            return;
+        }
     if (a >= n_apps) return;
     const uint32_t n_zone_cand = Z.n_zones;
     const uint32_t n_cand = n_zone_cand + (AZ_AWARE ? 1u : 0u);  // the launcher guarantees n_cand <= 64
@@ -581,23 +582,38 @@ __global__ __launch_bounds__(kWave* kFusedWaves, ALGO == GF_ALGO_MINIMAL_FRAGMEN
         }
     if (AZ_AWARE && best < 0 && sh.feas[n_zone_cand]) best = (int32_t)n_zone_cand;  // az_aware_pack_tightly.go:33-37
     const bool feasible = best >= 0;
-    if (FEAS) {
-        if (tid == 0) feasible_announce(exec_nodes, a, feasible);
-        return;
+    if constexpr (FEAS) {
+        if (tid == 0) feasible_announce(answers.words, a, feasible);
+    } else {
+        if (feasible) {
+            const uint32_t* src = zexec + (size_t)best * zexec_stride + app.exec_off;
+            uint32_t* dst = exec_nodes + app.exec_off;
+            for (int64_t i = tid; i < K; i += kWave * kFusedWaves) dst[i] = T.slot_node[src[i]];
+        }
+        if (tid == 0) {
+            gf_result r;
+            r.has_capacity = feasible ? 1 : 0;
+            r.driver_node = feasible ? T.slot_node[sh.ds[best]] : GF_NO_NODE;
+            r.exec_len = feasible ? (uint32_t)K : 0u;
+            r.evaluated = 1;
+            answers.results[a] = r;
+        }
     }
-    if (feasible) {
-        const uint32_t* src = zexec + (size_t)best * zexec_stride + app.exec_off;
-        uint32_t* dst = exec_nodes + app.exec_off;
-        for (int64_t i = tid; i < K; i += kWave * kFusedWaves) dst[i] = T.slot_node[src[i]];
-    }
-    if (tid == 0) {
-        gf_result r;
-        r.has_capacity = feasible ? 1 : 0;
-        r.driver_node = feasible ? T.slot_node[sh.ds[best]] : GF_NO_NODE;
-        r.exec_len = feasible ? (uint32_t)K : 0u;
-        r.evaluated = 1;
-        results[a] = r;
-    }
+}
+// The two parameter lists of that body: the batch proper, and feasibility only.
+template <int ALGO, bool AZ_AWARE>
+__global__ __launch_bounds__(kWave* kFusedWaves, ALGO == GF_ALGO_MINIMAL_FRAGMENTATION ? 4 : 1) void fit_zoned_fused_kernel(
+    NodeTable T, SparseTable G, ZoneTable Z, const int64_t* __restrict__ sched, uint32_t n_apps, const gf_app* __restrict__ apps,
+    gf_result* __restrict__ results, uint32_t* __restrict__ exec_nodes, uint32_t* __restrict__ zexec, uint64_t zexec_stride,
+    uint32_t* __restrict__ scratch, uint64_t scratch_half) {
+    fit_zoned_fused_body<ALGO, AZ_AWARE, false>(T, G, Z, sched, n_apps, apps, {results, nullptr}, exec_nodes, zexec, zexec_stride, scratch, scratch_half, 0u);
+}
+template <int ALGO, bool AZ_AWARE>
+__global__ __launch_bounds__(kWave* kFusedWaves, ALGO == GF_ALGO_MINIMAL_FRAGMENTATION ? 4 : 1) void fit_zoned_fused_feasible_kernel(
+    NodeTable T, SparseTable G, ZoneTable Z, const int64_t* __restrict__ sched, uint32_t n_apps, const gf_app* __restrict__ apps,
+    uint8_t* __restrict__ bytes, uint32_t* __restrict__ words, uint32_t* __restrict__ zexec, uint64_t zexec_stride,
+    uint32_t* __restrict__ scratch, uint64_t scratch_half, uint32_t eff_nonneg) {
+    fit_zoned_fused_body<ALGO, AZ_AWARE, true>(T, G, Z, sched, n_apps, apps, {bytes, words}, nullptr, zexec, zexec_stride, scratch, scratch_half, eff_nonneg);
 }
 
 // ComputePackingEfficiencies for ONE result in node-index space: phase 1 scatters the `reserved` map, phase 2 (one

@@ -1,6 +1,8 @@
 """gf_fit_feasible: the feasibility-only independent batch (what UnschedulablePodMarker reads: `!packingResult.HasCapacity`,
 internal/extender/unschedulablepods.go:132-166).  Same decision code as gf_fit_batch(GF_MODE_INDEPENDENT); only one byte per
 application crosses the host link."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -145,3 +147,122 @@ def test_feasible_on_the_four_kernel_zone_route(algo, route):
             fits = ctx.fit_feasible(algo, gangfit.make_apps(drv, exe, k))
             assert np.array_equal(fits, np.asarray(ref.results["has_capacity"]).astype(bool))
             assert fits.any()
+
+
+# ---- the collection's word edges, its words between calls, the staging modes and the counters' slot.  One congested 130-node
+# cluster (two full 64-slot chunks and a partial one) and one queue of 257 applications; a test takes a prefix of it — an
+# independent decision does not depend on the rest of its batch, so the oracle's answers for the whole queue serve every prefix.
+# Seed 0xFEA7, on the oracle: 74 of the 257 fit under each plain packer (72 of the first 255), 74 / 51 / 51 under packers 3 / 4 / 5
+# on the three zones; applications 0 .. 4 answer 1 0 1 0 0 and 252 .. 256 answer 0 1 1 1 1, so the first and the last word of the
+# collection both carry the two values.
+_EDGE_SIZES = (2, 3, 4, 5, 255, 256, 257)  # byte positions within a word; both sides of one 64-lane pass of feasible_collect (256)
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_problem():
+    w, s = _congested(130, 257, 0xFEA7)
+    zone = (wl.splitmix64(0xA7, len(s.avail), 9) % np.uint64(3)).astype(np.uint32)
+    return w, s, zone, wl.reference_node_order(s.avail, zone), gangfit.make_apps(w.drv, w.exe, w.k, w.flags)
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_oracle(algo):
+    w, s, _, _, _ = _edge_problem()
+    return ob.fit_independent(algo, s.avail, ob.make_apps(w.drv, w.exe, w.k, w.flags), s.driver_order, s.exec_order)
+
+
+def _edge_install(ctx, algo):
+    """The snapshot of _edge_problem as packer `algo` needs it (zones and the zone-ranked order for packers 3, 4, 5)."""
+    _, s, zone, order, _ = _edge_problem()
+    ctx.set_snapshot(s.avail, s.sched)
+    if algo >= 3:
+        ctx.set_zones(zone)
+        ctx.set_orders(order, order)
+    else:
+        ctx.set_orders(s.driver_order, s.exec_order)
+
+
+def _has_capacity(batch):
+    return np.asarray(batch.results["has_capacity"]).astype(bool)
+
+
+@pytest.mark.parametrize("n_apps", _EDGE_SIZES)
+@pytest.mark.parametrize("algo", [0, 1, 2])
+def test_feasible_word_edges_plain_packers(gf_ctx, algo, n_apps):
+    apps = _edge_problem()[4][:n_apps]
+    _edge_install(gf_ctx, algo)
+    fits = gf_ctx.fit_feasible(algo, apps)
+    assert np.array_equal(fits, _has_capacity(gf_ctx.fit_batch(IND, algo, apps)))
+    assert np.array_equal(fits, _has_capacity(_edge_oracle(algo))[:n_apps])
+    if n_apps >= 255:
+        assert fits.any() and not fits.all()
+
+
+@pytest.mark.parametrize("n_apps", _EDGE_SIZES)
+@pytest.mark.parametrize("algo", [3, 4, 5])
+def test_feasible_word_edges_zone_aware_packers(gf_ctx, algo, n_apps):
+    apps = _edge_problem()[4][:n_apps]
+    _edge_install(gf_ctx, algo)
+    fits = gf_ctx.fit_feasible(algo, apps)
+    assert np.array_equal(fits, _has_capacity(gf_ctx.fit_batch(IND, algo, apps)))
+    if n_apps >= 255:
+        assert fits.any() and not fits.all()
+
+
+@pytest.mark.parametrize("algo", [0, 3])
+def test_feasible_words_return_to_zero_between_calls(algo):
+    """257 applications, then 3, then the full batch of the same 3, then 257 again, on one context: a collection word that a call
+    left set, or an output that two routes shared, would show in the next answer."""
+    apps = _edge_problem()[4]
+    with gangfit.Context(0) as c:
+        _edge_install(c, algo)
+        first = c.fit_feasible(algo, apps)
+        few = c.fit_feasible(algo, apps[:3])
+        full = c.fit_batch(IND, algo, apps[:3])
+        again = c.fit_feasible(algo, apps)
+        assert first.any() and not first.all()
+        assert np.array_equal(few, first[:3]) and np.array_equal(few, _has_capacity(full))
+        assert np.array_equal(again, first)
+        assert np.array_equal(first, _has_capacity(c.fit_batch(IND, algo, apps)))
+        if algo < 3:
+            ref = _edge_oracle(algo)
+            assert np.array_equal(first, _has_capacity(ref))
+            assert np.array_equal(full.results, ref.results[:3])
+            for a in np.nonzero(_has_capacity(ref)[:3])[0]:
+                assert np.array_equal(full.placement(int(a))[2], ref.placement(int(a))[2])
+        else:  # the oracle of the zone-aware packer, on the same three applications
+            w, s, zone, order, _ = _edge_problem()
+            ref = ob.fit_independent(ob.ALGO_AZ_AWARE_TIGHTLY_PACK, s.avail, ob.make_apps(w.drv[:3], w.exe[:3], w.k[:3], w.flags[:3]),
+                                     order, order, sched=s.sched, zone=zone)
+            assert np.array_equal(full.results, ref.results)
+            for a in np.nonzero(_has_capacity(ref))[0]:
+                assert np.array_equal(full.placement(int(a))[2], ref.placement(int(a))[2])
+
+
+@pytest.mark.parametrize("options", [{"feasible_announce": 0}, {"zero_copy": 0}], ids=["feasible_announce=0", "zero_copy=0"])
+@pytest.mark.parametrize("algo", [1, 4])
+def test_feasible_word_edges_in_both_staging_modes(algo, options):
+    apps = _edge_problem()[4]
+    with gangfit.Context(0, options=options) as c:
+        _edge_install(c, algo)
+        fits = c.fit_feasible(algo, apps)
+        assert np.array_equal(fits, _has_capacity(c.fit_batch(IND, algo, apps)))
+        if algo < 3:
+            assert np.array_equal(fits, _has_capacity(_edge_oracle(algo)))
+        assert fits.any() and not fits.all()
+
+
+def test_scan_counters_arrive_and_feasible_leaves_them_alone():
+    """The counters of a plain independent batch still arrive, and a feasibility call — whose collection words once travelled in
+    the counters' parameter — neither counts nor disturbs them."""
+    apps = _edge_problem()[4]
+    with gangfit.Context(0) as c:
+        _edge_install(c, 0)
+        c.scan_stats(enable=True, reset=True)
+        c.fit_batch(IND, 0, apps)
+        counted = c.scan_stats(enable=True, reset=False)
+        assert counted[0] > 0 and counted[1] > 0
+        c.fit_feasible(0, apps)
+        assert c.scan_stats(enable=True, reset=True) == counted
+        c.fit_batch(IND, 0, apps)
+        assert c.scan_stats(enable=True, reset=False) == counted

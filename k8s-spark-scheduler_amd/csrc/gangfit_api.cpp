@@ -59,6 +59,7 @@ int view_refresh(gf_ctx* v) {
     v->d_gidx.alias(p->d_gidx);
     v->d_gmask.alias(p->d_gmask);
     v->d_nsnap.alias(p->d_nsnap);
+    v->d_nquad.alias(p->d_nquad);
     v->d_ncmax.alias(p->d_ncmax);
     v->d_sched.alias(p->d_sched);
     v->d_node_tab.alias(p->d_node_tab);
@@ -285,6 +286,7 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->d_capmat.release();
     ctx->d_mfhist.release();
     ctx->d_nsnap.release();
+    ctx->d_nquad.release();
     ctx->d_nwork.release();
     ctx->d_ncmax.release();
     ctx->d_ncmax_w.release();

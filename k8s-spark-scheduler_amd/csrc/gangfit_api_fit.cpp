@@ -30,6 +30,7 @@ NodeTable make_table(gf_ctx* ctx, int64_t* base) {
         t.ncpu = ctx->d_nsnap.ptr;
         t.nmem = t.ncpu + ctx->n_slots;
         t.ngpu = t.nmem + ctx->n_slots;
+        t.nquad = reinterpret_cast<const int4*>(ctx->d_nquad.ptr);  // (written with the columns: current whenever they are)
         for (int j = 0; j < 3; ++j) t.nunit[j] = ctx->unit[j] > 0 ? ctx->unit[j] : 1;
     }
     return t;

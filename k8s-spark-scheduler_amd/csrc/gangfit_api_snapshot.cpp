@@ -196,7 +196,7 @@ int gf_orders_set(gf_ctx* ctx, const uint32_t* driver_order, uint32_t n_d, const
     GF_HIP(ctx, ctx->h_index.reserve(z.index + z.zspan + 1));
     GF_HIP(ctx, ctx->h_masks.reserve(z.masks));
     GF_HIP(ctx, ctx->h_cmax.reserve(z.cmax));
-    GF_HIP(ctx, ctx->h_ntable.reserve(z.ntable));
+    GF_HIP(ctx, ctx->h_ntable.reserve(z.ntable + z.nquad));
     GF_HIP(ctx, ctx->h_gtab.reserve(z.gtab));
     GF_HIP(ctx, ctx->h_gidx.reserve(z.gidx));
     GF_HIP(ctx, ctx->h_zmasks.reserve(z.zmasks + z.gmask + 1));
@@ -208,6 +208,7 @@ int gf_orders_set(gf_ctx* ctx, const uint32_t* driver_order, uint32_t n_d, const
     t.masks = ctx->h_masks.ptr;
     t.cmax = ctx->h_cmax.ptr;
     t.ntable = ctx->h_ntable.ptr;
+    t.nquad = t.ntable + z.ntable;
     t.gtab = ctx->h_gtab.ptr;
     t.gidx = ctx->h_gidx.ptr;
     t.zmasks = ctx->h_zmasks.ptr;
@@ -221,6 +222,7 @@ int gf_orders_set(gf_ctx* ctx, const uint32_t* driver_order, uint32_t n_d, const
         GF_HIP(ctx, upload(ctx->d_nsnap, t.ntable, 3 * S, st));
         GF_HIP(ctx, ctx->d_nwork.reserve(3 * S));
         GF_HIP(ctx, upload(ctx->d_ncmax, t.ntable + 3 * S, 3 * C, st));
+        GF_HIP(ctx, upload(ctx->d_nquad, t.nquad, 4 * S, st));
     }
     GF_HIP(ctx, upload(ctx->d_cmax, t.cmax, 3 * C, st));
     GF_HIP(ctx, upload(ctx->d_masks, t.masks, 2 * C, st));
@@ -669,6 +671,7 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out,
     GF_HIP(ctx, ctx->d_nsnap.reserve(3 * S));
     GF_HIP(ctx, ctx->d_nwork.reserve(3 * S));
     GF_HIP(ctx, ctx->d_ncmax.reserve(3 * C));
+    GF_HIP(ctx, ctx->d_nquad.reserve(4 * S));
     gangfit::SnapshotFinalize f{};
     f.n_nodes = n;
     f.n_slots = n_slots;
@@ -696,6 +699,7 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out,
     f.d_zmasks = ctx->d_zmasks.ptr;
     f.d_nsnap = ctx->d_nsnap.ptr;
     f.d_ncmax = ctx->d_ncmax.ptr;
+    f.d_nquad = reinterpret_cast<int4*>(ctx->d_nquad.ptr);
     GF_HIP(ctx, ctx->h_bcols.reserve(6 * N + 8));
     GF_HIP(ctx, ctx->h_border.reserve(N + 16));
     // everything the host needs back is one range of sixteen words (SnapshotFinalize::d_scalars): the kernels write it into

@@ -308,7 +308,9 @@ struct gf_ctx {
     int64_t unit[3] = {1, 1, 1};
     int64_t nmax[3] = {0, 0, 0};  // largest |scaled value| per dimension: how far the units may still be refined per batch
     DeviceBuf<int32_t> d_nsnap, d_nwork, d_ncmax, d_ncmax_w;
-    PinnedBuf<int32_t> h_ntable;
+    DeviceBuf<int32_t> d_nquad;  // 4 * n_slots: d_nsnap and d_slot_node as one record {cpu, mem, gpu, node} per slot (NodeTable::nquad);
+                                 // written by whoever writes d_nsnap, in the same pass, and current exactly when d_nsnap is
+    PinnedBuf<int32_t> h_ntable;  // staging: the columns | their chunk maxima | the records
     bool fifo_generic = false;  // option "fifo_generic": chains run on the wide / generic global-memory kernels only
     bool force_general_layout = false;  // option "force_general_layout": gf_orders_set never merges the two orders
     uint32_t lds_budget = 0;   // bytes of LDS one workgroup may use

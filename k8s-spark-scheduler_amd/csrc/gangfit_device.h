@@ -48,6 +48,12 @@ struct NodeTable {
     const int32_t* nmem = nullptr;
     const int32_t* ngpu = nullptr;
     int64_t nunit[3] = {1, 1, 1};
+    // The same twin once more as ONE 16-byte record per slot, {ncpu[s], nmem[s], ngpu[s], slot_node[s]}, 16-byte aligned: what the
+    // resident worker's tightly-pack decisions read (NarrowView, gangfit_kernels.hip) — a slot's values and its node id are always
+    // wanted together there, and one address and one load bring them.  Exists exactly when the columns do.  (The last member:
+    // no other MEMBER's offset moves; the arguments behind a NodeTable move by eight bytes in every kernel that takes one, and
+    // WorkerKernargs, which embeds it, follows by construction.)
+    const int4* nquad = nullptr;
 };
 
 // Sparse-dimension view of the executor order for the independent batch (merged layout): the executor candidates that have
@@ -666,6 +672,7 @@ struct SnapshotFinalize {
     uint64_t* d_zmasks;         // 2 * n_zones * n_chunks: executor rows, then (from row n_zones) driver rows
     int32_t* d_nsnap;           // 3 * n_slots
     int32_t* d_ncmax;           // 3 * n_chunks
+    int4* d_nquad;              // n_slots records {cpu, mem, gpu, node}: d_nsnap and d_slot_node once more (NodeTable::nquad)
 };
 hipError_t launch_snapshot_finalize(const SnapshotFinalize& f, const uint32_t* d_sort_error, hipStream_t stream);
 struct CopyOut {  // three ranges of 32-bit words, any of them empty

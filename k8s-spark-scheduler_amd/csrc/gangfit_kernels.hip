@@ -219,22 +219,22 @@ struct InWorkerKernel {
     explicit constexpr InWorkerKernel() = default;
 };
 
-// The snapshot's scaled int32 twin (NodeTable::ncpu / nmem / ngpu) behind the same interface: twelve bytes per slot, 32-bit
-// compares.  Read-only (the resident worker's tightly-pack decisions; gangfit_worker.inc).  The chunk maxima stay the wide ones:
-// group 0 of the index is scaled once per launch by its user (Group0T<int32_t>); a chunk that is asked on its own (chunk_may_hold)
-// is compared in int64 against the request scaled back up.
+// The snapshot's scaled int32 twin as records (NodeTable::nquad: {cpu, mem, gpu, node} per slot, sixteen bytes) behind the same
+// interface: 32-bit compares, and a slot is ONE address and ONE 16-byte load that brings the node id along (kNodeWithValues: the
+// scans take the id from it instead of asking Orders::slot_node beside it).  Read-only (the resident worker's tightly-pack
+// decisions; gangfit_worker.inc).  The chunk maxima stay the wide ones: group 0 of the index is scaled once per launch by its
+// user (Group0T<int32_t>); a chunk that is asked on its own (chunk_may_hold) is compared in int64 against the request scaled back up.
 struct NarrowView {
-    const int32_t* cpu;
-    const int32_t* mem;
-    const int32_t* gpu;
+    const int4* quad;
     const uint64_t* xm;
     const uint64_t* dm;
     uint32_t n_chunks;
     static constexpr bool kCompactScan = true;
+    static constexpr bool kNodeWithValues = true;  // load(s, a0, a1, a2, node) exists
     // ONLY inside fit_worker_kernel (wide_here reads THAT kernel's argument segment): the constructor wants the kernel's token.
-    __device__ __forceinline__ NarrowView(const InWorkerKernel&, const int32_t* cpu_, const int32_t* mem_, const int32_t* gpu_,
-                                          const uint64_t* xm_, const uint64_t* dm_, uint32_t n_chunks_)
-        : cpu(cpu_), mem(mem_), gpu(gpu_), xm(xm_), dm(dm_), n_chunks(n_chunks_) {}
+    __device__ __forceinline__ NarrowView(const InWorkerKernel&, const int4* quad_, const uint64_t* xm_, const uint64_t* dm_,
+                                          uint32_t n_chunks_)
+        : quad(quad_), xm(xm_), dm(dm_), n_chunks(n_chunks_) {}
     // The wide maxima and the units are no members (eight scalar registers held through every decision) but read from the worker's
     // argument segment where a chunk asks for them (NodeTable::cmax: [3][n_chunks]).  Not cold, only less often read than the
     // columns: chunk_may_hold runs for the chunks behind group 0 (the headline's 157 chunks are three groups, so that is every
@@ -269,11 +269,18 @@ struct NarrowView {
     __device__ __forceinline__ uint64_t chunk_dmask(uint32_t c) const { return dm[c]; }
     __device__ __forceinline__ bool xcand(uint32_t s) const { return (xm[s >> 6] >> (s & 63)) & 1ull; }
     __device__ __forceinline__ bool dcand(uint32_t s) const { return (dm[s >> 6] >> (s & 63)) & 1ull; }
-    __device__ __forceinline__ void load(uint32_t s, int32_t& a0, int32_t& a1, int32_t& a2) const {
-        a0 = cpu[s];
-        a1 = mem[s];
-        a2 = gpu[s];
+    __device__ __forceinline__ void load(uint32_t s, int32_t& a0, int32_t& a1, int32_t& a2, uint32_t& node) const {
+        const int4 q = quad[s];
+        a0 = q.x;
+        a1 = q.y;
+        a2 = q.z;
+        node = (uint32_t)q.w;
     }
+    __device__ __forceinline__ void load(uint32_t s, int32_t& a0, int32_t& a1, int32_t& a2) const {
+        uint32_t node;
+        load(s, a0, a1, a2, node);
+    }
+    __device__ __forceinline__ uint32_t node_of(uint32_t s) const { return (uint32_t)quad[s].w; }
 };
 
 // FIFO chain: the first `lds_slots` slots of the (mutable) working table live in LDS — the front of the executor
@@ -397,6 +404,26 @@ struct Orders {
     }
     __device__ __forceinline__ uint32_t driver_slot(uint32_t i) const { return d_identity ? i : dslot[i]; }
 };
+
+// Slot j's values and the node id a placement on it names, requested together: from the one record of a view that keeps the id
+// with the values (kNodeWithValues), else the view's three values and Orders::slot_node beside them.
+template <class View, class = void>
+struct HasNodeWithValues {
+    static constexpr bool value = false;
+};
+template <class View>
+struct HasNodeWithValues<View, decltype((void)View::kNodeWithValues)> {
+    static constexpr bool value = true;
+};
+template <class View, class VAL>
+__device__ __forceinline__ void load_with_node(const View& V, const Orders& O, uint32_t j, VAL& a0, VAL& a1, VAL& a2, uint32_t& node) {
+    if constexpr (HasNodeWithValues<View>::value) {
+        V.load(j, a0, a1, a2, node);
+    } else {
+        V.load(j, a0, a1, a2);
+        node = O.slot_node[j];  // requested with the slot, not after the capacities are known
+    }
+}
 
 // ------------------------------------------------------------------------------------------------ emission
 
@@ -712,9 +739,10 @@ __device__ __forceinline__ int64_t wave_tight_scan_compact(const View& V, const 
                     a1 = pre.a1;
                     a2 = pre.a2;
                     node = pre.node;
-                } else {
+                } else if constexpr (SLOTS) {
                     V.load(j, a0, a1, a2);
-                    if (!SLOTS) node = O.slot_node[j];  // requested with the slot, not after the capacities are known
+                } else {
+                    load_with_node(V, O, j, a0, a1, a2, node);
                 }
                 if (j == ds) {
                     a0 -= app.drv0;
@@ -1020,18 +1048,26 @@ __device__ __forceinline__ Decision wave_decide(const View& V, const Orders& O, 
         const uint32_t id = (uint32_t)(bd < 0 ? 0 : bd) * kWave + lane, ix = (uint32_t)(pre.c < 0 ? 0 : pre.c) * kWave + lane;
         uint32_t dnode = GF_NO_NODE, dsub = GF_NO_NODE;
         if (bd >= 0 && id < limit) {
-            V.load(id, d0, d1, d2);
-            if (!SLOTS) dnode = O.slot_node[id];  // the result needs the driver's node id: not one more round trip at the end
+            if constexpr (SLOTS)
+                V.load(id, d0, d1, d2);
+            else
+                load_with_node(V, O, id, d0, d1, d2, dnode);  // the result needs the driver's node id: not one more round trip at the end
             if (sparse) dsub = gpu_view->sub_of_slot[id];  // where the driver's reservation lands in the compact table
         }
         if (pre.c >= 0 && ix < limit) {
-            if (pre.c != bd) V.load(ix, pre.a0, pre.a1, pre.a2);
-            if (!SLOTS) pre.node = O.slot_node[ix];
+            if constexpr (!SLOTS && HasNodeWithValues<View>::value) {
+                if (pre.c != bd) V.load(ix, pre.a0, pre.a1, pre.a2, pre.node);
+            } else {
+                if (pre.c != bd) V.load(ix, pre.a0, pre.a1, pre.a2);
+                if (!SLOTS) pre.node = O.slot_node[ix];
+            }
         }
         if (pre.c >= 0 && pre.c == bd) {
             pre.a0 = d0;
             pre.a1 = d1;
             pre.a2 = d2;
+            // (the driver's chunk again: its records are in hand, ids included — copied here, behind both requests)
+            if constexpr (!SLOTS && HasNodeWithValues<View>::value) pre.node = dnode;
         }
         uint32_t from = dc > (uint32_t)kWave ? (uint32_t)kWave * kWave : O.n_d;  // where the generic search resumes
         if (bd >= 0) {
@@ -1977,6 +2013,10 @@ hipError_t launch_fit_worker(gf_algo algo, const NodeTable& table, const SparseT
         const uint32_t n_cand = args.zones.n_zones + (algo == GF_ALGO_AZ_AWARE_TIGHTLY_PACK ? 1u : 0u);
         if (args.sched == nullptr || args.zones.xmask == nullptr || args.zones.dmask == nullptr || args.zones.n_zones == 0 || n_cand > 64u)
             return hipErrorInvalidValue;
+    }
+    if (algo == GF_ALGO_TIGHTLY_PACK && args.stats != nullptr) {  // gf_scan_stats is on: the instance that counts
+        hipLaunchKernelGGL(fit_worker_kernel<kWorkerCounting>, grid, block, 0, stream, table, gpu_view, args);
+        return hipGetLastError();
     }
     return with_worker_algo(algo, [&](auto A) {
         hipLaunchKernelGGL(fit_worker_kernel<A>, grid, block, 0, stream, table, gpu_view, args);

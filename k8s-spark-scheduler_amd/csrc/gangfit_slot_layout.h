@@ -48,6 +48,7 @@ struct LayoutSizes {
     size_t masks = 0;   // uint64 xmask | dmask, n_chunks each
     size_t cmax = 0;    // int64  [3][n_chunks]
     size_t ntable = 0;  // int32  [3][n_slots] | chunk maxima [3][n_chunks]
+    size_t nquad = 0;   // int32  [n_slots][4]: the twin again, one record {cpu, mem, gpu, node} per slot (NodeTable::nquad)
     size_t gtab = 0;    // int64  [3][n_gpad] | chunk maxima [3][n_gpad / 64]
     size_t gidx = 0;    // uint32 node of sub-slot (n_gpad) | sub-slot of slot (n_slots) | slot of sub-slot (n_gpad)
     size_t gmask = 0;   // uint64 [1 + n_zones][n_gpad / 64]: every sub-slot, then one row per zone
@@ -62,6 +63,7 @@ struct LayoutTables {
     uint64_t* masks = nullptr;
     int64_t* cmax = nullptr;
     int32_t* ntable = nullptr;
+    int32_t* nquad = nullptr;  // nullptr: not wanted (the columns alone)
     int64_t* gtab = nullptr;
     uint32_t* gidx = nullptr;
     uint64_t* gmask = nullptr;
@@ -211,8 +213,9 @@ inline void fill_general(const LayoutInput& in, LayoutPlan& p, const LayoutTable
     }
 }
 
-// narrow form: unit[j] = gcd of dimension j over the real slots; scaled magnitudes must stay below 2^30
-inline void fill_narrow(LayoutFacts& f, const int64_t* table, const uint32_t* slot_node, int32_t* nt) {
+// narrow form: unit[j] = gcd of dimension j over the real slots; scaled magnitudes must stay below 2^30.  nq (nullable): the same
+// values once more as one 16-byte record per slot, {cpu, mem, gpu, slot_node}, written in the pass that writes the columns.
+inline void fill_narrow(LayoutFacts& f, const int64_t* table, const uint32_t* slot_node, int32_t* nt, int32_t* nq = nullptr) {
     const uint32_t n_slots = f.n_slots, n_chunks = f.n_chunks;
     for (int j = 0; j < 3; ++j) {
         const int64_t* col = table + (size_t)j * n_slots;
@@ -248,6 +251,10 @@ inline void fill_narrow(LayoutFacts& f, const int64_t* table, const uint32_t* sl
                 if (mag > f.nmax[j]) f.nmax[j] = mag;
             }
             nt[(size_t)j * n_slots + s] = v32;
+            if (nq != nullptr) {
+                nq[4 * (size_t)s + j] = v32;
+                if (j == 0) nq[4 * (size_t)s + 3] = (int32_t)slot_node[s];
+            }
             int32_t& m = ncm[(size_t)j * n_chunks + (s >> 6)];
             m = v32 > m ? v32 : m;
         }
@@ -360,6 +367,7 @@ inline LayoutPlan plan_layout(const LayoutInput& in) {
     z.masks = 2 * C;
     z.cmax = 3 * C;
     z.ntable = 3 * S + 3 * C;
+    z.nquad = 4 * S;
     if (f.n_g) {
         z.gtab = 3 * G + 3 * (G / 64);
         z.gidx = 2 * G + S;
@@ -395,7 +403,7 @@ inline void fill_layout(const LayoutInput& in, LayoutPlan& p, const LayoutTables
     else
         fill_general(in, p, t);
     chunk_maxima(t.table, n_slots, f.n_chunks, t.cmax);  // chunk-maxima index over all slots (see NodeTable::cmax)
-    fill_narrow(f, t.table, slot_node, t.ntable);
+    fill_narrow(f, t.table, slot_node, t.ntable, t.nquad);
     if (p.sizes.sched)  // SchedulableResources in slot order (efficiencies); empty slots read 0
         for (int j = 0; j < 3; ++j)
             for (uint32_t s = 0; s < n_slots; ++s)

@@ -851,7 +851,8 @@ __global__ __launch_bounds__(4 * kReduceGroup) void finalize_reduce_kernel(Snaps
     }
 }
 
-// One thread per slot: the narrow (scaled int32) table + its chunk maxima, and the per-zone candidate masks.
+// One thread per slot: the narrow (scaled int32) table — as columns and as one record per slot (NodeTable::nquad) — + its chunk
+// maxima, and the per-zone candidate masks.
 __global__ __launch_bounds__(256) void finalize_narrow_zones_kernel(SnapshotFinalize f) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t c = s >> 6;
@@ -871,6 +872,7 @@ __global__ __launch_bounds__(256) void finalize_narrow_zones_kernel(SnapshotFina
         atomicOr(&f.d_scalars[1], 1u);
         if (f.h_out != nullptr) f.h_out[1] = 1u;
     }
+    if (s < ns) f.d_nquad[s] = make_int4(v[0], v[1], v[2], (int)node);  // the columns' values and the slot's node id as one record
     for (int j = 0; j < 3; ++j) {
         if (s < ns) f.d_nsnap[(size_t)j * ns + s] = v[j];
         int32_t m = s < ns ? v[j] : INT32_MIN;

@@ -80,9 +80,10 @@
 //                              group 0 (every application of a 10 000-node cluster gets there), and inside group 0 on the general
 //                              layout, in the fallback and behind a stale maximum: less often read than the columns, not cold;
 //                              the sparse view's size, asked only for a gang of gpu executors (sparse_serves)
-//   registers                  everything else: the narrow columns, xmask, dmask, n_chunks, slot_node, dslot, n_x, n_d, dev, sets,
-//                              leave_after, blocks_per_set, the stride constants, stats, and the operands of the int64 decision,
-//                              the sparse table, scratch, host, generation
+//   registers                  everything else: the narrow records (ONE pointer, NodeTable::nquad: {cpu, mem, gpu, node} per slot —
+//                              r10a below; three column pointers and slot_node before), xmask, dmask, n_chunks, dslot, n_x, n_d,
+//                              dev, sets, leave_after, blocks_per_set, the stride constants, stats, and the operands of the int64
+//                              decision (slot_node among them), the sparse table, scratch, host, generation
 // Measured on this code, parent and result alternately on one machine, seven runs each: spilled scalar registers 171 -> 112,
 // v_readlane on spill lanes inside the loop 510 -> 284; 724.9 k -> 696.5 k instructions per ticket at K = 2 000 (vector -17.6 k,
 // scalar -13.6 k, scalar-memory +2.8 k); 1 000-1 016 M -> 1 029-1 045 M decisions/s (medians +3.1 %, ranges apart); a window of
@@ -90,6 +91,25 @@
 // Measured and dropped: reading the int64 decision's operands (wide columns, SparseTable, scratch, host, generation) at their use
 // as well — that variant had 145 spilled registers and 437 in-loop spill reads, 3.8 k vector and 2.3 k scalar instructions per
 // ticket more than the same code without that part, and was no faster; on its own it was 1.2 % slower than the parent.
+
+// RECORDS (profiles/r10a_worker_quad_summary.md): a narrow decision loads about 2.3 chunks of 64 slots and wants a slot's three
+// values and its node id together every time; as four columns that was four global_load_dword behind five address computations and
+// a staircase of four waits, four base pointers live through the decision, and the slot_node pointer re-read from the argument
+// segment at three places.  The snapshot's twin now exists a second time as one 16-byte record per slot (written by both producers
+// of the twin in the pass that writes the columns), NarrowView holds that one pointer, and a chunk is one v_lshl_add_u64, one
+// global_load_dwordx4 and one wait; the node ids of the driver's chunk and of every scanned chunk — the driver's, the placements' —
+// come out of the same load (a driver found by wave_first_fitting_driver / wave_fallback: one more load of its record, behind the
+// decision).
+// Measured, parent and result alternately on one machine, seven runs each: 1 035-1 041 M -> 1 048-1 063 M decisions/s at K = 2 000
+// (medians +1.6 %, ranges apart); a window of twenty 402-420 M -> 405-418 M (medians 408.8 -> 414.9: no loss).  Spilled scalar
+// registers 112 -> 107; 97 VGPRs as before.
+// COUNTERS ONLY WHERE SOMEBODY READS THEM (same summary): fit_worker_kernel<tightly-pack> has nothing of xvis / dvis compiled in, the
+// host launches fit_worker_kernel<kWorkerCounting> while gf_scan_stats is on.  Measured against the tree without it, alternately,
+// seven runs each: 1 047-1 059 M -> 1 068-1 081 M decisions/s at K = 2 000 (medians +1.8 %, ranges apart); a window of twenty 411.7 ->
+// 417.1 M (medians; no loss).  Measured and dropped: the hand-out's fetch-and-add as ds_add_rtn_u64 in inline assembly under
+// `lane == 0` (without the compiler's one-lane reduction around it) — medians +1.1 % on the records alone (1 055-1 068 M against
+// 1 047-1 059 M) and +1.2 % on top of the counting split (1 077-1 091 M against 1 068-1 081 M): the ranges overlap both times, so it
+// does not pass the project's criterion; it also cost two VGPRs (97 -> 99).
 
 __device__ __forceinline__ unsigned long long sys_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -208,8 +228,15 @@ __device__ __forceinline__ Decision wave_decide_zones(const NodeTable& T, const 
                                                       uint32_t* cur, uint32_t* kept, int lane, unsigned long long& xvis,
                                                       unsigned long long& dvis, const uint32_t*& placed);
 
-template <int ALGO>
+// WHICH: the packer — or kWorkerCounting (tightly-pack with the scan counters).  The slots a decision visits (xvis / dvis, two 64-bit
+// wave-uniform accumulators that every chunk visit updates) are summed into W.stats by every instance but fit_worker_kernel<tightly-pack>,
+// which has nothing of the accumulation compiled in; the host launches fit_worker_kernel<kWorkerCounting> instead when gf_scan_stats
+// is on (launch_fit_worker).  The other packers' instances count whenever W.stats is set, as before.
+constexpr int kWorkerCounting = 100 + (int)GF_ALGO_TIGHTLY_PACK;
+template <int WHICH>
 __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(NodeTable T, SparseTable G, WorkerArgs W) {
+    constexpr int ALGO = WHICH == kWorkerCounting ? (int)GF_ALGO_TIGHTLY_PACK : WHICH;
+    constexpr bool COUNT = WHICH != (int)GF_ALGO_TIGHTLY_PACK;
     constexpr bool kZoned = ALGO == GF_ALGO_SINGLE_AZ_TIGHTLY_PACK || ALGO == GF_ALGO_AZ_AWARE_TIGHTLY_PACK;
     constexpr int kInner = kZoned ? (int)GF_ALGO_TIGHTLY_PACK : ALGO;  // the packer of one candidate view
     __shared__ uint32_t s_cnt[8];               // applications the workgroup has finished, per round (recycled every eight rounds)
@@ -302,7 +329,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     if (threadIdx.x < kCountSlots) s_cnt[threadIdx.x] = 0;
     if (threadIdx.x < 8) s_next[threadIdx.x] = 0ull;
     if (threadIdx.x < (uint32_t)kWorkerWaves) s_round[threadIdx.x] = 0;
-    const bool narrow_table = kNarrow && T.ncpu != nullptr;
+    const bool narrow_table = kNarrow && T.nquad != nullptr;
     if (wave == 0) {  // the tables do not change while the worker lives
         const Group0 g = load_group0(V, O, lane);
         s_g0[0][lane] = (unsigned long long)g.m0;
@@ -319,7 +346,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         }
     }
     // (the wide maxima and the units are no members of the narrow view: OPERANDS above)
-    const NarrowView VN(InWorkerKernel{}, T.ncpu, T.nmem, T.ngpu, T.xmask, T.dmask, T.n_chunks);
+    const NarrowView VN(InWorkerKernel{}, T.nquad, T.xmask, T.dmask, T.n_chunks);
     // lane l < 6 scales request word l of a record: dimension l mod 3
     const int64_t unit_l = T.nunit[lane % 3 == 0 ? 0 : (lane % 3 == 1 ? 1 : 2)];
     const double rcp_l = kNarrow ? fast_rcp((double)unit_l) : 0.0;
@@ -520,6 +547,8 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                     app_off = napp.exec_off;
                     dec = wave_decide<ALGO, NarrowView, false>(VN, O, napp, (direct ? exec_nodes : priv) + app_off, scratch + app_off,
                                                                scratch + half + app_off, lane, xvis, dvis, &g0n, nullptr, direct);
+                    // (a driver found behind the first chunk: its node id from its record, like every other id of this decision)
+                    if (dec.feasible && dec.ds_node == GF_NO_NODE) dec.ds_node = VN.node_of(dec.ds);
                     decided = true;
                 }
             }
@@ -547,9 +576,11 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                                                                  direct);
                 }
             }
-            if (W.stats != nullptr && lane == 0) {
-                atomicAdd(&W.stats->exec_slots_visited, xvis);
-                atomicAdd(&W.stats->driver_slots_visited, dvis);
+            if constexpr (COUNT) {
+                if (W.stats != nullptr && lane == 0) {
+                    atomicAdd(&W.stats->exec_slots_visited, xvis);
+                    atomicAdd(&W.stats->driver_slots_visited, dvis);
+                }
             }
             if (dec.feasible && !direct) {
                 // this wavefront's own stores, read back through its CU's L1 / L2 and sent out write-through
@@ -640,3 +671,4 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     }
     if (lane == 0) __hip_atomic_store(&s_round[wave], kRoundGone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // never in anybody's way
 }
+

@@ -348,9 +348,8 @@ __device__ __forceinline__ int32_t* chain_ckpt_slot(const ChainCkpt& ck, uint32_
 // re-tests the app's own two shapes on the chunks it touched, and any wave that evaluates a flagged chunk and finds no
 // fit clears the bit.  A stale 1 therefore costs one cheap chunk test, once; a 0 is always exact.  Apps whose shape did
 // not get an id (more than kMaxShapes distinct shapes, hash-tag collision) use the chunk-maxima masks.
-constexpr uint32_t kMaxShapes = 64;
+// (kMaxShapes and kNoShape: gangfit_chain_lds.h — the zoned chain's LDS layout depends on them)
 constexpr uint32_t kShapeHashSlots = 128;
-constexpr uint32_t kNoShape = 0xFFFFFFFFu;
 
 struct ShapeEntry {  // 16 bytes: hash-table entry during dedup
     int32_t v0, v1, v2;

@@ -81,12 +81,12 @@ struct MfShared {
     uint32_t ds[16];
     uint32_t nruns[16];
     double mx[16];
-    int32_t shape_x[kZShapes][3];
-    int32_t shape_d[kZShapes][3];
+    int32_t shape_x[kMaxShapes][3];
+    int32_t shape_d[kMaxShapes][3];
     // (this struct sits next to the per-view masks of a 100 000-node table with 76 bytes to spare: what it gains it must lose)
-    uint32_t shape_xm[kZShapes][3];  // narrow_magic multipliers of the executor shapes (the post-shifts follow from the requests)
+    uint32_t shape_xm[kMaxShapes][3];  // narrow_magic multipliers of the executor shapes (the post-shifts follow from the requests)
     uint32_t n_shape_x, n_shape_d;
-    int32_t total_cap[16][kZShapes];  // per candidate (at most 16 zones)
+    int32_t total_cap[16][kMaxShapes];  // per candidate (at most 16 zones)
     uint32_t lvl_total, pnext;
     unsigned long long row_ready;  // bit = executor shape id: its capacity-matrix row has been filled
     unsigned long long row_big;    // ... and holds a capacity >= kMfBins: no histogram for this shape
@@ -283,7 +283,7 @@ __device__ __forceinline__ bool mf_block_decide(const ZView& Z, uint32_t n_d, ui
                                                 uint32_t& nruns_out) {
     const NarrowHybridView& V = Z.V;
     const int32_t K = p.k;
-    const bool indexed = p.shape_x != kZNoShape;
+    const bool indexed = p.shape_x != kNoShape;
     nruns_out = 0;
     ds_out = 0;
     if (indexed && K > 0 && sh->total_cap[cand][p.shape_x] < K) return false;
@@ -866,7 +866,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
         sbx[i] = v;
         sbd[i] = v;
     }
-    for (uint32_t i = tid; i < 16 * kZShapes; i += BLOCK) sh->total_cap[i / kZShapes][i % kZShapes] = INT32_MAX;
+    for (uint32_t i = tid; i < 16 * kMaxShapes; i += BLOCK) sh->total_cap[i / kMaxShapes][i % kMaxShapes] = INT32_MAX;
     for (uint32_t i = tid; i < 512 * n_cand; i += BLOCK) fillh[i] = (i & 256u) ? kMfNoPos : 0;
     if (tid == 0) {
         sh->row_ready = 0ull;
@@ -1042,7 +1042,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
         // ---- the capacity-matrix row of this executor shape: filled on first use (every slot of the plain executor order,
         //      nothing reserved), by all wavefronts
         const int32_t* caprow = nullptr;
-        if (capmat != nullptr && app.shape_x != kZNoShape) {
+        if (capmat != nullptr && app.shape_x != kNoShape) {
             int32_t* row = capmat + (size_t)app.shape_x * T.n_slots;
             if (((sh->row_ready >> (app.shape_x & 63u)) & 1ull) == 0ull) {  // workgroup-uniform
                 for (uint32_t cc = wave; cc < nc; cc += NW) {
@@ -1315,14 +1315,7 @@ __global__ __launch_bounds__(kWave* NWV) void fit_fifo_minfrag_lds_kernel(
         for (int i = 0; i < 6; ++i) stats->fifo_phase_cycles[i] = ph[i];
     }
     if (lane == 0 && stats != nullptr && xvis != 0) atomicAdd(&stats->exec_slots_visited, xvis);
-    for (uint32_t r = a + tid; r < n_apps; r += BLOCK) {
-        gf_result z;
-        z.has_capacity = 0;
-        z.driver_node = GF_NO_NODE;
-        z.exec_len = 0;
-        z.evaluated = 0;
-        results[r] = z;
-    }
+    chain_mark_not_evaluated<BLOCK>(results, a, n_apps, tid);
     __syncthreads();
     const bool tip = RES && ck.tip != nullptr;  // (ChainCkpt::tip: the table this chain ended with, for the next Filter)
     for (uint32_t s = tid; s + 1 < T.n_slots; s += BLOCK) {

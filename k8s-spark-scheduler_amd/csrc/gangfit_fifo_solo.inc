@@ -1176,14 +1176,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_solo_kernel(NodeTable T, N
     __syncthreads();  // the helpers' dumps and wavefront 0's stores are done; everybody takes part in the epilogue
     // ---- epilogue, all wavefronts: apps behind an abort are reported as not evaluated; residuals back to the wide table
     const uint32_t a_end = sh->final_a;
-    for (uint32_t r = a_end + tid; r < n_apps; r += BLOCK) {
-        gf_result z;
-        z.has_capacity = 0;
-        z.driver_node = GF_NO_NODE;
-        z.exec_len = 0;
-        z.evaluated = 0;
-        results[r] = z;
-    }
+    chain_mark_not_evaluated<BLOCK>(results, a_end, n_apps, tid);
     // four slots per thread and trip, every value requested before the first is stored: the tail of a table larger than the LDS
     // front comes from global memory, and a trip that waits for its own three loads made this loop ~0.3 ms at 100 000 nodes
     constexpr int kEpi = 4;

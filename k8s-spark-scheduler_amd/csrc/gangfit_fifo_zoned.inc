@@ -25,37 +25,8 @@
 // later app.  Shapes are deduplicated while the app records are staged (n_shapes per role, as many as LDS allows;
 // later shapes scan unindexed).
 
-constexpr uint32_t kZRunMax = 64;   // runs per candidate kept in LDS
-constexpr int kZStage = 32;         // app records (wide + narrow) staged per refill
-constexpr uint32_t kZShapes = 64;   // distinct request shapes indexed per role
-constexpr uint32_t kZNoShape = 0xFFFFFFFFu;
+// (kZRunMax, kZStage, kMaxShapes, ZonedShared and the LDS layout, ZonedLds: gangfit_chain_lds.h)
 
-struct ZonedShared {
-    // per candidate view, two copies indexed by the application's parity: with one barrier per application (see the
-    // chain loop) a fast wavefront publishes application a + 1 while a slow one still reads the results of application a
-    int32_t feas[2][16];
-    uint32_t ds[2][16];
-    uint32_t nruns[2][16];
-    double mx[2][16];   // avg.Max of the candidate's placement: the reassociated sum (see wave_runs_avg_max<.., false>) ...
-    double me[2][16];   // ... and the bound of its distance from the reference's slice-order sum (+inf: not bounded)
-    double mxe[2][16];  // the slice-order sums, published only when the bounds do not separate the candidates
-    int32_t shape_x[kZShapes][3];  // executor request shapes seen so far (scaled)
-    int32_t shape_d[kZShapes][3];
-    uint32_t n_shape_x, n_shape_d;
-    // Upper bound on the total executor capacity of a (candidate view, executor shape): set whenever a full scan came
-    // out short (then every node's capacity was below K, so the clamped sum WAS the total); capacities only fall during
-    // a chain, so a later gang of that shape with K above the bound is infeasible in that view without any scan.
-    int32_t total_cap[17][kZShapes];  // always < K <= 2^20 when set; INT32_MAX = unknown
-    // commits performed by the helper wavefront: a + 1 once application a's usage has been subtracted (the winner's
-    // wavefront waits for it before its next scan; nobody else reads the slots of the winner's zone)
-    uint32_t commit_done;
-};
-
-inline size_t fifo_zoned_fixed_lds(uint32_t n_chunks, uint32_t n_views, uint32_t n_waves, uint32_t n_shapes) {
-    return (size_t)kZStage * (sizeof(gf_app) + sizeof(NApp)) + ((sizeof(ZonedShared) + 15) & ~(size_t)15) +
-           16 * (size_t)n_chunks * n_views + 12 * (size_t)n_chunks + 2 * 8 * (size_t)kZRunMax * n_waves +
-           2 * 8 * (size_t)n_shapes * n_views * ((n_chunks + 63) / 64) + 64;
-}
 // wavefronts of the workgroup: one per candidate view plus (while there is room) one that expands the winner's placement
 inline int fifo_zoned_waves(uint32_t n_cand) { return n_cand < 4 ? 4 : (n_cand < 8 ? 8 : 16); }
 
@@ -306,12 +277,12 @@ __device__ __forceinline__ void zshapes_assign(lds_u32* recs, uint32_t n_rec, ld
         y1 = tab_d[lane][1];
         y2 = tab_d[lane][2];
     }
-    uint32_t my_x = kZNoShape, my_d = kZNoShape;
+    uint32_t my_x = kNoShape, my_d = kNoShape;
     for (uint32_t i = 0; i < n_rec; ++i) {  // in queue order: ids are first-appearance ranks
         {
             const int32_t v0 = read_lane(e0, (int)i), v1 = read_lane(e1, (int)i), v2 = read_lane(e2, (int)i);
             const uint64_t hm = __ballot((uint32_t)lane < nx && x0 == v0 && x1 == v1 && x2 == v2);
-            uint32_t id = kZNoShape;
+            uint32_t id = kNoShape;
             if (hm) {
                 id = (uint32_t)(__ffsll((unsigned long long)hm) - 1);
             } else if (nx < n_max) {
@@ -331,7 +302,7 @@ __device__ __forceinline__ void zshapes_assign(lds_u32* recs, uint32_t n_rec, ld
         {
             const int32_t v0 = read_lane(d0, (int)i), v1 = read_lane(d1, (int)i), v2 = read_lane(d2, (int)i);
             const uint64_t hm = __ballot((uint32_t)lane < nd && y0 == v0 && y1 == v1 && y2 == v2);
-            uint32_t id = kZNoShape;
+            uint32_t id = kNoShape;
             if (hm) {
                 id = (uint32_t)(__ffsll((unsigned long long)hm) - 1);
             } else if (nd < n_max) {
@@ -561,26 +532,19 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
     const uint32_t n_cand = n_zone_cand + (AZ_AWARE ? 1u : 0u);  // host guarantees n_cand <= NW
     const uint32_t n_views = n_zone_cand + 1;                     // + the plain view (commit, az-aware candidate)
 
-    // ---- LDS carve
-    size_t off = 0;
-    lds_u8* stage = (lds_u8*)smem;
-    off += (size_t)kZStage * (sizeof(gf_app) + sizeof(NApp));
+    // ---- LDS carve (ZonedLds, gangfit_chain_lds.h)
+    const chain_lds::ZonedLds L = chain_lds::zoned_lds(lds_slots, nc, n_views, NW, n_shapes);
+    lds_u8* stage = (lds_u8*)(smem + L.stage);    // gf_app [kZStage]
+    lds_u8* nstage = (lds_u8*)(smem + L.nstage);  // NApp [kZStage]
     typedef __attribute__((address_space(3))) ZonedShared lds_zshared;  // typed: ds_* accesses, no flat/vmcnt waits
-    lds_zshared* sh = (lds_zshared*)(smem + off);
-    off += (sizeof(ZonedShared) + 15) & ~(size_t)15;
-    lds_u64* lmasks = (lds_u64*)(smem + off);  // [n_views][2][nc]: x then d
-    off += 16 * (size_t)nc * n_views;
-    lds_i32* lcm = (lds_i32*)(smem + off);
-    off += 12 * (size_t)nc;
-    lds_i32* lruns = (lds_i32*)(smem + off);   // [NW][2 = application parity][2][kZRunMax]: two lists per wavefront
-    off += 2 * 8 * (size_t)kZRunMax * NW;
-    const uint32_t nw = (nc + 63u) / 64u;      // 64-bit words per shape row
-    lds_u64* sbx = (lds_u64*)(smem + off);     // [n_views][n_shapes][nw] executor-shape index
-    off += 8 * (size_t)n_views * n_shapes * nw;
-    lds_u64* sbd = (lds_u64*)(smem + off);     // [n_views][n_shapes][nw] driver-shape index
-    off += 8 * (size_t)n_views * n_shapes * nw;
-    off = (off + 15) & ~(size_t)15;
-    lds_i32* ltab = (lds_i32*)(smem + off);    // [3][lds_slots]
+    lds_zshared* sh = (lds_zshared*)(smem + L.shared);
+    lds_u64* lmasks = (lds_u64*)(smem + L.lmasks);  // [n_views][2][nc]: x then d
+    lds_i32* lcm = (lds_i32*)(smem + L.lcm);
+    lds_i32* lruns = (lds_i32*)(smem + L.lruns);    // [NW][2 = application parity][2][kZRunMax]: two lists per wavefront
+    const uint32_t nw = (nc + 63u) / 64u;           // 64-bit words per shape row
+    lds_u64* sbx = (lds_u64*)(smem + L.sbx);        // [n_views][n_shapes][nw] executor-shape index
+    lds_u64* sbd = (lds_u64*)(smem + L.sbd);        // [n_views][n_shapes][nw] driver-shape index
+    lds_i32* ltab = (lds_i32*)(smem + L.ltab);      // [3][lds_slots]
 
     // ---- stage tables
     for (uint32_t i = tid; i < nc; i += BLOCK) {
@@ -606,7 +570,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
         sbx[i] = v;
         sbd[i] = v;
     }
-    for (uint32_t i = tid; i < 17 * kZShapes; i += BLOCK) sh->total_cap[i / kZShapes][i % kZShapes] = INT32_MAX;
+    for (uint32_t i = tid; i < 17 * kMaxShapes; i += BLOCK) sh->total_cap[i / kMaxShapes][i % kMaxShapes] = INT32_MAX;
     if (tid == 0) {
         sh->n_shape_x = 0;
         sh->n_shape_d = 0;
@@ -665,7 +629,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             const uint32_t* gw = reinterpret_cast<const uint32_t*>(apps + a);
             const uint32_t* gn = reinterpret_cast<const uint32_t*>(napps + a);
             lds_u32* sw = (lds_u32*)stage;
-            lds_u32* sn = (lds_u32*)(stage + (size_t)kZStage * sizeof(gf_app));
+            lds_u32* sn = (lds_u32*)nstage;
             for (uint32_t i = tid; i < words; i += BLOCK) {
                 sw[i] = gw[i];
                 sn[i] = gn[i];
@@ -702,8 +666,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             w.flags = (uint32_t)((uint64_t)kf >> 32);
             w.exec_off = (uint64_t)rec[7];
         }
-        NAppR app = read_staged_napp(
-            (const lds_u4*)(stage + (size_t)kZStage * sizeof(gf_app) + (size_t)(a % kZStage) * sizeof(NApp)));
+        NAppR app = read_staged_napp((const lds_u4*)(nstage + (size_t)(a % kZStage) * sizeof(NApp)));
         // what steers the control flow as scalars (every lane read the same record): tests on them are scalar compares, not a
         // vector compare handed over to a branch
         app.k = (int32_t)uniform32((uint32_t)app.k);
@@ -715,7 +678,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
         const uint32_t par = a & 1u;
         R.l_slot = lruns + ((size_t)wave * 2 + par) * 2 * kZRunMax;
         R.l_cnt = R.l_slot + kZRunMax;
-        R.l_dummy = ltab + 3 * (size_t)lds_slots;  // two of the 64 spare bytes behind the table (fifo_zoned_fixed_lds); shared by all views: nobody reads them
+        R.l_dummy = (lds_i32*)(smem + L.spare_words);  // shared by all views: nobody reads them
         R.g_slot = spill + (size_t)(2 * wave) * spill_stride + app.exec_off;
         R.g_cnt = spill + (size_t)(2 * wave + 1) * spill_stride + app.exec_off;
 
@@ -734,11 +697,11 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             ZView ZV;
             ZV.V = zone_view ? view_of(wave) : plain;
             const uint32_t view = zone_view ? wave : n_zone_cand;
-            ZV.xrow = app.shape_x != kZNoShape ? sbx + ((size_t)view * n_shapes + app.shape_x) * nw : nullptr;
-            ZV.drow = app.shape_d != kZNoShape ? sbd + ((size_t)view * n_shapes + app.shape_d) * nw : nullptr;
+            ZV.xrow = app.shape_x != kNoShape ? sbx + ((size_t)view * n_shapes + app.shape_x) * nw : nullptr;
+            ZV.drow = app.shape_d != kNoShape ? sbd + ((size_t)view * n_shapes + app.shape_d) * nw : nullptr;
             const NarrowHybridView& V = ZV.V;
             bool feasible = false;
-            const bool indexed = app.shape_x != kZNoShape;
+            const bool indexed = app.shape_x != kNoShape;
             const bool hopeless = indexed && K > 0 && (int64_t)sh->total_cap[wave][app.shape_x] < K;
             const int64_t p0 = hopeless ? -1 : nwave_first_driver(ZV, T.n_d, app, lane);
             if (p0 >= 0) {
@@ -948,14 +911,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
             break;
         }
     }
-    for (uint32_t r = a + tid; r < n_apps; r += BLOCK) {  // apps behind an abort are reported as not evaluated
-        gf_result z;
-        z.has_capacity = 0;
-        z.driver_node = GF_NO_NODE;
-        z.exec_len = 0;
-        z.evaluated = 0;
-        results[r] = z;
-    }
+    chain_mark_not_evaluated<BLOCK>(results, a, n_apps, tid);
     __syncthreads();
     // residuals back to the wide working table (gf_residual_get reads it): value = scaled value * unit
     const bool tip = RES && ck.tip != nullptr;  // (ChainCkpt::tip: the table this chain ended with, for the next Filter)
@@ -973,11 +929,8 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_zoned_lds_kernel(
         chain_tip_store(ck, T.n_slots, T.n_slots - 1u, b0, b1, b2);
     }
     if (tid == 0 && chain_failed_at != nullptr) *chain_failed_at = failed_at;
-    if (tid == 0 && stats != nullptr) {  // wave 0: stage | decide | efficiency | barrier | select+emit+commit | barrier
-        stats->fifo_shader_cycles = __builtin_readcyclecounter() - t0_cycles;
-        stats->fifo_realtime_ticks = wall_clock64() - t0_real;
-        for (int i = 0; i < 6; ++i) stats->fifo_phase_cycles[i] = ph[i];
-    }
+    // wave 0: stage | decide | efficiency | barrier | select+emit+commit | barrier
+    if (tid == 0 && stats != nullptr) chain_write_clocks(stats, t0_cycles, t0_real, ph);
 }
 
 // Follow-up of fit_fifo_zoned_lds_kernel: slot ids -> the caller's node indices (results and placements).  One wave per

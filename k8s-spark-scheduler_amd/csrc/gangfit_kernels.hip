@@ -24,6 +24,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "gangfit_chain_lds.h"
 #include "gangfit_device.h"
 
 namespace gangfit {
@@ -1308,13 +1309,7 @@ __global__ __launch_bounds__(kWave* kWavesPerBlock) void fit_independent_kernel(
 
 // ------------------------------------------------------------------------------------------------ FIFO chain
 
-// Workgroup-level exchange of one 32-bit value per wave through LDS.  Two alternating buffers: one barrier per
-// exchange is enough (a wave can only be one exchange ahead of the slowest wave).  16 entries regardless of NW (entries
-// >= NW hold the identity) so that lanes 0..15 of every wave can combine them with 4 DPP steps instead of a serial loop.
-struct Exchange {
-    uint32_t first[2][16];
-    int32_t tot[2][16];
-};
+// (Exchange — one 32-bit value per wave through LDS, two alternating buffers — is declared in gangfit_chain_lds.h)
 constexpr uint32_t kNoPos = 0xFFFFFFFFu;
 
 // Minimum over the waves of a wave-uniform position (kNoPos = none).
@@ -1349,7 +1344,6 @@ __device__ __forceinline__ void block_scan(Exchange* X, int& xb, int32_t wave_to
     total = read_lane(x, 15);
 }
 
-constexpr int kAppStage = 32;  // app records staged into LDS per refill
 constexpr int kRefresh = 8;    // apps between refreshes of the dirty entries of the chunk-maxima index
 
 struct FifoShared {
@@ -1358,6 +1352,27 @@ struct FifoShared {
     uint32_t slow_ds;
     int64_t slow_pass1;
 };
+static_assert(sizeof(App) == kWideAppBytes && sizeof(FifoShared) == kFifoSharedBytes && sizeof(NApp) == kNAppBytes,
+              "gangfit_chain_lds.h sizes the chain kernels' LDS from these");
+
+// apps behind an abort are reported as not evaluated (every chain kernel's epilogue)
+template <uint32_t BLOCK>
+__device__ __forceinline__ void chain_mark_not_evaluated(gf_result* __restrict__ results, uint32_t a, uint32_t n_apps, uint32_t tid) {
+    for (uint32_t r = a + tid; r < n_apps; r += BLOCK) {
+        gf_result z;
+        z.has_capacity = 0;
+        z.driver_node = GF_NO_NODE;
+        z.exec_len = 0;
+        z.evaluated = 0;
+        results[r] = z;
+    }
+}
+__device__ __forceinline__ void chain_write_clocks(ScanStats* __restrict__ stats, unsigned long long t0_cycles, unsigned long long t0_real,
+                                                   const unsigned long long (&ph)[6]) {
+    stats->fifo_shader_cycles = __builtin_readcyclecounter() - t0_cycles;
+    stats->fifo_realtime_ticks = wall_clock64() - t0_real;
+    for (int i = 0; i < 6; ++i) stats->fifo_phase_cycles[i] = ph[i];
+}
 
 // State of one executor scan of the FIFO fast path (all fields workgroup-uniform except `hit`).
 struct FifoScan {
@@ -1470,15 +1485,16 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
     const unsigned long long t0_cycles = __builtin_readcyclecounter();
     const unsigned long long t0_real = wall_clock64();
 
-    // ---- LDS carve: table front | chunk maxima | exchange | shared scalars + staged apps
-    lds_i64* lcpu = (lds_i64*)smem;
-    lds_i64* lmem = lcpu + lds_slots;
-    lds_i64* lgpu = lmem + lds_slots;
-    lds_i64* lmax = lgpu + lds_slots;  // [3][n_chunks]
-    lds_u64* lxm = (lds_u64*)(lmax + 3 * (size_t)T.n_chunks);  // [2][n_chunks] candidate masks
-    Exchange* X = reinterpret_cast<Exchange*>(smem + 24 * ((size_t)lds_slots + T.n_chunks) + 16 * (size_t)T.n_chunks);
-    FifoShared* sh = reinterpret_cast<FifoShared*>(X + 1);
-    lds_u8* dirty = (lds_u8*)(sh + 1);  // [n_chunks] chunk touched by a commit since the last maxima refresh
+    // ---- LDS carve (WideChainLds): table front | chunk maxima | masks | exchange | shared scalars + staged apps | dirty
+    const chain_lds::WideChainLds L = chain_lds::wide_chain_lds(lds_slots, T.n_chunks);
+    lds_i64* lcpu = (lds_i64*)(smem + L.lcpu);
+    lds_i64* lmem = (lds_i64*)(smem + L.lmem);
+    lds_i64* lgpu = (lds_i64*)(smem + L.lgpu);
+    lds_i64* lmax = (lds_i64*)(smem + L.lmax);  // [3][n_chunks]
+    lds_u64* lxm = (lds_u64*)(smem + L.lxm);    // [2][n_chunks] candidate masks
+    Exchange* X = reinterpret_cast<Exchange*>(smem + L.exchange);
+    FifoShared* sh = reinterpret_cast<FifoShared*>(smem + L.shared);
+    lds_u8* dirty = (lds_u8*)(smem + L.dirty);  // [n_chunks] chunk touched by a commit since the last maxima refresh
     for (uint32_t s = tid; s < lds_slots; s += BLOCK) {
         lcpu[s] = T.cpu[s];
         lmem[s] = T.mem[s];
@@ -1719,15 +1735,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
             __syncthreads();
         GF_TICK(prof, ph, tp, 4)
     }
-    // apps behind an abort are reported as not evaluated
-    for (uint32_t r = a + tid; r < n_apps; r += BLOCK) {
-        gf_result z;
-        z.has_capacity = 0;
-        z.driver_node = GF_NO_NODE;
-        z.exec_len = 0;
-        z.evaluated = 0;
-        results[r] = z;
-    }
+    chain_mark_not_evaluated<BLOCK>(results, a, n_apps, tid);
     __syncthreads();
     // write the LDS-resident front of the working table back (gf_residual_get reads the global copy)
     for (uint32_t s = tid; s < lds_slots; s += BLOCK) {
@@ -1740,9 +1748,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
         if (stats != nullptr) {
             atomicAdd(&stats->exec_slots_visited, xvis);
             atomicAdd(&stats->driver_slots_visited, dvis);
-            stats->fifo_shader_cycles = __builtin_readcyclecounter() - t0_cycles;
-            stats->fifo_realtime_ticks = wall_clock64() - t0_real;
-            for (int i = 0; i < 6; ++i) stats->fifo_phase_cycles[i] = ph[i];
+            chain_write_clocks(stats, t0_cycles, t0_real, ph);
         }
     }
 }
@@ -2082,10 +2088,7 @@ hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ExecSca
     });
 }
 
-size_t fifo_v2_lds_bytes(uint32_t lds_slots, uint32_t n_chunks) {
-    return 24 * ((size_t)lds_slots + n_chunks) + 16 * (size_t)n_chunks + sizeof(Exchange) + sizeof(FifoShared) + 64 +
-           ((n_chunks + 15) & ~15u);
-}
+size_t fifo_v2_lds_bytes(uint32_t lds_slots, uint32_t n_chunks) { return chain_lds::wide_chain_lds(lds_slots, n_chunks).bytes; }
 size_t fifo_solo_lds_bytes(uint32_t lds_slots, uint32_t n_chunks) {
     const size_t nw = (n_chunks + 63u) / 64u, nwp = nw < 4 ? 4 : nw;
     size_t off = kFusedStage * sizeof(NApp) + sizeof(SoloShared) + 16 * (size_t)n_chunks + 8 * (size_t)kMaxShapes * nwp +
@@ -2307,7 +2310,7 @@ hipError_t launch_fit_fifo_generic(const GenericChain& chain, const ChainTables&
 }
 
 size_t fifo_zoned_lds_bytes(uint32_t lds_slots, uint32_t n_chunks, uint32_t n_zones, uint32_t n_cand, uint32_t n_shapes) {
-    return fifo_zoned_fixed_lds(n_chunks, n_zones + 1, (uint32_t)fifo_zoned_waves(n_cand), n_shapes) + 12 * (size_t)lds_slots;
+    return chain_lds::zoned_lds(lds_slots, n_chunks, n_zones + 1, (uint32_t)fifo_zoned_waves(n_cand), n_shapes).bytes;
 }
 
 hipError_t launch_fit_fifo_zoned_lds(bool az_aware, uint32_t lds_slots, uint32_t n_shapes, const ChainTables& tables, const ChainBatch& B) {
@@ -2315,7 +2318,7 @@ hipError_t launch_fit_fifo_zoned_lds(bool az_aware, uint32_t lds_slots, uint32_t
     const ZoneTable& zones = tables.zones;
     if (B.n_apps == 0) return hipSuccess;
     if (zones.n_zones + (az_aware ? 1u : 0u) > 16 || !table.d_identity) return hipErrorInvalidValue;
-    if (n_shapes == 0 || n_shapes > kZShapes) return hipErrorInvalidValue;
+    if (n_shapes == 0 || n_shapes > kMaxShapes) return hipErrorInvalidValue;
     // one wavefront per candidate view; the rest of the workgroup only helps with the prologue and shares every barrier and
     // the per-app control flow, i.e. takes issue slots from the views' wavefronts: no more wavefronts than views need
     const uint32_t n_cand = zones.n_zones + (az_aware ? 1u : 0u);
@@ -2351,7 +2354,7 @@ hipError_t launch_fit_fifo_minfrag_lds(const MinfragLdsChain& chain, const Chain
     const bool zoned = chain.zoned;
     const uint32_t lds_slots = chain.lds_slots, n_shapes = chain.n_shapes, n_idx = chain.n_idx;
     if (B.n_apps == 0) return hipSuccess;
-    if ((zoned && zones.n_zones > 16) || !table.d_identity || n_shapes == 0 || n_shapes > kZShapes || n_idx > n_shapes)
+    if ((zoned && zones.n_zones > 16) || !table.d_identity || n_shapes == 0 || n_shapes > kMaxShapes || n_idx > n_shapes)
         return hipErrorInvalidValue;
     int32_t* const d_hist = chain.d_capmat != nullptr ? chain.d_hist : nullptr;  // the histograms are patched together with the matrix
     // (no initialisation of d_hist: the row fill of a shape writes every bin of its histograms and first positions)

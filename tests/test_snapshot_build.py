@@ -311,7 +311,8 @@ def test_priority_sort_key_groups(gf_ctx, spread):
         alloc[:, 0] = rng.integers(0, 1 << 61, size=n) | 1
         c["zone"] = rng.integers(0, 4000, size=n).astype(np.uint32)
         c["n_zones"] = 4000
-    elif spread == "all-equal":   # no varying bit at all: the order is the name order
+    elif spread == "all-equal":   # every key equal: ONE pass over the one-bit zone field (wz = bits_of(n_zones) >= 1, so the
+                                  # kernel's zero-pass arm cannot be reached through the ABI); the order is the name order
         alloc[:] = alloc[0]
         c["zone"] = np.zeros(n, dtype=np.uint32)
         c["n_zones"] = 1

@@ -177,6 +177,9 @@ const char *gf_last_error(gf_ctx *ctx);
  *   "force_general_layout"   1: gf_orders_set never merges the two orders into one slot order
  *   "sort_fault"             1: fault injection — the priority sort's grid barrier cannot complete; gf_snapshot_build* then
  *                            returns GF_ERR_HIP ("the priority sort's grid barrier gave up") instead of installing anything
+ *   "update_fault"           fault injection — 1: the resident usage, 2: the resident overhead, 3: both are marked unknown, as a
+ *                            gf_usage_apply / gf_overhead_update that failed half way leaves them (GF_ERR_STATE from the calls that
+ *                            read them until gf_usage_reset / gf_cluster_set); nothing on the device changes
  *   "rccl_selftest"          n: binds librccl at run time and checks a one-rank all-gather + reduce of n words on this device
  * GF_ERR_INVALID for an unknown key or a value out of range.  The only environment variables the library reads are
  * GANGFIT_WAIT=block (completion waits park the thread instead of polling) and GANGFIT_CHAIN_CACHE=0.  It never changes
@@ -249,6 +252,39 @@ int gf_snapshot_build_resident(gf_ctx *ctx, uint32_t n_res, const uint32_t *res_
  *   out[3]  bytes the build copied device -> host, not counting driver_order_out / exec_order_out (saturates at UINT32_MAX)
  * GF_ERR_INVALID for NULL arguments.  A view reports its parent's build, a multi-device context its first device's. */
 int gf_snapshot_build_info(gf_ctx *ctx, uint32_t out[4]);
+/* gf_snapshot_build_resident over a node set of the resident cluster: one resident cluster, one usage stream and one overhead
+ * stream serve the driver Filters of every instance group (the reference builds the Filter's snapshot from availableNodes, the
+ * nodes the driver's required affinity matches: internal/extender/resource.go:292-304).  member_words is a row as in
+ * gf_cluster_fit_feasible_sets: W = ceil(n_nodes / 64) words, bit (n & 63) of word n >> 6 = node n; m = its popcount.
+ * With M = the members in ascending cluster index, the installed snapshot, the two orders and every later decision on them equal
+ * what gf_cluster_set + gf_snapshot_build_resident install on a context that was given only the rows of M (the same zone ids and
+ * n_zones, name ranks = the rank among members of the cluster's name_rank, only the reservation entries that name a member, the
+ * members' flag and label-rank rows), every node index mapped back to the cluster's.  Zone sums, zone ranks, the schedulable
+ * check and the scaled units come from the members only.  A non-member is never a candidate whatever its flags, owns no slot
+ * (GF_NO_NODE, as nodes outside both orders of a host-built layout), its reservation entries and resident usage are not read, and
+ * an overhead above its allocatable does not disable the efficiencies.  Arrays indexed by node (node_flags, the label ranks,
+ * gf_snapshot_get, gf_residual_get, reserved / hosts_app) keep the cluster's n_nodes; gf_snapshot_get / gf_residual_get return 0
+ * in the rows of non-members; the efficiency rows of non-members are unspecified.  The layout is compact: m + 1 slots.
+ *   - member_words == NULL is gf_snapshot_build_resident: the same code path and launches.
+ *   - m == 0 is GF_OK: both orders empty, every decision answers has_capacity 0.
+ *   - refuses what gf_snapshot_build_resident refuses, with the same codes; a bit at or beyond n_nodes is GF_ERR_INVALID.  On a
+ *     refusal nothing is installed.  The entries that travel are range-checked as the parent call checks them, over every node
+ *     of the cluster: entries that could sum past 2^62 on a NON-member are refused too (GF_ERR_INVALID), although a cluster of
+ *     the members alone would never have read them.
+ * Generations, the behaviour on a view and on a multi-device context are those of gf_snapshot_build_resident. */
+int gf_snapshot_build_resident_set(gf_ctx *ctx, const uint64_t *member_words /* W = ceil(n_nodes/64), nullable */,
+                                   uint32_t n_res, const uint32_t *res_node, const int64_t *res_cpu_milli,
+                                   const int64_t *res_mem_bytes, const int64_t *res_gpu, const uint32_t *node_flags,
+                                   const uint32_t *driver_label_rank, const uint32_t *exec_label_rank,
+                                   uint32_t *driver_order_out, uint32_t *n_d_out, uint32_t *exec_order_out, uint32_t *n_x_out);
+/* The installed layout:
+ *   out[0]  1 = the installed snapshot was built from a node set (gf_snapshot_build_resident_set with a row), else 0
+ *   out[1]  members of that set (n_nodes when out[0] is 0)
+ *   out[2]  slots of the installed layout (a set built on the device: exactly members + 1; on the host: at most that)
+ *   out[3]  its 64-slot chunks
+ * GF_ERR_STATE without orders, GF_ERR_INVALID for NULL arguments.  A view reports its parent's layout, a multi-device context
+ * its first device's. */
+int gf_snapshot_set_info(gf_ctx *ctx, uint32_t out[4]);
 /* The third step of keeping the snapshot resident ("keep snapshot resident on device across requests and
  * apply deltas"): the per-node usage sums of UsageForNodes (LIB/resources/resources.go:31-43) stay on the device next to the
  * cluster columns.  gf_cluster_set zeroes them (a new node set starts from nothing); gf_usage_apply adds (sign = +1: a

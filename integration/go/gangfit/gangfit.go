@@ -73,6 +73,7 @@ type Context struct {
 	// the snapshot the last FilterResident installed (gf_generation right after it) and the flags it was built with
 	builtEpoch, builtCluster, builtUsage uint64
 	builtFlags                          []uint32
+	builtMembers                        []uint64 // the member row of that snapshot (FilterResidentGroup); nil = every node
 }
 
 func New(devices ...int) (*Context, error) {
@@ -526,11 +527,45 @@ func (c *Context) SnapshotBuildResident(requestFlags []uint32) error {
 }
 
 func (c *Context) buildResidentLocked(requestFlags []uint32) error {
-	if rc := C.gf_snapshot_build_resident(c.ctx, C.uint32_t(ResidentUsage), nil, nil, nil, nil, p32(requestFlags), nil, nil,
+	return c.buildResidentSetLocked(nil, requestFlags)
+}
+
+// SnapshotBuildResidentSet is SnapshotBuildResident over the nodes of one instance group (gf_snapshot_build_resident_set):
+// members holds ceil(nNodes / 64) words, bit (n & 63) of word n >> 6 = node n of the resident cluster is one of availableNodes
+// (the nodes the driver's required affinity matches, internal/extender/resource.go:292-304); nil = every node.  One resident
+// cluster, one usage stream and one overhead stream then serve the Filters of every group.  NOT atomic with a following fit:
+// a Filter must use FilterResidentGroup.  Unverified here (no Go toolchain).
+func (c *Context) SnapshotBuildResidentSet(members []uint64, requestFlags []uint32) error {
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	return c.buildResidentSetLocked(members, requestFlags)
+}
+
+func (c *Context) buildResidentSetLocked(members []uint64, requestFlags []uint32) error {
+	var words *C.uint64_t
+	if len(members) > 0 {
+		if len(members) != (len(c.names)+63)/64 {
+			return fmt.Errorf("gangfit: the member row has %d words, the resident cluster needs %d", len(members), (len(c.names)+63)/64)
+		}
+		words = (*C.uint64_t)(unsafe.Pointer(&members[0]))
+	}
+	if rc := C.gf_snapshot_build_resident_set(c.ctx, words, C.uint32_t(ResidentUsage), nil, nil, nil, nil, p32(requestFlags), nil, nil,
 		nil, nil, nil, nil); rc != C.GF_OK {
 		return c.err(rc)
 	}
 	return nil
+}
+
+// SetInfo describes the installed layout (gf_snapshot_set_info): whether it was built from a node set, its members (every node
+// otherwise), its slots and its 64-slot chunks.  A group's layout has members + 1 slots: non-members cost none.
+func (c *Context) SetInfo() (fromSet bool, members, slots, chunks uint32, err error) {
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	var out [4]C.uint32_t
+	if rc := C.gf_snapshot_set_info(c.ctx, &out[0]); rc != C.GF_OK {
+		return false, 0, 0, 0, c.err(rc)
+	}
+	return out[0] != 0, uint32(out[1]), uint32(out[2]), uint32(out[3]), nil
 }
 
 // BuildInfo reports the route of the last snapshot build of this context (gf_snapshot_build_info): route 0 = none yet,
@@ -556,6 +591,13 @@ func (c *Context) BuildInfo() (route int, labelGroup, mergeFailed bool, d2hBytes
 // gf_fit_batch(GF_MODE_FIFO_CHAIN) resumes from the previous chain's checkpoints (include/gangfit.h, "Incremental FIFO
 // chains"): the Filter of driver j + 1 after the Filter of driver j costs a few dozen applications instead of all of them.
 func (c *Context) FilterResident(requestFlags []uint32, fifo bool, algo int, apps []App) (results []Result, failedAt int, err error) {
+	return c.FilterResidentGroup(nil, requestFlags, fifo, algo, apps)
+}
+
+// FilterResidentGroup is FilterResident when the resident cluster holds every instance group: the snapshot is built over the
+// members of the row only (SnapshotBuildResidentSet; nil = every node).  "Nothing changed" additionally compares the row, so a
+// Filter for another group rebuilds — from the same resident columns and usage sums: no ClusterSet, no usage replay.
+func (c *Context) FilterResidentGroup(members []uint64, requestFlags []uint32, fifo bool, algo int, apps []App) (results []Result, failedAt int, err error) {
 	capps, total, err := flattenApps(apps)
 	if err != nil {
 		return nil, -1, err
@@ -565,20 +607,33 @@ func (c *Context) FilterResident(requestFlags []uint32, fifo bool, algo int, app
 	var gen [3]C.uint64_t
 	C.gf_generation(c.ctx, &gen[0])
 	same := c.builtEpoch != 0 && uint64(gen[0]) == c.builtEpoch && uint64(gen[1]) == c.builtCluster &&
-		uint64(gen[2]) == c.builtUsage && equalFlags(c.builtFlags, requestFlags)
+		uint64(gen[2]) == c.builtUsage && equalFlags(c.builtFlags, requestFlags) && equalWords(c.builtMembers, members)
 	if !same {
 		c.builtEpoch = 0
-		if err := c.buildResidentLocked(requestFlags); err != nil {
+		if err := c.buildResidentSetLocked(members, requestFlags); err != nil {
 			return nil, -1, err
 		}
 		C.gf_generation(c.ctx, &gen[0])
 		c.builtEpoch, c.builtCluster, c.builtUsage = uint64(gen[0]), uint64(gen[1]), uint64(gen[2])
 		c.builtFlags = append(c.builtFlags[:0], requestFlags...)
+		c.builtMembers = append(c.builtMembers[:0], members...)
 	}
 	return c.fitLocked(fifo, algo, apps, capps, total, c.names)
 }
 
 func equalFlags(a, b []uint32) bool {
+	if len(a) != len(b) {
+		return false
+	}
+	for i := range a {
+		if a[i] != b[i] {
+			return false
+		}
+	}
+	return true
+}
+
+func equalWords(a, b []uint64) bool {
 	if len(a) != len(b) {
 		return false
 	}

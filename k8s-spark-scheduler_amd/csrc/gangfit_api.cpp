@@ -327,6 +327,9 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->d_delta_u32.release();
     ctx->d_bi64.release();
     ctx->d_bu32.release();
+    ctx->d_set64.release();
+    ctx->d_set32.release();
+    ctx->h_set_labels.release();
     ctx->h_bcols.release();
     ctx->h_border.release();
     ctx->d_xexe.release();
@@ -465,6 +468,13 @@ int gf_set_option(gf_ctx* ctx, const char* key, int64_t value) {
         ctx->snapshot_finalize_on_device = value == 0;
     } else if (k == "sort_fault") {
         ctx->sort_fault = value != 0 ? 1 : 0;
+    } else if (k == "update_fault") {
+        // (tests) the state a gf_usage_apply / gf_overhead_update that failed half way leaves behind; host flags only
+        if (value < 1 || value > 3) return fail(ctx, GF_ERR_INVALID, "update_fault wants 1 (usage), 2 (overhead) or 3 (both)");
+        if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede update_fault");
+        if (value & 1) ctx->usage_ok = false;
+        if (value & 2) ctx->cl_over_ok = false;
+        return GF_OK;
     } else if (k == "force_general_layout") {
         ctx->force_general_layout = value != 0;
     } else if (k == "chain_cache") {

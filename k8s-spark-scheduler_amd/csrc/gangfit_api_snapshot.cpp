@@ -565,19 +565,28 @@ struct BuildScratch {
     uint32_t *perm_a, *perm_b, *perm_c, *res_node, *zone_order, *zone_rank, *zfirst, *zhasx, *zeval, *scalars;  // d_bu32
     uint32_t *label_d, *label_x, *perm_p, *ppos;  // the request's label ranks | the priority order and its inverse (label group)
     unsigned long long* merge_summary;            // LabelMerge::d_summary
+    uint32_t n;                                   // nodes the build runs over: the cluster's, or the members of a node set
+    // a node-set build (gf_snapshot_build_resident_set; members == nullptr otherwise): alloc .. flags above are then the members'
+    // compact columns, and what the finalize indexes by node is the members' until launch_snapshot_set_scatter has run
+    const std::vector<uint32_t>* members;  // member -> cluster index, ascending
+    uint64_t *set_words, *set_nbits;       // d_set64 ...
+    int64_t *set_usage, *set_node_tab;
+    uint32_t *set_prefix, *set_node, *set_node_slot;  // d_set32 ...
 };
 
-int carve_build_scratch(gf_ctx* ctx, size_t R, BuildScratch* out) {
-    const size_t N = ctx->cl_n, Z = ctx->cl_zones;
+int carve_build_scratch(gf_ctx* ctx, uint32_t n, size_t R, BuildScratch* out) {
+    const size_t N = n, Z = ctx->cl_zones;
     const size_t NCH = (N + 1 + 63) / 64;  // chunks of the slot space (nodes + sentinel)
     GF_HIP(ctx, ctx->d_bi64.reserve(9 * N + 3 * N + 3 * R + 3 * Z + 6 * NCH + 16 + 4 * (size_t)gangfit::kLabelMergeUnits));
     GF_HIP(ctx, ctx->d_bu32.reserve(3 * N + R + 5 * Z + 16 + 4 * N));
     BuildScratch& s = *out;
+    s.n = n;
+    s.members = nullptr;
     s.alloc = ctx->d_cl_i64.ptr;
-    s.over = s.alloc + 3 * N;
+    s.over = s.alloc + 3 * (size_t)ctx->cl_n;
     s.zone = ctx->d_cl_u32.ptr;
-    s.name_rank = s.zone + N;
-    s.flags = s.name_rank + N;
+    s.name_rank = s.zone + ctx->cl_n;
+    s.flags = s.name_rank + ctx->cl_n;
     s.usage = ctx->d_bi64.ptr;
     s.avail = s.usage + 3 * N;
     s.sched = s.avail + 3 * N;
@@ -606,9 +615,33 @@ int carve_build_scratch(gf_ctx* ctx, size_t R, BuildScratch* out) {
     return GF_OK;
 }
 
+// The scratch of a node-set build behind carve_build_scratch(m): the row, its name-order twin, the prefix counts, the usage sums of
+// entries that travel (by cluster index) and the members' compact columns, which replace the resident ones in *out.
+int carve_set_scratch(gf_ctx* ctx, const std::vector<uint32_t>& members, BuildScratch* out) {
+    const size_t N = ctx->cl_n, W = (N + 63) / 64, M = members.size();
+    GF_HIP(ctx, ctx->d_set64.reserve(2 * W + 3 * N + 9 * M + 6 * M + 1));
+    GF_HIP(ctx, ctx->d_set32.reserve(2 * W + 5 * M + 2));
+    BuildScratch& s = *out;
+    s.members = &members;
+    s.set_words = reinterpret_cast<uint64_t*>(ctx->d_set64.ptr);
+    s.set_nbits = s.set_words + W;
+    s.set_usage = ctx->d_set64.ptr + 2 * W;
+    s.alloc = s.set_usage + 3 * N;
+    s.over = s.alloc + 3 * M;
+    s.usage = s.over + 3 * M;  // (the compact sums: the build reads them as resident ones)
+    s.set_node_tab = s.usage + 3 * M;
+    s.set_prefix = ctx->d_set32.ptr;
+    s.zone = s.set_prefix + 2 * W;
+    s.name_rank = s.zone + M;
+    s.flags = s.name_rank + M;
+    s.set_node = s.flags + M;
+    s.set_node_slot = s.set_node + M;
+    return GF_OK;
+}
+
 gangfit::SnapshotBuild build_args(gf_ctx* ctx, const BuildScratch& s, uint32_t n_res, bool usage_resident, const LabelPlan& lp) {
     gangfit::SnapshotBuild b{};
-    b.n_nodes = ctx->cl_n;
+    b.n_nodes = s.n;
     b.n_res = n_res;
     b.n_zones = ctx->cl_zones;
     b.d_alloc = s.alloc;
@@ -617,7 +650,8 @@ gangfit::SnapshotBuild build_args(gf_ctx* ctx, const BuildScratch& s, uint32_t n
     b.d_res_req = s.res_req;
     b.d_zone = s.zone;
     b.d_name_rank = s.name_rank;
-    b.d_usage = usage_resident ? ctx->d_cl_usage.ptr : s.usage;
+    if (s.members != nullptr) usage_resident = true;  // the members' sums were gathered: neither zeroed nor scattered into
+    b.d_usage = (usage_resident && s.members == nullptr) ? ctx->d_cl_usage.ptr : s.usage;
     b.usage_resident = usage_resident;
     b.d_avail = s.avail;
     b.d_sched = s.sched;
@@ -656,8 +690,9 @@ struct BuildInfo {
 // both subsequences of C) nothing is installed, info->merge_failed is set and the caller takes the host route.
 int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out, BuildInfo* info) {
     hipStream_t st = ctx->stream;
-    const uint32_t n = ctx->cl_n, n_slots = n + 1, n_chunks = (n_slots + 63) / 64;
-    const size_t N = n, S = n_slots, C = n_chunks, Z = ctx->cl_zones;
+    const uint32_t n = s.n, n_slots = n + 1, n_chunks = (n_slots + 63) / 64;
+    const bool set = s.members != nullptr;  // n members: their slots and the sentinel, node-indexed tables at the cluster's size
+    const size_t N = ctx->cl_n, S = n_slots, C = n_chunks, Z = ctx->cl_zones;
     GF_HIP(ctx, ctx->d_snap.reserve(3 * S));
     GF_HIP(ctx, ctx->d_work.reserve(3 * S));
     GF_HIP(ctx, ctx->d_sched.reserve(3 * S));
@@ -685,11 +720,11 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out,
     f.d_snap = ctx->d_snap.ptr;
     f.d_sched_slot = ctx->d_sched.ptr;
     f.d_slot_node = ctx->d_slot_node.ptr;
-    f.d_node_slot = ctx->d_node_slot.ptr;
+    f.d_node_slot = set ? s.set_node_slot : ctx->d_node_slot.ptr;
     f.d_dslot = ctx->d_dslot.ptr;
     f.d_masks = ctx->d_masks.ptr;
     f.d_cmax = ctx->d_cmax.ptr;
-    f.d_node_tab = ctx->d_node_tab.ptr;
+    f.d_node_tab = set ? s.set_node_tab : ctx->d_node_tab.ptr;
     f.d_gcd_part = s.gcd_part;
     f.d_units = s.units;
     f.d_zfirst = s.zfirst;
@@ -710,6 +745,22 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out,
         f.h_out = ctx->h_border.dev;
     }
     GF_HIP(ctx, gangfit::launch_snapshot_finalize(f, ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word(), st));
+    if (set) {
+        gangfit::SnapshotSetScatter sc{};
+        sc.n_nodes = ctx->cl_n;
+        sc.n_members = n;
+        sc.d_words = s.set_words;
+        sc.d_prefix = s.set_prefix;
+        sc.c_node = s.set_node;
+        sc.c_node_slot = s.set_node_slot;
+        sc.c_node_tab = s.set_node_tab;
+        sc.d_node_slot = ctx->d_node_slot.ptr;
+        sc.d_node_tab = ctx->d_node_tab.ptr;
+        sc.d_status = s.scalars + 3;  // (finalize_reduce_kernel has written it)
+        sc.d_slot_node = ctx->d_slot_node.ptr;
+        sc.d_nquad = reinterpret_cast<int4*>(ctx->d_nquad.ptr);
+        GF_HIP(ctx, gangfit::launch_snapshot_set_scatter(sc, st));
+    }
     if (f.h_out == nullptr) GF_HIP(ctx, hipMemcpyAsync(h_scalars, s.scalars, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     GF_HIP(ctx, gf_wait_stream(st));
     info->d2h_bytes += 16 * sizeof(uint32_t);
@@ -720,7 +771,7 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out,
     }
     // ---- the snapshot itself (what gf_snapshot_set + gf_zones_set record on the host path) ...
     ctx->have_sched = h_scalars[2] == 0;  // a negative schedulable value (overhead above allocatable) disables the efficiencies
-    ctx->n_nodes = n;
+    ctx->n_nodes = ctx->cl_n;
     ctx->have_snapshot = true;
     ctx->zone = ctx->cl_zone;
     ctx->eff_nonneg = false;  // nothing compared available with schedulable
@@ -742,11 +793,12 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out,
     lf.zspan_ok = false;         // the zone masks were built on the device: the shards scan every zone over their whole range
     lf.host_stale = true;
     install_layout(ctx, std::move(lf));
-    if (out.any()) {  // the two lists, for callers that want them
-        GF_HIP(ctx, hipMemcpyAsync(ctx->h_border.ptr, s.perm_b, N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (out.any()) {  // the two lists, for callers that want them (a set's order in cluster indices: its slots' nodes)
+        GF_HIP(ctx, hipMemcpyAsync(ctx->h_border.ptr, set ? ctx->d_slot_node.ptr : s.perm_b, (size_t)n * sizeof(uint32_t),
+                                   hipMemcpyDeviceToHost, st));
         GF_HIP(ctx, gf_wait_stream(st));
         uint32_t nd, nx;
-        candidate_lists(ctx->h_border.ptr, N, ctx->cl_flags.data(), out.driver_order, out.exec_order, &nd, &nx);
+        candidate_lists(ctx->h_border.ptr, n, ctx->cl_flags.data(), out.driver_order, out.exec_order, &nd, &nx);
         out.counts(nd, nx);
     }
     return GF_OK;
@@ -760,7 +812,7 @@ int finalize_on_device(gf_ctx* ctx, const BuildScratch& s, const OrderOuts& out,
 int finalize_on_host(gf_ctx* ctx, const BuildScratch& s, const uint32_t* d_order, const uint32_t* driver_label_rank,
                      const uint32_t* exec_label_rank, const OrderOuts& out, BuildInfo* info) {
     hipStream_t st = ctx->stream;
-    const uint32_t n = ctx->cl_n;
+    const uint32_t n = s.n;
     const size_t N = n;
     GF_HIP(ctx, ctx->h_bcols.reserve(6 * N));
     GF_HIP(ctx, ctx->h_border.reserve(N + 8));
@@ -774,7 +826,22 @@ int finalize_on_host(gf_ctx* ctx, const BuildScratch& s, const uint32_t* d_order
     const int64_t* h_avail = ctx->h_bcols.ptr;
     const int64_t* h_sched = ctx->h_bcols.ptr + 3 * N;
     bool sched_ok = true;
-    for (size_t i = 0; i < 3 * N && sched_ok; ++i) sched_ok = h_sched[i] >= 0;
+    for (size_t i = 0; i < 3 * N && sched_ok; ++i) sched_ok = h_sched[i] >= 0;  // (a node set: over its members only)
+    // a node set: rows and order in cluster indices — the members' rows, zeros for every other node
+    const uint32_t n_inst = ctx->cl_n;
+    std::vector<int64_t> wide;
+    if (s.members != nullptr) {
+        const std::vector<uint32_t>& mem = *s.members;
+        const size_t CN = n_inst;
+        wide.assign(6 * CN, 0);
+        for (size_t c = 0; c < N; ++c) {
+            for (int j = 0; j < 6; ++j) wide[(size_t)j * CN + mem[c]] = ctx->h_bcols.ptr[(size_t)j * N + c];
+            ctx->h_border.ptr[c] = mem[ctx->h_border.ptr[c]];
+        }
+        h_avail = wide.data();
+        h_sched = wide.data() + 3 * CN;
+    }
+    const size_t NI = n_inst;
     std::vector<uint32_t> D(N), X(N);
     uint32_t nd, nx;
     candidate_lists(ctx->h_border.ptr, N, ctx->cl_flags.data(), D.data(), X.data(), &nd, &nx);
@@ -785,8 +852,8 @@ int finalize_on_host(gf_ctx* ctx, const BuildScratch& s, const uint32_t* d_order
     };
     if (driver_label_rank) by_rank(D, driver_label_rank);
     if (exec_label_rank) by_rank(X, exec_label_rank);
-    int rc = gf_snapshot_set(ctx, n, h_avail, h_avail + N, h_avail + 2 * N, sched_ok ? h_sched : nullptr,
-                             sched_ok ? h_sched + N : nullptr, sched_ok ? h_sched + 2 * N : nullptr);
+    int rc = gf_snapshot_set(ctx, n_inst, h_avail, h_avail + NI, h_avail + 2 * NI, sched_ok ? h_sched : nullptr,
+                             sched_ok ? h_sched + NI : nullptr, sched_ok ? h_sched + 2 * NI : nullptr);
     if (rc != GF_OK) return rc;
     if (!ctx->cl_zone.empty() && (rc = gf_zones_set(ctx, ctx->cl_zone.data())) != GF_OK) return rc;
     if ((rc = gf_orders_set(ctx, D.data(), nd, X.data(), nx)) != GF_OK) return rc;
@@ -798,23 +865,29 @@ int finalize_on_host(gf_ctx* ctx, const BuildScratch& s, const uint32_t* d_order
 
 }  // namespace
 
-extern "C" int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_node, const int64_t* res_cpu_milli,
-                                          const int64_t* res_mem_bytes, const int64_t* res_gpu, const uint32_t* node_flags,
-                                          const uint32_t* driver_label_rank, const uint32_t* exec_label_rank,
-                                          uint32_t* driver_order_out, uint32_t* n_d_out, uint32_t* exec_order_out, uint32_t* n_x_out) {
-    if (ctx != nullptr && !ctx->group.empty())  // the caller's order lists come from the first device only
-        return each_device(ctx, nullptr, [&](gf_ctx* sub, bool first) {
-            return gf_snapshot_build_resident(sub, n_res, res_node, res_cpu_milli, res_mem_bytes, res_gpu, node_flags, driver_label_rank,
-                                              exec_label_rank, first ? driver_order_out : nullptr, first ? n_d_out : nullptr,
-                                              first ? exec_order_out : nullptr, first ? n_x_out : nullptr);
-        });
-    if (!ctx) return GF_ERR_INVALID;
+namespace {
+
+// gf_snapshot_build_resident (member_words == nullptr: every node of the resident cluster) and gf_snapshot_build_resident_set (the
+// members of the row) on one device.
+int build_resident(gf_ctx* ctx, const uint64_t* member_words, uint32_t n_res, const uint32_t* res_node, const int64_t* res_cpu_milli,
+                   const int64_t* res_mem_bytes, const int64_t* res_gpu, const uint32_t* node_flags, const uint32_t* driver_label_rank,
+                   const uint32_t* exec_label_rank, const OrderOuts& out) {
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);
     GF_NOT_ON_A_VIEW(ctx);
     InstallGuard install_guard(ctx);
-    if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede gf_snapshot_build_resident");
-    const OrderOuts out{driver_order_out, n_d_out, exec_order_out, n_x_out};
+    if (!ctx->have_cluster)
+        return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede gf_snapshot_build_resident%s", member_words ? "_set" : "");
     const uint32_t n = ctx->cl_n;
+    const bool set = member_words != nullptr;
+    std::vector<uint32_t> members;  // member -> cluster index, ascending
+    if (set) {
+        const uint32_t W = (n + 63u) / 64u;
+        if ((n & 63u) != 0 && (member_words[W - 1] >> (n & 63u)) != 0)
+            return fail(ctx, GF_ERR_INVALID, "the member row has a bit at or beyond n_nodes = %u", n);
+        for (uint32_t w = 0; w < W; ++w)
+            for (uint64_t bits = member_words[w]; bits != 0; bits &= bits - 1) members.push_back(w * 64u + (uint32_t)__builtin_ctzll(bits));
+    }
+    const uint32_t m = set ? (uint32_t)members.size() : n;  // nodes the build runs over
     const bool usage_resident = n_res == GF_RESIDENT_USAGE;  // the sums gf_usage_apply maintains: no entry travels
     if (usage_resident) n_res = 0;
     if (n_res > 0 && (!res_node || !res_cpu_milli || !res_mem_bytes || !res_gpu))
@@ -838,55 +911,137 @@ extern "C" int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uin
         ctx->build_info[1] = info.label_group;
         ctx->build_info[2] = info.merge_failed;
         ctx->build_info[3] = info.d2h_bytes > UINT32_MAX ? UINT32_MAX : (uint32_t)info.d2h_bytes;
+        if (set) {  // (every install behind this point moves snap_epoch on: the layout is a set's while the two are equal)
+            ctx->set_epoch = ctx->snap_epoch;
+            ctx->set_members = m;
+        }
         return rc;
     };
-    if (n == 0) {
-        int rc = gf_snapshot_set(ctx, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (m == 0) {  // no node (or no member): an empty layout; a set keeps the node-indexed rows of the cluster, all zero
+        const std::vector<int64_t> zeros(n, 0);
+        const int64_t* const z = zeros.data();
+        int rc = n == 0 ? gf_snapshot_set(ctx, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) : gf_snapshot_set(ctx, n, z, z, z, z, z, z);
         if (rc != GF_OK) return rc;
+        if (n != 0 && !ctx->cl_zone.empty() && (rc = gf_zones_set(ctx, ctx->cl_zone.data())) != GF_OK) return rc;
         out.counts(0, 0);
         return done(gf_orders_set(ctx, nullptr, 0, nullptr, 0), 2);
     }
-    const LabelPlan lp = plan_labels(n, driver_label_rank, exec_label_rank, ctx->snapshot_finalize_on_device);
-    const bool label_group = lp.device_route && lp.which != 0;
     GF_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const size_t N = n, R = n_res;
+    const size_t N = n, M = m, R = n_res;
     GF_HIP(ctx, gf_wait_stream(st));  // nothing in flight may still read buffers that are about to grow
+    // a set's label ranks travel as its members' rows: the plan, the key width and the route are those of the members alone.
+    // (Staged in the context's pinned memory, which outlives an early return with the copy still on the stream.)
+    const uint32_t* label_in[2] = {driver_label_rank, exec_label_rank};
+    if (set && (label_in[0] != nullptr || label_in[1] != nullptr)) {
+        GF_HIP(ctx, ctx->h_set_labels.reserve(2 * M));
+        for (int r = 0; r < 2; ++r)
+            if (label_in[r] != nullptr) {
+                uint32_t* const row = ctx->h_set_labels.ptr + (size_t)r * M;
+                for (uint32_t c = 0; c < m; ++c) row[c] = label_in[r][members[c]];
+                label_in[r] = row;
+            }
+    }
+    const LabelPlan lp = plan_labels(m, label_in[0], label_in[1], ctx->snapshot_finalize_on_device);
+    const bool label_group = lp.device_route && lp.which != 0;
     BuildScratch s;
-    if (int rc = carve_build_scratch(ctx, R, &s); rc != GF_OK) return rc;
+    if (int rc = carve_build_scratch(ctx, m, R, &s); rc != GF_OK) return rc;
+    const uint32_t* const d_cl_flags = s.flags;
+    if (set)
+        if (int rc = carve_set_scratch(ctx, members, &s); rc != GF_OK) return rc;
     for (int j = 0; j < 3 && R; ++j)
         GF_HIP(ctx, hipMemcpyAsync(s.res_req + j * R, rcols[j], R * sizeof(int64_t), hipMemcpyHostToDevice, st));
     if (R) GF_HIP(ctx, hipMemcpyAsync(s.res_node, res_node, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (flags_upload) {
-        GF_HIP(ctx, hipMemcpyAsync(s.flags, flags_upload, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        GF_HIP(ctx, hipMemcpyAsync(const_cast<uint32_t*>(d_cl_flags), flags_upload, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         ctx->d_flags_default = node_flags == nullptr;
     }
     if (label_group) {  // the rank arrays that re-sort something: 4 bytes per node each, like the flags
-        if (lp.driver_active)
-            GF_HIP(ctx, hipMemcpyAsync(s.label_d, driver_label_rank, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-        if (lp.exec_active) GF_HIP(ctx, hipMemcpyAsync(s.label_x, exec_label_rank, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (lp.driver_active) GF_HIP(ctx, hipMemcpyAsync(s.label_d, label_in[0], M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (lp.exec_active) GF_HIP(ctx, hipMemcpyAsync(s.label_x, label_in[1], M * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    }
+    if (set) {  // the row (8 bytes per 64 nodes), then the members' columns gathered on the device
+        const size_t W = (N + 63) / 64;
+        GF_HIP(ctx, hipMemcpyAsync(s.set_words, member_words, W * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        // nbits, and behind it the sums of entries that travel: by cluster index, so that an entry on a non-member is never read
+        GF_HIP(ctx, hipMemsetAsync(s.set_nbits, 0, (W + (usage_resident ? 0 : 3 * N)) * sizeof(uint64_t), st));
+        if (R)
+            GF_HIP(ctx, gangfit::launch_usage_apply(n_res, n, s.res_node, s.res_req, +1, s.set_usage, nullptr, nullptr, st));
+        gangfit::SnapshotSetGather g{};
+        g.n_nodes = n;
+        g.n_members = m;
+        g.d_words = s.set_words;
+        g.d_nbits = s.set_nbits;
+        g.d_prefix = s.set_prefix;
+        g.d_alloc = ctx->d_cl_i64.ptr;
+        g.d_overhead = ctx->cl_over ? ctx->d_cl_i64.ptr + 3 * N : nullptr;
+        g.d_usage = usage_resident ? ctx->d_cl_usage.ptr : s.set_usage;
+        g.d_zone = ctx->d_cl_u32.ptr;
+        g.d_name_rank = ctx->d_cl_u32.ptr + N;
+        g.d_flags = d_cl_flags;
+        g.c_alloc = s.alloc;
+        g.c_overhead = s.over;
+        g.c_usage = s.usage;
+        g.c_zone = s.zone;
+        g.c_flags = s.flags;
+        g.c_name_rank = s.name_rank;
+        g.c_node = s.set_node;
+        GF_HIP(ctx, gangfit::launch_snapshot_set_gather(g, st));
     }
     GF_HIP(ctx, ctx->d_sortwork.reserve(gangfit::snapshot_sort_work_words()));
-    GF_HIP(ctx, gangfit::launch_snapshot_build(build_args(ctx, s, n_res, usage_resident, lp), st));
+    GF_HIP(ctx, gangfit::launch_snapshot_build(build_args(ctx, s, set ? 0 : n_res, usage_resident, lp), st));
     if (lp.device_route) {
         if (label_group) {
             info.label_group = 1;
-            gangfit::LabelMerge m{};
-            m.n_nodes = n;
-            m.d_order = s.perm_b;
-            m.d_flags = s.flags;
-            m.d_ppos = s.ppos;
-            m.d_rank[0] = lp.driver_active ? s.label_d : nullptr;
-            m.d_rank[1] = lp.exec_active ? s.label_x : nullptr;
-            m.d_summary = s.merge_summary;
-            m.d_fail = ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word() + 1;
-            GF_HIP(ctx, gangfit::launch_label_merge_check(m, st));
+            gangfit::LabelMerge mc{};
+            mc.n_nodes = m;
+            mc.d_order = s.perm_b;
+            mc.d_flags = s.flags;
+            mc.d_ppos = s.ppos;
+            mc.d_rank[0] = lp.driver_active ? s.label_d : nullptr;
+            mc.d_rank[1] = lp.exec_active ? s.label_x : nullptr;
+            mc.d_summary = s.merge_summary;
+            mc.d_fail = ctx->d_sortwork.ptr + gangfit::snapshot_sort_error_word() + 1;
+            GF_HIP(ctx, gangfit::launch_label_merge_check(mc, st));
         }
         const int rc = finalize_on_device(ctx, s, out, &info);
         if (rc != GF_OK || !info.merge_failed) return done(rc, 1);
     }
     // (behind a label key group the sort left the priority order itself in perm_p)
     return done(finalize_on_host(ctx, s, label_group ? s.perm_p : s.perm_b, driver_label_rank, exec_label_rank, out, &info), 2);
+}
+
+// ... on every device of a multi-device context (the caller's order lists come from the first device only)
+int build_resident_each(gf_ctx* ctx, const uint64_t* member_words, uint32_t n_res, const uint32_t* res_node, const int64_t* res_cpu_milli,
+                        const int64_t* res_mem_bytes, const int64_t* res_gpu, const uint32_t* node_flags, const uint32_t* driver_label_rank,
+                        const uint32_t* exec_label_rank, const OrderOuts& out) {
+    if (!ctx) return GF_ERR_INVALID;
+    if (ctx->group.empty())
+        return build_resident(ctx, member_words, n_res, res_node, res_cpu_milli, res_mem_bytes, res_gpu, node_flags, driver_label_rank,
+                              exec_label_rank, out);
+    return each_device(ctx, nullptr, [&](gf_ctx* sub, bool first) {
+        return build_resident(sub, member_words, n_res, res_node, res_cpu_milli, res_mem_bytes, res_gpu, node_flags, driver_label_rank,
+                              exec_label_rank, first ? out : OrderOuts{nullptr, nullptr, nullptr, nullptr});
+    });
+}
+
+}  // namespace
+
+extern "C" int gf_snapshot_build_resident(gf_ctx* ctx, uint32_t n_res, const uint32_t* res_node, const int64_t* res_cpu_milli,
+                                          const int64_t* res_mem_bytes, const int64_t* res_gpu, const uint32_t* node_flags,
+                                          const uint32_t* driver_label_rank, const uint32_t* exec_label_rank,
+                                          uint32_t* driver_order_out, uint32_t* n_d_out, uint32_t* exec_order_out, uint32_t* n_x_out) {
+    return build_resident_each(ctx, nullptr, n_res, res_node, res_cpu_milli, res_mem_bytes, res_gpu, node_flags, driver_label_rank,
+                               exec_label_rank, OrderOuts{driver_order_out, n_d_out, exec_order_out, n_x_out});
+}
+
+extern "C" int gf_snapshot_build_resident_set(gf_ctx* ctx, const uint64_t* member_words, uint32_t n_res, const uint32_t* res_node,
+                                              const int64_t* res_cpu_milli, const int64_t* res_mem_bytes, const int64_t* res_gpu,
+                                              const uint32_t* node_flags, const uint32_t* driver_label_rank,
+                                              const uint32_t* exec_label_rank, uint32_t* driver_order_out, uint32_t* n_d_out,
+                                              uint32_t* exec_order_out, uint32_t* n_x_out) {
+    return build_resident_each(ctx, member_words, n_res, res_node, res_cpu_milli, res_mem_bytes, res_gpu, node_flags, driver_label_rank,
+                               exec_label_rank, OrderOuts{driver_order_out, n_d_out, exec_order_out, n_x_out});
 }
 
 extern "C" {
@@ -933,6 +1088,20 @@ int gf_snapshot_build_info(gf_ctx* ctx, uint32_t out[4]) {
     gf_ctx* const src = ctx->view_of != nullptr ? ctx->view_of : ctx;  // a view fits on its parent's snapshot: its parent's build
     std::lock_guard<std::recursive_mutex> lock(src->mu);
     for (int i = 0; i < 4; ++i) out[i] = src->build_info[i];
+    return GF_OK;
+}
+
+int gf_snapshot_set_info(gf_ctx* ctx, uint32_t out[4]) {
+    GF_DELEGATE(ctx, gf_snapshot_set_info(ctx, out));
+    if (!ctx || !out) return GF_ERR_INVALID;
+    gf_ctx* const src = ctx->view_of != nullptr ? ctx->view_of : ctx;  // a view fits on its parent's layout
+    std::lock_guard<std::recursive_mutex> lock(src->mu);
+    if (!src->have_snapshot || !src->have_orders) return fail(ctx, GF_ERR_STATE, "no orders installed");
+    const bool set = src->set_epoch == src->snap_epoch;
+    out[0] = set ? 1u : 0u;
+    out[1] = set ? src->set_members : src->n_nodes;
+    out[2] = src->n_slots;
+    out[3] = src->n_chunks;
     return GF_OK;
 }
 

@@ -390,6 +390,12 @@ struct gf_ctx {
     PinnedBuf<int64_t> h_bcols;  // avail | sched (3n each)
     PinnedBuf<uint32_t> h_border;
     uint32_t build_info[4] = {0, 0, 0, 0};  // gf_snapshot_build_info: route | label group ran | merge check failed | bytes device -> host
+    // gf_snapshot_build_resident_set: the member words, their prefix counts and the members' compact columns (SetScratch)
+    DeviceBuf<int64_t> d_set64;
+    DeviceBuf<uint32_t> d_set32;
+    PinnedBuf<uint32_t> h_set_labels;  // the members' driver | executor label ranks on their way to the device
+    uint64_t set_epoch = 0;    // snap_epoch the last node-set build left behind: the installed snapshot is a set's while they are equal
+    uint32_t set_members = 0;  // ... and its member count (gf_snapshot_set_info)
 
     // single-executor requests (gf_executor_fit)
     DeviceBuf<int64_t> d_xexe, d_xreserved;

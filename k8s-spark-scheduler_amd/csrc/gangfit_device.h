@@ -688,6 +688,43 @@ size_t snapshot_sort_work_words();     // uint32 words of SnapshotBuild::d_sort_
 uint32_t snapshot_sort_error_word();   // index of the word that is non-zero when the sort's grid barrier gave up; the word behind
                                        // it is LabelMerge::d_fail of the same build (launch_snapshot_finalize reads both)
 hipError_t launch_snapshot_build(const SnapshotBuild& b, hipStream_t stream);
+// A snapshot over a node set of the resident cluster (gf_snapshot_build_resident_set).  Membership is a row of W = ceil(n_nodes / 64)
+// words as in ScanSetsArgs (no bit at or beyond n_nodes, n_members = its popcount, at least 1: the entry point checks).  The
+// members' columns are gathered into compact ones (member c = the c-th set bit), launch_snapshot_build / launch_snapshot_finalize
+// run on those at size n_members exactly as they run on a cluster of the members alone, and launch_snapshot_set_scatter maps what
+// the finalize left in member indices back to cluster indices.
+struct SnapshotSetGather {
+    uint32_t n_nodes, n_words, n_members;
+    const uint64_t* d_words;      // W
+    uint64_t* d_nbits;            // W, ZERO at launch: receives bit p = "the node of name rank p is a member"
+    uint32_t* d_prefix;           // 2 * W: set bits before word w of d_words | of d_nbits
+    const int64_t* d_alloc;       // 3 * n_nodes, by cluster index
+    const int64_t* d_overhead;    // 3 * n_nodes or nullptr (c_overhead is then not written)
+    const int64_t* d_usage;       // 3 * n_nodes
+    const uint32_t* d_zone;       // n_nodes
+    const uint32_t* d_name_rank;  // n_nodes, a permutation
+    const uint32_t* d_flags;      // n_nodes
+    int64_t *c_alloc, *c_overhead, *c_usage;  // 3 * n_members each, by member
+    uint32_t *c_zone, *c_flags;   // n_members
+    uint32_t* c_name_rank;        // n_members: the member's rank among the members' names (a permutation of 0 .. n_members - 1)
+    uint32_t* c_node;             // n_members: member -> cluster index
+};
+hipError_t launch_snapshot_set_gather(const SnapshotSetGather& g, hipStream_t stream);
+struct SnapshotSetScatter {
+    uint32_t n_nodes, n_members;
+    const uint64_t* d_words;      // W
+    const uint32_t* d_prefix;     // W: set bits before word w
+    const uint32_t* c_node;       // n_members
+    const uint32_t* c_node_slot;  // n_members: SnapshotFinalize::d_node_slot of the compact build
+    const int64_t* c_node_tab;    // 6 * n_members: its d_node_tab
+    uint32_t* d_node_slot;        // n_nodes: the members' slots, GF_NO_NODE for every other node
+    int64_t* d_node_tab;          // 6 * n_nodes: the members' rows, 0 for every other node
+    const uint32_t* d_status;     // SnapshotFinalize::d_scalars + 3: not zero (the sort gave up, the merge check failed) = nothing
+                                  // will be installed from these tables, and nothing is written
+    uint32_t* d_slot_node;        // n_members + 1 slots holding member indices: rewritten to cluster indices
+    int4* d_nquad;                // ... and the node word of the slot records
+};
+hipError_t launch_snapshot_set_scatter(const SnapshotSetScatter& s, hipStream_t stream);
 
 // Device self-test of the wave primitives (DPP scan, exact clamped division) against plain reference code.
 // Writes the number of mismatching lanes/cases to *d_mismatch.

@@ -1072,6 +1072,116 @@ hipError_t launch_snapshot_build(const SnapshotBuild& b, hipStream_t stream) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------ node sets
+// gf_snapshot_build_resident_set: the members of a bit row, gathered into compact columns the kernels above then take for a whole
+// cluster.  A workgroup's wavefronts hold 64 consecutive, 64-aligned nodes each: one word of the row per wavefront, bit `lane`.
+//   set_mark_kernel     nbits: the row once more, in name order (bit name_rank[n] for every member n)
+//   set_scan_kernel     exclusive prefix counts over the words of both rows (workgroup 0: the row, 1: nbits)
+//   set_gather_kernel   member index c = bits before n in the row; its name rank among the members = bits before name_rank[n] in
+//                       nbits — the compact name_rank metadata_kernel turns into the sort's starting permutation
+//   set_scatter_kernel  behind the finalize: node-indexed tables back at the cluster's size, slot -> node in cluster indices
+__global__ __launch_bounds__(256) void set_mark_kernel(SnapshotSetGather g) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= g.n_nodes) return;
+    const uint64_t word = g.d_words[n >> 6];
+    if (!((word >> (n & 63u)) & 1ull)) return;
+    const uint32_t r = g.d_name_rank[n];
+    if (r >= g.n_nodes) return;  // (never: a permutation, checked on the host; a store outside the row must not depend on that)
+    atomicOr(reinterpret_cast<unsigned long long*>(&g.d_nbits[r >> 6]), 1ull << (r & 63u));
+}
+
+constexpr uint32_t kSetScanBlock = 1024;
+__global__ __launch_bounds__(kSetScanBlock) void set_scan_kernel(SnapshotSetGather g) {
+    __shared__ uint32_t wsum[kSetScanBlock / 64];
+    const uint64_t* const src = blockIdx.x == 0 ? g.d_words : g.d_nbits;
+    uint32_t* const dst = g.d_prefix + (size_t)blockIdx.x * g.n_words;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t running = 0;
+    for (uint32_t base = 0; base < g.n_words; base += kSetScanBlock) {
+        const uint32_t w = base + threadIdx.x;
+        const uint32_t mine = w < g.n_words ? (uint32_t)__popcll(src[w]) : 0u;
+        uint32_t incl = mine;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = __shfl_up(incl, o, 64);
+            if ((int)lane >= o) incl += t;
+        }
+        if (lane == 63u) wsum[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t v = 0; v < kSetScanBlock / 64; ++v) {
+            const uint32_t t = wsum[v];
+            before += v < wave ? t : 0u;
+            total += t;
+        }
+        if (w < g.n_words) dst[w] = running + before + incl - mine;
+        running += total;
+        __syncthreads();  // wsum is rewritten by the next step
+    }
+}
+
+__global__ __launch_bounds__(256) void set_gather_kernel(SnapshotSetGather g) {
+    const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= g.n_nodes) return;
+    const uint32_t lane = n & 63u;
+    const uint64_t word = g.d_words[n >> 6];
+    if (!((word >> lane) & 1ull)) return;
+    const uint32_t c = g.d_prefix[n >> 6] + (uint32_t)__popcll(word & ((1ull << lane) - 1ull));
+    const uint32_t r = g.d_name_rank[n];
+    if (c >= g.n_members || r >= g.n_nodes) return;  // (never: the host counted the row and checked the permutation)
+    const uint32_t cr = g.d_prefix[g.n_words + (r >> 6)] + (uint32_t)__popcll(g.d_nbits[r >> 6] & ((1ull << (r & 63u)) - 1ull));
+    if (cr >= g.n_members) return;
+    const size_t N = g.n_nodes, M = g.n_members;
+    for (int j = 0; j < 3; ++j) {
+        g.c_alloc[(size_t)j * M + c] = g.d_alloc[(size_t)j * N + n];
+        g.c_usage[(size_t)j * M + c] = g.d_usage[(size_t)j * N + n];
+        if (g.d_overhead != nullptr) g.c_overhead[(size_t)j * M + c] = g.d_overhead[(size_t)j * N + n];
+    }
+    g.c_zone[c] = g.d_zone[n];
+    g.c_flags[c] = g.d_flags[n];
+    g.c_name_rank[c] = cr;
+    g.c_node[c] = n;
+}
+
+__global__ __launch_bounds__(256) void set_scatter_kernel(SnapshotSetScatter s) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t N = s.n_nodes, M = s.n_members;
+    if (s.d_status[0] != 0u) return;  // (uniform) the build is refused or goes through the host: the compact tables are not an answer
+    if (i < s.n_nodes) {  // node i of the cluster
+        const uint32_t lane = i & 63u;
+        const uint64_t word = s.d_words[i >> 6];
+        const uint32_t c = s.d_prefix[i >> 6] + (uint32_t)__popcll(word & ((1ull << lane) - 1ull));
+        const bool member = ((word >> lane) & 1ull) && c < s.n_members;
+        s.d_node_slot[i] = member ? s.c_node_slot[c] : GF_NO_NODE;
+        for (int j = 0; j < 6; ++j) s.d_node_tab[(size_t)j * N + i] = member ? s.c_node_tab[(size_t)j * M + c] : 0;
+    }
+    if (i < s.n_members) {  // slot i of the layout (the sentinel behind them keeps GF_NO_NODE)
+        const uint32_t c = s.d_slot_node[i];
+        if (c < s.n_members) {
+            const uint32_t node = s.c_node[c];
+            s.d_slot_node[i] = node;
+            s.d_nquad[i].w = (int)node;
+        }
+    }
+}
+
+hipError_t launch_snapshot_set_gather(const SnapshotSetGather& g_, hipStream_t stream) {
+    SnapshotSetGather g = g_;
+    g.n_words = (g.n_nodes + 63u) / 64u;
+    if (g.n_nodes == 0 || g.n_members == 0) return hipSuccess;
+    const dim3 block(256), grid((g.n_nodes + 255u) / 256u);
+    hipLaunchKernelGGL(set_mark_kernel, grid, block, 0, stream, g);
+    hipLaunchKernelGGL(set_scan_kernel, dim3(2), dim3(kSetScanBlock), 0, stream, g);
+    hipLaunchKernelGGL(set_gather_kernel, grid, block, 0, stream, g);
+    return hipGetLastError();
+}
+
+hipError_t launch_snapshot_set_scatter(const SnapshotSetScatter& s, hipStream_t stream) {
+    if (s.n_nodes == 0) return hipSuccess;
+    const uint32_t most = s.n_nodes > s.n_members ? s.n_nodes : s.n_members;
+    hipLaunchKernelGGL(set_scatter_kernel, dim3((most + 255u) / 256u), dim3(256), 0, stream, s);
+    return hipGetLastError();
+}
+
 size_t snapshot_sort_work_words() { return kSortHistWords + kSortStateWords + 2u * kSortScalars; }
 uint32_t snapshot_sort_error_word() { return kSortHistWords + 2u; }  // (+ 1: the label merge check's word)
 

@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = [
     "gf_usage_reset", "gf_usage_apply", "gf_overhead_update", "gf_set_option", "gf_chain_cache_stats", "gf_generation", "gf_shard_count", "gf_ctx_view",
     "gf_worker_fit", "gf_worker_submit_dev", "gf_worker_wait", "gf_worker_stop", "gf_worker_stats", "gf_worker_geometry", "gf_worker_kernel_time", "gf_call_phases",
     "gf_cluster_fit_feasible", "gf_cluster_fit_feasible_sets", "gf_snapshot_build_info", "gf_cluster_executor_fit",
+    "gf_snapshot_build_resident_set", "gf_snapshot_set_info",
 ]
 
 
@@ -241,6 +242,10 @@ def load() -> C.CDLL:
     L.gf_chain_cache_stats.argtypes = [p, i32, p]
     L.gf_snapshot_build_info.restype = i32
     L.gf_snapshot_build_info.argtypes = [p, p]
+    L.gf_snapshot_build_resident_set.restype = i32
+    L.gf_snapshot_build_resident_set.argtypes = [p, p, u32, p, p, p, p, p, p, p, p, p, p, p]
+    L.gf_snapshot_set_info.restype = i32
+    L.gf_snapshot_set_info.argtypes = [p, p]
     _lib = L
     return L
 

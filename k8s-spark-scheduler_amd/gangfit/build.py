@@ -18,6 +18,7 @@ HOST_CLUSTER_SCAN_TEST_PATH = os.path.join(_PKG_ROOT, "host_cluster_scan_test") 
 HOST_CLUSTER_SCAN_SETS_TEST_PATH = os.path.join(_PKG_ROOT, "host_cluster_scan_sets_test")  # ... of the all-groups scan (host_cluster_scan_sets_test.cpp)
 HOST_SNAPSHOT_LABELS_TEST_PATH = os.path.join(_PKG_ROOT, "host_snapshot_labels_test")  # ... of builds with a prioritized label (host_snapshot_labels_test.cpp)
 HOST_EXECUTOR_RESIDENT_TEST_PATH = os.path.join(_PKG_ROOT, "host_executor_resident_test")  # ... of the resident executor Filter (host_executor_resident_test.cpp)
+HOST_GROUP_FILTER_TEST_PATH = os.path.join(_PKG_ROOT, "host_group_filter_test")  # ... of the driver Filters of several groups (host_group_filter_test.cpp)
 INCLUDE = os.path.join(_REPO_ROOT, "include")
 
 _SOURCES = ["gangfit_kernels.hip", "gangfit_snapshot.hip", "gangfit_api.cpp", "gangfit_api_snapshot.cpp", "gangfit_api_fit.cpp",
@@ -105,6 +106,11 @@ def build_host(force: bool = False) -> str:
     if os.path.exists(exec_src) and (force or _stale(HOST_EXECUTOR_RESIDENT_TEST_PATH, [exec_src, HOST_LIB_PATH] + hdrs)):
         cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, exec_src, "-L", _PKG_ROOT,
                "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_EXECUTOR_RESIDENT_TEST_PATH]
+        subprocess.check_call(cmd)
+    group_src = os.path.join(host_dir, "tests", "host_group_filter_test.cpp")
+    if os.path.exists(group_src) and (force or _stale(HOST_GROUP_FILTER_TEST_PATH, [group_src, HOST_LIB_PATH] + hdrs)):
+        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, group_src, "-L", _PKG_ROOT,
+               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_GROUP_FILTER_TEST_PATH]
         subprocess.check_call(cmd)
     bench_src = os.path.join(host_dir, "tests", "host_bench.cpp")
     if os.path.exists(bench_src) and (force or _stale(HOST_BENCH_PATH, [bench_src, HOST_LIB_PATH] + hdrs)):

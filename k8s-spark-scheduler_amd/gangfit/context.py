@@ -240,6 +240,31 @@ class Context:
                                 exec_label_rank=None, want_orders: bool = True, res_cols=None, resident_usage: bool = False):
         """gf_snapshot_build_resident.  res_cols = (cpu, mem, gpu) contiguous int64 columns of the reservation entries, for
         callers that keep them that way (the C ABI takes columns; res_req = (n, 3) rows is split here on every call)."""
+        return self._build_resident(self._lib.gf_snapshot_build_resident, (), res_node, res_req, node_flags, driver_label_rank,
+                                    exec_label_rank, want_orders, res_cols, resident_usage)
+
+    def build_snapshot_resident_set(self, members, res_node=None, res_req=None, node_flags=None, driver_label_rank=None,
+                                    exec_label_rank=None, want_orders: bool = True, res_cols=None, resident_usage: bool = False):
+        """gf_snapshot_build_resident_set: build_snapshot_resident over the nodes of `members` only — a list of node indices or
+        an (n_nodes,) boolean mask of the resident cluster; None = every node (gf_snapshot_build_resident itself).  Every other
+        argument and the result are build_snapshot_resident's; node-indexed arrays keep the cluster's size."""
+        n = self._cluster_n
+        words = None
+        if members is not None:
+            mem = np.asarray(members)
+            if mem.dtype != np.bool_:
+                idx = mem.astype(np.int64).reshape(-1)
+                assert ((idx >= 0) & (idx < n)).all(), "a member index outside the cluster"
+                mem = np.zeros(n, dtype=bool)
+                mem[idx] = True
+            assert mem.shape == (n,), "one truth value per node of the cluster"
+            words = np.ascontiguousarray(pack_node_sets(mem.reshape(1, n), n)[0]) if n else np.zeros(1, dtype=np.uint64)
+        return self._build_resident(self._lib.gf_snapshot_build_resident_set, (N.ptr(words),), res_node, res_req, node_flags,
+                                    driver_label_rank, exec_label_rank, want_orders, res_cols, resident_usage)
+
+    def _build_resident(self, call, head, res_node, res_req, node_flags, driver_label_rank, exec_label_rank, want_orders, res_cols,
+                        resident_usage):
+        """The arguments the two resident builds share, behind `head` (nothing | the member row)."""
         n = self._cluster_n
         rn = np.zeros(0, dtype=np.uint32) if res_node is None else np.ascontiguousarray(res_node, dtype=np.uint32)
         if res_cols is not None:
@@ -253,15 +278,21 @@ class Context:
         self.n_nodes = n
         n_res = N.GF_RESIDENT_USAGE if resident_usage else len(rn)  # resident_usage: build from the sums of usage_apply
         if not want_orders:
-            self._check(self._lib.gf_snapshot_build_resident(self._h, n_res, N.ptr(rn), *[N.ptr(c) for c in rcols], N.ptr(fl),
-                                                             N.ptr(dl), N.ptr(el), None, None, None, None))
+            self._check(call(self._h, *head, n_res, N.ptr(rn), *[N.ptr(c) for c in rcols], N.ptr(fl), N.ptr(dl), N.ptr(el), None, None,
+                             None, None))
             return None, None
         d_out, x_out = np.zeros(n + 1, dtype=np.uint32), np.zeros(n + 1, dtype=np.uint32)
         nd, nx = C.c_uint32(0), C.c_uint32(0)
-        self._check(self._lib.gf_snapshot_build_resident(self._h, n_res, N.ptr(rn), *[N.ptr(c) for c in rcols], N.ptr(fl),
-                                                         N.ptr(dl), N.ptr(el), N.ptr(d_out), C.byref(nd), N.ptr(x_out),
-                                                         C.byref(nx)))
+        self._check(call(self._h, *head, n_res, N.ptr(rn), *[N.ptr(c) for c in rcols], N.ptr(fl), N.ptr(dl), N.ptr(el), N.ptr(d_out),
+                         C.byref(nd), N.ptr(x_out), C.byref(nx)))
         return d_out[: nd.value].copy(), x_out[: nx.value].copy()
+
+    def snapshot_set_info(self):
+        """gf_snapshot_set_info: (1 when the installed snapshot was built from a node set, its members — n_nodes otherwise —,
+        slots of the installed layout, its 64-slot chunks)"""
+        out = np.zeros(4, dtype=np.uint32)
+        self._check(self._lib.gf_snapshot_set_info(self._h, N.ptr(out)))
+        return tuple(int(v) for v in out)
 
     def snapshot(self):
         """(avail, sched) of the installed snapshot, (n_nodes, 3) int64 each."""

@@ -758,6 +758,36 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
                                                               const std::vector<std::string>& nodeNames,
                                                               const FlatCluster& cluster, const FlatReservations* flat,
                                                               const FlatOverhead* flatOverhead) {
+    return selectDriverNodeFlatOver(instanceGroup, driver, nodeNames, cluster, nullptr, flat, flatOverhead);
+}
+
+SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatGroup(const std::string& instanceGroup, const Pod& driver,
+                                                                   const std::vector<std::string>& nodeNames,
+                                                                   const FlatCluster& cluster, const std::vector<Node>& groupNodes,
+                                                                   const FlatReservations* flat, const FlatOverhead* flatOverhead) {
+    // availableNodes as one bit row of the resident cluster (include/gangfit.h, gf_snapshot_build_resident_set)
+    std::vector<uint64_t> members((cluster.names.size() + 63) / 64, 0);
+    bool listed = true;
+    for (const Node& node : groupNodes) {
+        const auto it = cluster.index.find(node.Name);
+        if (it == cluster.index.end()) {
+            listed = false;  // a node the lister knows and `cluster` does not
+            break;
+        }
+        members[it->second >> 6] |= 1ull << (it->second & 63u);
+    }
+    if (listed) {
+        SelectNodeResult out = selectDriverNodeFlatOver(instanceGroup, driver, nodeNames, cluster, &members, flat, flatOverhead);
+        if (out.served) return out;
+    }
+    return selectDriverNode(instanceGroup, driver, nodeNames, groupNodes);
+}
+
+// members: nullptr = `cluster` describes exactly the driver's nodes; else the row of the driver's nodes inside it.
+SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatOver(const std::string& instanceGroup, const Pod& driver,
+                                                                  const std::vector<std::string>& nodeNames,
+                                                                  const FlatCluster& cluster, const std::vector<uint64_t>* members,
+                                                                  const FlatReservations* flat, const FlatOverhead* flatOverhead) {
     SelectNodeResult out;
     auto not_served = [&](const std::string& why) {
         out.served = false;
@@ -893,28 +923,39 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
         // nothing changed since this extender's last Filter (no overhead row differed either: a change above cleared built_epoch_):
         // the installed snapshot IS this request's snapshot
         const bool same_snapshot = keep_usage && built_epoch_ != 0 && gen[0] == built_epoch_ && built_cluster_ == cluster.version &&
-                                   built_usage_ == flat->version && built_flags_ == flags;
+                                   built_usage_ == flat->version && built_flags_ == flags &&
+                                   (members != nullptr ? built_set_ && built_members_ == *members : !built_set_);
         if (resident_route && !same_snapshot) {
             built_epoch_ = 0;
+            // (a NULL row is gf_snapshot_build_resident itself; another group's row rebuilds from the same resident columns and
+            //  usage sums: no gf_cluster_set, no usage replay)
+            const uint64_t* const row = members != nullptr ? members->data() : nullptr;
             const int brc = keep_usage
-                                ? gf_snapshot_build_resident(ctx, GF_RESIDENT_USAGE, nullptr, nullptr, nullptr, nullptr, flags.data(),
-                                                             nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
-                                : gf_snapshot_build_resident(ctx, (uint32_t)rnode.size(), rnode.data(), rreq[0].data(),
-                                                             rreq[1].data(), rreq[2].data(), flags.data(), nullptr, nullptr, nullptr,
-                                                             nullptr, nullptr, nullptr);
+                                ? gf_snapshot_build_resident_set(ctx, row, GF_RESIDENT_USAGE, nullptr, nullptr, nullptr, nullptr,
+                                                                 flags.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
+                                : gf_snapshot_build_resident_set(ctx, row, (uint32_t)rnode.size(), rnode.data(), rreq[0].data(),
+                                                                 rreq[1].data(), rreq[2].data(), flags.data(), nullptr, nullptr,
+                                                                 nullptr, nullptr, nullptr, nullptr);
             if (brc != GF_OK) {
                 resident_cluster_ = 0;
                 resident_usage_ = 0;
-                return not_served(std::string("gf_snapshot_build_resident: ") + gf_last_error(ctx));
+                return not_served(std::string("gf_snapshot_build_resident_set: ") + gf_last_error(ctx));
             }
             if (keep_usage && gf_generation(ctx, gen) == GF_OK) {
                 built_epoch_ = gen[0];
                 built_cluster_ = cluster.version;
                 built_usage_ = flat->version;
                 built_flags_ = flags;
+                built_set_ = members != nullptr;
+                if (built_set_)
+                    built_members_ = *members;
+                else
+                    built_members_.clear();
             }
         }
     }
+    if (!resident_route && members != nullptr)  // the full build below installs every node of `cluster`: not this group's snapshot
+        return not_served("the resident route could not take this request");
     if (!resident_route) {  // what the resident route could not take: everything travels, nothing stays
         resident_cluster_ = 0;
         built_epoch_ = 0;

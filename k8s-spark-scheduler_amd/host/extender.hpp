@@ -133,6 +133,17 @@ public:
     SelectNodeResult selectDriverNodeFlat(const std::string& instanceGroup, const Pod& driver,
                                           const std::vector<std::string>& nodeNames, const FlatCluster& cluster,
                                           const FlatReservations* flat = nullptr, const FlatOverhead* flatOverhead = nullptr);
+    // The same Filter when `cluster` holds EVERY instance group (what scanForUnschedulablePodsAllGroups and rescheduleExecutorFlat
+    // want resident) and groupNodes = availableNodes, the nodes the driver's required affinity matches (resource.go:292-304): the
+    // snapshot is built over the members of that row only (include/gangfit.h, gf_snapshot_build_resident_set), so one resident
+    // cluster, one usage stream and one overhead stream serve the Filters of every group.  The sync is selectDriverNodeFlat's;
+    // "nothing changed => no rebuild" additionally compares the member row, so a Filter for another group rebuilds — without a
+    // gf_cluster_set and without a usage replay.  Whatever this route cannot take (a group node outside `cluster`, a request that is
+    // not exactly representable, a refusal of the device) is answered by selectDriverNode on groupNodes.
+    SelectNodeResult selectDriverNodeFlatGroup(const std::string& instanceGroup, const Pod& driver,
+                                               const std::vector<std::string>& nodeNames, const FlatCluster& cluster,
+                                               const std::vector<Node>& groupNodes, const FlatReservations* flat = nullptr,
+                                               const FlatOverhead* flatOverhead = nullptr);
     // The next selectDriverNodeFlat rebuilds the snapshot even if nothing changed (host_bench times both).
     void forgetInstalledSnapshot() { built_epoch_ = 0; }
     // What the flat route has sent so far (tests and host_bench read them): Filters served, gf_overhead_update calls and the rows
@@ -222,6 +233,10 @@ public:
     bool shouldSkipDriverFifo(const Pod& pod, const std::string& instanceGroup) const;
 
 private:
+    SelectNodeResult selectDriverNodeFlatOver(const std::string& instanceGroup, const Pod& driver,
+                                              const std::vector<std::string>& nodeNames, const FlatCluster& cluster,
+                                              const std::vector<uint64_t>* members, const FlatReservations* flat,
+                                              const FlatOverhead* flatOverhead);
     enum class ResidentSync { ok, no_resident_route, failed };
     ResidentSync syncResident(gf_ctx* ctx, const FlatCluster& cluster, const FlatOverhead& fo, const FlatReservations* usage,
                               uint64_t gen[3], std::string* err);
@@ -240,6 +255,8 @@ private:
     // chain's checkpoints (include/gangfit.h, "Incremental FIFO chains")
     uint64_t built_epoch_ = 0, built_cluster_ = 0, built_usage_ = 0;
     std::vector<uint32_t> built_flags_;
+    bool built_set_ = false;               // ... built over a node set (selectDriverNodeFlatGroup),
+    std::vector<uint64_t> built_members_;  // this row of the resident cluster
     // The reference parses the nine annotations of every earlier driver on every Filter (sparkpods.go:73-137 from
     // resource.go:231) and matches the request's NodeNames against the node set again.  Both are pure functions of things
     // that carry a version: the flat route keeps the canonical requests per (pod UID, resourceVersion) and the candidate

@@ -477,6 +477,36 @@ int gf_avg_packing_efficiency(gf_ctx *ctx, gf_algo algo, uint32_t n_apps, const 
 int gf_packing_efficiencies(gf_ctx *ctx, gf_algo algo, const gf_app *app, const gf_result *result,
                             const uint32_t *exec_nodes, double *eff_out /* n_nodes * 3 */);
 
+/* computeAvgPackingEfficiencyForResult (internal/extender/resource.go:372-381): ComputeAvgPackingEfficiency
+ * (LIB/binpack/efficiency.go:114-156) over one PackingEfficiency per metadata KEY — the value selectDriverNode reports with
+ * metrics.ReportPackingEfficiency (:352) —, not over [DriverNode] ++ ExecutorNodes (that is gf_avg_packing_efficiency).
+ *   - per-node values: those of gf_packing_efficiencies(algo, app, result, exec_nodes); `algo` selects how the packer left the
+ *     `reserved` map (the minimal-fragmentation packers leave the driver only).
+ *   - against: GF_EFF_AGAINST_SNAPSHOT takes a node's available quantities from the installed snapshot, GF_EFF_AGAINST_RESIDUAL
+ *     from the working table of the last GF_MODE_FIFO_CHAIN call — the metadata after fitEarlierDrivers (:255), what
+ *     gf_residual_get returns: the snapshot's value for a node that owns no slot; GF_ERR_STATE when gf_residual_get would be.
+ *   - member_words (nullable: every node is a key): a bit row as in gf_snapshot_build_resident_set, W = ceil(n_nodes / 64) words;
+ *     only members are keys, non-members are not read; a bit at or beyond n_nodes is GF_ERR_INVALID.
+ *   - counts_out (nullable): {len, nodesWithGPU}.  No key with a schedulable gpu gives gpu == 1.0 (:142-143); has_capacity == 0
+ *     (or no key) gives four zeros and {0, 0} (WorstAvgPackingEfficiency), and then nothing is launched.
+ * The reference sums in map-range order, which is unspecified.  This sum is a fixed tree, a function of n_nodes, the member row
+ * and the per-node values alone (not of the grid; no floating-point atomics): (1) nodes 64c .. 64c + 63 form chunk c, a node that
+ * is no key contributes +0.0, and the chunk's partial is the balanced binary tree over its 64 positions (2i with 2i + 1, then pairs
+ * of pairs, ...); (2) the partials, padded with +0.0 to a multiple of 64, are added per position l = c mod 64 in ascending c onto
+ * +0.0; (3) the 64 sums are added by the same balanced tree.  cpu, memory, gpu (over the keys with a schedulable gpu) and max share
+ * the tree.  Where every per-node value is a dyadic rational with few bits the result is the reference's bit for bit; otherwise it
+ * lies within the reordering bound 2 (n - 1) 2^-53 sum|e_i| / len of any order's.
+ * Refusals: no schedulable columns: GF_ERR_STATE; NULL app, result or out, against not 0 or 1, k outside [0, GF_MAX_K]:
+ * GF_ERR_INVALID.  A view serves it (against its own chain's working table); a multi-device context answers as
+ * gf_packing_efficiencies does.  Leaves untouched: the installed snapshot, the three generations, the chain cache,
+ * gf_residual_get's table, the resident worker.  Blocking; the record, the result, k placements and W words go in, 40 bytes come
+ * back; its device buffers are its own. */
+#define GF_EFF_AGAINST_SNAPSHOT 0
+#define GF_EFF_AGAINST_RESIDUAL 1
+int gf_filter_efficiency(gf_ctx *ctx, gf_algo algo, int against, const gf_app *app, const gf_result *result,
+                         const uint32_t *exec_nodes, const uint64_t *member_words, gf_avg_efficiency *out,
+                         uint32_t counts_out[2] /* nullable: {len, nodesWithGPU} */);
+
 /* Placing single executors: the reschedule / extra-executor path of the executor Filter
  * (internal/extender/resource.go:594-703), n_req independent requests against the current snapshot and the executor
  * order of gf_orders_set.

@@ -991,3 +991,63 @@ func (c *Context) WorkerStop() error {
 	return nil
 }
 
+
+// FilterEfficiency is computeAvgPackingEfficiencyForResult (internal/extender/resource.go:372-381) of the pack a FilterResident /
+// FilterResidentGroup call just made — the argument of metrics.ReportPackingEfficiency (:352): ComputeAvgPackingEfficiency over
+// one PackingEfficiency per key of availableNodesSchedulingMetadata, taken against the metadata after fitEarlierDrivers (fifo:
+// the chain's residual; otherwise the installed snapshot), summed on the device (gf_filter_efficiency; the fixed summation
+// tree is spelled out in include/gangfit.h).  app / result: the last entries of that call's apps and results; members: the row
+// the call was given (nil = every node).  Call it under the same external sequencing as the Filter: another goroutine's
+// install between the two would change the snapshot it is taken against.  ok = false (with the library's message in err) leaves
+// the metric unreported and does not fail the Filter.  Unverified here (no Go toolchain).
+func (c *Context) FilterEfficiency(algo int, fifo bool, app App, result Result, members []uint64) (eff binpack.AvgPackingEfficiency, ok bool, err error) {
+	capps, _, err := flattenApps([]App{app})
+	if err != nil {
+		return eff, false, err
+	}
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	index := make(map[string]uint32, len(result.ExecutorNodes)+1)
+	want := map[string]bool{result.DriverNode: true}
+	for _, n := range result.ExecutorNodes {
+		want[n] = true
+	}
+	for i, n := range c.names { // (k + 1 names at most are looked for; a host that keeps a name index passes through it instead)
+		if want[n] {
+			index[n] = uint32(i)
+		}
+	}
+	var cres C.gf_result
+	cres.driver_node = C.GF_NO_NODE
+	execNodes := make([]uint32, 0, len(result.ExecutorNodes))
+	if result.HasCapacity {
+		d, found := index[result.DriverNode]
+		if !found {
+			return eff, false, fmt.Errorf("gangfit: driver node %q is not in the resident cluster", result.DriverNode)
+		}
+		cres.has_capacity, cres.driver_node, cres.exec_len, cres.evaluated = 1, C.uint32_t(d), C.uint32_t(len(result.ExecutorNodes)), 1
+		for _, n := range result.ExecutorNodes {
+			ix, found := index[n]
+			if !found {
+				return eff, false, fmt.Errorf("gangfit: executor node %q is not in the resident cluster", n)
+			}
+			execNodes = append(execNodes, ix)
+		}
+	}
+	var words *C.uint64_t
+	if len(members) > 0 {
+		if len(members) != (len(c.names)+63)/64 {
+			return eff, false, fmt.Errorf("gangfit: the member row has %d words, the resident cluster needs %d", len(members), (len(c.names)+63)/64)
+		}
+		words = (*C.uint64_t)(unsafe.Pointer(&members[0]))
+	}
+	against := C.int(C.GF_EFF_AGAINST_SNAPSHOT)
+	if fifo {
+		against = C.int(C.GF_EFF_AGAINST_RESIDUAL)
+	}
+	var avg C.gf_avg_efficiency
+	if rc := C.gf_filter_efficiency(c.ctx, C.gf_algo(algo), against, &capps[0], &cres, p32(execNodes), words, &avg, nil); rc != C.GF_OK {
+		return eff, false, c.err(rc)
+	}
+	return binpack.AvgPackingEfficiency{CPU: float64(avg.cpu), Memory: float64(avg.memory), GPU: float64(avg.gpu), Max: float64(avg.max)}, true, nil
+}

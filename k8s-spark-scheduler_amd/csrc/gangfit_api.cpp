@@ -305,6 +305,14 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->d_reserved.release();
     ctx->d_eff.release();
     ctx->h_avg.release();
+    ctx->d_fe_in.release();
+    ctx->h_fe_in.release();
+    ctx->d_fe_row.release();
+    ctx->d_fe_reserved.release();
+    ctx->d_fe_part.release();
+    ctx->d_fe_cnt.release();
+    ctx->d_fe_out.release();
+    ctx->h_fe_out.release();
     ctx->d_cl_i64.release();
     ctx->d_cl_u32.release();
     ctx->d_cl_usage.release();

@@ -490,6 +490,17 @@ struct gf_ctx {
                                       // that lays checkpoints 1 .. i over the snapshot instead of a copy
     } chain;
     uint64_t chain_stat[4] = {0, 0, 0, 0};  // chains | resumed chains | applications evaluated | applications skipped
+
+    // gf_filter_efficiency (gangfit_api_eff.cpp).  Its own: no other entry point reads or writes them
+    DeviceBuf<uint64_t> d_fe_in;      // the record (8 words) | its result (2 words) | k placements, sent as one copy
+    PinnedBuf<uint64_t> h_fe_in;
+    DeviceBuf<uint64_t> d_fe_row;     // the member row
+    DeviceBuf<int64_t> d_fe_reserved; // n_nodes x 3, all-zero between calls while fe_reserved_clean
+    bool fe_reserved_clean = false;   // false: a fresh allocation, or a call failed half way; zeroed as a whole before the next launch
+    DeviceBuf<double> d_fe_part;      // [4][n_pad] chunk partials
+    DeviceBuf<uint32_t> d_fe_cnt;     // [2][n_pad] chunk counts
+    DeviceBuf<gangfit::FilterEffOut> d_fe_out;
+    PinnedBuf<gangfit::FilterEffOut> h_fe_out;
 };
 
 namespace gfapi {

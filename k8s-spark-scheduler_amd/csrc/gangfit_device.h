@@ -406,6 +406,32 @@ hipError_t launch_node_efficiencies(bool reserve_execs, const EffTables& eff_by_
                                     const gf_app* d_app, const gf_result* d_result, const uint32_t* d_exec_nodes,
                                     int64_t* d_reserved, double* d_eff_out, hipStream_t stream);
 
+// ComputeAvgPackingEfficiency over one PackingEfficiency per metadata key, for ONE result (gangfit_filter_eff.inc;
+// gf_filter_efficiency): the sum is a fixed tree over 64-node chunks, spelled out in that file.
+struct FilterEffArgs {
+    EffTables tab;              // by node index: the snapshot's available quantities, the schedulable quantities
+    const int64_t* work;        // nullable: the chain's working table, cpu | mem | gpu by slot; read where a node owns a slot
+    const uint32_t* node_slot;  // ... node -> slot, GF_NO_NODE = none (needed with work)
+    uint32_t n_slots;
+    uint32_t n_nodes;
+    uint32_t n_words;           // ceil(n_nodes / 64): chunks, and words of the member row
+    uint32_t n_pad;             // n_words rounded up to a multiple of 64: entries per row of part / part_cnt
+    const uint64_t* members;    // nullable: every node is a key
+    const int64_t* reserved;    // n_nodes x 3, all-zero outside the result's nodes
+    double* part;               // [4][n_pad] chunk partials: cpu | memory | gpu | max
+    uint32_t* part_cnt;         // [2][n_pad]: keys | keys with a schedulable gpu
+};
+struct FilterEffOut {
+    double avg[4];       // gf_avg_efficiency
+    uint32_t counts[2];  // len, nodesWithGPU
+};
+inline uint32_t filter_eff_pad(uint32_t n_words) { return (uint32_t)((((uint64_t)n_words + 63u) / 64u) * 64u); }
+// d_app / d_result / d_exec_nodes: the one record, its result and its placements (exec_off = 0) on the device.  d_reserved is the
+// table args.reserved names: all-zero on entry, all-zero again when the launches have run.
+hipError_t launch_filter_efficiency(bool reserve_execs, const FilterEffArgs& args, int32_t k, const gf_app* d_app,
+                                    const gf_result* d_result, const uint32_t* d_exec_nodes, int64_t* d_reserved,
+                                    FilterEffOut* d_out, hipStream_t stream);
+
 // Node-range sharding of an independent batch (gangfit_shard.inc): a GPU owns one or more ranges
 // [c_lo, c_hi) of 64-slot chunks of the merged slot order — one per shard it hosts (one shard per device on a real box; a
 // repeated device id, the one-GPU stand-in, makes one device host several: its kernels then run ONE launch per step with a

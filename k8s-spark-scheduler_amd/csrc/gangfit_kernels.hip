@@ -1764,6 +1764,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
 #include "gangfit_findnodes.inc"
 #include "gangfit_scan.inc"
 #include "gangfit_exec_scan.inc"
+#include "gangfit_filter_eff.inc"
 
 // ------------------------------------------------------------------------------------------------ self-test
 
@@ -2580,6 +2581,38 @@ hipError_t launch_find_nodes(bool chained, const NodeTable& table, uint32_t n_re
 
 hipError_t launch_selftest(uint64_t seed, uint32_t n_cases, uint32_t* d_mismatch, hipStream_t stream) {
     hipLaunchKernelGGL(selftest_kernel, dim3(64), dim3(kWave), 0, stream, seed, n_cases, d_mismatch);
+    return hipGetLastError();
+}
+
+// (last in this file: gangfit_filter_eff.inc says why)
+hipError_t launch_filter_efficiency(bool reserve_execs, const FilterEffArgs& a, int32_t k, const gf_app* d_app,
+                                    const gf_result* d_result, const uint32_t* d_exec_nodes, int64_t* d_reserved,
+                                    FilterEffOut* d_out, hipStream_t stream) {
+    if (a.n_nodes == 0 || a.n_pad == 0 || a.n_pad % kWave != 0 || a.n_words > a.n_pad || a.reserved != d_reserved ||
+        (a.work != nullptr && a.node_slot == nullptr))
+        return hipErrorInvalidValue;
+    const unsigned k_blocks = (unsigned)(((k > 0 ? k : 1) + 255) / 256);
+    if (reserve_execs)
+        hipLaunchKernelGGL(reserved_scatter_kernel<true>, dim3(k_blocks), dim3(256), 0, stream, d_app, d_result,
+                           d_exec_nodes, a.n_nodes, reinterpret_cast<unsigned long long*>(d_reserved));
+    else
+        hipLaunchKernelGGL(reserved_scatter_kernel<false>, dim3(1), dim3(64), 0, stream, d_app, d_result, d_exec_nodes,
+                           a.n_nodes, reinterpret_cast<unsigned long long*>(d_reserved));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const uint32_t n_groups = a.n_pad / kWave;
+    const dim3 grid(n_groups < 2048u ? n_groups : 2048u);
+    if (a.work != nullptr)
+        hipLaunchKernelGGL(filter_efficiency_partials_kernel<true>, grid, dim3(kWave * kFeWaves), 0, stream, a);
+    else
+        hipLaunchKernelGGL(filter_efficiency_partials_kernel<false>, grid, dim3(kWave * kFeWaves), 0, stream, a);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (reserve_execs)
+        hipLaunchKernelGGL(filter_efficiency_combine_kernel<true>, dim3(1), dim3(kWave), 0, stream, a, d_app, d_result, d_exec_nodes,
+                           d_reserved, d_out);
+    else
+        hipLaunchKernelGGL(filter_efficiency_combine_kernel<false>, dim3(1), dim3(kWave), 0, stream, a, d_app, d_result, d_exec_nodes,
+                           d_reserved, d_out);
     return hipGetLastError();
 }
 

@@ -40,6 +40,8 @@ assert APP_DTYPE.itemsize == 64 and RESULT_DTYPE.itemsize == 16
 GF_RESIDENT_USAGE = 0xFFFFFFFF
 GF_ANY_ZONE = 0xFFFFFFFF
 GF_WORKER_LEAVE_AFTER = 2
+GF_EFF_AGAINST_SNAPSHOT = 0
+GF_EFF_AGAINST_RESIDUAL = 1
 
 EXPORTED_SYMBOLS = [
     "gf_version", "gf_init", "gf_destroy", "gf_last_error", "gf_snapshot_set", "gf_orders_set", "gf_fit_batch", "gf_fit_feasible",
@@ -53,7 +55,7 @@ EXPORTED_SYMBOLS = [
     "gf_usage_reset", "gf_usage_apply", "gf_overhead_update", "gf_set_option", "gf_chain_cache_stats", "gf_generation", "gf_shard_count", "gf_ctx_view",
     "gf_worker_fit", "gf_worker_submit_dev", "gf_worker_wait", "gf_worker_stop", "gf_worker_stats", "gf_worker_geometry", "gf_worker_kernel_time", "gf_call_phases",
     "gf_cluster_fit_feasible", "gf_cluster_fit_feasible_sets", "gf_snapshot_build_info", "gf_cluster_executor_fit",
-    "gf_snapshot_build_resident_set", "gf_snapshot_set_info",
+    "gf_snapshot_build_resident_set", "gf_snapshot_set_info", "gf_filter_efficiency",
 ]
 
 
@@ -134,6 +136,8 @@ def load() -> C.CDLL:
     L.gf_avg_packing_efficiency.argtypes = [p, i32, u32, p, p, p, u64, p]
     L.gf_packing_efficiencies.restype = i32
     L.gf_packing_efficiencies.argtypes = [p, i32, p, p, p, p]
+    L.gf_filter_efficiency.restype = i32
+    L.gf_filter_efficiency.argtypes = [p, i32, i32, p, p, p, p, p, p]
     L.gf_hbm_probe.restype = i32
     L.gf_hbm_probe.argtypes = [p, u64, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.gf_graph_begin.restype = i32

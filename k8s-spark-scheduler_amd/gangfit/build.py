@@ -19,10 +19,11 @@ HOST_CLUSTER_SCAN_SETS_TEST_PATH = os.path.join(_PKG_ROOT, "host_cluster_scan_se
 HOST_SNAPSHOT_LABELS_TEST_PATH = os.path.join(_PKG_ROOT, "host_snapshot_labels_test")  # ... of builds with a prioritized label (host_snapshot_labels_test.cpp)
 HOST_EXECUTOR_RESIDENT_TEST_PATH = os.path.join(_PKG_ROOT, "host_executor_resident_test")  # ... of the resident executor Filter (host_executor_resident_test.cpp)
 HOST_GROUP_FILTER_TEST_PATH = os.path.join(_PKG_ROOT, "host_group_filter_test")  # ... of the driver Filters of several groups (host_group_filter_test.cpp)
+HOST_FILTER_EFFICIENCY_TEST_PATH = os.path.join(_PKG_ROOT, "host_filter_efficiency_test")  # ... of the Filters' packing efficiency (host_filter_efficiency_test.cpp)
 INCLUDE = os.path.join(_REPO_ROOT, "include")
 
 _SOURCES = ["gangfit_kernels.hip", "gangfit_snapshot.hip", "gangfit_api.cpp", "gangfit_api_snapshot.cpp", "gangfit_api_fit.cpp",
-            "gangfit_api_worker.cpp", "gangfit_api_group.cpp", "gangfit_api_scan.cpp"]
+            "gangfit_api_worker.cpp", "gangfit_api_group.cpp", "gangfit_api_scan.cpp", "gangfit_api_eff.cpp"]
 _HEADERS = [os.path.join(CSRC, "gangfit_device.h"), os.path.join(CSRC, "gangfit_slot_layout.h"), os.path.join(CSRC, "gangfit_label_plan.h"),
             os.path.join(CSRC, "gangfit_worker_rounds.h"), os.path.join(CSRC, "gangfit_chain_lds.h"),
             os.path.join(INCLUDE, "gangfit.h")]
@@ -44,7 +45,7 @@ def _stale(target: str, deps) -> bool:
 
 def build_native(force: bool = False) -> str:
     """hipcc --offload-arch=gfx950 ... -> k8s-spark-scheduler_amd/libgangfit.so.  The translation units are compiled side by side
-    (one hipcc process each: the two kernel files take most of a minute, the six host files a few seconds), then linked."""
+    (one hipcc process each: the two kernel files take most of a minute, the seven host files a few seconds), then linked."""
     srcs = [os.path.join(CSRC, s) for s in _SOURCES]
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + _HEADERS  # .inc files are #included by the .hip
     if force or _stale(LIB_PATH, deps):
@@ -111,6 +112,11 @@ def build_host(force: bool = False) -> str:
     if os.path.exists(group_src) and (force or _stale(HOST_GROUP_FILTER_TEST_PATH, [group_src, HOST_LIB_PATH] + hdrs)):
         cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, group_src, "-L", _PKG_ROOT,
                "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_GROUP_FILTER_TEST_PATH]
+        subprocess.check_call(cmd)
+    eff_src = os.path.join(host_dir, "tests", "host_filter_efficiency_test.cpp")
+    if os.path.exists(eff_src) and (force or _stale(HOST_FILTER_EFFICIENCY_TEST_PATH, [eff_src, HOST_LIB_PATH] + hdrs)):
+        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, eff_src, "-L", _PKG_ROOT,
+               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_FILTER_EFFICIENCY_TEST_PATH]
         subprocess.check_call(cmd)
     bench_src = os.path.join(host_dir, "tests", "host_bench.cpp")
     if os.path.exists(bench_src) and (force or _stale(HOST_BENCH_PATH, [bench_src, HOST_LIB_PATH] + hdrs)):

@@ -398,6 +398,29 @@ class Context:
                                                       N.ptr(ex) if len(ex) else None, N.ptr(eff)))
         return eff
 
+    def filter_efficiency(self, algo: int, app, result, exec_nodes, against: str = "residual", members=None):
+        """gf_filter_efficiency: (avg, counts) — avg = (4,) float64 [CPU, Memory, GPU, Max], ComputeAvgPackingEfficiency over one
+        PackingEfficiency per metadata key (computeAvgPackingEfficiencyForResult), counts = (len, nodesWithGPU).
+        app / result: one gf_app / gf_result record (or arrays of one); exec_nodes: its k placements (node indices).
+        against: "residual" (the working table of the last FIFO chain) or "snapshot".  members: (n_nodes,) truth values, or the
+        packed (W,) uint64 row itself; None = every node is a key."""
+        a = np.ascontiguousarray(app, dtype=N.APP_DTYPE).reshape(1)
+        r = np.ascontiguousarray(result, dtype=N.RESULT_DTYPE).reshape(1)
+        ex = None if exec_nodes is None else np.ascontiguousarray(exec_nodes, dtype=np.uint32).reshape(-1)
+        how = {"snapshot": N.GF_EFF_AGAINST_SNAPSHOT, "residual": N.GF_EFF_AGAINST_RESIDUAL}.get(against, against)
+        words = None
+        if members is not None:
+            m = np.asarray(members)
+            words = np.ascontiguousarray(m) if m.dtype == np.uint64 else pack_node_sets(m.reshape(1, -1), self.n_nodes)[0]
+            assert len(words) == (self.n_nodes + 63) // 64, "one bit per node of the snapshot"
+        avg = np.zeros(4, dtype=np.float64)
+        counts = np.zeros(2, dtype=np.uint32)
+        self._check(self._lib.gf_filter_efficiency(self._h, algo, int(how), N.ptr(a), N.ptr(r),
+                                                   N.ptr(ex) if ex is not None and len(ex) else None,
+                                                   N.ptr(words) if words is not None and len(words) else None, N.ptr(avg),
+                                                   N.ptr(counts)))
+        return avg, (int(counts[0]), int(counts[1]))
+
     def executor_fit(self, exe, reserved=None, minimal_fragmentation: bool = False, hosts=None, node_zone=None,
                      req_zone=None) -> np.ndarray:
         """One node index (GF_NO_NODE = no capacity) per executor request: rescheduleExecutor's first-fit loop, or

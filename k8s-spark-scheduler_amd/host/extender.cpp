@@ -33,6 +33,18 @@ bool SparkSchedulerExtender::shouldSkipDriverFifo(const Pod& pod, const std::str
     return pod.CreationTimestampNanos + age > nowNanos;
 }
 
+// computeAvgPackingEfficiencyForResult (resource.go:329, 372-381) of the pack a chain just made: over every key of the installed
+// snapshot (row: the keys inside a resident cluster, nullptr = all), against what fitEarlierDrivers left when FIFO is on.
+static void fillEfficiency(gf_ctx* ctx, gf_algo algo, bool fifo, const gf_app& app, const gf_result& result, const uint32_t* exec_nodes,
+                           const uint64_t* row, SelectNodeResult* out) {
+    gf_avg_efficiency avg{};
+    if (gf_filter_efficiency(ctx, algo, fifo ? GF_EFF_AGAINST_RESIDUAL : GF_EFF_AGAINST_SNAPSHOT, &app, &result, exec_nodes, row, &avg,
+                             nullptr) != GF_OK)
+        return;
+    out->efficiency = AvgPackingEfficiency{avg.cpu, avg.memory, avg.gpu, avg.max};
+    out->has_efficiency = true;
+}
+
 SelectNodeResult SparkSchedulerExtender::selectDriverNode(const std::string& instanceGroup, const Pod& driver,
                                                           const std::vector<std::string>& nodeNames,
                                                           const std::vector<Node>& availableNodes) {
@@ -122,6 +134,7 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNode(const std::string& ins
     for (uint32_t i = 0; i < last.exec_len; ++i) executorNodes.push_back(snap.names[exec[off + i]]);
     out.node = snap.names[last.driver_node];
     out.outcome = outcome::success;
+    fillEfficiency(binpacker_.ctx, binpacker_.Algo, isFIFO_, cur, last, exec.data() + off, nullptr, &out);
     out.created = newResourceReservation(out.node, executorNodes, driver, resources->DriverResources,
                                          resources->ExecutorResources);
     return out;
@@ -989,6 +1002,8 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatOver(const std::str
     for (uint32_t i = 0; i < last.exec_len; ++i) executorNodes.push_back(cluster.names[exec[off + i]]);
     out.node = cluster.names[last.driver_node];
     out.outcome = outcome::success;
+    // (the group route's keys are the row the snapshot was built from: built_members_ when recorded, this request's row always)
+    fillEfficiency(ctx, binpacker_.Algo, isFIFO_, cur, last, exec.data() + off, members != nullptr ? members->data() : nullptr, &out);
     out.created = newResourceReservation(out.node, executorNodes, driver, resources->DriverResources,
                                          resources->ExecutorResources);
     return out;

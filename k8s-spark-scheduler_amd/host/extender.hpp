@@ -51,12 +51,21 @@ ResourceReservation newResourceReservation(const std::string& driverNode, const 
                                            const Resources& executorResources);
 std::string executorReservationName(int i);  // "executor-<i+1>"
 
+struct AvgPackingEfficiency {  // binpack.AvgPackingEfficiency (LIB/binpack/efficiency.go:25-31)
+    double CPU = 0.0, Memory = 0.0, GPU = 0.0, Max = 0.0;
+};
+
 struct SelectNodeResult {
     std::string node;     // empty on failure
     std::string outcome;  // one of outcome::*
     std::string error;    // the reference's error text (or why the device could not serve the request)
     bool served = true;   // false: the accelerator could not serve the request -> the Go host must run its own path
     std::optional<ResourceReservation> created;  // what CreateReservations would persist
+    // computeAvgPackingEfficiencyForResult (resource.go:329, 372-381): what metrics.ReportPackingEfficiency is given (:352), over
+    // every metadata key, against the metadata after fitEarlierDrivers (gf_filter_efficiency).  Filled by the driver Filters on
+    // `success` with a fresh pack; has_efficiency stays false when the call is refused — that does not fail the Filter.
+    AvgPackingEfficiency efficiency;
+    bool has_efficiency = false;
 };
 
 // The node side of the cluster in the flat form gf_snapshot_build consumes.  Built when the node set changes (an informer

@@ -9,7 +9,8 @@ INC = os.path.join(REPO, "include")
 
 def demangle(names):
     out = subprocess.run(["c++filt"] + names, capture_output=True, text=True).stdout.split("\n")
-    return [re.sub(r"^void gangfit::\(anonymous namespace\)::|^void gangfit::|\(.*$", "", o) for o in out[: len(names)]]
+    # (a template kernel demangles with its return type, a plain one — filter_efficiency_partials_kernel — without)
+    return [re.sub(r"^(void )?gangfit::(\(anonymous namespace\)::)?|\(.*$", "", o) for o in out[: len(names)]]
 
 
 def table(src, extra):

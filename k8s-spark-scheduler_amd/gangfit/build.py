@@ -2,6 +2,7 @@
 package so that it travels with the repository snapshot to the GPU box."""
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -78,51 +79,24 @@ def build_host(force: bool = False) -> str:
         cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I", INCLUDE, "-I", host_dir, *srcs,
                "-L", _PKG_ROOT, "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_LIB_PATH]
         subprocess.check_call(cmd)
-    test_src = os.path.join(host_dir, "tests", "host_test.cpp")
-    if os.path.exists(test_src) and (force or _stale(HOST_TEST_PATH, [test_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, test_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_TEST_PATH]
-        subprocess.check_call(cmd)
-    over_src = os.path.join(host_dir, "tests", "host_overhead_test.cpp")
-    if os.path.exists(over_src) and (force or _stale(HOST_OVERHEAD_TEST_PATH, [over_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, over_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_OVERHEAD_TEST_PATH]
-        subprocess.check_call(cmd)
-    scan_src = os.path.join(host_dir, "tests", "host_cluster_scan_test.cpp")
-    if os.path.exists(scan_src) and (force or _stale(HOST_CLUSTER_SCAN_TEST_PATH, [scan_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, scan_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_CLUSTER_SCAN_TEST_PATH]
-        subprocess.check_call(cmd)
-    sets_src = os.path.join(host_dir, "tests", "host_cluster_scan_sets_test.cpp")
-    if os.path.exists(sets_src) and (force or _stale(HOST_CLUSTER_SCAN_SETS_TEST_PATH, [sets_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, sets_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_CLUSTER_SCAN_SETS_TEST_PATH]
-        subprocess.check_call(cmd)
-    labels_src = os.path.join(host_dir, "tests", "host_snapshot_labels_test.cpp")
-    if os.path.exists(labels_src) and (force or _stale(HOST_SNAPSHOT_LABELS_TEST_PATH, [labels_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, labels_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_SNAPSHOT_LABELS_TEST_PATH]
-        subprocess.check_call(cmd)
-    exec_src = os.path.join(host_dir, "tests", "host_executor_resident_test.cpp")
-    if os.path.exists(exec_src) and (force or _stale(HOST_EXECUTOR_RESIDENT_TEST_PATH, [exec_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, exec_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_EXECUTOR_RESIDENT_TEST_PATH]
-        subprocess.check_call(cmd)
-    group_src = os.path.join(host_dir, "tests", "host_group_filter_test.cpp")
-    if os.path.exists(group_src) and (force or _stale(HOST_GROUP_FILTER_TEST_PATH, [group_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, group_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_GROUP_FILTER_TEST_PATH]
-        subprocess.check_call(cmd)
-    eff_src = os.path.join(host_dir, "tests", "host_filter_efficiency_test.cpp")
-    if os.path.exists(eff_src) and (force or _stale(HOST_FILTER_EFFICIENCY_TEST_PATH, [eff_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O1", "-std=c++17", "-Wall", "-pthread", "-I", INCLUDE, "-I", host_dir, eff_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_FILTER_EFFICIENCY_TEST_PATH]
-        subprocess.check_call(cmd)
-    bench_src = os.path.join(host_dir, "tests", "host_bench.cpp")
-    if os.path.exists(bench_src) and (force or _stale(HOST_BENCH_PATH, [bench_src, HOST_LIB_PATH] + hdrs)):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-I", INCLUDE, "-I", host_dir, bench_src, "-L", _PKG_ROOT,
-               "-lgangfit_host", "-lgangfit", "-Wl,-rpath,$ORIGIN", "-o", HOST_BENCH_PATH]
-        subprocess.check_call(cmd)
+    # the programs on top of the library: (source under host/tests/, output, flags); the tests run threads, host_bench is timed
+    test_flags, bench_flags = ["-O1", "-std=c++17", "-Wall", "-pthread"], ["-O2", "-std=c++17", "-Wall"]
+    programs = [("host_test.cpp", HOST_TEST_PATH, test_flags),
+                ("host_overhead_test.cpp", HOST_OVERHEAD_TEST_PATH, test_flags),
+                ("host_cluster_scan_test.cpp", HOST_CLUSTER_SCAN_TEST_PATH, test_flags),
+                ("host_cluster_scan_sets_test.cpp", HOST_CLUSTER_SCAN_SETS_TEST_PATH, test_flags),
+                ("host_snapshot_labels_test.cpp", HOST_SNAPSHOT_LABELS_TEST_PATH, test_flags),
+                ("host_executor_resident_test.cpp", HOST_EXECUTOR_RESIDENT_TEST_PATH, test_flags),
+                ("host_group_filter_test.cpp", HOST_GROUP_FILTER_TEST_PATH, test_flags),
+                ("host_filter_efficiency_test.cpp", HOST_FILTER_EFFICIENCY_TEST_PATH, test_flags),
+                ("host_bench.cpp", HOST_BENCH_PATH, bench_flags)]
+    tests_dir = os.path.join(host_dir, "tests")
+    test_hdrs = glob.glob(os.path.join(tests_dir, "*.hpp"))  # what the test programs share
+    for name, out, flags in programs:
+        src = os.path.join(tests_dir, name)
+        if os.path.exists(src) and (force or _stale(out, [src, HOST_LIB_PATH] + hdrs + test_hdrs)):
+            subprocess.check_call(["g++", *flags, "-I", INCLUDE, "-I", host_dir, src, "-L", _PKG_ROOT, "-lgangfit_host", "-lgangfit",
+                                   "-Wl,-rpath,$ORIGIN", "-o", out])
     return HOST_LIB_PATH
 
 

@@ -6,6 +6,120 @@
 
 namespace gangfit::host {
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The steps the routes below share, each written once.
+namespace {
+
+SelectNodeResult notServed(std::string why) {  // the accelerator cannot take the request: the Go host runs its own path
+    SelectNodeResult r;
+    r.served = false;
+    r.error = std::move(why);
+    return r;
+}
+
+SelectNodeResult failure(const char* outcome, std::string error) {  // the reference's own failure
+    SelectNodeResult r;
+    r.outcome = outcome;
+    r.error = std::move(error);
+    return r;
+}
+
+// A quantity triple the device columns can hold: exactly representable and not negative.
+bool canonicalNonNegative(const Resources& r, int64_t v[3]) { return r.canonical(v) && v[0] >= 0 && v[1] >= 0 && v[2] >= 0; }
+
+// an application that already holds a reservation keeps its driver node (resource.go:278-291); nullopt: it holds none
+std::optional<SelectNodeResult> answerFromReservation(const std::vector<ResourceReservation>& reservations, const Pod& driver) {
+    auto app_label = driver.labels.find(common::SparkAppIDLabel);
+    const std::string app_id = app_label == driver.labels.end() ? "" : app_label->second;
+    for (const ResourceReservation& rr : reservations)
+        if (rr.Name == app_id && rr.Namespace == driver.Namespace) {
+            SelectNodeResult out;
+            auto d = rr.Reservations.find("driver");
+            out.node = d == rr.Reservations.end() ? "" : d->second.Node;
+            out.outcome = outcome::success;
+            return out;
+        }
+    return std::nullopt;
+}
+
+// SparkResources as a chain application; false: not exactly representable (*app is then unspecified).
+bool toApp(const SparkApplicationResources& r, gf_app* app) {
+    *app = gf_app{};
+    if (!r.DriverResources.canonical(app->drv) || !r.ExecutorResources.canonical(app->exe) || r.MinExecutorCount < 0 ||
+        r.MinExecutorCount > GF_MAX_K)
+        return false;
+    app->k = r.MinExecutorCount;
+    return true;
+}
+
+// {pod name, exceedsCapacity} of a feasibility batch, in listing order
+std::vector<std::pair<std::string, bool>> scanResult(const std::vector<const Pod*>& pods, const std::vector<uint8_t>& fits) {
+    std::vector<std::pair<std::string, bool>> out;
+    for (size_t i = 0; i < pods.size(); ++i) out.emplace_back(pods[i]->Name, fits[i] == 0);
+    return out;
+}
+
+// Dense overhead columns as the C ABI takes them: three NULLs stand for "no overhead anywhere" (empty columns).
+struct OverheadColumns {
+    const int64_t* col[3];
+};
+OverheadColumns nullableColumns(const std::vector<int64_t> over[3]) {
+    const bool with_over = !over[0].empty();
+    return {{with_over ? over[0].data() : nullptr, with_over ? over[1].data() : nullptr, with_over ? over[2].data() : nullptr}};
+}
+
+// `list` (Nodes, or pointers to them) as a bit row over `cluster`'s node index, ORed into row[ceil(n / 64)]; `keep` may narrow
+// the list.  false: the list names a node outside the cluster, and the walk ended there.
+const Node& nodeOf(const Node& n) { return n; }
+const Node& nodeOf(const Node* n) { return *n; }
+bool everyNode(const Node&) { return true; }
+template <class List, class Keep = bool (*)(const Node&)>
+bool nodeBitRow(const FlatCluster& cluster, const List& list, uint64_t* row, Keep keep = everyNode) {
+    for (const auto& item : list) {
+        const Node& node = nodeOf(item);
+        const auto at = cluster.index.find(node.Name);
+        if (at == cluster.index.end()) return false;
+        if (keep(node)) row[at->second >> 6] |= UINT64_C(1) << (at->second & 63u);
+    }
+    return true;
+}
+
+// A request's NodeNames as one number, order-sensitive across names.
+// (eight bytes per multiply: a byte-at-a-time hash of 100 000 names is a 1.5 ms dependent chain)
+uint64_t hashNodeNames(const std::vector<std::string>& nodeNames) {
+    uint64_t names_hash = 1469598103934665603ull;
+    for (const std::string& name : nodeNames) {
+        const char* p = name.data();
+        size_t left = name.size();
+        uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)left;
+        for (; left >= 8; left -= 8, p += 8) {
+            uint64_t w;
+            std::memcpy(&w, p, 8);
+            h = (h ^ w) * 0xFF51AFD7ED558CCDull;
+            h ^= h >> 29;
+        }
+        if (left) {
+            uint64_t w = 0;
+            std::memcpy(&w, p, left);
+            h = (h ^ w) * 0xC4CEB9FE1A85EC53ull;
+            h ^= h >> 31;
+        }
+        names_hash = (names_hash ^ h) * 1099511628211ull;  // order-sensitive across names; h of each name is independent work
+    }
+    return names_hash;
+}
+
+// The executor Filter's answer (resource.go:657-673): names = node index -> name of what the device was asked about.
+SelectNodeResult executorAnswer(uint32_t node, const std::vector<std::string>& names, bool isExtraExecutor) {
+    if (node == GF_NO_NODE) return failure(outcome::failureFit, "not enough capacity to reschedule the executor");
+    SelectNodeResult out;
+    out.node = names[node];
+    out.outcome = isExtraExecutor ? outcome::successScheduledExtraExecutor : outcome::successRescheduled;
+    return out;
+}
+
+}  // namespace
+
 std::string executorReservationName(int i) { return "executor-" + std::to_string(i + 1); }
 
 ResourceReservation newResourceReservation(const std::string& driverNode, const std::vector<std::string>& executorNodes,
@@ -45,20 +159,93 @@ static void fillEfficiency(gf_ctx* ctx, gf_algo algo, bool fifo, const gf_app& a
     out->has_efficiency = true;
 }
 
+// A pod's annotations as a chain application (sparkResources, then toApp).  The flat route's cache holds what this returns per
+// (pod, resourceVersion); the string route calls it afresh.
+SparkSchedulerExtender::PodApp SparkSchedulerExtender::podApp(const Pod& pod, std::string* err) {
+    PodApp pa;
+    auto r = sparkResources(pod, err);
+    pa.parsed = r.has_value();
+    pa.representable = pa.parsed && toApp(*r, &pa.app);
+    return pa;
+}
+
+// The stale pending drivers of this scheduler in listing order (unschedulablepods.go:93-129).  An unparsable pod ends the listing
+// there, as the reference returns from the scan ("failed to check if pod was unschedulable", unschedulablepods.go:112-116); a pod
+// that is not exactly representable is listed like any other (its app is unspecified) and the first such pod is reported.  What to
+// do about either is each scan's own decision.
+SparkSchedulerExtender::StaleDrivers SparkSchedulerExtender::listStaleDrivers(const std::vector<Pod>& allPods, int64_t timeoutNanos) const {
+    if (timeoutNanos <= 0) timeoutNanos = 600ll * 1000000000;  // 10 minutes (unschedulablepods.go:62-64)
+    StaleDrivers stale;
+    for (const Pod& pod : allPods) {
+        auto role = pod.labels.find(common::SparkRoleLabel);
+        if (pod.SchedulerName != common::SparkSchedulerName || !pod.NodeName.empty() || pod.Deleting ||
+            role == pod.labels.end() || role->second != common::Driver || pod.CreationTimestampNanos + timeoutNanos >= nowNanos)
+            continue;
+        const PodApp pa = podApp(pod, &stale.parse_error);
+        if (!pa.parsed) {
+            stale.stopped = true;
+            break;
+        }
+        if (!pa.representable && stale.unrepresentable == nullptr) stale.unrepresentable = &pod;
+        stale.pods.push_back(&pod);
+        stale.apps.push_back(pa.app);
+    }
+    return stale;
+}
+
+// fitEarlierDrivers' applications in creation order (resource.go:224-270), appended to *apps; app_of(pod) gives a pod's PodApp.
+// false: an earlier driver is not exactly representable (*why names it).
+template <class AppOf>
+bool SparkSchedulerExtender::earlierDriverApps(const std::string& instanceGroup, const Pod& driver, AppOf app_of, std::vector<gf_app>* apps,
+                                               std::string* why) const {
+    if (!isFIFO_) return true;
+    for (const Pod* p : filterToEarliestAndSort(driver, pods)) {
+        const PodApp& pa = app_of(*p);
+        if (!pa.parsed) continue;  // "failed to get driver resources, skipping driver" (resource.go:231-237)
+        if (!pa.representable) {
+            *why = "earlier driver " + p->Name + " is not exactly representable";
+            return false;
+        }
+        gf_app a = pa.app;
+        a.flags = shouldSkipDriverFifo(*p, instanceGroup) ? GF_APP_SKIPPABLE : 0u;  // (the skip flag depends on the clock)
+        apps->push_back(a);
+    }
+    return true;
+}
+
+// FIFO replay + final pack as one chain on the installed snapshot (resource.go:309-328), as the Filter's answer.  apps: the earlier
+// drivers, then the one being filtered; names: node index -> name of the snapshot; row: the keys of the efficiency (fillEfficiency).
+SelectNodeResult SparkSchedulerExtender::fitChain(gf_ctx* ctx, const std::vector<gf_app>& apps, const std::vector<std::string>& names,
+                                                  const uint64_t* row, const Pod& driver, const SparkApplicationResources& resources) const {
+    uint64_t total_k = 0;
+    for (const gf_app& a : apps) total_k += (uint64_t)a.k;
+    std::vector<gf_result> results(apps.size());
+    std::vector<uint32_t> exec(total_k + 1);
+    int32_t failed_at = -1;
+    if (gf_fit_batch(ctx, GF_MODE_FIFO_CHAIN, binpacker_.Algo, (uint32_t)apps.size(), apps.data(), results.data(), exec.data(), total_k,
+                     &failed_at) != GF_OK)
+        return notServed(std::string("gf_fit_batch: ") + gf_last_error(ctx));
+    if (failed_at >= 0)  // resource.go:315-318
+        return failure(outcome::failureEarlierDriver, "earlier drivers do not fit to the cluster");
+    const gf_app& cur = apps.back();
+    const gf_result& last = results.back();
+    if (!last.has_capacity)  // resource.go:346-349
+        return failure(outcome::failureFit, "application does not fit to the cluster");
+    SelectNodeResult out;
+    std::vector<std::string> executorNodes;
+    const uint64_t off = total_k - (uint64_t)cur.k;
+    for (uint32_t i = 0; i < last.exec_len; ++i) executorNodes.push_back(names[exec[off + i]]);
+    out.node = names[last.driver_node];
+    out.outcome = outcome::success;
+    fillEfficiency(ctx, binpacker_.Algo, isFIFO_, cur, last, exec.data() + off, row, &out);
+    out.created = newResourceReservation(out.node, executorNodes, driver, resources.DriverResources, resources.ExecutorResources);
+    return out;
+}
+
 SelectNodeResult SparkSchedulerExtender::selectDriverNode(const std::string& instanceGroup, const Pod& driver,
                                                           const std::vector<std::string>& nodeNames,
                                                           const std::vector<Node>& availableNodes) {
-    SelectNodeResult out;
-    auto app_label = driver.labels.find(common::SparkAppIDLabel);
-    const std::string app_id = app_label == driver.labels.end() ? "" : app_label->second;
-    // an application that already holds a reservation keeps its driver node (resource.go:278-291)
-    for (const ResourceReservation& rr : reservations)
-        if (rr.Name == app_id && rr.Namespace == driver.Namespace) {
-            auto d = rr.Reservations.find("driver");
-            out.node = d == rr.Reservations.end() ? "" : d->second.Node;
-            out.outcome = outcome::success;
-            return out;
-        }
+    if (auto held = answerFromReservation(reservations, driver)) return *held;
     // snapshot (resource.go:300-303)
     NodeGroupResources usage = UsageForNodes(reservations);
     for (const auto& [n, r] : softReservationUsage) usage[n].Add(r);
@@ -66,98 +253,30 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNode(const std::string& ins
     auto [driverNodeNames, executorNodeNames] = sorter_.PotentialNodes(metadata, nodeNames);
     std::string err;
     auto resources = sparkResources(driver, &err);
-    if (!resources) {
-        out.outcome = outcome::failureInternal;
-        out.error = "failed to get spark resources: " + err;
-        return out;
-    }
-    // FIFO replay + final pack as one chain (resource.go:309-328)
-    std::vector<gf_app> apps;
-    if (isFIFO_) {
-        for (const Pod* p : filterToEarliestAndSort(driver, pods)) {
-            auto r = sparkResources(*p, nullptr);
-            if (!r) continue;  // "failed to get driver resources, skipping driver" (resource.go:231-237)
-            gf_app a{};
-            if (!r->DriverResources.canonical(a.drv) || !r->ExecutorResources.canonical(a.exe) || r->MinExecutorCount < 0 ||
-                r->MinExecutorCount > GF_MAX_K) {
-                out.served = false;
-                out.error = "earlier driver " + p->Name + " is not exactly representable";
-                return out;
-            }
-            a.k = r->MinExecutorCount;
-            a.flags = shouldSkipDriverFifo(*p, instanceGroup) ? GF_APP_SKIPPABLE : 0u;
-            apps.push_back(a);
-        }
-    }
+    if (!resources) return failure(outcome::failureInternal, "failed to get spark resources: " + err);
+    // the applications: earlier drivers in creation order, then this one
     // (this route parses every pod afresh and never touches parsed_apps_: the cache and its prune belong to the flat route,
     //  under flat_mu_)
-    gf_app cur{};
-    if (!resources->DriverResources.canonical(cur.drv) || !resources->ExecutorResources.canonical(cur.exe) ||
-        resources->MinExecutorCount < 0 || resources->MinExecutorCount > GF_MAX_K) {
-        out.served = false;
-        out.error = "application resources are not exactly representable";
-        return out;
-    }
-    cur.k = resources->MinExecutorCount;
+    std::vector<gf_app> apps;
+    if (!earlierDriverApps(instanceGroup, driver, [](const Pod& p) { return podApp(p, nullptr); }, &apps, &err)) return notServed(err);
+    gf_app cur;
+    if (!toApp(*resources, &cur)) return notServed("application resources are not exactly representable");
     apps.push_back(cur);
     FlatSnapshot snap;
     CtxSequence seq(binpacker_.ctx);
-    if (!flatten(metadata, driverNodeNames, executorNodeNames, &snap, &err) || !upload(binpacker_.ctx, snap, &err)) {
-        out.served = false;
-        out.error = err;
-        return out;
-    }
-    uint64_t total_k = 0;
-    for (const gf_app& a : apps) total_k += (uint64_t)a.k;
-    std::vector<gf_result> results(apps.size());
-    std::vector<uint32_t> exec(total_k + 1);
-    int32_t failed_at = -1;
-    if (gf_fit_batch(binpacker_.ctx, GF_MODE_FIFO_CHAIN, binpacker_.Algo, (uint32_t)apps.size(), apps.data(), results.data(),
-                     exec.data(), total_k, &failed_at) != GF_OK) {
-        out.served = false;
-        out.error = std::string("gf_fit_batch: ") + gf_last_error(binpacker_.ctx);
-        return out;
-    }
-    if (failed_at >= 0) {  // resource.go:315-318
-        out.outcome = outcome::failureEarlierDriver;
-        out.error = "earlier drivers do not fit to the cluster";
-        return out;
-    }
-    const gf_result& last = results.back();
-    if (!last.has_capacity) {  // resource.go:346-349
-        out.outcome = outcome::failureFit;
-        out.error = "application does not fit to the cluster";
-        return out;
-    }
-    std::vector<std::string> executorNodes;
-    const uint64_t off = total_k - (uint64_t)cur.k;
-    for (uint32_t i = 0; i < last.exec_len; ++i) executorNodes.push_back(snap.names[exec[off + i]]);
-    out.node = snap.names[last.driver_node];
-    out.outcome = outcome::success;
-    fillEfficiency(binpacker_.ctx, binpacker_.Algo, isFIFO_, cur, last, exec.data() + off, nullptr, &out);
-    out.created = newResourceReservation(out.node, executorNodes, driver, resources->DriverResources,
-                                         resources->ExecutorResources);
-    return out;
+    if (!flatten(metadata, driverNodeNames, executorNodeNames, &snap, &err) || !upload(binpacker_.ctx, snap, &err)) return notServed(err);
+    return fitChain(binpacker_.ctx, apps, snap.names, nullptr, driver, *resources);
 }
 
 SelectNodeResult SparkSchedulerExtender::rescheduleExecutor(const Pod& driver, const std::vector<std::string>& nodeNames,
                                                             const std::vector<Node>& availableNodes,
                                                             const std::set<std::string>& nodesHostingApp,
                                                             bool isExtraExecutor) {
-    SelectNodeResult out;
     std::string err;
     auto resources = sparkResources(driver, &err);
-    if (!resources) {
-        out.outcome = outcome::failureInternal;
-        out.error = err;
-        return out;
-    }
+    if (!resources) return failure(outcome::failureInternal, err);
     int64_t exe[3];
-    if (!resources->ExecutorResources.canonical(exe) || exe[0] < 0 || exe[1] < 0 || exe[2] < 0) {
-        out.served = false;
-        out.error = "executor resources are not exactly representable";
-        return out;
-    }
+    if (!canonicalNonNegative(resources->ExecutorResources, exe)) return notServed("executor resources are not exactly representable");
     NodeGroupResources usage = UsageForNodes(reservations);  // GetReservedResources
     for (const auto& [n, r] : softReservationUsage) usage[n].Add(r);
     std::set<std::string> had_usage;
@@ -167,11 +286,7 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutor(const Pod& driver, c
     (void)driverOrder;
     FlatSnapshot snap;
     CtxSequence seq(binpacker_.ctx);
-    if (!flatten(metadata, {}, executorNodeNames, &snap, &err) || !upload(binpacker_.ctx, snap, &err)) {
-        out.served = false;
-        out.error = err;
-        return out;
-    }
+    if (!flatten(metadata, {}, executorNodeNames, &snap, &err) || !upload(binpacker_.ctx, snap, &err)) return notServed(err);
     const bool minfrag = binpacker_.Name == "single-az-minimal-fragmentation";
     // what this path subtracts on top of the snapshot: `usage.Add(overhead)` (:642) counts the overhead a second time
     // for nodes NodeSchedulingMetadataForNodes already updated in place; GetNodeCapacities (:682) is handed the
@@ -183,11 +298,7 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutor(const Pod& driver, c
         if (o == overhead.end()) continue;
         if (!minfrag && !had_usage.count(snap.names[i])) continue;
         int64_t v[3];
-        if (!o->second.canonical(v) || v[0] < 0 || v[1] < 0 || v[2] < 0) {
-            out.served = false;
-            out.error = "overhead of node " + snap.names[i] + " is not exactly representable";
-            return out;
-        }
+        if (!canonicalNonNegative(o->second, v)) return notServed("overhead of node " + snap.names[i] + " is not exactly representable");
         for (int j = 0; j < 3; ++j) reserved[3 * i + j] = v[j];
         any_reserved = true;
     }
@@ -196,19 +307,9 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutor(const Pod& driver, c
         if (auto it = snap.index.find(n); it != snap.index.end()) hosts[it->second >> 5] |= 1u << (it->second & 31);
     uint32_t node = GF_NO_NODE;
     if (gf_executor_fit(binpacker_.ctx, minfrag ? 1 : 0, 1, exe, any_reserved ? reserved.data() : nullptr,
-                        minfrag ? hosts.data() : nullptr, &node) != GF_OK) {
-        out.served = false;
-        out.error = std::string("gf_executor_fit: ") + gf_last_error(binpacker_.ctx);
-        return out;
-    }
-    if (node == GF_NO_NODE) {
-        out.outcome = outcome::failureFit;
-        out.error = "not enough capacity to reschedule the executor";
-        return out;
-    }
-    out.node = snap.names[node];
-    out.outcome = isExtraExecutor ? outcome::successScheduledExtraExecutor : outcome::successRescheduled;
-    return out;
+                        minfrag ? hosts.data() : nullptr, &node) != GF_OK)
+        return notServed(std::string("gf_executor_fit: ") + gf_last_error(binpacker_.ctx));
+    return executorAnswer(node, snap.names, isExtraExecutor);
 }
 
 bool filterNodesToZone(const std::vector<Node>& initialNodes, const std::string& zone, std::vector<Node>* out, std::string* err) {
@@ -267,14 +368,9 @@ std::pair<std::string, bool> SparkSchedulerExtender::getCommonZoneForExecutorsAp
 SelectNodeResult SparkSchedulerExtender::rescheduleExecutor(const Pod& executor, const Pod& driver, const std::vector<Pod>& allPods,
                                                             const std::vector<std::string>& nodeNames,
                                                             const std::set<std::string>& nodesHostingApp, bool isExtraExecutor) {
-    SelectNodeResult out;
     std::string err;
     // sparkResources(driver) comes first in the reference (:599-602): its failure is failure-internal whatever the zones say
-    if (!sparkResources(driver, &err)) {
-        out.outcome = outcome::failureInternal;
-        out.error = err;
-        return out;
-    }
+    if (!sparkResources(driver, &err)) return failure(outcome::failureInternal, err);
     std::vector<Node> availableNodes;  // getNodes (:448-460): lister order of nodeNames, unknown names skipped
     for (const std::string& name : nodeNames)
         for (const Node& n : nodes)
@@ -285,18 +381,10 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutor(const Pod& executor,
     std::vector<std::string> names = nodeNames;
     if (binpacker_.IsSingleAz && shouldScheduleDynamicallyAllocatedExecutorsInSameAZ) {  // :608
         auto [zone, allPodsInSameAz] = getCommonZoneForExecutorsApplication(executor, allPods, &err);
-        if (!err.empty()) {  // :611-613: ("", "", err)
-            out.outcome = "";
-            out.error = err;
-            return out;
-        }
-        if (allPodsInSameAz) {  // :614-627
+        if (!err.empty()) return failure("", err);  // :611-613: ("", "", err)
+        if (allPodsInSameAz) {                      // :614-627
             std::vector<Node> inZone;
-            if (!filterNodesToZone(availableNodes, zone, &inZone, &err)) {
-                out.outcome = outcome::failureInternal;
-                out.error = err;
-                return out;
-            }
+            if (!filterNodesToZone(availableNodes, zone, &inZone, &err)) return failure(outcome::failureInternal, err);
             availableNodes = std::move(inZone);
             names.clear();
             for (const Node& n : availableNodes) names.push_back(n.Name);
@@ -331,41 +419,26 @@ bool SparkSchedulerExtender::DoesPodExceedClusterCapacity(const Pod& driver, con
     return !r.HasCapacity;
 }
 
-}  // namespace gangfit::host
-
-namespace gangfit::host {
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The UnschedulablePodMarker's scans.  All three list the stale drivers the same way (listStaleDrivers); what each does with a pod
+// it cannot take is its own, stated where the listing returns:
+//                            unparsable pod                          pod not exactly representable
+//   scanForUnschedulablePods   *err, answers the pods before it        not served, *err names the pod
+//   ...Resident                the installing scan decides             the installing scan decides
+//   ...AllGroups               *err, answers the pods before it        the per-group route (installing scans) decides
 
 std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnschedulablePods(
     const std::vector<Pod>& allPods, int64_t timeoutNanos, const std::vector<Node>& availableNodes,
     const NodeGroupResources& nonSchedulableOverhead, bool* served, std::string* err) {
-    std::vector<std::pair<std::string, bool>> out;
     if (served) *served = true;
-    if (timeoutNanos <= 0) timeoutNanos = 600ll * 1000000000;  // 10 minutes (unschedulablepods.go:62-64)
-    std::vector<const Pod*> stale;
-    std::vector<gf_app> apps;
-    for (const Pod& pod : allPods) {
-        auto role = pod.labels.find(common::SparkRoleLabel);
-        if (pod.SchedulerName != common::SparkSchedulerName || !pod.NodeName.empty() || pod.Deleting ||
-            role == pod.labels.end() || role->second != common::Driver || pod.CreationTimestampNanos + timeoutNanos >= nowNanos)
-            continue;
-        std::string e;
-        auto r = sparkResources(pod, &e);
-        if (!r) {  // "failed to check if pod was unschedulable": the reference returns from the scan
-            if (err) *err = e;
-            break;
-        }
-        gf_app a{};
-        if (!r->DriverResources.canonical(a.drv) || !r->ExecutorResources.canonical(a.exe) || r->MinExecutorCount < 0 ||
-            r->MinExecutorCount > GF_MAX_K) {
-            if (served) *served = false;
-            if (err) *err = "pod " + pod.Name + " is not exactly representable";
-            return {};
-        }
-        a.k = r->MinExecutorCount;
-        stale.push_back(&pod);
-        apps.push_back(a);
+    const StaleDrivers stale = listStaleDrivers(allPods, timeoutNanos);
+    if (stale.unrepresentable != nullptr) {
+        if (served) *served = false;
+        if (err) *err = "pod " + stale.unrepresentable->Name + " is not exactly representable";
+        return {};
     }
-    if (apps.empty()) return out;
+    if (stale.stopped && err) *err = stale.parse_error;
+    if (stale.apps.empty()) return {};
     NodeGroupResources usage;  // zeroUsage: the cluster as if nothing ran on it
     NodeGroupSchedulingMetadata metadata = NodeSchedulingMetadataForNodes(availableNodes, usage, nonSchedulableOverhead);
     std::vector<std::string> names;
@@ -379,14 +452,36 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
         return {};
     }
     // DoesPodExceedClusterCapacity reads HasCapacity and nothing else (unschedulablepods.go:165): the feasibility-only batch
-    std::vector<uint8_t> fits(apps.size());
-    if (gf_fit_feasible(binpacker_.ctx, binpacker_.Algo, (uint32_t)apps.size(), apps.data(), fits.data()) != GF_OK) {
+    std::vector<uint8_t> fits(stale.apps.size());
+    if (gf_fit_feasible(binpacker_.ctx, binpacker_.Algo, (uint32_t)stale.apps.size(), stale.apps.data(), fits.data()) != GF_OK) {
         if (served) *served = false;
         if (err) *err = std::string("gf_fit_feasible: ") + gf_last_error(binpacker_.ctx);
         return {};
     }
-    for (size_t i = 0; i < stale.size(); ++i) out.emplace_back(stale[i]->Name, fits[i] == 0);
-    return out;
+    return scanResult(stale.pods, fits);
+}
+
+// One question to the resident cluster next to the Filter's installed snapshot: under flat_mu_ (the record of what sits on the
+// device) and then the context's sequence lock, `ask(ctx)` — the call of the entry point named `entry` — runs if the columns on the
+// device are this cluster's.  fall_back: not resident, or the entry point refused (GF_ERR_UNSUPPORTED); the caller answers by an
+// installing route once this has returned, outside both locks, since that route takes them itself.  failed: the device call went
+// wrong, the scan is not served (*served) and *err says why.
+template <class Ask>
+SparkSchedulerExtender::Asked SparkSchedulerExtender::askResident(const FlatCluster& cluster, const char* entry, Ask ask, bool* served,
+                                                                  std::string* err) {
+    std::lock_guard<std::mutex> flat_lock(*flat_mu_);  // before the sequence lock
+    gf_ctx* ctx = binpacker_.ctx;
+    CtxSequence seq(ctx);
+    uint64_t gen[3] = {0, 0, 0};
+    (void)gf_generation(ctx, gen);
+    // the columns on the device must be this cluster's: put there by this extender's Filter and not replaced since
+    const bool resident = cluster.version != 0 && resident_cluster_ == cluster.version && gen[1] == seen_cluster_gen_;
+    const int rc = resident ? ask(ctx) : GF_ERR_UNSUPPORTED;
+    if (rc == GF_OK) return Asked::answered;
+    if (rc == GF_ERR_UNSUPPORTED) return Asked::fall_back;
+    if (served) *served = false;
+    if (err) *err = std::string(entry) + ": " + gf_last_error(ctx);
+    return Asked::failed;
 }
 
 std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnschedulablePodsResident(
@@ -394,9 +489,8 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
     const NodeGroupResources& nonSchedulableOverhead, bool* served, std::string* err, bool* residentRoute) {
     if (residentRoute) *residentRoute = false;
     auto installs = [&] { return scanForUnschedulablePods(allPods, timeoutNanos, availableNodes, nonSchedulableOverhead, served, err); };
-    const uint32_t n = (uint32_t)cluster.names.size();
     // the selection: the nodes the drivers' affinity matches, by the cluster's node index
-    std::vector<uint8_t> select(n, 0);
+    std::vector<uint8_t> select(cluster.names.size(), 0);
     for (const Node& nd : availableNodes) {
         auto it = cluster.index.find(nd.Name);
         if (it == cluster.index.end()) return installs();
@@ -404,52 +498,23 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
     }
     FlatOverhead over;
     if (!FlatOverhead::Build(nonSchedulableOverhead, cluster, &over, nullptr)) return installs();
-    // the stale pending drivers, as in scanForUnschedulablePods
-    if (timeoutNanos <= 0) timeoutNanos = 600ll * 1000000000;
-    std::vector<const Pod*> stale;
-    std::vector<gf_app> apps;
-    for (const Pod& pod : allPods) {
-        auto role = pod.labels.find(common::SparkRoleLabel);
-        if (pod.SchedulerName != common::SparkSchedulerName || !pod.NodeName.empty() || pod.Deleting ||
-            role == pod.labels.end() || role->second != common::Driver || pod.CreationTimestampNanos + timeoutNanos >= nowNanos)
-            continue;
-        auto r = sparkResources(pod, nullptr);
-        gf_app a{};
-        if (!r || !r->DriverResources.canonical(a.drv) || !r->ExecutorResources.canonical(a.exe) || r->MinExecutorCount < 0 ||
-            r->MinExecutorCount > GF_MAX_K)
-            return installs();  // (an unparsable or unrepresentable pod: the other route says what the reference says)
-        a.k = r->MinExecutorCount;
-        stale.push_back(&pod);
-        apps.push_back(a);
-    }
+    const StaleDrivers stale = listStaleDrivers(allPods, timeoutNanos);
+    if (stale.stopped || stale.unrepresentable != nullptr) return installs();  // (the other route says what the reference says)
     if (served) *served = true;
-    std::vector<std::pair<std::string, bool>> out;
-    if (apps.empty()) return out;
-    std::vector<uint8_t> fits(apps.size());
-    int rc = GF_ERR_UNSUPPORTED;
-    {
-        std::lock_guard<std::mutex> flat_lock(*flat_mu_);  // the record of what sits on the device; before the sequence lock
-        gf_ctx* ctx = binpacker_.ctx;
-        CtxSequence seq(ctx);
-        uint64_t gen[3] = {0, 0, 0};
-        (void)gf_generation(ctx, gen);
-        // the columns on the device must be this cluster's: put there by this extender's Filter and not replaced since
-        const bool resident = cluster.version != 0 && resident_cluster_ == cluster.version && gen[1] == seen_cluster_gen_;
-        const bool with_over = !over.over[0].empty();
-        if (resident)
-            rc = gf_cluster_fit_feasible(ctx, binpacker_.Algo, with_over ? over.over[0].data() : nullptr,
-                                         with_over ? over.over[1].data() : nullptr, with_over ? over.over[2].data() : nullptr,
-                                         select.data(), (uint32_t)apps.size(), apps.data(), fits.data());
-        if (rc != GF_OK && rc != GF_ERR_UNSUPPORTED) {
-            if (served) *served = false;
-            if (err) *err = std::string("gf_cluster_fit_feasible: ") + gf_last_error(ctx);
-            return {};
-        }
-    }
-    if (rc == GF_ERR_UNSUPPORTED) return installs();  // refused, or not resident (outside the locks: that route takes them itself)
+    if (stale.apps.empty()) return {};
+    std::vector<uint8_t> fits(stale.apps.size());
+    const OverheadColumns oc = nullableColumns(over.over);
+    const Asked asked = askResident(
+        cluster, "gf_cluster_fit_feasible",
+        [&](gf_ctx* ctx) {
+            return gf_cluster_fit_feasible(ctx, binpacker_.Algo, oc.col[0], oc.col[1], oc.col[2], select.data(), (uint32_t)stale.apps.size(),
+                                           stale.apps.data(), fits.data());
+        },
+        served, err);
+    if (asked == Asked::fall_back) return installs();
+    if (asked == Asked::failed) return {};
     if (residentRoute) *residentRoute = true;
-    for (size_t i = 0; i < stale.size(); ++i) out.emplace_back(stale[i]->Name, fits[i] == 0);
-    return out;
+    return scanResult(stale.pods, fits);
 }
 
 std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnschedulablePodsAllGroups(
@@ -458,33 +523,10 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
     bool* served, std::string* err, bool* residentRoute) {
     if (residentRoute) *residentRoute = false;
     if (served) *served = true;
-    if (timeoutNanos <= 0) timeoutNanos = 600ll * 1000000000;
-    // the stale pending drivers, as in scanForUnschedulablePodsResident; an unparsable one ends the listing there
-    // ("failed to check if pod was unschedulable": the reference returns from the scan, unschedulablepods.go:112-116)
-    std::vector<const Pod*> stale;
-    std::vector<gf_app> apps;
-    bool representable = true;
-    for (const Pod& pod : allPods) {
-        auto role = pod.labels.find(common::SparkRoleLabel);
-        if (pod.SchedulerName != common::SparkSchedulerName || !pod.NodeName.empty() || pod.Deleting ||
-            role == pod.labels.end() || role->second != common::Driver || pod.CreationTimestampNanos + timeoutNanos >= nowNanos)
-            continue;
-        std::string e;
-        auto r = sparkResources(pod, &e);
-        if (!r) {
-            if (err) *err = e;
-            break;
-        }
-        gf_app a{};
-        if (!r->DriverResources.canonical(a.drv) || !r->ExecutorResources.canonical(a.exe) || r->MinExecutorCount < 0 ||
-            r->MinExecutorCount > GF_MAX_K)
-            representable = false;  // (the other route says so)
-        a.k = r->MinExecutorCount;
-        stale.push_back(&pod);
-        apps.push_back(a);
-    }
-    std::vector<std::pair<std::string, bool>> out;
-    if (stale.empty()) return out;
+    const StaleDrivers listing = listStaleDrivers(allPods, timeoutNanos);
+    if (listing.stopped && err) *err = listing.parse_error;
+    const std::vector<const Pod*>& stale = listing.pods;
+    if (stale.empty()) return {};
     static const std::vector<Node> kNoNodes;
     auto nodes_of = [&](const std::string& group) -> const std::vector<Node>& {
         auto it = nodesByInstanceGroup.find(group);
@@ -519,10 +561,9 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
         }
         return merged;
     };
-    if (!representable) return per_group();
+    if (listing.unrepresentable != nullptr) return per_group();  // (the other route says so)
     // the sets: one row of ceil(n / 64) words per instance group a stale driver asks, by the cluster's node index
-    const uint32_t n = (uint32_t)cluster.names.size();
-    const size_t W = ((size_t)n + 63) / 64;
+    const size_t W = (cluster.names.size() + 63) / 64;
     std::map<std::string, uint32_t> row_of;
     std::vector<uint64_t> words;
     std::vector<uint32_t> app_set(stale.size());
@@ -531,46 +572,27 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
         app_set[i] = it->second;
         if (!fresh) continue;
         words.resize(words.size() + W, 0);
-        uint64_t* row = words.data() + (size_t)it->second * W;
-        for (const Node& nd : nodes_of(stale[i]->InstanceGroup)) {
-            auto at = cluster.index.find(nd.Name);
-            if (at == cluster.index.end()) return per_group();
-            row[at->second >> 6] |= UINT64_C(1) << (at->second & 63u);
-        }
+        if (!nodeBitRow(cluster, nodes_of(stale[i]->InstanceGroup), words.data() + (size_t)it->second * W)) return per_group();
     }
     FlatOverhead over;
     if (!FlatOverhead::Build(nonSchedulableOverhead, cluster, &over, nullptr)) return per_group();
-    std::vector<uint8_t> fits(apps.size());
-    int rc = GF_ERR_UNSUPPORTED;
-    {
-        std::lock_guard<std::mutex> flat_lock(*flat_mu_);  // the record of what sits on the device; before the sequence lock
-        gf_ctx* ctx = binpacker_.ctx;
-        CtxSequence seq(ctx);
-        uint64_t gen[3] = {0, 0, 0};
-        (void)gf_generation(ctx, gen);
-        // the columns on the device must be this cluster's: put there by this extender's Filter and not replaced since
-        const bool resident = cluster.version != 0 && resident_cluster_ == cluster.version && gen[1] == seen_cluster_gen_;
-        const bool with_over = !over.over[0].empty();
-        if (resident)
-            rc = gf_cluster_fit_feasible_sets(ctx, binpacker_.Algo, with_over ? over.over[0].data() : nullptr,
-                                              with_over ? over.over[1].data() : nullptr, with_over ? over.over[2].data() : nullptr,
-                                              (uint32_t)row_of.size(), words.data(), app_set.data(), (uint32_t)apps.size(), apps.data(),
-                                              fits.data());
-        if (rc != GF_OK && rc != GF_ERR_UNSUPPORTED) {
-            if (served) *served = false;
-            if (err) *err = std::string("gf_cluster_fit_feasible_sets: ") + gf_last_error(ctx);
-            return {};
-        }
-    }
-    if (rc == GF_ERR_UNSUPPORTED) return per_group();  // refused, or not resident (outside the locks: that route takes them itself)
+    std::vector<uint8_t> fits(listing.apps.size());
+    const OverheadColumns oc = nullableColumns(over.over);
+    const Asked asked = askResident(
+        cluster, "gf_cluster_fit_feasible_sets",
+        [&](gf_ctx* ctx) {
+            return gf_cluster_fit_feasible_sets(ctx, binpacker_.Algo, oc.col[0], oc.col[1], oc.col[2], (uint32_t)row_of.size(), words.data(),
+                                                app_set.data(), (uint32_t)listing.apps.size(), listing.apps.data(), fits.data());
+        },
+        served, err);
+    if (asked == Asked::fall_back) return per_group();
+    if (asked == Asked::failed) return {};
     if (residentRoute) *residentRoute = true;
-    for (size_t i = 0; i < stale.size(); ++i) out.emplace_back(stale[i]->Name, fits[i] == 0);
-    return out;
+    return scanResult(stale, fits);
 }
 
-}  // namespace gangfit::host
-
-namespace gangfit::host {
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The flat form of the cluster state, and the routes that keep it on the device.
 
 bool FlatCluster::Build(const std::vector<Node>& nodes, FlatCluster* out, std::string* err) {
     static std::atomic<uint64_t> next_version{1};
@@ -596,7 +618,7 @@ bool FlatCluster::Build(const std::vector<Node>& nodes, FlatCluster* out, std::s
         if (auto it = nd.Allocatable.find(kResourceMemory); it != nd.Allocatable.end()) a.Memory = it->second;
         if (auto it = nd.Allocatable.find(kResourceNvidiaGPU); it != nd.Allocatable.end()) a.NvidiaGPU = it->second;
         int64_t v[3];
-        if (!a.canonical(v) || v[0] < 0 || v[1] < 0 || v[2] < 0) {
+        if (!canonicalNonNegative(a, v)) {
             if (err) *err = "allocatable of node " + nd.Name + " is not exactly representable";
             return false;
         }
@@ -628,7 +650,7 @@ bool FlatReservations::Build(const std::vector<ResourceReservation>& reservation
         auto it = cluster.index.find(node);
         if (it == cluster.index.end()) return true;  // usage of a node outside this instance group is never read
         int64_t v[3];
-        if (!r.canonical(v) || v[0] < 0 || v[1] < 0 || v[2] < 0) return false;
+        if (!canonicalNonNegative(r, v)) return false;
         f.node.push_back(it->second);
         for (int j = 0; j < 3; ++j) f.req[j].push_back(v[j]);
         return true;
@@ -662,7 +684,7 @@ bool FlatOverhead::Build(const NodeGroupResources& overhead, const FlatCluster& 
         auto it = cluster.index.find(node);
         if (it == cluster.index.end()) continue;
         int64_t v[3];
-        if (!r.canonical(v) || v[0] < 0 || v[1] < 0 || v[2] < 0) {
+        if (!canonicalNonNegative(r, v)) {
             if (err) *err = "overhead of " + node + " is not exactly representable";
             return false;
         }
@@ -699,6 +721,7 @@ SparkSchedulerExtender::ResidentSync SparkSchedulerExtender::syncResident(gf_ctx
     const std::vector<int64_t>* const over = fo.over;
     bool resident_route = true;
     const bool with_over = !over[0].empty();
+    const OverheadColumns oc = nullableColumns(over);
     const bool known_over = fo.version != 0 && fo.version == resident_over_version_;  // compared before
     (void)gf_generation(ctx, gen);
     const bool own_cluster = resident_cluster_ == cluster.version && cluster.version != 0;
@@ -710,10 +733,9 @@ SparkSchedulerExtender::ResidentSync SparkSchedulerExtender::syncResident(gf_ctx
     }
     if (set_cluster) {
         ++cluster_set_calls_;
-        if (gf_cluster_set(ctx, n, cluster.alloc[0].data(), cluster.alloc[1].data(), cluster.alloc[2].data(),
-                           with_over ? over[0].data() : nullptr, with_over ? over[1].data() : nullptr,
-                           with_over ? over[2].data() : nullptr, cluster.base_flags.data(), cluster.zone.data(),
-                           (uint32_t)cluster.zone_labels.size(), cluster.name_rank.data()) != GF_OK) {
+        if (gf_cluster_set(ctx, n, cluster.alloc[0].data(), cluster.alloc[1].data(), cluster.alloc[2].data(), oc.col[0], oc.col[1], oc.col[2],
+                           cluster.base_flags.data(), cluster.zone.data(), (uint32_t)cluster.zone_labels.size(),
+                           cluster.name_rank.data()) != GF_OK) {
             resident_cluster_ = 0;
             *err = std::string("gf_cluster_set: ") + gf_last_error(ctx);
             return ResidentSync::failed;
@@ -774,22 +796,36 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlat(const std::string&
     return selectDriverNodeFlatOver(instanceGroup, driver, nodeNames, cluster, nullptr, flat, flatOverhead);
 }
 
+// The usage entries and overhead columns a flat request reads: the caller's (kept_usage / kept_over, versions and all) or, for a
+// NULL one, this request's own, flattened here from `reservations` + `softReservationUsage` / `overhead`.  false: *why — a quantity
+// is not exactly representable, or the kept overhead columns are not of this cluster's length.
+bool SparkSchedulerExtender::requestColumns(const FlatCluster& cluster, const FlatReservations* kept_usage, const FlatOverhead* kept_over,
+                                            RequestColumns* cols, std::string* why) const {
+    const size_t n = cluster.names.size();
+    cols->usage = kept_usage;
+    if (kept_usage == nullptr) {
+        if (!FlatReservations::Build(reservations, softReservationUsage, cluster, &cols->own_usage, why)) return false;
+        cols->usage = &cols->own_usage;
+    }
+    cols->over = kept_over;
+    if (kept_over == nullptr) {
+        if (!FlatOverhead::Build(overhead, cluster, &cols->own_over, why)) return false;
+        cols->own_over.version = 0;  // this request's own: compared with the resident columns on every Filter
+        cols->over = &cols->own_over;
+    } else if (!kept_over->over[0].empty() && (kept_over->over[0].size() != n || kept_over->over[1].size() != n || kept_over->over[2].size() != n)) {
+        *why = "the flat overhead columns do not belong to this cluster";
+        return false;
+    }
+    return true;
+}
+
 SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatGroup(const std::string& instanceGroup, const Pod& driver,
                                                                    const std::vector<std::string>& nodeNames,
                                                                    const FlatCluster& cluster, const std::vector<Node>& groupNodes,
                                                                    const FlatReservations* flat, const FlatOverhead* flatOverhead) {
     // availableNodes as one bit row of the resident cluster (include/gangfit.h, gf_snapshot_build_resident_set)
     std::vector<uint64_t> members((cluster.names.size() + 63) / 64, 0);
-    bool listed = true;
-    for (const Node& node : groupNodes) {
-        const auto it = cluster.index.find(node.Name);
-        if (it == cluster.index.end()) {
-            listed = false;  // a node the lister knows and `cluster` does not
-            break;
-        }
-        members[it->second >> 6] |= 1ull << (it->second & 63u);
-    }
-    if (listed) {
+    if (nodeBitRow(cluster, groupNodes, members.data())) {  // (false: a node the lister knows and `cluster` does not)
         SelectNodeResult out = selectDriverNodeFlatOver(instanceGroup, driver, nodeNames, cluster, &members, flat, flatOverhead);
         if (out.served) return out;
     }
@@ -801,69 +837,27 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatOver(const std::str
                                                                   const std::vector<std::string>& nodeNames,
                                                                   const FlatCluster& cluster, const std::vector<uint64_t>* members,
                                                                   const FlatReservations* flat, const FlatOverhead* flatOverhead) {
-    SelectNodeResult out;
-    auto not_served = [&](const std::string& why) {
-        out.served = false;
-        out.error = why;
-        return out;
-    };
-    auto app_label = driver.labels.find(common::SparkAppIDLabel);
-    const std::string app_id = app_label == driver.labels.end() ? "" : app_label->second;
-    for (const ResourceReservation& rr : reservations)
-        if (rr.Name == app_id && rr.Namespace == driver.Namespace) {
-            auto d = rr.Reservations.find("driver");
-            out.node = d == rr.Reservations.end() ? "" : d->second.Node;
-            out.outcome = outcome::success;
-            return out;
-        }
+    if (auto held = answerFromReservation(reservations, driver)) return *held;
     const uint32_t n = (uint32_t)cluster.names.size();
     // ---- the per-request columns: one entry per reservation (UsageForNodes' input), overhead, request flags
-    FlatReservations local;
-    if (flat == nullptr) {
-        std::string ferr;
-        if (!FlatReservations::Build(reservations, softReservationUsage, cluster, &local, &ferr)) return not_served(ferr);
-        flat = &local;
-    }
+    // (a caller that hands over no entry list gets this request's own, which travels whole with every Filter)
+    std::string err;
+    RequestColumns cols;
+    if (!requestColumns(cluster, flat, flatOverhead, &cols, &err)) return notServed(err);
+    const bool keep_usage = flat != nullptr && flat->version != 0;
+    flat = cols.usage;
+    flatOverhead = cols.over;
     const std::vector<uint32_t>& rnode = flat->node;
     const std::vector<int64_t>* rreq = flat->req;
-    FlatOverhead local_over;
-    if (flatOverhead == nullptr) {
-        std::string oerr;
-        if (!FlatOverhead::Build(overhead, cluster, &local_over, &oerr)) return not_served(oerr);
-        local_over.version = 0;  // this request's own: compared with the resident columns on every Filter
-        flatOverhead = &local_over;
-    } else if (!flatOverhead->over[0].empty() &&
-               (flatOverhead->over[0].size() != n || flatOverhead->over[1].size() != n || flatOverhead->over[2].size() != n)) {
-        return not_served("the flat overhead columns do not belong to this cluster");
-    }
     const std::vector<int64_t>* const over = flatOverhead->over;
     // ---- from here on this Filter reads and writes the extender's caches and its record of what sits on the device
     std::lock_guard<std::mutex> flat_lock(*flat_mu_);
     ++flat_calls_;
     // the request's NodeNames as candidate flags: the same list for every Filter of an instance group until the node set
     // changes, so the 10 000 map lookups are done once per (cluster version, list)
-    // (eight bytes per multiply: a byte-at-a-time hash of 100 000 names is a 1.5 ms dependent chain)
-    uint64_t names_hash = 1469598103934665603ull;
-    for (const std::string& name : nodeNames) {
-        const char* p = name.data();
-        size_t left = name.size();
-        uint64_t h = 0x9E3779B97F4A7C15ull ^ (uint64_t)left;
-        for (; left >= 8; left -= 8, p += 8) {
-            uint64_t w;
-            std::memcpy(&w, p, 8);
-            h = (h ^ w) * 0xFF51AFD7ED558CCDull;
-            h ^= h >> 29;
-        }
-        if (left) {
-            uint64_t w = 0;
-            std::memcpy(&w, p, left);
-            h = (h ^ w) * 0xC4CEB9FE1A85EC53ull;
-            h ^= h >> 31;
-        }
-        names_hash = (names_hash ^ h) * 1099511628211ull;  // order-sensitive across names; h of each name is independent work
-    }
     // (a hash hit is confirmed on the list itself: comparing 10 000 short strings costs a fraction of the 10 000 map lookups
     //  it saves, and a collision would silently change the node the Filter returns)
+    const uint64_t names_hash = hashNodeNames(nodeNames);
     if (cluster.version == 0 || flags_cluster_ != cluster.version || flags_hash_ != names_hash || flags_names_ != nodeNames) {
         flags_cache_ = cluster.base_flags;
         for (const std::string& name : nodeNames)
@@ -874,48 +868,27 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatOver(const std::str
     }
     const std::vector<uint32_t>& flags = flags_cache_;
     // ---- the applications: earlier drivers in creation order, then this one
-    std::string err;
     auto resources = sparkResources(driver, &err);
-    if (!resources) {
-        out.outcome = outcome::failureInternal;
-        out.error = "failed to get spark resources: " + err;
-        return out;
-    }
-    std::vector<gf_app> apps;
-    if (isFIFO_)
-        for (const Pod* p : filterToEarliestAndSort(driver, pods)) {
-            // annotations -> canonical requests, once per (pod, resourceVersion); the skip flag depends on the clock
-            ParsedApp fresh;
-            ParsedApp* pa = &fresh;
-            bool cached = false;
-            if (p->ResourceVersion != 0) {
-                pa = &parsed_apps_[p->UID.empty() ? p->Namespace + "/" + p->Name : p->UID];
-                cached = pa->version == p->ResourceVersion;
-            }
-            pa->seen = flat_calls_;
-            if (!cached) {
-                pa->version = p->ResourceVersion;
-                pa->app = gf_app{};
-                auto r = sparkResources(*p, nullptr);
-                pa->ok = r.has_value();
-                pa->representable = pa->ok && r->DriverResources.canonical(pa->app.drv) && r->ExecutorResources.canonical(pa->app.exe) &&
-                                    r->MinExecutorCount >= 0 && r->MinExecutorCount <= GF_MAX_K;
-                if (pa->representable) pa->app.k = r->MinExecutorCount;
-            }
-            if (!pa->ok) continue;
-            if (!pa->representable) return not_served("earlier driver " + p->Name + " is not exactly representable");
-            gf_app a = pa->app;
-            a.flags = shouldSkipDriverFifo(*p, instanceGroup) ? GF_APP_SKIPPABLE : 0u;
-            apps.push_back(a);
+    if (!resources) return failure(outcome::failureInternal, "failed to get spark resources: " + err);
+    // annotations -> canonical requests, once per (pod, resourceVersion)
+    PodApp uncached;
+    auto cached_app = [&](const Pod& p) -> const PodApp& {
+        if (p.ResourceVersion == 0) return uncached = podApp(p, nullptr);
+        ParsedApp& pa = parsed_apps_[p.UID.empty() ? p.Namespace + "/" + p.Name : p.UID];
+        pa.seen = flat_calls_;
+        if (pa.version != p.ResourceVersion) {
+            pa.version = p.ResourceVersion;
+            pa.parsed = podApp(p, nullptr);
         }
+        return pa.parsed;
+    };
+    std::vector<gf_app> apps;
+    if (!earlierDriverApps(instanceGroup, driver, cached_app, &apps, &err)) return notServed(err);
     // pods come and go: entries no request has used lately are dropped once the map outgrows the pods it is asked about
     if (parsed_apps_.size() > 2 * pods.size() + 64)
         for (auto it = parsed_apps_.begin(); it != parsed_apps_.end();) it = it->second.seen == flat_calls_ ? std::next(it) : parsed_apps_.erase(it);
-    gf_app cur{};
-    if (!resources->DriverResources.canonical(cur.drv) || !resources->ExecutorResources.canonical(cur.exe) ||
-        resources->MinExecutorCount < 0 || resources->MinExecutorCount > GF_MAX_K)
-        return not_served("application resources are not exactly representable");
-    cur.k = resources->MinExecutorCount;
+    gf_app cur;
+    if (!toApp(*resources, &cur)) return notServed("application resources are not exactly representable");
     apps.push_back(cur);
     // ---- snapshot + orders on the device, then the chain
     gf_ctx* ctx = binpacker_.ctx;
@@ -926,49 +899,45 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatOver(const std::str
     // may have replaced the resident cluster or usage in between: the context's generations say so.
     // (syncResident, above: the cluster columns, the overhead rows that differ and — for a caller that keeps its flattened
     //  reservations — the usage sums, each sent only when it changed)
-    const bool keep_usage = flat != &local && flat->version != 0;
     uint64_t gen[3] = {0, 0, 0};
-    std::string sync_err;
-    const ResidentSync synced = syncResident(ctx, cluster, *flatOverhead, keep_usage ? flat : nullptr, gen, &sync_err);
-    if (synced == ResidentSync::failed) return not_served(sync_err);
-    bool resident_route = synced == ResidentSync::ok;
-    {
-        // nothing changed since this extender's last Filter (no overhead row differed either: a change above cleared built_epoch_):
-        // the installed snapshot IS this request's snapshot
-        const bool same_snapshot = keep_usage && built_epoch_ != 0 && gen[0] == built_epoch_ && built_cluster_ == cluster.version &&
-                                   built_usage_ == flat->version && built_flags_ == flags &&
-                                   (members != nullptr ? built_set_ && built_members_ == *members : !built_set_);
-        if (resident_route && !same_snapshot) {
-            built_epoch_ = 0;
-            // (a NULL row is gf_snapshot_build_resident itself; another group's row rebuilds from the same resident columns and
-            //  usage sums: no gf_cluster_set, no usage replay)
-            const uint64_t* const row = members != nullptr ? members->data() : nullptr;
-            const int brc = keep_usage
-                                ? gf_snapshot_build_resident_set(ctx, row, GF_RESIDENT_USAGE, nullptr, nullptr, nullptr, nullptr,
-                                                                 flags.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
-                                : gf_snapshot_build_resident_set(ctx, row, (uint32_t)rnode.size(), rnode.data(), rreq[0].data(),
-                                                                 rreq[1].data(), rreq[2].data(), flags.data(), nullptr, nullptr,
-                                                                 nullptr, nullptr, nullptr, nullptr);
-            if (brc != GF_OK) {
-                resident_cluster_ = 0;
-                resident_usage_ = 0;
-                return not_served(std::string("gf_snapshot_build_resident_set: ") + gf_last_error(ctx));
-            }
-            if (keep_usage && gf_generation(ctx, gen) == GF_OK) {
-                built_epoch_ = gen[0];
-                built_cluster_ = cluster.version;
-                built_usage_ = flat->version;
-                built_flags_ = flags;
-                built_set_ = members != nullptr;
-                if (built_set_)
-                    built_members_ = *members;
-                else
-                    built_members_.clear();
-            }
+    const ResidentSync synced = syncResident(ctx, cluster, *flatOverhead, keep_usage ? flat : nullptr, gen, &err);
+    if (synced == ResidentSync::failed) return notServed(err);
+    const bool resident_route = synced == ResidentSync::ok;
+    // (a NULL row is gf_snapshot_build_resident itself; another group's row rebuilds from the same resident columns and
+    //  usage sums: no gf_cluster_set, no usage replay)
+    const uint64_t* const row = members != nullptr ? members->data() : nullptr;
+    // nothing changed since this extender's last Filter (no overhead row differed either: a change above cleared built_epoch_):
+    // the installed snapshot IS this request's snapshot
+    const bool same_snapshot = keep_usage && built_epoch_ != 0 && gen[0] == built_epoch_ && built_cluster_ == cluster.version &&
+                               built_usage_ == flat->version && built_flags_ == flags &&
+                               (members != nullptr ? built_set_ && built_members_ == *members : !built_set_);
+    if (resident_route && !same_snapshot) {
+        built_epoch_ = 0;
+        const int brc = keep_usage
+                            ? gf_snapshot_build_resident_set(ctx, row, GF_RESIDENT_USAGE, nullptr, nullptr, nullptr, nullptr,
+                                                             flags.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)
+                            : gf_snapshot_build_resident_set(ctx, row, (uint32_t)rnode.size(), rnode.data(), rreq[0].data(),
+                                                             rreq[1].data(), rreq[2].data(), flags.data(), nullptr, nullptr,
+                                                             nullptr, nullptr, nullptr, nullptr);
+        if (brc != GF_OK) {
+            resident_cluster_ = 0;
+            resident_usage_ = 0;
+            return notServed(std::string("gf_snapshot_build_resident_set: ") + gf_last_error(ctx));
+        }
+        if (keep_usage && gf_generation(ctx, gen) == GF_OK) {
+            built_epoch_ = gen[0];
+            built_cluster_ = cluster.version;
+            built_usage_ = flat->version;
+            built_flags_ = flags;
+            built_set_ = members != nullptr;
+            if (built_set_)
+                built_members_ = *members;
+            else
+                built_members_.clear();
         }
     }
     if (!resident_route && members != nullptr)  // the full build below installs every node of `cluster`: not this group's snapshot
-        return not_served("the resident route could not take this request");
+        return notServed("the resident route could not take this request");
     if (!resident_route) {  // what the resident route could not take: everything travels, nothing stays
         resident_cluster_ = 0;
         built_epoch_ = 0;
@@ -976,37 +945,10 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatOver(const std::str
                               over[1].data(), over[2].data(), (uint32_t)rnode.size(), rnode.data(), rreq[0].data(), rreq[1].data(),
                               rreq[2].data(), flags.data(), cluster.zone.data(), (uint32_t)cluster.zone_labels.size(),
                               cluster.name_rank.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) != GF_OK)
-            return not_served(std::string("gf_snapshot_build: ") + gf_last_error(ctx));
+            return notServed(std::string("gf_snapshot_build: ") + gf_last_error(ctx));
     }
-    uint64_t total_k = 0;
-    for (const gf_app& a : apps) total_k += (uint64_t)a.k;
-    std::vector<gf_result> results(apps.size());
-    std::vector<uint32_t> exec(total_k + 1);
-    int32_t failed_at = -1;
-    if (gf_fit_batch(ctx, GF_MODE_FIFO_CHAIN, binpacker_.Algo, (uint32_t)apps.size(), apps.data(), results.data(), exec.data(),
-                     total_k, &failed_at) != GF_OK)
-        return not_served(std::string("gf_fit_batch: ") + gf_last_error(ctx));
-    if (failed_at >= 0) {
-        out.outcome = outcome::failureEarlierDriver;
-        out.error = "earlier drivers do not fit to the cluster";
-        return out;
-    }
-    const gf_result& last = results.back();
-    if (!last.has_capacity) {
-        out.outcome = outcome::failureFit;
-        out.error = "application does not fit to the cluster";
-        return out;
-    }
-    std::vector<std::string> executorNodes;
-    const uint64_t off = total_k - (uint64_t)cur.k;
-    for (uint32_t i = 0; i < last.exec_len; ++i) executorNodes.push_back(cluster.names[exec[off + i]]);
-    out.node = cluster.names[last.driver_node];
-    out.outcome = outcome::success;
     // (the group route's keys are the row the snapshot was built from: built_members_ when recorded, this request's row always)
-    fillEfficiency(ctx, binpacker_.Algo, isFIFO_, cur, last, exec.data() + off, members != nullptr ? members->data() : nullptr, &out);
-    out.created = newResourceReservation(out.node, executorNodes, driver, resources->DriverResources,
-                                         resources->ExecutorResources);
-    return out;
+    return fitChain(ctx, apps, cluster.names, row, driver, *resources);
 }
 
 SelectNodeResult SparkSchedulerExtender::rescheduleExecutorFlat(const Pod& executor, const Pod& driver, const std::vector<Pod>& allPods,
@@ -1016,16 +958,11 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutorFlat(const Pod& execu
                                                                 const FlatOverhead* flatOverhead, bool* residentRoute) {
     if (residentRoute) *residentRoute = false;
     auto installs = [&] { return rescheduleExecutor(executor, driver, allPods, nodeNames, nodesHostingApp, isExtraExecutor); };
-    SelectNodeResult out;
     std::string err;
     auto resources = sparkResources(driver, &err);  // first in the reference (:599-602)
-    if (!resources) {
-        out.outcome = outcome::failureInternal;
-        out.error = err;
-        return out;
-    }
+    if (!resources) return failure(outcome::failureInternal, err);
     int64_t exe[3];
-    if (!resources->ExecutorResources.canonical(exe) || exe[0] < 0 || exe[1] < 0 || exe[2] < 0) return installs();
+    if (!canonicalNonNegative(resources->ExecutorResources, exe)) return installs();
     if (sorter_.hasExecutorLabelPriority() || cluster.version == 0) return installs();
     const uint32_t n = (uint32_t)cluster.names.size();
     // ---- the zone step on the host, as rescheduleExecutor does it (:606-632); its errors are the reference's
@@ -1033,11 +970,7 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutorFlat(const Pod& execu
     std::string zone;
     if (binpacker_.IsSingleAz && shouldScheduleDynamicallyAllocatedExecutorsInSameAZ) {
         auto [z, allPodsInSameAz] = getCommonZoneForExecutorsApplication(executor, allPods, &err);
-        if (!err.empty()) {
-            out.outcome = "";
-            out.error = err;
-            return out;
-        }
+        if (!err.empty()) return failure("", err);  // :611-613: ("", "", err)
         narrow = allPodsInSameAz;
         zone = z;
     }
@@ -1045,43 +978,29 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutorFlat(const Pod& execu
     std::unordered_map<std::string, const Node*> listed;
     listed.reserve(nodes.size());
     for (const Node& nd : nodes) listed.emplace(nd.Name, &nd);
+    std::vector<const Node*> available;
+    for (const std::string& name : nodeNames)
+        if (auto nd = listed.find(name); nd != listed.end()) available.push_back(nd->second);
+    bool unlabelled = false;
+    auto in_zone = [&](const Node& node) {  // filterNodesToZone (:462-478)
+        if (!narrow) return true;
+        auto z = node.labels.find(kLabelTopologyZone);
+        if (z == node.labels.end()) unlabelled = true;
+        return z != node.labels.end() && z->second == zone;
+    };
     std::vector<uint64_t> row(((size_t)n + 63) / 64, 0);
-    for (const std::string& name : nodeNames) {
-        auto nd = listed.find(name);
-        if (nd == listed.end()) continue;
-        auto at = cluster.index.find(name);
-        if (at == cluster.index.end()) return installs();  // `cluster` does not describe this request's nodes
-        if (narrow) {  // filterNodesToZone (:462-478)
-            auto z = nd->second->labels.find(kLabelTopologyZone);
-            if (z == nd->second->labels.end()) {
-                out.outcome = outcome::failureInternal;
-                out.error = "Could not read zone label from node, unable to make scheduling decisions based on AZ";
-                return out;
-            }
-            if (z->second != zone) continue;
-        }
-        row[at->second >> 6] |= UINT64_C(1) << (at->second & 63u);
-    }
+    const bool known = nodeBitRow(cluster, available, row.data(), in_zone);
+    if (unlabelled)  // (met before any node outside the cluster: the walk ends at such a node)
+        return failure(outcome::failureInternal, "Could not read zone label from node, unable to make scheduling decisions based on AZ");
+    if (!known) return installs();  // `cluster` does not describe this request's nodes
     const bool minfrag = binpacker_.Name == "single-az-minimal-fragmentation";
     std::vector<uint32_t> hosts(((size_t)n + 31) / 32, 0u);
     for (const std::string& name : nodesHostingApp)
         if (auto it = cluster.index.find(name); it != cluster.index.end()) hosts[it->second >> 5] |= 1u << (it->second & 31);
     // ---- the per-request columns, as in selectDriverNodeFlat; the device reads the RESIDENT usage, so an entry list always travels
-    // by version (a caller that keeps none gets this request's own, with a version of its own)
-    FlatReservations local;
-    if (flat == nullptr || flat->version == 0) {
-        if (!FlatReservations::Build(reservations, softReservationUsage, cluster, &local, nullptr)) return installs();
-        flat = &local;
-    }
-    FlatOverhead local_over;
-    if (flatOverhead == nullptr) {
-        if (!FlatOverhead::Build(overhead, cluster, &local_over, nullptr)) return installs();
-        local_over.version = 0;  // this request's own: compared with the resident columns
-        flatOverhead = &local_over;
-    } else if (!flatOverhead->over[0].empty() &&
-               (flatOverhead->over[0].size() != n || flatOverhead->over[1].size() != n || flatOverhead->over[2].size() != n)) {
-        return installs();
-    }
+    // by version (a caller that keeps none, or one without a version, gets this request's own, with a version of its own)
+    RequestColumns cols;
+    if (!requestColumns(cluster, flat != nullptr && flat->version != 0 ? flat : nullptr, flatOverhead, &cols, &err)) return installs();
     uint32_t node = GF_NO_NODE;
     int rc = GF_ERR_UNSUPPORTED;
     {
@@ -1089,8 +1008,7 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutorFlat(const Pod& execu
         gf_ctx* ctx = binpacker_.ctx;
         CtxSequence seq(ctx);
         uint64_t gen[3] = {0, 0, 0};
-        std::string sync_err;
-        if (syncResident(ctx, cluster, *flatOverhead, flat, gen, &sync_err) == ResidentSync::ok) {
+        if (syncResident(ctx, cluster, *cols.over, cols.usage, gen, &err) == ResidentSync::ok) {
             const uint32_t row0 = 0;
             rc = gf_cluster_executor_fit(ctx, minfrag ? 1 : 0, 1, row.data(), 1, exe, &row0, minfrag ? hosts.data() : nullptr, nullptr,
                                          nullptr, nullptr, &node);
@@ -1098,14 +1016,7 @@ SelectNodeResult SparkSchedulerExtender::rescheduleExecutorFlat(const Pod& execu
     }
     if (rc != GF_OK) return installs();  // refused, or not resident (outside the locks: that route takes them itself)
     if (residentRoute) *residentRoute = true;
-    if (node == GF_NO_NODE) {
-        out.outcome = outcome::failureFit;
-        out.error = "not enough capacity to reschedule the executor";
-        return out;
-    }
-    out.node = cluster.names[node];
-    out.outcome = isExtraExecutor ? outcome::successScheduledExtraExecutor : outcome::successRescheduled;
-    return out;
+    return executorAnswer(node, cluster.names, isExtraExecutor);
 }
 
 }  // namespace gangfit::host

@@ -249,6 +249,35 @@ private:
     enum class ResidentSync { ok, no_resident_route, failed };
     ResidentSync syncResident(gf_ctx* ctx, const FlatCluster& cluster, const FlatOverhead& fo, const FlatReservations* usage,
                               uint64_t gen[3], std::string* err);
+    // The steps the routes share (extender.cpp says what each does).
+    struct PodApp {  // a pod's annotations as a chain application
+        bool parsed = false, representable = false;
+        gf_app app{};
+    };
+    static PodApp podApp(const Pod& pod, std::string* err);
+    struct StaleDrivers {  // what a capacity scan lists: facts, no policy
+        std::vector<const Pod*> pods;
+        std::vector<gf_app> apps;
+        bool stopped = false;  // at an unparsable pod:
+        std::string parse_error;
+        const Pod* unrepresentable = nullptr;  // the first listed pod that is not exactly representable
+    };
+    StaleDrivers listStaleDrivers(const std::vector<Pod>& allPods, int64_t timeoutNanos) const;
+    template <class AppOf>
+    bool earlierDriverApps(const std::string& instanceGroup, const Pod& driver, AppOf app_of, std::vector<gf_app>* apps, std::string* why) const;
+    SelectNodeResult fitChain(gf_ctx* ctx, const std::vector<gf_app>& apps, const std::vector<std::string>& names, const uint64_t* row,
+                              const Pod& driver, const SparkApplicationResources& resources) const;
+    struct RequestColumns {  // the usage entries and overhead columns one flat request reads: the caller's, or its own
+        FlatReservations own_usage;
+        FlatOverhead own_over;
+        const FlatReservations* usage = nullptr;
+        const FlatOverhead* over = nullptr;
+    };
+    bool requestColumns(const FlatCluster& cluster, const FlatReservations* kept_usage, const FlatOverhead* kept_over, RequestColumns* cols,
+                        std::string* why) const;
+    enum class Asked { answered, fall_back, failed };
+    template <class Ask>
+    Asked askResident(const FlatCluster& cluster, const char* entry, Ask ask, bool* served, std::string* err);
     uint64_t resident_cluster_ = 0;  // FlatCluster::version whose static columns sit on the device (selectDriverNodeFlat)
     uint64_t resident_usage_ = 0;    // FlatReservations::version whose usage sums sit on the device (for resident_cluster_)
     // the dense overhead columns this extender last put on the device for resident_cluster_ (gf_cluster_set or
@@ -276,8 +305,7 @@ private:
     struct ParsedApp {
         uint64_t version = 0;
         uint64_t seen = 0;  // flat_calls_ of the last Filter that used the entry: what a prune keeps
-        bool ok = false, representable = false;
-        gf_app app{};
+        PodApp parsed;
     };
     std::shared_ptr<std::mutex> flat_mu_ = std::make_shared<std::mutex>();  // (the extender stays copyable: copies share it)
     uint64_t flat_calls_ = 0;

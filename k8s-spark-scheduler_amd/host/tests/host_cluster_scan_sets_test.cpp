@@ -3,7 +3,7 @@
 // instance groups plus one of a group nobody names, against one scanForUnschedulablePods per group (which installs the
 // empty-cluster snapshot) merged back into listing order; the resident route answers after a flat Filter and not before one, and
 // leaves gf_generation alone.
-// `host_cluster_scan_sets_test cpu` needs no GPU (the listing: nothing stale, an unparsable pod); `host_cluster_scan_sets_test gpu`
+// `host_cluster_scan_sets_test cpu` needs no GPU (the listing: nothing stale, an unparsable pod, an unrepresentable one); `host_cluster_scan_sets_test gpu`
 // drives the device through the C ABI.  Exit code 0 = all passed.
 #include <cstdio>
 #include <cstdlib>
@@ -11,31 +11,8 @@
 #include <string>
 #include <vector>
 
-#include "extender.hpp"
-
-using namespace gangfit::host;
-
-static int g_failed = 0, g_checked = 0;
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        ++g_checked;                                                           \
-        if (!(cond)) {                                                         \
-            ++g_failed;                                                        \
-            std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);        \
-        }                                                                      \
-    } while (0)
-
-static const int64_t Mi = 1024 * 1024, Gi = 1024 * Mi;
-static gf_ctx* g_ctx = nullptr;
-
-static uint64_t g_rng = 0x5E75;
-static uint64_t next() {
-    g_rng += 0x9E3779B97F4A7C15ull;
-    uint64_t z = g_rng;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+#define HOST_TEST_SEED 0x5E75
+#include "host_test_common.hpp"
 
 static Pod Driver(const std::string& app, const std::string& group, int numExecutors, const char* executorMem, const char* executorCPU,
                   bool executorGpu, int64_t created_s) {
@@ -87,6 +64,14 @@ static void TestTheListingNeedsNoDevice() {
     resident = true;
     r = ext.scanForUnschedulablePodsAllGroups({young, broken, behind}, kTimeout, cluster, groups, {}, &served, &err, &resident);
     CHECK(r.empty() && served && !resident && !err.empty());
+    // an unrepresentable pod in a group that has nodes takes the per-group route, whose installing scan does not serve it
+    Pod micro = Driver("micro", "group-a", 2, "1Gi", "1500u", false, 1);
+    served = true;
+    resident = true;
+    err.clear();
+    r = ext.scanForUnschedulablePodsAllGroups({young, micro, behind}, kTimeout, cluster, groups, {}, &served, &err, &resident);
+    CHECK(r.empty() && !served && !resident);
+    CHECK(err == "pod micro-spark-driver is not exactly representable");
 }
 
 // ------------------------------------------------------------------------------------------------ through the device
@@ -193,18 +178,12 @@ static void TestThreeGroupsAndAnUnknownOne() {
     }
 }
 
-int main(int argc, char** argv) {
-    (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);  // the deployment's part ("Deployment")
-    const std::string mode = argc > 1 ? argv[1] : "cpu";
-    if (mode == "cpu" || mode == "all") TestTheListingNeedsNoDevice();
-    if (mode == "gpu" || mode == "all") {
-        if (gf_init(nullptr, 0, &g_ctx) != GF_OK) {
-            std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
-            return 2;
-        }
-        TestThreeGroupsAndAnUnknownOne();
-        gf_destroy(g_ctx);
-    }
-    std::printf("%s: %d checks, %d failed\n", mode.c_str(), g_checked, g_failed);
-    return g_failed == 0 ? 0 : 1;
+static void CpuHalf() {
+    TestTheListingNeedsNoDevice();
 }
+
+static void GpuHalf() {
+    TestThreeGroupsAndAnUnknownOne();
+}
+
+int main(int argc, char** argv) { return RunHostTests(argc, argv, CpuHalf, GpuHalf); }

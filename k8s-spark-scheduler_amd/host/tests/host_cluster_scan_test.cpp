@@ -3,39 +3,16 @@
 // scanForUnschedulablePods, which installs the empty-cluster snapshot, on the scenarios of the reference's
 // unschedulablepods_test.go (the gpu scenario included) and on a cluster with zones, overhead and a node selection; the Filter
 // after the scan resumes its chain; a question the entry point refuses falls back to the installing route.
-// `host_cluster_scan_test cpu` needs no GPU (the node selection of a flat cluster); `host_cluster_scan_test gpu` drives the
-// device through the C ABI.  Exit code 0 = all passed.
+// `host_cluster_scan_test cpu` needs no GPU (the node selection of a flat cluster, the listing filter and the refusals of
+// the scans); `host_cluster_scan_test gpu` drives the device through the C ABI.  Exit code 0 = all passed.
 #include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <string>
 #include <vector>
 
-#include "extender.hpp"
-
-using namespace gangfit::host;
-
-static int g_failed = 0, g_checked = 0;
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        ++g_checked;                                                           \
-        if (!(cond)) {                                                         \
-            ++g_failed;                                                        \
-            std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);        \
-        }                                                                      \
-    } while (0)
-
-static const int64_t Mi = 1024 * 1024, Gi = 1024 * Mi;
-static gf_ctx* g_ctx = nullptr;
-
-static uint64_t g_rng = 0x5CA9;
-static uint64_t next() {
-    g_rng += 0x9E3779B97F4A7C15ull;
-    uint64_t z = g_rng;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+#define HOST_TEST_SEED 0x5CA9
+#include "host_test_common.hpp"
 
 static Node NewNode(const std::string& name, const char* zone) {  // extendertest.NewNode (extender_test_utils.go:239-271)
     Node n;
@@ -89,6 +66,80 @@ static void TestNodesOutsideTheClusterTakeTheOtherRoute() {
     bool served = false, resident = true;
     const ScanResult r = ext.scanForUnschedulablePodsResident({}, 0, cluster, {NewNode("node2", "zone1")}, {}, &served, &err, &resident);
     CHECK(r.empty() && !resident);  // (no pending driver: the installing route returns before it needs a device)
+}
+
+// What each scan does with a stale pod it cannot take, decided before any device call: an unparsable pod ends the listing with
+// the parse error, an unrepresentable one is not served; the resident scan hands both to the installing scan.
+static void TestRefusalsOfTheScans() {
+    SparkSchedulerExtender ext(SelectBinpacker("tightly-pack", nullptr), NodeSorter(), true, FifoConfig{});
+    ext.nodes = {NewNode("node1", "zone1")};
+    ext.nowNanos = 10000ll * 1000000000;
+    FlatCluster cluster;
+    std::string err;
+    CHECK(FlatCluster::Build(ext.nodes, &cluster, &err));
+    Pod unparsable = Driver("unparsable", StaticAnnotations(2), 1);
+    unparsable.Annotations["spark-executor-count"] = "many";
+    Pod unrepresentable = Driver("unrepresentable", StaticAnnotations(2), 1);
+    unrepresentable.Annotations["spark-executor-cpu"] = "1500u";
+    const Pod behind = Driver("behind", StaticAnnotations(2), 2);
+    std::string parse_err;
+    CHECK(!sparkResources(unparsable, &parse_err) && !parse_err.empty());
+    CHECK(sparkResources(unrepresentable, nullptr).has_value());
+    // ---- scanForUnschedulablePods
+    bool served = false;
+    err.clear();
+    ScanResult r = ext.scanForUnschedulablePods({unparsable, behind}, 0, ext.nodes, {}, &served, &err);
+    CHECK(r.empty() && served && err == parse_err);
+    served = true;
+    err.clear();
+    r = ext.scanForUnschedulablePods({unrepresentable, behind}, 0, ext.nodes, {}, &served, &err);
+    CHECK(r.empty() && !served && err == "pod unrepresentable-spark-driver is not exactly representable");
+    // ---- scanForUnschedulablePodsResident: what scanForUnschedulablePods says, by the installing route
+    bool resident = true;
+    served = false;
+    err.clear();
+    r = ext.scanForUnschedulablePodsResident({unparsable, behind}, 0, cluster, ext.nodes, {}, &served, &err, &resident);
+    CHECK(r.empty() && served && err == parse_err && !resident);
+    resident = true;
+    served = true;
+    err.clear();
+    r = ext.scanForUnschedulablePodsResident({unrepresentable, behind}, 0, cluster, ext.nodes, {}, &served, &err, &resident);
+    CHECK(r.empty() && !served && err == "pod unrepresentable-spark-driver is not exactly representable" && !resident);
+}
+
+// The listing of all three scans: a young driver, a bound one, a deleting one, an executor and a pod of another scheduler are
+// skipped, so nothing is asked and no device is needed.
+static void TestTheListingFilterOfTheScans() {
+    SparkSchedulerExtender ext(SelectBinpacker("tightly-pack", nullptr), NodeSorter(), true, FifoConfig{});
+    ext.nodes = {NewNode("node1", "zone1")};
+    ext.nowNanos = 10000ll * 1000000000;
+    FlatCluster cluster;
+    std::string err;
+    CHECK(FlatCluster::Build(ext.nodes, &cluster, &err));
+    const Pod young = Driver("young", StaticAnnotations(2), 9999);
+    Pod bound = Driver("bound", StaticAnnotations(2), 1);
+    bound.NodeName = "node1";
+    Pod deleting = Driver("deleting", StaticAnnotations(2), 1);
+    deleting.Deleting = true;
+    Pod executor = Driver("executor", StaticAnnotations(2), 1);
+    executor.labels[common::SparkRoleLabel] = common::Executor;
+    Pod foreign = Driver("foreign", StaticAnnotations(2), 1);
+    foreign.SchedulerName = "default-scheduler";
+    // (each of them unparsable: a pod the filter let through would end the listing with an error)
+    std::vector<Pod> skipped = {young, bound, deleting, executor, foreign};
+    for (Pod& p : skipped) p.Annotations["spark-executor-count"] = "many";
+    const std::map<std::string, std::vector<Node>> groups = {{"batch-medium-priority", ext.nodes}};
+    bool served = false, resident = true;
+    err.clear();
+    ScanResult r = ext.scanForUnschedulablePods(skipped, 600ll * 1000000000, ext.nodes, {}, &served, &err);
+    CHECK(r.empty() && served && err.empty());
+    served = false;
+    r = ext.scanForUnschedulablePodsResident(skipped, 600ll * 1000000000, cluster, ext.nodes, {}, &served, &err, &resident);
+    CHECK(r.empty() && served && err.empty() && !resident);
+    served = false;
+    resident = true;
+    r = ext.scanForUnschedulablePodsAllGroups(skipped, 600ll * 1000000000, cluster, groups, {}, &served, &err, &resident);
+    CHECK(r.empty() && served && err.empty() && !resident);
 }
 
 // ------------------------------------------------------------------------------------------------ through the device
@@ -259,20 +310,16 @@ static void TestARefusedQuestionFallsBack() {
     if (got2.size() == 2) CHECK(!got2[0].second && got2[1].second);
 }
 
-int main(int argc, char** argv) {
-    (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);  // the deployment's part ("Deployment")
-    const std::string mode = argc > 1 ? argv[1] : "cpu";
-    if (mode == "cpu" || mode == "all") TestNodesOutsideTheClusterTakeTheOtherRoute();
-    if (mode == "gpu" || mode == "all") {
-        if (gf_init(nullptr, 0, &g_ctx) != GF_OK) {
-            std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
-            return 2;
-        }
-        TestReferenceScenarios();
-        TestZonesOverheadSelectionAndTheNextFilter();
-        TestARefusedQuestionFallsBack();
-        gf_destroy(g_ctx);
-    }
-    std::printf("%s: %d checks, %d failed\n", mode.c_str(), g_checked, g_failed);
-    return g_failed == 0 ? 0 : 1;
+static void CpuHalf() {
+    TestNodesOutsideTheClusterTakeTheOtherRoute();
+    TestRefusalsOfTheScans();
+    TestTheListingFilterOfTheScans();
 }
+
+static void GpuHalf() {
+    TestReferenceScenarios();
+    TestZonesOverheadSelectionAndTheNextFilter();
+    TestARefusedQuestionFallsBack();
+}
+
+int main(int argc, char** argv) { return RunHostTests(argc, argv, CpuHalf, GpuHalf); }

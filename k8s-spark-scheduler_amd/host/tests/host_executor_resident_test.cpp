@@ -4,7 +4,7 @@
 // (resource_test.go:172-372, the same-AZ case included) and TestMinimalFragmentation*, on a cluster with zones, overhead and
 // reservations, and for a call the entry point refuses (which must fall back); the driver Filter after a resident executor Filter
 // resumes its chain.
-// `host_executor_resident_test cpu` needs no GPU (what the flat route decides before it touches a context);
+// `host_executor_resident_test cpu` needs no GPU (what the flat route decides before it touches a context, the refusals of both routes);
 // `host_executor_resident_test gpu` drives the device through the C ABI.  Exit code 0 = all passed.
 #include <cstdio>
 #include <cstdlib>
@@ -13,31 +13,8 @@
 #include <string>
 #include <vector>
 
-#include "extender.hpp"
-
-using namespace gangfit::host;
-
-static int g_failed = 0, g_checked = 0;
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        ++g_checked;                                                           \
-        if (!(cond)) {                                                         \
-            ++g_failed;                                                        \
-            std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);        \
-        }                                                                      \
-    } while (0)
-
-static const int64_t Mi = 1024 * 1024, Gi = 1024 * Mi;
-static gf_ctx* g_ctx = nullptr;
-
-static uint64_t g_rng = 0xE8EC;
-static uint64_t next() {
-    g_rng += 0x9E3779B97F4A7C15ull;
-    uint64_t z = g_rng;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+#define HOST_TEST_SEED 0xE8EC
+#include "host_test_common.hpp"
 
 static Node NewNode(const std::string& name, const char* zone) {  // extendertest.NewNode (extender_test_utils.go:239-271)
     Node n;
@@ -149,6 +126,39 @@ static void TestWhatIsDecidedBeforeTheDevice() {
     r = ext.rescheduleExecutorFlat(Executor("app", 0), driver, {running}, {"node1", "node2"}, {}, true, cluster, nullptr, nullptr, &resident);
     CHECK(r.node.empty() && r.outcome == std::string(outcome::failureInternal) &&
           r.error == "Could not read zone label from node, unable to make scheduling decisions based on AZ");
+}
+
+// An unparsable driver is failure-internal with the bare parse error, an executor request that is not exactly representable is
+// not served: by rescheduleExecutor and by rescheduleExecutorFlat (which hands the second to rescheduleExecutor) alike.
+static void TestRefusalsOfTheExecutorFilters() {
+    SparkSchedulerExtender ext(SelectBinpacker("tightly-pack", nullptr), NodeSorter(), true, FifoConfig{});
+    ext.nodes = {NewNode("node1", "zone1"), NewNode("node2", "zone2")};
+    FlatCluster cluster;
+    std::string err;
+    CHECK(FlatCluster::Build(ext.nodes, &cluster, &err));
+    const std::vector<std::string> names = {"node1", "node2"};
+    Pod unparsable = Driver("app", StaticAnnotations(2));
+    unparsable.Annotations["spark-executor-count"] = "many";
+    std::string parse_err;
+    CHECK(!sparkResources(unparsable, &parse_err) && !parse_err.empty());
+    auto internal = [&](const SelectNodeResult& r) {
+        return r.served && r.node.empty() && r.outcome == std::string(outcome::failureInternal) && r.error == parse_err;
+    };
+    CHECK(internal(ext.rescheduleExecutor(Executor("app", 0), unparsable, {unparsable}, names, {}, false)));
+    CHECK(internal(ext.rescheduleExecutor(unparsable, names, ext.nodes, {}, false)));
+    bool resident = true;
+    CHECK(internal(ext.rescheduleExecutorFlat(Executor("app", 0), unparsable, {unparsable}, names, {}, false, cluster, nullptr, nullptr, &resident)));
+    CHECK(!resident);
+    const Pod micro = Driver("app", StaticAnnotations(2, "1", "1", "1", "1500u"));
+    CHECK(sparkResources(micro, nullptr).has_value());
+    auto not_served = [](const SelectNodeResult& r) {
+        return !r.served && r.node.empty() && r.error == "executor resources are not exactly representable";
+    };
+    CHECK(not_served(ext.rescheduleExecutor(Executor("app", 0), micro, {micro}, names, {}, false)));
+    CHECK(not_served(ext.rescheduleExecutor(micro, names, ext.nodes, {}, false)));
+    resident = true;
+    CHECK(not_served(ext.rescheduleExecutorFlat(Executor("app", 0), micro, {micro}, names, {}, false, cluster, nullptr, nullptr, &resident)));
+    CHECK(!resident);
 }
 
 // ------------------------------------------------------------------------------------------------ through the device
@@ -421,21 +431,16 @@ static void TestARefusedCallFallsBack() {
     CHECK(r2.served && !r2.node.empty());
 }
 
-int main(int argc, char** argv) {
-    (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);  // the deployment's part ("Deployment")
-    const std::string mode = argc > 1 ? argv[1] : "cpu";
-    if (mode == "cpu" || mode == "all") TestWhatIsDecidedBeforeTheDevice();
-    if (mode == "gpu" || mode == "all") {
-        if (gf_init(nullptr, 0, &g_ctx) != GF_OK) {
-            std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
-            return 2;
-        }
-        TestDynamicAllocationSameAZ();
-        TestSoftReservationsAndMinimalFragmentation();
-        TestOverheadReservationsAndTheNextFilter();
-        TestARefusedCallFallsBack();
-        gf_destroy(g_ctx);
-    }
-    std::printf("%s: %d checks, %d failed\n", mode.c_str(), g_checked, g_failed);
-    return g_failed == 0 ? 0 : 1;
+static void CpuHalf() {
+    TestWhatIsDecidedBeforeTheDevice();
+    TestRefusalsOfTheExecutorFilters();
 }
+
+static void GpuHalf() {
+    TestDynamicAllocationSameAZ();
+    TestSoftReservationsAndMinimalFragmentation();
+    TestOverheadReservationsAndTheNextFilter();
+    TestARefusedCallFallsBack();
+}
+
+int main(int argc, char** argv) { return RunHostTests(argc, argv, CpuHalf, GpuHalf); }

@@ -13,32 +13,10 @@
 #include <string>
 #include <vector>
 
-#include "extender.hpp"
+#define HOST_TEST_SEED 0xEFF1
+#include "host_test_common.hpp"
 
-using namespace gangfit::host;
-
-static int g_failed = 0, g_checked = 0;
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        ++g_checked;                                                           \
-        if (!(cond)) {                                                         \
-            ++g_failed;                                                        \
-            std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);        \
-        }                                                                      \
-    } while (0)
-
-static const int64_t Gi = 1024ll * 1024 * 1024;
-static gf_ctx* g_ctx = nullptr;   // the extender's
 static gf_ctx* g_rows = nullptr;  // where the residual is installed for gf_packing_efficiencies
-
-static uint64_t g_rng = 0xEFF1;
-static uint64_t next() {
-    g_rng += 0x9E3779B97F4A7C15ull;
-    uint64_t z = g_rng;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 static Pod Driver(const std::string& app, const std::string& group, int k, const char* emem, const char* ecpu, int64_t created_s) {
     Pod p;
@@ -282,19 +260,17 @@ static void TestFilterWithTwoEarlierDrivers() {
     }
 }
 
-int main(int argc, char** argv) {
-    (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);  // the deployment's part ("Deployment")
-    const std::string mode = argc > 1 ? argv[1] : "cpu";
-    if (mode == "cpu" || mode == "all") TestWhatNeedsNoDevice();
-    if (mode == "gpu" || mode == "all") {
-        if (gf_init(nullptr, 0, &g_ctx) != GF_OK || gf_init(nullptr, 0, &g_rows) != GF_OK) {
-            std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
-            return 2;
-        }
-        TestFilterWithTwoEarlierDrivers();
-        gf_destroy(g_rows);
-        gf_destroy(g_ctx);
-    }
-    std::printf("%s: %d checks, %d failed\n", mode.c_str(), g_checked, g_failed);
-    return g_failed == 0 ? 0 : 1;
+static void CpuHalf() {
+    TestWhatNeedsNoDevice();
 }
+
+static void GpuHalf() {
+    if (gf_init(nullptr, 0, &g_rows) != GF_OK) {
+        std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
+        std::exit(2);
+    }
+    TestFilterWithTwoEarlierDrivers();
+    gf_destroy(g_rows);
+}
+
+int main(int argc, char** argv) { return RunHostTests(argc, argv, CpuHalf, GpuHalf); }

@@ -3,7 +3,8 @@
 // every node; Filters of the three groups alternate, a scanForUnschedulablePodsAllGroups and a rescheduleExecutorFlat run in
 // between; every Filter equals selectDriverNode (the string-map route) on that group's nodes, gf_cluster_set is sent once, and
 // the same group's Filter twice in a row does not rebuild.
-// `host_group_filter_test cpu` needs no GPU (what the route hands to selectDriverNode before it touches a device);
+// `host_group_filter_test cpu` needs no GPU (what the route hands to selectDriverNode before it touches a device, and what the
+// three driver Filters refuse before they do);
 // `host_group_filter_test gpu` drives the device through the C ABI.  Exit code 0 = all passed.
 #include <cstdio>
 #include <cstdlib>
@@ -11,31 +12,8 @@
 #include <string>
 #include <vector>
 
-#include "extender.hpp"
-
-using namespace gangfit::host;
-
-static int g_failed = 0, g_checked = 0;
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        ++g_checked;                                                           \
-        if (!(cond)) {                                                         \
-            ++g_failed;                                                        \
-            std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);        \
-        }                                                                      \
-    } while (0)
-
-static const int64_t Mi = 1024 * 1024, Gi = 1024 * Mi;
-static gf_ctx* g_ctx = nullptr;
-
-static uint64_t g_rng = 0x6709;
-static uint64_t next() {
-    g_rng += 0x9E3779B97F4A7C15ull;
-    uint64_t z = g_rng;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+#define HOST_TEST_SEED 0x6709
+#include "host_test_common.hpp"
 
 static Pod Driver(const std::string& app, const std::string& group, int k, const char* emem, const char* ecpu, int64_t created_s) {
     Pod p;
@@ -106,7 +84,88 @@ static void TestWhatNeedsNoDevice() {
     CHECK(ext.clusterSetCalls() == 0);
 }
 
+// What the three driver Filters answer before any device call, each case with the same expectation for selectDriverNode,
+// selectDriverNodeFlat and selectDriverNodeFlatGroup.
+static void TestRefusalsOfTheDriverFilters() {
+    SparkSchedulerExtender ext(SelectBinpacker("tightly-pack", nullptr), NodeSorter(), true, FifoConfig{});
+    ext.nodes = {NewNode("node1", "az-a"), NewNode("node2", "az-b")};
+    ext.nowNanos = 1000ll * 1000000000;
+    FlatCluster cluster;
+    std::string err;
+    CHECK(FlatCluster::Build(ext.nodes, &cluster, &err));
+    const std::vector<std::string> names = {"node1", "node2"};
+    auto all_three = [&](const Pod& d, auto expected) {
+        CHECK(expected(ext.selectDriverNode("group-a", d, names, ext.nodes)));
+        CHECK(expected(ext.selectDriverNodeFlat("group-a", d, names, cluster)));
+        CHECK(expected(ext.selectDriverNodeFlatGroup("group-a", d, names, cluster, ext.nodes)));
+    };
+    // ---- an existing reservation answers with the reserved node; one without a "driver" entry with no node
+    const Pod reserved = Driver("reserved", "group-a", 2, "1Gi", "1", 5);
+    ResourceReservation rr;
+    rr.Name = "reserved";
+    rr.Namespace = "namespace";
+    rr.Reservations["driver"].Node = "node2";
+    ext.reservations = {rr};
+    all_three(reserved, [](const SelectNodeResult& r) {
+        return r.served && r.outcome == std::string(outcome::success) && r.node == "node2" && r.error.empty() && !r.created;
+    });
+    rr.Reservations.clear();
+    rr.Reservations[executorReservationName(0)].Node = "node1";
+    ext.reservations = {rr};
+    all_three(reserved, [](const SelectNodeResult& r) { return r.served && r.outcome == std::string(outcome::success) && r.node.empty(); });
+    ext.reservations.clear();
+    // ---- an unparsable current driver: failure-internal with the parse error behind its prefix, and served
+    Pod unparsable = Driver("unparsable", "group-a", 2, "1Gi", "1", 5);
+    unparsable.Annotations["spark-executor-count"] = "many";
+    std::string parse_err;
+    CHECK(!sparkResources(unparsable, &parse_err) && !parse_err.empty());
+    all_three(unparsable, [&](const SelectNodeResult& r) {
+        return r.served && r.node.empty() && r.outcome == std::string(outcome::failureInternal) &&
+               r.error == "failed to get spark resources: " + parse_err;
+    });
+    // ---- an unrepresentable current driver is not served
+    const Pod micro = Driver("micro", "group-a", 2, "1Gi", "1500u", 5);
+    all_three(micro, [](const SelectNodeResult& r) {
+        return !r.served && r.node.empty() && r.error == "application resources are not exactly representable";
+    });
+    // ---- an unrepresentable earlier driver (FIFO on) is not served either, and is named
+    const Pod current = Driver("current", "group-a", 2, "1Gi", "1", 5);
+    ext.pods = {Driver("earlier", "group-a", 2, "1Gi", "1500u", 1), current};
+    all_three(current, [](const SelectNodeResult& r) {
+        return !r.served && r.node.empty() && r.error == "earlier driver earlier-spark-driver is not exactly representable";
+    });
+    // (the earlier driver is looked at first: the same answer when the current one is unrepresentable too)
+    ext.pods.push_back(micro);
+    all_three(micro, [](const SelectNodeResult& r) {
+        return !r.served && r.error == "earlier driver earlier-spark-driver is not exactly representable";
+    });
+    CHECK(ext.clusterSetCalls() == 0);
+}
+
 // ------------------------------------------------------------------------------------------------ through the device
+// "failed to get driver resources, skipping driver" (resource.go:231-237): an earlier driver that cannot be parsed is left out of
+// the FIFO replay by the string route and by the flat route alike.  Two nodes, two pods.
+static void TestAnUnparsableEarlierDriverIsSkipped() {
+    SparkSchedulerExtender ext(SelectBinpacker("tightly-pack", g_ctx), NodeSorter(), true, FifoConfig{});
+    ext.nodes = {NewNode("node1", "az-a"), NewNode("node2", "az-b")};
+    ext.nowNanos = 1000ll * 1000000000;
+    FlatCluster cluster;
+    std::string err;
+    CHECK(FlatCluster::Build(ext.nodes, &cluster, &err));
+    const std::vector<std::string> names = {"node1", "node2"};
+    Pod earlier = Driver("earlier", "group-a", 2, "1Gi", "1", 1);
+    earlier.Annotations["spark-executor-count"] = "many";
+    const Pod current = Driver("current", "group-a", 2, "1Gi", "1", 5);
+    ext.pods = {earlier, current};
+    const SelectNodeResult flat = ext.selectDriverNodeFlat("group-a", current, names, cluster);
+    const SelectNodeResult map = ext.selectDriverNode("group-a", current, names, ext.nodes);
+    CHECK(map.served && map.outcome == std::string(outcome::success) && !map.node.empty() && map.created.has_value());
+    CHECK(SameAnswer(flat, map));
+    // alone in the queue the driver gets the same answer: the unparsable one took nothing
+    ext.pods = {current};
+    CHECK(SameAnswer(ext.selectDriverNode("group-a", current, names, ext.nodes), map));
+}
+
 static void TestThreeGroupsOnOneResidentCluster() {
     const int n = 300, n_pending = 36;
     const char* group_names[] = {"group-a", "group-b", "group-c"};
@@ -253,18 +312,14 @@ static void TestThreeGroupsOnOneResidentCluster() {
     }
 }
 
-int main(int argc, char** argv) {
-    (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);  // the deployment's part ("Deployment")
-    const std::string mode = argc > 1 ? argv[1] : "cpu";
-    if (mode == "cpu" || mode == "all") TestWhatNeedsNoDevice();
-    if (mode == "gpu" || mode == "all") {
-        if (gf_init(nullptr, 0, &g_ctx) != GF_OK) {
-            std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
-            return 2;
-        }
-        TestThreeGroupsOnOneResidentCluster();
-        gf_destroy(g_ctx);
-    }
-    std::printf("%s: %d checks, %d failed\n", mode.c_str(), g_checked, g_failed);
-    return g_failed == 0 ? 0 : 1;
+static void CpuHalf() {
+    TestWhatNeedsNoDevice();
+    TestRefusalsOfTheDriverFilters();
 }
+
+static void GpuHalf() {
+    TestThreeGroupsOnOneResidentCluster();
+    TestAnUnparsableEarlierDriverIsSkipped();
+}
+
+int main(int argc, char** argv) { return RunHostTests(argc, argv, CpuHalf, GpuHalf); }

@@ -2,7 +2,7 @@
 // node carries the requests of its daemonsets and non-Spark pods).  selectDriverNodeFlat keeps the overhead columns resident and
 // sends the rows that changed (gf_overhead_update); every answer must be the one selectDriverNode gives through the string-keyed
 // maps, which installs its own snapshot per call and replays the whole chain like the reference (resource.go:309-328).
-// `host_overhead_test cpu` needs no GPU (the row diff against a brute-force compare); `host_overhead_test gpu` drives the device
+// `host_overhead_test cpu` needs no GPU (the row diff against a brute-force compare, overhead columns of the wrong length); `host_overhead_test gpu` drives the device
 // through the C ABI.  Exit code 0 = all passed.
 #include <cstdio>
 #include <cstdlib>
@@ -10,30 +10,8 @@
 #include <string>
 #include <vector>
 
-#include "extender.hpp"
-
-using namespace gangfit::host;
-
-static int g_failed = 0, g_checked = 0;
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        ++g_checked;                                                           \
-        if (!(cond)) {                                                         \
-            ++g_failed;                                                        \
-            std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);        \
-        }                                                                      \
-    } while (0)
-
-static const int64_t Mi = 1024 * 1024, Gi = 1024 * Mi;
-
-static uint64_t g_rng = 0x0E4D;
-static uint64_t next() {
-    g_rng += 0x9E3779B97F4A7C15ull;
-    uint64_t z = g_rng;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+#define HOST_TEST_SEED 0x0E4D
+#include "host_test_common.hpp"
 
 // ------------------------------------------------------------------------------------------------ the row diff (no device)
 static void TestRowDiff() {
@@ -75,9 +53,6 @@ static void TestRowDiff() {
     CHECK((rows == std::vector<uint32_t>{1, 2}));
 }
 
-// ------------------------------------------------------------------------------------------------ through the device
-static gf_ctx* g_ctx = nullptr;
-
 static Pod Driver(const std::string& app, int k, const char* emem, const char* ecpu, int64_t created_s) {
     Pod p;
     p.Name = app + "-spark-driver";
@@ -105,6 +80,36 @@ static Resources RandomOverhead() {  // a daemonset's worth: some cpu, some memo
     return Resources{Quantity::FromMilli(100 + 50 * (int64_t)(next() % 20)), Quantity::FromInt((int64_t)(256 + 128 * (next() % 16)) * Mi), Quantity()};
 }
 
+// ------------------------------------------------------------------------------------------------ no device
+// Flat overhead columns of another length than the cluster are not this cluster's: the flat Filter does not serve the request, and
+// says so before it touches its caches or a device.
+static void TestOverheadColumnsOfTheWrongLength() {
+    SparkSchedulerExtender ext(SelectBinpacker("tightly-pack", nullptr), NodeSorter(), true, FifoConfig{});
+    for (const char* name : {"node1", "node2"}) {
+        Node nd;
+        nd.Name = name;
+        nd.Allocatable = {{kResourceCPU, Quantity::FromInt(8)}, {kResourceMemory, Quantity::FromInt(8 * Gi)}, {kResourceNvidiaGPU, Quantity::FromInt(0)}};
+        nd.Ready = true;
+        ext.nodes.push_back(nd);
+    }
+    ext.overhead["node1"] = Resources{Quantity::FromMilli(500), Quantity::FromInt(256 * Mi), Quantity()};
+    FlatCluster cluster;
+    FlatOverhead fo;
+    std::string err;
+    CHECK(FlatCluster::Build(ext.nodes, &cluster, &err));
+    CHECK(FlatOverhead::Build(ext.overhead, cluster, &fo, &err) && fo.over[0].size() == 2);
+    const Pod d = Driver("app", 1, "1Gi", "1", 1);
+    ext.pods = {d};
+    for (int j = 0; j < 3; ++j) {  // any one column is enough
+        FlatOverhead wrong = fo;
+        wrong.over[j].pop_back();
+        const SelectNodeResult r = ext.selectDriverNodeFlat("batch-medium-priority", d, {"node1", "node2"}, cluster, nullptr, &wrong);
+        CHECK(!r.served && r.node.empty() && r.error == "the flat overhead columns do not belong to this cluster");
+    }
+    CHECK(ext.flatCalls() == 0 && ext.clusterSetCalls() == 0);
+}
+
+// ------------------------------------------------------------------------------------------------ through the device
 static void TestFiltersWithOverhead() {
     const int n = 400, n_pending = 60;
     for (const char* packer : {"tightly-pack", "single-az-tightly-pack"}) {
@@ -300,18 +305,13 @@ static void TestFiltersWithOverhead() {
     }
 }
 
-int main(int argc, char** argv) {
-    (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);  // the deployment's part ("Deployment")
-    const std::string mode = argc > 1 ? argv[1] : "cpu";
-    if (mode == "cpu" || mode == "all") TestRowDiff();
-    if (mode == "gpu" || mode == "all") {
-        if (gf_init(nullptr, 0, &g_ctx) != GF_OK) {
-            std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
-            return 2;
-        }
-        TestFiltersWithOverhead();
-        gf_destroy(g_ctx);
-    }
-    std::printf("%s: %d checks, %d failed\n", mode.c_str(), g_checked, g_failed);
-    return g_failed == 0 ? 0 : 1;
+static void CpuHalf() {
+    TestRowDiff();
+    TestOverheadColumnsOfTheWrongLength();
 }
+
+static void GpuHalf() {
+    TestFiltersWithOverhead();
+}
+
+int main(int argc, char** argv) { return RunHostTests(argc, argv, CpuHalf, GpuHalf); }

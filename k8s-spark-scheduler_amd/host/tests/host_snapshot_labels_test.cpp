@@ -14,22 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "extender.hpp"
-
-using namespace gangfit::host;
-
-static int g_failed = 0, g_checked = 0;
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        ++g_checked;                                                           \
-        if (!(cond)) {                                                         \
-            ++g_failed;                                                        \
-            std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);        \
-        }                                                                      \
-    } while (0)
-
-static const int64_t Mi = 1024 * 1024, Gi = 1024 * Mi;
-static gf_ctx* g_ctx = nullptr;
+#include "host_test_common.hpp"
 
 struct Cluster {
     std::vector<Node> nodes;
@@ -200,19 +185,13 @@ static void BuildAndCompare(bool confined) {
     }
 }
 
-int main(int argc, char** argv) {
-    (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);  // the deployment's part ("Deployment")
-    const std::string mode = argc > 1 ? argv[1] : "cpu";
-    if (mode == "cpu" || mode == "all") TestMirrorConfinedListsShareOneOrder();
-    if (mode == "gpu" || mode == "all") {
-        if (gf_init(nullptr, 0, &g_ctx) != GF_OK) {
-            std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
-            return 2;
-        }
-        BuildAndCompare(false);
-        BuildAndCompare(true);
-        gf_destroy(g_ctx);
-    }
-    std::printf("%s: %d checks, %d failed\n", mode.c_str(), g_checked, g_failed);
-    return g_failed == 0 ? 0 : 1;
+static void CpuHalf() {
+    TestMirrorConfinedListsShareOneOrder();
 }
+
+static void GpuHalf() {
+    BuildAndCompare(false);
+    BuildAndCompare(true);
+}
+
+int main(int argc, char** argv) { return RunHostTests(argc, argv, CpuHalf, GpuHalf); }

@@ -18,22 +18,8 @@
 #include <thread>
 #include <vector>
 
-#include "extender.hpp"
+#include "host_test_common.hpp"
 #include "failover.hpp"
-
-using namespace gangfit::host;
-
-static int g_failed = 0, g_checked = 0;
-#define CHECK(cond)                                                            \
-    do {                                                                       \
-        ++g_checked;                                                           \
-        if (!(cond)) {                                                         \
-            ++g_failed;                                                        \
-            std::printf("FAIL %s:%d  %s\n", __FILE__, __LINE__, #cond);        \
-        }                                                                      \
-    } while (0)
-
-static const int64_t Mi = 1024 * 1024, Gi = 1024 * Mi;
 
 // ------------------------------------------------------------------------------------------------ quantity
 static void TestParseQuantity() {
@@ -338,7 +324,6 @@ static void TestSnapshotAndReservations() {
 }
 
 // ------------------------------------------------------------------------------------------------ device-backed tests
-static gf_ctx* g_ctx = nullptr;
 
 static SparkSchedulerExtender NewTestExtender(const char* binpackAlgo, std::vector<Node> nodes, bool fifo = true) {
     SparkSchedulerExtender e(SelectBinpacker(binpackAlgo, g_ctx), NodeSorter(), fifo, FifoConfig{});
@@ -722,7 +707,6 @@ static void TestDeviceSnapshotBuildAgainstHostMirror() {
         CHECK(same_exec);
     }
 }
-
 
 // Consecutive Filters on an unchanged cluster (selectDriverNodeFlat with the host's flattened reservations): the snapshot is
 // not rebuilt and the FIFO chain resumes from the previous chain's checkpoints (include/gangfit.h, "Incremental FIFO chains").
@@ -1280,43 +1264,34 @@ static void TestMultiDeviceContext() {
     (void)unsetenv("GANGFIT_TEST_GROUP_SPLIT");
 }
 
-int main(int argc, char** argv) {
-    // the deployment's part ("Deployment"): the library never changes the environment itself
-    (void)setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    const std::string mode = argc > 1 ? argv[1] : "cpu";
-    if (mode == "cpu" || mode == "all") {
-        TestParseQuantity();
-        TestSparkResources();
-        TestIsEarliest();
-        TestResourcesSorting();
-        TestScheduleContextSorting();
-        TestAZAwareNodeSorting();
-        TestAZAwareNodeSortingWorksIfZoneLabelIsMissing();
-        TestLabelPrioritySorting();
-        TestPotentialNodes();
-        TestSnapshotAndReservations();
-    }
-    if (mode == "gpu" || mode == "all") {
-        if (gf_init(nullptr, 0, &g_ctx) != GF_OK) {
-            std::printf("FAIL gf_init: no gfx950 device (there is no CPU fallback)\n");
-            return 2;
-        }
-        TestScheduler();
-        TestUnschedulablePodMarker();
-        TestUnschedulablePodScanBatched();
-        TestSchedulerFailsToScheduleWhenNotEnoughNvidiaGPUs();
-        TestFifoAndBinpackers();
-        TestMinimalFragmentationEdgeCase();
-        TestDynamicAllocationSameAZ();
-        TestDeviceSnapshotBuildAgainstHostMirror();
-        TestIncrementalFilters();
-        TestFindNodes();
-        TestTwoThreadsOneContext();
-        TestConcurrentViews();
-        TestResidentWorker();
-        TestMultiDeviceContext();
-        gf_destroy(g_ctx);
-    }
-    std::printf("%s: %d checks, %d failed\n", mode.c_str(), g_checked, g_failed);
-    return g_failed == 0 ? 0 : 1;
+static void CpuHalf() {
+    TestParseQuantity();
+    TestSparkResources();
+    TestIsEarliest();
+    TestResourcesSorting();
+    TestScheduleContextSorting();
+    TestAZAwareNodeSorting();
+    TestAZAwareNodeSortingWorksIfZoneLabelIsMissing();
+    TestLabelPrioritySorting();
+    TestPotentialNodes();
+    TestSnapshotAndReservations();
 }
+
+static void GpuHalf() {
+    TestScheduler();
+    TestUnschedulablePodMarker();
+    TestUnschedulablePodScanBatched();
+    TestSchedulerFailsToScheduleWhenNotEnoughNvidiaGPUs();
+    TestFifoAndBinpackers();
+    TestMinimalFragmentationEdgeCase();
+    TestDynamicAllocationSameAZ();
+    TestDeviceSnapshotBuildAgainstHostMirror();
+    TestIncrementalFilters();
+    TestFindNodes();
+    TestTwoThreadsOneContext();
+    TestConcurrentViews();
+    TestResidentWorker();
+    TestMultiDeviceContext();
+}
+
+int main(int argc, char** argv) { return RunHostTests(argc, argv, CpuHalf, GpuHalf); }

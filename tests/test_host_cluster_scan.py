@@ -3,33 +3,18 @@
 unschedulablepods_test.go and on a zoned cluster with overhead and a node selection, the Filter after it resumes, a refused
 question falls back.  The C++ program host/tests/host_cluster_scan_test.cpp does the checking; this file runs it the way
 test_host_overhead.py runs host_overhead_test: `cpu` needs no GPU, `gpu` drives the device through the C ABI."""
-import os
-import subprocess
-
 import pytest
 
 from gangfit import build
-
-
-def _binary():
-    build.build_native()
-    build.build_host()
-    assert os.path.exists(build.HOST_CLUSTER_SCAN_TEST_PATH), "host_cluster_scan_test was not built"
-    return build.HOST_CLUSTER_SCAN_TEST_PATH
-
-
-def _run(mode):
-    p = subprocess.run([_binary(), mode], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert p.returncode == 0 and " 0 failed" in p.stdout, p.stdout[-4000:]
-    return p.stdout
+from host_programs import _run
 
 
 def test_cluster_scan_cpu_half():
-    out = _run("cpu")
+    out = _run(build.HOST_CLUSTER_SCAN_TEST_PATH, "cpu")
     assert "cpu:" in out
 
 
 @pytest.mark.gpu
 def test_resident_scan_through_the_device():
-    out = _run("gpu")
+    out = _run(build.HOST_CLUSTER_SCAN_TEST_PATH, "gpu")
     assert "gpu:" in out

@@ -3,33 +3,18 @@ earlier drivers through the string route, the flat route and the group route rep
 against the chain's residual, bit for bit what the host computes from gf_packing_efficiencies' rows in the summation tree of
 include/gangfit.h.  The C++ program host/tests/host_filter_efficiency_test.cpp does the checking; this file runs it the way
 test_host_cluster_scan_sets.py runs host_cluster_scan_sets_test: `cpu` needs no GPU, `gpu` drives the device through the C ABI."""
-import os
-import subprocess
-
 import pytest
 
 from gangfit import build
-
-
-def _binary():
-    build.build_native()
-    build.build_host()
-    assert os.path.exists(build.HOST_FILTER_EFFICIENCY_TEST_PATH), "host_filter_efficiency_test was not built"
-    return build.HOST_FILTER_EFFICIENCY_TEST_PATH
-
-
-def _run(mode):
-    p = subprocess.run([_binary(), mode], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert p.returncode == 0 and " 0 failed" in p.stdout, p.stdout[-4000:]
-    return p.stdout
+from host_programs import _run
 
 
 def test_filter_efficiency_cpu_half():
-    out = _run("cpu")
+    out = _run(build.HOST_FILTER_EFFICIENCY_TEST_PATH, "cpu")
     assert "cpu:" in out
 
 
 @pytest.mark.gpu
 def test_filter_efficiency_through_the_device():
-    out = _run("gpu")
+    out = _run(build.HOST_FILTER_EFFICIENCY_TEST_PATH, "gpu")
     assert "gpu:" in out

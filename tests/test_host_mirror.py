@@ -8,29 +8,17 @@ import subprocess
 import pytest
 
 from gangfit import build
-
-
-def _binary():
-    build.build_native()
-    build.build_host()
-    assert os.path.exists(build.HOST_TEST_PATH), "host_test was not built"
-    return build.HOST_TEST_PATH
-
-
-def _run(mode):
-    p = subprocess.run([_binary(), mode], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert p.returncode == 0 and " 0 failed" in p.stdout, p.stdout[-4000:]
-    return p.stdout
+from host_programs import _binary, _run
 
 
 def test_host_mirror_cpu_half():
-    out = _run("cpu")
+    out = _run(build.HOST_TEST_PATH, "cpu")
     assert "cpu:" in out
 
 
 @pytest.mark.gpu
 def test_host_mirror_through_the_device():
-    out = _run("gpu")
+    out = _run(build.HOST_TEST_PATH, "gpu")
     assert "gpu:" in out
 
 
@@ -41,7 +29,7 @@ def test_flat_route_agrees_with_map_route(packer):
     """selectDriverNode on string-keyed maps (the reference's shape) and selectDriverNodeFlat (snapshot built on the
     device by gf_snapshot_build) must produce the same Filter result and the same reservation; host_bench exits 1 if
     they do not."""
-    _binary()
+    _binary(build.HOST_TEST_PATH)
     assert os.path.exists(build.HOST_BENCH_PATH)
     p = subprocess.run([build.HOST_BENCH_PATH, "700", "120", "90", packer], stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                        text=True, timeout=600)

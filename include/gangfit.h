@@ -791,6 +791,14 @@ int gf_worker_stop(gf_ctx *ctx);
 int gf_worker_stats(gf_ctx *ctx, uint64_t out[4]);
 /* out[0] sets, out[1] workgroups per set of the worker's last launch (0 0 before the first) */
 int gf_worker_geometry(gf_ctx *ctx, uint32_t out[2]);
+/* Shape rows of the tightly-pack worker: a workgroup that has met one scaled executor request often enough keeps the first 64
+ * nodes with room for it (node, capacity) as a row in its LDS and decides later gangs of that shape from the row — the same
+ * answers, without the scan of the node table.  Rows are per workgroup and per launch by design: they die with the launch, and
+ * the worker leaves before every install, so no row outlives its snapshot.  (Out of scope: rows in device memory, rows that
+ * survive a launch.)  out[0] rows built, [1] decisions served from a row, [2] decisions that looked a row up and were decided
+ * by the scan: totals since the context was created, over the launches that have LEFT the device (gf_worker_stop first); the
+ * counting instance (gf_scan_stats on) builds none. */
+int gf_worker_row_stats(gf_ctx *ctx, uint64_t out[3]);
 /* Measurement helper: where the last blocking gf_fit_batch(GF_MODE_INDEPENDENT) of a plain packer on the zero-copy path spent
  * its time on the host's clock, in microseconds: [0] validation + staging of the records into pinned memory, [1] the launch
  * call, [2] the wait for the stream (dispatch, the kernel — which reads the records from and writes the answers to pinned host

@@ -437,6 +437,19 @@ int gf_worker_geometry(gf_ctx* ctx, uint32_t out[2]) {
     return GF_OK;
 }
 
+int gf_worker_row_stats(gf_ctx* ctx, uint64_t out[3]) {
+    if (!ctx || !out) return GF_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    out[0] = out[1] = out[2] = 0;
+    const gf_ctx::Worker& w = ctx->worker;
+    if (!w.allocated) return GF_OK;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    unsigned long long h[3] = {0, 0, 0};
+    GF_HIP(ctx, hipMemcpy(h, w.d->rows, sizeof(h), hipMemcpyDeviceToHost));  // (a workgroup adds its counts when it leaves)
+    for (int i = 0; i < 3; ++i) out[i] = h[i];
+    return GF_OK;
+}
+
 int gf_worker_kernel_time(gf_ctx* ctx, float* ms, uint64_t* tickets) {
     if (!ctx || !ms || !tickets) return GF_ERR_INVALID;
     std::lock_guard<std::recursive_mutex> lock(ctx->mu);

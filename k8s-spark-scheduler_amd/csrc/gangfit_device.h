@@ -9,6 +9,7 @@
 
 #include "gangfit.h"
 #include "gangfit_worker_rounds.h"
+#include "gangfit_worker_rows.h"
 
 namespace gangfit {
 
@@ -190,7 +191,10 @@ struct WorkerHostCtl {  // pinned host memory, device-mapped
 
 struct WorkerDevCtl {  // fine-grained device memory
     unsigned long long quit;  // = generation of the launch whose leader has left (never reset: the next launch has another one)
-    unsigned long long pad0[7];
+    // shape rows of the tightly-pack instance (gangfit_worker_rows.h): rows built, decisions served from a row, decisions that
+    // looked a row up and fell back — every workgroup adds its LDS counts once, when it leaves (gf_worker_row_stats)
+    unsigned long long rows[3];
+    unsigned long long pad0[4];
     uint32_t count[kWorkerRing * kWorkerCountStride];  // [slot * stride]: applications of the slot's ticket finished so far
     WorkerTicket ring[kWorkerRing];
 };

@@ -111,6 +111,30 @@
 // 1 047-1 059 M) and +1.2 % on top of the counting split (1 077-1 091 M against 1 068-1 081 M): the ranges overlap both times, so it
 // does not pass the project's criterion; it also cost two VGPRs (97 -> 99).
 
+// SHAPE ROWS (profiles/r11a_worker_rows_summary.md; the arithmetic and the proof: gangfit_worker_rows.h): the capacity of a node for
+// an executor request does not depend on the application, a real queue asks for a handful of pod sizes, and the snapshot cannot
+// change while the worker lives — yet every decision recomputed it: group 0 of the index, ~2.3 chunk loads, the compares, the
+// gather, three multiply-highs per lane.  A workgroup now keeps, per scaled executor request it has met kRowSightings times, the
+// first 64 slots with room for it {slot, node, capacity} as a row in its LDS (40 rows, a directory probed by 40 lanes at once, no
+// eviction), and a wavefront that finds a READY row decides from it: wave_row_driver (the driver step of wave_decide on its own),
+// the driver's slot corrected, one wave scan, the run emission; gangs of gpu executors included.  A row that does not cover K, K == 0,
+// a driver behind group 0, the general layout: wave_decide on the same record, as before — nothing has been written by then.
+// Per workgroup and per launch BY DESIGN: LDS dies with the launch and the worker leaves before every install, so no row outlives
+// its snapshot; nothing waits for a row (BUILDING means "not there"); no loop here exits on another wavefront's progress.  Out of
+// scope: rows in device memory, rows that survive a launch (that is where a window of twenty could gain).
+// The build is inline (a real call gives the kernel a stack); the row state is ONE LDS object addressed through a lane index made
+// new at its use (as separate arrays the addresses were hoisted into ten VGPRs: 107; now 104, the whole budget, no scratch).  Not
+// looked up at all: the counting instance, a bounded launch of fewer than kRowSightings rounds per set, a wavefront that found the
+// directory full before any row was built.  Counters: three LDS words per workgroup, added to WorkerDevCtl::rows when the
+// workgroup's last wavefront leaves (gf_worker_row_stats).
+// Measured first, as a ceiling: the narrow decision without any pack (wrong answers on purpose) 1 913-1 957 M decisions/s against
+// 1 068-1 082 M (+80 %).  The change, parent and result alternately on one machine, seven runs each: 1 068-1 085 M -> 1 389-1 396 M
+// decisions/s at K = 2 000 (medians +29.2 %; the result's minimum 304 M above the parent's maximum, whose own range is 17 M wide);
+// 673.9 k -> 492.2 k instructions per ticket, 97.8 % of the decisions served from a row (a served decision: about 490 instructions).
+// A window of twenty, rows off: 412.9-448.1 M -> 418.7-431.6 M (medians 440.6 -> 429.2, inside the parent's range) — not free:
+// 727.5 k -> 772.1 k instructions per ticket there, the register pressure of the code around the row path (97 -> 104 VGPRs, 106 -> 111
+// spilled scalar registers).
+
 __device__ __forceinline__ unsigned long long sys_load(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -228,6 +252,42 @@ __device__ __forceinline__ Decision wave_decide_zones(const NodeTable& T, const 
                                                       uint32_t* cur, uint32_t* kept, int lane, unsigned long long& xvis,
                                                       unsigned long long& dvis, const uint32_t*& placed);
 
+// SHAPE ROWS (gangfit_worker_rows.h; tightly-pack instance, narrow path): the driver step of wave_decide on its own — the group-0
+// test for the driver role, the driver chunk's records, the fit mask, the first fitting lane; the same expressions as
+// wave_decide's merged branch (binpack.go:67-71) — so that a decision served from a row touches the node table for its driver
+// only.  found == false (no candidate chunk in group 0, or a stale maximum): the caller decides on wave_decide, which searches on.
+// The driver's three values stay in lane fl of d0 .. d2.
+struct RowDriver {
+    bool found;
+    uint32_t ds, node;
+    int fl;
+    int32_t d0, d1, d2;
+};
+__device__ __forceinline__ RowDriver wave_row_driver(const NarrowView& V, const Orders& O, const NarrowApp& app,
+                                                     const Group0T<int32_t>& g0, int lane) {
+    RowDriver r{false, 0u, GF_NO_NODE, 0, 0, 0, 0};
+    const uint32_t dc = (O.n_d + kWave - 1) / kWave;
+    const uint64_t ind_m = low_lanes(dc < V.n_chunks ? dc : V.n_chunks);
+    constexpr int kNE = 33;
+    const uint64_t md = ge3_mask(g0.m0, g0.m1, g0.m2, app.drv0, app.drv1, app.drv2) & ind_m &
+                        __builtin_amdgcn_uicmpl((unsigned long)g0.dcand, 0ul, kNE);
+    if (!md) return r;
+    const int bd = __ffsll((unsigned long long)md) - 1;
+    const uint32_t limit = O.n_d > O.n_x ? O.n_d : O.n_x;
+    const uint32_t id = (uint32_t)bd * kWave + lane;
+    uint32_t dnode = GF_NO_NODE;
+    if (id < limit) V.load(id, r.d0, r.d1, r.d2, dnode);
+    const uint64_t cdm = (uint64_t)read_lane((int64_t)g0.dcand, bd);
+    const uint64_t fm = ge3_mask(r.d0, r.d1, r.d2, app.drv0, app.drv1, app.drv2) & cdm & low_lanes(chunk_len(O.n_d, (uint32_t)bd * kWave, kWave));
+    if (!fm) return r;
+    r.fl = __ffsll((unsigned long long)fm) - 1;
+    r.ds = (uint32_t)bd * kWave + (uint32_t)r.fl;
+    r.node = read_lane(dnode, r.fl);
+    r.found = true;
+    return r;
+}
+static_assert(rows::kCapClamp == GF_MAX_K && rows::kRowLen == (uint32_t)kWave && rows::kRows <= (uint32_t)kWave, "lane = entry");
+
 // WHICH: the packer — or kWorkerCounting (tightly-pack with the scan counters).  The slots a decision visits (xvis / dvis, two 64-bit
 // wave-uniform accumulators that every chunk visit updates) are summed into W.stats by every instance but fit_worker_kernel<tightly-pack>,
 // which has nothing of the accumulation compiled in; the host launches fit_worker_kernel<kWorkerCounting> instead when gf_scan_stats
@@ -247,9 +307,27 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     // NARROW (tightly-pack): a wavefront decides an application in the snapshot's scaled int32 domain (NarrowView, NarrowApp:
     // 12 bytes per slot, 32-bit compares, capacities by multiplication, a four-dword gather) when the snapshot has that form
     // and the application's requests do (scale_record) — wave-uniform per application; otherwise on the int64 path, as the
-    // other instances always do.  Gangs of gpu executors keep the int64 path: the compact SparseTable has wide columns only.
+    // other instances always do.  Gangs of gpu executors take the int64 path (the compact SparseTable has wide columns only)
+    // until their shape has a row: then they are decided from it, on the narrow path, like any other (SHAPE ROWS).
     constexpr bool kNarrow = ALGO == GF_ALGO_TIGHTLY_PACK;
     __shared__ int32_t s_g0n[kNarrow ? 3 : 1][kWave];  // the three maxima of s_g0 in units (upper bounds: rounded up)
+    // SHAPE ROWS (gangfit_worker_rows.h): the product instance only — the counting instance keeps the launch path's counters, which
+    // a decision served from a row would not add to.  Directory word and key per entry, then the rows as three columns of 64.
+    constexpr bool kRowsOn = WHICH == (int)GF_ALGO_TIGHTLY_PACK;
+    constexpr uint32_t kRowsN = kRowsOn ? rows::kRows : 1u;
+    // (ONE object, and every access below through a lane index made new where it stands — GF_HERE —: a lane's words are one address
+    //  register plus immediate offsets, computed at the use; as separate arrays indexed by `lane` their addresses were hoisted out
+    //  of the round loop into VGPRs held through every decision: 107 VGPRs against the budget of 104; 104 this way)
+    struct RowsLds {
+        uint32_t dir[kWave];
+        int32_t key[3][kWave];
+        uint32_t slot[kRowsN][kWave];
+        uint32_t node[kRowsN][kWave];
+        int32_t cap[kRowsN][kWave];
+    };
+    __shared__ RowsLds s_rows[1];
+    __shared__ unsigned long long s_row_stat[3];  // rows built, decisions served from a row, decisions that looked up and fell back
+    __shared__ uint32_t s_left;                   // wavefronts of the workgroup that have left (the last one flushes s_row_stat)
     const int lane = lane_id();
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (blockIdx.x == 0) {
@@ -329,7 +407,21 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
     if (threadIdx.x < kCountSlots) s_cnt[threadIdx.x] = 0;
     if (threadIdx.x < 8) s_next[threadIdx.x] = 0ull;
     if (threadIdx.x < (uint32_t)kWorkerWaves) s_round[threadIdx.x] = 0;
+    if constexpr (kRowsOn) {
+        if (threadIdx.x < kRowsN) s_rows[0].dir[threadIdx.x] = rows::kEmpty;
+        if (threadIdx.x < 3) s_row_stat[threadIdx.x] = 0ull;
+        if (threadIdx.x == 0) s_left = 0u;
+    }
     const bool narrow_table = kNarrow && T.nquad != nullptr;
+    // SHAPE ROWS are looked up by a resident worker and by a bounded stream of at least kRowSightings rounds per set.  A shorter
+    // launch shows a workgroup no shape often enough to build a row that pays back — a window of twenty tickets is two rounds — and
+    // would pay the probe and the sighting of every decision for nothing (measured: 414.9 against 437.8 M decisions/s, medians of
+    // seven, before this condition).  Merged layout only (the driver step of a row decision is the merged one).
+    // (per wavefront, and switched off for good by a wavefront that finds the directory full before its workgroup has built any row:
+    //  a queue whose shapes do not repeat would otherwise pay the probe for every decision — measured on a stream of 2 000 tickets in
+    //  which every record has its own executor request: 960 against 1 032 M decisions/s, medians, before this guard)
+    bool rows_live = kRowsOn && merged &&
+                           (W.leave_after == 0ull || W.leave_after - W.first_ticket >= (unsigned long long)rows::kRowSightings * W.sets);
     if (wave == 0) {  // the tables do not change while the worker lives
         const Group0 g = load_group0(V, O, lane);
         s_g0[0][lane] = (unsigned long long)g.m0;
@@ -526,6 +618,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
             int32_t app_k = 0;
             uint64_t app_off = 0;
             bool decided = false;
+            int build_row = -1;  // SHAPE ROWS: the directory entry whose row this wavefront builds behind its decision
             const uint32_t* placed = nullptr;  // kZoned: the winner's placement, slot ids
             if constexpr (kNarrow) {
                 NarrowApp napp;
@@ -533,8 +626,81 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                 // (asked in this order, the sparse view's size is wanted only for a gang of gpu executors — and read there, from the
                 //  argument segment: OPERANDS)
                 auto sparse_serves = [&]() { return worker_kernargs_here()->G.n_x != 0u && O.d_identity; };
-                if (narrow_table && scale_record(wrec, lane, unit_l, rcp_l, napp) &&
-                    !(napp.exe2 > 0 && napp.k > 0 && sparse_serves())) {
+                if (narrow_table && scale_record(wrec, lane, unit_l, rcp_l, napp)) {
+                if constexpr (kRowsOn) {
+                    // SHAPE ROWS: one lane-parallel probe of the directory (lane l = entry l), then by the entry's word — READY: the
+                    // row decides, or says nothing and the decision below runs as ever; COUNTING: one sighting, and the wavefront
+                    // whose sighting is the kRowSightings-th builds the row behind its own decision; BUILDING: "not there"; no entry:
+                    // one attempt to claim an empty one.  Nothing here waits for another wavefront.  Gangs of gpu executors included.
+                    if (rows_live && napp.k > 0) {
+                        RowsLds& R = s_rows[0];
+                        int rl = lane;
+                        GF_HERE(rl);
+                        uint32_t st = rows::kEmpty;
+                        bool same = false;
+                        if ((uint32_t)rl < kRowsN) {
+                            st = __hip_atomic_load(&R.dir[rl], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                            // (the three key words requested together, compared without short cuts: one LDS wait, not three)
+                            const int32_t k0 = R.key[0][rl], k1 = R.key[1][rl], k2 = R.key[2][rl];
+                            same = (bool)((int)rows::dir_has_key(st) & (int)(k0 == napp.exe0) & (int)(k1 == napp.exe1) & (int)(k2 == napp.exe2));
+                        }
+                        const uint64_t hit = __ballot(same);
+                        bool served = false;
+                        if (hit) {
+                            const int e = __ffsll((unsigned long long)hit) - 1;
+                            const uint32_t ste = read_lane(st, e);
+                            if (rows::dir_ready(ste)) {
+                                const RowDriver rd = wave_row_driver(VN, O, napp, g0n_regs, lane);
+                                if (rd.found) {
+                                    // the driver's slot keeps c_ds for this shape; every other entry is the row's (lanes behind the
+                                    // row's count hold capacity 0 and a slot no driver has)
+                                    const int32_t c_ds = read_lane(cap3(rd.d0 - napp.drv0, rd.d1 - napp.drv1, rd.d2 - napp.drv2, napp), rd.fl);
+                                    const int32_t cp = rows::entry_cap(R.slot[e][rl], R.cap[e][rl], rd.ds, c_ds);
+                                    const uint32_t node = R.node[e][rl];
+                                    const int32_t incl = wave_inclusive_scan(cp);
+                                    if (rows::served((int64_t)read_lane(incl, kWave - 1), napp.k)) {
+                                        const int64_t start = (int64_t)(incl - cp);
+                                        emit_runs((direct ? exec_nodes : priv) + napp.exec_off, start, rows::run_of(start, cp, napp.k), node,
+                                                  lane, direct);
+                                        app_k = napp.k;
+                                        app_off = napp.exec_off;
+                                        dec.feasible = true;
+                                        dec.ds = rd.ds;
+                                        dec.pass1 = 0;
+                                        dec.ds_node = rd.node;
+                                        decided = served = true;
+                                    }
+                                }
+                            } else if (rows::dir_counting(ste)) {
+                                uint32_t old = 0;
+                                if (lane == 0) old = __hip_atomic_fetch_add(&R.dir[e], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                if (rows::dir_sighting_builds((uint32_t)__builtin_amdgcn_readfirstlane(old))) build_row = e;
+                            }
+                        } else {
+                            const uint64_t empty = __ballot((uint32_t)rl < kRowsN && st == rows::kEmpty);
+                            // (an entry whose key is still being written may be this very shape's: no second entry beside it —
+                            //  the shape is seen again soon enough; so is the shape of a lost race)
+                            const uint64_t claimed = __ballot(st == rows::kClaimed);
+                            if (empty == 0ull && claimed == 0ull &&
+                                __hip_atomic_load(&s_row_stat[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0ull)
+                                rows_live = false;
+                            if (empty != 0ull && claimed == 0ull && lane == 0) {
+                                const int e = __ffsll((unsigned long long)empty) - 1;
+                                uint32_t expect = rows::kEmpty;
+                                if (__hip_atomic_compare_exchange_strong(&R.dir[e], &expect, rows::kClaimed, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                                         __HIP_MEMORY_SCOPE_WORKGROUP)) {
+                                    R.key[0][e] = napp.exe0;
+                                    R.key[1][e] = napp.exe1;
+                                    R.key[2][e] = napp.exe2;
+                                    __hip_atomic_store(&R.dir[e], rows::kFirstSighting, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                                }
+                            }
+                        }
+                        if (lane == 0)
+                            __hip_atomic_fetch_add(&s_row_stat[served ? 1 : 2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
+                if (!decided && !(napp.exe2 > 0 && napp.k > 0 && sparse_serves())) {
                     Group0T<int32_t> g0n = g0n_regs;
                     if constexpr (!kG0Regs) {
                         g0n.m0 = s_g0n[0][lane];
@@ -550,6 +716,7 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                     // (a driver found behind the first chunk: its node id from its record, like every other id of this decision)
                     if (dec.feasible && dec.ds_node == GF_NO_NODE) dec.ds_node = VN.node_of(dec.ds);
                     decided = true;
+                }
                 }
             }
             if (__builtin_expect(!decided, !kNarrow)) {
@@ -600,6 +767,54 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
                 const unsigned long long hi = (unsigned long long)(dec.feasible ? (uint32_t)app_k : 0u) | (1ull << 32);
                 __hip_atomic_store(reinterpret_cast<unsigned long long*>(results + a) + lane, lane == 0 ? lo : hi, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_SYSTEM);
+            }
+            if constexpr (kRowsOn) {
+                if (__builtin_expect(build_row >= 0, 0)) {
+                    // BUILD: one scan of the narrow records over the executor order — chunk maxima and candidate words as skips —
+                    // for this record's shape (scaled again from the record: nothing of it was kept across the decision), every
+                    // qualifying lane writes its entry straight to row[fill + rank]; until 64 entries or the end of the order.
+                    // Inline, not a call: a real call gives the kernel a stack (scratch) and the ABI's registers.
+                    NarrowApp b;
+                    (void)scale_record(wrec, lane, unit_l, rcp_l, b);
+                    b.k = rows::kCapClamp;
+                    RowsLds& R = s_rows[0];
+                    int rl = lane;
+                    GF_HERE(rl);
+                    R.slot[build_row][rl] = GF_NO_NODE;  // (no driver has this slot; capacity 0)
+                    R.node[build_row][rl] = GF_NO_NODE;
+                    R.cap[build_row][rl] = 0;
+                    const uint32_t xc = (O.n_x + kWave - 1) / kWave;
+                    const uint64_t lt_mask = (1ull << lane) - 1ull;
+                    uint32_t fill = 0;
+                    for (uint32_t g = 0; g * kWave < xc && fill < rows::kRowLen; ++g) {
+                        uint64_t cand;
+                        uint64_t m = chunk_group_mask<false>(VN, g, xc, b.exe0, b.exe1, b.exe2, lane, cand);
+                        while (m != 0ull && fill < rows::kRowLen) {
+                            const int bit = __ffsll((unsigned long long)m) - 1;
+                            const uint32_t c = g * kWave + (uint32_t)bit;
+                            m &= m - 1;
+                            const uint32_t j = c * kWave + lane;
+                            const uint64_t in_m = (uint64_t)read_lane((int64_t)cand, bit) & low_lanes(chunk_len(O.n_x, c * kWave, kWave));
+                            int32_t a0 = 0, a1 = 0, a2 = 0;
+                            uint32_t node = 0;
+                            if (lane_in(in_m)) VN.load(j, a0, a1, a2, node);
+                            const uint64_t fm = ge3_mask(a0, a1, a2, b.exe0, b.exe1, b.exe2) & in_m;
+                            const uint32_t pos = fill + (uint32_t)__popcll((unsigned long long)(fm & lt_mask));
+                            if (lane_in(fm) && pos < rows::kRowLen) {
+                                R.slot[build_row][pos] = j;
+                                R.node[build_row][pos] = node;
+                                R.cap[build_row][pos] = cap3(a0, a1, a2, b);
+                            }
+                            fill += (uint32_t)__popcll((unsigned long long)fm);
+                        }
+                    }
+                    // every lane's entries are in LDS before the word says READY (readers: the acquire load of the probe)
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+                    if (lane == 0) {
+                        __hip_atomic_fetch_add(&s_row_stat[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        __hip_atomic_fetch_or(&R.dir[build_row], rows::kReadyBit, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
+                }
             }
             ++mine;
             if constexpr (kRecords) {  // the next application of this round, whoever's it would have been
@@ -670,5 +885,13 @@ __global__ __launch_bounds__(kWave* kWorkerWaves, 4) void fit_worker_kernel(Node
         rows = rows_n;
     }
     if (lane == 0) __hip_atomic_store(&s_round[wave], kRoundGone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // never in anybody's way
+    if constexpr (kRowsOn) {  // the last wavefront to leave adds the workgroup's row counts to the context's totals, once
+        uint32_t left = 0;
+        if (lane == 0) left = __hip_atomic_fetch_add(&s_left, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if ((uint32_t)__builtin_amdgcn_readfirstlane(left) == (uint32_t)kWorkerWaves - 1u && lane < 3) {
+            const unsigned long long n = __hip_atomic_load(&s_row_stat[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (n != 0ull) __hip_atomic_fetch_add(&W.dev->rows[lane], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 

@@ -26,7 +26,8 @@ INCLUDE = os.path.join(_REPO_ROOT, "include")
 _SOURCES = ["gangfit_kernels.hip", "gangfit_snapshot.hip", "gangfit_api.cpp", "gangfit_api_snapshot.cpp", "gangfit_api_fit.cpp",
             "gangfit_api_worker.cpp", "gangfit_api_group.cpp", "gangfit_api_scan.cpp", "gangfit_api_eff.cpp"]
 _HEADERS = [os.path.join(CSRC, "gangfit_device.h"), os.path.join(CSRC, "gangfit_slot_layout.h"), os.path.join(CSRC, "gangfit_label_plan.h"),
-            os.path.join(CSRC, "gangfit_worker_rounds.h"), os.path.join(CSRC, "gangfit_chain_lds.h"),
+            os.path.join(CSRC, "gangfit_worker_rounds.h"), os.path.join(CSRC, "gangfit_worker_rows.h"),
+            os.path.join(CSRC, "gangfit_chain_lds.h"),
             os.path.join(INCLUDE, "gangfit.h")]
 
 

@@ -564,6 +564,12 @@ class Context:
         self._check(self._lib.gf_worker_geometry(self._h, out))
         return int(out[0]), int(out[1])
 
+    def worker_row_stats(self):
+        """Shape rows of the tightly-pack worker, totals of the launches that have left the device (worker_stop first)."""
+        out = (C.c_uint64 * 3)()
+        self._check(self._lib.gf_worker_row_stats(self._h, out))
+        return {"built": int(out[0]), "served": int(out[1]), "fell_back": int(out[2])}
+
     def call_phases(self):
         """Host-clock phases (us) of the last blocking independent gf_fit_batch on the zero-copy path."""
         out = (C.c_double * 5)()

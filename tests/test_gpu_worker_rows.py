@@ -7,13 +7,12 @@ import numpy as np
 import pytest
 
 import gangfit
-from gangfit import _native as N
 from gangfit import workloads as wl
+# (the launch's answers, the stream and the hand-made cluster are shared with tests/test_gpu_worker_rows_edges.py: one copy)
+from worker_rows_cases import apps_of as _apps, edge_cluster as _edge_cluster, stream as _stream
 
 pytestmark = pytest.mark.gpu
 
-IND, TIGHT = gangfit.GF_MODE_INDEPENDENT, gangfit.GF_ALGO_TIGHTLY_PACK
-HOST_OUTPUTS = N.GF_WORKER_HOST_OUTPUTS
 GIB = 1 << 30
 K_ROWS, K_SIGHTINGS, GF_MAX_K = 40, 4, 1 << 20  # gangfit_worker_rows.h
 
@@ -21,67 +20,6 @@ K_ROWS, K_SIGHTINGS, GF_MAX_K = 40, 4, 1 << 20  # gangfit_worker_rows.h
 def _install(ctx, avail, sched, d_order, x_order):
     ctx.set_snapshot(avail, sched)
     ctx.set_orders(d_order, x_order)
-
-
-def _launch_answers(ctx, apps):
-    """(d_apps, results, placements, mask of the placement words of feasible records) of one launch on `apps` (with offsets)."""
-    import torch
-
-    dev = torch.device("cuda:0")
-    total_k = int(apps["k"].sum())
-    d_apps = torch.from_numpy(apps.view(np.uint8).copy()).to(dev)
-    res = torch.zeros(len(apps) * 16, dtype=torch.uint8, device=dev)
-    exe = torch.zeros(total_k + 1, dtype=torch.int32, device=dev)
-    torch.cuda.synchronize()
-    ctx.fit_batch_dev(IND, TIGHT, len(apps), d_apps.data_ptr(), res.data_ptr(), exe.data_ptr(), total_k)
-    torch.cuda.synchronize()
-    feas = res.cpu().numpy().view(N.RESULT_DTYPE)["has_capacity"] != 0
-    mask = np.zeros(total_k + 1, dtype=bool)
-    for a in np.nonzero(feas)[0]:
-        mask[int(apps["exec_off"][a]): int(apps["exec_off"][a]) + int(apps["k"][a])] = True
-    return d_apps, res, exe, torch.from_numpy(mask).to(dev), feas
-
-
-def _stream(ctx, tickets, host_outputs=False):
-    """Posts the tickets (a list of record arrays; identical objects share one upload and one launch) as ONE stream, waits, stops
-    the worker, compares every ticket with the launch on its records.  Returns the feasibility vectors per distinct array."""
-    import torch
-
-    dev = torch.device("cuda:0")
-    known = {}
-    for t in tickets:
-        if id(t) not in known:
-            known[id(t)] = _launch_answers(ctx, t)
-    res, exe, batches = [], [], []
-    for t in tickets:
-        d_apps, _, w_exe, _, _ = known[id(t)]
-        if host_outputs:
-            res.append(torch.zeros(len(t) * 16, dtype=torch.uint8).pin_memory())
-            exe.append(torch.zeros(len(w_exe), dtype=torch.int32).pin_memory())
-        else:
-            res.append(torch.zeros(len(t) * 16, dtype=torch.uint8, device=dev))
-            exe.append(torch.zeros(len(w_exe), dtype=torch.int32, device=dev))
-        batches.append((len(t), d_apps.data_ptr(), res[-1].data_ptr(), exe[-1].data_ptr(), len(w_exe) - 1, HOST_OUTPUTS if host_outputs else 0))
-    torch.cuda.synchronize()
-    first = ctx.worker_submit_dev(TIGHT, batches)
-    ctx.worker_wait(first, len(tickets))
-    ctx.worker_stop()
-    torch.cuda.synchronize()
-    bad = []
-    for i, t in enumerate(tickets):
-        _, w_res, w_exe, mask, _ = known[id(t)]
-        if not torch.equal(res[i].to(dev), w_res):
-            bad.append((i, "results"))
-        if not torch.equal(exe[i].to(dev)[mask], w_exe[mask]):
-            bad.append((i, "placements"))
-    assert not bad, bad[:8]
-    return {k: v[4] for k, v in known.items()}
-
-
-def _apps(drv, exe, k):
-    apps, _ = gangfit.with_offsets(gangfit.make_apps(np.asarray(drv, dtype=np.int64), np.asarray(exe, dtype=np.int64),
-                                                     np.asarray(k, dtype=np.int32)))
-    return apps
 
 
 @pytest.fixture(scope="module")
@@ -133,19 +71,6 @@ def test_a_stream_builds_rows_and_then_hits_them(small, sets, bps):
         assert st["served"] * 2 >= n_tickets * len(apps), st
     finally:
         ctx.close()
-
-
-def _edge_cluster():
-    """130 nodes in priority order (memory, then cpu, then index): two overcommitted nodes, 118 nodes of 8 cpu / 32 GiB, ten of
-    16 cpu / 64 GiB at the end.  Slots = positions: 0, 1 negative; 2 .. 119 small; 120 .. 129 big."""
-    avail = np.zeros((130, 3), dtype=np.int64)
-    avail[:2] = [-1000, -GIB, 0]
-    avail[2:120] = [8000, 32 * GIB, 0]
-    avail[120:] = [16000, 64 * GIB, 0]
-    sched = np.abs(avail) + np.array([1000, GIB, 0])
-    order = wl.reference_node_order(avail)
-    assert np.array_equal(order, np.arange(130))
-    return avail, sched, order
 
 
 def test_edges_of_a_row_on_a_hand_made_cluster():

@@ -3,7 +3,8 @@ header is pure code, so a small extern "C" shim (tests/worker_rows_shim.cpp) com
 libgangfit.so.
 
 What is proven here is the row DECISION (entry_cap, served, run_of).  The rows themselves are cut by the definition in the shim, not
-by the kernel's build — its chunk skips and its `fill + rank` placement are covered by tests/test_gpu_worker_rows.py only.
+by the kernel's build — its chunk skips and its `fill + rank` placement are covered by tests/test_gpu_worker_rows.py and
+tests/test_gpu_worker_rows_edges.py only.
 
 Per application: the row of its executor shape is cut from the capacities of the executor order WITHOUT a driver (numpy, from the
 definition: min over the dimensions of floor(avail / request), 0 on a node that is short anywhere, a zero request never limits,
@@ -11,83 +12,38 @@ clamped at GF_MAX_K), the driver is the first node of the driver order that hold
 with the driver reserved.  Whenever the row says SERVED, driver and placements are the oracle's; when it says NOT SERVED nothing is
 claimed — and that happens for at most a quarter of the cases."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import worker_rows_cases as wc
 from gangfit import workloads as wl
 from oracle import binding as ob
+from worker_rows_cases import U32, I32, _p
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-U32, I32 = ctypes.c_uint32, ctypes.c_int32
-NO_SLOT = 0xFFFFFFFF
+# (the numpy row model — _caps, the row by definition, the first fitting driver, c_ds — lives in tests/worker_rows_cases.py: one copy
+#  for this file and for tests/test_worker_rows_cases_cpu.py)
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    so = tmp_path_factory.mktemp("worker_rows") / "worker_rows_shim.so"
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-shared", "-fPIC", "-I", os.path.join(REPO, "k8s-spark-scheduler_amd", "csrc"),
-                           os.path.join(REPO, "tests", "worker_rows_shim.cpp"), "-o", str(so)])
-    lib = ctypes.CDLL(str(so))
-    lib.wrow_consts.restype = None
-    lib.wrow_build.restype = U32
-    lib.wrow_decide.restype = ctypes.c_int
-    lib.wrow_directory_walk.restype = None
-    return lib
-
-
-def _p(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
+    return wc.compile_shim(tmp_path_factory.mktemp("worker_rows"))
 
 
 def _consts(shim):
-    c = np.zeros(4, dtype=np.uint32)
-    shim.wrow_consts(_p(c))
-    return [int(x) for x in c]
-
-
-def _caps(avail_rows, exe, clamp):
-    a = avail_rows.astype(np.int64)
-    q = np.full(a.shape, np.iinfo(np.int64).max, dtype=np.int64)
-    for d in range(3):
-        if exe[d] > 0:
-            q[:, d] = np.floor_divide(a[:, d], int(exe[d]))
-    c = np.minimum(q.min(axis=1), clamp)
-    c[(a < 0).any(axis=1)] = 0
-    return np.maximum(c, 0).astype(np.int32)
+    return wc.consts(shim)
 
 
 def _rows_against_oracle(shim, avail, d_order, x_order, drv, exe, k):
-    row_len, _, _, clamp = _consts(shim)
     oapps = ob.make_apps(drv, exe, k, np.zeros(len(k), dtype=np.uint32))
     ref = ob.fit_independent(0, avail, oapps, d_order, x_order)
-    slot_node = np.ascontiguousarray(x_order, dtype=np.uint32)
-    pos_of = {int(n): j for j, n in enumerate(x_order)}
     served = 0
-    rows = {}
-    for a in range(len(k)):
-        key = tuple(int(x) for x in exe[a])
-        if key not in rows:
-            caps = _caps(avail[x_order], exe[a], clamp)
-            slot, node, cap = np.zeros(row_len, np.uint32), np.zeros(row_len, np.uint32), np.zeros(row_len, np.int32)
-            hdr = shim.wrow_build(U32(len(x_order)), _p(caps), _p(slot_node), _p(slot), _p(node), _p(cap))
-            assert hdr == min(row_len, int((caps >= 1).sum()))
-            rows[key] = (slot, node, cap, hdr)
-        slot, node, cap, hdr = rows[key]
-        fits = (avail[d_order] >= drv[a]).all(axis=1)
-        if not fits.any():
-            continue  # (no driver: the kernel's driver step finds none and the old path answers)
-        dn = int(d_order[int(np.argmax(fits))])
-        ds = pos_of.get(dn, NO_SLOT)
-        c_ds = int(_caps((avail[dn] - drv[a])[None, :], exe[a], clamp)[0])
-        out = np.full(max(int(k[a]), 1), NO_SLOT, dtype=np.uint32)
-        if shim.wrow_decide(_p(slot), _p(node), _p(cap), U32(hdr), U32(ds), I32(c_ds), I32(int(k[a])), _p(out)):
+    for a, (dn, ok, nodes) in enumerate(wc.row_model(shim, avail, d_order, x_order, drv, exe, k)):
+        if ok:
             served += 1
             feasible, r_dn, r_nodes = ref.placement(a)
             assert feasible and r_dn == dn, (a, dn, r_dn)
-            assert np.array_equal(r_nodes, out[:int(k[a])]), a
+            assert np.array_equal(r_nodes, nodes), a
     return served
 
 

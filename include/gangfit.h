@@ -598,6 +598,42 @@ typedef struct gf_find_result {
 int gf_find_nodes(gf_ctx *ctx, int chained, uint32_t n_req, const int64_t *exe, const int32_t *k, gf_find_result *results,
                   uint32_t *exec_nodes, uint64_t exec_nodes_cap, uint32_t *reserved_adds);
 
+/* The same findNodes answered from the RESIDENT cluster, for the stale applications of every instance group in one call and with
+ * nothing installed (syncResourceReservationsAndDemands runs inside Predicate, in front of the driver Filter: an install there
+ * drops the Filter's chain cache, recorded graphs and resident worker).  The reconciler's table (availableResourcesPerInstanceGroup,
+ * failover.go:286-323) is what the device already holds:
+ *   A[n]  = allocatable - (resident usage sum + resident overhead) per dimension, the available column of every cluster entry point;
+ *   O_q   = the nodes of row req_set[q] with GF_NODE_READY set and GF_NODE_UNSCHEDULABLE clear in the flags of gf_cluster_set, in
+ *           ascending create_rank.
+ * results[q], request q's slice of exec_nodes and row q of reserved_adds equal what gf_find_nodes returns on a context that was
+ * given gf_snapshot_set(A) and gf_orders_set(NULL, 0, O_q); node indices are the cluster's.  The over-add of :424-427 is kept
+ * ((placed + 1) x exe on a node left because it is full, placed x exe on the node where k was reached), and a node that holds
+ * nothing is still visited and charged one add.
+ *   n_sets, set_words, req_set  rows as in gf_cluster_executor_fit: ceil(n_nodes / 64) words each, a row = one instance group
+ *                 (schedulableNodes[instanceGroup], :296-314); n_sets == 0 with NULL pointers = every node
+ *   create_rank   n_nodes entries, a permutation of 0 .. n_nodes - 1; rank 0 = the node the reconciler visits first.  The reference
+ *                 sorts newest creation timestamp first with an unstable sort.Slice (:292-294): the host breaks the ties, the
+ *                 library takes the order as given.  The one O(n_nodes) array the call moves.
+ *   exe, k        as in gf_find_nodes: requests in [0, 2^62), k in [0, GF_MAX_K]
+ *   chained != 0  the requests of one row run in ascending q and each sees A minus the `reserved` maps of the earlier requests of
+ *                 that row (`r.availableResources[instanceGroup].Sub(reservedResources)`, :159).  Requests of different rows do
+ *                 not interact (the reference keeps one map per group), so the rows two requests name must be equal or disjoint.
+ *                 chained == 0: every request sees A.
+ *   residual_out  nullable, n_nodes x 3 row-major: A after every subtraction of a chained call, for every node of the cluster (an
+ *                 untouched node keeps A[n]); with chained == 0 it is A
+ *   reserved_adds nullable, n_req x n_nodes, as in gf_find_nodes
+ * Leaves untouched: the installed snapshot, zones and orders, all three words of gf_generation, the chain cache, recorded graphs,
+ * gf_residual_get's table (and whether it is valid), the resident usage and overhead, the resident worker.  Blocking; its device
+ * buffers are its own.  n_req == 0 is GF_OK.  A multi-device context answers from its first device.
+ * Refusals (nothing changes, the outputs stay as preset): no gf_cluster_set, a view, resident usage or overhead unusable after a
+ * failed update: GF_ERR_STATE; create_rank NULL or not a permutation, a request value outside [0, 2^62), k outside [0, GF_MAX_K],
+ * req_set[q] >= n_sets, a set bit at or beyond n_nodes, req_set (or set_words) NULL with n_sets > 0, rows of a chained call that
+ * overlap without being equal, exe, k or results NULL: GF_ERR_INVALID; exec_nodes_cap below the sum of k: GF_ERR_CAPACITY. */
+int gf_cluster_find_nodes(gf_ctx *ctx, int chained, uint32_t n_sets, const uint64_t *set_words, const uint32_t *create_rank,
+                          uint32_t n_req, const int64_t *exe, const int32_t *k, const uint32_t *req_set,
+                          gf_find_result *results, uint32_t *exec_nodes, uint64_t exec_nodes_cap,
+                          uint32_t *reserved_adds, int64_t *residual_out);
+
 /* ---- node-range sharding of an INDEPENDENT batch across the GPUs of one box ----
  * One gf_ctx per GPU, each given the same snapshot and orders; gf_shard_set tells it which contiguous range of the
  * priority order it owns (ranges are cut on 64-slot boundaries of the merged driver/executor order; GF_ERR_UNSUPPORTED

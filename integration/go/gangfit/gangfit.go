@@ -981,6 +981,124 @@ func (c *Context) ExecutorFitOnResidentCluster(minimalFragmentation bool, execut
 	return names, nil
 }
 
+// FindNodesResident is the reconciler's findNodes (internal/extender/failover.go:412-436, the chain's Sub :159) for the stale
+// applications of EVERY instance group in one call, answered from the RESIDENT cluster (ClusterSet / OverheadUpdate / UsageApply)
+// instead of one installed snapshot per group (include/gangfit.h, gf_cluster_find_nodes): nothing is installed, so the driver Filter
+// this reconcile runs in front of keeps its snapshot, chain cache and resident worker.  setWords holds nSets rows of
+// ceil(nNodes / 64) words, one row per instance group (schedulableNodes[instanceGroup], :296-314; readiness is tested on the
+// device); reqSet[q] is the row of request q; createRank[n] is the position at which the reconciler visits node n (newest creation
+// timestamp first, :292-294; the caller breaks the ties).  The requests of one row run in order and each sees the table after the
+// `reserved` maps of the earlier ones.  Returns, per request, the node names and the `reserved` map rebuilt along the row's own
+// order as the header describes; the caller subtracts it from availableResources[instanceGroup].  flags[n] are the flags given to
+// ClusterSet (the row's order is its ready, schedulable members by createRank).  On any error install per group with
+// FindNodesForStaleApplications, as before.  Unverified here (no Go toolchain); tests/test_gpu_cluster_find_nodes.py drives the C
+// entry point.
+func (c *Context) FindNodesResident(counts []int, executor []*resources.Resources, nSets int, setWords []uint64, reqSet []uint32,
+	createRank []uint32, flags []uint32) (nodes [][]string, reserved []resources.NodeGroupResources, err error) {
+	if len(counts) == 0 {
+		return nil, nil, nil
+	}
+	if len(executor) != len(counts) || (nSets > 0 && len(reqSet) != len(counts)) {
+		return nil, nil, fmt.Errorf("gangfit: %d counts, %d executors, %d set numbers", len(counts), len(executor), len(reqSet))
+	}
+	n := len(c.names)
+	if len(createRank) != n || len(flags) != n {
+		return nil, nil, fmt.Errorf("gangfit: %d nodes, %d ranks, %d flags", n, len(createRank), len(flags))
+	}
+	exe := make([]int64, 0, 3*len(counts))
+	ks := make([]C.int32_t, len(counts))
+	total := 0
+	for q, k := range counts {
+		e, err := canonical(executor[q])
+		if err != nil {
+			return nil, nil, err
+		}
+		if k <= 0 || k > C.GF_MAX_K {
+			return nil, nil, ErrNotRepresentable
+		}
+		exe = append(exe, e[0], e[1], e[2])
+		ks[q] = C.int32_t(k)
+		total += k
+	}
+	var words *C.uint64_t
+	var sets *C.uint32_t
+	if nSets > 0 {
+		if len(setWords) > 0 {
+			words = (*C.uint64_t)(unsafe.Pointer(&setWords[0]))
+		}
+		sets = p32(reqSet)
+	}
+	res := make([]C.gf_find_result, len(counts))
+	placed := make([]uint32, total+1)
+	c.mu.Lock()
+	if rc := C.gf_cluster_find_nodes(c.ctx, 1, C.uint32_t(nSets), words, p32(createRank), C.uint32_t(len(counts)), p64(exe), &ks[0], sets,
+		&res[0], p32(placed), C.uint64_t(total), nil, nil); rc != C.GF_OK {
+		err := c.err(rc)
+		c.mu.Unlock()
+		return nil, nil, err
+	}
+	c.mu.Unlock()
+	// position -> node, then every row's own order on first use
+	visit := make([]uint32, n)
+	for node, p := range createRank {
+		visit[p] = uint32(node)
+	}
+	W := (n + 63) / 64
+	orders := map[uint32][]uint32{}
+	orderOf := func(row uint32) []uint32 {
+		if o, ok := orders[row]; ok {
+			return o
+		}
+		o := []uint32{}
+		for _, node := range visit {
+			if flags[node]&C.GF_NODE_READY == 0 || flags[node]&C.GF_NODE_UNSCHEDULABLE != 0 {
+				continue
+			}
+			if nSets == 0 || setWords[int(row)*W+int(node>>6)]>>(node&63)&1 != 0 {
+				o = append(o, node)
+			}
+		}
+		orders[row] = o
+		return o
+	}
+	off := 0
+	for q, k := range counts {
+		got := placed[off : off+int(res[q].placed)]
+		names := make([]string, len(got))
+		mult := map[uint32]int64{}
+		for i, ix := range got {
+			names[i] = c.names[ix]
+			mult[ix]++
+		}
+		rmap := resources.NodeGroupResources{}
+		if res[q].last_node != C.GF_NO_NODE {
+			row := uint32(0)
+			if nSets > 0 {
+				row = reqSet[q]
+			}
+			for _, ix := range orderOf(row) {
+				adds := mult[ix] + 1
+				last := ix == uint32(res[q].last_node)
+				if last && int(res[q].placed) == k {
+					adds--
+				}
+				r := resources.Zero()
+				for i := int64(0); i < adds; i++ {
+					r.Add(executor[q])
+				}
+				rmap[c.names[ix]] = r
+				if last {
+					break
+				}
+			}
+		}
+		nodes = append(nodes, names)
+		reserved = append(reserved, rmap)
+		off += k
+	}
+	return nodes, reserved, nil
+}
+
 // WorkerStop makes the resident worker leave the device now (it leaves by itself when idle).
 func (c *Context) WorkerStop() error {
 	c.mu.Lock()

@@ -331,6 +331,12 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->d_xs_out.release();
     ctx->h_xs_req.release();
     ctx->h_xs_out.release();
+    ctx->d_cf_i64.release();
+    ctx->d_cf_u32.release();
+    ctx->d_cf_sets.release();
+    ctx->d_cf_res.release();
+    ctx->d_cf_exec.release();
+    ctx->d_cf_adds.release();
     ctx->d_delta_i64.release();
     ctx->d_delta_u32.release();
     ctx->d_bi64.release();

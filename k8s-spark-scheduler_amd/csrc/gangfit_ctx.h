@@ -384,6 +384,14 @@ struct gf_ctx {
     PinnedBuf<uint64_t> h_xs_req;
     PinnedBuf<uint32_t> h_xs_out;
 
+    // gf_cluster_find_nodes (gangfit_api_scan.cpp): the working table (3n) | requests (3r) | placement offsets (r) | list bases;
+    // create_rank (n) | perm (n) | the used rows and the grouped requests | the rows' lists; the set rows; results, placements and
+    // the `reserved` maps.  Its own: gf_find_nodes' buffers and gf_residual_get's table are not touched.
+    DeviceBuf<int64_t> d_cf_i64;
+    DeviceBuf<uint32_t> d_cf_u32, d_cf_exec, d_cf_adds;
+    DeviceBuf<uint64_t> d_cf_sets;
+    DeviceBuf<gf_find_result> d_cf_res;
+
     // gf_snapshot_build
     DeviceBuf<int64_t> d_bi64;  // alloc | overhead | usage | avail | sched (3n each) | keys_a | keys_b (n each) | res_req (3r) | zone_sum
     DeviceBuf<uint32_t> d_bu32;  // zone | name_rank | perm_a | perm_b (n each) | res_node (r) | zone_order | zone_rank | ... (BuildScratch)

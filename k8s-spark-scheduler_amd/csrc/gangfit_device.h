@@ -672,6 +672,36 @@ struct ExecScanArgs {
     uint32_t* out;                // n_req node indices
 };
 hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ExecScanArgs& args, hipStream_t stream);
+// findNodes of the failover reconciler on the resident cluster (gangfit_find_scan.inc; gf_cluster_find_nodes): request q walks the
+// ready, schedulable nodes of its row in ascending create_rank on available = alloc - (usage + over), exactly as find_nodes_kernel
+// walks the executor order of an installed snapshot.  The entry point names the rows some request uses (`used rows`: under
+// `chained`, rows of equal content are one used row and two used rows share no node) and groups the requests by used row, stable
+// in q.  Three launches: prepare (perm, work), order (every used row's list in ord), walk.  Reads nothing of the installed snapshot.
+struct FindScanArgs {
+    const int64_t* alloc;         // 3 * n_nodes: cpu | mem | gpu (gf_cluster_set)
+    const int64_t* over;          // 3 * n_nodes resident overhead, or nullptr: none
+    const int64_t* usage;         // 3 * n_nodes resident usage sums (gf_usage_apply)
+    const uint32_t* flags;        // n_nodes: the cluster's default GF_NODE_* flags
+    const uint32_t* create_rank;  // n_nodes, a permutation (the entry point checks): the position at which a node is visited
+    const uint64_t* set_words;    // n_sets * n_words, or nullptr: every node.  No bit at or beyond n_nodes (the entry point checks)
+    const uint32_t* row_set;      // n_rows: the row of set_words a used row stands for (with set_words)
+    const uint64_t* row_base;     // n_rows: where the used row's list starts in ord; the next base is at least its popcount further
+    const uint32_t* row_req;      // n_rows + 1: used row r owns req_list[row_req[r] .. row_req[r + 1])
+    const uint32_t* req_list;     // n_req: the requests grouped by used row, ascending q inside a row
+    const uint32_t* req_row;      // n_req: request q's used row
+    const int64_t* exe;           // n_req * 3
+    const int32_t* k;             // n_req counts in [0, GF_MAX_K]
+    const uint64_t* exec_off;     // n_req: where request q's placements start in exec_nodes
+    uint32_t n_nodes, n_words /* set by the launcher */, n_rows, n_req;
+    uint32_t* perm;               // n_nodes: position -> node (written by prepare)
+    uint32_t* ord;                // the used rows' lists
+    uint32_t* row_len;            // n_rows: the lists' lengths (written by order)
+    int64_t* work;                // 3 * n_nodes: the call's working table, cpu | mem | gpu by node; the residual afterwards
+    gf_find_result* results;      // n_req
+    uint32_t* exec_nodes;         // sum of k
+    uint32_t* adds_out;           // n_req * n_nodes (zeroed by the caller), or nullptr
+};
+hipError_t launch_cluster_find_nodes(bool chained, const FindScanArgs& args, hipStream_t stream);
 // The slot tables of the merged layout built from the device-resident snapshot columns (what gf_orders_set builds on the
 // host): every node gets the slot of its position in the priority order.
 struct SnapshotFinalize {

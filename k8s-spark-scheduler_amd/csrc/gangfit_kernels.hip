@@ -1764,6 +1764,7 @@ __global__ __launch_bounds__(kWave* NW) void fit_fifo_chain_kernel(NodeTable T, 
 #include "gangfit_findnodes.inc"
 #include "gangfit_scan.inc"
 #include "gangfit_exec_scan.inc"
+#include "gangfit_find_scan.inc"
 #include "gangfit_filter_eff.inc"
 
 // ------------------------------------------------------------------------------------------------ self-test
@@ -2085,6 +2086,29 @@ hipError_t launch_cluster_executor_fit(bool minimal_fragmentation, const ExecSca
     args.n_words = (uint32_t)(((uint64_t)a.n_nodes + kWave - 1) / kWave);
     return with_value<true, false>(minimal_fragmentation, [&](auto MF) {
         hipLaunchKernelGGL(cluster_executor_fit_kernel<MF>, dim3(args.n_req), dim3(kWave * kWavesPerBlock), 0, stream, args);
+        return hipGetLastError();
+    });
+}
+
+hipError_t launch_cluster_find_nodes(bool chained, const FindScanArgs& a, hipStream_t stream) {
+    if (a.n_req == 0) return hipSuccess;
+    if (a.n_rows == 0 || a.exe == nullptr || a.k == nullptr || a.exec_off == nullptr || a.results == nullptr || a.exec_nodes == nullptr ||
+        a.row_base == nullptr || a.row_req == nullptr || a.req_list == nullptr || a.req_row == nullptr || a.row_len == nullptr ||
+        (a.set_words != nullptr && a.row_set == nullptr) ||
+        (a.n_nodes > 0 && (a.alloc == nullptr || a.usage == nullptr || a.flags == nullptr || a.create_rank == nullptr ||
+                           a.perm == nullptr || a.ord == nullptr || a.work == nullptr)))
+        return hipErrorInvalidValue;
+    FindScanArgs args = a;
+    args.n_words = (uint32_t)(((uint64_t)a.n_nodes + kWave - 1) / kWave);
+    const dim3 block(kWave * kWavesPerBlock);
+    if (args.n_nodes > 0) {
+        hipLaunchKernelGGL(cluster_find_prepare_kernel, dim3((args.n_nodes + block.x - 1) / block.x), block, 0, stream, args);
+        if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(cluster_find_order_kernel, app_grid(args.n_rows), block, 0, stream, args);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    return with_value<true, false>(chained, [&](auto C) {
+        hipLaunchKernelGGL(cluster_find_nodes_kernel<C>, app_grid(C ? args.n_rows : args.n_req), block, 0, stream, args);
         return hipGetLastError();
     });
 }

@@ -498,6 +498,38 @@ class Context:
                                             N.ptr(adds)))
         return res[:, 0].copy(), res[:, 1].copy(), off, out[:total], adds
 
+    def cluster_find_nodes(self, exe, k, create_rank, sets=None, req_set=None, chained: bool = True, want_adds: bool = False,
+                           want_residual: bool = False):
+        """gf_cluster_find_nodes: findNodes for the stale applications of every instance group in one call, from the columns of
+        set_cluster / overhead_update / usage_apply.  create_rank: (n_nodes,) the position at which the reconciler visits each
+        node (a permutation); sets: (n_sets, n_nodes) truth values, one row per instance group (None = every node); req_set: the
+        row of each request.  Returns (placed, last_node, exec_off, exec_nodes, adds, residual) with node indices of the cluster;
+        adds / residual are None unless asked for.  Installs nothing."""
+        exe = np.ascontiguousarray(exe, dtype=np.int64).reshape(-1, 3)
+        k = np.ascontiguousarray(k, dtype=np.int32).reshape(-1)
+        assert len(exe) == len(k)
+        n = self._cluster_n
+        rank = np.ascontiguousarray(create_rank, dtype=np.uint32).reshape(-1)
+        assert len(rank) == n, "one rank per node of the cluster"
+        words, rs, n_sets = None, None, 0
+        if sets is not None:
+            words = pack_node_sets(sets, n)
+            n_sets = len(words)
+            rs = np.ascontiguousarray(req_set, dtype=np.uint32).reshape(-1)
+            assert len(rs) == len(k), "one set per request"
+        kk = np.clip(k.astype(np.int64), 0, None)
+        off = np.zeros(len(k), dtype=np.uint64)
+        if len(k) > 1:
+            off[1:] = np.cumsum(kk[:-1]).astype(np.uint64)
+        total = int(kk.sum())
+        res = np.zeros((len(k), 2), dtype=np.uint32)
+        out = np.zeros(total + 1, dtype=np.uint32)
+        adds = np.zeros((len(k), n), dtype=np.uint32) if want_adds else None
+        residual = np.zeros((n, 3), dtype=np.int64) if want_residual else None
+        self._check(self._lib.gf_cluster_find_nodes(self._h, int(chained), n_sets, N.ptr(words), N.ptr(rank), len(k), N.ptr(exe),
+                                                    N.ptr(k), N.ptr(rs), N.ptr(res), N.ptr(out), total, N.ptr(adds), N.ptr(residual)))
+        return res[:, 0].copy(), res[:, 1].copy(), off, out[:total], adds, residual
+
     def residual(self) -> np.ndarray:
         out = np.zeros((self.n_nodes, 3), dtype=np.int64)
         self._check(self._lib.gf_residual_get(self._h, N.ptr(out)))

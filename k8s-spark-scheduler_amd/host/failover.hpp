@@ -10,6 +10,7 @@
 // comparison is not taken back (:424-427), and the caller subtracts the whole map (:159).
 #pragma once
 
+#include <map>
 #include <string>
 #include <utility>
 #include <vector>
@@ -40,5 +41,37 @@ FindNodesResult findNodes(gf_ctx* ctx, int executorCount, const Resources& execu
 std::vector<FindNodesResult> findNodesForStaleApplications(gf_ctx* ctx, const std::vector<FindNodesRequest>& requests,
                                                            NodeGroupResources* availableResources,
                                                            const std::vector<Node>& orderedNodes);
+
+// What the resident reconcile sends beside the requests: one bit row per instance group over the flat cluster's node indices
+// (schedulableNodes[instanceGroup], :296-314 — readiness is the device's to test, from the flags of gf_cluster_set) and the
+// position at which the reconciler visits every node: newest creation timestamp first (:292-294; the reference's sort.Slice is
+// unstable, ties here keep the input order).  A group only a request names gets an empty row.
+struct ReconcileRows {
+    std::vector<std::string> groups;    // row -> instance group: the nodes' groups by first appearance, then the requests' own
+    size_t words_per_row = 0;           // ceil(nodes / 64)
+    std::vector<uint64_t> words;        // groups.size() rows
+    std::vector<uint32_t> create_rank;  // node -> position
+    std::vector<uint32_t> visit;        // position -> node
+    std::vector<uint32_t> req_set;      // request -> row
+};
+ReconcileRows buildReconcileRows(const std::vector<std::string>& nodeInstanceGroup, const std::vector<int64_t>& nodeCreationTimestamp,
+                                 const std::vector<std::string>& requestInstanceGroup);
+
+struct FlatCluster;  // extender.hpp
+
+// The reconciler's findNodes for the stale applications of EVERY instance group as ONE gf_cluster_find_nodes call on the resident
+// cluster (include/gangfit.h): nothing is installed, so the driver Filter this reconcile runs in front of keeps its snapshot, chain
+// cache and resident worker.  `cluster` is the flat cluster whose columns, overhead rows and usage the extender's flat Filter keeps
+// on ctx; nodeInstanceGroup / nodeCreationTimestamp hold one entry per node of it, requestInstanceGroup one per request.  Request i
+// sees its group's table after the `Sub` of the earlier requests of that group; every request's `reserved` map is rebuilt from the
+// results as the header describes and subtracted from (*availableResources)[group] like r.availableResources[ig] (:159).
+// On any refusal of the entry point — and for quantities that are not exactly representable — every group is answered by
+// findNodesForStaleApplications on its own ordered nodes (which installs).  *residentRoute (nullable): true when the resident entry
+// point answered.
+std::vector<FindNodesResult> findNodesForStaleApplicationsResident(
+    gf_ctx* ctx, const FlatCluster& cluster, const std::vector<std::string>& nodeInstanceGroup,
+    const std::vector<int64_t>& nodeCreationTimestamp, const std::vector<std::string>& requestInstanceGroup,
+    const std::vector<FindNodesRequest>& requests, std::map<std::string, NodeGroupResources>* availableResources,
+    bool* residentRoute = nullptr);
 
 }  // namespace gangfit::host

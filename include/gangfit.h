@@ -319,11 +319,44 @@ int gf_usage_apply(gf_ctx *ctx, uint32_t n_entries, const uint32_t *res_node, co
  * Blocking with respect to the caller's arrays. */
 int gf_overhead_update(gf_ctx *ctx, uint32_t n_rows, const uint32_t *node, const int64_t *over_cpu_milli,
                        const int64_t *over_mem_bytes, const int64_t *over_gpu);
+/* The node rows of the resident cluster, changed in place: a node that joins, leaves, is cordoned, turns NotReady or whose
+ * allocatable changes no longer costs a gf_cluster_set and the replay of every reservation entry behind it.  gf_cluster_update
+ * REPLACES, for each named node, its allocatable, its default flags (the flags of gf_cluster_set: what a build with
+ * node_flags == NULL selects and what the gf_cluster_* calls read — never a request's candidate flags of an earlier build) and,
+ * when zone_of_node is not NULL, its zone id.  name_rank, when not NULL, replaces the whole name order: a joining name shifts
+ * many ranks, so that array travels whole (the cluster's n_nodes entries, 4 bytes per node).  The overhead columns, the usage
+ * sums, the per-node entry counts of gf_usage_apply and the totals both range checks keep are KEPT.
+ * Equivalence: after the call every consumer of the resident columns — gf_snapshot_build_resident[_set] with travelling entries
+ * and with GF_RESIDENT_USAGE, gf_cluster_fit_feasible[_sets], gf_cluster_executor_fit, gf_cluster_find_nodes — answers exactly as
+ * on a fresh context that was given gf_cluster_set with the new allocatable, flags, zones and name ranks, the same n_zones and
+ * this context's current overhead columns, followed by gf_usage_apply(+1) of every entry this context currently carries.
+ *   - gf_cluster_set must have been called (GF_ERR_STATE; GF_ERR_STATE on a view, and while the resident cluster is marked
+ *     unknown by a failed update).  n_rows == 0 with name_rank == NULL is GF_OK, changes nothing and bumps nothing; n_rows == 0
+ *     with name_rank replaces the ranks.
+ *   - GF_ERR_INVALID: a NULL column (node, alloc_*, node_flags) with n_rows > 0; node[i] >= the cluster's n_nodes; a node twice
+ *     in one call; an allocatable outside [0, 2^62); zone_of_node[i] >= the cluster's n_zones; zones given on a cluster that was
+ *     installed without zones, unless every value is 0; name_rank that is not a permutation of 0 .. n_nodes-1.  n_nodes and
+ *     n_zones do not change through this call: a new zone label or a larger cluster is a gf_cluster_set.  A host that expects
+ *     nodes to join installs spare ABSENT rows (allocatable 0, flags 0, any valid zone, name ranks behind every present name) and
+ *     names them here when a node arrives.  On any refusal nothing on the device or in the context has changed.
+ *   - an absent row is exact wherever the caller names its nodes by a bit row or a selection: every gf_cluster_* call and
+ *     gf_snapshot_build_resident_set (a non-member is never summed, ranked or read).  gf_snapshot_build_resident without a row
+ *     still treats every row of the cluster as a node of the snapshot, absent ones included.
+ *   - bumps the cluster generation (gf_generation out[1]) only, and only when something was sent: the installed snapshot, the
+ *     snapshot epoch, the chain cache, recorded graphs, gf_residual_get's table and the resident worker are as the call found
+ *     them, as after gf_overhead_update.  The next build sees the new rows.
+ *   - multi-device context: every device gets the rows; when the update fails after the first device took it the resident
+ *     cluster is unusable (GF_ERR_STATE) until the next gf_cluster_set.
+ * Blocking with respect to the caller's arrays. */
+int gf_cluster_update(gf_ctx *ctx, uint32_t n_rows, const uint32_t *node, const int64_t *alloc_cpu_milli,
+                      const int64_t *alloc_mem_bytes, const int64_t *alloc_gpu, const uint32_t *node_flags,
+                      const uint32_t *zone_of_node /* nullable: zones unchanged */,
+                      const uint32_t *name_rank /* nullable: the cluster's n_nodes entries, replaces the whole permutation */);
 /* Generations of the state a context keeps between calls, for hosts that decide from them what a Filter must resend:
  *   out[0]  snapshot epoch: bumped by every call that installs a snapshot, zones or orders (the chain cache and recorded
  *           graphs are tied to it)
  *   out[1]  cluster generation: bumped by gf_cluster_set (and gf_snapshot_build, which calls it) and by every gf_overhead_update
- *           that changed something
+ *           and gf_cluster_update that changed something
  *   out[2]  usage generation: bumped by gf_cluster_set, gf_usage_reset and every gf_usage_apply
  * A host that finds the generations it recorded after its own last call unchanged knows that no other user of the context
  * touched that state (internal/extender keeps one extender per context, but the UnschedulablePodMarker shares it). */

@@ -472,6 +472,39 @@ func (c *Context) OverheadUpdate(nodes []uint32, overhead []*resources.Resources
 	return nil
 }
 
+// ClusterUpdate replaces the node rows of the named nodes in the resident cluster columns (gf_cluster_update): what a node
+// informer event changes — a node joins (it takes a spare absent row), leaves (its row becomes absent: allocatable 0, flags 0),
+// is cordoned, turns NotReady, or its allocatable moves.  allocatable, flags (GF_NODE_*) and zones (nil: zones unchanged) hold one
+// entry per named node; nameRank (nil: the name order stands) holds the cluster's n_nodes ranks and replaces the whole
+// permutation.  Node INDICES in the order given to gf_cluster_set, no index twice in one call; n_nodes and n_zones do not change
+// through this call.  The overhead rows and the resident usage sums stay; the next gf_snapshot_build_resident reads the new rows.
+// Unverified here (no Go toolchain); the C entry point is exercised by tests/test_gpu_cluster_update.py.
+func (c *Context) ClusterUpdate(nodes []uint32, allocatable []*resources.Resources, flags []uint32, zones []uint32, nameRank []uint32) error {
+	if len(nodes) != len(allocatable) || len(nodes) != len(flags) || (zones != nil && len(zones) != len(nodes)) {
+		return fmt.Errorf("gangfit: %d nodes, %d allocatable rows, %d flags, %d zones", len(nodes), len(allocatable), len(flags), len(zones))
+	}
+	if len(nodes) == 0 && len(nameRank) == 0 {
+		return nil
+	}
+	var cols [3][]int64
+	for _, r := range allocatable {
+		v, err := canonical(r)
+		if err != nil {
+			return err
+		}
+		for j := 0; j < 3; j++ {
+			cols[j] = append(cols[j], v[j])
+		}
+	}
+	c.mu.Lock()
+	defer c.mu.Unlock()
+	if rc := C.gf_cluster_update(c.ctx, C.uint32_t(len(nodes)), p32(nodes), p64(cols[0]), p64(cols[1]), p64(cols[2]), p32(flags), p32(zones),
+		p32(nameRank)); rc != C.GF_OK {
+		return c.err(rc)
+	}
+	return nil
+}
+
 // UsageReset zeroes the resident usage (gf_cluster_set does it too: a new node set starts from nothing).
 func (c *Context) UsageReset() error {
 	c.mu.Lock()

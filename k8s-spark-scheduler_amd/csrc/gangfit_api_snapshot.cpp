@@ -493,6 +493,95 @@ int gf_overhead_update(gf_ctx* ctx, uint32_t n_rows, const uint32_t* node, const
     return GF_OK;
 }
 
+int gf_cluster_update(gf_ctx* ctx, uint32_t n_rows, const uint32_t* node, const int64_t* alloc_cpu_milli, const int64_t* alloc_mem_bytes,
+                      const int64_t* alloc_gpu, const uint32_t* node_flags, const uint32_t* zone_of_node, const uint32_t* name_rank) {
+    // every device keeps the same columns; an update that reaches some devices and fails on another leaves them apart:
+    // the resident cluster is then unusable everywhere until gf_cluster_set
+    if (ctx != nullptr && !ctx->group.empty())
+        return each_device(ctx, &gf_ctx::cl_over_ok, [&](gf_ctx* sub, bool) {
+            return gf_cluster_update(sub, n_rows, node, alloc_cpu_milli, alloc_mem_bytes, alloc_gpu, node_flags, zone_of_node, name_rank);
+        });
+    if (!ctx) return GF_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    GF_NOT_ON_A_VIEW(ctx);
+    if (!ctx->have_cluster) return fail(ctx, GF_ERR_STATE, "gf_cluster_set must precede gf_cluster_update");
+    if (!ctx->cl_over_ok)
+        return fail(ctx, GF_ERR_STATE, "an earlier update failed half way: gf_cluster_set must replace the resident cluster");
+    if (n_rows == 0 && name_rank == nullptr) return GF_OK;
+    if (n_rows > 0 && (!node || !alloc_cpu_milli || !alloc_mem_bytes || !alloc_gpu || !node_flags))
+        return fail(ctx, GF_ERR_INVALID, "row columns must not be NULL");
+    const int64_t* cols[3] = {alloc_cpu_milli, alloc_mem_bytes, alloc_gpu};
+    for (int j = 0; j < 3; ++j)
+        for (uint32_t i = 0; i < n_rows; ++i)
+            if (cols[j][i] < 0 || cols[j][i] >= GF_MAX_ABS_QUANTITY) return fail(ctx, GF_ERR_INVALID, "allocatable of row %u out of range", i);
+    for (uint32_t i = 0; i < n_rows; ++i)
+        if (node[i] >= ctx->cl_n) return fail(ctx, GF_ERR_INVALID, "row %u names node %u of %u", i, node[i], ctx->cl_n);
+    if (n_rows > 0 && zone_of_node != nullptr) {
+        bool any = false;
+        for (uint32_t i = 0; i < n_rows; ++i) {
+            if (zone_of_node[i] >= ctx->cl_zones) return fail(ctx, GF_ERR_INVALID, "zone_of_node[%u] >= n_zones = %u", i, ctx->cl_zones);
+            any |= zone_of_node[i] != 0;
+        }
+        if (ctx->cl_zone.empty()) {  // installed without zones: every node is in zone 0, and zeros say nothing new
+            if (any) return fail(ctx, GF_ERR_INVALID, "the cluster was installed without zones: a zone id needs gf_cluster_set");
+            zone_of_node = nullptr;
+        }
+    }
+    if (n_rows == 0) zone_of_node = nullptr;
+    if (name_rank != nullptr) {  // a permutation, as in gf_cluster_set
+        std::vector<uint8_t> seen(ctx->cl_n, 0);
+        for (uint32_t i = 0; i < ctx->cl_n; ++i) {
+            if (name_rank[i] >= ctx->cl_n || seen[name_rank[i]]) return fail(ctx, GF_ERR_INVALID, "name_rank is not a permutation");
+            seen[name_rank[i]] = 1;
+        }
+    }
+    if (n_rows > 0) {
+        if (ctx->cl_row_stamp.size() != ctx->cl_n || ctx->cl_row_call == UINT32_MAX) {
+            ctx->cl_row_stamp.assign(ctx->cl_n, 0);
+            ctx->cl_row_call = 0;
+        }
+        ++ctx->cl_row_call;
+        for (uint32_t i = 0; i < n_rows; ++i) {
+            if (ctx->cl_row_stamp[node[i]] == ctx->cl_row_call) return fail(ctx, GF_ERR_INVALID, "node %u is named twice in one update", node[i]);
+            ctx->cl_row_stamp[node[i]] = ctx->cl_row_call;
+        }
+    }
+    const size_t R = n_rows, N = ctx->cl_n;
+    if (N == 0) return GF_OK;  // (name_rank of no node: nothing to replace)
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    GF_HIP(ctx, gf_wait_stream(st));  // an earlier update may still read the staging buffers that are about to grow
+    GF_HIP(ctx, ctx->d_delta_i64.reserve(3 * R));
+    GF_HIP(ctx, ctx->d_delta_u32.reserve(3 * R));  // node | flags | zone
+    // ---- from here on the device changes: a runtime failure leaves the columns unknown
+    ctx->cl_over_ok = false;
+    if (R) {
+        uint32_t* const d_rows32 = ctx->d_delta_u32.ptr;
+        for (int j = 0; j < 3; ++j)
+            GF_HIP(ctx, hipMemcpyAsync(ctx->d_delta_i64.ptr + j * R, cols[j], R * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        GF_HIP(ctx, hipMemcpyAsync(d_rows32, node, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        GF_HIP(ctx, hipMemcpyAsync(d_rows32 + R, node_flags, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        if (zone_of_node) GF_HIP(ctx, hipMemcpyAsync(d_rows32 + 2 * R, zone_of_node, R * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        // (while the build's flag column holds a request's candidate flags, d_flags_default == false, the next build uploads the
+        // whole default column from cl_default_flags below; the kernel's stores there are then overwritten)
+        GF_HIP(ctx, gangfit::launch_cluster_update(n_rows, ctx->cl_n, d_rows32, ctx->d_delta_i64.ptr, d_rows32 + R,
+                                                   zone_of_node ? d_rows32 + 2 * R : nullptr, ctx->d_cl_i64.ptr, ctx->d_cl_u32.ptr,
+                                                   ctx->d_cl_u32.ptr + 2 * N, ctx->d_cl_x32.ptr + N, st));
+    }
+    if (name_rank) GF_HIP(ctx, hipMemcpyAsync(ctx->d_cl_u32.ptr + N, name_rank, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    GF_HIP(ctx, gf_wait_stream(st));  // the caller's arrays are free again
+    for (uint32_t i = 0; i < n_rows; ++i) {  // the host copies follow the rows: the build's host route and the range checks read them
+        const uint32_t n = node[i];
+        for (int j = 0; j < 3; ++j) ctx->cl_alloc[(size_t)j * N + n] = cols[j][i];
+        ctx->cl_default_flags[n] = node_flags[i];
+        if (zone_of_node) ctx->cl_zone[n] = zone_of_node[i];
+    }
+    if (n_rows > 0) ctx->cl_flags = ctx->cl_default_flags;  // no request's candidate flags outlive the update
+    ctx->cl_over_ok = true;
+    ++ctx->cluster_gen;
+    return GF_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -349,7 +349,7 @@ struct gf_ctx {
     // reservation entries per node (n, next to the sums: gf_usage_apply adds sign per entry) | the flags of gf_cluster_set (n; the
     // flags column of d_cl_u32 may hold a request's candidate flags): what gf_cluster_executor_fit reads beside the columns above
     DeviceBuf<uint32_t> d_cl_x32;
-    DeviceBuf<int64_t> d_delta_i64; // one gf_usage_apply call's entries / one gf_overhead_update call's rows
+    DeviceBuf<int64_t> d_delta_i64; // one gf_usage_apply call's entries / one gf_overhead_update or gf_cluster_update call's rows
     DeviceBuf<uint32_t> d_delta_u32;
     __int128 usage_total[3] = {0, 0, 0};  // sum of everything applied: bounds every node's sum
     DeviceBuf<uint32_t> d_cl_u32;  // zone | name_rank | node_flags (n each)
@@ -357,15 +357,15 @@ struct gf_ctx {
     std::vector<uint32_t> cl_default_flags;   // the flags of gf_cluster_set: what node_flags == NULL selects
     bool d_flags_default = true;              // the device column holds cl_default_flags (not a request's candidate flags)
     bool usage_ok = true;                     // false after a failed update: the resident sums are unknown until gf_usage_reset
-    uint64_t cluster_gen = 0, usage_gen = 0;  // bumped by gf_cluster_set + gf_overhead_update / gf_usage_reset + gf_usage_apply (gf_generation)
+    uint64_t cluster_gen = 0, usage_gen = 0;  // bumped by gf_cluster_set + gf_overhead_update + gf_cluster_update / gf_usage_reset + gf_usage_apply (gf_generation)
     DeviceBuf<uint32_t> d_flag32;             // one device word for yes / no answers of small kernels
     DeviceBuf<uint32_t> d_sortwork;           // count tables, grid barrier and scalars of the priority sort (gangfit_snapshot.hip)
     uint32_t cl_n = 0, cl_zones = 1;
     bool cl_over = false, have_cluster = false;
     int64_t cl_max_over[3] = {0, 0, 0};       // upper bound of every node's overhead (gf_overhead_update only ever raises it)
-    bool cl_over_ok = true;                   // false after a gf_overhead_update that reached only some devices: until gf_cluster_set
+    bool cl_over_ok = true;                   // false after a gf_overhead_update / gf_cluster_update that reached only some devices: until gf_cluster_set
     std::vector<int64_t> cl_alloc;            // host copy of the allocatable columns (3n): gf_cluster_fit_feasible compares an overhead with them
-    std::vector<uint32_t> cl_row_stamp;       // gf_overhead_update: [node] the call that last named it (a node twice in one call)
+    std::vector<uint32_t> cl_row_stamp;       // gf_overhead_update / gf_cluster_update: [node] the call that last named it (a node twice in one call)
     uint32_t cl_row_call = 0;
 
     // gf_cluster_fit_feasible (gangfit_api_scan.cpp): the call's overhead columns (3n), node selection (n), records and answers.

@@ -615,6 +615,13 @@ hipError_t launch_usage_apply(uint32_t n_entries, uint32_t n_nodes, const uint32
 // before any later build.
 hipError_t launch_overhead_update(uint32_t n_rows, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_rows, int64_t* d_overhead,
                                   hipStream_t stream);
+// The node side of d_node[i] = row i for n_rows rows of the resident cluster: allocatable (columns cpu | memory | gpu of d_rows,
+// n_rows each -> d_alloc: 3 * n_nodes), the flag word (d_row_flags -> d_build_flags and d_default_flags, n_nodes each) and, when
+// d_row_zone is not nullptr, the zone id (-> d_zone).  Every d_node[i] < n_nodes and no node twice (the caller checks): plain
+// stores, stream-ordered before whatever reads the columns next.
+hipError_t launch_cluster_update(uint32_t n_rows, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_rows, const uint32_t* d_row_flags,
+                                 const uint32_t* d_row_zone, int64_t* d_alloc, uint32_t* d_zone, uint32_t* d_build_flags,
+                                 uint32_t* d_default_flags, hipStream_t stream);
 // The empty-cluster capacity scan (gangfit_scan.inc; gf_cluster_fit_feasible): d_out[a] = HasCapacity of application a on the
 // cluster columns in node-index order — available = d_alloc - d_over (d_over nullable: no overhead), driver and executor
 // candidates = the nodes with d_select[n] != 0 (nullable: every node), nothing reserved.  zoned: the single-AZ answer (some zone

@@ -62,6 +62,28 @@ __global__ __launch_bounds__(256) void overhead_update_kernel(uint32_t n_rows, u
     over[2 * (size_t)n_nodes + n] = r2[i];
 }
 
+// gf_cluster_update: row i of the update REPLACES the node side of node row_node[i] — its allocatable (cpu | memory | gpu, n_nodes
+// each), its default flag word in both places that hold it (the build's flag column and the column the gf_cluster_* calls read) and,
+// with row_zone, its zone id.  No node twice and none outside the cluster (the host has refused them): plain stores.
+__global__ __launch_bounds__(256) void cluster_update_kernel(uint32_t n_rows, uint32_t n_nodes, const uint32_t* __restrict__ row_node,
+                                                             const int64_t* __restrict__ a0, const int64_t* __restrict__ a1,
+                                                             const int64_t* __restrict__ a2, const uint32_t* __restrict__ row_flags,
+                                                             const uint32_t* __restrict__ row_zone, int64_t* __restrict__ alloc,
+                                                             uint32_t* __restrict__ zone, uint32_t* __restrict__ build_flags,
+                                                             uint32_t* __restrict__ default_flags) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const uint32_t n = row_node[i];
+    if (n >= n_nodes) return;  // (never: checked on the host; a store outside the columns must not depend on that)
+    alloc[n] = a0[i];
+    alloc[(size_t)n_nodes + n] = a1[i];
+    alloc[2 * (size_t)n_nodes + n] = a2[i];
+    const uint32_t fl = row_flags[i];
+    build_flags[n] = fl;
+    default_flags[n] = fl;
+    if (row_zone != nullptr) zone[n] = row_zone[i];
+}
+
 // order-preserving map of a signed quantity to unsigned
 __device__ __forceinline__ unsigned long long biased(int64_t v) { return (unsigned long long)v ^ 0x8000000000000000ull; }
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -1010,6 +1032,16 @@ hipError_t launch_overhead_update(uint32_t n_rows, uint32_t n_nodes, const uint3
     if (n_rows == 0 || n_nodes == 0) return hipSuccess;
     hipLaunchKernelGGL(overhead_update_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, stream, n_rows, n_nodes, d_node, d_rows,
                        d_rows + n_rows, d_rows + 2 * (size_t)n_rows, d_overhead);
+    return hipGetLastError();
+}
+
+hipError_t launch_cluster_update(uint32_t n_rows, uint32_t n_nodes, const uint32_t* d_node, const int64_t* d_rows, const uint32_t* d_row_flags,
+                                 const uint32_t* d_row_zone, int64_t* d_alloc, uint32_t* d_zone, uint32_t* d_build_flags,
+                                 uint32_t* d_default_flags, hipStream_t stream) {
+    if (n_rows == 0 || n_nodes == 0) return hipSuccess;
+    hipLaunchKernelGGL(cluster_update_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, stream, n_rows, n_nodes, d_node, d_rows,
+                       d_rows + n_rows, d_rows + 2 * (size_t)n_rows, d_row_flags, d_row_zone, d_alloc, d_zone, d_build_flags,
+                       d_default_flags);
     return hipGetLastError();
 }
 

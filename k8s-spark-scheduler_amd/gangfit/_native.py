@@ -55,7 +55,7 @@ EXPORTED_SYMBOLS = [
     "gf_usage_reset", "gf_usage_apply", "gf_overhead_update", "gf_set_option", "gf_chain_cache_stats", "gf_generation", "gf_shard_count", "gf_ctx_view",
     "gf_worker_fit", "gf_worker_submit_dev", "gf_worker_wait", "gf_worker_stop", "gf_worker_stats", "gf_worker_geometry", "gf_worker_row_stats", "gf_worker_kernel_time", "gf_call_phases",
     "gf_cluster_fit_feasible", "gf_cluster_fit_feasible_sets", "gf_snapshot_build_info", "gf_cluster_executor_fit",
-    "gf_snapshot_build_resident_set", "gf_snapshot_set_info", "gf_filter_efficiency", "gf_cluster_find_nodes",
+    "gf_snapshot_build_resident_set", "gf_snapshot_set_info", "gf_filter_efficiency", "gf_cluster_find_nodes", "gf_cluster_update",
 ]
 
 
@@ -160,6 +160,8 @@ def load() -> C.CDLL:
     L.gf_usage_apply.argtypes = [p, u32, p, p, p, p, i32]
     L.gf_overhead_update.restype = i32
     L.gf_overhead_update.argtypes = [p, u32, p, p, p, p]
+    L.gf_cluster_update.restype = i32
+    L.gf_cluster_update.argtypes = [p, u32, p, p, p, p, p, p, p]
     L.gf_snapshot_build_resident.restype = i32
     L.gf_snapshot_build_resident.argtypes = [p, u32, p, p, p, p, p, p, p, p, p, p, p]
     L.gf_snapshot_get.restype = i32

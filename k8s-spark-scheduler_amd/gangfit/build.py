@@ -22,6 +22,7 @@ HOST_EXECUTOR_RESIDENT_TEST_PATH = os.path.join(_PKG_ROOT, "host_executor_reside
 HOST_GROUP_FILTER_TEST_PATH = os.path.join(_PKG_ROOT, "host_group_filter_test")  # ... of the driver Filters of several groups (host_group_filter_test.cpp)
 HOST_FILTER_EFFICIENCY_TEST_PATH = os.path.join(_PKG_ROOT, "host_filter_efficiency_test")  # ... of the Filters' packing efficiency (host_filter_efficiency_test.cpp)
 HOST_CLUSTER_FIND_NODES_TEST_PATH = os.path.join(_PKG_ROOT, "host_cluster_find_nodes_test")  # ... of the resident failover reconcile (host_cluster_find_nodes_test.cpp)
+HOST_CLUSTER_UPDATE_TEST_PATH = os.path.join(_PKG_ROOT, "host_cluster_update_test")  # ... of node rows changed in place (host_cluster_update_test.cpp)
 INCLUDE = os.path.join(_REPO_ROOT, "include")
 
 _SOURCES = ["gangfit_kernels.hip", "gangfit_snapshot.hip", "gangfit_api.cpp", "gangfit_api_snapshot.cpp", "gangfit_api_fit.cpp",
@@ -92,6 +93,7 @@ def build_host(force: bool = False) -> str:
                 ("host_group_filter_test.cpp", HOST_GROUP_FILTER_TEST_PATH, test_flags),
                 ("host_filter_efficiency_test.cpp", HOST_FILTER_EFFICIENCY_TEST_PATH, test_flags),
                 ("host_cluster_find_nodes_test.cpp", HOST_CLUSTER_FIND_NODES_TEST_PATH, test_flags),
+                ("host_cluster_update_test.cpp", HOST_CLUSTER_UPDATE_TEST_PATH, test_flags),
                 ("host_bench.cpp", HOST_BENCH_PATH, bench_flags)]
     tests_dir = os.path.join(host_dir, "tests")
     test_hdrs = glob.glob(os.path.join(tests_dir, "*.hpp"))  # what the test programs share

@@ -236,6 +236,20 @@ class Context:
         assert all(len(c) == len(nd) for c in ocols), "one row per named node"
         self._check(self._lib.gf_overhead_update(self._h, len(nd), N.ptr(nd), *[N.ptr(c) for c in ocols]))
 
+    def cluster_update(self, rows, alloc, flags, zone=None, name_rank=None):
+        """gf_cluster_update: replace the node side of the named rows of the resident cluster in place — alloc = (n, 3)
+        allocatable rows, flags = their default GF_NODE_* words, zone = their zone ids (None: zones unchanged) — and, with
+        name_rank, the whole name order (the cluster's n_nodes entries).  Overhead, usage sums and entry counts stay."""
+        nd = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+        aa = np.ascontiguousarray(alloc, dtype=np.int64).reshape(-1, 3)
+        cols = [np.ascontiguousarray(aa[:, j]) for j in range(3)]
+        fl = np.ascontiguousarray(flags, dtype=np.uint32).reshape(-1)
+        z = None if zone is None else np.ascontiguousarray(zone, dtype=np.uint32).reshape(-1)
+        nr = None if name_rank is None else np.ascontiguousarray(name_rank, dtype=np.uint32).reshape(-1)
+        assert all(len(c) == len(nd) for c in cols) and len(fl) == len(nd) and (z is None or len(z) == len(nd)), "one row per named node"
+        assert nr is None or len(nr) == self._cluster_n, "name_rank covers every node of the cluster"
+        self._check(self._lib.gf_cluster_update(self._h, len(nd), N.ptr(nd), *[N.ptr(c) for c in cols], N.ptr(fl), N.ptr(z), N.ptr(nr)))
+
     def build_snapshot_resident(self, res_node=None, res_req=None, node_flags=None, driver_label_rank=None,
                                 exec_label_rank=None, want_orders: bool = True, res_cols=None, resident_usage: bool = False):
         """gf_snapshot_build_resident.  res_cols = (cpu, mem, gpu) contiguous int64 columns of the reservation entries, for

@@ -594,10 +594,14 @@ std::vector<std::pair<std::string, bool>> SparkSchedulerExtender::scanForUnsched
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The flat form of the cluster state, and the routes that keep it on the device.
 
-bool FlatCluster::Build(const std::vector<Node>& nodes, FlatCluster* out, std::string* err) {
+static uint64_t nextClusterVersion() {  // unique per Build / Rebuild
     static std::atomic<uint64_t> next_version{1};
+    return next_version.fetch_add(1);
+}
+
+bool FlatCluster::Build(const std::vector<Node>& nodes, FlatCluster* out, std::string* err) {
     FlatCluster c;
-    c.version = next_version.fetch_add(1);
+    c.version = nextClusterVersion();
     const size_t n = nodes.size();
     std::map<std::string, uint32_t> zone_ids;  // label order
     for (const Node& nd : nodes) {
@@ -636,6 +640,128 @@ bool FlatCluster::Build(const std::vector<Node>& nodes, FlatCluster* out, std::s
     std::sort(by_name.begin(), by_name.end());
     c.name_rank.assign(n, 0);
     for (size_t r = 0; r < n; ++r) c.name_rank[by_name[r].second] = (uint32_t)r;
+    *out = std::move(c);
+    return true;
+}
+
+namespace {
+
+// A node's allocatable, zone label and base flags as FlatCluster::Build reads them.
+bool nodeAllocatable(const Node& nd, int64_t v[3]) {
+    Resources a = Resources::Zero();
+    if (auto it = nd.Allocatable.find(kResourceCPU); it != nd.Allocatable.end()) a.CPU = it->second;
+    if (auto it = nd.Allocatable.find(kResourceMemory); it != nd.Allocatable.end()) a.Memory = it->second;
+    if (auto it = nd.Allocatable.find(kResourceNvidiaGPU); it != nd.Allocatable.end()) a.NvidiaGPU = it->second;
+    return canonicalNonNegative(a, v);
+}
+const std::string& nodeZoneLabel(const Node& nd) {
+    static const std::string placeholder = kZoneLabelPlaceholder;
+    auto z = nd.labels.find(kLabelZoneFailureDomain);
+    return z == nd.labels.end() ? placeholder : z->second;
+}
+
+// present / name_rank of a cluster with absent rows (names[i] empty): the present names in lexicographic order, then the absent
+// rows in index order; `present` stays empty when every row is present.
+void rankRows(FlatCluster* c) {
+    const size_t n = c->names.size();
+    std::vector<std::pair<std::string, uint32_t>> by_name;
+    std::vector<uint32_t> absent;
+    for (size_t i = 0; i < n; ++i) {
+        if (c->index.count(c->names[i]) != 0 && c->index.at(c->names[i]) == (uint32_t)i)
+            by_name.emplace_back(c->names[i], (uint32_t)i);
+        else
+            absent.push_back((uint32_t)i);
+    }
+    std::sort(by_name.begin(), by_name.end());
+    c->name_rank.assign(n, 0);
+    for (size_t r = 0; r < by_name.size(); ++r) c->name_rank[by_name[r].second] = (uint32_t)r;
+    for (size_t a = 0; a < absent.size(); ++a) c->name_rank[absent[a]] = (uint32_t)(by_name.size() + a);
+    c->present.clear();
+    if (absent.empty()) return;
+    c->present.assign((n + 63) / 64, 0);
+    for (const auto& [name, i] : by_name) c->present[i >> 6] |= UINT64_C(1) << (i & 63u);
+}
+
+}  // namespace
+
+bool FlatCluster::BuildWithSpare(const std::vector<Node>& nodes, uint32_t spare, FlatCluster* out, std::string* err) {
+    FlatCluster c;
+    if (!Build(nodes, &c, err)) return false;
+    if (spare != 0 && c.zone_labels.empty()) c.zone_labels.push_back(kZoneLabelPlaceholder);  // (no node yet: zone 0 must exist)
+    const uint32_t zone0 = c.zone.empty() ? 0u : c.zone[0];
+    for (uint32_t s = 0; s < spare; ++s) {
+        c.names.emplace_back();
+        for (int j = 0; j < 3; ++j) c.alloc[j].push_back(0);
+        c.zone.push_back(zone0);
+        c.base_flags.push_back(0u);
+    }
+    if (spare != 0) rankRows(&c);
+    *out = std::move(c);
+    return true;
+}
+
+bool FlatCluster::Rebuild(const FlatCluster& prev, const std::vector<Node>& nodes, const FlatReservations* carried, FlatCluster* out,
+                          std::vector<uint32_t>* rows_out, std::string* err) {
+    auto refuse = [&](std::string why) {
+        if (err) *err = std::move(why);
+        return false;
+    };
+    const size_t n = prev.names.size();
+    // zone ids follow the label order: they are prev's exactly when the set of labels is
+    std::map<std::string, uint32_t> zone_ids;
+    for (const Node& nd : nodes) zone_ids.emplace(nodeZoneLabel(nd), 0u);
+    if (zone_ids.size() != prev.zone_labels.size()) return refuse("the set of zone labels changed");
+    uint32_t zi = 0;
+    for (auto& kv : zone_ids) {
+        if (kv.first != prev.zone_labels[zi]) return refuse("the set of zone labels changed");
+        kv.second = zi++;
+    }
+    std::unordered_map<std::string, const Node*> listed;
+    listed.reserve(nodes.size());
+    for (const Node& nd : nodes)
+        if (nd.Name.empty() || !listed.emplace(nd.Name, &nd).second) return refuse("duplicate node name " + nd.Name);
+    FlatCluster c = prev;
+    c.version = nextClusterVersion();
+    c.derived_from = prev.version;
+    // ---- the departed: the row becomes absent, the name leaves the index
+    for (size_t i = 0; i < n; ++i) {
+        if (prev.isAbsent((uint32_t)i) || listed.count(prev.names[i]) != 0) continue;
+        c.index.erase(prev.names[i]);
+        c.names[i].clear();
+        for (int j = 0; j < 3; ++j) c.alloc[j][i] = 0;
+        c.base_flags[i] = 0u;
+    }
+    // ---- the present and the joining, in the order of `nodes`
+    std::vector<uint8_t> carries(n, 0);  // rows an entry of the carried list names: not for a newcomer
+    if (carried != nullptr)
+        for (const uint32_t at : carried->node)
+            if (at < n) carries[at] = 1;
+    size_t free_row = 0;
+    for (const Node& nd : nodes) {
+        int64_t v[3];
+        if (!nodeAllocatable(nd, v)) return refuse("allocatable of node " + nd.Name + " is not exactly representable");
+        uint32_t row;
+        if (auto at = c.index.find(nd.Name); at != c.index.end()) {
+            row = at->second;
+        } else {
+            while (free_row < n && (!c.names[free_row].empty() || carries[free_row])) ++free_row;
+            if (free_row == n) return refuse("no absent row is free for node " + nd.Name);
+            row = (uint32_t)free_row;
+            c.names[row] = nd.Name;
+            c.index.emplace(nd.Name, row);
+        }
+        for (int j = 0; j < 3; ++j) c.alloc[j][row] = v[j];
+        c.zone[row] = zone_ids.at(nodeZoneLabel(nd));
+        c.base_flags[row] = (nd.Unschedulable ? GF_NODE_UNSCHEDULABLE : 0u) | (nd.Ready ? GF_NODE_READY : 0u);
+    }
+    rankRows(&c);
+    c.ranks_changed = c.name_rank != prev.name_rank;
+    c.changed_rows.clear();
+    for (size_t i = 0; i < n; ++i)
+        if (c.alloc[0][i] != prev.alloc[0][i] || c.alloc[1][i] != prev.alloc[1][i] || c.alloc[2][i] != prev.alloc[2][i] ||
+            c.base_flags[i] != prev.base_flags[i] || c.zone[i] != prev.zone[i])
+            c.changed_rows.push_back((uint32_t)i);
+    if (rows_out) *rows_out = c.changed_rows;
     *out = std::move(c);
     return true;
 }
@@ -712,7 +838,8 @@ void overheadRowDiff(const std::vector<int64_t> want[3], const std::vector<int64
 }
 
 // What selectDriverNodeFlat and rescheduleExecutorFlat keep on the device, brought up to this request: the node-side columns
-// (gf_cluster_set), the overhead rows that differ from what is resident (gf_overhead_update) and, with `usage`, the usage sums of
+// (gf_cluster_set — or, for a cluster that FlatCluster::Rebuild derived from the resident one, the node rows that changed:
+// gf_cluster_update), the overhead rows that differ from what is resident (gf_overhead_update) and, with `usage`, the usage sums of
 // that entry list (gf_usage_reset + gf_usage_apply when the list's version changed).  Called under flat_mu_ and the context's
 // sequence lock.  gen: the context's generations afterwards.
 SparkSchedulerExtender::ResidentSync SparkSchedulerExtender::syncResident(gf_ctx* ctx, const FlatCluster& cluster, const FlatOverhead& fo,
@@ -724,7 +851,31 @@ SparkSchedulerExtender::ResidentSync SparkSchedulerExtender::syncResident(gf_ctx
     const OverheadColumns oc = nullableColumns(over);
     const bool known_over = fo.version != 0 && fo.version == resident_over_version_;  // compared before
     (void)gf_generation(ctx, gen);
-    const bool own_cluster = resident_cluster_ == cluster.version && cluster.version != 0;
+    bool own_cluster = resident_cluster_ == cluster.version && cluster.version != 0;
+    // the node rows changed in place (FlatCluster::Rebuild): what is resident is the cluster this one was derived from, and nobody
+    // else replaced it — the rows that differ travel (gf_cluster_update), with the name ranks when they moved; the overhead columns
+    // and the usage sums on the device stay what they are.  Most of the cluster: the full set below is cheaper.
+    if (!own_cluster && cluster.version != 0 && cluster.derived_from != 0 && resident_cluster_ == cluster.derived_from &&
+        gen[1] == seen_cluster_gen_ && cluster.changed_rows.size() <= (size_t)n / 2) {
+        const std::vector<uint32_t>& moved = cluster.changed_rows;
+        std::vector<int64_t> acol[3];
+        std::vector<uint32_t> fl, zn;
+        for (const uint32_t r : moved) {
+            for (int j = 0; j < 3; ++j) acol[j].push_back(cluster.alloc[j][r]);
+            fl.push_back(cluster.base_flags[r]);
+            zn.push_back(cluster.zone[r]);
+        }
+        ++cluster_update_calls_;
+        cluster_rows_sent_ += moved.size();
+        built_epoch_ = 0;  // the installed snapshot was built from other rows
+        if (gf_cluster_update(ctx, (uint32_t)moved.size(), moved.data(), acol[0].data(), acol[1].data(), acol[2].data(), fl.data(), zn.data(),
+                              cluster.ranks_changed ? cluster.name_rank.data() : nullptr) == GF_OK) {
+            resident_cluster_ = cluster.version;
+            own_cluster = true;
+            (void)gf_generation(ctx, gen);
+            seen_cluster_gen_ = gen[1];
+        }  // (refused: the full set below decides)
+    }
     bool set_cluster = !own_cluster || gen[1] != seen_cluster_gen_;
     std::vector<uint32_t> rows;  // the rows in which this request's overhead differs from what this extender last sent
     if (own_cluster && !known_over && (with_over || !resident_over_[0].empty())) {
@@ -777,6 +928,7 @@ SparkSchedulerExtender::ResidentSync SparkSchedulerExtender::syncResident(gf_ctx
     // its ResourceReservation events would send only the K + 1 entries of the object that changed: gf_usage_apply.)
     if (resident_route && usage != nullptr && (resident_usage_ != usage->version || gen[2] != seen_usage_gen_)) {
         resident_usage_ = 0;
+        ++usage_replay_calls_;
         if (gf_usage_reset(ctx) != GF_OK || gf_usage_apply(ctx, (uint32_t)usage->node.size(), usage->node.data(), usage->req[0].data(),
                                                            usage->req[1].data(), usage->req[2].data(), +1) != GF_OK) {
             *err = std::string("gf_usage_apply: ") + gf_last_error(ctx);
@@ -839,6 +991,8 @@ SelectNodeResult SparkSchedulerExtender::selectDriverNodeFlatOver(const std::str
                                                                   const FlatReservations* flat, const FlatOverhead* flatOverhead) {
     if (auto held = answerFromReservation(reservations, driver)) return *held;
     const uint32_t n = (uint32_t)cluster.names.size();
+    // "every node" of a cluster with absent rows is the row of its present nodes: an absent row must not become a metadata key
+    if (members == nullptr && !cluster.present.empty()) members = &cluster.present;
     // ---- the per-request columns: one entry per reservation (UsageForNodes' input), overhead, request flags
     // (a caller that hands over no entry list gets this request's own, which travels whole with every Filter)
     std::string err;

@@ -71,6 +71,7 @@ struct SelectNodeResult {
 // The node side of the cluster in the flat form gf_snapshot_build consumes.  Built when the node set changes (an informer
 // event in the Go host), reused by every Filter: names in lexicographic order give the name ranks, zone ids follow the
 // label order (the tie-break documented at the C ABI).
+struct FlatReservations;
 struct FlatCluster {
     std::vector<std::string> names;                  // node index -> name (the order of `nodes` at Build time)
     std::unordered_map<std::string, uint32_t> index;
@@ -79,6 +80,25 @@ struct FlatCluster {
     std::vector<int64_t> alloc[3];
     uint64_t version = 0;  // unique per Build: lets a caller keep the columns resident on the device (gf_cluster_set)
     static bool Build(const std::vector<Node>& nodes, FlatCluster* out, std::string* err);
+    // ---- node rows that change in place (include/gangfit.h, gf_cluster_update): a host whose cluster gains and loses nodes keeps
+    // `spare` ABSENT rows behind the present ones, so that n_nodes stands while nodes come and go.  An absent row has no name (names[i]
+    // is empty and `index` does not know it), allocatable 0, flags 0, a valid zone id (row 0's at BuildWithSpare) and a name rank
+    // behind every present name, in index order.  It is never a candidate and never a member of a row built from node lists; calls
+    // that mean "every node" pass `present` instead of NULL.
+    std::vector<uint64_t> present;       // the row of present nodes, ceil(n / 64) words; EMPTY: every row is present
+    uint64_t derived_from = 0;           // Rebuild: the version whose rows this cluster changed in place (0: Build / BuildWithSpare)
+    std::vector<uint32_t> changed_rows;  // Rebuild: the indices whose allocatable, flags or zone differ from derived_from's, ascending
+    bool ranks_changed = false;          // Rebuild: name_rank differs from derived_from's
+    // Build, plus `spare` absent rows at the end.
+    static bool BuildWithSpare(const std::vector<Node>& nodes, uint32_t spare, FlatCluster* out, std::string* err);
+    // `prev` brought to `nodes` with every index kept: a name keeps its index, a departed node's row becomes absent and its name
+    // leaves `index`, a joining node (in the order of `nodes`) takes the lowest absent index that no entry of `carried` names — a
+    // stale reservation of a departed node must not land on the newcomer —, name ranks are recomputed over all rows.  rows_out
+    // (nullable) receives changed_rows.  false (*err says why; the caller takes BuildWithSpare): no absent row is free, the set of
+    // zone labels differs from prev's, a duplicate name, an allocatable that is not exactly representable.
+    static bool Rebuild(const FlatCluster& prev, const std::vector<Node>& nodes, const FlatReservations* carried, FlatCluster* out,
+                        std::vector<uint32_t>* rows_out, std::string* err);
+    bool isAbsent(uint32_t i) const { return !present.empty() && ((present[i >> 6] >> (i & 63u)) & 1u) == 0u; }
 };
 
 // UsageForNodes' input in flat form: one (node index, cpu milli, memory bytes, gpus) entry per reservation of every
@@ -161,6 +181,11 @@ public:
     uint64_t overheadUpdateCalls() const { return overhead_update_calls_; }
     uint64_t overheadRowsSent() const { return overhead_rows_sent_; }
     uint64_t clusterSetCalls() const { return cluster_set_calls_; }
+    // ... gf_cluster_update calls and the rows they carried (node rows changed in place instead of a gf_cluster_set), and the
+    // replays of the whole reservation list (gf_usage_reset + gf_usage_apply)
+    uint64_t clusterUpdateCalls() const { return cluster_update_calls_; }
+    uint64_t clusterRowsSent() const { return cluster_rows_sent_; }
+    uint64_t usageReplayCalls() const { return usage_replay_calls_; }
 
     // unschedulablepods.go:132-166: does the application fit an EMPTY cluster (usage = 0, the given overhead)?
     // nodes are used in lister order for both candidate lists.
@@ -285,6 +310,7 @@ private:
     std::vector<int64_t> resident_over_[3];
     uint64_t resident_over_version_ = 0;  // FlatOverhead::version those columns came from (0: from the map, always compared)
     uint64_t overhead_update_calls_ = 0, overhead_rows_sent_ = 0, cluster_set_calls_ = 0;
+    uint64_t cluster_update_calls_ = 0, cluster_rows_sent_ = 0, usage_replay_calls_ = 0;
     // what the context held after this extender's last call (gf_generation): another user of the same gf_ctx that replaces the
     // cluster, its overhead rows, the usage or the snapshot moves these on, and the next Filter sends its own state again
     uint64_t seen_cluster_gen_ = 0, seen_usage_gen_ = 0;

@@ -166,6 +166,12 @@ const char *gf_last_error(gf_ctx *ctx);
  *   "chain_cache"            0: every FIFO chain replays from the snapshot (also GANGFIT_CHAIN_CACHE=0 in the environment)
  *   "fifo_generic"           1: FIFO chains run on the wide / generic global-memory kernels only
  *   "lds_budget"             bytes of LDS one workgroup may use (<= the device's): smaller table fronts, global tails
+ *   "narrow_floor"           0: FIFO chains use the exact narrow form only (every table value a multiple of the unit); a queue that
+ *                            it does not prove takes the wide / generic kernels.  1 (default): such a queue runs the LDS chain
+ *                            kernels on the FLOORED form when its requests share a unit that keeps floor(value / unit) inside
+ *                            (-2^30, 2^30) — same answers bit for bit (gf_chain_units tells which form served).  On a table that
+ *                            has an exact form the floored one needs the chain cache's plan: not with "chain_cache" = 0
+ *                            or the scan counters on (gf_scan_stats)
  *   "minfrag_matrix", "minfrag_hist", "sparse_gpu", "zero_copy"   0 disables the respective structure
  *   "feasible_announce"      0: gf_fit_feasible waits for its stream instead of watching the answers arrive in pinned memory
  *                            (GANGFIT_WAIT=block has the same effect: no spinning on the answers)
@@ -461,6 +467,13 @@ int gf_cluster_fit_feasible_sets(gf_ctx *ctx, gf_algo algo, const int64_t *over_
  * out[0] = chains served with the cache armed, out[1] = of those resumed from a checkpoint, out[2] = applications
  * evaluated, out[3] = applications skipped (taken from the cache).  reset != 0 zeroes the counters afterwards. */
 int gf_chain_cache_stats(gf_ctx *ctx, int reset, uint64_t out[4]);
+
+/* The narrow units of the last FIFO chain of gf_fit_batch that an LDS chain kernel served for certain (every request proven to
+ * have a scaled form on the host) since the last install or gf_set_option: out[0..2] = the units of cpu, memory and gpu, all 0 when there was
+ * none; out[3] = 1 when the chain ran on the floored form of the table (the units divide the queue's requests and the table
+ * holds floor(value / unit); option "narrow_floor"), 0 on the exact form (the units divide every table value too).  A
+ * diagnostic: answers do not depend on the form.  On a multi-device context: of its first device, like gf_chain_cache_stats. */
+int gf_chain_units(gf_ctx *ctx, int64_t out[4]);
 
 /* Same decision kernels on DEVICE-resident buffers, asynchronous on `stream` (a hipStream_t; NULL = the context's own
  * stream).  d_apps must carry exec_off and must already be validated (k in [0, GF_MAX_K], requests in [0, 2^62)).

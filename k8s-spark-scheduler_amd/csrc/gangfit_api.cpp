@@ -44,7 +44,12 @@ int view_refresh(gf_ctx* v) {
     for (int j = 0; j < 3; ++j) {
         v->unit[j] = p->unit[j];
         v->nmax[j] = p->nmax[j];
+        v->tmin[j] = p->tmin[j];
+        v->tmax[j] = p->tmax[j];
     }
+    v->range_known = p->range_known;  // (false: the view fetches the range itself; its floored snapshot is its own in any case)
+    v->floor_epoch = 0;
+    for (int64_t& u : v->chain_unit_last) u = 0;
     v->n_zones = p->n_zones;
     v->zstride = p->zstride;
     v->zd_row0 = p->zd_row0;
@@ -290,6 +295,10 @@ void gf_destroy(gf_ctx* ctx) {
     ctx->d_nwork.release();
     ctx->d_ncmax.release();
     ctx->d_ncmax_w.release();
+    ctx->d_fsnap.release();
+    ctx->d_fcmax.release();
+    ctx->d_frem.release();
+    ctx->d_frange.release();
     ctx->h_ntable.release();
     ctx->h_cmax.release();
     ctx->d_sched.release();
@@ -493,6 +502,8 @@ int gf_set_option(gf_ctx* ctx, const char* key, int64_t value) {
         ctx->force_general_layout = value != 0;
     } else if (k == "chain_cache") {
         ctx->chain_cache_on = value != 0;
+    } else if (k == "narrow_floor") {
+        ctx->narrow_floor = value != 0;
     } else if (k == "worker_sets" || k == "worker_blocks_per_set" || k == "worker_idle_us") {
         worker_quiesce(ctx);
         if (k == "worker_sets") {
@@ -533,6 +544,7 @@ int gf_set_option(gf_ctx* ctx, const char* key, int64_t value) {
         return fail(ctx, GF_ERR_INVALID, "unknown option '%s'", key);
     }
     ctx->chain.valid = false;
+    for (int64_t& u : ctx->chain_unit_last) u = 0;  // (gf_chain_units starts over with the cache)
     return GF_OK;
 }
 

@@ -3,6 +3,7 @@
 // the plain chain, the LDS chains with their generic twin, the generic chain); the incremental chain cache, gf_fit_batch /
 // gf_fit_batch_dev / gf_fit_feasible / gf_spark_binpack, single executors, findNodes and the packing efficiencies.
 #include "gangfit_ctx.h"
+#include "gangfit_floor_units.h"
 
 using namespace gfapi;
 
@@ -130,44 +131,63 @@ int ensure_cnt(gf_ctx* ctx, uint64_t n_decisions, hipStream_t stream) {
 // *proven (nullable): every request of the batch is a multiple of the resulting units and fits the narrow range, i.e. the
 // narrow kernel will not hand the batch to its wide twin (what prepare_app tests on the device).
 void narrow_units(const gf_ctx* ctx, const gf_app* h_apps, uint32_t n_apps, int64_t eff[3], int32_t factor[3], bool* proven) {
+    refine_units(ctx->unit, ctx->nmax, h_apps, n_apps, eff, factor, proven);  // (gangfit_floor_units.h: the exact form)
+}
+
+// The smallest and largest table value per dimension, which the floored form is decided from: kept at install for a table the host
+// built; a snapshot built on the device reads back magnitudes only, so the first chain that asks fetches them (one small kernel and
+// a copy of six words, once per snapshot, on a route that had no narrow form before).
+int table_range(gf_ctx* ctx) {
+    if (ctx->range_known) return GF_OK;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    GF_HIP(ctx, ctx->d_frange.reserve(6));
+    GF_HIP(ctx, gangfit::launch_table_range(ctx->d_snap.ptr, ctx->d_slot_node.ptr, ctx->n_slots, ctx->d_frange.ptr, ctx->stream));
+    int64_t h[6];
+    GF_HIP(ctx, hipMemcpyAsync(h, ctx->d_frange.ptr, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    GF_HIP(ctx, gf_wait_stream(ctx->stream));
     for (int j = 0; j < 3; ++j) {
-        eff[j] = ctx->unit[j];
-        factor[j] = 1;
+        ctx->tmin[j] = h[j];
+        ctx->tmax[j] = h[3 + j];
     }
-    if (proven) *proven = false;
-    if (h_apps == nullptr) return;
-    for (uint32_t a = 0; a < n_apps; ++a)
-        for (int j = 0; j < 3; ++j)
-            for (const int64_t v : {h_apps[a].drv[j], h_apps[a].exe[j]})
-                if (v > 0 && v % eff[j] != 0) {
-                    int64_t x = eff[j], y = v;
-                    while (y) {
-                        const int64_t t = x % y;
-                        x = y;
-                        y = t;
-                    }
-                    eff[j] = x;
-                }
-    bool ok = true;
-    for (int j = 0; j < 3; ++j) {
-        const int64_t f = ctx->unit[j] / eff[j];
-        const int64_t room = ctx->nmax[j] > 0 ? ((INT64_C(1) << 30) - 1) / ctx->nmax[j] : (INT64_C(1) << 30) - 1;
-        ok = ok && f <= room;
-        factor[j] = ok ? (int32_t)f : 1;
-    }
-    if (!ok)
-        for (int j = 0; j < 3; ++j) {
-            eff[j] = ctx->unit[j];
-            factor[j] = 1;
+    ctx->range_known = true;
+    return GF_OK;
+}
+
+// The floored narrow form of a queue on this context (gangfit_floor_units.h), for a caller that knows the exact form does not serve:
+// the table has none, or refine_units did not prove the queue.  true: unit[] divides every request and the floored table fits.
+// Like chain_plan's scan of the exact form, a queue that shares a prefix with a cached floored chain is only scanned behind it:
+// the cached units divide the prefix by construction and the table fits them, so when they divide the new applications too they
+// are a valid set of units for this queue — and the checkpoints are scaled in them.  known_common (nullable): the length of that
+// prefix, where the caller has counted it.
+bool floor_plan(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, const gf_app* h_apps, int64_t unit[3], const uint32_t* known_common = nullptr) {
+    if (!ctx->narrow_floor || !ctx->merged || ctx->fifo_generic || h_apps == nullptr) return false;
+    const gf_ctx::ChainCache& C = ctx->chain;
+    if (C.valid && C.floored && C.epoch == ctx->snap_epoch && C.algo == (int)algo && C.n_apps > 0) {
+        uint32_t common = 0;
+        if (known_common != nullptr) {
+            common = *known_common;
+        } else {
+            const uint32_t lim = (n_apps < C.n_apps ? n_apps : C.n_apps) - 1;
+            while (common < lim && std::memcmp(&h_apps[common], &C.apps[common], sizeof(gf_app)) == 0) ++common;
         }
-    if (proven) {
-        bool all = true;
-        for (uint32_t a = 0; a < n_apps && all; ++a)
-            for (int j = 0; j < 3; ++j)
-                for (const int64_t v : {h_apps[a].drv[j], h_apps[a].exe[j]})
-                    all = all && v >= 0 && v % eff[j] == 0 && v / eff[j] < (INT64_C(1) << 30);
-        *proven = all;
+        bool ok = common > 0;
+        for (uint32_t i = common; i < n_apps && ok; ++i) {
+            ok = h_apps[i].k >= 0 && h_apps[i].k <= GF_MAX_K;
+            for (int j = 0; j < 3 && ok; ++j)
+                for (const int64_t v : {h_apps[i].drv[j], h_apps[i].exe[j]})
+                    ok = ok && v >= 0 && v % C.unit[j] == 0 && v / C.unit[j] < kNarrowBound;
+        }
+        if (ok) {
+            for (int j = 0; j < 3; ++j) unit[j] = C.unit[j];
+            return true;
+        }
     }
+    if (table_range(ctx) != GF_OK) {  // the range is not known: no floored form, the batch takes the route it took without one
+        (void)hipGetLastError();
+        ctx->err.clear();  // (not this call's failure: whatever is wrong with the device, the launch reports it)
+        return false;
+    }
+    return floor_units(ctx->tmin, ctx->tmax, h_apps, n_apps, unit);
 }
 
 // How one FIFO chain of gf_fit_batch uses the chain cache (decided by chain_plan before the launch).
@@ -180,6 +200,11 @@ struct ChainRun {
     bool write_tip = false;      // the launch leaves its own tip in ctx->chain.d_tip
     int64_t eff[3] = {0, 0, 0};  // the narrow units of the queue and their factors (narrow_units): narrow_begin does not scan it again
     int32_t factor[3] = {1, 1, 1};
+    // The chain runs on the FLOORED narrow form in units eff (factor = 1, narrow_proven): decided by gf_fit_batch before the route
+    // where the table has no exact form, by chain_plan where the exact form did not prove the queue.  Such a run is handed on even
+    // when the chain cache is not used (record = false, a_begin = 0): the launch needs its units.
+    bool floored = false;
+    uint32_t exact_fails_at = 0;  // ... and the shortest prefix of the queue that has no exact form (0: the table has none at all)
 };
 
 // One call's batch, as launch() and its helpers see it: the WHOLE queue on the device — q.n_apps, d_apps, d_results,
@@ -217,7 +242,26 @@ int narrow_begin(gf_ctx* ctx, const FitCall& call, gangfit::NarrowTable* nt, gan
     const size_t table_bytes = 3 * (size_t)ctx->n_slots * sizeof(int32_t);
     const bool whole = restore != nullptr && !restore_dirty_chunks;  // the checkpoint is the whole table
     const int32_t* src = nullptr;  // what the working copy starts from, when a plain copy makes it
-    if (factor[0] == 1 && factor[1] == 1 && factor[2] == 1) {
+    if (call.run != nullptr && call.run->floored) {
+        // the floored snapshot in these units takes the place of d_nsnap: built once per (snapshot epoch, units)
+        const size_t S = ctx->n_slots, C = ctx->n_chunks;
+        if (ctx->floor_epoch != ctx->snap_epoch || std::memcmp(ctx->floor_unit, eff, sizeof ctx->floor_unit) != 0) {
+            ctx->floor_epoch = 0;
+            GF_HIP(ctx, ctx->d_fsnap.reserve(3 * S));
+            GF_HIP(ctx, ctx->d_fcmax.reserve(3 * C));
+            GF_HIP(ctx, ctx->d_frem.reserve(3 * S));
+            GF_HIP(ctx, gangfit::launch_floor_snapshot(ctx->d_snap.ptr, ctx->d_slot_node.ptr, ctx->n_slots, ctx->n_chunks, eff,
+                                                       ctx->d_fsnap.ptr, ctx->d_fcmax.ptr, ctx->d_frem.ptr, call.q.stream));
+            std::memcpy(ctx->floor_unit, eff, sizeof ctx->floor_unit);
+            ctx->floor_epoch = ctx->snap_epoch;
+        }
+        GF_HIP(ctx, ctx->d_nwork.reserve(3 * S));  // (a table without an exact form has none yet)
+        nt->cpu = ctx->d_nwork.ptr;
+        nt->mem = nt->cpu + S;
+        nt->gpu = nt->mem + S;
+        src = whole ? restore : ctx->d_fsnap.ptr;
+        nt->cmax = ctx->d_fcmax.ptr;
+    } else if (factor[0] == 1 && factor[1] == 1 && factor[2] == 1) {
         src = whole ? restore : ctx->d_nsnap.ptr;
         nt->cmax = ctx->d_ncmax.ptr;
     } else {
@@ -366,7 +410,8 @@ int minfrag_lds_chain(gf_ctx* ctx, bool zoned, uint32_t lds_slots, uint32_t n_id
 
 // What serves a batch of (mode, packer) on this context: the kernel route and the geometry of its chain kernel.  It depends
 // on the context's state and options only, never on the batch (what a batch adds — the narrow proof, the resume point —
-// is ChainRun's).
+// is ChainRun's), with one exception: on a table without an exact narrow form, `floored` (route_of's last argument) says that
+// this queue has the floored one (floor_plan), which is as good a table for the LDS chain kernels.
 struct Route {
     enum Kind {
         kPlain,       // independent, plain packers: fit_independent_kernel
@@ -391,7 +436,7 @@ struct Route {
 // Refusals in order: no orders (GF_ERR_STATE), a packer without a device path, an unknown mode (GF_ERR_UNSUPPORTED),
 // a zone-aware packer without the schedulable columns (GF_ERR_STATE), a zone-aware FIFO chain with more than 63 zones
 // (GF_ERR_UNSUPPORTED).
-int route_of(gf_ctx* ctx, gf_mode mode, gf_algo algo, Route* r) {
+int route_of(gf_ctx* ctx, gf_mode mode, gf_algo algo, Route* r, bool floored = false) {
     *r = Route{};
     if (!ctx->have_orders) return fail(ctx, GF_ERR_STATE, "gf_snapshot_set + gf_orders_set must precede a fit");
     const bool zoned = is_zone_algo(algo);
@@ -410,7 +455,7 @@ int route_of(gf_ctx* ctx, gf_mode mode, gf_algo algo, Route* r) {
     }
     if (zoned && nz + 1 > 64) return fail(ctx, GF_ERR_UNSUPPORTED, "more than 63 zones in a FIFO chain");
     // the LDS chain kernels work on the narrow table of the merged layout
-    const bool lds = ctx->merged && ctx->narrow_ok && !ctx->fifo_generic;
+    const bool lds = ctx->merged && (ctx->narrow_ok || floored) && !ctx->fifo_generic;
     if (r->inner != GF_ALGO_MINIMAL_FRAGMENTATION && !zoned) {
         r->kind = lds ? Route::kSolo : Route::kWide;
         if (lds) r->lds_slots = solo_lds_slots(ctx);
@@ -465,9 +510,16 @@ int lds_chain_begin(gf_ctx* ctx, const FitCall& call, bool answers_final, bool r
 // form.  Returns false when the chain cache is not used for this call (run is then not handed on; only its
 // a_begin = 0 is read).
 bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, const gf_app* h_apps, ChainRun* run) {
+    const ChainRun before = *run;  // (gf_fit_batch has decided the floored form where the table has no exact one)
     *run = ChainRun{};
+    if (before.floored && route.lds_chain()) {
+        run->floored = run->narrow_proven = true;
+        for (int j = 0; j < 3; ++j) run->eff[j] = before.eff[j];
+    }
     gf_ctx::ChainCache& C = ctx->chain;
-    // (the LDS chain kernels dump and restore the checkpoints)
+    // (the LDS chain kernels dump and restore the checkpoints.)  Without the cache the host proves nothing about an exact table's
+    // queue — narrow_begin scans the units, the guarded twin stands by — and so the floored form is not tried there either: with
+    // option "chain_cache" = 0 or the counters on, a table that HAS an exact form keeps today's route for every queue.
     if (!route.lds_chain() || !ctx->chain_cache_on || ctx->stats_on) return false;
     const bool solo = route.kind == Route::kSolo, table_in_lds = route.table_in_lds;
     // The narrow units of the queue and the proof that every request has a scaled form.  A scan of the whole queue is twelve
@@ -480,9 +532,26 @@ bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, 
     bool proven = false;
     uint32_t common = 0;  // applications this queue shares with the cached one, from the front (the last of either excluded)
     bool units_from_cache = false;
-    if (C.valid && C.epoch == ctx->snap_epoch && C.algo == (int)algo && C.n_apps > 0) {
+    const bool cached = C.valid && C.epoch == ctx->snap_epoch && C.algo == (int)algo && C.n_apps > 0;
+    if (cached) {
         const uint32_t lim = (n_apps < C.n_apps ? n_apps : C.n_apps) - 1;
         while (common < lim && std::memcmp(&h_apps[common], &C.apps[common], sizeof(gf_app)) == 0) ++common;
+    }
+    // The floored form (gangfit_floor_units.h) serves only a queue the exact form does not prove.  Decided before the route where
+    // the table has no exact form; else here, behind the scan that did not prove the queue — or without that scan, when the cached
+    // chain is a floored one and this queue still begins with the prefix that had no exact form then (exact_fails_at): it has none now.
+    bool floor_tried = false;
+    if (run->floored) {
+        proven = units_from_cache = true;  // (nothing left to scan; `same` below compares the units with the cached chain's)
+    } else if (cached && C.floored) {
+        if (common >= C.exact_fails_at) {
+            floor_tried = true;
+            if (floor_plan(ctx, algo, n_apps, h_apps, eff, &common)) {
+                run->floored = run->narrow_proven = proven = units_from_cache = true;  // (whatever becomes of the cache below)
+                run->exact_fails_at = C.exact_fails_at;
+            }
+        }
+    } else if (cached) {
         bool ok = common > 0;
         for (uint32_t i = common; i < n_apps && ok; ++i) {
             ok = h_apps[i].k >= 0 && h_apps[i].k <= GF_MAX_K;
@@ -498,7 +567,20 @@ bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, 
             }
         }
     }
-    if (!units_from_cache) narrow_units(ctx, h_apps, n_apps, eff, factor, &proven);
+    if (!units_from_cache) {
+        narrow_units(ctx, h_apps, n_apps, eff, factor, &proven);
+        if (!proven && !floor_tried) {
+            int64_t fu[3];
+            if (floor_plan(ctx, algo, n_apps, h_apps, fu, cached ? &common : nullptr)) {
+                run->floored = run->narrow_proven = proven = true;  // (whatever becomes of the cache below)
+                run->exact_fails_at = exact_fails_at(ctx->unit, ctx->nmax, h_apps, n_apps);
+                for (int j = 0; j < 3; ++j) {
+                    eff[j] = fu[j];
+                    factor[j] = 1;
+                }
+            }
+        }
+    }
     if (!proven) return false;
     // checkpoint interval: 32 applications while a dump is cheap — the whole table from LDS, or (solo kernel, table with a
     // global tail) only the chunks that differ from the snapshot; 128 where a dump copies a table that lives in global memory
@@ -511,7 +593,8 @@ bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, 
     if (n_ck * slot_words * sizeof(int32_t) > (UINT64_C(4) << 30)) return false;
     uint32_t a_begin = 0;
     const bool same = C.valid && C.epoch == ctx->snap_epoch && C.algo == (int)algo && C.shift == shift && C.dirty_format == dirty_format &&
-                      C.slot_words == slot_words && C.unit[0] == eff[0] && C.unit[1] == eff[1] && C.unit[2] == eff[2];
+                      C.slot_words == slot_words && C.unit[0] == eff[0] && C.unit[1] == eff[1] && C.unit[2] == eff[2] &&
+                      C.floored == run->floored;
     if (same) {
         // longest common prefix of the two queues, the last application of either excluded (nothing is committed behind
         // the driver being filtered: its table is not a state of the longer chain)
@@ -569,6 +652,8 @@ bool chain_plan(gf_ctx* ctx, const Route& route, gf_algo algo, uint32_t n_apps, 
     C.slot_words = slot_words;
     C.dirty_format = dirty_format;
     for (int j = 0; j < 3; ++j) C.unit[j] = eff[j];
+    C.floored = run->floored;
+    C.exact_fails_at = run->exact_fails_at;
     run->a_begin = a_begin;
     run->common = same ? common : 0;
     run->record = true;
@@ -608,10 +693,10 @@ void chain_commit(gf_ctx* ctx, gf_algo algo, uint32_t n_apps, uint64_t total_k, 
     ctx->chain_stat[3] += run.a_begin;
 }
 
-// The tables of a chain: the wide working table, nt — its scaled twin — and the zones.
-gangfit::ChainTables chain_tables(gf_ctx* ctx, const Route& r, const gangfit::NarrowTable& nt) {
+// The tables of a chain: the wide working table, nt — its scaled twin —, the zones, and the remainders when nt is the floored form.
+gangfit::ChainTables chain_tables(gf_ctx* ctx, const Route& r, const gangfit::NarrowTable& nt, bool floored = false) {
     return gangfit::ChainTables{make_table(ctx, ctx->d_work.ptr), nt, r.zoned ? zone_table(ctx) : gangfit::ZoneTable{nullptr, nullptr, 0, 0},
-                                r.zoned ? ctx->d_sched.ptr : nullptr};
+                                r.zoned ? ctx->d_sched.ptr : nullptr, floored ? ctx->d_frem.ptr : nullptr};
 }
 // Makes b — the whole queue with its ckpt and io set — the batch of the queue's tail [b->ckpt.a_base, n_apps), once the context's
 // buffers have their sizes: exec_off is absolute, so the record, scaled-record and result pointers are all that moves.
@@ -625,6 +710,12 @@ void chain_batch_tail(gf_ctx* ctx, gangfit::ChainBatch* b) {
     b->d_scratch = ctx->d_scratch.ptr;
     b->d_zexec = ctx->d_zexec.ptr;
     b->d_stats = ctx->stats_on ? ctx->d_stats.ptr : nullptr;
+}
+
+// Behind a chain on the floored narrow form: its epilogue left q' * unit in the wide working table, the residuals are q' * unit + r.
+int floor_residuals(gf_ctx* ctx, hipStream_t stream) {
+    GF_HIP(ctx, gangfit::launch_floor_residual(ctx->d_work.ptr, ctx->d_frem.ptr, ctx->n_slots, stream));
+    return GF_OK;
 }
 
 // Independent batches: every application against the snapshot.  The FitBatch of n_apps records and their answers on the context's
@@ -695,9 +786,10 @@ int launch_plain_chain(gf_ctx* ctx, const Route& r, FitCall* call) {
     ctx->work_valid = true;
     chain_batch_tail(ctx, &b);
     const uint64_t heads_lo = b.ckpt.a_base > 0 ? call->h_apps[b.ckpt.a_base].exec_off : 0;  // placements of the skipped prefix
-    GF_HIP(ctx, gangfit::launch_fit_fifo((gf_algo)r.inner, plan, chain_tables(ctx, r, nt), b, heads_lo));
+    const bool floored = plan.narrow && call->run != nullptr && call->run->floored;
+    GF_HIP(ctx, gangfit::launch_fit_fifo((gf_algo)r.inner, plan, chain_tables(ctx, r, nt, floored), b, heads_lo));
     chain_io_end(ctx, call, b.io);
-    return GF_OK;
+    return floored ? floor_residuals(ctx, call->q.stream) : GF_OK;
 }
 
 // FIFO chains of the zone-aware and minimal-fragmentation packers.  What the generic chain kernel needs before anything of
@@ -741,14 +833,16 @@ int launch_lds_chain(gf_ctx* ctx, const Route& r, FitCall* call) {
     gangfit::NarrowTable nt{};
     if (const int rc = lds_chain_begin(ctx, *call, proven, false, &b, &nt); rc != GF_OK) return rc;
     chain_batch_tail(ctx, &b);
+    const bool floored = proven && call->run->floored;
     if (r.kind == Route::kZonedLds) {
-        GF_HIP(ctx, gangfit::launch_fit_fifo_zoned_lds(r.az_aware, r.lds_slots, r.n_shapes, chain_tables(ctx, r, nt), b));
+        GF_HIP(ctx, gangfit::launch_fit_fifo_zoned_lds(r.az_aware, r.lds_slots, r.n_shapes, chain_tables(ctx, r, nt, floored), b));
     } else {
         gangfit::MinfragLdsChain m;
         if (const int rc = minfrag_lds_chain(ctx, r.zoned, r.lds_slots, /* n_idx */ r.n_shapes, &m); rc != GF_OK) return rc;
-        GF_HIP(ctx, gangfit::launch_fit_fifo_minfrag_lds(m, chain_tables(ctx, r, nt), b));
+        GF_HIP(ctx, gangfit::launch_fit_fifo_minfrag_lds(m, chain_tables(ctx, r, nt, floored), b));
     }
     chain_io_end(ctx, call, b.io);
+    if (floored) return floor_residuals(ctx, call->q.stream);
     return proven ? GF_OK : launch_generic_chain(ctx, r, call, b.d_wide_needed);
 }
 
@@ -799,6 +893,14 @@ int gf_chain_cache_stats(gf_ctx* ctx, int reset, uint64_t out[4]) {
     return GF_OK;
 }
 
+int gf_chain_units(gf_ctx* ctx, int64_t out[4]) {
+    GF_DELEGATE(ctx, gf_chain_units(ctx, out));
+    if (!ctx || !out) return GF_ERR_INVALID;
+    std::lock_guard<std::recursive_mutex> lock(ctx->mu);
+    for (int i = 0; i < 4; ++i) out[i] = ctx->chain_unit_last[i];
+    return GF_OK;
+}
+
 int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const gf_app* apps, gf_result* results,
                  uint32_t* exec_nodes, uint64_t exec_nodes_cap, int32_t* chain_failed_at) {
     if (ctx != nullptr && !ctx->group.empty())
@@ -817,8 +919,13 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     if (total_k > exec_nodes_cap || (total_k > 0 && !exec_nodes))
         return fail(ctx, GF_ERR_CAPACITY, "exec_nodes holds %llu entries, %llu needed",
                     (unsigned long long)exec_nodes_cap, (unsigned long long)total_k);
+    // A table without an exact narrow form takes the wide kernels — unless this queue has the floored form (floor_plan), which
+    // the route has to know: the LDS chain kernels then serve it as they serve an exact table.
+    ChainRun run;
+    if (mode == GF_MODE_FIFO_CHAIN && ctx->have_orders && !ctx->narrow_ok && floor_plan(ctx, algo, n_apps, ctx->h_apps.ptr, run.eff))
+        run.floored = true;
     Route route;
-    if (const int rc = route_of(ctx, mode, algo, &route); rc != GF_OK) {
+    if (const int rc = route_of(ctx, mode, algo, &route, run.floored); rc != GF_OK) {
         ctx->chain.valid = false;
         return rc;
     }
@@ -857,7 +964,6 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
         }
     }
     // ---- FIFO chains of the plain packers on the solo kernel: resume from the last chain's checkpoints where the queues agree
-    ChainRun run;
     const bool use_cache = chain_plan(ctx, route, algo, n_apps, ctx->h_apps.ptr, &run);
     const uint32_t a0 = run.a_begin;
     const uint64_t k0 = a0 > 0 ? ctx->h_apps.ptr[a0].exec_off : 0;  // placements of the skipped prefix
@@ -871,7 +977,7 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
     call.q.d_apps = ctx->d_apps.ptr;
     call.q.d_results = ctx->d_results.ptr;
     call.q.d_exec_nodes = ctx->d_exec.ptr;
-    call.run = use_cache ? &run : nullptr;
+    call.run = use_cache || run.floored ? &run : nullptr;  // (a floored chain needs its units even when nothing is cached)
     if (mapped && mode == GF_MODE_FIFO_CHAIN && da != nullptr) {
         call.host.apps = static_cast<const gf_app*>(da);
         call.host.results = static_cast<gf_result*>(dr);
@@ -922,6 +1028,10 @@ int gf_fit_batch(gf_ctx* ctx, gf_mode mode, gf_algo algo, uint32_t n_apps, const
         if (failed_at >= 0) failed_at += (int32_t)a0;
     }
     if (use_cache) chain_commit(ctx, algo, n_apps, total_k, failed_at, run);
+    if (call.run != nullptr && route.lds_chain() && run.narrow_proven) {  // gf_chain_units: an LDS chain kernel served for certain
+        for (int j = 0; j < 3; ++j) ctx->chain_unit_last[j] = run.eff[j];
+        ctx->chain_unit_last[3] = run.floored ? 1 : 0;
+    }
     std::memcpy(results + a0, ctx->h_results.ptr + a0, (size_t)(n_apps - a0) * sizeof(gf_result));
     if (total_k > k0) std::memcpy(exec_nodes + k0, ctx->h_exec.ptr + k0, (size_t)(total_k - k0) * sizeof(uint32_t));
     if (mode == GF_MODE_FIFO_CHAIN && chain_failed_at) *chain_failed_at = failed_at;

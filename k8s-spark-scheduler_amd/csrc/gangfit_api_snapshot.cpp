@@ -71,7 +71,12 @@ void install_layout(gf_ctx* ctx, LayoutFacts&& f) {
     for (int j = 0; j < 3; ++j) {
         ctx->unit[j] = f.unit[j];
         ctx->nmax[j] = f.nmax[j];
+        ctx->tmin[j] = f.tmin[j];
+        ctx->tmax[j] = f.tmax[j];
     }
+    ctx->range_known = f.range_known;
+    ctx->floor_epoch = 0;  // the floored snapshot of the old table, and what gf_chain_units reports
+    for (int64_t& u : ctx->chain_unit_last) u = 0;
     ctx->n_g = f.n_g;
     ctx->n_gpad = f.n_gpad;
     ctx->g_prefix = std::move(f.g_prefix);

@@ -311,6 +311,19 @@ struct gf_ctx {
     DeviceBuf<int32_t> d_nquad;  // 4 * n_slots: d_nsnap and d_slot_node as one record {cpu, mem, gpu, node} per slot (NodeTable::nquad);
                                  // written by whoever writes d_nsnap, in the same pass, and current exactly when d_nsnap is
     PinnedBuf<int32_t> h_ntable;  // staging: the columns | their chunk maxima | the records
+    // The FLOORED narrow form of a chain (gangfit_floor_units.h): units that divide the queue's requests, the table floored.
+    bool narrow_floor = true;   // option "narrow_floor" = 0: only the exact form, every batch takes the route it took without this one
+    bool range_known = false;   // tmin / tmax are those of the installed table (false behind a device build until a chain asks)
+    int64_t tmin[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, tmax[3] = {INT64_MIN, INT64_MIN, INT64_MIN};  // over the real slots
+    // the floored snapshot, built once per (snapshot epoch, units) by floor_snapshot_kernel — a warm Filter finds it: the columns
+    // (3 * n_slots, empty and sentinel slots kNarrowNever) | their chunk maxima (3 * n_chunks) | the remainders A - q * u
+    // (3 * n_slots int64: a unit of 2^32 and more is ordinary, so no int32 column holds them)
+    DeviceBuf<int32_t> d_fsnap, d_fcmax;
+    DeviceBuf<int64_t> d_frem;
+    DeviceBuf<int64_t> d_frange;  // 3 minima | 3 maxima of a device-built table on their way to the host
+    uint64_t floor_epoch = 0;     // snap_epoch the floored snapshot was built at (0: none) ...
+    int64_t floor_unit[3] = {0, 0, 0};  // ... and its units
+    int64_t chain_unit_last[4] = {0, 0, 0, 0};  // gf_chain_units: the last chain an LDS chain kernel served since the install
     bool fifo_generic = false;  // option "fifo_generic": chains run on the wide / generic global-memory kernels only
     bool force_general_layout = false;  // option "force_general_layout": gf_orders_set never merges the two orders
     uint32_t lds_budget = 0;   // bytes of LDS one workgroup may use
@@ -481,6 +494,8 @@ struct gf_ctx {
         uint64_t epoch = 0;
         int algo = -1;
         int64_t unit[3] = {0, 0, 0};  // narrow units the checkpoints are scaled in
+        bool floored = false;         // ... of the floored form: the checkpoints hold floor(value / unit), not value / unit
+        uint32_t exact_fails_at = 0;  // ... and the shortest prefix of the cached queue without an exact form (ChainRun::exact_fails_at)
         uint32_t shift = 5;
         uint32_t n_apps = 0;
         uint32_t n_ckpt = 0;          // checkpoints 1 .. n_ckpt hold the table before application i << shift

@@ -113,6 +113,20 @@ static_assert(sizeof(NApp) == 64, "NApp must be 64 bytes");
 hipError_t launch_narrow_rescale(const int32_t* d_src, int32_t* d_dst, uint32_t n_slots, const int32_t* d_cmax_src,
                                  int32_t* d_cmax_dst, uint32_t n_chunks, const int32_t factor[3], hipStream_t stream);
 
+// The floored narrow form (gangfit_floor_units.h): value = q * unit[dimension] + r, q = floor(value / unit), 0 <= r < unit.
+struct FloorUnitArgs {
+    int64_t unit[3];
+    double rcp[3];  // 1 / (double)unit
+};
+// d_fsnap (3 * n_slots) = q of the wide snapshot d_snap, empty and sentinel slots kNarrowNever; d_fcmax (3 * n_chunks) its chunk
+// maxima; d_frem (3 * n_slots) = r, 0 on empty and sentinel slots.  The caller has checked -2^30 < q < 2^30 for every real slot.
+hipError_t launch_floor_snapshot(const int64_t* d_snap, const uint32_t* d_slot_node, uint32_t n_slots, uint32_t n_chunks,
+                                 const int64_t unit[3], int32_t* d_fsnap, int32_t* d_fcmax, int64_t* d_frem, hipStream_t stream);
+// d_work (3 * n_slots, q' * unit as a chain's epilogue leaves it) += d_frem: the true residuals.
+hipError_t launch_floor_residual(int64_t* d_work, const int64_t* d_frem, uint32_t n_slots, hipStream_t stream);
+// d_out6 = the 3 minima | 3 maxima of d_snap's dimensions over the real slots (INT64_MAX | INT64_MIN without one).
+hipError_t launch_table_range(const int64_t* d_snap, const uint32_t* d_slot_node, uint32_t n_slots, int64_t* d_out6, hipStream_t stream);
+
 struct NarrowTable {  // value = scaled value * unit[dimension]
     int32_t* cpu;  // [n_slots] working copy, scaled
     int32_t* mem;
@@ -339,6 +353,7 @@ struct ChainTables {
     NarrowTable ntable;
     ZoneTable zones;
     const int64_t* d_sched;
+    const int64_t* d_frem = nullptr;  // ntable is the floored narrow form: its remainders, [3][n_slots] (nullptr: the exact form)
 };
 size_t fifo_v2_lds_bytes(uint32_t lds_slots, uint32_t n_chunks);
 size_t fifo_solo_lds_bytes(uint32_t lds_slots, uint32_t n_chunks);

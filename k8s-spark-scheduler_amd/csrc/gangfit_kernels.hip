@@ -2355,10 +2355,15 @@ hipError_t launch_fit_fifo_zoned_lds(bool az_aware, uint32_t lds_slots, uint32_t
         return with_value<true, false>(az_aware, [&](auto AZ) {
             return with_value<4, 8, 16>(wg_waves, [&](auto NWV) {
                 return with_value<true, false>(res, [&](auto RS) {
+                    if (tables.d_frem != nullptr)  // the floored narrow form: the averages take the remainders in
+                        return launch_one_workgroup(fit_fifo_zoned_lds_floor_kernel<AZ, NWV, RS>, NWV, lds, B.stream, table, tables.ntable,
+                                                    zones, tables.d_sched, lds_slots, B.n_apps, n_shapes, B.d_apps, (const NApp*)B.d_napps,
+                                                    (const int32_t*)B.d_wide_needed, B.d_results, B.d_exec_nodes, B.d_zexec, B.half,
+                                                    B.d_chain_failed_at, B.ckpt, B.d_stats, tables.d_frem);
                     return launch_one_workgroup(fit_fifo_zoned_lds_kernel<AZ, NWV, RS>, NWV, lds, B.stream, table, tables.ntable, zones,
                                                 tables.d_sched, lds_slots, B.n_apps, n_shapes, B.d_apps, (const NApp*)B.d_napps,
                                                 (const int32_t*)B.d_wide_needed, B.d_results, B.d_exec_nodes, B.d_zexec, B.half,
-                                                B.d_chain_failed_at, B.ckpt, B.d_stats);
+                                                B.d_chain_failed_at, B.ckpt, B.d_stats, (const int64_t*)nullptr);
                 });
             });
         });
@@ -2394,10 +2399,18 @@ hipError_t launch_fit_fifo_minfrag_lds(const MinfragLdsChain& chain, const Chain
         return with_value<true, false>(zoned, [&](auto ZO) {
             return with_value<true, false>(res, [&](auto RS) {
                 return with_value<8, (int)kMfNWmax>(eight ? 8 : (int)kMfNWmax, [&](auto NWV) {
+                    // the floored narrow form: the zones' averages take the remainders in (the plain packer compares none)
+                    if constexpr (decltype(ZO)::value)
+                        if (tables.d_frem != nullptr)
+                            return launch_one_workgroup(fit_fifo_minfrag_lds_floor_kernel<true, RS, NWV>, NWV, lds, B.stream, table, tables.ntable,
+                                                        zones, tables.d_sched, lds_slots, B.n_apps, n_shapes, n_idx, B.d_apps,
+                                                        (const NApp*)B.d_napps, (const int32_t*)B.d_wide_needed, B.d_results,
+                                                        B.d_exec_nodes, B.d_zexec, B.half, B.d_chain_failed_at, chain.d_capmat, d_hist, B.ckpt,
+                                                        B.d_stats, tables.d_frem);
                     return launch_one_workgroup(fit_fifo_minfrag_lds_kernel<ZO, RS, NWV>, NWV, lds, B.stream, table, tables.ntable, zones,
                                                 tables.d_sched, lds_slots, B.n_apps, n_shapes, n_idx, B.d_apps, (const NApp*)B.d_napps,
                                                 (const int32_t*)B.d_wide_needed, B.d_results, B.d_exec_nodes, B.d_zexec, B.half,
-                                                B.d_chain_failed_at, chain.d_capmat, d_hist, B.ckpt, B.d_stats);
+                                                B.d_chain_failed_at, chain.d_capmat, d_hist, B.ckpt, B.d_stats, (const int64_t*)nullptr);
                 });
             });
         });
@@ -2569,6 +2582,114 @@ hipError_t launch_narrow_rescale(const int32_t* d_src, int32_t* d_dst, uint32_t 
     const unsigned blocks = (unsigned)((n_all + 255) / 256 < 2048 ? (n_all + 255) / 256 : 2048);
     hipLaunchKernelGGL(narrow_rescale_kernel, dim3(blocks), dim3(256), 0, stream, d_src, d_dst, n_slots, d_cmax_src, d_cmax_dst,
                        n_chunks, factor[0], factor[1], factor[2]);
+    return hipGetLastError();
+}
+
+// The FLOORED narrow snapshot of a chain (gangfit_floor_units.h): for every real slot and dimension q = floor(A / u) toward minus
+// infinity and r = A - q * u in [0, u), with the chunk maxima of q; empty and sentinel slots keep kNarrowNever and r = 0.  One
+// wavefront per 64-slot chunk.  The host has checked -2^30 < floor(A / u) < 2^30 for every real slot, so the quotient is an
+// estimate and one exact fix-up, as in cap_dim_full (no 64-bit divider on this chip): (double)A * rcp, rcp = 1 / (double)u, is
+// within 2^-20 of A / u, its floor within one of q, and r = A - q * u — taken modulo 2^64: its true value lies in [-u, 2u),
+// u < 2^62 — says which way.
+__global__ __launch_bounds__(256) void floor_snapshot_kernel(const int64_t* __restrict__ snap, const uint32_t* __restrict__ slot_node,
+                                                             uint32_t n_slots, uint32_t n_chunks, FloorUnitArgs u,
+                                                             int32_t* __restrict__ fsnap, int32_t* __restrict__ fcmax,
+                                                             int64_t* __restrict__ frem) {
+    const uint32_t c = blockIdx.x * (blockDim.x / kWave) + (threadIdx.x >> 6);
+    if (c >= n_chunks) return;  // (wave-uniform)
+    const int lane = lane_id();
+    const uint32_t s = c * 64u + (uint32_t)lane;
+    const bool real = s + 1 < n_slots && slot_node[s] != GF_NO_NODE;
+    for (int j = 0; j < 3; ++j) {
+        int32_t q32 = INT32_MIN / 2;
+        int64_t r = 0;
+        if (real) {
+            const int64_t a = snap[(size_t)j * n_slots + s], unit = u.unit[j];
+            int64_t q = (int64_t)__builtin_floor((double)a * u.rcp[j]);
+            r = (int64_t)((uint64_t)a - (uint64_t)q * (uint64_t)unit);
+            if (r < 0) {
+                q -= 1;
+                r += unit;
+            } else if (r >= unit) {
+                q += 1;
+                r -= unit;
+            }
+            q32 = (int32_t)q;
+        }
+        if (s < n_slots) {
+            fsnap[(size_t)j * n_slots + s] = q32;
+            frem[(size_t)j * n_slots + s] = r;
+        }
+        const int32_t m = wave_max_i32(s < n_slots ? q32 : INT32_MIN);
+        if (lane == 0) fcmax[(size_t)j * n_chunks + c] = m;
+    }
+}
+
+hipError_t launch_floor_snapshot(const int64_t* d_snap, const uint32_t* d_slot_node, uint32_t n_slots, uint32_t n_chunks,
+                                 const int64_t unit[3], int32_t* d_fsnap, int32_t* d_fcmax, int64_t* d_frem, hipStream_t stream) {
+    if (n_chunks == 0) return hipSuccess;
+    FloorUnitArgs u;
+    for (int j = 0; j < 3; ++j) {
+        if (unit[j] <= 0) return hipErrorInvalidValue;
+        u.unit[j] = unit[j];
+        u.rcp[j] = 1.0 / (double)unit[j];
+    }
+    hipLaunchKernelGGL(floor_snapshot_kernel, dim3((n_chunks + 3u) / 4u), dim3(256), 0, stream, d_snap, d_slot_node, n_slots, n_chunks, u,
+                       d_fsnap, d_fcmax, d_frem);
+    return hipGetLastError();
+}
+
+// The residual table a chain on the floored form leaves behind: its epilogue wrote q' * u, the true value is q' * u + r.
+__global__ __launch_bounds__(256) void floor_residual_kernel(int64_t* __restrict__ work, const int64_t* __restrict__ frem, size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) work[i] += frem[i];
+}
+
+hipError_t launch_floor_residual(int64_t* d_work, const int64_t* d_frem, uint32_t n_slots, hipStream_t stream) {
+    const size_t n = 3 * (size_t)n_slots;
+    if (n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    hipLaunchKernelGGL(floor_residual_kernel, dim3(blocks), dim3(256), 0, stream, d_work, d_frem, n);
+    return hipGetLastError();
+}
+
+// The smallest and the largest value of each dimension over the real slots of a table that was built on the device (the host
+// keeps them for a table it built itself): out = 3 minima | 3 maxima, INT64_MAX | INT64_MIN without a real slot.  One workgroup.
+__global__ __launch_bounds__(1024) void table_range_kernel(const int64_t* __restrict__ snap, const uint32_t* __restrict__ slot_node,
+                                                           uint32_t n_slots, long long* __restrict__ out) {
+    __shared__ long long part[6][1024 / kWave];
+    const uint32_t wave = threadIdx.x >> 6;
+    const int lane = lane_id();
+    int64_t lo[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, hi[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
+    for (uint32_t s = threadIdx.x; s + 1 < n_slots; s += 1024u) {
+        if (slot_node[s] == GF_NO_NODE) continue;
+        for (int j = 0; j < 3; ++j) {
+            const int64_t a = snap[(size_t)j * n_slots + s];
+            lo[j] = a < lo[j] ? a : lo[j];
+            hi[j] = a > hi[j] ? a : hi[j];
+        }
+    }
+    for (int j = 0; j < 3; ++j) {
+        const int64_t l = wave_min_any_i64(lo[j]), h = wave_max_i64(hi[j]);
+        if (lane == 0) {
+            part[j][wave] = l;
+            part[3 + j][wave] = h;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        long long v = part[threadIdx.x][0];
+        for (uint32_t w = 1; w < 1024 / kWave; ++w) {
+            const long long o = part[threadIdx.x][w];
+            v = threadIdx.x < 3 ? (o < v ? o : v) : (o > v ? o : v);
+        }
+        out[threadIdx.x] = v;
+    }
+}
+
+hipError_t launch_table_range(const int64_t* d_snap, const uint32_t* d_slot_node, uint32_t n_slots, int64_t* d_out6, hipStream_t stream) {
+    hipLaunchKernelGGL(table_range_kernel, dim3(1), dim3(1024), 0, stream, d_snap, d_slot_node, n_slots,
+                       reinterpret_cast<long long*>(d_out6));
     return hipGetLastError();
 }
 

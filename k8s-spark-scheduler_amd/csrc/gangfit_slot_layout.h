@@ -39,6 +39,11 @@ struct LayoutFacts {
     bool zspan_ok = false;   // the zone spans were built (merged layout with at least one zone, host-built only)
     bool host_stale = false; // node_slot (and the snapshot's host mirrors) still sit on the device: node_slot below is unused
     std::vector<uint32_t> node_slot;
+    // the smallest and largest value of each dimension over the real slots (tmin > tmax: none), whatever narrow_ok says: what the
+    // floored narrow form of a chain is decided from (gangfit_floor_units.h).  range_known = false (a snapshot built on the device):
+    // fetched from the device when a chain first asks
+    bool range_known = false;
+    int64_t tmin[3] = {INT64_MAX, INT64_MAX, INT64_MAX}, tmax[3] = {INT64_MIN, INT64_MIN, INT64_MIN};
 };
 
 // Element counts of the staging regions fill_layout writes (0 = the table does not exist in this layout).
@@ -261,6 +266,22 @@ inline void fill_narrow(LayoutFacts& f, const int64_t* table, const uint32_t* sl
     }
 }
 
+// tmin / tmax of the facts: every real slot of every dimension (fill_narrow stops at the first value without a scaled form).
+inline void fill_range(LayoutFacts& f, const int64_t* table, const uint32_t* slot_node) {
+    for (int j = 0; j < 3; ++j) {
+        const int64_t* col = table + (size_t)j * f.n_slots;
+        int64_t lo = INT64_MAX, hi = INT64_MIN;
+        for (uint32_t s = 0; s + 1 < f.n_slots; ++s) {
+            if (slot_node[s] == GF_NO_NODE) continue;
+            lo = col[s] < lo ? col[s] : lo;
+            hi = col[s] > hi ? col[s] : hi;
+        }
+        f.tmin[j] = lo;
+        f.tmax[j] = hi;
+    }
+    f.range_known = true;
+}
+
 }  // namespace layout_detail
 
 // Step 1.  Positions of the known nodes in the two orders: unknown names (index >= n_nodes) never host anything (binpack.go:68,
@@ -404,6 +425,7 @@ inline void fill_layout(const LayoutInput& in, LayoutPlan& p, const LayoutTables
         fill_general(in, p, t);
     chunk_maxima(t.table, n_slots, f.n_chunks, t.cmax);  // chunk-maxima index over all slots (see NodeTable::cmax)
     fill_narrow(f, t.table, slot_node, t.ntable, t.nquad);
+    fill_range(f, t.table, slot_node);
     if (p.sizes.sched)  // SchedulableResources in slot order (efficiencies); empty slots read 0
         for (int j = 0; j < 3; ++j)
             for (uint32_t s = 0; s < n_slots; ++s)

@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = [
     "gf_shard_mf_finish_dev",
     "gf_find_nodes", "gf_ctx_lock", "gf_ctx_unlock", "gf_launch_floor",
     "gf_graph_begin", "gf_graph_end", "gf_graph_launch", "gf_graph_destroy", "gf_cluster_set", "gf_snapshot_build_resident",
-    "gf_usage_reset", "gf_usage_apply", "gf_overhead_update", "gf_set_option", "gf_chain_cache_stats", "gf_generation", "gf_shard_count", "gf_ctx_view",
+    "gf_usage_reset", "gf_usage_apply", "gf_overhead_update", "gf_set_option", "gf_chain_cache_stats", "gf_chain_units", "gf_generation", "gf_shard_count", "gf_ctx_view",
     "gf_worker_fit", "gf_worker_submit_dev", "gf_worker_wait", "gf_worker_stop", "gf_worker_stats", "gf_worker_geometry", "gf_worker_row_stats", "gf_worker_kernel_time", "gf_call_phases",
     "gf_cluster_fit_feasible", "gf_cluster_fit_feasible_sets", "gf_snapshot_build_info", "gf_cluster_executor_fit",
     "gf_snapshot_build_resident_set", "gf_snapshot_set_info", "gf_filter_efficiency", "gf_cluster_find_nodes", "gf_cluster_update",
@@ -250,6 +250,8 @@ def load() -> C.CDLL:
     L.gf_generation.argtypes = [p, p]
     L.gf_chain_cache_stats.restype = i32
     L.gf_chain_cache_stats.argtypes = [p, i32, p]
+    L.gf_chain_units.restype = i32
+    L.gf_chain_units.argtypes = [p, p]
     L.gf_snapshot_build_info.restype = i32
     L.gf_snapshot_build_info.argtypes = [p, p]
     L.gf_snapshot_build_resident_set.restype = i32

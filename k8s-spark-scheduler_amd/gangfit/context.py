@@ -123,6 +123,13 @@ class Context:
         self._check(self._lib.gf_chain_cache_stats(self._h, 1 if reset else 0, N.ptr(out)))
         return tuple(int(v) for v in out)
 
+    def chain_units(self):
+        """gf_chain_units: (cpu unit, memory unit, gpu unit, floored) of the last FIFO chain an LDS chain kernel served since the
+        install or set_option — all 0 when there was none; floored = 1: the units divide the queue's requests and the table was floored."""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self._lib.gf_chain_units(self._h, N.ptr(out)))
+        return tuple(int(v) for v in out)
+
     # -- lifecycle
     def close(self):
         if getattr(self, "_h", None):
